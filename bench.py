@@ -11,12 +11,17 @@ SINA default options.  One "step" = one batch of --batch queries through
 famfinder (k-mer search + family selection) and aligner (family DAG, mesh DP,
 backtrack, NAST fix-up).  Queries, references and index are resident before the
 timed region; every rank runs its own K steps on its own queries (weak scaling,
-no per-step collective; one RCCL broadcast of the index at start-up).
+no per-step collective; one RCCL broadcast of the index at start-up).  The steps
+draw their queries from a fixed pool of --distinct-steps batches (step s aligns
+batch s mod pool), so that set-up does not grow with K.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--refs R]
+    python bench.py --full ...            # + CPU baseline, oracle check, isolated kernels, confined leg
+    python bench.py --dump-outputs DIR    # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints the line; everything
+else it can measure or check runs only with --full.  Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -56,10 +61,25 @@ def parse():
                          "in 23.4 / 42.3 / 61.6 / 80.4 ms = 595 / 660 / 680 / 694 Gcell/s -- so longer launches are "
                          "faster per query; the trace-back planes (66 GB each at 9216 16S queries) come from the "
                          "device's pool of two, csrc/ctx.h)")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="CPU baseline: queries per thread and thread count (0 = 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline figure: the CPU "
+                         "baseline, the oracle re-check of timed queries (--verify), one untimed step with a single batch "
+                         "in flight for the kernels' own times (roofline.isolated, roofline_other, "
+                         "kernels_ms_per_step_isolated) and the confined leg (--confined-cpus).  Off: none of them runs "
+                         "and their fields are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; rank 0's step when several "
+                         "ranks run): per query status / head / tail / qual / number of aligned bases / CRC-32 of the "
+                         "aligned bases / family ids and scores, and the aligned columns and base masks of a fixed "
+                         "sample of queries.  Same arguments, same inputs: two builds compare output for output")
+    ap.add_argument("--distinct-steps", type=int, default=32,
+                    help="batches of distinct queries in the pool the steps cycle through (at least one launch's worth: "
+                         "no launch sees a query twice; the pipeline keeps nothing from one launch to the next).  Each "
+                         "batch has a seed of its own and the batches are generated in parallel")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="CPU baseline (--full): queries per thread and thread count (0 = 4)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--verify", type=int, default=64,
-                    help="queries of the timed run re-done by the oracle afterwards and compared (0 = none; "
+                    help="--full: queries of the timed run re-done by the oracle afterwards and compared (0 = none; "
                          "skipped together with the CPU baseline, whose oracle index it shares)")
     ap.add_argument("--dup-rate", type=float, default=0.0,
                     help="fraction of every step's queries that repeat another query of the same step (amplicon-like "
@@ -69,7 +89,7 @@ def parse():
                     help="queries at 0.5 / 3 / 10 / 20 %% substitutions (indels in proportion), interleaved: every launch "
                          "mixes near-identical and distant queries (default: 3 %% throughout, the headline workload)")
     ap.add_argument("--confined-cpus", type=int, default=2,
-                    help="N = 1 only: after the timed region the same number of steps runs once more with every thread of "
+                    help="N = 1 and --full only: after the timed region the same number of steps runs once more with every thread of "
                          "the process confined to this many CPUs (an 8-rank node inside a 16-CPU quota leaves a rank two) "
                          "and --confined-threads loop-pool threads; the line reports confined_rate_frac = that rate / "
                          "the timed region's.  0 = skip")
@@ -79,7 +99,10 @@ def parse():
                     help="threads of the host-side loop pool (0 = default: 6 for a single rank -- measured on one MI355X: "
                          "3 threads 140.1 k seq/s at 1.56 busy cores, 4: 141.8 k / 1.67, 6: 143.1 k / 1.69, 12: 143.9 k / "
                          "1.97, profiles/r04_host_threads.txt; with several ranks inside one CPU quota: 1.5 x the rank's share)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0 or a.distinct_steps < 1:
+        ap.error("--steps and --distinct-steps must be at least 1, --warmup at least 0")
+    return a
 
 
 def kernel_source_rev():
@@ -187,10 +210,11 @@ def cpu_baseline(world, refs, qs, per_thread):
 def verify_against_oracle(world, qs, picked):
     """Untimed: re-does the picked queries of the timed run with the oracle (k-mer search + family
     selection + DAG + DP + backtrack + NAST at the full reference count) and compares family, aligned
-    columns and case bits, head / tail / quality.  Returns (checked, identical, first differences)."""
+    columns and case bits, head / tail / quality.  picked: (query of qs, its result) pairs.  Returns (checked,
+    identical, first differences)."""
     po = world.po
     diffs = []
-    for q, got in sorted(picked.items()):
+    for q, got in picked:
         c = world.query(qs, q)
         ids, sc, fflog = world.idx.famfinder(c, po.ff_opts())
         if len(ids) == 0:
@@ -209,6 +233,109 @@ def verify_against_oracle(world, qs, picked):
         if not ok:
             diffs.append("query %d: %s" % (q, what))
     return len(picked), len(picked) - len(diffs), diffs[:4]
+
+
+def cycled(qs, first, n):
+    """Queries first .. first + n - 1 of the endless repetition of qs, as Pipeline.run takes them: (masks, offsets).
+    Copies whole runs of the pool, never one query at a time."""
+    masks, offs, base = [], [], 0
+    q, left = first % qs.n, n
+    while left:
+        take = min(left, qs.n - q)
+        lo, hi = int(qs.off[q]), int(qs.off[q + take])
+        masks.append(qs.mask[lo:hi])
+        offs.append(qs.off[q:q + take] - lo + base)
+        base += hi - lo
+        q, left = 0, left - take
+    offs.append(np.array([base], dtype=np.int64))
+    return np.concatenate(masks), np.concatenate(offs).astype(np.uint64)
+
+
+def query_pool(refs, n_batches, batch, seed, **kw):
+    """n_batches batches of `batch` synthetic queries, batch b drawn with seed (seed, b): the same pool whatever
+    the number of threads that generate it (at most 8, within this process's CPUs)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from sina_amd import synth
+    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    with ThreadPoolExecutor(max(1, min(8, cpus))) as ex:
+        parts = list(ex.map(lambda b: synth.make_queries(refs, batch, seed=(seed, b), **kw), range(n_batches)))
+    off = [np.zeros(1, np.int64)]
+    for p in parts:
+        off.append(p.off[1:] + off[-1][-1])
+    return synth.QuerySet(mask=np.concatenate([p.mask for p in parts]), off=np.concatenate(off),
+                          src=np.concatenate([p.src for p in parts]))
+
+
+def count_aligned(pl, n):
+    """How many of queries 0 .. n-1 of the pipeline's last run came out aligned (status 0: by DP, 1: copied), read
+    through the C ABI's status accessor alone -- Pipeline.result() also renders every query's log and family."""
+    import ctypes as C
+    st, hd, tl, ql, w, nb = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_uint32(), C.c_uint32()
+    res, h = pl.H.sina_host_result, pl.h
+    args = (C.byref(st), C.byref(hd), C.byref(tl), C.byref(ql), C.byref(w), C.byref(nb))
+    count = 0
+    for q in range(n):
+        if res(h, q, *args) == 0 and st.value in (0, 1):
+            count += 1
+    return count
+
+
+DUMP_MAX_QUERIES = 16384     # per-query arrays: the whole step up to this many queries, else a fixed sample of them
+DUMP_ALIGNMENTS = 256        # queries whose aligned columns and base masks are written in full
+
+
+def dump_outputs(path, result, first, n):
+    """--dump-outputs: what the timed path computed for queries first .. first + n - 1 of its last run (the last
+    timed step), as float64 arrays in path/<name>.npy -- every value is an integer or a two-decimal score, exact
+    in float64.  A fixed, seeded sample where the step is larger than DUMP_MAX_QUERIES; the full aligned bases of
+    DUMP_ALIGNMENTS of the queries, and a CRC-32 of every query's aligned bases (column | mask << 24, uint32).
+    `result(q)` is Pipeline.result.  Returns the bytes written."""
+    import zlib
+    picked = np.arange(n, dtype=np.int64)
+    if n > DUMP_MAX_QUERIES:
+        picked = np.sort(np.random.default_rng(20250101).choice(n, size=DUMP_MAX_QUERIES, replace=False))
+    full = set(np.random.default_rng(20250102).choice(len(picked), size=min(DUMP_ALIGNMENTS, len(picked)),
+                                                      replace=False).tolist())
+    scalars = {k: np.zeros(len(picked)) for k in ("status", "head", "tail", "qual", "n_bases", "bases_crc32")}
+    fam_ids, fam_scores, cols, masks, sample, sample_off = [], [], [], [], [], [0]
+    for i, q in enumerate(picked):
+        r = result(first + int(q))
+        ab = np.ascontiguousarray(r["packed"], dtype=np.uint32)
+        for k in ("status", "head", "tail", "qual"):
+            scalars[k][i] = r[k]
+        scalars["n_bases"][i] = len(ab)
+        scalars["bases_crc32"][i] = zlib.crc32(ab.tobytes())
+        ids, scores = [], []
+        for item in r["family"].split():   # "<name>.<start>:<score>", name = ref<id> (the bench's store)
+            name, score = item.rsplit(":", 1)
+            ids.append(int(name.split(".")[0][3:]))
+            scores.append(float(score))
+        fam_ids.append(ids)
+        fam_scores.append(scores)
+        if i in full:
+            sample.append(q)
+            cols.append(ab & 0xFFFFFF)
+            masks.append(ab >> 24)
+            sample_off.append(sample_off[-1] + len(ab))
+    width = max([1] + [len(x) for x in fam_ids])
+    out = dict(scalars)
+    out["query"] = picked.astype(np.float64)          # (index inside the step)
+    out["family_ids"] = np.full((len(picked), width), -1.0)
+    out["family_scores"] = np.full((len(picked), width), -1.0)
+    for i, (ids, scores) in enumerate(zip(fam_ids, fam_scores)):
+        out["family_ids"][i, :len(ids)] = ids
+        out["family_scores"][i, :len(scores)] = scores
+    out["sample_query"] = np.array(sample, dtype=np.float64)
+    out["sample_offsets"] = np.array(sample_off, dtype=np.float64)
+    out["sample_columns"] = np.concatenate(cols).astype(np.float64) if cols else np.zeros(0)
+    out["sample_masks"] = np.concatenate(masks).astype(np.float64) if masks else np.zeros(0)
+    total = sum(v.nbytes for v in out.values())
+    if total > 64 << 20:
+        raise RuntimeError("--dump-outputs: %d bytes, more than the 64 MB allowed" % total)
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return total
 
 
 def self_launch(a):
@@ -269,17 +396,18 @@ def main():
     full_mask = os.sched_getaffinity(0) if hasattr(os, "sched_getaffinity") else None
     pinned = affinity.pin_rank(local_rank, int(os.environ.get("LOCAL_WORLD_SIZE", world)))
 
-    # ---- synthetic inputs (identical on every rank; queries differ per rank)
+    # ---- synthetic inputs (references identical on every rank; queries differ per rank).  The queries: a pool of
+    # --distinct-steps batches (at least one launch's worth) that the set-up pass, the warm-up, the timed steps and
+    # --full's isolated step cycle through -- step s aligns batch s mod pool
     refs = synth.make_refs(a.refs, length=a.length, width=a.width, seed=2)
-    # + one untimed step for the isolated kernel timings + the set-up pass (launches of the timed size)
     prime_n = a.sub_batch * 2 * max(1, a.inflight)
-    n_q = a.batch * (a.steps + a.warmup + 1) + prime_n
+    n_pool = max(a.distinct_steps, -(-a.sub_batch // a.batch))
     window = (1.0 / 3.0, a.window) if a.window else None
     mix = dict(sub=[0.005, 0.03, 0.10, 0.20], dele=[0.001, 0.005, 0.015, 0.03], ins=[0.001, 0.003, 0.01, 0.02]) if a.divergence_mix else {}
     if a.exact_rate > 0 and not mix:  # (query i of every hundred: exact if i < 100 x the rate)
         k = int(round(100 * min(1.0, a.exact_rate)))
         mix = dict(sub=[0.0] * k + [0.03] * (100 - k), dele=[0.0] * k + [0.005] * (100 - k), ins=[0.0] * k + [0.003] * (100 - k))
-    qs = synth.make_queries(refs, n_q, seed=3 + 1000 * rank, window=window, **mix)
+    qs = query_pool(refs, n_pool, a.batch, 3 + 1000 * rank, window=window, **mix)
     if a.dup_rate > 0:
         qs = synth.with_repeats(qs, a.dup_rate, a.batch, seed=17 + rank)
 
@@ -306,21 +434,20 @@ def main():
         host_threads = int(max(4, min(12, round(1.5 * share))))
     pl = pipeline.Pipeline(store, aligner=al_opts, host_threads=host_threads)
 
-    def run_steps(first, count):
-        lo, hi = qs.off[first * a.batch], qs.off[(first + count) * a.batch]
-        off = (qs.off[first * a.batch:(first + count) * a.batch + 1] - lo).astype(np.uint64)
-        return pl.run(qs.mask[lo:hi], off, batch=a.sub_batch, inflight=a.inflight)
+    def run_steps(first, count, inflight=None, inputs=None):
+        m, off = inputs if inputs is not None else cycled(qs, first * a.batch, count * a.batch)
+        return pl.run(m, off, batch=a.sub_batch, inflight=inflight or a.inflight)
 
     # Set-up, like the index build: one pass that lets every context of the pipeline allocate its
     # scratch (a 48 GB trace-back plane takes 1.4 s to allocate; with few warm-up steps not every
-    # aligner context would have seen a batch before the timed region).  Its own queries; launches of
-    # the timed size, two per aligner context.
-    q_p = a.batch * (a.steps + a.warmup + 1)  # its own queries, behind those of the steps
-    lo_p, hi_p = qs.off[q_p], qs.off[q_p + prime_n]
-    off_p = (qs.off[q_p:q_p + prime_n + 1] - lo_p).astype(np.uint64)
-    pl.run(qs.mask[lo_p:hi_p], off_p, batch=a.sub_batch, inflight=a.inflight)
+    # aligner context would have seen a batch before the timed region).  Launches of the timed size,
+    # two per aligner context.
+    m_p, off_p = cycled(qs, 0, prime_n)
+    pl.run(m_p, off_p, batch=a.sub_batch, inflight=a.inflight)
+    del m_p, off_p
     if a.warmup:
         run_steps(0, a.warmup)
+    timed_inputs = cycled(qs, a.warmup * a.batch, a.steps * a.batch)  # (resident before the timed region)
     pl.profile(reset=True)
     s0 = store.stats()
     if dist is not None:
@@ -345,7 +472,7 @@ def main():
     if os.environ.get("SINA_HOST_TRACE"):
         pipeline.load_host().sina_host_profile_mark(0)
     t0 = time.time()
-    timing = run_steps(a.warmup, a.steps)
+    timing = run_steps(a.warmup, a.steps, inputs=timed_inputs)
     torch.cuda.synchronize(device)
     if dist is not None:
         dist.barrier()
@@ -372,27 +499,29 @@ def main():
     s1 = store.stats()
 
     n_done = a.batch * a.steps
-    n_aligned = sum(1 for q in range(n_done) if pl.result(q)["status"] in (0, 1))
-    picked = {}
-    if a.verify and not a.no_cpu_baseline and rank == 0 and world == 1:
+    n_aligned = count_aligned(pl, n_done)
+    if a.dump_outputs and rank == 0:  # (results are indexed from the first query of the timed call)
+        dump_outputs(a.dump_outputs, pl.result, (a.steps - 1) * a.batch, a.batch)
+    picked = []
+    if a.full and a.verify and not a.no_cpu_baseline and rank == 0 and world == 1:
         rng = np.random.default_rng(12345)
-        first = a.warmup * a.batch  # (results are indexed from the first query of the timed call)
-        for q in rng.choice(n_done, size=min(a.verify, n_done), replace=False):
-            picked[first + int(q)] = pl.result(int(q))
+        first = a.warmup * a.batch  # (the timed call's first query, in the pool's numbering)
+        for q in sorted(rng.choice(n_done, size=min(a.verify, n_done), replace=False)):
+            picked.append(((first + int(q)) % qs.n, pl.result(int(q))))
 
-    # One more step, untimed and with ONE batch in flight: kernels run alone on the GPU, so their
+    # --full: one more step, untimed and with ONE batch in flight: kernels run alone on the GPU, so their
     # HIP-event durations are the kernels' own (in the timed region batches overlap on separate
     # streams and every kernel's duration includes the time it shares the CUs with the others).
-    lo, hi = qs.off[(a.warmup + a.steps) * a.batch], qs.off[(a.warmup + a.steps + 1) * a.batch]
-    off = (qs.off[(a.warmup + a.steps) * a.batch:(a.warmup + a.steps + 1) * a.batch + 1] - lo).astype(np.uint64)
-    pl.run(qs.mask[lo:hi], off, batch=a.sub_batch, inflight=1)
-    s2 = store.stats()
-    iso = {k: s2[k] - s1[k] for k in s1}
+    iso = None
+    if a.full:
+        run_steps(a.warmup + a.steps, 1, inflight=1)
+        s2 = store.stats()
+        iso = {k: s2[k] - s1[k] for k in s1}
 
-    # ---- the host budget of an 8-rank node, proven on this one GPU: the same steps once more with the whole
+    # ---- --full: the host budget of an 8-rank node, proven on this one GPU: the same steps once more with the whole
     # process (loop pool, stage driver threads, the HIP runtime's helpers) on --confined-cpus CPUs
     confined = None
-    if world == 1 and a.confined_cpus > 0 and hasattr(os, "sched_setaffinity"):
+    if a.full and world == 1 and a.confined_cpus > 0 and hasattr(os, "sched_setaffinity"):
         def all_tasks():
             return [int(t) for t in os.listdir("/proc/self/task")]
         allowed = sorted(os.sched_getaffinity(0))
@@ -409,11 +538,11 @@ def main():
             run_steps(a.warmup, min(2, a.steps))  # (the pool's new threads, the caches on the new CPUs)
             ru_a = resource.getrusage(resource.RUSAGE_SELF)
             t_c = time.time()
-            run_steps(a.warmup, a.steps)
+            run_steps(a.warmup, a.steps, inputs=timed_inputs)
             torch.cuda.synchronize(device)
             dt_c = time.time() - t_c
             ru_b = resource.getrusage(resource.RUSAGE_SELF)
-            n_c = sum(1 for q in range(n_done) if pl.result(q)["status"] in (0, 1))
+            n_c = count_aligned(pl, n_done)
             confined = {"cpus": len(cpus), "pool_threads": a.confined_threads, "sequences_per_s": n_c / dt_c,
                         "host_cores_busy": ((ru_b.ru_utime - ru_a.ru_utime) + (ru_b.ru_stime - ru_a.ru_stime)) / dt_c,
                         "rate_frac": (n_c / dt_c) / (n_aligned / elapsed)}
@@ -520,6 +649,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": bool(a.full),
             "config": {
                 "workload": "%s (~%d bp%s) vs %d-seq SILVA-NR-like aligned reference, "
                             "width %d, SINA defaults (k=10 fast, family 40, match 2/mismatch -1/gap 5/ext 2)"
@@ -530,6 +660,7 @@ def main():
                                a.length, (", cut to %d" % a.window) if a.window else "", a.refs, a.width),
                 "refs": a.refs, "length": a.length, "width": a.width, "window": a.window, "dup_rate": a.dup_rate, "exact_rate": a.exact_rate, "divergence_mix": bool(a.divergence_mix),
                 "queries_per_step_per_gpu": a.batch,
+                "distinct_queries_per_gpu": qs.n,  # (the pool the steps cycle through)
                 "queries_per_launch": a.sub_batch,
                 "inflight_batches": a.inflight,
                 "family_dag": "host" if a.host_graph else "device",
@@ -583,8 +714,8 @@ def main():
                         "count that shared time once (time with a DP kernel resident / launches), "
                         "ms_per_launch_start_to_end / frac_by_start_to_end count it in both launches (what a kernel "
                         "trace's average duration gives; tools/kt_union.py on the committed trace gives both); "
-                        "`isolated` = one extra untimed step with a single batch in flight, nothing overlapping",
-                "isolated": {
+                        "`isolated` = one extra untimed step with a single batch in flight, nothing overlapping (--full only)",
+                "isolated": None if iso is None else {
                     "achieved": DP_BYTES_PER_CELL * iso["dp_cells_swept"] / (iso["dp_ms"] * 1e-3) / 1e9,
                     "frac": DP_BYTES_PER_CELL * iso["dp_cells_swept"] / (iso["dp_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
                     "ms_per_launch": iso["dp_ms"] / max(1, iso["dp_launches"]),
@@ -616,7 +747,7 @@ def main():
             # deliver, never above 1.  SURVEY 8d's algorithmic bytes are reported beside it: the k-mer count moves LESS than
             # those (dense lists are read as bitmaps, the score rows never leave LDS), the DAG build more (2.3 x).  Both are
             # bound by instruction issue, not bytes.
-            "roofline_other": {
+            "roofline_other": None if iso is None else {
                 name: (lambda tr, alg, ms_alone, ms_pipe, launches, note: None if launches <= 0 else {
                     "bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
                     "measured_bytes_per_launch": tr["hbm_bytes"] if tr else None,
@@ -648,7 +779,7 @@ def main():
                      "one lane per query walking its trace-back cells (a dependent 2-byte read per step; 74 MB of path cells per "
                      "launch are useful, a 64-byte sector holds 32 columns of ONE row): latency-bound, runs beside the next launch"))
             },
-            "kernels_ms_per_step_isolated": {
+            "kernels_ms_per_step_isolated": None if iso is None else {
                 "kmer_count_kernel": iso["kmer_count_ms"],
                 "kmer_select_kernel": iso["kmer_select_ms"],
                 "graph_kernel": iso["graph_ms"],
@@ -688,7 +819,7 @@ def main():
                 out["per_rank"]["warning"] = ("the ranks keep %.1f host cores busy and the container's CPU quota is %.1f: "
                                               "the job is host-bound, not GPU-bound" % (need, quota))
                 print("warning: " + out["per_rank"]["warning"], file=sys.stderr)
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             if pinned and full_mask:
                 os.sched_setaffinity(0, full_mask)  # the CPU baseline gets the whole machine
             ow = OracleWorld(refs)

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -17,7 +18,7 @@ def test_bench_line_and_rank_confined_to_two_cpus():
     --threads) -- keeps most of the unconfined rate.  (One MI355X, full-size steps, round 6: 0.86-0.93 at two CPUs at
     5 us of host CPU per query; the floor asserted here leaves a shared test box some room.)"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "16", "--warmup", "2", "--no-cpu-baseline",
-           "--refs", "20000", "--batch", "3072", "--sub-batch", "3072", "--inflight", "4"]
+           "--refs", "20000", "--batch", "3072", "--sub-batch", "3072", "--inflight", "4", "--full"]
 
     def line():
         p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
@@ -55,13 +56,47 @@ def test_bench_workload_flags(flags):
     """The bench's other workloads -- exact relatives (the aligner's copy short-cut), mixed divergence, repeated
     queries -- at a small size: the line comes out, every query is aligned, the verify leg finds nothing."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--refs", "20000", "--batch", "2048",
-           "--sub-batch", "2048", "--inflight", "2", "--confined-cpus", "0", "--cpu-sample", "1", "--verify", "16"] + flags
+           "--sub-batch", "2048", "--inflight", "2", "--confined-cpus", "0", "--cpu-sample", "1", "--verify", "16", "--full"] + flags
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert j["value"] > 10000 and j["verify"]["checked"] > 0 and j["verify"]["identical"] == j["verify"]["checked"], j["verify"]
     if flags[0] == "--exact-rate":
         assert j["config"]["exact_rate"] == 0.3
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full) times the steps and prints the line with nothing else measured: no CPU baseline, no
+    oracle check, no isolated step, no confined leg.  --dump-outputs writes the last timed step's results as float64
+    arrays within 64 MB, and a second run with the same arguments writes the same arrays (same inputs, same results)."""
+    def run(out):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--refs", "20000",
+               "--batch", "2048", "--sub-batch", "2048", "--inflight", "2", "--distinct-steps", "3",
+               "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        return json.loads(lines[0])
+
+    j = run(tmp_path / "a")
+    assert j["steps"] == 5 and j["warmup"] == 1 and j["full"] is False and j["config"]["distinct_queries_per_gpu"] == 3 * 2048
+    assert j["value"] > 10000 and abs(j["value"] * j["ms_per_step"] * 1e-3 / 2048 - 1.0) < 0.02
+    assert "cpu_baseline" not in j and "verify" not in j and j["confined"] is None and j["confined_rate_frac"] is None
+    assert j["kernels_ms_per_step_isolated"] is None and j["roofline_other"] is None and j["roofline"]["isolated"] is None
+    assert 0.0 < j["roofline"]["frac"] < 1.0
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert "status.npy" in files and "bases_crc32.npy" in files and "sample_columns.npy" in files
+    arrays = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    aligned = arrays["status.npy"] <= 1
+    assert len(aligned) == 2048 and aligned.mean() > 0.98
+    assert (arrays["n_bases.npy"][aligned] > 0).all() and (arrays["family_ids.npy"][aligned, 0] >= 0).all()
+    assert len(arrays["sample_offsets.npy"]) == len(arrays["sample_query.npy"]) + 1 > 1
+    run(tmp_path / "b")
+    for f in files:
+        assert np.array_equal(arrays[f], np.load(tmp_path / "b" / f)), f
 
 
 _CHILD = r"""
