@@ -358,14 +358,11 @@ int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint3
     // stretches that launch by 10 (profiles/r04_bt_delay.txt).  With chained launches the walk and the assembly
     // are queued right behind their DP kernel on the same FIFO stream: they start the moment it ends, run beside
     // the launch that started in its drain (the other FIFO stream), and the launch after that -- often the next DP
-    // launch -- is ordered behind them by the stream itself.  SINA_HIP_BT_ON_FIFO=0: the context's stream.
-    static const bool bt_fifo_wanted = !(experiment_env("SINA_HIP_BT_ON_FIFO") && experiment_env("SINA_HIP_BT_ON_FIFO")[0] == '0');
+    // launch -- is ordered behind them by the stream itself.  A launch that is not chained walks on stream_dp.
     bool bt_done = false;
     {
-        // the DP kernel: on the store's heavy stream, behind the uploads queued on c->stream; the
-        // backtrack walk and the result copies then follow it on the context's low-priority stream
-        std::unique_lock<std::mutex> token(c->st->dp_token, std::defer_lock);
-        if (!serialize_kernels()) token.lock();  // (then: one DP kernel at a time by this token)
+        // the DP kernel: on the store's heavy stream, behind the uploads queued on c->stream; the result copies
+        // then follow it on the context's stream_dp
         SH_CHECK(hipEventRecord(c->ev[8], s));
         s = c->stream_dp;
         SH_CHECK(hipStreamWaitEvent(s, c->ev[8], 0));
@@ -379,23 +376,17 @@ int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint3
             SH_CHECK(hipEventRecord(c->st->dp_end[dp_no % 8], hl.stream()));
             c->st->dp_end_no[dp_no % 8].store(dp_no, std::memory_order_release);
         }
-        if (hl.chained && bt_fifo_wanted) {
+        if (hl.chained) {
             if (launch_backtrack(b, hl.stream())) return 1;
             if (p->assemble && launch_assemble(b, hl.stream())) return 1;
             SH_CHECK(hipEventRecord(c->ev[2], hl.stream()));
             bt_done = true;
         }
         if (hl.done()) return 1;
-        if (experiment_env("SINA_HIP_DEBUG_SYNC")) fprintf(stderr, "[sina_hip] DP kernel done: %u queries, geometry %dx%d, weighted %d forbid %d\n", bq, pl.geom.T, pl.geom.B, (int)weighted, (int)forbid);
-        if (token.owns_lock()) SH_CHECK(wait_event(c->ev[1]));
     }
     if (!bt_done) {
         if (launch_backtrack(b, s)) return 1;
         if (p->assemble && launch_assemble(b, s)) return 1;
-        if (experiment_env("SINA_HIP_DEBUG_SYNC")) {
-            SH_CHECK(hipStreamSynchronize(s));
-            fprintf(stderr, "[sina_hip] backtrack kernel done\n");
-        }
         SH_CHECK(hipEventRecord(c->ev[2], s));
     }
     // (h_out_pos was sized for the whole call by the entry point; this range's columns go to their place in it)
@@ -482,25 +473,17 @@ int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint3
     return 0;
 }
 
-// The two streams of a context: uploads, k-mer searches' copies ... on `stream`; DP hand-over, result copies (and, with
-// SINA_HIP_CHAIN=0 / SINA_HIP_BT_ON_FIFO=0, the backtrack walk) on `stream_dp`.  Both at the DEFAULT priority since round 4.
+// The two streams of a context: uploads, k-mer searches' copies ... on `stream`; DP hand-over, result copies (and, for a
+// launch that is not chained, the backtrack walk) on `stream_dp`.  Both at the DEFAULT priority since round 4.
 // Rounds 1-3 created `stream` at the highest and `stream_dp` at the lowest priority (round 1: kernels of different
 // batches overlapped freely and a DAG build starved beside a DP kernel).  Since the device-filling kernels go through
 // the store's FIFO that no longer decides anything -- except that a lowest-priority walk is not dispatched while a
 // default-priority kernel still has workgroups to hand out: with one more stream in the process the walk started
 // 5 ms late in half of the launches, ran beside the next DP launch and took 16 ms instead of 7
-// (profiles/r04_bt_delay.txt).  SINA_HIP_STREAM_PRIO=1 restores the priorities.
+// (profiles/r04_bt_delay.txt).
 int make_streams(sina_hip_ctx *c) {
-    static const bool prio = experiment_env("SINA_HIP_STREAM_PRIO") && experiment_env("SINA_HIP_STREAM_PRIO")[0] == '1';
-    if (!prio) {
-        SH_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        SH_CHECK(hipStreamCreateWithFlags(&c->stream_dp, hipStreamNonBlocking));
-        return 0;
-    }
-    int least = 0, greatest = 0;
-    SH_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    SH_CHECK(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, greatest));
-    SH_CHECK(hipStreamCreateWithPriority(&c->stream_dp, hipStreamNonBlocking, least));
+    SH_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    SH_CHECK(hipStreamCreateWithFlags(&c->stream_dp, hipStreamNonBlocking));
     return 0;
 }
 

@@ -27,17 +27,6 @@ void set_error(const std::string &msg);
 //   SINA_HIP_NO_RUNTIME_DEFAULTS         the load-time constructor leaves the process environment alone (api.hip)
 //   SINA_HIP_TRACE_ALLOC                 one line per device / pinned allocation
 //   SINA_HIP_TEST="key=value;..."        test hooks (tests/ only): geom=T,B  generic=1  dense_div=N  lds_kb=N  rho=X  kmer_rows=1  bt_lanes=0/1  scout=0  scout_add=X  scout_set=X
-// The experiment switches of rounds 1-4 (SINA_HIP_SERIALIZE, _DP_BURST, _GRAPH_DRY, _BT_ON_FIFO, _STREAM_PRIO,
-// _SHARE_DAGS, _DP_ROUNDS, _DEBUG_SYNC) exist only in a build made with -DSINA_EXPERIMENTS
-// (make -C sina_amd/csrc VARIANT=exp EXTRA=-DSINA_EXPERIMENTS): the production library does not look at them.
-inline const char *experiment_env(const char *name) {
-#ifdef SINA_EXPERIMENTS
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
 // value of `key` in SINA_HIP_TEST ("" if absent); read every time: tests change it between calls
 inline std::string test_knob(const char *key) {
     const char *e = getenv("SINA_HIP_TEST");
@@ -372,6 +361,14 @@ struct DpGeom {
     int Lp() const { return T * B; }
 };
 bool pick_geom(uint32_t maxL, DpGeom *g);
+// DP waves per SIMD of geometry B (one wave = one query): what launches are sized by (dp_wave_slots, ctx.h) and what
+// each wave's LDS is left for (dp_default_lds_budget).  (B = 4: the simple kernel needs 87 VGPRs, five waves per
+// SIMD -- 5120-query launches of V4 amplicons run 11 % faster per query than 4096-query ones; the general B = 4
+// kernels stay at four.)  The kernels' __launch_bounds__ are minimum occupancies, not this number.
+#ifndef SINA_DP_SIMPLE_WAVES8
+#define SINA_DP_SIMPLE_WAVES8 3  // waves per SIMD the B = 8 kernel is compiled for
+#endif
+constexpr int dp_waves_per_simd(int B) { return B <= 4 ? 5 : (B <= 8 ? SINA_DP_SIMPLE_WAVES8 : 2); }
 size_t dp_slot_bytes(const DpGeom &g);
 size_t dp_fixed_lds_bytes(const DpGeom &g);
 int dp_max_ring(const DpGeom &g);  // deepest LDS ring the slot allocators support

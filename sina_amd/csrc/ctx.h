@@ -29,10 +29,6 @@ struct sina_hip_store {
     std::atomic<bool> dense_ready{false};
     std::mutex aux_mu;
     std::mutex stats_mu;
-    // One DP kernel at a time per device: a DP launch fills every CU by itself, and contexts that
-    // all reach their DP phase together would otherwise run in lock-step (GPU idle while all of
-    // them are in their host phases).  Holding this while the DP kernel runs staggers them.
-    std::mutex dp_token;
     // The device-filling kernels of all contexts (k-mer count/select, DAG build, DP) go through ONE
     // stream, in the order the host threads reach them: see sina_hip::heavy_launch below.
     hipStream_t heavy = nullptr;
@@ -58,11 +54,9 @@ struct sina_hip_store {
     bool heavy_prev_dry = false;     // the last launch signals "dry" (flag word reaches heavy_prev_seq) ...
     uint32_t heavy_prev_seq = 0;     // (its number: NOT heavy_seq -- a launch that failed half-way took a number too)
     bool heavy_prev_any = false;     // ... there has been one at all
-    // admission (heavy_launch): launches handed to the GPU and not yet known to have ended, the kind of the
-    // last one handed over, and who is waiting to be
+    // admission (heavy_launch): launches handed to the GPU and not yet known to have ended, and who is waiting to be
     std::condition_variable heavy_cv;
     int heavy_outstanding = 0;
-    int heavy_last_kind = -1;
     uint64_t heavy_ticket = 0;
     struct heavy_waiter {
         uint64_t ticket;
@@ -107,8 +101,8 @@ struct sina_hip_store {
 struct sina_hip_ctx {
     int device = 0;
     int n_cu = 256;  // compute units of the device (4 SIMDs each)
-    hipStream_t stream = nullptr;     // everything but the DP: highest priority
-    hipStream_t stream_dp = nullptr;  // DP kernel + backtrack: lowest priority (see make_streams)
+    hipStream_t stream = nullptr;     // uploads, k-mer searches' copies ... (see make_streams)
+    hipStream_t stream_dp = nullptr;  // DP hand-over, result copies
     std::mutex mu;
     hipEvent_t ev[12];  // [10], [11]: hand-over to / from the store's heavy stream
 
@@ -326,13 +320,12 @@ inline int ensure_ref_off_host(sina_hip_ctx *c) {
 }  // namespace sina_hip
 
 namespace sina_hip {
-// DP waves the device holds at once (one wave = one query; mesh_dp_kernel's launch bounds).  A launch
+// DP waves the device holds at once (one wave = one query, dp_waves_per_simd per SIMD).  A launch
 // of exactly that many queries -- or a multiple -- keeps every SIMD at its full wave count until the
 // last round; a launch of 4/3 of it runs the last third on a quarter-filled device (measured, 16S:
 // 3072 queries 27.7 ms, 4096 41.1 ms, 6144 49.7 ms).
 inline uint32_t dp_wave_slots(const sina_hip_ctx *c, int B) {
-    const int waves_per_simd = B <= 4 ? 5 : (B <= 8 ? 3 : 2);  // (mesh_dp.hip, dp_default_lds_budget)
-    return (uint32_t)(waves_per_simd * 4 * (c->n_cu > 0 ? c->n_cu : 256));
+    return (uint32_t)(dp_waves_per_simd(B) * 4 * (c->n_cu > 0 ? c->n_cu : 256));
 }
 // End of a DP launch range that the trace-back budget cut short (q1 < limit): whole rounds of wave
 // slots if it holds at least one.
@@ -351,15 +344,6 @@ namespace sina_hip {
 // works off without the host in between: the kernel waits (event) for what its context queued before
 // it; the host thread that queued it waits for its end.  Thin, latency-bound work (copies,
 // the backtrack walk) stays on the contexts' streams and runs beside whatever is resident.
-// SINA_HIP_SERIALIZE=0 (experiments): every kernel on its own context's stream again, DP launches
-// taking turns through a host-side token.
-inline bool serialize_kernels() {
-    static const bool on = [] {
-        const char *v = sina_hip::experiment_env("SINA_HIP_SERIALIZE");
-        return !(v && *v == '0');
-    }();
-    return on;
-}
 // Waits for an event / for everything queued on a stream of the context WITHOUT burning a core: the
 // runtime's hipStreamSynchronize and hipEventSynchronize (hipEventBlockingSync or not) busy-poll, and
 // so does its hipLaunchHostFunc helper thread (tools/ubench/wait_cpu.hip: 50 ms of CPU per 50 ms
@@ -418,7 +402,7 @@ inline int download(sina_hip_ctx *c, int slot, const void *src, size_t bytes, hi
 //   * for the END of the launch two places ahead (stream order: same stream),
 //   * for the launch right ahead of it only to have RUN DRY -- hipStreamWaitValue32 on a flag word that
 //     launch's last-started workgroup writes (tools/ubench/chain.hip: the follower starts 0.3 ms after the
-//     flag, i.e. as soon as a slot is free) -- if that launch signals it (DP, DAG build), else for its end.
+//     flag, i.e. as soon as a slot is free) -- if that launch signals it (a DP launch does), else for its end.
 // So at most two device-filling kernels are resident, and only while the older one has nothing left to
 // dispatch: the newer one gets exactly the slots the drain leaves empty.  Nothing runs beside a kernel
 // that still has workgroups waiting (what round 1 measured as mutual stretching).  Every wait refers to
@@ -444,25 +428,16 @@ inline bool chain_kernels() {
 //     much, and ends with a drain that wide (a DP wave runs three 16 ms queries back to back: nothing evens a
 //     5 ms stagger out).  A DAG build or a k-mer search, made of thousands of short workgroups, absorbs that;
 //     a DP launch hands it on to whatever follows it;
-//   * the finished launch's backtrack walk starts on its context's own stream the moment it ends and runs beside
+//   * the finished launch's backtrack walk starts the moment it ends and runs beside
 //     whatever is resident then: it stretches a DAG build by 1.8 ms and a DP launch by 8 (its waves take the LDS
 //     of retiring DP waves).
 // Kernel trace of a run that PREFERRED a DP launch behind a DP launch (profiles/r04_burst_trace.txt): two DP
 // launches back to back took 102 ms, 2 x 48.3 alone.  So at most kHeavyDepth launches are handed to the GPU
 // ahead of time (one running, one queued behind it -- enough to never leave the device idle: every launch
 // runs for milliseconds), the other callers wait on the host, and when a place frees up the waiter to take it
-// is: behind a DP launch the oldest waiting DAG build, else the oldest k-mer search, and only if neither is
-// waiting another DP launch; behind anything else the oldest waiter.
-// SINA_HIP_DP_BURST: 0 = arrival order, 1 = DP behind DP preferred (the experiment above), default -1.
+// is the oldest waiting DAG build, else the oldest k-mer search, else the oldest waiter.
 enum heavy_kind { kHeavyKmer = 0, kHeavyGraph = 1, kHeavyDp = 2 };
 constexpr int kHeavyDepth = 2;
-inline int heavy_order_policy() {
-    static const int mode = [] {
-        const char *v = experiment_env("SINA_HIP_DP_BURST");
-        return v && *v ? atoi(v) : -1;
-    }();
-    return mode;
-}
 struct heavy_launch {
     sina_hip_ctx *c;
     hipStream_t own, hs;
@@ -476,7 +451,7 @@ struct heavy_launch {
     uint32_t my_seq = 0;
     // `own`: the context stream whose queued work (uploads) the kernel depends on
     heavy_launch(sina_hip_ctx *c_, hipStream_t own_, int kind_ = kHeavyKmer) : c(c_), own(own_), hs(own_), kind(kind_) {
-        if (!serialize_kernels() || !c->st->heavy) return;
+        if (!c->st->heavy) return;
         sina_hip_store *st = c->st;
         if (st->wedged.load(std::memory_order_relaxed)) {
             failed = true;
@@ -492,25 +467,19 @@ struct heavy_launch {
             st->heavy_cv.wait(lk, [&] {
                 if (st->heavy_outstanding >= kHeavyDepth) return false;
                 // whose turn is it?
-                const sina_hip_store::heavy_waiter *pick = nullptr;
                 auto oldest_of = [&](int k) {
                     const sina_hip_store::heavy_waiter *o = nullptr;
                     for (const auto &w : st->heavy_waiting)
                         if ((k < 0 || w.kind == k) && (!o || w.ticket < o->ticket)) o = &w;
                     return o;
                 };
-                if (st->heavy_last_kind == kHeavyDp && heavy_order_policy() > 0) {
-                    pick = oldest_of(kHeavyDp);
-                    if (!pick) pick = oldest_of(kHeavyGraph);
-                } else if (heavy_order_policy() < 0) {
-                    // (round 6: a DAG build, then a k-mer search, goes before a DP launch WHENEVER one waits, not only
-                    // behind a DP launch: a batch's scout pass runs between its DAG build and its DP launch, on the
-                    // context's own stream -- with the build scheduled right in front of the batch's own DP launch the
-                    // FIFO sat idle for the scout's 4.5 ms every step (profiles/r06_heavy_gaps_before.txt); built a DP
-                    // launch earlier, the scout runs beside the DP launch of the batch before)
-                    pick = oldest_of(kHeavyGraph);
-                    if (!pick) pick = oldest_of(kHeavyKmer);
-                }
+                // (round 6: a DAG build, then a k-mer search, goes before a DP launch WHENEVER one waits, not only
+                // behind a DP launch: a batch's scout pass runs between its DAG build and its DP launch, on the
+                // context's own stream -- with the build scheduled right in front of the batch's own DP launch the
+                // FIFO sat idle for the scout's 4.5 ms every step (profiles/r06_heavy_gaps_before.txt); built a DP
+                // launch earlier, the scout runs beside the DP launch of the batch before)
+                const sina_hip_store::heavy_waiter *pick = oldest_of(kHeavyGraph);
+                if (!pick) pick = oldest_of(kHeavyKmer);
                 if (!pick) pick = oldest_of(-1);
                 return pick && pick->ticket == me;
             });
@@ -520,7 +489,6 @@ struct heavy_launch {
                     break;
                 }
             ++st->heavy_outstanding;
-            st->heavy_last_kind = kind;
             admitted = true;
         }
         turn = chain ? st->heavy_turn : 0;

@@ -101,7 +101,6 @@ struct GraphArgs {
     int want_smin;             // succ_min is read by somebody (--insertion=forbid, the debug entry): else it is not touched at all
     uint2 *reach;              // [nq][ncap] or nullptr: the DP kernel's row-skip bound (step 9; units: common.h): {R(m), last successor | C(m) << 16}
     float kappa64;             // ... 64 * 1.0001 * (largest match gain per unit of node weight)
-    DryArgs dry;               // (ctx.h, heavy_launch: tells the launch queued behind when the last workgroup has started)
 };
 
 // per family member, in LDS
@@ -273,7 +272,6 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint32_t s_tmp[kGT / 64 + 8];
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    dry_signal(a.dry, gridDim.x, tid == 0);
     const uint32_t nwords = (a.width + 31) / 32;
     const uint64_t f0 = a.fam_off[q];
     const uint32_t F = (uint32_t)(a.fam_off[q + 1] - f0);
@@ -834,14 +832,10 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
             // The launch behind a DAG build waits for its END: the build's own drain is a millisecond, and a DP launch
             // that starts in it begins with a stagger it carries to its own end (measured: 142.1 k sequences/s with
             // the signal, 143.1 k without, DP 49.5 against 48.3 ms per launch; profiles/r04_chain_ab.txt).
-            // SINA_HIP_GRAPH_DRY=1 (experiments): the build tells its follower when its queue has run dry, like a DP launch.
-            static const bool graph_dry = experiment_env("SINA_HIP_GRAPH_DRY") && experiment_env("SINA_HIP_GRAPH_DRY")[0] == '1';
-            ga.dry = graph_dry ? hl.dry() : DryArgs{nullptr, nullptr, 0};
             hipLaunchKernelGGL(family_graph_kernel, dim3(bq), dim3(kGT), glds, hl.stream(), ga);
             SH_CHECK(hipGetLastError());
             SH_CHECK(hipEventRecord(c->ev[7], hl.stream()));
             if (hl.done()) return 1;
-            if (experiment_env("SINA_HIP_DEBUG_SYNC")) fprintf(stderr, "[sina_hip] DAG build kernel done: %u families, ncap %u\n", bq, ncap);
         }
         if (download(c, 4, c->g_sizes.p, 4 * kSz * (uint64_t)bq, s)) return 1;
         SH_CHECK(wait_stream(c, s));
@@ -902,11 +896,10 @@ int sina_hip_align_families(sina_hip_ctx *c, const uint32_t *fam_ids, const uint
     const uint64_t tb_budget_cells = tb_plane_budget(c) / tb_cell_bytes(p->insertion == SINA_INSERTION_FORBID);
     // queries per DAG build and DP launch: up to three rounds of DP wave slots (one DP wave per query) -- a DP
     // launch ends with ~4.4 ms of draining device whatever its size, so a third round makes it 3 % faster per
-    // query than two (a fourth adds 2 % and another 22 GB per trace-back plane; SINA_HIP_DP_ROUNDS); the DP
+    // query than two (a fourth adds 2 % and another 22 GB per trace-back plane); the DP
     // launches below are whole rounds where the trace-back budget cuts a chunk
     const uint32_t slots = dp_wave_slots(c, pl.geom.B);
-    static const uint32_t rounds = experiment_env("SINA_HIP_DP_ROUNDS") ? (uint32_t)std::max(1, atoi(experiment_env("SINA_HIP_DP_ROUNDS"))) : 3u;
-    const uint32_t chunk_q = rounds * slots;
+    const uint32_t chunk_q = 3 * slots;
     BuiltGraphs bg;
     std::vector<uint32_t> dag_of;      // per query of the chunk: which of the chunk's distinct DAGs is its family's
     std::vector<uint32_t> ufam_ids;    // the distinct families, concatenated
@@ -916,14 +909,13 @@ int sina_hip_align_families(sina_hip_ctx *c, const uint32_t *fam_ids, const uint
         // Queries with the same ORDERED family share one DAG (node order, weights, predecessor lists and the DP's
         // row-slot assignment depend on nothing else): amplicons of one region against one reference clade.  The
         // DAG is built once per distinct family of the chunk; every query keeps its own trace-back cells, spill
-        // rows and edge records.  (SINA_HIP_SHARE_DAGS=0: one build per query.)
-        static const bool share = !(experiment_env("SINA_HIP_SHARE_DAGS") && experiment_env("SINA_HIP_SHARE_DAGS")[0] == '0');
+        // rows and edge records.
         dag_of.assign(bq, 0);
         uint32_t n_dags = bq;
         const uint32_t *b_ids = fam_ids;
         const uint64_t *b_off = fam_off;
         uint32_t b_q0 = q0;
-        if (share && bq > 1) {
+        if (bq > 1) {
             auto fam_hash = [&](uint32_t q) {
                 uint64_t h = 0xcbf29ce484222325ull ^ (fam_off[q + 1] - fam_off[q]);
                 for (uint64_t x = fam_off[q]; x < fam_off[q + 1]; x++) {

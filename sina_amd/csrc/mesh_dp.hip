@@ -1014,9 +1014,6 @@ mesh_dp_kernel(const QDesc *__restrict__ qdv, const uint32_t *__restrict__ order
 // mesh_dp_kernel.  Results are bit-identical between the two: tests/test_gpu_parity.py runs every
 // simple-scheme plane test through both (SINA_HIP_TEST=generic=1 forces the generic kernel).
 template <int B, bool DBG, bool PRUNE>
-#ifndef SINA_DP_SIMPLE_WAVES8
-#define SINA_DP_SIMPLE_WAVES8 3  // waves per SIMD the B = 8 kernel is compiled for
-#endif
 __global__ void __launch_bounds__(64, (B <= 4 ? 4 : (B <= 8 ? SINA_DP_SIMPLE_WAVES8 : 2)))
 mesh_dp_simple_kernel(const QDesc *__restrict__ qdv, const uint32_t *__restrict__ orderv, const uint4 *__restrict__ recv,
                       const uint32_t *__restrict__ predv, const uint8_t *__restrict__ qmaskv, void *__restrict__ tbv,
@@ -1846,32 +1843,101 @@ mesh_dp_simple_kernel(const QDesc *__restrict__ qdv, const uint32_t *__restrict_
     }
 }
 
-// One wave per query: the cell walk of backtrack() (mesh.h:594-721).  The walk is one logical thread
-// (every lane computes the same thing) -- a chain of dependent look-ups, two per step when they go
-// to HBM.  It only ever moves to smaller rows and smaller columns, so the wave keeps a WINDOW of the
-// trace-back plane in LDS: the 64 rows x 32 columns whose upper right corner is the cell that missed,
-// one row per lane, together with those rows' records, columns and first four predecessors.  A step
-// inside the window costs LDS latency; a refill (two round trips, every ~30 steps) is paid by 64
-// lanes at once.  LAZY: 16-bit cells (type code + predecessor ordinal) instead of 32-bit ones.
+// The cell walk of backtrack() (mesh.h:594-721) reads three things of the trace-back plane: cells, row records
+// and predecessor entries.  Two memory policies fetch them; walk_query() below is the walk itself.  A policy
+// offers cell(row, col), rec(row) (the row record, .w replaced by the node's column), pred(row, pb, e)
+// (predecessor entry e of the row, whose first is pb = rec.x) and `writes`: whether this thread stores the
+// query's output.  LAZY: 16-bit cells (type code + predecessor ordinal) instead of 32-bit ones.
+//
+// BtDirect: plain global loads, one lane per query (backtrack_lanes_kernel).
+template <bool LAZY>
+struct BtDirect {
+    using cell_t = typename std::conditional<LAZY, uint16_t, uint32_t>::type;
+    static constexpr bool writes = true;
+    const cell_t *tb;
+    const uint4 *recs;
+    const uint32_t *node_pos, *preds;
+    uint32_t Lp;
+    __device__ BtDirect(const BtArgs &a, const QDesc &d)
+        : tb(reinterpret_cast<const cell_t *>(a.tb) + d.tb_off), recs(a.rec + d.node_off), node_pos(a.node_pos + d.node_off),
+          preds(a.pred + d.edge_off), Lp(a.Lp) {}
+    __device__ uint32_t cell(uint32_t row, uint32_t col) const { return (uint32_t)tb[(size_t)row * Lp + col]; }
+    __device__ uint4 rec(uint32_t row) const {  // (a caller that reads no .w loads no column)
+        uint4 rx = recs[row];
+        rx.w = node_pos[row];
+        return rx;
+    }
+    __device__ uint32_t pred(uint32_t, uint32_t pb, uint32_t e) const { return preds[pb + e] & 0xffffu; }
+};
+
+// BtWindow: one wave per query (backtrack_kernel).  There the walk is one logical thread (every lane computes the
+// same thing) -- a chain of dependent look-ups, two per step when they go to HBM.  It only ever moves to smaller
+// rows and smaller columns, so the wave keeps a WINDOW of the trace-back plane in LDS: the 64 rows x 32 columns
+// whose upper right corner is the cell that missed, one row per lane, together with those rows' records, columns
+// and first four predecessors.  A step inside the window costs LDS latency; a refill (two round trips, every ~30
+// steps) is paid by 64 lanes at once.  Lane 0 writes.
 constexpr int kBtRows = 64, kBtCols = 32;
 template <bool LAZY>
-__global__ void __launch_bounds__(64) backtrack_kernel(BtArgs a) {
-    using cell_t = typename std::conditional<LAZY, uint16_t, uint32_t>::type;
-    constexpr uint32_t kAlign = 16 / sizeof(cell_t);  // cells per 16-byte load
-    __shared__ __attribute__((aligned(16))) cell_t w_cell[kBtRows][kBtCols];
-    __shared__ uint4 w_rec[kBtRows];   // row records, .w replaced by the node's column
-    __shared__ uint4 w_pred[kBtRows];  // first four predecessor entries of the row
-    const uint32_t q = blockIdx.x;
-    const uint32_t lane = threadIdx.x;
-    if (q >= a.nq) return;
-    const QDesc d = a.qd[q];
-    const uint32_t L = d.L, N = d.N;
-    const uint32_t Lp = a.Lp;
-    const cell_t *tb = reinterpret_cast<const cell_t *>(a.tb) + d.tb_off;
-    const uint4 *rec = a.rec + d.node_off;
-    const uint32_t *node_pos = a.node_pos + d.node_off;
-    const uint32_t *pred = a.pred + d.edge_off;
-    uint32_t *out = a.out_pos + d.q_off;
+struct BtWindow {
+    using cell_t = typename BtDirect<LAZY>::cell_t;
+    static constexpr uint32_t kAlign = 16 / sizeof(cell_t);  // cells per 16-byte load
+    struct Lds {
+        cell_t cell[kBtRows][kBtCols];
+        uint4 rec[kBtRows];   // row records, .w replaced by the node's column
+        uint4 pred[kBtRows];  // first four predecessor entries of the row
+    };
+    BtDirect<LAZY> g;  // (refills and the look-ups outside the window)
+    Lds &w;
+    uint32_t N, lane;
+    bool writes;
+    // rows [wr0, wr0 + 64), columns [wc0, wc0 + 32); empty until the first miss
+    uint32_t wr0 = 0x80000000u, wc0 = 0;  // (no row is within 64 of that)
+    __device__ BtWindow(const BtArgs &a, const QDesc &d, Lds &lds, uint32_t lane_)
+        : g(a, d), w(lds), N(d.N), lane(lane_), writes(lane_ == 0) {}
+    __device__ void refill(uint32_t row, uint32_t col) {
+        __syncthreads();  // (one wave: orders the LDS reads before against the writes below)
+        wr0 = row + 1 >= (uint32_t)kBtRows ? row + 1 - kBtRows : 0u;
+        const uint32_t ctop = (col & ~(kAlign - 1)) + kAlign;  // first column right of the window
+        wc0 = ctop >= (uint32_t)kBtCols ? ctop - kBtCols : 0u;
+        const uint32_t x = wr0 + lane;
+        if (x < N) {
+            const uint4 *src = reinterpret_cast<const uint4 *>(g.tb + (size_t)x * g.Lp + wc0);
+            uint4 *dst = reinterpret_cast<uint4 *>(&w.cell[lane][0]);
+#pragma unroll
+            for (uint32_t i = 0; i < kBtCols / kAlign; i++) dst[i] = src[i];
+            const uint4 rx = g.rec(x);
+            w.rec[lane] = rx;
+            const uint32_t np = rx.z & 0xffu;
+            uint4 pe = {0u, 0u, 0u, 0u};
+            if (np > 0) pe.x = g.preds[rx.x];
+            if (np > 1) pe.y = g.preds[rx.x + 1];
+            if (np > 2) pe.z = g.preds[rx.x + 2];
+            if (np > 3) pe.w = g.preds[rx.x + 3];
+            w.pred[lane] = pe;
+        }
+        __syncthreads();
+    }
+    __device__ bool in_rows(uint32_t row) const { return row - wr0 < (uint32_t)kBtRows; }
+    __device__ uint32_t cell(uint32_t row, uint32_t col) {
+        if (!(in_rows(row) && col - wc0 < (uint32_t)kBtCols)) refill(row, col);
+        return (uint32_t)w.cell[row - wr0][col - wc0];
+    }
+    __device__ uint4 rec(uint32_t row) const {
+        if (in_rows(row)) return w.rec[row - wr0];
+        return g.rec(row);
+    }
+    __device__ uint32_t pred(uint32_t row, uint32_t pb, uint32_t e) const {
+        if (e < 4 && in_rows(row)) {
+            const uint4 pe = w.pred[row - wr0];
+            return (e == 0 ? pe.x : (e == 1 ? pe.y : (e == 2 ? pe.z : pe.w))) & 0xffffu;
+        }
+        return g.pred(row, pb, e);
+    }
+};
+
+// The walk of query q, from its DP result to its emitted columns (out_pos) and its sina_hip_align_out.
+template <bool LAZY, class Mem>
+__device__ __forceinline__ void walk_query(const BtArgs &a, uint32_t q, const QDesc &d, Mem &mem) {
     const DpResult r = a.res[q];
     sina_hip_align_out o;
     o.status = r.status;
@@ -1884,69 +1950,26 @@ __global__ void __launch_bounds__(64) backtrack_kernel(BtArgs a) {
     o.n_out = 0;
     o.assembled = o.nast_total = o.nast_longest = o.nast_last_run = 0;
     if (r.status != 0) {
-        if (lane == 0) a.out[q] = o;
+        if (mem.writes) a.out[q] = o;
         return;
     }
-    // ---- the window: rows [wr0, wr0 + 64), columns [wc0, wc0 + 32); empty until the first miss
-    uint32_t wr0 = 0x80000000u, wc0 = 0;  // (no row is within 64 of that)
-    auto refill = [&](uint32_t row, uint32_t col) {
-        __syncthreads();  // (one wave: orders the LDS reads before against the writes below)
-        wr0 = row + 1 >= (uint32_t)kBtRows ? row + 1 - kBtRows : 0u;
-        const uint32_t ctop = (col & ~(kAlign - 1)) + kAlign;  // first column right of the window
-        wc0 = ctop >= (uint32_t)kBtCols ? ctop - kBtCols : 0u;
-        const uint32_t x = wr0 + lane;
-        if (x < N) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(tb + (size_t)x * Lp + wc0);
-            uint4 *dst = reinterpret_cast<uint4 *>(&w_cell[lane][0]);
-#pragma unroll
-            for (uint32_t i = 0; i < kBtCols / kAlign; i++) dst[i] = src[i];
-            uint4 rx = rec[x];
-            rx.w = node_pos[x];
-            w_rec[lane] = rx;
-            const uint32_t np = rx.z & 0xffu;
-            uint4 pe = {0u, 0u, 0u, 0u};
-            if (np > 0) pe.x = pred[rx.x];
-            if (np > 1) pe.y = pred[rx.x + 1];
-            if (np > 2) pe.z = pred[rx.x + 2];
-            if (np > 3) pe.w = pred[rx.x + 3];
-            w_pred[lane] = pe;
-        }
-        __syncthreads();
-    };
-    auto in_rows = [&](uint32_t row) -> bool { return row - wr0 < (uint32_t)kBtRows; };
-    auto cell_at = [&](uint32_t row, uint32_t col) -> uint32_t {
-        if (!(in_rows(row) && col - wc0 < (uint32_t)kBtCols)) refill(row, col);
-        return (uint32_t)w_cell[row - wr0][col - wc0];
-    };
-    // row record / column / predecessor entry e of a row (through the window if the row is in it)
-    auto rec_at = [&](uint32_t row) -> uint4 {  // (.w = the node's column)
-        if (in_rows(row)) return w_rec[row - wr0];
-        uint4 rx = rec[row];
-        rx.w = node_pos[row];
-        return rx;
-    };
-    auto pred_at = [&](uint32_t row, uint32_t pb, uint32_t e) -> uint32_t {
-        if (e < 4 && in_rows(row)) {
-            const uint4 pe = w_pred[row - wr0];
-            return (e == 0 ? pe.x : (e == 1 ? pe.y : (e == 2 ? pe.z : pe.w))) & 0xffffu;
-        }
-        return pred[pb + e] & 0xffffu;
-    };
+    uint32_t *out = a.out_pos + d.q_off;
     const uint32_t width = a.width;
     uint32_t m = r.end_m, s = r.end_s;
     uint32_t n = 0;
-    const uint32_t send = L - 1;
-    auto emit = [&](uint32_t p) {  // (lane 0 writes; the walk itself is wave-uniform)
-        if (lane == 0) out[n] = p;
+    const uint32_t send = d.L - 1;
+    auto emit = [&](uint32_t p) {
+        if (mem.writes) out[n] = p;
         n++;
     };
 
     // right hand overhang (:594-615)
     const int tail = (int)(send - s);
     o.cutoff_tail = tail;
-    uint32_t c = cell_at(m, s);  // (fills the window around the end cell)
+    uint32_t c = mem.cell(m, s);  // (first: a window is filled around the end cell)
+    uint4 rm = mem.rec(m);
     if (tail && a.overhang != SINA_OVERHANG_REMOVE) {
-        int pos = (a.overhang == SINA_OVERHANG_ATTACH) ? (int)(width - 1 - rec_at(m).w - (uint32_t)tail) : 0;
+        int pos = (a.overhang == SINA_OVERHANG_ATTACH) ? (int)(width - 1 - rm.w - (uint32_t)tail) : 0;
         for (int i = 0; i < tail; i++) {
             const int p = pos++;
             emit((uint32_t)(p > 0 ? p : 0));
@@ -1963,7 +1986,6 @@ __global__ void __launch_bounds__(64) backtrack_kernel(BtArgs a) {
         }
         return a.ms * wgt;
     };
-    uint4 rm = rec_at(m);
     unsigned int pos = width - 1 - rm.w;
     float sum_weight = 0.f;
     int aligned = 0;
@@ -1976,11 +1998,11 @@ __global__ void __launch_bounds__(64) backtrack_kernel(BtArgs a) {
     constexpr uint32_t ext_bit = LAZY ? kTb16Ext : kTbExt;
     auto gapm_idx = [&](uint32_t x, uint32_t col) -> uint32_t {
         for (uint32_t guard = 0; guard < 65536u; ++guard) {
-            const uint32_t cx = cell_at(x, col);  // (first: a refill brings the row's record along)
-            const uint4 rx = rec_at(x);
+            const uint32_t cx = mem.cell(x, col);  // (first: a refill brings the row's record along)
+            const uint4 rx = mem.rec(x);
             const uint32_t np = rx.z & 0xffu;
             if (np == 0) return 0u;  // an edge row keeps its initial gapm_idx
-            const uint32_t lastp = pred_at(x, rx.x, np - 1);
+            const uint32_t lastp = mem.pred(x, rx.x, np - 1);
             if (LAZY ? !(cx & kTb16XLast) : (cx & kTbOpLast) != 0) return lastp;
             x = lastp;
         }
@@ -1993,7 +2015,7 @@ __global__ void __launch_bounds__(64) backtrack_kernel(BtArgs a) {
         const uint32_t t = cc & kTbTypeMask;
         if (t == kTbIns) return row;
         if (t == kTbNone) return 0u;
-        return pred_at(row, pb, cc >> kTb16OrdShift);
+        return mem.pred(row, pb, cc >> kTb16OrdShift);
     };
     // value_sidx of cell cc = (row, col): stored, or (type-code cells, common.h) what the type implies
     auto sidx_of = [&](uint32_t cc, uint32_t row, uint32_t col) -> uint32_t {
@@ -2003,7 +2025,7 @@ __global__ void __launch_bounds__(64) backtrack_kernel(BtArgs a) {
         if (t == kTbMatch) return col - 1;
         if (t == kTbDel) return col;
         uint32_t k = col - 1;  // insertion: the gap began where the run of insertion cells to the left ends
-        while (k > 0 && (cell_at(row, k) & kTbTypeMask) == kTbIns) --k;
+        while (k > 0 && (mem.cell(row, k) & kTbTypeMask) == kTbIns) --k;
         return k;
     };
     auto is_deletion_at = [&](uint32_t cc, uint32_t col) -> bool {  // value_sidx == own column
@@ -2015,13 +2037,13 @@ __global__ void __launch_bounds__(64) backtrack_kernel(BtArgs a) {
         const uint32_t snew = sidx_of(c, m, s);
         const uint32_t vm = midx_raw(c, m, rm.x);
         m = (c & ext_bit) ? gapm_idx(vm, s) : vm;
-        c = cell_at(m, snew);
+        c = mem.cell(m, snew);
         if (snew != 0 && is_deletion_at(c, snew)) {  // the one-step deletion skip (:653-655)
-            const uint32_t vm2 = midx_raw(c, m, rec_at(m).x);
+            const uint32_t vm2 = midx_raw(c, m, mem.rec(m).x);
             m = (c & ext_bit) ? gapm_idx(vm2, snew) : vm2;
-            c = cell_at(m, snew);
+            c = mem.cell(m, snew);
         }
-        rm = rec_at(m);
+        rm = mem.rec(m);
         npred_m = rm.z & 0xffu;
         pos = width - 1 - rm.w;
         while (s != snew) {
@@ -2047,159 +2069,33 @@ __global__ void __launch_bounds__(64) backtrack_kernel(BtArgs a) {
     o.sum_weight = sum_weight;
     o.aligned_bases = aligned;
     o.n_out = n;
-    if (lane == 0) a.out[q] = o;
+    if (mem.writes) a.out[q] = o;
 }
 
+template <bool LAZY>
+__global__ void __launch_bounds__(64) backtrack_kernel(BtArgs a) {
+    __shared__ typename BtWindow<LAZY>::Lds lds;
+    const uint32_t q = blockIdx.x;
+    if (q >= a.nq) return;
+    const QDesc d = a.qd[q];
+    BtWindow<LAZY> mem(a, d, lds, threadIdx.x);
+    walk_query<LAZY>(a, q, d, mem);
+}
 
-// The same walk with one LANE per query (launches of kBtLanesMin queries and more).  The wave-per-query kernel
-// above spends a whole wave's issue slots on one logical thread -- 60 instructions per step, 3000 steps, 9216
-// waves: 3 ms of a device whose other kernels (the next batch's DAG build, k-mer search and DP, running beside
-// it) are bound by instruction issue as well.  Here a wave walks 64 queries: 64 times fewer instructions, every
-// look-up a global load of its own (cells 2 bytes, a 64-byte sector each: a quarter of the window refills'
-// traffic), and the walk's latency -- a few dependent round trips per step, the rare branches of any lane paid by
-// the whole wave -- is hidden behind the kernels it runs beside instead of competing with them.
+// One LANE per query (launches of kBtLanesMin queries and more).  The wave-per-query kernel above spends a whole
+// wave's issue slots on one logical thread -- 60 instructions per step, 3000 steps, 9216 waves: 3 ms of a device
+// whose other kernels (the next batch's DAG build, k-mer search and DP, running beside it) are bound by instruction
+// issue as well.  Here a wave walks 64 queries: 64 times fewer instructions, every look-up a global load of its own
+// (cells 2 bytes, a 64-byte sector each: a quarter of the window refills' traffic), and the walk's latency -- a few
+// dependent round trips per step, the rare branches of any lane paid by the whole wave -- is hidden behind the
+// kernels it runs beside instead of competing with them.
 template <bool LAZY>
 __global__ void __launch_bounds__(64) backtrack_lanes_kernel(BtArgs a) {
-    using cell_t = typename std::conditional<LAZY, uint16_t, uint32_t>::type;
     const uint32_t q = blockIdx.x * 64u + threadIdx.x;
     if (q >= a.nq) return;
     const QDesc d = a.qd[q];
-    const uint32_t L = d.L;
-    const uint32_t Lp = a.Lp;
-    const cell_t *tb = reinterpret_cast<const cell_t *>(a.tb) + d.tb_off;
-    const uint4 *rec = a.rec + d.node_off;
-    const uint32_t *node_pos = a.node_pos + d.node_off;
-    const uint32_t *pred = a.pred + d.edge_off;
-    uint32_t *out = a.out_pos + d.q_off;
-    const DpResult r = a.res[q];
-    sina_hip_align_out o;
-    o.status = r.status;
-    o.end_m = r.end_m;
-    o.end_s = r.end_s;
-    o.raw = r.raw;
-    o.sum_weight = 0.f;
-    o.aligned_bases = 0;
-    o.cutoff_head = o.cutoff_tail = 0;
-    o.n_out = 0;
-    o.assembled = o.nast_total = o.nast_longest = o.nast_last_run = 0;
-    if (r.status != 0) {
-        a.out[q] = o;
-        return;
-    }
-    auto cell_at = [&](uint32_t row, uint32_t col) -> uint32_t { return (uint32_t)tb[(size_t)row * Lp + col]; };
-    auto rec_at = [&](uint32_t row) -> uint4 {  // (.w = the node's column)
-        uint4 rx = rec[row];
-        rx.w = node_pos[row];
-        return rx;
-    };
-    auto pred_at = [&](uint32_t pb, uint32_t e) -> uint32_t { return pred[pb + e] & 0xffffu; };
-    const uint32_t width = a.width;
-    uint32_t m = r.end_m, s = r.end_s;
-    uint32_t n = 0;
-    const uint32_t send = L - 1;
-    auto emit = [&](uint32_t p) { out[n++] = p; };
-
-    // right hand overhang (:594-615)
-    const int tail = (int)(send - s);
-    o.cutoff_tail = tail;
-    uint32_t c = cell_at(m, s);
-    uint4 rm = rec_at(m);
-    if (tail && a.overhang != SINA_OVERHANG_REMOVE) {
-        int pos = (a.overhang == SINA_OVERHANG_ATTACH) ? (int)(width - 1 - rm.w - (uint32_t)tail) : 0;
-        for (int i = 0; i < tail; i++) {
-            const int p = pos++;
-            emit((uint32_t)(p > 0 ? p : 0));
-        }
-    }
-    const uint8_t *qmb = a.qmask + d.q_off;
-    auto mscore_at = [&](const uint4 &rx, uint32_t si) -> float {  // tr.s.match(sum, ab2, ab1) with comp()==true
-        if (a.self16 != nullptr) return a.self16[qmb[si] & 0xfu];
-        const float wgt = __uint_as_float(rx.y);
-        if (a.weights != nullptr) {
-            const uint32_t nw1 = a.n_weights - 1;
-            return a.ms * a.weights[rx.w < nw1 ? rx.w : nw1] * wgt;
-        }
-        return a.ms * wgt;
-    };
-    unsigned int pos = width - 1 - rm.w;
-    float sum_weight = 0.f;
-    int aligned = 0;
-    emit(pos);
-    aligned++;
-    sum_weight = sum_weight + mscore_at(rm, s);
-
-    constexpr uint32_t ext_bit = LAZY ? kTb16Ext : kTbExt;
-    auto gapm_idx = [&](uint32_t x, uint32_t col) -> uint32_t {  // (see backtrack_kernel)
-        for (uint32_t guard = 0; guard < 65536u; ++guard) {
-            const uint32_t cx = cell_at(x, col);
-            const uint4 rx = rec[x];
-            const uint32_t np = rx.z & 0xffu;
-            if (np == 0) return 0u;
-            const uint32_t lastp = pred_at(rx.x, np - 1);
-            if (LAZY ? !(cx & kTb16XLast) : (cx & kTbOpLast) != 0) return lastp;
-            x = lastp;
-        }
-        return 0u;
-    };
-    auto midx_raw = [&](uint32_t cc, uint32_t row, uint32_t pb) -> uint32_t {
-        if (!LAZY) return cc >> 16;
-        const uint32_t t = cc & kTbTypeMask;
-        if (t == kTbIns) return row;
-        if (t == kTbNone) return 0u;
-        return pred_at(pb, cc >> kTb16OrdShift);
-    };
-    auto sidx_of = [&](uint32_t cc, uint32_t row, uint32_t col) -> uint32_t {
-        if (!LAZY) return cc & kTbSMask;
-        const uint32_t t = cc & kTbTypeMask;
-        if (t == kTbNone) return 0u;
-        if (t == kTbMatch) return col - 1;
-        if (t == kTbDel) return col;
-        uint32_t k = col - 1;  // insertion: the gap began where the run of insertion cells to the left ends
-        while (k > 0 && (cell_at(row, k) & kTbTypeMask) == kTbIns) --k;
-        return k;
-    };
-    auto is_deletion_at = [&](uint32_t cc, uint32_t col) -> bool {
-        return LAZY ? (cc & kTbTypeMask) == kTbDel : (cc & kTbSMask) == col;
-    };
-    // :642-685 (a source node has no predecessors)
-    uint32_t npred_m = rm.z & 0xffu;
-    while (s != 0 && npred_m != 0) {
-        const uint32_t snew = sidx_of(c, m, s);
-        const uint32_t vm = midx_raw(c, m, rm.x);
-        m = (c & ext_bit) ? gapm_idx(vm, s) : vm;
-        c = cell_at(m, snew);
-        if (snew != 0 && is_deletion_at(c, snew)) {  // the one-step deletion skip (:653-655)
-            const uint32_t vm2 = midx_raw(c, m, rec[m].x);
-            m = (c & ext_bit) ? gapm_idx(vm2, snew) : vm2;
-            c = cell_at(m, snew);
-        }
-        rm = rec_at(m);
-        npred_m = rm.z & 0xffu;
-        pos = width - 1 - rm.w;
-        while (s != snew) {
-            --s;
-            emit(pos);
-            aligned++;
-            sum_weight = sum_weight + mscore_at(rm, s);
-        }
-    }
-    // left hand overhang (:690-721)
-    if (s != 0) {
-        o.cutoff_head = (int)s;
-        if (a.overhang == SINA_OVERHANG_ATTACH) {
-            while (s-- != 0) {
-                ++pos;
-                emit((width - 1 < pos) ? width - 1 : pos);
-            }
-        } else if (a.overhang == SINA_OVERHANG_EDGE) {
-            int k = (int)s;
-            while (k--) emit(width - (uint32_t)k - 1);
-        }
-    }
-    o.sum_weight = sum_weight;
-    o.aligned_bases = aligned;
-    o.n_out = n;
-    a.out[q] = o;
+    BtDirect<LAZY> mem(a, d);
+    walk_query<LAZY>(a, q, d, mem);
 }
 
 
@@ -2432,12 +2328,7 @@ size_t dp_slot_bytes(const DpGeom &g) { return (size_t)64 * g.B * 8 + 16; }
 size_t dp_fixed_lds_bytes(const DpGeom &) { return 0; }
 int dp_max_ring(const DpGeom &) { return 8; }  // the slot allocators keep 8 slot states; deeper rings gain nothing
 // LDS per workgroup (= per wave) that still lets the kernel's register budget decide the occupancy
-size_t dp_default_lds_budget(const DpGeom &g) {
-    // (B = 4: the simple kernel needs 87 VGPRs, five waves per SIMD -- 5120-query launches of V4 amplicons
-    // run 11 % faster per query than 4096-query ones; the general B = 4 kernels stay at four)
-    const int waves_per_simd = g.B <= 4 ? 5 : (g.B <= 8 ? SINA_DP_SIMPLE_WAVES8 : 2);
-    return (size_t)160 * 1024 / (4 * waves_per_simd) - 64;
-}
+size_t dp_default_lds_budget(const DpGeom &g) { return (size_t)160 * 1024 / (4 * dp_waves_per_simd(g.B)) - 64; }
 
 int launch_mesh_dp(const DpGeom &g, bool weighted, bool forbid, const DpArgs &a, uint32_t nq,
                    size_t lds, hipStream_t s) {

@@ -129,8 +129,7 @@ def test_launch_order_settings_do_not_change_results(env):
     scheduling / bookkeeping / which exact code path computes the same thing: chained launches, the load-time
     environment defaults, the DP kernel's certified row skip (off; and with a guess no query can meet, so that every
     one is swept twice), the trace-back plane pool, allocation tracing, the test hooks (generic DP kernel, no dense
-    posting-list bitmaps).  Eight batches in flight twice over give the same trays bit for bit under every setting.
-    (The experiment switches of rounds 1-4 exist only in -DSINA_EXPERIMENTS builds.)"""
+    posting-list bitmaps).  Eight batches in flight twice over give the same trays bit for bit under every setting."""
     def run(extra):
         e = dict(os.environ)
         for k in ("SINA_HIP_CHAIN", "SINA_HIP_NO_RUNTIME_DEFAULTS", "SINA_HIP_DP_PRUNE", "SINA_HIP_TB_PLANES", "SINA_HIP_TB_GB",
