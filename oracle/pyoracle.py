@@ -394,13 +394,8 @@ class Index:
         return ids[:n].copy(), sc[:n].copy(), txt
 
 
-def mseq_build(fam, weight=1.0):
-    """Returns dict of numpy arrays describing the family DAG (or None if it would throw)."""
-    h = handles(fam)
-    g = lib().so_mseq_build(h, len(fam), weight)
-    if not g:
-        return None
-    G = g.contents
+def _graph_arrays(G):
+    """The arrays of a so_graph as a dict of numpy copies (prof: [n, 6] for a profile, else None)."""
     n = G.n
 
     def arr(p, cnt, dt):
@@ -409,23 +404,32 @@ def mseq_build(fam, weight=1.0):
         return np.ctypeslib.as_array(p, shape=(cnt,)).astype(dt).copy()
     pred_off = arr(G.pred_off, n + 1, np.uint32)
     succ_off = arr(G.succ_off, n + 1, np.uint32)
-    d = dict(n=n, width=G.width, pos=arr(G.pos, n, np.uint32), mask=arr(G.mask, n, np.uint8),
-             weight=arr(G.weight, n, np.float32), pred_off=pred_off,
-             pred=arr(G.pred, int(pred_off[-1]) if n else 0, np.uint32), succ_off=succ_off,
-             succ=arr(G.succ, int(succ_off[-1]) if n else 0, np.uint32),
-             src=arr(G.src, G.n_src, np.uint32), snk=arr(G.snk, G.n_snk, np.uint32))
+    return dict(n=n, width=G.width, pos=arr(G.pos, n, np.uint32), mask=arr(G.mask, n, np.uint8),
+                weight=arr(G.weight, n, np.float32), pred_off=pred_off,
+                pred=arr(G.pred, int(pred_off[-1]) if n else 0, np.uint32), succ_off=succ_off,
+                succ=arr(G.succ, int(succ_off[-1]) if n else 0, np.uint32),
+                src=arr(G.src, G.n_src, np.uint32), snk=arr(G.snk, G.n_snk, np.uint32),
+                prof=(np.ctypeslib.as_array(G.prof, shape=(n, 6)).copy() if n else np.zeros((0, 6), np.float32))
+                if G.prof else None)
+
+
+def mseq_build(fam, weight=1.0):
+    """Returns dict of numpy arrays describing the family DAG (or None if it would throw)."""
+    h = handles(fam)
+    g = lib().so_mseq_build(h, len(fam), weight)
+    if not g:
+        return None
+    d = _graph_arrays(g.contents)
+    del d["prof"]
     lib().so_graph_free(g)
     return d
 
 
 def pseq_build(fam):
-    """The family as a profile (--fs-no-graph): dict(n, width, pos, prof[n, 6])."""
+    """The family as a profile (--fs-no-graph): dict(n, width, pos, prof[n, 6]) and the chain's DAG arrays
+    (every node's one predecessor the node before it; first node the source, last the sink)."""
     g = lib().so_pseq_build(handles(fam), len(fam))
-    G = g.contents
-    n = G.n
-    d = dict(n=n, width=G.width,
-             pos=np.ctypeslib.as_array(G.pos, shape=(n,)).copy() if n else np.zeros(0, np.uint32),
-             prof=np.ctypeslib.as_array(G.prof, shape=(n, 6)).copy() if n else np.zeros((0, 6), np.float32))
+    d = _graph_arrays(g.contents)
     lib().so_graph_free(g)
     return d
 
@@ -448,6 +452,32 @@ def mesh_compute(fam, query, opts=None, weight=None):
     lib().so_mesh_compute(g, _p(q, u32p), len(q), C.byref(opts), cells.ctypes.data_as(C.c_void_p))
     lib().so_graph_free(g)
     return cells
+
+
+def backtrack(fam, query, opts=None):
+    """mesh compute + backtrack() of `query` AS GIVEN against the family's DAG (or profile), without the
+    aligner glue of align() (which upper-cases the query and takes members that contain it out of the family).
+    Returns dict(status, head, tail, score, log, packed, width, aligned, cells)."""
+    opts = opts or align_opts()
+    L = lib()
+    h = handles(fam)
+    g = L.so_pseq_build(h, len(fam)) if opts.fs_no_graph else L.so_mseq_build(h, len(fam), opts.fs_weight)
+    if not g:
+        return dict(status=-1)
+    q = query.packed()
+    cells = np.zeros((g.contents.n, len(q)), CELL_DTYPE)
+    L.so_mesh_compute(g, _p(q, u32p), len(q), C.byref(opts), cells.ctypes.data_as(C.c_void_p))
+    out = Cseq("out")
+    head, tail = C.c_int(), C.c_int()
+    lg = new_log()
+    score = L.so_backtrack(g, _p(q, u32p), len(q), cells.ctypes.data_as(C.c_void_p), C.byref(opts), out.h,
+                           C.byref(head), C.byref(tail), C.byref(lg))
+    txt = log_text(lg)
+    L.so_log_free(C.byref(lg))
+    L.so_graph_free(g)
+    ok = np.float32(score) != np.float32(-1e30)
+    return dict(status=0 if ok else -1, head=head.value, tail=tail.value, score=np.float32(score), log=txt,
+                packed=out.packed(), width=out.width, aligned=out.aligned() if ok else None, cells=cells)
 
 
 def align(fam, query, opts=None):

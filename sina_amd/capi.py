@@ -248,8 +248,10 @@ class Context:
         return p
 
     @staticmethod
-    def graph_batch(graphs, width):
-        """graphs: list of dicts with pos, mask, weight, pred_off, pred[, succ_minpos]."""
+    def graph_batch(graphs, width, node_score16=None, self_score16=None):
+        """graphs: list of dicts with pos, mask, weight, pred_off, pred[, succ_minpos].
+        node_score16 / self_score16: a profile batch (--fs-no-graph, sina_hip_graph_batch): float32
+        [total nodes, 16] match terms per node and query iupac mask, and the 16 self-comparison terms."""
         nq = len(graphs)
         node_off = np.zeros(nq + 1, np.uint64)
         edge_off = np.zeros(nq + 1, np.uint64)
@@ -273,6 +275,12 @@ class Context:
         gb.pred = _ptr(arrs["pred"], u32p)
         gb.succ_minpos = _ptr(arrs["succ_minpos"], u32p) if "succ_minpos" in arrs else None
         gb.width = width
+        if node_score16 is not None:
+            arrs["node_score16"] = _c(np.asarray(node_score16).reshape(-1), np.float32)
+            arrs["self_score16"] = _c(self_score16, np.float32)
+            assert len(arrs["node_score16"]) == 16 * int(node_off[nq]) and len(arrs["self_score16"]) == 16
+            gb.node_score16 = _ptr(arrs["node_score16"], f32p)
+            gb.self_score16 = _ptr(arrs["self_score16"], f32p)
         gb._keep = arrs
         return gb
 

@@ -33,9 +33,10 @@ def graph_dict(fam, weight=1.0):
     return g
 
 
-def finish_alignment(q_masks, out, pos, width, lowercase_unaligned=False, insertion_remove=False):
+def finish_alignment(q_masks, out, pos, width, lowercase_unaligned=False, insertion_remove=False, want_packed=False):
     """Applies the cseq container steps of backtrack() (mesh.h:603-726) to the device's
-    per-append columns, using the oracle's cseq ops.  Returns (aligned string, log)."""
+    per-append columns, using the oracle's cseq ops.  Returns (aligned string, log), or with want_packed
+    (packed aligned bases, log)."""
     L = po.lib()
     c = po.Cseq("out")
     n = int(out["n_out"])
@@ -69,6 +70,8 @@ def finish_alignment(q_masks, out, pos, width, lowercase_unaligned=False, insert
     rc = L.so_cseq_fix_duplicate_positions(c.h, C.byref(lg), int(lowercase_unaligned), int(insertion_remove))
     txt = po.log_text(lg)
     L.so_log_free(C.byref(lg))
+    if want_packed:
+        return (c.packed() if rc == 0 else None), txt
     return (c.aligned() if rc == 0 else None), txt
 
 
@@ -172,6 +175,63 @@ def plane_hash(a):
     b = np.ascontiguousarray(a)
     b = b.view(np.uint32) if b.dtype == np.float32 else b.astype(np.uint32)
     return np.frombuffer(hashlib.sha1(b.tobytes()).digest()[:8], np.uint64)[0]
+
+
+# ---------------------------------------------------------------- the seeded fuzz generator
+# (test_mesh_plane_fuzz and test_walk_fuzz share these; the ORDER of the draws is part of it: a seed names a case)
+
+def fuzz_world(seed):
+    """Seeded random reference set (1 - 90 members, heavy to no divergence, long deletions that make far-away
+    predecessors, ambiguity codes, lower case).  Returns (rng, pick, refs, cseqs, usable member indices); the rng is
+    handed on so that the caller's later draws belong to the same seed."""
+    for attempt in range(8):  # (short references under long deletions can all come out empty: draw again)
+        rng = np.random.default_rng(9000 + seed + 100000 * attempt)
+        pick = lambda xs: xs[int(rng.integers(0, len(xs)))]  # noqa: E731
+        length = int(pick([60, 150, 320, 700]))
+        refs = synth.make_refs(int(pick([8, 40, 90])), length=length, width=int(length * pick([3, 8])), seed=9100 + seed,
+                               n_clades=int(pick([1, 3, 8])), clade_div=float(pick([0.05, 0.2, 0.4])),
+                               sub_hi=float(pick([0.02, 0.1, 0.3])), del_rate=float(pick([0.0, 0.01, 0.08])),
+                               ins_rate=float(pick([0.0, 0.005, 0.05])), long_del_prob=float(pick([0.0, 0.3, 1.0])),
+                               amb_rate=float(pick([0.0, 0.03])), lower_rate=float(pick([0.0, 0.1])))
+        cs = cseqs_from_refs(refs)
+        usable = [i for i in range(refs.n) if cs[i].size >= 20]
+        if usable:
+            break
+    assert usable
+    return rng, pick, refs, cs, usable
+
+
+def fuzz_family(rng, pick, cs, usable):
+    nfam = int(pick([1, 2, 7, 40, 60]))
+    return [cs[i] for i in list(rng.permutation(usable)[:nfam])]
+
+
+def fuzz_query(rng, pick, refs, usable):
+    """A piece of a member, mutated (iupac masks, upper case)."""
+    src = (refs.seq(usable[int(rng.integers(0, len(usable)))]) >> 24) & 0x0f
+    lo = int(rng.integers(0, max(1, len(src) // 3)))
+    hi = int(rng.integers(min(len(src), lo + 5), len(src) + 1))
+    qm = src[lo:hi].copy()
+    mut = rng.random(len(qm)) < float(pick([0.0, 0.05, 0.3]))
+    qm[mut] = rng.choice([1, 2, 4, 8, 15, 3], size=int(mut.sum()))
+    return np.asarray(qm, np.uint8)
+
+
+def fuzz_knobs_and_scoring(rng, pick, refs, max_qlen):
+    """DP geometry (incl. a single LDS row slot), scoring parameters, insertion rule, node-weight scale, positional
+    weights.  Returns (knobs for set_knobs, options)."""
+    knobs = {}
+    geom = pick([None, None, "64,4", "128,4", "64,8", "128,8", "64,12", "128,12"])
+    if geom and max_qlen <= int(geom.split(",")[0]) * int(geom.split(",")[1]):
+        knobs["geom"] = geom
+    if rng.integers(0, 3) == 0:
+        knobs["lds_kb"] = pick([5, 9])
+    gp, gpe = pick([(5, 2), (4, 1.5), (2, 3), (3, 3), (6, 0.5), (0.3, 0.1)])
+    opts = dict(match_score=float(pick([2, 3, 0.7])), mismatch_score=float(pick([-1, -2, -0.1])), gap_penalty=float(gp),
+                gap_ext_penalty=float(gpe), insertion=int(pick([0, 0, 1])), fs_weight=float(pick([1.0, 0.0, 2.5])))
+    if rng.integers(0, 3) == 0:
+        opts["weights"] = rng.uniform(0.2, 1.6, size=refs.width).astype(np.float32)
+    return knobs, opts
 
 
 def set_knobs(monkeypatch, **kw):
