@@ -258,6 +258,22 @@ int sina_hip_align_families(sina_hip_ctx *ctx, const uint32_t *fam_ids, const ui
                             const sina_hip_align_params *p, sina_hip_align_out *out,
                             uint32_t *out_pos);
 
+/* Same, but the family is the template as a PROFILE (--fs-no-graph: pseq p(vcp.begin(), vcp.end()) and
+ * scoring_scheme_profile, src/align.cpp:428-433; src/pseq.cpp, base_profile and base_profile::comp,
+ * src/pseq.h:65-113), built on the GPU from the member ids: one node for column 0 and one per occupied column,
+ * a chain; per node the match term of every query iupac mask.  Arguments, limits and refusals as for
+ * sina_hip_align_families (1..128 members, every id in the store, references uploaded first, width at most
+ * 524288); a profile of more than 65535 nodes fails the call like an oversized DAG.  p->weights must be NULL / 0
+ * (scoring_scheme_profile takes no positional weights), p->fs_weight is ignored.  out / out_pos are byte for byte
+ * what sina_hip_align_graphs returns for the same families given as node_score16 / self_score16 tables.
+ * One input is outside that promise, as it is outside the reference's arithmetic: a column in which EVERY member
+ * has a base without any of the four base bits has no points at all, its shares are 0 / 0, and the NaN the device
+ * writes there need not have the bit pattern of the host's (both are NaN; reference stores hold no such bases). */
+int sina_hip_align_profiles(sina_hip_ctx *ctx, const uint32_t *fam_ids, const uint64_t *fam_off,
+                            uint32_t nq, const uint8_t *qmask, const uint64_t *qoff,
+                            const sina_hip_align_params *p, sina_hip_align_out *out,
+                            uint32_t *out_pos);
+
 /* Test hook: DP planes of ONE query for bit-exact comparison with the oracle.
  * tb_vm/tb_vs: [N*L] value_midx / value_sidx; value: [N*L] float (may be NULL).
  * prune: 0 = every row of every strip is swept (the planes are the reference's cell for cell), 1 = the launch as
@@ -293,12 +309,22 @@ int sina_hip_debug_family_graph(sina_hip_ctx *ctx, const uint32_t *fam_ids, uint
                                 uint32_t *succ_minpos, uint8_t *sink, uint32_t *spill_idx, uint32_t cap_nodes,
                                 uint32_t cap_edges);
 
+/* Test hook: the profile the GPU builds for ONE family (ids into the uploaded store, in family order), for
+ * comparison with pseq (src/pseq.cpp) and base_profile::comp (src/pseq.h:100-113): the nodes' columns, the
+ * [n_nodes][16] table of match terms (entry 0 of a row: +inf) and the 16 self-comparison terms.  match,
+ * mismatch, gap, gap_ext are the SCHEME's arguments (-match_score, -mismatch_score, pen_gap, pen_gapext,
+ * src/align.cpp:428-433).  The node counters of up to 6144 nodes are in LDS at a time (fewer for alignments of
+ * more than ~300 000 columns); a longer profile is swept in several tiles. */
+int sina_hip_debug_family_profile(sina_hip_ctx *ctx, const uint32_t *fam_ids, uint32_t F, float match,
+                                  float mismatch, float gap, float gap_ext, uint32_t *n_nodes, uint32_t *pos,
+                                  float *score16, float *self16, uint32_t cap_nodes);
+
 /* Cumulative statistics of this context and its forks since sina_hip_init (callers take
  * differences); kernel times come from HIP events on the context stream. */
 typedef struct sina_hip_stats {
     double dp_ms;          /* mesh DP fill kernel(s)                  */
     double backtrack_ms;   /* backtrack walk kernel                   */
-    double graph_ms;       /* device DAG build                        */
+    double graph_ms;       /* device DAG build, device profile build  */
     double kmer_count_ms;  /* k-mer count kernel                      */
     double kmer_select_ms; /* top-k select kernel                     */
     uint64_t dp_cells;     /* sum of N*L over the batch               */
@@ -312,7 +338,7 @@ typedef struct sina_hip_stats {
     double dp_busy_ms;       /* time during which a DP kernel was resident: dp_ms minus the time a launch shared
                                 the device with the launch before it (a DP launch starts when its predecessor
                                 has dispatched its last workgroup, not when it has ended)                     */
-    uint64_t dags_built;     /* family DAGs built on the device ...                                             */
+    uint64_t dags_built;     /* family DAGs -- and family profiles (sina_hip_align_profiles) -- built on the device ... */
     uint64_t dags_used;      /* ... and queries aligned against them (queries with the same ordered family share one) */
     /* Certified row skip of the DP kernel (the reference fills every cell, src/mesh.h:512-528; here a row of a
      * 512-column strip whose every input provably exceeds what any path ending at the optimum can hold is not
@@ -327,8 +353,9 @@ typedef struct sina_hip_stats {
     uint64_t dp_full_sweeps;     /* ... and whose second did too (swept in full)                                 */
     double dp_prune_rho;         /* gauge: the guess (optimum / bound on the whole gain) the next launch starts with */
     uint64_t graph_bytes;        /* device DAG build, algorithmic bytes: the families' packed bases read once, the DAGs
-                                    (row records, columns, row-skip bounds, predecessor lists) written once          */
-    uint32_t graph_launches, kmer_queries; /* DAG-build launches; queries searched by the k-mer count kernel           */
+                                    (row records, columns, row-skip bounds, predecessor lists) written once; a device
+                                    profile build counts the same way (its nodes carry 64 bytes of match terms each) */
+    uint32_t graph_launches, kmer_queries; /* DAG-build and profile-build launches; queries searched by the k-mer count kernel */
     double scout_ms;             /* the scout pass (a bound on the optimum per query from a banded sweep, one lane per
                                     query): launch to end, on the context's own stream beside other batches' kernels    */
     uint32_t scout_launches, pad_;

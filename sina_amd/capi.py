@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "sina_hip_upload_refs", "sina_hip_build_index", "sina_hip_download_index", "sina_hip_upload_index", "sina_hip_store_view_get",
     "sina_hip_store_alloc_like", "sina_hip_kmer_topk", "sina_hip_kmer_scores", "sina_hip_compare",
     "sina_hip_align_params_default", "sina_hip_staged_out_pos", "sina_hip_align_graphs", "sina_hip_align_families",
+    "sina_hip_align_profiles", "sina_hip_debug_family_profile",
     "sina_hip_debug_mesh", "sina_hip_debug_family_graph", "sina_hip_debug_dp_info", "sina_hip_debug_rgain", "sina_hip_get_stats",
 ]
 
@@ -123,6 +124,9 @@ def load():
                                         C.POINTER(AlignOut), u32p]
     L.sina_hip_align_families.argtypes = [vp, u32p, u64p, C.c_uint32, u8p, u64p, C.POINTER(AlignParams),
                                           C.POINTER(AlignOut), u32p]
+    L.sina_hip_align_profiles.argtypes = L.sina_hip_align_families.argtypes
+    L.sina_hip_debug_family_profile.argtypes = [vp, u32p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, u32p, u32p,
+                                                f32p, f32p, C.c_uint32]
     L.sina_hip_debug_mesh.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
                                       u32p, u32p, f32p, C.c_int]
     L.sina_hip_debug_family_graph.argtypes = [vp, u32p, C.c_uint32, C.c_float, C.c_uint32, u32p, u32p, u32p, u8p,
@@ -321,6 +325,35 @@ class Context:
                                                    _ptr(qmask, u8p), _ptr(qoff, u64p), C.byref(params),
                                                    out.ctypes.data_as(C.POINTER(AlignOut)), _ptr(pos, u32p)))
         return out, pos
+
+    def align_profiles(self, fam_ids, fam_off, qmask, qoff, params=None):
+        """--fs-no-graph: like align_families, the families as profiles built on the device."""
+        params = params or self.params()
+        fam_ids = _c(fam_ids, np.uint32)
+        fam_off = _c(fam_off, np.uint64)
+        qmask = _c(qmask, np.uint8)
+        qoff = _c(qoff, np.uint64)
+        nq = len(qoff) - 1
+        out = np.zeros(nq, ALIGN_OUT_DTYPE)
+        pos = np.zeros(max(len(qmask), 1), np.uint32)
+        self._check(self.L.sina_hip_align_profiles(self.h, _ptr(fam_ids, u32p), _ptr(fam_off, u64p), nq,
+                                                   _ptr(qmask, u8p), _ptr(qoff, u64p), C.byref(params),
+                                                   out.ctypes.data_as(C.POINTER(AlignOut)), _ptr(pos, u32p)))
+        return out, pos
+
+    def debug_family_profile(self, fam_ids, match, mismatch, gap, gap_ext):
+        """The profile the device builds for ONE family: (columns [n], match terms [n, 16], self terms [16]); the four
+        numbers are the scheme's (-match_score, -mismatch_score, pen_gap, pen_gapext)."""
+        fam_ids = _c(fam_ids, np.uint32)
+        cap = 65536
+        nn = C.c_uint32()
+        pos = np.zeros(cap, np.uint32)
+        sc = np.zeros((cap, 16), np.float32)
+        own = np.zeros(16, np.float32)
+        self._check(self.L.sina_hip_debug_family_profile(self.h, _ptr(fam_ids, u32p), len(fam_ids), match, mismatch, gap,
+                                                         gap_ext, C.byref(nn), _ptr(pos, u32p), _ptr(sc, f32p),
+                                                         _ptr(own, f32p), cap))
+        return pos[:nn.value].copy(), sc[:nn.value].copy(), own
 
     def debug_mesh(self, gb, qmask, params=None, want_value=True, prune=False):
         """DP planes of ONE query.  prune=False (default): every row of every strip is swept, the planes are

@@ -130,6 +130,7 @@ struct sina_hip_ctx {
     uint64_t out_pos_base = 0;
     sina_hip::HostBuf h_stage[12];       // pinned staging of the per-batch uploads / downloads (sina_hip::upload)
     float wtab_fs_weight = NAN;  // fs_weight the device weight table was computed for
+    uint32_t prof_ncap = 0;      // nodes per profile the profile builds (profile_build.hip) size their arrays for: the largest seen so far
 
     size_t lds_budget = 0;  // LDS per DP workgroup; 0 = what keeps the register-limited occupancy (dp_default_lds_budget)
 
@@ -168,7 +169,8 @@ struct sina_hip_ctx {
     int prewarm(int kind) {
         sina_hip::DevBuf *search[] = {&k_qoff, &k_scores, &k_out_ids, &k_out_scores, &k_out_n, &k_tmp0, &k_tmp1, &k_tmp2, &qmask};
         sina_hip::DevBuf *align[] = {&qd, &order, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &edge, &res, &weights, &out,
-                                     &out_pos, &g_fam_ids, &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &rgain, &scout, &scout_u};
+                                     &out_pos, &g_fam_ids, &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &rgain, &scout, &scout_u,
+                                     &prof16, &self16};
         sina_hip::DevBuf *compare[] = {&s_qab, &s_qoff, &s_cand, &s_coff, &s_out};
         sina_hip::DevBuf **list = kind == 0 ? search : (kind == 1 ? align : compare);
         const size_t n = kind == 0 ? sizeof search / sizeof *search : (kind == 1 ? sizeof align / sizeof *align : sizeof compare / sizeof *compare);
@@ -564,6 +566,28 @@ struct heavy_launch {
     }
     ~heavy_launch() { leave(); }
 };
+}  // namespace sina_hip
+
+namespace sina_hip {
+// ---- alignment against device-built templates: sina_hip_align_families (the family as a DAG, graph_build.hip) and
+// sina_hip_align_profiles (the family as a profile, profile_build.hip) differ in the builder only
+constexpr int kFamilyMax = 128;  // members of a family the device builders take (their per-member LDS records)
+constexpr int kBuiltWords = 8;   // u32 words a builder reports per family (BuiltGraphs::sizes)
+// What a builder left in the context's rec / node_pos / succ_minpos / pred (/ rgain, prof16) buffers for the n distinct
+// families of a chunk: family u's node arrays start at u * ncap, its predecessor entries at pred_off[u].
+struct BuiltGraphs {
+    uint32_t ncap = 0;
+    std::vector<uint64_t> pred_off;  // per family, into c->pred
+    std::vector<uint32_t> sizes;     // per family: kBuiltWords words -- N, raw edge entries, n_spill, status, first sink row, gmin
+};
+// Builds the templates of families q0 .. q0 + n - 1 (fam_off is absolute); pp: the row skip the launches will run with
+using family_builder = int (*)(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t q0, uint32_t n,
+                               const sina_hip_align_params *p, int W, const PrunePlan &pp, BuiltGraphs *bg);
+// The launch loop both entry points share (graph_build.hip): argument checks, one build per DISTINCT ordered family of a
+// chunk, DP launches in sub-ranges under the trace-back budget.  `who` names the entry point in error messages.
+int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build, bool profile_batch, const uint32_t *fam_ids,
+                         const uint64_t *fam_off, uint32_t nq, const uint8_t *qmask, const uint64_t *qoff,
+                         const sina_hip_align_params *p, sina_hip_align_out *out, uint32_t *out_pos);
 }  // namespace sina_hip
 
 // publishes the context's scratch capacities when an API call ends (see sina_hip_store::cap_hint)

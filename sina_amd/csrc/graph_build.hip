@@ -53,8 +53,8 @@ namespace {
 #endif
 constexpr int kGT = SINA_GRAPH_THREADS;  // threads per workgroup (the phases are latency-bound: more loads in flight per LDS byte)
 constexpr uint32_t kNoPrev = 0xFFFFu;
-constexpr int kMaxFam = 128;
-constexpr int kSz = 8;  // u32 words the kernel reports per query (GraphArgs::sizes)
+constexpr int kMaxFam = kFamilyMax;
+constexpr int kSz = kBuiltWords;  // u32 words the kernel reports per query (GraphArgs::sizes)
 #ifndef SINA_GRAPH_KTC
 #define SINA_GRAPH_KTC 128  // (a multiple of 64: a wave takes 64 consecutive entry slots of one member)
 #endif
@@ -742,12 +742,6 @@ using namespace sina_hip;
 
 namespace {
 
-struct BuiltGraphs {
-    uint32_t ncap = 0;
-    std::vector<uint64_t> pred_off;  // per query, into c->pred
-    std::vector<uint32_t> sizes;     // per query: kSz words -- N, raw edge entries, n_spill, status, first sink row
-};
-
 // Builds the DAGs of bq families (fam_off is absolute, first family = q0) into the context's
 // rec / node_pos / succ_minpos / pred buffers; grows the per-query caps and retries on overflow.
 int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t q0,
@@ -864,27 +858,38 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
     return 0;
 }
 
+// the DAG builder behind sina_hip_align_families
+int build_graphs_for_launch(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t q0, uint32_t n,
+                            const sina_hip_align_params *p, int W, const PrunePlan &pp, BuiltGraphs *bg) {
+    return build_family_graphs(c, fam_ids, fam_off, q0, n, p->fs_weight, W, bg, p->insertion == SINA_INSERTION_FORBID,
+                               pp.on ? pp.kappa64 : 0.f);
+}
+
 }  // namespace
 
-extern "C" {
+namespace sina_hip {
 
-int sina_hip_align_families(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t nq,
-                            const uint8_t *qmask, const uint64_t *qoff, const sina_hip_align_params *p,
-                            sina_hip_align_out *out, uint32_t *out_pos) {
+int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build, bool profile_batch, const uint32_t *fam_ids,
+                         const uint64_t *fam_off, uint32_t nq, const uint8_t *qmask, const uint64_t *qoff,
+                         const sina_hip_align_params *p, sina_hip_align_out *out, uint32_t *out_pos) {
+    const std::string w(who);
     if (!c || !fam_ids || !fam_off || !qmask || !qoff || !p || !out)
-        SH_FAIL("align_families: null argument");
+        SH_FAIL(w + ": null argument");
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
-    if (!c->st->have_refs) SH_FAIL("align_families: upload references first");
+    if (!c->st->have_refs) SH_FAIL(w + ": upload references first");
     if (nq == 0) return 0;
     SH_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    if (c->st->width > 524288u) SH_FAIL("align_families: alignment wider than 524288 columns (use align_graphs)");
+    if (c->st->width > 524288u) SH_FAIL(w + ": alignment wider than 524288 columns (use align_graphs)");
+    // (scoring_scheme_profile takes no positional weights, src/align.cpp:428-433: refused like a profile batch of align_graphs)
+    if (profile_batch && p->weights != nullptr && p->n_weights > 0)
+        SH_FAIL(w + ": a profile batch takes no positional weights (scoring_scheme_profile)");
     uint32_t maxL = 0;
     for (uint32_t q = 0; q < nq; q++) {
         const uint64_t L = qoff[q + 1] - qoff[q], F = fam_off[q + 1] - fam_off[q];
-        if (L == 0 || L > 65535) SH_FAIL("align_families: query length must be in 1..65535");
-        if (F == 0 || F > (uint64_t)kMaxFam) SH_FAIL("align_families: family size must be in 1..128");
+        if (L == 0 || L > 65535) SH_FAIL(w + ": query length must be in 1..65535");
+        if (F == 0 || F > (uint64_t)kMaxFam) SH_FAIL(w + ": family size must be in 1..128");
         maxL = std::max<uint32_t>(maxL, (uint32_t)L);
     }
     DpPlan pl;
@@ -965,11 +970,12 @@ int sina_hip_align_families(sina_hip_ctx *c, const uint32_t *fam_ids, const uint
         } else {
             for (uint32_t q = 0; q < bq; q++) dag_of[q] = q;
         }
-        // (certified row skip of the DP kernel: the DAG build adds every node's bound on the gain still to come)
-        PrunePlan pp = prune_plan(p, (float)(1.0 / (double)(p->fs_weight + 1) + (double)p->fs_weight), p->fs_weight >= 0.f ? 0.f : -1.f, maxL, false);
-        if (build_family_graphs(c, b_ids, b_off, b_q0, n_dags, p->fs_weight, pl.W, &bg, p->insertion == SINA_INSERTION_FORBID,
-                                pp.on ? pp.kappa64 : 0.f))
-            return 1;
+        // (certified row skip of the DP kernel: the DAG build adds every node's bound on the gain still to come; a
+        // profile launch runs without it and without the scout)
+        PrunePlan pp;
+        if (!profile_batch)
+            pp = prune_plan(p, (float)(1.0 / (double)(p->fs_weight + 1) + (double)p->fs_weight), p->fs_weight >= 0.f ? 0.f : -1.f, maxL, false);
+        if (build(c, b_ids, b_off, b_q0, n_dags, p, pl.W, pp, &bg)) return 1;
         {
             std::lock_guard<std::mutex> slk(c->st->stats_mu);
             c->st->stats.dags_built += n_dags;
@@ -1023,15 +1029,25 @@ int sina_hip_align_families(sina_hip_ctx *c, const uint32_t *fam_ids, const uint
             if (c->qd.reserve(sizeof(QDesc) * rq) || c->qmask.reserve(std::max<uint64_t>(nqm, 1))) return 1;
             if (upload(c, 5, c->qd.p, qd.data(), sizeof(QDesc) * rq, s) || upload(c, 6, c->qmask.p, qmask + qbase, nqm, s))
                 return 1;
-            c->profile_batch = false;  // (device-built DAGs: never a profile)
+            c->profile_batch = profile_batch;  // (the DP reads the builder's prof16, the walk the entry point's self16)
             c->out_pos_base = qbase - qoff[0];
             if (run_dp_device(c, pl, qd.data(), rq, (uint64_t)n_dags * bg.ncap, tbc, sprows, cells, nqm, p, c->st->width,
-                              out + q0 + r0, out_pos ? out_pos + qbase : nullptr, false, pp, chain_ref.data()))
+                              out + q0 + r0, out_pos ? out_pos + qbase : nullptr, false, pp, profile_batch ? nullptr : chain_ref.data()))
                 return 1;
             r0 = r1;
         }
     }
     return 0;
+}
+
+}  // namespace sina_hip
+
+extern "C" {
+
+int sina_hip_align_families(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t nq,
+                            const uint8_t *qmask, const uint64_t *qoff, const sina_hip_align_params *p,
+                            sina_hip_align_out *out, uint32_t *out_pos) {
+    return align_family_batches(c, "align_families", build_graphs_for_launch, false, fam_ids, fam_off, nq, qmask, qoff, p, out, out_pos);
 }
 
 #ifdef SINA_DP_PROFILE

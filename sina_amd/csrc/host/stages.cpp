@@ -1572,6 +1572,10 @@ static aligner::options al_defaults() {  // src/align.cpp:231-274
     o.gap_ext_penalty = 2.0f;
     o.debug_graph = o.write_used_rels = o.use_subst_matrix = false;
     o.device_graph = true;  // family DAGs are built on the GPU (sina_hip_align_families)
+    // --fs-no-graph profiles are built on the GPU (sina_hip_align_profiles) only on request: the device route gives the
+    // host route's bytes, but the two have not been timed against each other yet (tools/perf_profile.py), so the
+    // route that has always been taken stays the default
+    o.device_profile = false;
     return o;
 }
 static aligner::options &al_opts() {
@@ -1610,6 +1614,7 @@ void aligner::set_option(const std::string &name, const std::string &value) {
     else if (name == "use-subst-matrix" || name == "debug-graph") {
         if (to_bool(value)) throw std::logic_error("aligner: --" + name + " is outside the accelerated path");
     } else if (name == "device-graph") o.device_graph = to_bool(value);
+    else if (name == "device-profile") o.device_profile = to_bool(value);
     else if (name == "db") o.database = value;
     else throw std::logic_error("aligner: unknown option " + name);
 }
@@ -1849,12 +1854,14 @@ void aligner::operator()(std::vector<tray> &batch) {
     // twin of that kernel (build_family_graph) and handed over as a graph (sina_hip_align_graphs)
     constexpr size_t kDeviceFamilyMax = 128;
     std::map<std::pair<std::vector<float>, bool>, std::vector<size_t>> groups;
-    // (--fs-no-graph: the family as a profile, built by the host; scoring_scheme_profile takes no positional
-    // weights, src/align.cpp:428-433)
+    // (--fs-no-graph: the family as a profile, built by build_family_profile on the host or -- with device-profile on,
+    // under the conditions a DAG is built on the device -- by sina_hip_align_profiles; scoring_scheme_profile takes no
+    // positional weights, src/align.cpp:428-433)
     for (size_t i = 0; i < batch.size(); i++)
         if (need_dp[i]) {
-            if (o.fs_no_graph) groups[{std::vector<float>(), false}].push_back(i);
-            else groups[{batch[i].astats->getWeights(), o.device_graph && jobs[i].family_size() <= kDeviceFamilyMax}].push_back(i);
+            const bool on_device = o.device_graph && jobs[i].family_size() <= kDeviceFamilyMax;
+            if (o.fs_no_graph) groups[{std::vector<float>(), on_device && o.device_profile}].push_back(i);
+            else groups[{batch[i].astats->getWeights(), on_device}].push_back(i);
         }
 
     std::shared_ptr<reference_store> store;
@@ -1966,10 +1973,17 @@ void aligner::operator()(std::vector<tray> &batch) {
                 for (size_t y = 0; y < jb.family_size(); y++) fids[foff[x] + y] = store->id_of(jb.member(y));
             });
             width = store->getAlignmentWidth();
-            ph.reset(), ph.reset(new scoped_phase("al.align_families(C-ABI)"));  // (the old phase ends first: the new one names the pool jobs)
-            hip_check(sina_hip_align_families(ctx, fids.data(), foff.data(), (uint32_t)nq, qmask, qoff.data(),
-                                              &p, out.data(), out_pos),
-                      "align_families");
+            if (o.fs_no_graph) {
+                ph.reset(), ph.reset(new scoped_phase("al.align_profiles(C-ABI)"));  // (the old phase ends first: the new one names the pool jobs)
+                hip_check(sina_hip_align_profiles(ctx, fids.data(), foff.data(), (uint32_t)nq, qmask, qoff.data(),
+                                                  &p, out.data(), out_pos),
+                          "align_profiles");
+            } else {
+                ph.reset(), ph.reset(new scoped_phase("al.align_families(C-ABI)"));  // (the old phase ends first: the new one names the pool jobs)
+                hip_check(sina_hip_align_families(ctx, fids.data(), foff.data(), (uint32_t)nq, qmask, qoff.data(),
+                                                  &p, out.data(), out_pos),
+                          "align_families");
+            }
         } else {
             std::vector<host_graph> gs(nq);
             ph.reset(), ph.reset(new scoped_phase("al.host_graph_build"));  // (the old phase ends first: the new one names the pool jobs)
