@@ -49,7 +49,7 @@ def test_compare_counts_equal_traverse(oracle, gpu_ctx, filter_lc):
     gpu_ctx.upload_refs(refs.ab, refs.off, refs.width)
     qs = _aligned_queries(refs, 9, 402, lower_rate=0.15, amb_rate=0.03)
     # one query without any upper-case base in the middle of a run, one fully lower case at both ends
-    qs[3] = qs[3] | np.uint32(0)
+    qs[3] |= np.uint32(0x10 << 24)
     qs[4][:7] |= np.uint32(0x10 << 24)
     qs[4][-5:] |= np.uint32(0x10 << 24)
     rng = np.random.default_rng(403)
@@ -141,7 +141,34 @@ def test_search_stage_option_fuzz(oracle, seed):
     _search_stage_case(oracle, 420, sopts, o, n_queries=10)
 
 
-def _search_stage_case(oracle, n_refs, sopts, oopts, n_queries=24):
+def _fragments(refs, lengths, seed):
+    """Pieces of full-length references with 3 % substitutions: queries that cover part of a reference."""
+    rng = np.random.default_rng(seed)
+    full = np.flatnonzero(np.diff(refs.off) >= 280)
+    out = []
+    for n in lengths:
+        m = ((refs.seq(int(full[int(rng.integers(len(full)))])) >> 24) & 0xff).astype(np.uint8)
+        a = int(rng.integers(0, len(m) - n + 1))
+        piece = m[a:a + n].copy()
+        sub = rng.random(n) < 0.03
+        piece[sub] = rng.choice([1, 2, 4, 8], size=int(sub.sum()))
+        out.append(piece)
+    return out
+
+
+JC_FRAGMENT_LENGTHS = (100, 120, 140, 160, 110, 130, 150, 105, 125, 145, 155, 160)
+
+
+def test_search_stage_with_jukes_cantor_correction(oracle):
+    """--search-correction jc through the stage.  Jukes-Cantor of an identity above 0.75 is NaN and the reference leaves
+    the order of NaN scores open, so the queries are fragments of 100 to 160 bases scored over the target (300-base
+    references: identities of about a half); the case asserts that no comparison of any query with any reference is
+    NaN, and then asks for the oracle's ids, score bits, nearest_slv and LCA like every other case."""
+    _search_stage_case(oracle, 420, {"search-correction": "jc", "search-cover": "target", "search-min-sim": 0.0},
+                       dict(dist="jc", cover="target", min_sim=0.0), fragments=JC_FRAGMENT_LENGTHS)
+
+
+def _search_stage_case(oracle, n_refs, sopts, oopts, n_queries=24, fragments=None):
     refs = synth.make_refs(n_refs, length=300, width=3000, seed=451, amb_rate=0.01, lower_rate=0.03)
     cs = util.cseqs_from_refs(refs)
     idx = oracle.Index(cs, k=10)
@@ -159,6 +186,8 @@ def _search_stage_case(oracle, n_refs, sopts, oopts, n_queries=24):
     # three more queries that are exact pieces of references (contained: --search-ignore-super matters)
     extra = [((refs.seq(i) >> 24) & 0xff).astype(np.uint8)[a:b] for i, a, b in ((5, 10, 250), (77, 0, 200), (300, 40, 290))]
     masks = [qs.seq(i) for i in range(qs.n)] + extra
+    if fragments is not None:
+        masks = _fragments(refs, fragments, 453)
     off = np.zeros(len(masks) + 1, np.int64)
     off[1:] = np.cumsum([len(m) for m in masks])
     qs = synth.QuerySet(mask=np.concatenate(masks), off=off, src=np.zeros(len(masks), np.int64))
@@ -180,6 +209,10 @@ def _search_stage_case(oracle, n_refs, sopts, oopts, n_queries=24):
             assert got["search_ids"] is None
             continue
         aligned = po.Cseq.from_packed("query%d" % qi, al["packed"], al["width"])
+        if oopts.get("dist") == "jc":
+            every = [po.compare(aligned, c, oopts.get("iupac", "optimistic"), "jc", oopts.get("cover", "query"),
+                                bool(oopts.get("filter_lc", 0))) for c in cs]
+            assert not np.isnan(every).any(), qi
         want_ids, want_sc, _ = oracle.search(idx, aligned, so)
         assert (got["search_ids"] == want_ids).all(), qi
         assert (util.f32_bits(got["search_scores"]) == util.f32_bits(want_sc)).all(), qi
