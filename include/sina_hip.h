@@ -35,6 +35,11 @@ typedef struct sina_hip_ctx sina_hip_ctx;
 
 int sina_hip_abi_version(void);
 const char *sina_hip_last_error(void);
+/* 1 if the calling thread's last FAILED call was refused because an input exceeds one of the documented limits of
+ * the fast path -- sina_hip_align_graphs: nodes, predecessors, query length, spill rows; sina_hip_align_families:
+ * too wide, spill rows, exceeds device limits; sina_hip_align_profiles: too wide, exceeds device limits --, else 0.
+ * Thread-local like sina_hip_last_error.  Such an input is valid: sina_hip_align_graphs_any takes it. */
+int sina_hip_last_error_is_limit(void);
 
 /* Creates a context on HIP device `device` (own stream). */
 int sina_hip_init(int device, sina_hip_ctx **ctx);
@@ -185,9 +190,10 @@ const uint32_t *sina_hip_staged_out_pos(sina_hip_ctx *ctx);
 #define SINA_HIP_MAX_QUERY_LEN 10240u
 
 /* A batch of family DAGs in CSR form (node id == topological rank == mesh row).
- * All arrays are concatenated over the nq queries of the batch.  Limits (the call fails, nothing is
- * truncated): at most 65535 nodes per DAG, at most 255 predecessors per node, every predecessor id
- * smaller than its node's id, queries of 1..SINA_HIP_MAX_QUERY_LEN bases. */
+ * All arrays are concatenated over the nq queries of the batch.  Limits of sina_hip_align_graphs (the call fails,
+ * nothing is truncated; sina_hip_align_graphs_any has none of the first three): at most 65535 nodes per DAG, at most
+ * 255 predecessors per node, queries of 1..SINA_HIP_MAX_QUERY_LEN bases; every predecessor id smaller than its
+ * node's id. */
 typedef struct sina_hip_graph_batch {
     uint32_t nq;
     const uint64_t *node_off;  /* [nq+1] into the node arrays                      */
@@ -249,6 +255,24 @@ int sina_hip_align_graphs(sina_hip_ctx *ctx, const sina_hip_graph_batch *g, cons
                           const uint64_t *qoff, const sina_hip_align_params *p,
                           sina_hip_align_out *out, uint32_t *out_pos);
 
+/* Same arguments and result layout (out_pos == NULL and sina_hip_staged_out_pos included), without the limits of the
+ * fast path: any number of nodes, any number of predecessors per node, any query of at least one base -- what the
+ * reference takes (src/mesh.h:76,119-121).  Routing is per query: a query the fast path can take runs there, its
+ * results bit for bit those of sina_hip_align_graphs; the others -- more than 65535 nodes, a node of more than 255
+ * predecessors, more than SINA_HIP_MAX_QUERY_LEN bases, more rows with far-away successors than the fast kernel keeps
+ * -- go through the wide kernel: the reference's mesh, 28 bytes per cell (--insertion=forbid: 32) in device memory,
+ * one workgroup per query.  Those queries are never assembled (assembled = 0 whatever p->assemble says).  The wide
+ * kernel's launches hold at most SINA_HIP_WIDE_CELLS cells (of a diagonal-major mesh: (N + L - 1) * min(N, L) per
+ * query, 16 GiB of planes at most); a single query beyond that fails the call with a message that names the bytes
+ * it needs, nothing is truncated.  Malformed input -- a predecessor id not smaller than its node's, pred_off not
+ * ascending -- is an error as before. */
+#define SINA_HIP_WIDE_CELLS ((uint64_t)1 << 29)
+int sina_hip_align_graphs_any(sina_hip_ctx *ctx, const sina_hip_graph_batch *g, const uint8_t *qmask,
+                              const uint64_t *qoff, const sina_hip_align_params *p,
+                              sina_hip_align_out *out, uint32_t *out_pos);
+/* Number of queries the wide kernel has aligned on this context since sina_hip_init / sina_hip_fork. */
+int sina_hip_wide_queries(sina_hip_ctx *ctx, uint64_t *n);
+
 /* Same, but the DAGs are built on the GPU from family member ids into the
  * uploaded reference store (order of ids = family order = mseq input order).
  *   fam_ids/fam_off : concatenated reference ids, offsets [nq+1]
@@ -281,6 +305,12 @@ int sina_hip_align_profiles(sina_hip_ctx *ctx, const uint32_t *fam_ids, const ui
 int sina_hip_debug_mesh(sina_hip_ctx *ctx, const sina_hip_graph_batch *g, const uint8_t *qmask,
                         uint32_t qlen, const sina_hip_align_params *p, uint32_t *tb_vm,
                         uint32_t *tb_vs, float *value, int prune);
+
+/* Test hook, the twin of sina_hip_debug_mesh for the wide kernel: its planes of ONE query (any size the wide path's
+ * budget holds), [N*L] row-major; value may be NULL. */
+int sina_hip_debug_mesh_wide(sina_hip_ctx *ctx, const sina_hip_graph_batch *g, const uint8_t *qmask,
+                             uint32_t qlen, const sina_hip_align_params *p, uint32_t *tb_vm,
+                             uint32_t *tb_vs, float *value);
 
 /* Test hooks for the certified row skip: what the DP kernel reported for query q of the context's LAST launch
  * (attempts 0: that launch swept everything), and the first n entries of the per-node bound R(m) the last launch /

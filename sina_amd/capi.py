@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "sina_hip_align_params_default", "sina_hip_staged_out_pos", "sina_hip_align_graphs", "sina_hip_align_families",
     "sina_hip_align_profiles", "sina_hip_debug_family_profile",
     "sina_hip_debug_mesh", "sina_hip_debug_family_graph", "sina_hip_debug_dp_info", "sina_hip_debug_rgain", "sina_hip_get_stats",
+    "sina_hip_align_graphs_any", "sina_hip_debug_mesh_wide", "sina_hip_wide_queries", "sina_hip_last_error_is_limit",
 ]
 
 
@@ -122,6 +123,11 @@ def load():
     L.sina_hip_align_params_default.restype = None
     L.sina_hip_align_graphs.argtypes = [vp, C.POINTER(GraphBatch), u8p, u64p, C.POINTER(AlignParams),
                                         C.POINTER(AlignOut), u32p]
+    L.sina_hip_align_graphs_any.argtypes = L.sina_hip_align_graphs.argtypes
+    L.sina_hip_wide_queries.argtypes = [vp, u64p]
+    L.sina_hip_last_error_is_limit.restype = C.c_int
+    L.sina_hip_debug_mesh_wide.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
+                                           u32p, u32p, f32p]
     L.sina_hip_align_families.argtypes = [vp, u32p, u64p, C.c_uint32, u8p, u64p, C.POINTER(AlignParams),
                                           C.POINTER(AlignOut), u32p]
     L.sina_hip_align_profiles.argtypes = L.sina_hip_align_families.argtypes
@@ -298,6 +304,46 @@ class Context:
                                                  C.byref(params), out.ctypes.data_as(C.POINTER(AlignOut)),
                                                  _ptr(pos, u32p)))
         return out, pos
+
+    def align_graphs_any(self, gb, qmask, qoff, params=None, staged=False):
+        """align_graphs without the fast path's limits: a query the fast kernel cannot take goes through the wide
+        kernel.  staged: pass out_pos == NULL and read the columns from the context's staging buffer."""
+        params = params or self.params()
+        qmask = _c(qmask, np.uint8)
+        qoff = _c(qoff, np.uint64)
+        out = np.zeros(gb.nq, ALIGN_OUT_DTYPE)
+        pos = np.zeros(max(len(qmask), 1), np.uint32)
+        self._check(self.L.sina_hip_align_graphs_any(self.h, C.byref(gb), _ptr(qmask, u8p), _ptr(qoff, u64p),
+                                                     C.byref(params), out.ctypes.data_as(C.POINTER(AlignOut)),
+                                                     None if staged else _ptr(pos, u32p)))
+        if staged:
+            n = int(qoff[-1] - qoff[0])
+            pos[:n] = np.ctypeslib.as_array(self.L.sina_hip_staged_out_pos(self.h), shape=(max(n, 1),))[:n]
+        return out, pos
+
+    def wide_queries(self):
+        """Queries the wide kernel has aligned on this context so far."""
+        n = C.c_uint64()
+        self._check(self.L.sina_hip_wide_queries(self.h, C.byref(n)))
+        return int(n.value)
+
+    def last_error_is_limit(self):
+        """True if this thread's last failed call was refused for exceeding a documented limit of the fast path."""
+        return bool(self.L.sina_hip_last_error_is_limit())
+
+    def debug_mesh_wide(self, gb, qmask, params=None, want_value=True):
+        """The wide kernel's planes of ONE query: (value_midx, value_sidx, value), each [N, L]."""
+        params = params or self.params()
+        qmask = _c(qmask, np.uint8)
+        n = int(gb._keep["node_off"][1])
+        L = len(qmask)
+        vm = np.zeros((n, L), np.uint32)
+        vs = np.zeros((n, L), np.uint32)
+        val = np.zeros((n, L), np.float32) if want_value else None
+        self._check(self.L.sina_hip_debug_mesh_wide(self.h, C.byref(gb), _ptr(qmask, u8p), L, C.byref(params),
+                                                    _ptr(vm, u32p), _ptr(vs, u32p),
+                                                    _ptr(val, f32p) if want_value else None))
+        return vm, vs, val
 
     def compare(self, q_ab, q_off, cand_ids, cand_off, iupac=0, filter_lc=False):
         """Search-stage comparison: int32 [n candidates][6] = only_a_overhang, only_b_overhang, only_a,

@@ -11,10 +11,18 @@
 namespace sina_hip {
 
 static thread_local std::string g_last_error;
-void set_error(const std::string &msg) { g_last_error = msg; }
+static thread_local bool g_last_error_is_limit = false;
+void set_error(const std::string &msg) {
+    g_last_error = msg;
+    g_last_error_is_limit = false;
+}
+void set_limit_error(const std::string &msg) {
+    g_last_error = msg;
+    g_last_error_is_limit = true;
+}
 
 int plan_dp(sina_hip_ctx *c, uint32_t maxL, DpPlan *pl) {
-    if (!pick_geom(maxL, &pl->geom)) SH_FAIL("align: query longer than SINA_HIP_MAX_QUERY_LEN bases");
+    if (!pick_geom(maxL, &pl->geom)) SH_FAIL_LIMIT("align: query longer than SINA_HIP_MAX_QUERY_LEN bases");
     const size_t slot = dp_slot_bytes(pl->geom), fixed = dp_fixed_lds_bytes(pl->geom);
     size_t budget = c->lds_budget ? c->lds_budget : dp_default_lds_budget(pl->geom);
     if (budget < fixed + slot) budget = fixed + slot;
@@ -66,8 +74,10 @@ struct HostPrep {
     uint64_t tb_cells = 0, spill_rows = 0, cells = 0;
 };
 
+// spill_q: where a query that needs more than kMaxSpillRows spill rows is reported (sina_hip_align_graphs_any sends
+// that query through the wide kernel)
 static int prep_range(const sina_hip_graph_batch *g, const uint64_t *qoff, uint32_t q0, uint32_t q1, int Lp, int W,
-                       HostPrep *hp, float kappa64) {
+                       HostPrep *hp, float kappa64, uint32_t *spill_q) {
     const uint64_t nbase = g->node_off[q0], ebase = g->edge_off[q0];
     const uint64_t nn = g->node_off[q1] - nbase;
     hp->qd.resize(q1 - q0);
@@ -94,8 +104,10 @@ static int prep_range(const sina_hip_graph_batch *g, const uint64_t *qoff, uint3
         uint4 *rec = hp->rec.data() + d.node_off;
         for (uint32_t m = 0; m < N; m++) {
             // (what the row record and the kernel's topological sweep can represent: fail, do not truncate)
-            if (po[m + 1] < po[m] || po[m + 1] - po[m] > 255u)
-                SH_FAIL("align_graphs: a node has more than 255 predecessors (or pred_off is not ascending)");
+            // (the count is a limit of this path, a descending pred_off is malformed input: same message, different kind)
+            if (po[m + 1] < po[m]) SH_FAIL("align_graphs: a node has more than 255 predecessors (or pred_off is not ascending)");
+            if (po[m + 1] - po[m] > 255u)
+                SH_FAIL_LIMIT("align_graphs: a node has more than 255 predecessors (or pred_off is not ascending)");
             for (uint32_t e = po[m]; e < po[m + 1]; e++)
                 if (g->pred[eo + e] >= m) SH_FAIL("align_graphs: predecessor ids must be smaller than the node's id");
             uint32_t wbits;
@@ -161,7 +173,10 @@ static int prep_range(const sina_hip_graph_batch *g, const uint64_t *qoff, uint3
             }
             rec[m].z |= (first_far << 24) | (std::min(dist, kRecDistFar) << kRecDistShift);
         }
-        if (nsp > kMaxSpillRows) SH_FAIL("align_graphs: too many spill rows for one query");
+        if (nsp > kMaxSpillRows) {
+            if (spill_q) *spill_q = q;
+            SH_FAIL_LIMIT("align_graphs: too many spill rows for one query");
+        }
         // The row-skip bound, as the device DAG build computes it (graph_build.hip step 9): R(m) = the sum, over the
         // columns right of node m's, of the column's best node's gain.  It is a bound only for a DAG laid out like
         // mseq's -- columns ascend with the node ids, every edge leads to a column further right --, which a caller's
@@ -498,22 +513,29 @@ int upload_weights(sina_hip_ctx *c, const sina_hip_align_params *p) {
 
 static bool weighted_scheme(const sina_hip_align_params *p) { return p->weights != nullptr && p->n_weights > 0; }
 
+// [qa, qb): the queries of the batch to align (qa = 0, qb = 0: all of them); every offset of the batch is absolute, the
+// staged columns are laid out for the whole batch.  done_to / spill_q (sina_hip_align_graphs_any): on failure, the
+// queries before *done_to have their results, and *spill_q names the query that needs too many spill rows (if that
+// is why).
 static int align_graphs_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask,
                              const uint64_t *qoff, const sina_hip_align_params *p, sina_hip_align_out *out,
-                             uint32_t *out_pos, float *dbg_value_host, uint32_t *dbg_vm, uint32_t *dbg_vs) {
+                             uint32_t *out_pos, float *dbg_value_host, uint32_t *dbg_vm, uint32_t *dbg_vs,
+                             uint32_t qa = 0, uint32_t qb = 0, uint32_t *done_to = nullptr, uint32_t *spill_q = nullptr) {
     if (!c || !g || !qmask || !qoff || !p || !out) SH_FAIL("align_graphs: null argument");
     const uint32_t nq = g->nq;
     if (nq == 0) return 0;
+    if (qb == 0) qb = nq;
+    if (done_to) *done_to = qa;
     SH_CHECK(hipSetDevice(c->device));
     if (c->h_out_pos.reserve(4 * std::max<uint64_t>(qoff[nq] - qoff[0], 1))) return 1;
     const bool forbid = p->insertion == SINA_INSERTION_FORBID;
     if (forbid && !g->succ_minpos) SH_FAIL("align_graphs: insertion=forbid needs succ_minpos");
     uint32_t maxL = 0;
-    for (uint32_t q = 0; q < nq; q++) {
+    for (uint32_t q = qa; q < qb; q++) {
         const uint64_t L = qoff[q + 1] - qoff[q];
         const uint64_t N = g->node_off[q + 1] - g->node_off[q];
         if (L == 0 || N == 0) SH_FAIL("align_graphs: empty query or graph");
-        if (L > SINA_HIP_MAX_QUERY_LEN || N > 65535) SH_FAIL("align_graphs: query longer than SINA_HIP_MAX_QUERY_LEN bases or DAG of more than 65535 nodes");
+        if (L > SINA_HIP_MAX_QUERY_LEN || N > 65535) SH_FAIL_LIMIT("align_graphs: query longer than SINA_HIP_MAX_QUERY_LEN bases or DAG of more than 65535 nodes");
         maxL = std::max<uint32_t>(maxL, (uint32_t)L);
     }
     DpPlan pl;
@@ -522,9 +544,9 @@ static int align_graphs_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, con
     if (upload_weights(c, p)) return 1;
     float wmax = 0.f, wmin = 0.f;
     if (!g->node_score16 && g->node_weight) {
-        const uint64_t n_all = g->node_off[nq] - g->node_off[0];
+        const uint64_t n_all = g->node_off[qb] - g->node_off[qa];
         for (uint64_t i = 0; i < n_all; i++) {
-            const float w = g->node_weight[g->node_off[0] + i];
+            const float w = g->node_weight[g->node_off[qa] + i];
             if (!(w == w)) wmax = wmin = NAN;  // (a NaN compares false both ways and would slip through: it switches the row skip off)
             if (!(wmax == wmax)) break;
             wmax = (i == 0 || w > wmax) ? w : wmax;
@@ -536,21 +558,21 @@ static int align_graphs_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, con
 
     const uint64_t tb_budget_cells = tb_plane_budget(c) / tb_cell_bytes(forbid);
     HostPrep hp;
-    uint32_t q0 = 0;
-    while (q0 < nq) {
+    uint32_t q0 = qa;
+    while (q0 < qb) {
         // largest sub-batch whose trace-back plane fits the budget
         uint32_t q1 = q0;
         uint64_t cells = 0;
-        while (q1 < nq) {
+        while (q1 < qb) {
             const uint64_t N = g->node_off[q1 + 1] - g->node_off[q1];
             if (q1 > q0 && cells + N * Lp > tb_budget_cells) break;
             cells += N * Lp;
             q1++;
         }
-        q1 = dp_round_range(q0, q1, nq, dp_wave_slots(c, pl.geom.B));
+        q1 = dp_round_range(q0, q1, qb, dp_wave_slots(c, pl.geom.B));
         if (dbg_vm) q1 = q0 + 1;
         c->dbg_planes = dbg_vm != nullptr;
-        if (prep_range(g, qoff, q0, q1, Lp, pl.W, &hp, pp.on ? pp.kappa64 : 0.f)) return 1;
+        if (prep_range(g, qoff, q0, q1, Lp, pl.W, &hp, pp.on ? pp.kappa64 : 0.f, spill_q)) return 1;
         const uint32_t bq = q1 - q0;
         const uint64_t nbase = g->node_off[q0], nn = g->node_off[q1] - nbase;
         const uint64_t ebase = g->edge_off[q0], ne = g->edge_off[q1] - ebase;
@@ -637,8 +659,77 @@ static int align_graphs_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, con
                 }
         }
         q0 = q1;
+        if (done_to) *done_to = q0;
     }
     c->dbg_planes = false;  // (only this call's launches were the debug entry's: a later launch must not clear a plane)
+    return 0;
+}
+
+// sina_hip_align_graphs_any: what is malformed in any path, and which queries only the wide kernel takes by the cheap
+// limits (nodes, bases, predecessors per node; the spill-row limit shows when a fast range is prepared).  Every edge of
+// every query is looked at here, and prep_range looks at a fitting query's edges again: one more pass over the CSR per
+// batch, the price of routing before anything runs on this opt-in path.
+static int classify_any(const sina_hip_graph_batch *g, const uint64_t *qoff, bool all_wide, std::vector<uint8_t> *wide) {
+    wide->assign(g->nq, all_wide ? 1 : 0);
+    for (uint32_t q = 0; q < g->nq; q++) {
+        const uint64_t L = qoff[q + 1] - qoff[q];
+        const uint64_t N = g->node_off[q + 1] - g->node_off[q];
+        if (L == 0 || N == 0) SH_FAIL("align_graphs_any: empty query or graph");
+        if (L > 0xFFFFFFFFull || N > 0xFFFFFFFFull) SH_FAIL("align_graphs_any: more than 2^32 - 1 nodes or bases");
+        // (the wide mesh has (N + L - 1) * min(N, L) cells: kept below 2^63, so that the budget sees the real number)
+        if (N + L - 1 > (1ull << 63) / std::min(N, L)) SH_FAIL("align_graphs_any: a mesh of more than 2^63 cells");
+        if (L > SINA_HIP_MAX_QUERY_LEN || N > 65535) (*wide)[q] = 1;
+        const uint64_t no = g->node_off[q], eo = g->edge_off[q], ne = g->edge_off[q + 1] - eo;
+        const uint32_t *po = g->pred_off + no + q;
+        for (uint64_t m = 0; m < N; m++) {
+            if (po[m + 1] < po[m] || po[m + 1] > ne) SH_FAIL("align_graphs_any: pred_off is not ascending (or leaves the query's edges)");
+            if (po[m + 1] - po[m] > 255u) (*wide)[q] = 1;
+            for (uint32_t e = po[m]; e < po[m + 1]; e++)
+                if (g->pred[eo + e] >= m) SH_FAIL("align_graphs_any: predecessor ids must be smaller than the node's id");
+        }
+    }
+    return 0;
+}
+
+static int align_graphs_any_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask, const uint64_t *qoff,
+                                 const sina_hip_align_params *p, sina_hip_align_out *out, uint32_t *out_pos) {
+    if (!c || !g || !qmask || !qoff || !p || !out) SH_FAIL("align_graphs_any: null argument");
+    const uint32_t nq = g->nq;
+    if (nq == 0) return 0;
+    SH_CHECK(hipSetDevice(c->device));
+    if (p->insertion == SINA_INSERTION_FORBID && !g->succ_minpos) SH_FAIL("align_graphs_any: insertion=forbid needs succ_minpos");
+    if (g->node_score16 != nullptr) {
+        if (!g->self_score16) SH_FAIL("align_graphs_any: node_score16 without self_score16");
+        if (weighted_scheme(p)) SH_FAIL("align_graphs_any: a profile batch takes no positional weights (scoring_scheme_profile)");
+    } else if (!g->node_mask || !g->node_weight) {
+        SH_FAIL("align_graphs_any: null argument");
+    }
+    std::vector<uint8_t> wide;
+    if (classify_any(g, qoff, test_knob("wide") == "1", &wide)) return 1;
+    if (c->h_out_pos.reserve(4 * std::max<uint64_t>(qoff[nq] - qoff[0], 1))) return 1;
+    std::vector<uint32_t> qs;
+    uint32_t q = 0;
+    while (q < nq) {
+        uint32_t e = q;
+        while (e < nq && wide[e] == wide[q]) e++;
+        if (wide[q]) {  // a run of queries for the wide kernel
+            qs.resize(e - q);
+            for (uint32_t i = q; i < e; i++) qs[i - q] = i;
+            if (run_wide(c, g, qmask, qoff, p, qs.data(), e - q, out, out_pos)) return 1;
+            q = e;
+            continue;
+        }
+        // a maximal run of fitting queries through the fast path, unchanged -- up to a query that needs too many
+        // spill rows: the run is split there, that one query goes wide
+        uint32_t done_to = q, spill_q = 0xFFFFFFFFu;
+        if (align_graphs_impl(c, g, qmask, qoff, p, out, out_pos, nullptr, nullptr, nullptr, q, e, &done_to, &spill_q)) {
+            if (spill_q == 0xFFFFFFFFu || spill_q < done_to || spill_q >= e) return 1;
+            wide[spill_q] = 1;
+            q = done_to;  // (the queries before it have their results; [done_to, spill_q) run again as a range of their own)
+            continue;
+        }
+        q = e;
+    }
     return 0;
 }
 
@@ -650,6 +741,7 @@ extern "C" {
 
 int sina_hip_abi_version(void) { return SINA_HIP_ABI_VERSION; }
 const char *sina_hip_last_error(void) { return g_last_error.c_str(); }
+int sina_hip_last_error_is_limit(void) { return g_last_error_is_limit ? 1 : 0; }
 
 // a partly built context is taken apart again when init / fork fails half-way
 static void discard_ctx(sina_hip_ctx *c) {
@@ -839,6 +931,39 @@ int sina_hip_align_graphs(sina_hip_ctx *c, const sina_hip_graph_batch *g, const 
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
     return align_graphs_impl(c, g, qmask, qoff, p, out, out_pos, nullptr, nullptr, nullptr);
+}
+
+int sina_hip_align_graphs_any(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask,
+                              const uint64_t *qoff, const sina_hip_align_params *p, sina_hip_align_out *out,
+                              uint32_t *out_pos) {
+    if (!c) SH_FAIL("align_graphs_any: null ctx");
+    std::lock_guard<std::mutex> lk(c->mu);
+    sina_hip_hint_guard hints(c);
+    return align_graphs_any_impl(c, g, qmask, qoff, p, out, out_pos);
+}
+
+int sina_hip_wide_queries(sina_hip_ctx *c, uint64_t *n) {
+    if (!c || !n) SH_FAIL("wide_queries: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *n = c->wide_queries;
+    return 0;
+}
+
+int sina_hip_debug_mesh_wide(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask, uint32_t qlen,
+                             const sina_hip_align_params *p, uint32_t *tb_vm, uint32_t *tb_vs, float *value) {
+    if (!c || !g || g->nq != 1 || !qmask || !p || !tb_vm || !tb_vs) SH_FAIL("debug_mesh_wide: needs exactly one query");
+    std::lock_guard<std::mutex> lk(c->mu);
+    SH_CHECK(hipSetDevice(c->device));
+    if (p->insertion == SINA_INSERTION_FORBID && !g->succ_minpos) SH_FAIL("debug_mesh_wide: insertion=forbid needs succ_minpos");
+    if (g->node_score16 != nullptr && (!g->self_score16 || weighted_scheme(p)))
+        SH_FAIL("debug_mesh_wide: a profile batch needs self_score16 and takes no positional weights");
+    const uint64_t qoff[2] = {0, qlen};
+    std::vector<uint8_t> wide;
+    if (classify_any(g, qoff, true, &wide)) return 1;
+    if (c->h_out_pos.reserve(4 * std::max<uint64_t>(qlen, 1))) return 1;
+    sina_hip_align_out o;
+    const uint32_t q0 = 0;
+    return run_wide(c, g, qmask, qoff, p, &q0, 1, &o, nullptr, tb_vm, tb_vs, value);
 }
 
 int sina_hip_debug_mesh(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask, uint32_t qlen,

@@ -19,6 +19,8 @@
 namespace sina_hip {
 
 void set_error(const std::string &msg);
+// ... of a call refused because an input exceeds a documented limit of the fast path (sina_hip_last_error_is_limit)
+void set_limit_error(const std::string &msg);
 
 // ---- environment.  What the library reads at run time (all of it listed in INTEGRATION.md):
 //   SINA_HIP_TB_GB, SINA_HIP_TB_PLANES   size / number of the device's trace-back planes (ctx.h)
@@ -27,6 +29,7 @@ void set_error(const std::string &msg);
 //   SINA_HIP_NO_RUNTIME_DEFAULTS         the load-time constructor leaves the process environment alone (api.hip)
 //   SINA_HIP_TRACE_ALLOC                 one line per device / pinned allocation
 //   SINA_HIP_TEST="key=value;..."        test hooks (tests/ only): geom=T,B  generic=1  dense_div=N  lds_kb=N  rho=X  kmer_rows=1  bt_lanes=0/1  scout=0  scout_add=X  scout_set=X
+//                                        wide=1 (every query of sina_hip_align_graphs_any takes the wide kernel)  wide_cells=N (its budget, cells per launch)
 // value of `key` in SINA_HIP_TEST ("" if absent); read every time: tests change it between calls
 inline std::string test_knob(const char *key) {
     const char *e = getenv("SINA_HIP_TEST");
@@ -55,6 +58,12 @@ inline std::string test_knob(const char *key) {
     do {                               \
         ::sina_hip::set_error(msg);    \
         return 1;                      \
+    } while (0)
+
+#define SH_FAIL_LIMIT(msg)                  \
+    do {                                    \
+        ::sina_hip::set_limit_error(msg);   \
+        return 1;                           \
     } while (0)
 
 // Growable device buffer (never shrinks): batches reuse their scratch.

@@ -113,6 +113,10 @@ struct sina_hip_ctx {
     sina_hip::DevBuf qd, order, rec, node_pos, pred, succ_minpos, qmask, spill, edge, res, weights, out, out_pos, dbg;
     sina_hip::DevBuf prof16, self16;  // --fs-no-graph: match-term tables of a profile batch (sina_hip_graph_batch)
     sina_hip::DevBuf rgain;           // per DAG node: bound on the gain still to come (the DP kernel's row skip, common.h)
+    // the wide path (mesh_wide.hip): a launch's inputs, and its mesh -- every cell's fields in HBM; grow-only, apart from
+    // the trace-back pool above, allocated by the first query that needs it
+    sina_hip::DevBuf wide_in, wide_planes;
+    uint64_t wide_queries = 0;        // queries the wide kernel has aligned on this context (sina_hip_wide_queries)
     sina_hip::DevBuf scout, scout_u;  // the scout pass (scout.hip): its band rows, and its result -- a bound U per query
     sina_hip::HostBuf h_res;          // pinned copy of a launch's DpResults (row-skip statistics, the next launch's guess)
     bool profile_batch = false;       // the launch being prepared is one (set by sina_hip_align_graphs)
@@ -186,6 +190,8 @@ struct sina_hip_ctx {
         scratch(all);
         for (auto *b : all) b->release();
         dbg.release();
+        wide_in.release();
+        wide_planes.release();
         h_out.release();
         h_out_pos.release();
         h_res.release();
@@ -588,6 +594,16 @@ using family_builder = int (*)(sina_hip_ctx *c, const uint32_t *fam_ids, const u
 int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build, bool profile_batch, const uint32_t *fam_ids,
                          const uint64_t *fam_off, uint32_t nq, const uint8_t *qmask, const uint64_t *qoff,
                          const sina_hip_align_params *p, sina_hip_align_out *out, uint32_t *out_pos);
+}  // namespace sina_hip
+
+namespace sina_hip {
+// ---- the wide path (mesh_wide.hip): queries qs[0 .. n) of the batch (indices into g / qoff, all offsets absolute)
+// through the wide kernel and its walk, in launches under wide_budget_cells(); results into out[q], the context's
+// staged out_pos and, if given, out_pos.  dbg_*: [N * L] planes of the one query (sina_hip_debug_mesh_wide).
+uint64_t wide_budget_cells();
+int run_wide(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask, const uint64_t *qoff,
+             const sina_hip_align_params *p, const uint32_t *qs, uint32_t n, sina_hip_align_out *out, uint32_t *out_pos,
+             uint32_t *dbg_vm = nullptr, uint32_t *dbg_vs = nullptr, float *dbg_value = nullptr);
 }  // namespace sina_hip
 
 // publishes the context's scratch capacities when an API call ends (see sina_hip_store::cap_hint)

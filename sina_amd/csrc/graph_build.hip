@@ -782,7 +782,7 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
         }
         const size_t glds_tables = graph_lds_bytes(c->st->width, max_f);
         const size_t glds = graph_lds_total(c->st->width, max_f);
-        if (glds > 160 * 1024) SH_FAIL("align_families: family too wide for the device DAG build");
+        if (glds > 160 * 1024) SH_FAIL_LIMIT("align_families: family too wide for the device DAG build");
         if (c->g_fam_ids.reserve(4 * std::max<uint64_t>(foff[bq], 1)) || c->g_fam_off.reserve(8 * ((uint64_t)bq + 1)) ||
             c->g_tmp1.reserve(8 * (uint64_t)bq) ||
             c->rec.reserve(sizeof(uint4) * (uint64_t)bq * ncap) || c->node_pos.reserve(4 * (uint64_t)bq * ncap) ||
@@ -848,10 +848,10 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
         uint32_t need_n = 0;
         for (uint32_t q = 0; q < bq; q++) {
             if (bg->sizes[kSz * q + 3] == 2) need_n = std::max(need_n, bg->sizes[kSz * q]);
-            if (bg->sizes[kSz * q + 3] == 4) SH_FAIL("align_families: too many spill rows for one query");
+            if (bg->sizes[kSz * q + 3] == 4) SH_FAIL_LIMIT("align_families: too many spill rows for one query");
         }
         if (!need_n) break;
-        if (attempt >= 3 || need_n > 65535u) SH_FAIL("align_families: family DAG exceeds device limits");
+        if (attempt >= 3 || need_n > 65535u) SH_FAIL_LIMIT("align_families: family DAG exceeds device limits");
         ncap = std::min<uint32_t>(65535, need_n + need_n / 8 + 16);
     }
     bg->ncap = ncap;
@@ -881,7 +881,7 @@ int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build,
     if (nq == 0) return 0;
     SH_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    if (c->st->width > 524288u) SH_FAIL(w + ": alignment wider than 524288 columns (use align_graphs)");
+    if (c->st->width > 524288u) SH_FAIL_LIMIT(w + ": alignment wider than 524288 columns (use align_graphs)");
     // (scoring_scheme_profile takes no positional weights, src/align.cpp:428-433: refused like a profile batch of align_graphs)
     if (profile_batch && p->weights != nullptr && p->n_weights > 0)
         SH_FAIL(w + ": a profile batch takes no positional weights (scoring_scheme_profile)");

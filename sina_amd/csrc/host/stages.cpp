@@ -1576,6 +1576,9 @@ static aligner::options al_defaults() {  // src/align.cpp:231-274
     // host route's bytes, but the two have not been timed against each other yet (tools/perf_profile.py), so the
     // route that has always been taken stays the default
     o.device_profile = false;
+    // families beyond the fast DP path's limits (sina_hip.h) through sina_hip_align_graphs_any and its wide kernel:
+    // on request
+    o.wide_fallback = false;
     return o;
 }
 static aligner::options &al_opts() {
@@ -1615,6 +1618,7 @@ void aligner::set_option(const std::string &name, const std::string &value) {
         if (to_bool(value)) throw std::logic_error("aligner: --" + name + " is outside the accelerated path");
     } else if (name == "device-graph") o.device_graph = to_bool(value);
     else if (name == "device-profile") o.device_profile = to_bool(value);
+    else if (name == "wide-fallback") o.wide_fallback = to_bool(value);
     else if (name == "db") o.database = value;
     else throw std::logic_error("aligner: unknown option " + name);
 }
@@ -1964,27 +1968,9 @@ void aligner::operator()(std::vector<tray> &batch) {
         const size_t nq = dnq;
         const std::vector<uint64_t> &qoff = dqoff;
         const uint8_t *const qmask = dqmask;
-        if (graph_on_device) {
-            std::vector<uint64_t> foff(nq + 1, 0);
-            for (size_t x = 0; x < nq; x++) foff[x + 1] = foff[x] + jobs[idx[x]].family_size();
-            std::vector<uint32_t> fids(foff.back() ? foff.back() : 1);
-            parallel_for(nq, [&](size_t x) {
-                const dp_job &jb = jobs[idx[x]];
-                for (size_t y = 0; y < jb.family_size(); y++) fids[foff[x] + y] = store->id_of(jb.member(y));
-            });
-            width = store->getAlignmentWidth();
-            if (o.fs_no_graph) {
-                ph.reset(), ph.reset(new scoped_phase("al.align_profiles(C-ABI)"));  // (the old phase ends first: the new one names the pool jobs)
-                hip_check(sina_hip_align_profiles(ctx, fids.data(), foff.data(), (uint32_t)nq, qmask, qoff.data(),
-                                                  &p, out.data(), out_pos),
-                          "align_profiles");
-            } else {
-                ph.reset(), ph.reset(new scoped_phase("al.align_families(C-ABI)"));  // (the old phase ends first: the new one names the pool jobs)
-                hip_check(sina_hip_align_families(ctx, fids.data(), foff.data(), (uint32_t)nq, qmask, qoff.data(),
-                                                  &p, out.data(), out_pos),
-                          "align_families");
-            }
-        } else {
+        // the host-graph route: the families' DAGs (profiles) built by the host twins of the device builders and handed
+        // over as graphs -- with wide-fallback through sina_hip_align_graphs_any, which takes a DAG of any size
+        auto host_graph_route = [&]() {
             std::vector<host_graph> gs(nq);
             ph.reset(), ph.reset(new scoped_phase("al.host_graph_build"));  // (the old phase ends first: the new one names the pool jobs)
             parallel_for(nq, [&](size_t x) {
@@ -2032,8 +2018,41 @@ void aligner::operator()(std::vector<tray> &batch) {
             gb.node_score16 = o.fs_no_graph ? nscore.data() : nullptr;
             gb.self_score16 = o.fs_no_graph ? self16 : nullptr;
             ph.reset(), ph.reset(new scoped_phase("al.align_graphs(C-ABI)"));  // (the old phase ends first: the new one names the pool jobs)
-            hip_check(sina_hip_align_graphs(ctx, &gb, qmask, qoff.data(), &p, out.data(), out_pos),
-                      "align_graphs");
+            if (o.wide_fallback)
+                hip_check(sina_hip_align_graphs_any(ctx, &gb, qmask, qoff.data(), &p, out.data(), out_pos),
+                          "align_graphs_any");
+            else
+                hip_check(sina_hip_align_graphs(ctx, &gb, qmask, qoff.data(), &p, out.data(), out_pos),
+                          "align_graphs");
+        };
+        // wide-fallback: a group the device builders refuse because a family exceeds one of their documented limits
+        // is redone once over host-built graphs; any other failure propagates
+        auto device_route = [&](int rc, const char *what) {
+            if (rc != 0 && o.wide_fallback && sina_hip_last_error_is_limit() == 1) host_graph_route();
+            else hip_check(rc, what);
+        };
+        if (graph_on_device) {
+            std::vector<uint64_t> foff(nq + 1, 0);
+            for (size_t x = 0; x < nq; x++) foff[x + 1] = foff[x] + jobs[idx[x]].family_size();
+            std::vector<uint32_t> fids(foff.back() ? foff.back() : 1);
+            parallel_for(nq, [&](size_t x) {
+                const dp_job &jb = jobs[idx[x]];
+                for (size_t y = 0; y < jb.family_size(); y++) fids[foff[x] + y] = store->id_of(jb.member(y));
+            });
+            width = store->getAlignmentWidth();
+            if (o.fs_no_graph) {
+                ph.reset(), ph.reset(new scoped_phase("al.align_profiles(C-ABI)"));  // (the old phase ends first: the new one names the pool jobs)
+                device_route(sina_hip_align_profiles(ctx, fids.data(), foff.data(), (uint32_t)nq, qmask, qoff.data(),
+                                                     &p, out.data(), out_pos),
+                             "align_profiles");
+            } else {
+                ph.reset(), ph.reset(new scoped_phase("al.align_families(C-ABI)"));  // (the old phase ends first: the new one names the pool jobs)
+                device_route(sina_hip_align_families(ctx, fids.data(), foff.data(), (uint32_t)nq, qmask, qoff.data(),
+                                                     &p, out.data(), out_pos),
+                             "align_families");
+            }
+        } else {
+            host_graph_route();
         }
         }   // ---- (end of the device's share)
 

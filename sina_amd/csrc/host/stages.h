@@ -396,6 +396,7 @@ public:
         float fs_weight;
         float match_score, mismatch_score, gap_penalty, gap_ext_penalty;
         bool debug_graph, write_used_rels, use_subst_matrix;
+        bool wide_fallback;   // families beyond the fast DP path's limits go through sina_hip_align_graphs_any (default off)
         bool device_profile;  // fs_no_graph: build the family profile on the GPU too (needs device_graph; default off: see stages.cpp)
         bool device_graph;  // build the family DAG on the GPU (default) or on the host
         std::string database;  // reference store the DAGs are built from (same as famfinder "db")

@@ -407,7 +407,7 @@ int build_family_profiles(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64
     uint32_t max_n = 1;
     for (int attempt = 0;; attempt++) {
         ProfileLds lds;
-        if (!profile_lds(c->st->width, max_f, ncap, &lds)) SH_FAIL("align_profiles: family too wide for the device profile build");
+        if (!profile_lds(c->st->width, max_f, ncap, &lds)) SH_FAIL_LIMIT("align_profiles: family too wide for the device profile build");
         const uint32_t pred_stride = ncap + 8;  // (slack behind every list, like the DAG build's)
         if (c->rec.reserve(sizeof(uint4) * (uint64_t)n * ncap) || c->node_pos.reserve(4 * (uint64_t)n * ncap) ||
             c->succ_minpos.reserve(4 * (uint64_t)n * ncap) || c->pred.reserve(4 * (uint64_t)n * pred_stride) ||
@@ -469,7 +469,7 @@ int build_family_profiles(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64
             }
         }
         if (!need_n) break;
-        if (attempt >= 3 || need_n > 65535u) SH_FAIL("align_profiles: family profile exceeds device limits (more than 65535 nodes)");
+        if (attempt >= 3 || need_n > 65535u) SH_FAIL_LIMIT("align_profiles: family profile exceeds device limits (more than 65535 nodes)");
         ncap = std::min<uint32_t>(65535, need_n + need_n / 8 + 16);
     }
     // what the next launch starts with: never less than before -- a workload that alternates short and long families
