@@ -1715,499 +1715,562 @@ struct dp_job {
         return v;
     }
 };
-}  // namespace
 
-tray aligner::operator()(tray t) {
-    std::vector<tray> b{t};
-    (*this)(b);
-    return b[0];
+// |K(q)|: windows of k unambiguous bases ending before the last base, first base A in "fast" mode
+// (src/kmer.h:69-83,122-124,188-201) -- for a family whose scores famfinder stamped as
+// raw k-mer counts (tray::family_scores_kmer_k: k, negative = no-fast)
+static unsigned query_kmer_count(const cseq &c, int stamp) {
+    const unsigned k = (unsigned)(stamp < 0 ? -stamp : stamp);
+    const bool nofast = stamp < 0;
+    const auto &b = c.getAlignedBases();
+    unsigned run = 0, n = 0;
+    for (size_t e = 0; e + 1 < b.size(); e++) {
+        const unsigned m = (b[e].raw >> 24) & 0xfu;
+        run = (m & (m - 1)) == 0 && m != 0 ? run + 1 : 0;  // exactly one base bit
+        if (run >= k && (nofast || ((b[e + 1 - k].raw >> 24) & 0xfu) == 1u)) n++;
+    }
+    return n;
 }
 
-// src/align.cpp:307-460 for a batch of trays.
-void aligner::operator()(std::vector<tray> &batch) {
-    const options &o = al_opts();
-    std::vector<dp_job> jobs(batch.size());
-    std::vector<char> need_dp(batch.size(), 0);
-
-    std::unique_ptr<scoped_phase> ph(new scoped_phase("al.prepare(partition)"));
-    std::shared_ptr<reference_store> prep_store;
-    {
-        const std::string db = o.database.empty() ? ff_opts.database : o.database;
-        if (!db.empty()) {
-            try {
-                prep_store = reference_store::get(db);
-            } catch (const std::exception &) {
+// Takes a tray as famfinder left it (prep_store: the reference store, if there is one, for its cached upper-case bases);
+// gives true if it needs the DP, false if it is done: nothing to align, too long, or its alignment copied from a relative.
+static bool prepare_tray(tray &t, const aligner::options &o, reference_store *prep_store) {
+    if (t.input_sequence == nullptr || t.alignment_reference == nullptr || t.astats == nullptr) return false;  // :310-318
+    if (t.input_sequence->size() > SINA_HIP_MAX_QUERY_LEN) {  // (device limit: soft failure of this tray)
+        t.log << "unable to align: sequence of " << t.input_sequence->size() << " bases (device limit "
+              << SINA_HIP_MAX_QUERY_LEN << ");";
+        return false;
+    }
+    uint64_t tk = host_tsc();
+    // (the working copy -- src/align.cpp:320-326 -- is made where its bases are known: below for a copied
+    // alignment, when the DP is back for the rest; it never holds the query's own bases)
+    search::result_vector &vc = *t.alignment_reference;
+    // (the query's upper-case base string: only built if a family member passes the k-mer-count
+    // test below and has to be searched for it -- exact relatives only)
+    std::string ubases_store;
+    bool have_ubases = false;
+    const size_t n_bases = t.input_sequence->size();
+    auto ubases_of_query = [&]() -> const std::string & {
+        if (!have_ubases) {
+            ubases_store = upper_copy(t.input_sequence->getBases());
+            have_ubases = true;
+        }
+        return ubases_store;
+    };
+    // upper-case bases of a family member: cached per store (40 members x every query)
+    auto ref_ubases = [&](const cseq *r, std::string &tmp) -> const std::string & {
+        if (prep_store && prep_store->owns(r)) return prep_store->upper_bases(prep_store->id_of(r));
+        tmp = upper_copy(r->getBases());
+        return tmp;
+    };
+    // A family member can only contain the query's bases if it has every one of the query's
+    // k-mers, i.e. if its k-mer score (what famfinder ranked it by) is the query's k-mer count --
+    // which spares the string search for all but exact relatives.
+    const float all_kmers = t.family_scores_kmer_k == 0 ? -1.f
+                            : (float)(t.query_kmer_count >= 0 ? (unsigned)t.query_kmer_count
+                                                              : query_kmer_count(*t.input_sequence, t.family_scores_kmer_k));
+    auto lacks_query = [&](search::result_item &item) {
+        if (item.score < all_kmers) return true;
+        std::string tmp;
+        return find_bases(ref_ubases(item.sequence, tmp), ubases_of_query()) == std::string::npos;
+    };
+    tk = host_tick("prepare: kmer count", tk);
+    // (the order this leaves the family in is the member order its DAG is built from)
+    auto holders = std::partition(vc.begin(), vc.end(), lacks_query);
+    tk = host_tick("prepare: partition", tk);
+    if (holders != vc.end()) {
+        if (o.realign) {  // :337-348
+            t.log << "sequences ";
+            for (auto it = holders; it != vc.end(); ++it)
+                t.log << it->sequence->get_attr<std::string>(fn::acc) << " ";
+            t.log << "containing exact candidate removed from family;";
+            vc.erase(holders, vc.end());
+            if (vc.empty()) {
+                t.log << "that's ALL of them. skipping sequence;";
+                return false;
             }
-            if (prep_store && !batch.empty() && prep_store->size() > 0) prep_store->upper_bases(0);  // (fills the cache outside the loop)
+        } else {  // :349-388 steal the alignment
+            auto is_query_itself = [&](search::result_item &item) {
+                std::string tmp;
+                return ref_ubases(item.sequence, tmp) == ubases_of_query();
+            };
+            auto exact = std::find_if(holders, vc.end(), is_query_itself);
+            cseq &c = *object_cache<cseq, cache_aligned_seq>::take();
+            c.copy_meta(*t.input_sequence);
+            if (exact != vc.end()) {
+                c.setAlignedBases(exact->sequence->getAlignedBases());
+                t.log << "copied alignment from identical template sequence "
+                      << exact->sequence->get_attr<std::string>(fn::acc) << ":"
+                      << exact->sequence->get_attr<std::string>(fn::start, "0") << "; ";
+            } else {
+                const auto &refal = holders->sequence->getAlignedBases();
+                std::string tmp;
+                const size_t at = find_bases(ref_ubases(holders->sequence, tmp), ubases_of_query());
+                c.setAlignedBases(refal.data() + at, n_bases);
+                t.log << "copied alignment from (longer) template sequence "
+                      << holders->sequence->get_attr<std::string>(fn::acc) << ":"
+                      << holders->sequence->get_attr<std::string>(fn::start, "0") << "; ";
+            }
+            c.setWidth(holders->sequence->getWidth());
+            c.set_attr(fn::date, make_datetime());
+            c.set_attr(fn::qual, 100);
+            if (o.calc_idty) c.set_attr(fn::idty, 100.f);
+            c.set_attr(fn::head, 0);
+            c.set_attr(fn::tail, 0);
+            c.set_attr(fn::filter, "");
+            t.aligned_sequence = &c;
+            return false;
         }
     }
-    // |K(q)|: windows of k unambiguous bases ending before the last base, first base A in "fast" mode
-    // (src/kmer.h:69-83,122-124,188-201) -- for a family whose scores famfinder stamped as
-    // raw k-mer counts (tray::family_scores_kmer_k: k, negative = no-fast)
-    auto query_kmer_count = [](const cseq &c, int stamp) -> unsigned {
-        const unsigned k = (unsigned)(stamp < 0 ? -stamp : stamp);
-        const bool nofast = stamp < 0;
-        const auto &b = c.getAlignedBases();
-        unsigned run = 0, n = 0;
-        for (size_t e = 0; e + 1 < b.size(); e++) {
-            const unsigned m = (b[e].raw >> 24) & 0xfu;
-            run = (m & (m - 1)) == 0 && m != 0 ? run + 1 : 0;  // exactly one base bit
-            if (run >= k && (nofast || ((b[e + 1 - k].raw >> 24) & 0xfu) == 1u)) n++;
-        }
-        return n;
-    };
-    parallel_for(batch.size(), [&](size_t i) {
-        tray &t = batch[i];
-        if (t.input_sequence == nullptr || t.alignment_reference == nullptr || t.astats == nullptr) return;  // :310-318
-        if (t.input_sequence->size() > SINA_HIP_MAX_QUERY_LEN) {  // (device limit: soft failure of this tray)
-            t.log << "unable to align: sequence of " << t.input_sequence->size() << " bases (device limit "
-                  << SINA_HIP_MAX_QUERY_LEN << ");";
-            return;
-        }
-        uint64_t tk = host_tsc();
-        // (the working copy -- src/align.cpp:320-326 -- is made where its bases are known: below for a copied
-        // alignment, when the DP is back for the rest; it never holds the query's own bases)
-        search::result_vector &vc = *t.alignment_reference;
-        // (the query's upper-case base string: only built if a family member passes the k-mer-count
-        // test below and has to be searched for it -- exact relatives only)
-        std::string ubases_store;
-        bool have_ubases = false;
-        const size_t n_bases = t.input_sequence->size();
-        auto ubases_of_query = [&]() -> const std::string & {
-            if (!have_ubases) {
-                ubases_store = upper_copy(t.input_sequence->getBases());
-                have_ubases = true;
-            }
-            return ubases_store;
-        };
-        // upper-case bases of a family member: cached per store (40 members x every query)
-        auto ref_ubases = [&](const cseq *r, std::string &tmp) -> const std::string & {
-            if (prep_store && prep_store->owns(r)) return prep_store->upper_bases(prep_store->id_of(r));
-            tmp = upper_copy(r->getBases());
-            return tmp;
-        };
-        // A family member can only contain the query's bases if it has every one of the query's
-        // k-mers, i.e. if its k-mer score (what famfinder ranked it by) is the query's k-mer count --
-        // which spares the string search for all but exact relatives.
-        const float all_kmers = t.family_scores_kmer_k == 0 ? -1.f
-                                : (float)(t.query_kmer_count >= 0 ? (unsigned)t.query_kmer_count
-                                                                  : query_kmer_count(*t.input_sequence, t.family_scores_kmer_k));
-        auto lacks_query = [&](search::result_item &item) {
-            if (item.score < all_kmers) return true;
-            std::string tmp;
-            return find_bases(ref_ubases(item.sequence, tmp), ubases_of_query()) == std::string::npos;
-        };
-        tk = host_tick("prepare: kmer count", tk);
-        auto holders = std::partition(vc.begin(), vc.end(), lacks_query);
-        tk = host_tick("prepare: partition", tk);
-        if (holders != vc.end()) {
-            if (o.realign) {  // :337-348
-                t.log << "sequences ";
-                for (auto it = holders; it != vc.end(); ++it)
-                    t.log << it->sequence->get_attr<std::string>(fn::acc) << " ";
-                t.log << "containing exact candidate removed from family;";
-                vc.erase(holders, vc.end());
-                if (vc.empty()) {
-                    t.log << "that's ALL of them. skipping sequence;";
-                    return;
-                }
-            } else {  // :349-388 steal the alignment
-                auto is_query_itself = [&](search::result_item &item) {
-                    std::string tmp;
-                    return ref_ubases(item.sequence, tmp) == ubases_of_query();
-                };
-                auto exact = std::find_if(holders, vc.end(), is_query_itself);
-                cseq &c = *object_cache<cseq, cache_aligned_seq>::take();
-                c.copy_meta(*t.input_sequence);
-                if (exact != vc.end()) {
-                    c.setAlignedBases(exact->sequence->getAlignedBases());
-                    t.log << "copied alignment from identical template sequence "
-                          << exact->sequence->get_attr<std::string>(fn::acc) << ":"
-                          << exact->sequence->get_attr<std::string>(fn::start, "0") << "; ";
-                } else {
-                    const auto &refal = holders->sequence->getAlignedBases();
-                    std::string tmp;
-                    const size_t at = find_bases(ref_ubases(holders->sequence, tmp), ubases_of_query());
-                    c.setAlignedBases(refal.data() + at, n_bases);
-                    t.log << "copied alignment from (longer) template sequence "
-                          << holders->sequence->get_attr<std::string>(fn::acc) << ":"
-                          << holders->sequence->get_attr<std::string>(fn::start, "0") << "; ";
-                }
-                c.setWidth(holders->sequence->getWidth());
-                c.set_attr(fn::date, make_datetime());
-                c.set_attr(fn::qual, 100);
-                if (o.calc_idty) c.set_attr(fn::idty, 100.f);
-                c.set_attr(fn::head, 0);
-                c.set_attr(fn::tail, 0);
-                c.set_attr(fn::filter, "");
-                t.aligned_sequence = &c;
-                return;
-            }
-        }
-        jobs[i].t = &t;
-        jobs[i].fam = &vc;
-        need_dp[i] = 1;
-        host_tick("prepare: family list", tk);
-    });
+    host_tick("prepare: family list", tk);
+    return true;
+}
 
-    ph.reset();
+// Takes the options and a group's positional weights (empty: simple scheme; they outlive the result); gives the device call's parameters.
+static sina_hip_align_params make_align_params(const aligner::options &o, const std::vector<float> &weights) {
+    sina_hip_align_params p;
+    sina_hip_align_params_default(&p);
+    p.match_score = o.match_score;
+    p.mismatch_score = o.mismatch_score;
+    p.gap_penalty = o.gap_penalty;
+    p.gap_ext_penalty = o.gap_ext_penalty;
+    p.fs_weight = o.fs_weight;
+    p.overhang = (int)o.overhang;
+    p.lowercase = (int)o.lowercase;
+    p.insertion = (int)o.insertion;
+    p.weights = weights.empty() ? nullptr : weights.data();
+    p.n_weights = (uint32_t)weights.size();
+    p.assemble = 1;  // (the device finishes what it can: sina_hip_align_out::assembled)
+    return p;
+}
+
+// Takes a group; gives its queries' mask bytes, member x at qoff[x] .. qoff[x + 1], in a buffer of the calling thread
+// that is valid until the next call.
+static const uint8_t *pack_group_queries(const std::vector<dp_job *> &members, std::vector<uint64_t> &qoff) {
+    const size_t nq = members.size();
+    qoff.assign(nq + 1, 0);
+    for (size_t x = 0; x < nq; x++) qoff[x + 1] = qoff[x] + members[x]->t->input_sequence->size();
+    thread_local batch_scratch<uint8_t> qmask_buf;
+    uint8_t *const qmask = qmask_buf.get(qoff.back() + 1);
+    parallel_for(nq, [&](size_t x) {  // (the DP looks at the four base bits only: case does not matter)
+        const cseq &qs = *members[x]->t->input_sequence;
+        const size_t nb = qs.size();
+        uint8_t *dst = qmask + qoff[x];
+        if (const uint8_t *dense = qs.denseMasks()) memcpy(dst, dense, nb);
+        else masks_of_packed(dst, qs.packed(), nb);
+    });
+    return qmask;
+}
+
+// What the device is given of a group: one SLOT per distinct (query, ordered family); every member reads one slot's results.
+struct device_slots {
+    size_t dnq = 0;                   // number of slots
+    std::vector<uint32_t> slot_of;    // [members] slot of group member x
+    std::vector<uint64_t> dqoff;      // [dnq + 1] slot u's mask bytes -- and its aligned columns coming back -- start at dqoff[u]
+    const uint8_t *dqmask = nullptr;  // the slots' mask bytes (a thread's scratch buffer: pack_group_queries, distinct_slots)
+    const std::vector<dp_job *> *members = nullptr;
+    std::vector<uint32_t> first;  // [dnq] first member of slot u; empty if nothing repeats (slot u is member u)
+    const dp_job &job(size_t u) const { return *(*members)[first.empty() ? u : first[u]]; }  // the job slot u is aligned for
+};
+
+// Repeated queries -- the same bases in the same case against the same ordered family: amplicon runs are full of
+// them -- are aligned ONCE (one DAG, one DP, one walk); every tray then finishes from the device results of its first
+// occurrence, with its own name, log and attributes (group_equal_items above).  Takes a group, packs its queries
+// (pack_group_queries); gives the slots.  Where nothing repeats the packing is handed on as it is: nothing is copied.
+static device_slots distinct_slots(const std::vector<dp_job *> &members) {
+    scoped_phase ph("al.pack_queries");
+    const size_t nq = members.size();
+    std::vector<uint64_t> qoff;
+    const uint8_t *const qmask = pack_group_queries(members, qoff);
+    device_slots s;
+    s.members = &members;
+    std::vector<uint32_t> rep;
+    s.dnq = group_equal_items(
+        nq,
+        [&](size_t x) {
+            const dp_job &jb = *members[x];
+            uint64_t hf = 0xcbf29ce484222325ull ^ jb.family_size();
+            for (size_t y = 0; y < jb.family_size(); y++) {
+                hf = (hf ^ (uint64_t)reinterpret_cast<uintptr_t>(jb.member(y))) * 0x100000001b3ull;
+                hf ^= hf >> 29;
+            }
+            return hash_ends(qmask + qoff[x], qoff[x + 1] - qoff[x], hf);
+        },
+        [&](size_t a, size_t b) {
+            const dp_job &ja = *members[a], &jb = *members[b];
+            if (qoff[a + 1] - qoff[a] != qoff[b + 1] - qoff[b] || ja.family_size() != jb.family_size()) return false;
+            for (size_t y = 0; y < ja.family_size(); y++)
+                if (ja.member(y) != jb.member(y)) return false;
+            return memcmp(qmask + qoff[a], qmask + qoff[b], qoff[a + 1] - qoff[a]) == 0;
+        },
+        rep);
+    s.slot_of.resize(nq);
+    if (s.dnq == nq) {
+        for (size_t x = 0; x < nq; x++) s.slot_of[x] = (uint32_t)x;
+        s.dqoff = std::move(qoff);
+        s.dqmask = qmask;
+        return s;
+    }
+    s.first.reserve(s.dnq);
+    s.dqoff.assign(s.dnq + 1, 0);
+    for (size_t x = 0; x < nq; x++) {
+        if (rep[x] == x) {
+            s.slot_of[x] = (uint32_t)s.first.size();
+            s.dqoff[s.first.size() + 1] = s.dqoff[s.first.size()] + (qoff[x + 1] - qoff[x]);
+            s.first.push_back((uint32_t)x);
+        } else {
+            s.slot_of[x] = s.slot_of[rep[x]];
+        }
+    }
+    thread_local batch_scratch<uint8_t> dqmask_buf;  // (not the packing's buffer: that one is being read)
+    uint8_t *const um = dqmask_buf.get(s.dqoff.back() + 1);
+    parallel_for(s.dnq, [&](size_t u) { memcpy(um + s.dqoff[u], qmask + qoff[s.first[u]], s.dqoff[u + 1] - s.dqoff[u]); });
+    s.dqmask = um;
+    return s;
+}
+
+// The host-graph route: the slots' families as DAGs (--fs-no-graph: profiles) built by the host twins of the device
+// builders and handed over as graphs -- with wide-fallback through sina_hip_align_graphs_any, which takes a DAG of
+// any size.  Fills out[slot] and the context's staged columns; gives the graphs' width.
+static uint32_t align_host_graphs(sina_hip_ctx *ctx, const aligner::options &o, const sina_hip_align_params &p,
+                                  const device_slots &s, sina_hip_align_out *out) {
+    const size_t n = s.dnq;
+    std::vector<host_graph> gs(n);
+    {
+        scoped_phase ph("al.host_graph_build");
+        parallel_for(n, [&](size_t u) {
+            if (o.fs_no_graph) build_family_profile(s.job(u).family(), -o.match_score, -o.mismatch_score, o.gap_penalty, o.gap_ext_penalty, &gs[u]);
+            else build_family_graph(s.job(u).family(), o.fs_weight, &gs[u]);
+        });
+    }
+    sina_hip_graph_batch gb;
+    std::vector<uint64_t> node_off(n + 1, 0), edge_off(n + 1, 0);
+    std::vector<uint32_t> npos, pred, poff, smin;
+    std::vector<uint8_t> nmask;
+    std::vector<float> nw, nscore;  // (all sized below, under the phase that pays for them)
+    float self16[16];
+    {
+        scoped_phase ph("al.host_graph_concat");
+        for (size_t u = 0; u < n; u++) {
+            node_off[u + 1] = node_off[u] + gs[u].pos.size();
+            edge_off[u + 1] = edge_off[u] + gs[u].pred.size();
+        }
+        npos.resize(node_off.back()), pred.resize(edge_off.back() ? edge_off.back() : 1), poff.resize(node_off.back() + n);
+        smin.resize(node_off.back()), nmask.resize(node_off.back()), nw.resize(node_off.back());
+        nscore.resize(o.fs_no_graph ? 16 * (size_t)node_off.back() : 0);
+        if (o.fs_no_graph) profile_self_scores(-o.match_score, -o.mismatch_score, o.gap_penalty, o.gap_ext_penalty, self16);
+        parallel_for(n, [&](size_t u) {
+            const host_graph &g = gs[u];
+            std::copy(g.pos.begin(), g.pos.end(), npos.begin() + node_off[u]);
+            std::copy(g.mask.begin(), g.mask.end(), nmask.begin() + node_off[u]);
+            std::copy(g.weight.begin(), g.weight.end(), nw.begin() + node_off[u]);
+            std::copy(g.succ_minpos.begin(), g.succ_minpos.end(), smin.begin() + node_off[u]);
+            std::copy(g.pred_off.begin(), g.pred_off.end(), poff.begin() + node_off[u] + u);
+            std::copy(g.pred.begin(), g.pred.end(), pred.begin() + edge_off[u]);
+            if (o.fs_no_graph) std::copy(g.score16.begin(), g.score16.end(), nscore.begin() + 16 * node_off[u]);
+        });
+        gb.nq = (uint32_t)n;
+        gb.node_off = node_off.data();
+        gb.edge_off = edge_off.data();
+        gb.node_pos = npos.data();
+        gb.node_mask = nmask.data();
+        gb.node_weight = nw.data();
+        gb.pred_off = poff.data();
+        gb.pred = pred.data();
+        gb.succ_minpos = smin.data();
+        gb.width = gs[0].width;
+        gb.node_score16 = o.fs_no_graph ? nscore.data() : nullptr;
+        gb.self_score16 = o.fs_no_graph ? self16 : nullptr;
+    }
+    scoped_phase ph("al.align_graphs(C-ABI)");
+    // (out_pos == nullptr: the aligned columns are read where the device copied them, sina_hip_staged_out_pos)
+    if (o.wide_fallback)
+        hip_check(sina_hip_align_graphs_any(ctx, &gb, s.dqmask, s.dqoff.data(), &p, out, nullptr), "align_graphs_any");
+    else
+        hip_check(sina_hip_align_graphs(ctx, &gb, s.dqmask, s.dqoff.data(), &p, out, nullptr), "align_graphs");
+    return gb.width;
+}
+
+// The family-id route: the slots' families as lists of reference ids, their DAGs (--fs-no-graph: profiles) built on
+// the device.  wide-fallback: a group the device builders refuse because a family exceeds one of their documented
+// limits is redone once over host-built graphs; any other failure propagates.  Fills out[slot] and the context's
+// staged columns; gives the alignment's width.
+static uint32_t align_family_ids(sina_hip_ctx *ctx, reference_store &store, const aligner::options &o,
+                                 const sina_hip_align_params &p, const device_slots &s, sina_hip_align_out *out) {
+    const size_t n = s.dnq;
+    std::vector<uint64_t> foff(n + 1, 0);
+    std::vector<uint32_t> fids;
+    {
+        scoped_phase ph("al.pack_queries");  // (the families' ids are packed under the phase the queries were)
+        for (size_t u = 0; u < n; u++) foff[u + 1] = foff[u] + s.job(u).family_size();
+        fids.resize(foff.back() ? foff.back() : 1);
+        parallel_for(n, [&](size_t u) {
+            const dp_job &jb = s.job(u);
+            for (size_t y = 0; y < jb.family_size(); y++) fids[foff[u] + y] = store.id_of(jb.member(y));
+        });
+    }
+    int rc;
+    // (out_pos == nullptr: the aligned columns are read where the device copied them, sina_hip_staged_out_pos)
+    if (o.fs_no_graph) {
+        scoped_phase ph("al.align_profiles(C-ABI)");
+        rc = sina_hip_align_profiles(ctx, fids.data(), foff.data(), (uint32_t)n, s.dqmask, s.dqoff.data(), &p, out, nullptr);
+    } else {
+        scoped_phase ph("al.align_families(C-ABI)");
+        rc = sina_hip_align_families(ctx, fids.data(), foff.data(), (uint32_t)n, s.dqmask, s.dqoff.data(), &p, out, nullptr);
+    }
+    if (rc != 0 && o.wide_fallback && sina_hip_last_error_is_limit() == 1) return align_host_graphs(ctx, o, p, s, out);
+    hip_check(rc, o.fs_no_graph ? "align_profiles" : "align_families");
+    return store.getAlignmentWidth();
+}
+
+// The device's share: out[u] = slot u's result, its aligned columns at sina_hip_staged_out_pos(ctx) + dqoff[u] while the
+// context stays leased; gives the alignment's width.
+static uint32_t align_slots(sina_hip_ctx *ctx, reference_store &store, const aligner::options &o, const sina_hip_align_params &p,
+                            const device_slots &s, bool graph_on_device, sina_hip_align_out *out) {
+    return graph_on_device ? align_family_ids(ctx, store, o, p, s, out) : align_host_graphs(ctx, o, p, s, out);
+}
+
+// The bases a walk emits, in its order -- `tail` overhang bases from the query's end, the aligned bases back from
+// end_s, `head` overhang bases -- as emit(column as the device gave it, base bits of that query base): upper-cased
+// unless --lowercase=original (src/align.cpp:324-326), overhang bases lower-cased with --lowercase=unaligned.
+template <class Emit>
+static void for_each_emission(const cseq &query, const sina_hip_align_out &r, uint32_t tail, uint32_t head, LOWERCASE_TYPE lowercase,
+                              const uint32_t *pos, Emit &&emit) {
+    const uint32_t *qraw = query.packed();
+    const uint32_t L = (uint32_t)query.size();
+    const uint32_t keep_case = lowercase == LOWERCASE_ORIGINAL ? 0xFFFFFFFFu : ~((uint32_t)16 << 24);
+    const uint32_t lower_bit = lowercase == LOWERCASE_UNALIGNED ? (uint32_t)16 << 24 : 0u;
+    auto qbase = [&](uint32_t i, bool overhang_base) -> uint32_t {  // base bits of query base i, in place
+        return ((qraw[i] & keep_case) & 0xFF000000u) | (overhang_base ? lower_bit : 0u);
+    };
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < tail; k++) emit(pos[n++], qbase(L - 1 - k, true));
+    for (int k = 0; k < r.aligned_bases; k++) emit(pos[n++], qbase((uint32_t)r.end_s - (uint32_t)k, false));
+    for (uint32_t k = 0; k < head; k++) emit(pos[n++], qbase((uint32_t)r.cutoff_head - 1 - k, true));
+}
+
+// Takes the result and emitted columns of a walk the device did not assemble; gives the working copy `c` its bases: the
+// container steps of backtrack() (src/mesh.h:603-726) and the NAST fix-up with its log line.  Gives the tick to go on from.
+static uint64_t assemble_on_host(tray &t, cseq &c, const sina_hip_align_out &r, const uint32_t *pos, uint32_t width,
+                                 const aligner::options &o, uint64_t tk) {
+    const bool keep_over = (o.overhang != OVERHANG_REMOVE);
+    const uint32_t tail = keep_over ? (uint32_t)r.cutoff_tail : 0;
+    const uint32_t head = keep_over ? (uint32_t)r.cutoff_head : 0;
+    const uint32_t n_out = tail + (uint32_t)r.aligned_bases + head;
+    // The container steps in one pass: every emitted base is appended under the container rule (a column left of
+    // the current width is moved up to it, src/cseq.cpp:79-95), then the sequence is reversed (order and columns,
+    // :283-289).  The columns after the rule never decrease, so the result is written back to front directly.
+    c.clearSequence();
+    base_vector &fin = c.mutableAlignedBases();  // (a recycled sequence: no allocation)
+    fin.resize(n_out);
+    uint32_t reach = 0;  // alignment_width while appending (clearSequence: 0)
+    bool direct = true;
+    uint32_t n = 0;
+    for_each_emission(*t.input_sequence, r, tail, head, o.lowercase, pos, [&](uint32_t column, uint32_t base_bits) {
+        if (column >= reach) reach = column;
+        else column = reach;
+        if (column >= width) direct = false;  // (setWidth would have to repack: the general way below)
+        fin[n_out - 1 - n] = aligned_base::from_raw(((width - 1 - column) & 0xFFFFFFu) | base_bits);
+        n++;
+    });
+    if (direct) {
+        c.setWidth(width);
+    } else {  // the same through the container's own operations
+        c.clearSequence();
+        for_each_emission(*t.input_sequence, r, tail, head, o.lowercase, pos, [&](uint32_t column, uint32_t base_bits) {
+            c.append(aligned_base::from_raw((column & 0xFFFFFFu) | base_bits));
+        });
+        c.setWidth(width);
+        c.reverse();
+    }
+    tk = host_tick("finish: assemble", tk);
+    c.fix_duplicate_positions(t.log, o.lowercase == LOWERCASE_UNALIGNED, o.insertion == INSERTION_REMOVE);
+    return host_tick("finish: NAST fix-up", tk);
+}
+
+// Takes a job, its slot's device result `r` and aligned columns `pos`; gives the tray its aligned sequence, attributes and log
+// (backtrack()'s container steps, src/mesh.h:603-736, + do_align's attributes, src/align.cpp:507-509).  Throws on a failed query.
+static void finish_tray(dp_job &jb, const sina_hip_align_out &r, const uint32_t *pos, uint32_t width, const aligner::options &o,
+                        bool defer_score_line) {
+    tray &t = *jb.t;
+    if (r.status != 0) throw std::runtime_error("device alignment failed for " + t.input_sequence->getName());
+    uint64_t tk = host_tsc();
+    // the working copy: name and attributes of the input plus do_align's own (src/align.cpp:507-509,455-457),
+    // made in one pass (cseq.h copy_meta_with); its bases follow
+    const float score_q = r.raw / r.sum_weight;
+    const std::string &date_text = make_datetime();
+    const std::string &filter_name = t.astats->getName();
+    struct keys_t {
+        const std::string *head = cseq::attr_key(fn::head), *tail = cseq::attr_key(fn::tail), *filter = cseq::attr_key(fn::filter),
+                          *qual = cseq::attr_key(fn::qual), *date = cseq::attr_key(fn::date);
+    };
+    static const keys_t keys;  // ("align_cutoff_head_slv" < "align_cutoff_tail_slv" < "align_filter_slv" < "align_quality_slv" < "aligned_slv")
+    const cseq::attr_init extra[5] = {
+        cseq::attr_init::of(keys.head, (int)r.cutoff_head),
+        cseq::attr_init::of(keys.tail, (int)r.cutoff_tail),
+        cseq::attr_init::of(keys.filter, std::string_view(filter_name)),
+        cseq::attr_init::of(keys.qual, (int)std::min(100.f, std::max(0.f, 100.f * score_q))),
+        cseq::attr_init::of(keys.date, std::string_view(date_text)),
+    };
+    cseq &c = *object_cache<cseq, cache_aligned_seq>::take();
+    jb.c = &c;
+    c.copy_meta_with(*t.input_sequence, extra, 5);
+    tk = host_tick("finish: working copy + attributes", tk);
+    if (r.assembled) {
+        // the device did the container steps (append rule, setWidth, reverse) and a NAST fix-up
+        // in which every insertion fitted its gap: the finished bases, and the fix-up's log line
+        c.clearSequence();
+        base_vector &fin = c.mutableAlignedBases();  // (a recycled sequence: no allocation)
+        // (one pass, past the cache: base lists are not zeroed by resize() -- cseq.h, base_block_allocator -- and
+        // nobody reads the finished list before a sink takes it)
+        fin.resize(r.n_out);
+        stream_copy(static_cast<void *>(fin.data()), pos, sizeof(aligned_base) * (size_t)r.n_out);
+        c.setWidth(width);
+        tk = host_tick("finish: assemble", tk);
+        if (o.insertion == INSERTION_REMOVE) t.log << "insertion=remove not implemented, using shift; ";
+        if (r.nast_total > 0)
+            t.log << "total inserted bases=" << r.nast_total << ";"
+                  << "longest insertion=" << r.nast_longest << ";"
+                  << "total inserted bases before shifting=" << r.nast_last_run << ";";
+    } else {
+        tk = assemble_on_host(t, c, r, pos, width, o, tk);
+    }
+    if (c.getWidth() > width) t.log << "warning: result sequence too wide!";
+    // (the line itself is rendered when the log is read: tray::score_note -- or at once, for a caller that
+    // reads the stream itself)
+    const tray::score_note note{r.raw, r.sum_weight, score_q, (uint32_t)t.input_sequence->size(), (int32_t)r.aligned_bases,
+                                (uint32_t)t.log.view().size(), true};
+    if (defer_score_line) {
+        t.pending_score = note;
+    } else {
+        char line[192];
+        t.log.write(line, (std::streamsize)note.render(line, sizeof line));
+    }
+    tk = host_tick("finish: score log text", tk);
+    if (o.write_used_rels) {
+        std::string s;
+        for (size_t y = 0; y < jb.family_size(); y++) s += jb.member(y)->getName() + " ";
+        c.set_attr(fn::used_rels, s);
+    }
+    t.aligned_sequence = &c;
+    host_tick("finish: attributes", tk);
+}
+
+// Takes n aligned sequences seq_of(x) and for each the n_ids_of(x) reference ids that put_ids(x, dst) writes, packs both and
+// compares them in ONE launch; gives the counters of sequence x against its candidate r at counts[coff[x] + r].
+struct pair_counts {
+    std::vector<uint64_t> coff;
+    std::vector<sina_hip_match_counts> counts;
+};
+template <class SeqOf, class NIdsOf, class PutIds>
+static pair_counts compare_packed(sina_hip_ctx *ctx, size_t n, SeqOf &&seq_of, NIdsOf &&n_ids_of, PutIds &&put_ids, int iupac_rule,
+                                  int filter_lowercase) {
+    pair_counts pc;
+    std::vector<uint64_t> qoff(n + 1, 0);
+    pc.coff.assign(n + 1, 0);
+    for (size_t x = 0; x < n; x++) {
+        qoff[x + 1] = qoff[x] + seq_of(x).size();
+        pc.coff[x + 1] = pc.coff[x] + n_ids_of(x);
+    }
+    std::vector<uint32_t> qab(qoff.back() ? qoff.back() : 1), cids(pc.coff.back() ? pc.coff.back() : 1);
+    for (size_t x = 0; x < n; x++) {
+        const cseq &c = seq_of(x);
+        memcpy(qab.data() + qoff[x], c.packed(), 4 * (size_t)c.size());
+        put_ids(x, cids.data() + pc.coff[x]);
+    }
+    pc.counts.resize(pc.coff.back() ? pc.coff.back() : 1);
+    hip_check(sina_hip_compare(ctx, qab.data(), qoff.data(), (uint32_t)n, cids.data(), pc.coff.data(), iupac_rule, filter_lowercase,
+                               pc.counts.data()),
+              "sina_hip_compare");
+    return pc;
+}
+
+// --calc-idty (src/align.cpp:443-453): takes a finished group; gives every aligned query its best overlap identity with a
+// member of its family as an attribute -- one comparison launch for the group (sina_hip_compare).
+static void set_family_identity(const std::vector<dp_job *> &members, reference_store &store) {
+    scoped_phase ph("al.calc_idty(C-ABI)");
+    auto dev = store.worker_device(reference_store::dev_compare);
+    const pair_counts pc = compare_packed(
+        dev.get(), members.size(), [&](size_t x) -> const cseq & { return *members[x]->c; },
+        [&](size_t x) { return members[x]->family_size(); },
+        [&](size_t x, uint32_t *dst) {
+            for (size_t y = 0; y < members[x]->family_size(); y++) dst[y] = store.id_of(members[x]->member(y));
+        },
+        SINA_CMP_IUPAC_OPTIMISTIC, 0);
+    const cseq_comparator calc_id(CMP_IUPAC_OPTIMISTIC, CMP_DIST_NONE, CMP_COVER_OVERLAP, false);
+    for (size_t x = 0; x < members.size(); x++) {
+        float idty = 0;
+        for (uint64_t y = pc.coff[x]; y < pc.coff[x + 1]; y++) idty = std::max(idty, calc_id.score(pc.counts[y]));
+        members[x]->c->set_attr(fn::idty, 100.f * idty);
+    }
+}
+}  // namespace
+
+// src/align.cpp:307-460 for a batch of trays: prepare every tray, group those that need the DP, then per group pack
+// the queries, find the distinct ones, align them on the device, finish every tray and -- on request -- its identity.
+void aligner::operator()(std::vector<tray> &batch) {
+    const options &o = al_opts();
+    std::vector<dp_job> jobs(batch.size());  // (a tray that needs the DP has its job's `t` set)
+    const std::string db = o.database.empty() ? ff_opts.database : o.database;
+    std::shared_ptr<reference_store> store;
+    {
+        scoped_phase ph("al.prepare(partition)");
+        if (!db.empty()) {
+            try {
+                store = reference_store::get(db);
+            } catch (const std::exception &) {  // (a batch without DP jobs does without the store)
+            }
+            if (store && !batch.empty() && store->size() > 0) store->upper_bases(0);  // (fills the cache outside the loop)
+        }
+        parallel_for(batch.size(), [&](size_t i) {
+            if (!prepare_tray(batch[i], o, store.get())) return;
+            jobs[i].t = &batch[i];
+            jobs[i].fam = batch[i].alignment_reference;
+        });
+    }
     // group DP jobs by scoring scheme: default-constructed astats (width 0) => simple
     // scheme, otherwise weighted with that tray's weights (src/align.cpp:404-416)
     // ... and by where the family's DAG is built: on the device (families of up to 128 members: the
     // DAG-build kernel's LDS tables) or, for the rare larger family (--fs-max beyond 128), by the host
     // twin of that kernel (build_family_graph) and handed over as a graph (sina_hip_align_graphs)
     constexpr size_t kDeviceFamilyMax = 128;
-    std::map<std::pair<std::vector<float>, bool>, std::vector<size_t>> groups;
+    std::map<std::pair<std::vector<float>, bool>, std::vector<dp_job *>> groups;
     // (--fs-no-graph: the family as a profile, built by build_family_profile on the host or -- with device-profile on,
     // under the conditions a DAG is built on the device -- by sina_hip_align_profiles; scoring_scheme_profile takes no
     // positional weights, src/align.cpp:428-433)
-    for (size_t i = 0; i < batch.size(); i++)
-        if (need_dp[i]) {
-            const bool on_device = o.device_graph && jobs[i].family_size() <= kDeviceFamilyMax;
-            if (o.fs_no_graph) groups[{std::vector<float>(), on_device && o.device_profile}].push_back(i);
-            else groups[{batch[i].astats->getWeights(), on_device}].push_back(i);
+    for (dp_job &jb : jobs)
+        if (jb.t != nullptr) {
+            const bool on_device = o.device_graph && jb.family_size() <= kDeviceFamilyMax;
+            if (o.fs_no_graph) groups[{std::vector<float>(), on_device && o.device_profile}].push_back(&jb);
+            else groups[{jb.t->astats->getWeights(), on_device}].push_back(&jb);
         }
+    if (!groups.empty() && !store) store = reference_store::get(db);  // (the DP needs the store: this throws what the lookup above met)
 
-    std::shared_ptr<reference_store> store;
-    if (!groups.empty()) {
-        const std::string db = o.database.empty() ? ff_opts.database : o.database;
-        store = reference_store::get(db);
-    }
     for (auto &grp : groups) {
-        const std::vector<float> &weights = grp.first.first;
-        const bool graph_on_device = grp.first.second;
-        const std::vector<size_t> &idx = grp.second;
-        const size_t nq = idx.size();
-        sina_hip_align_params p;
-        sina_hip_align_params_default(&p);
-        p.match_score = o.match_score;
-        p.mismatch_score = o.mismatch_score;
-        p.gap_penalty = o.gap_penalty;
-        p.gap_ext_penalty = o.gap_ext_penalty;
-        p.fs_weight = o.fs_weight;
-        p.overhang = (int)o.overhang;
-        p.lowercase = (int)o.lowercase;
-        p.insertion = (int)o.insertion;
-        p.weights = weights.empty() ? nullptr : weights.data();
-        p.n_weights = (uint32_t)weights.size();
-        p.assemble = 1;  // (the device finishes what it can: sina_hip_align_out::assembled)
-
-        ph.reset(), ph.reset(new scoped_phase("al.pack_queries"));  // (the old phase ends first: the new one names the pool jobs)
-        std::vector<uint64_t> qoff(nq + 1, 0);
-        for (size_t x = 0; x < nq; x++) qoff[x + 1] = qoff[x] + jobs[idx[x]].t->input_sequence->size();
-        thread_local batch_scratch<uint8_t> qmask_buf;
-        uint8_t *const qmask = qmask_buf.get(qoff.back() + 1);
-        parallel_for(nq, [&](size_t x) {  // (the DP looks at the four base bits only: case does not matter)
-            const cseq &qs = *jobs[idx[x]].t->input_sequence;
-            const size_t nb = qs.size();
-            uint8_t *dst = qmask + qoff[x];
-            if (const uint8_t *dense = qs.denseMasks()) memcpy(dst, dense, nb);
-            else masks_of_packed(dst, qs.packed(), nb);
-        });
-        // Repeated queries -- the same bases in the same case against the same ordered family: amplicon runs are
-        // full of them -- are aligned ONCE (one DAG, one DP, one walk); every tray then finishes from the device
-        // results of its first occurrence, with its own name, log and attributes (group_equal_items above).
-        std::vector<uint32_t> rep;
-        const size_t dnq = group_equal_items(
-            nq,
-            [&](size_t x) {
-                const dp_job &jb = jobs[idx[x]];
-                uint64_t hf = 0xcbf29ce484222325ull ^ jb.family_size();
-                for (size_t y = 0; y < jb.family_size(); y++) {
-                    hf = (hf ^ (uint64_t)reinterpret_cast<uintptr_t>(jb.member(y))) * 0x100000001b3ull;
-                    hf ^= hf >> 29;
-                }
-                return hash_ends(qmask + qoff[x], qoff[x + 1] - qoff[x], hf);
-            },
-            [&](size_t a, size_t b) {
-                const dp_job &ja = jobs[idx[a]], &jb = jobs[idx[b]];
-                if (qoff[a + 1] - qoff[a] != qoff[b + 1] - qoff[b] || ja.family_size() != jb.family_size()) return false;
-                for (size_t y = 0; y < ja.family_size(); y++)
-                    if (ja.member(y) != jb.member(y)) return false;
-                return memcmp(qmask + qoff[a], qmask + qoff[b], qoff[a + 1] - qoff[a]) == 0;
-            },
-            rep);
-        std::vector<uint32_t> slot_of(nq);       // device slot of group member x
-        std::vector<size_t> uidx;                // job of device slot u
-        std::vector<uint64_t> dqoff_store;
-        const uint8_t *dqmask = qmask;
-        thread_local batch_scratch<uint8_t> dqmask_buf;
-        if (dnq == nq) {
-            for (size_t x = 0; x < nq; x++) slot_of[x] = (uint32_t)x;
-        } else {
-            uidx.reserve(dnq);
-            dqoff_store.assign(dnq + 1, 0);
-            std::vector<uint32_t> first_x;
-            first_x.reserve(dnq);
-            for (size_t x = 0; x < nq; x++) {
-                if (rep[x] == x) {
-                    slot_of[x] = (uint32_t)uidx.size();
-                    dqoff_store[uidx.size() + 1] = dqoff_store[uidx.size()] + (qoff[x + 1] - qoff[x]);
-                    uidx.push_back(idx[x]);
-                    first_x.push_back((uint32_t)x);
-                } else {
-                    slot_of[x] = slot_of[rep[x]];
-                }
-            }
-            uint8_t *const um = dqmask_buf.get(dqoff_store.back() + 1);
-            parallel_for(dnq, [&](size_t u) { memcpy(um + dqoff_store[u], qmask + qoff[first_x[u]], dqoff_store[u + 1] - dqoff_store[u]); });
-            dqmask = um;
-        }
-        const std::vector<uint64_t> &dqoff = dnq == nq ? qoff : dqoff_store;
-        std::vector<sina_hip_align_out> out(dnq);
+        const std::vector<dp_job *> &members = grp.second;
+        const sina_hip_align_params p = make_align_params(o, grp.first.first);
+        const device_slots slots = distinct_slots(members);
+        std::vector<sina_hip_align_out> out(slots.dnq);
         // (the aligned columns are read where the device copied them, in the context's pinned staging buffer:
-        // sina_hip_staged_out_pos -- the context stays leased until the alignments below are finished)
-        uint32_t *const out_pos = nullptr;
+        // sina_hip_staged_out_pos -- the context stays leased until the group's last tray is finished)
         auto dev = store->worker_device(reference_store::dev_align);
-        sina_hip_ctx *ctx = dev.get();
-        uint32_t width = 0;
-
-        {   // ---- the device's share, over the DISTINCT queries of the group (the names below shadow the group's)
-        const std::vector<size_t> &group_idx = idx;
-        const std::vector<size_t> &idx = dnq == group_idx.size() ? group_idx : uidx;
-        const size_t nq = dnq;
-        const std::vector<uint64_t> &qoff = dqoff;
-        const uint8_t *const qmask = dqmask;
-        // the host-graph route: the families' DAGs (profiles) built by the host twins of the device builders and handed
-        // over as graphs -- with wide-fallback through sina_hip_align_graphs_any, which takes a DAG of any size
-        auto host_graph_route = [&]() {
-            std::vector<host_graph> gs(nq);
-            ph.reset(), ph.reset(new scoped_phase("al.host_graph_build"));  // (the old phase ends first: the new one names the pool jobs)
-            parallel_for(nq, [&](size_t x) {
-                if (o.fs_no_graph)
-                    build_family_profile(jobs[idx[x]].family(), -o.match_score, -o.mismatch_score, o.gap_penalty,
-                                         o.gap_ext_penalty, &gs[x]);
-                else
-                    build_family_graph(jobs[idx[x]].family(), o.fs_weight, &gs[x]);
+        const uint32_t width = align_slots(dev.get(), *store, o, p, slots, grp.first.second, out.data());
+        const uint32_t *const staged_pos = sina_hip_staged_out_pos(dev.get());
+        {
+            scoped_phase ph("al.finish(NAST,log)");
+            parallel_for(members.size(), [&](size_t x) {
+                const uint32_t u = slots.slot_of[x];
+                finish_tray(*members[x], out[u], staged_pos + slots.dqoff[u], width, o, defer_score_line);
             });
-            ph.reset(), ph.reset(new scoped_phase("al.host_graph_concat"));  // (the old phase ends first: the new one names the pool jobs)
-            sina_hip_graph_batch gb;
-            std::vector<uint64_t> node_off(nq + 1, 0), edge_off(nq + 1, 0);
-            for (size_t x = 0; x < nq; x++) {
-                node_off[x + 1] = node_off[x] + gs[x].pos.size();
-                edge_off[x + 1] = edge_off[x] + gs[x].pred.size();
-            }
-            std::vector<uint32_t> npos(node_off.back()), pred(edge_off.back() ? edge_off.back() : 1),
-                poff(node_off.back() + nq), smin(node_off.back());
-            std::vector<uint8_t> nmask(node_off.back());
-            std::vector<float> nw(node_off.back());
-            std::vector<float> nscore(o.fs_no_graph ? 16 * (size_t)node_off.back() : 0);
-            float self16[16];
-            if (o.fs_no_graph) profile_self_scores(-o.match_score, -o.mismatch_score, o.gap_penalty, o.gap_ext_penalty, self16);
-            parallel_for(nq, [&](size_t x) {
-                const host_graph &g = gs[x];
-                std::copy(g.pos.begin(), g.pos.end(), npos.begin() + node_off[x]);
-                std::copy(g.mask.begin(), g.mask.end(), nmask.begin() + node_off[x]);
-                std::copy(g.weight.begin(), g.weight.end(), nw.begin() + node_off[x]);
-                std::copy(g.succ_minpos.begin(), g.succ_minpos.end(), smin.begin() + node_off[x]);
-                std::copy(g.pred_off.begin(), g.pred_off.end(), poff.begin() + node_off[x] + x);
-                std::copy(g.pred.begin(), g.pred.end(), pred.begin() + edge_off[x]);
-                if (o.fs_no_graph) std::copy(g.score16.begin(), g.score16.end(), nscore.begin() + 16 * node_off[x]);
-            });
-            width = gs[0].width;
-            gb.nq = (uint32_t)nq;
-            gb.node_off = node_off.data();
-            gb.edge_off = edge_off.data();
-            gb.node_pos = npos.data();
-            gb.node_mask = nmask.data();
-            gb.node_weight = nw.data();
-            gb.pred_off = poff.data();
-            gb.pred = pred.data();
-            gb.succ_minpos = smin.data();
-            gb.width = width;
-            gb.node_score16 = o.fs_no_graph ? nscore.data() : nullptr;
-            gb.self_score16 = o.fs_no_graph ? self16 : nullptr;
-            ph.reset(), ph.reset(new scoped_phase("al.align_graphs(C-ABI)"));  // (the old phase ends first: the new one names the pool jobs)
-            if (o.wide_fallback)
-                hip_check(sina_hip_align_graphs_any(ctx, &gb, qmask, qoff.data(), &p, out.data(), out_pos),
-                          "align_graphs_any");
-            else
-                hip_check(sina_hip_align_graphs(ctx, &gb, qmask, qoff.data(), &p, out.data(), out_pos),
-                          "align_graphs");
-        };
-        // wide-fallback: a group the device builders refuse because a family exceeds one of their documented limits
-        // is redone once over host-built graphs; any other failure propagates
-        auto device_route = [&](int rc, const char *what) {
-            if (rc != 0 && o.wide_fallback && sina_hip_last_error_is_limit() == 1) host_graph_route();
-            else hip_check(rc, what);
-        };
-        if (graph_on_device) {
-            std::vector<uint64_t> foff(nq + 1, 0);
-            for (size_t x = 0; x < nq; x++) foff[x + 1] = foff[x] + jobs[idx[x]].family_size();
-            std::vector<uint32_t> fids(foff.back() ? foff.back() : 1);
-            parallel_for(nq, [&](size_t x) {
-                const dp_job &jb = jobs[idx[x]];
-                for (size_t y = 0; y < jb.family_size(); y++) fids[foff[x] + y] = store->id_of(jb.member(y));
-            });
-            width = store->getAlignmentWidth();
-            if (o.fs_no_graph) {
-                ph.reset(), ph.reset(new scoped_phase("al.align_profiles(C-ABI)"));  // (the old phase ends first: the new one names the pool jobs)
-                device_route(sina_hip_align_profiles(ctx, fids.data(), foff.data(), (uint32_t)nq, qmask, qoff.data(),
-                                                     &p, out.data(), out_pos),
-                             "align_profiles");
-            } else {
-                ph.reset(), ph.reset(new scoped_phase("al.align_families(C-ABI)"));  // (the old phase ends first: the new one names the pool jobs)
-                device_route(sina_hip_align_families(ctx, fids.data(), foff.data(), (uint32_t)nq, qmask, qoff.data(),
-                                                     &p, out.data(), out_pos),
-                             "align_families");
-            }
-        } else {
-            host_graph_route();
         }
-        }   // ---- (end of the device's share)
-
-        const uint32_t *const staged_pos = sina_hip_staged_out_pos(ctx);
-        // cseq container steps of backtrack() (src/mesh.h:603-736) + do_align attrs (:507-509)
-        ph.reset(), ph.reset(new scoped_phase("al.finish(NAST,log)"));  // (the old phase ends first: the new one names the pool jobs)
-        parallel_for(nq, [&](size_t x) {
-            dp_job &jb = jobs[idx[x]];
-            tray &t = *jb.t;
-            const sina_hip_align_out &r = out[slot_of[x]];
-            if (r.status != 0) throw std::runtime_error("device alignment failed for " + t.input_sequence->getName());
-            uint64_t tk = host_tsc();
-            // the working copy: name and attributes of the input plus do_align's own (src/align.cpp:507-509,455-457),
-            // made in one pass (cseq.h copy_meta_with); its bases follow
-            const float score_q = r.raw / r.sum_weight;
-            const std::string &date_text = make_datetime();
-            const std::string &filter_name = t.astats->getName();
-            struct keys_t {
-                const std::string *head = cseq::attr_key(fn::head), *tail = cseq::attr_key(fn::tail), *filter = cseq::attr_key(fn::filter),
-                                  *qual = cseq::attr_key(fn::qual), *date = cseq::attr_key(fn::date);
-            };
-            static const keys_t keys;  // ("align_cutoff_head_slv" < "align_cutoff_tail_slv" < "align_filter_slv" < "align_quality_slv" < "aligned_slv")
-            const cseq::attr_init extra[5] = {
-                cseq::attr_init::of(keys.head, (int)r.cutoff_head),
-                cseq::attr_init::of(keys.tail, (int)r.cutoff_tail),
-                cseq::attr_init::of(keys.filter, std::string_view(filter_name)),
-                cseq::attr_init::of(keys.qual, (int)std::min(100.f, std::max(0.f, 100.f * score_q))),
-                cseq::attr_init::of(keys.date, std::string_view(date_text)),
-            };
-            cseq &c = *object_cache<cseq, cache_aligned_seq>::take();
-            jb.c = &c;
-            c.copy_meta_with(*t.input_sequence, extra, 5);
-            tk = host_tick("finish: working copy + attributes", tk);
-            const uint32_t L = (uint32_t)t.input_sequence->size();
-            const uint32_t *pos = staged_pos + dqoff[slot_of[x]];
-            if (r.assembled) {
-                // the device did the container steps (append rule, setWidth, reverse) and a NAST fix-up
-                // in which every insertion fitted its gap: the finished bases, and the fix-up's log line
-                c.clearSequence();
-                base_vector &fin = c.mutableAlignedBases();  // (a recycled sequence: no allocation)
-                // (one pass, past the cache: base lists are not zeroed by resize() -- cseq.h, base_block_allocator -- and
-                // nobody reads the finished list before a sink takes it)
-                fin.resize(r.n_out);
-                stream_copy(static_cast<void *>(fin.data()), pos, sizeof(aligned_base) * (size_t)r.n_out);
-                c.setWidth(width);
-                tk = host_tick("finish: assemble", tk);
-                if (o.insertion == INSERTION_REMOVE) t.log << "insertion=remove not implemented, using shift; ";
-                if (r.nast_total > 0)
-                    t.log << "total inserted bases=" << r.nast_total << ";"
-                          << "longest insertion=" << r.nast_longest << ";"
-                          << "total inserted bases before shifting=" << r.nast_last_run << ";";
-            } else {
-            // query bases: the input's, upper-cased unless --lowercase=original (src/align.cpp:324-326)
-            const uint32_t *qraw = t.input_sequence->packed();
-            const uint32_t keep_case = o.lowercase == LOWERCASE_ORIGINAL ? 0xFFFFFFFFu : ~((uint32_t)16 << 24);
-            const uint32_t lower_bit = o.lowercase == LOWERCASE_UNALIGNED ? (uint32_t)16 << 24 : 0u;
-            auto qbase = [&](uint32_t i, bool overhang_base) -> uint32_t {  // base bits of query base i, in place
-                return ((qraw[i] & keep_case) & 0xFF000000u) | (overhang_base ? lower_bit : 0u);
-            };
-            const bool keep_over = (o.overhang != OVERHANG_REMOVE);
-            const uint32_t tail = keep_over ? (uint32_t)r.cutoff_tail : 0;
-            const uint32_t head = keep_over ? (uint32_t)r.cutoff_head : 0;
-            const uint32_t n_out = tail + (uint32_t)r.aligned_bases + head;
-            // The container steps of backtrack() (src/mesh.h:603-726) in one pass: every emitted base is
-            // appended under the container rule (a column left of the current width is moved up to it,
-            // src/cseq.cpp:79-95), then the sequence is reversed (order and columns, :283-289).  The
-            // columns after the rule never decrease, so the result is written back to front directly.
-            c.clearSequence();
-            base_vector &fin = c.mutableAlignedBases();  // (a recycled sequence: no allocation)
-            fin.resize(n_out);
-            uint32_t reach = 0;  // alignment_width while appending (clearSequence: 0)
-            bool direct = true;
-            {
-                uint32_t n = 0;
-                auto put = [&](uint32_t column, uint32_t base_bits) {
-                    if (column >= reach) reach = column;
-                    else column = reach;
-                    if (column >= width) direct = false;  // (setWidth would have to repack: the general way below)
-                    fin[n_out - 1 - n] = aligned_base::from_raw(((width - 1 - column) & 0xFFFFFFu) | base_bits);
-                    n++;
-                };
-                for (uint32_t k = 0; k < tail; k++) put(pos[n], qbase(L - 1 - k, true));
-                for (int k = 0; k < r.aligned_bases; k++) put(pos[n], qbase((uint32_t)r.end_s - (uint32_t)k, false));
-                for (uint32_t k = 0; k < head; k++) put(pos[n], qbase((uint32_t)r.cutoff_head - 1 - k, true));
-            }
-            if (direct) {
-                c.setWidth(width);
-            } else {  // the same through the container's own operations
-                c.clearSequence();
-                uint32_t n = 0;
-                for (uint32_t k = 0; k < tail; k++, n++) c.append(aligned_base::from_raw((pos[n] & 0xFFFFFFu) | qbase(L - 1 - k, true)));
-                for (int k = 0; k < r.aligned_bases; k++, n++)
-                    c.append(aligned_base::from_raw((pos[n] & 0xFFFFFFu) | qbase((uint32_t)r.end_s - (uint32_t)k, false)));
-                for (uint32_t k = 0; k < head; k++, n++)
-                    c.append(aligned_base::from_raw((pos[n] & 0xFFFFFFu) | qbase((uint32_t)r.cutoff_head - 1 - k, true)));
-                c.setWidth(width);
-                c.reverse();
-            }
-            tk = host_tick("finish: assemble", tk);
-            c.fix_duplicate_positions(t.log, o.lowercase == LOWERCASE_UNALIGNED, o.insertion == INSERTION_REMOVE);
-            tk = host_tick("finish: NAST fix-up", tk);
-            }
-            if (c.getWidth() > width) t.log << "warning: result sequence too wide!";
-            const float rval = r.raw, sum_weight = r.sum_weight;
-            const float score = rval / sum_weight;
-            // (the line itself is rendered when the log is read: tray::score_note -- or at once, for a caller that
-            // reads the stream itself)
-            {
-                const tray::score_note note{rval, sum_weight, score, L, (int32_t)r.aligned_bases, (uint32_t)t.log.view().size(), true};
-                if (defer_score_line) {
-                    t.pending_score = note;
-                } else {
-                    char line[192];
-                    t.log.write(line, (std::streamsize)note.render(line, sizeof line));
-                }
-            }
-            tk = host_tick("finish: score log text", tk);
-            if (o.write_used_rels) {
-                std::string s;
-                for (size_t y = 0; y < jb.family_size(); y++) s += jb.member(y)->getName() + " ";
-                c.set_attr(fn::used_rels, s);
-            }
-            t.aligned_sequence = &c;
-            host_tick("finish: attributes", tk);
-        });
-
-        // --calc-idty (src/align.cpp:443-453): best overlap identity of the aligned query with a member
-        // of its family -- one comparison launch for the group (sina_hip_compare)
-        if (o.calc_idty) {
-            scoped_phase ph_idty("al.calc_idty(C-ABI)");
-            std::vector<uint64_t> qoff(nq + 1, 0), coff(nq + 1, 0);
-            for (size_t x = 0; x < nq; x++) {
-                qoff[x + 1] = qoff[x] + jobs[idx[x]].c->size();
-                coff[x + 1] = coff[x] + jobs[idx[x]].family_size();
-            }
-            std::vector<uint32_t> qab(qoff.back() ? qoff.back() : 1), cids(coff.back() ? coff.back() : 1);
-            for (size_t x = 0; x < nq; x++) {
-                const cseq &c = *jobs[idx[x]].c;
-                memcpy(qab.data() + qoff[x], c.packed(), 4 * (size_t)c.size());
-                for (size_t y = 0; y < jobs[idx[x]].family_size(); y++)
-                    cids[coff[x] + y] = store->id_of(jobs[idx[x]].member(y));
-            }
-            std::vector<sina_hip_match_counts> counts(coff.back() ? coff.back() : 1);
-            auto dev = store->worker_device(reference_store::dev_compare);
-            hip_check(sina_hip_compare(dev.get(), qab.data(), qoff.data(), (uint32_t)nq, cids.data(), coff.data(),
-                                       SINA_CMP_IUPAC_OPTIMISTIC, 0, counts.data()),
-                      "sina_hip_compare");
-            const cseq_comparator calc_id(CMP_IUPAC_OPTIMISTIC, CMP_DIST_NONE, CMP_COVER_OVERLAP, false);
-            for (size_t x = 0; x < nq; x++) {
-                float idty = 0;
-                for (uint64_t y = coff[x]; y < coff[x + 1]; y++) idty = std::max(idty, calc_id.score(counts[y]));
-                jobs[idx[x]].c->set_attr(fn::idty, 100.f * idty);
-            }
-        }
+        if (o.calc_idty) set_family_identity(members, *store);  // (its own context, while this group's is still leased)
     }
+}
+
+tray aligner::operator()(tray t) {
+    std::vector<tray> b{t};
+    (*this)(b);
+    return b[0];
 }
 
 // ================================================================ cseq_comparator (src/cseq_comparator.cpp)
@@ -2523,36 +2586,27 @@ void search_filter::operator()(std::vector<tray> &batch) {
                 pairs += k;
                 x1++;
             }
-            std::vector<uint64_t> qoff(x1 - x0 + 1, 0), coff(x1 - x0 + 1, 0);
-            for (size_t x = x0; x < x1; x++) {
-                qoff[x - x0 + 1] = qoff[x - x0] + batch[idx[x]].aligned_sequence->size();
-                coff[x - x0 + 1] = coff[x - x0] + (o.search_all ? n_refs : cand[x].size());
-            }
-            std::vector<uint32_t> qab(qoff.back() ? qoff.back() : 1), cids(coff.back() ? coff.back() : 1);
-            for (size_t x = x0; x < x1; x++) {
-                const cseq &c = *batch[idx[x]].aligned_sequence;
-                memcpy(qab.data() + qoff[x - x0], c.packed(), 4 * (size_t)c.size());
-                uint32_t *dst = cids.data() + coff[x - x0];
-                if (o.search_all) {
-                    for (unsigned r = 0; r < n_refs; r++) dst[r] = r;
-                } else {
-                    for (size_t r = 0; r < cand[x].size(); r++) dst[r] = st.id_of(cand[x][r].sequence);
-                }
-            }
-            std::vector<sina_hip_match_counts> counts(coff.back() ? coff.back() : 1);
-            if (coff.back())
-                hip_check(sina_hip_compare(dev.get(), qab.data(), qoff.data(), (uint32_t)(x1 - x0), cids.data(),
-                                           coff.data(), (int)o.comparator.iupac_rule,
-                                           o.comparator.filter_lc_rule ? 1 : 0, counts.data()),
-                          "sina_hip_compare");
-            for (size_t x = x0; x < x1; x++) {
-                const sina_hip_match_counts *m = counts.data() + coff[x - x0];
-                if (o.search_all) {
-                    cand[x].clear();
-                    cand[x].reserve(n_refs);
-                    for (unsigned r = 0; r < n_refs; r++) cand[x].emplace_back(o.comparator.score(m[r]), &st.getCseq(r));
-                } else {
-                    for (size_t r = 0; r < cand[x].size(); r++) cand[x][r].score = o.comparator.score(m[r]);
+            if (pairs) {  // (a slice without a single candidate is not sent -- and has no scores to take)
+                const pair_counts pc = compare_packed(
+                    dev.get(), x1 - x0, [&](size_t x) -> const cseq & { return *batch[idx[x0 + x]].aligned_sequence; },
+                    [&](size_t x) { return o.search_all ? (size_t)n_refs : cand[x0 + x].size(); },
+                    [&](size_t x, uint32_t *dst) {
+                        if (o.search_all) {
+                            for (unsigned r = 0; r < n_refs; r++) dst[r] = r;
+                        } else {
+                            for (size_t r = 0; r < cand[x0 + x].size(); r++) dst[r] = st.id_of(cand[x0 + x][r].sequence);
+                        }
+                    },
+                    (int)o.comparator.iupac_rule, o.comparator.filter_lc_rule ? 1 : 0);
+                for (size_t x = x0; x < x1; x++) {
+                    const sina_hip_match_counts *m = pc.counts.data() + pc.coff[x - x0];
+                    if (o.search_all) {
+                        cand[x].clear();
+                        cand[x].reserve(n_refs);
+                        for (unsigned r = 0; r < n_refs; r++) cand[x].emplace_back(o.comparator.score(m[r]), &st.getCseq(r));
+                    } else {
+                        for (size_t r = 0; r < cand[x].size(); r++) cand[x][r].score = o.comparator.score(m[r]);
+                    }
                 }
             }
             x0 = x1;

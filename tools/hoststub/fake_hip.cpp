@@ -24,6 +24,7 @@ static thread_local std::string g_err;
 extern "C" {
 int sina_hip_abi_version(void) { return SINA_HIP_ABI_VERSION; }
 const char *sina_hip_last_error(void) { return g_err.c_str(); }
+int sina_hip_last_error_is_limit(void) { return 0; }
 int sina_hip_init(int, sina_hip_ctx **ctx) {
     *ctx = new sina_hip_ctx();
     (*ctx)->root = *ctx;
@@ -101,5 +102,9 @@ int sina_hip_align_families(sina_hip_ctx *c, const uint32_t *, const uint64_t *,
 }
 int sina_hip_align_graphs(sina_hip_ctx *, const sina_hip_graph_batch *, const uint8_t *, const uint64_t *,
                           const sina_hip_align_params *, sina_hip_align_out *, uint32_t *) { g_err = "stub"; return 1; }
+int sina_hip_align_graphs_any(sina_hip_ctx *, const sina_hip_graph_batch *, const uint8_t *, const uint64_t *,
+                              const sina_hip_align_params *, sina_hip_align_out *, uint32_t *) { g_err = "stub"; return 1; }
+int sina_hip_align_profiles(sina_hip_ctx *, const uint32_t *, const uint64_t *, uint32_t, const uint8_t *, const uint64_t *,
+                            const sina_hip_align_params *, sina_hip_align_out *, uint32_t *) { g_err = "stub"; return 1; }
 int sina_hip_get_stats(sina_hip_ctx *, sina_hip_stats *s) { memset(s, 0, sizeof *s); return 0; }
 }
