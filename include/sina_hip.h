@@ -324,10 +324,15 @@ typedef struct sina_hip_dp_info {
     uint32_t rows_swept, cells_swept, attempts;
     float gain0, ubound;
     uint32_t prune_step, prune_gmin;
-    float scout;  /* what the scout pass found for this query (the first attempt's bound U); NaN: the launch had none */
+    float scout;  /* what the scout pass found for this query (the first attempt's bound U; +inf: the band never met the
+                   * query's last column); NaN: the launch had none */
 } sina_hip_dp_info;
 int sina_hip_debug_dp_info(sina_hip_ctx *ctx, uint32_t q, sina_hip_dp_info *out);
 int sina_hip_debug_rgain(sina_hip_ctx *ctx, uint32_t n, uint32_t *out, uint32_t *cols_right /* C(m), may be NULL */);
+/* Test hook for the scout pass: the chain the last DAG build (a launch's, or sina_hip_debug_family_graph's) left for its
+ * FIRST DAG -- the node of every base of the family's first member, in base order.  *len: the member's bases; the
+ * first min(*len, cap) node ids go to out. */
+int sina_hip_debug_chain_rows(sina_hip_ctx *ctx, uint16_t *out, uint32_t cap, uint32_t *len);
 
 /* Test hook: the DAG the GPU builds for ONE family (ids into the uploaded store, in family
  * order), in compact CSR form, for comparison with mseq (src/mseq.cpp:47-118).
@@ -386,9 +391,9 @@ typedef struct sina_hip_stats {
                                     (row records, columns, row-skip bounds, predecessor lists) written once; a device
                                     profile build counts the same way (its nodes carry 64 bytes of match terms each) */
     uint32_t graph_launches, kmer_queries; /* DAG-build and profile-build launches; queries searched by the k-mer count kernel */
-    double scout_ms;             /* the scout pass (a bound on the optimum per query from a banded sweep, one lane per
-                                    query): launch to end, on the context's own stream beside other batches' kernels    */
-    uint32_t scout_launches, pad_;
+    double scout_ms;             /* always 0: the scout pass (a bound on the optimum per query from a banded sweep) is the
+                                    first thing a DP wave does and has no time of its own (kept: the struct's layout)  */
+    uint32_t scout_launches, pad_; /* DP launches whose waves ran the scout pass */
 } sina_hip_stats;
 int sina_hip_get_stats(sina_hip_ctx *ctx, sina_hip_stats *s);
 

@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "sina_hip_store_alloc_like", "sina_hip_kmer_topk", "sina_hip_kmer_scores", "sina_hip_compare",
     "sina_hip_align_params_default", "sina_hip_staged_out_pos", "sina_hip_align_graphs", "sina_hip_align_families",
     "sina_hip_align_profiles", "sina_hip_debug_family_profile",
-    "sina_hip_debug_mesh", "sina_hip_debug_family_graph", "sina_hip_debug_dp_info", "sina_hip_debug_rgain", "sina_hip_get_stats",
+    "sina_hip_debug_mesh", "sina_hip_debug_family_graph", "sina_hip_debug_dp_info", "sina_hip_debug_rgain", "sina_hip_debug_chain_rows", "sina_hip_get_stats",
     "sina_hip_align_graphs_any", "sina_hip_debug_mesh_wide", "sina_hip_wide_queries", "sina_hip_last_error_is_limit",
 ]
 
@@ -451,6 +451,14 @@ class Context:
         cols = np.zeros(max(n, 1), np.uint32)
         self._check(self.L.sina_hip_debug_rgain(self.h, n, _ptr(out, u32p), _ptr(cols, u32p)))
         return out[:n], cols[:n]
+
+    def chain_rows(self):
+        """The chain the last DAG build left for its first DAG: the node of every base of the family's first member."""
+        cap = 65536
+        out = np.zeros(cap, np.uint16)
+        n = C.c_uint32()
+        self._check(self.L.sina_hip_debug_chain_rows(self.h, out.ctypes.data_as(C.POINTER(C.c_uint16)), cap, C.byref(n)))
+        return out[:min(n.value, cap)].copy()
 
     def stats(self):
         s = Stats()

@@ -219,7 +219,7 @@ static int prep_range(const sina_hip_graph_batch *g, const uint64_t *qoff, uint3
 int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint32_t bq, uint64_t n_node_entries,
                   uint64_t tb_cells, uint64_t spill_rows, uint64_t cells, uint64_t nqm, const sina_hip_align_params *p, uint32_t width,
                   sina_hip_align_out *out, uint32_t *out_pos, bool want_dbg_value, const PrunePlan &pp,
-                  const uint32_t *chain_ref) {
+                  uint32_t chain_ncap) {
     hipStream_t s = c->stream;
     const int Lp = pl.geom.Lp();
     const bool weighted = p->weights != nullptr && p->n_weights > 0;
@@ -252,7 +252,6 @@ int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint3
     a.node_pos = c->node_pos.as<uint32_t>();
     a.succ_minpos = c->succ_minpos.as<uint32_t>();
     a.qmask = c->qmask.as<uint8_t>();
-    a.tb = nullptr;  // (the plane is borrowed below, once the scout is back)
     a.dbg_value = want_dbg_value ? c->dbg.as<float>() : nullptr;
     a.spill = c->spill.as<float>();
     a.edge = c->edge.as<EdgeRec>();
@@ -289,12 +288,15 @@ int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint3
         for (uint32_t q = 0; q < bq; q++) max_n = std::max<uint32_t>(max_n, qd_host[q].N);
         a.below_init = (!weighted && !forbid && dp_below_init(max_n, a.gp, a.gpe)) ? 1 : 0;
     }
-    // The scout pass (scout.hip): every query's own bound U -- the cost of a real path, its alignment against the chain
-    // of its family's first member -- instead of the store's guess alone.  On the context's own stream (150 waves, a
-    // lane per query: not a device-filling kernel), before the launch borrows a trace-back plane and asks for its place
-    // in the FIFO.  A fixed guess (SINA_HIP_TEST=rho=) or SINA_HIP_TEST=scout=0 leaves it out, and so does a caller
-    // that brought its own DAGs (sina_hip_align_graphs: no family to take a chain from).
+    // The scout pass (mesh_dp.hip, chain_scout_wave): every query's own bound U -- the cost of a real path, its alignment
+    // against the chain of its family's first member -- instead of the store's guess alone.  It is the first thing the
+    // query's DP wave does: no launch, no event and nothing for the host to wait for.  A fixed guess
+    // (SINA_HIP_TEST=rho=) or SINA_HIP_TEST=scout=0 leaves it out, and so does a caller that brought its own DAGs
+    // (sina_hip_align_graphs: no family to take a chain from).
     a.scout_u = nullptr;
+    a.chain_rows = nullptr;
+    a.chain_sizes = nullptr;
+    a.chain_ncap = 0;
     a.scout_bias = (float)atof(test_knob("scout_add").c_str());
     c->last_scout = false;
     if (const std::string fixed = test_knob("scout_set"); !fixed.empty() && pp.on && !rho_fixed) {
@@ -305,32 +307,23 @@ int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint3
         if (upload(c, 7, c->scout_u.p, vals.data(), 4 * (size_t)bq, s)) return 1;
         a.scout_u = c->scout_u.as<float>();
         c->last_scout = true;
-    } else if (chain_ref != nullptr && pp.on && !rho_fixed && a.below_init && a.gp >= a.gpe && pl.geom.T > 64 && test_knob("scout") != "0") {
-        if (c->scout.reserve(4 * (size_t)bq) || c->scout_u.reserve(4 * (size_t)bq)) return 1;
-        if (upload(c, 7, c->scout.p, chain_ref, 4 * (size_t)bq, s)) return 1;
-        SH_CHECK(hipEventRecord(c->ev[3], s));
-        if (launch_chain_scout(a, bq, c->st->ref_ab.as<uint32_t>(), c->st->ref_off.as<uint64_t>(), c->scout.as<uint32_t>(),
-                               c->scout_u.as<float>(), s))
-            return 1;
-        SH_CHECK(hipEventRecord(c->ev[4], s));
-        SH_CHECK(wait_event(c->ev[4]));
-        float sms = 0;
-        SH_CHECK(hipEventElapsedTime(&sms, c->ev[3], c->ev[4]));
-        {
-            std::lock_guard<std::mutex> slk(c->st->stats_mu);
-            c->st->stats.scout_ms += sms;
-            c->st->stats.scout_launches++;
-        }
+    } else if (chain_ncap != 0 && !weighted && !forbid && pp.on && !rho_fixed && a.below_init && a.gp >= a.gpe && pl.geom.T > 64 &&
+               test_knob("scout") != "0" && atoi(test_knob("generic").c_str()) == 0) {
+        if (c->scout_u.reserve(4 * (size_t)bq)) return 1;
         a.scout_u = c->scout_u.as<float>();
+        a.chain_rows = c->scout.as<uint16_t>();
+        a.chain_sizes = c->g_sizes.as<uint32_t>();
+        a.chain_ncap = chain_ncap;
         c->last_scout = true;
+        std::lock_guard<std::mutex> slk(c->st->stats_mu);
+        c->st->stats.scout_launches++;  // (DP launches whose waves ran the pass; it has no time of its own: scout_ms stays 0)
     }
     if (a.scout_u != nullptr && !rho_fixed) {
         std::lock_guard<std::mutex> slk(c->st->stats_mu);
         a.prune_rho = c->st->prune_rho_guard;
     }
     // The trace-back plane is the one buffer whose size follows the batch (tens of GB for 16S): borrowed
-    // from the device's pool of two (ctx.h) until this launch's results are on the host -- and not before the scout
-    // is back: a launch waiting for its scout does not hold a plane another launch could fill meanwhile.
+    // from the device's pool of two (ctx.h) until this launch's results are on the host.
     const uint64_t tb_bytes = tb_cell_bytes(forbid) * tb_cells;
     tb_plane_lease plane;
     if (plane.acquire(c, std::max<uint64_t>(tb_bytes, 16))) return 1;
@@ -1017,6 +1010,19 @@ int sina_hip_debug_rgain(sina_hip_ctx *c, uint32_t n, uint32_t *out, uint32_t *c
         out[i] = tmp[i].x;
         if (cols_right) cols_right[i] = tmp[i].y >> 16;
     }
+    return 0;
+}
+
+int sina_hip_debug_chain_rows(sina_hip_ctx *c, uint16_t *out, uint32_t cap, uint32_t *len) {
+    if (!c || !out || !len) SH_FAIL("debug_chain_rows: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scout.p || !c->g_sizes.p) SH_FAIL("debug_chain_rows: no device-built DAG in this context");
+    SH_CHECK(hipSetDevice(c->device));
+    uint32_t sizes[kBuiltWords];
+    SH_CHECK(hipMemcpy(sizes, c->g_sizes.p, sizeof sizes, hipMemcpyDeviceToHost));
+    *len = sizes[kBuiltChainLen];
+    const size_t n = std::min<size_t>(std::min<uint32_t>(*len, cap), c->scout.cap / 2);
+    if (n) SH_CHECK(hipMemcpy(out, c->scout.p, 2 * n, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -311,6 +311,9 @@ inline bool dp_below_init(uint32_t max_n, float gp, float gpe) {
     return gp >= 0.f && gpe >= 0.f && 1.0f + (float)max_n * gp * 1.01f + gp + gpe < 900000.0f;
 }
 
+constexpr int kBuiltWords = 8;     // u32 words a device builder reports per family (BuiltGraphs::sizes, ctx.h)
+constexpr int kBuiltChainLen = 6;  // ... of which this one is the number of bases of member 0: the length of its chain
+
 struct DpArgs {
     const QDesc *qd;
     const uint32_t *order;      // workgroup -> query (decreasing N*L)
@@ -339,7 +342,13 @@ struct DpArgs {
     float prune_rho;
     uint32_t prune_amax;
     float scout_bias;           // test hook (SINA_HIP_TEST=scout_add=<x>): added to every scout value -- a scout forced wrong
-    const float *scout_u;       // per query: the cost of a real path (scout.hip), the first attempt's bound U; nullptr: the guess rho
+    float *scout_u;             // per query: the cost of a real path, the first attempt's bound U; nullptr: the guess rho
+    // the scout pass in the DP wave (mesh_dp.hip, chain_scout_wave): the chain of every DAG's first member as the
+    // DAG build left it -- node ids [chain_ncap] per DAG, the per-DAG size words with the chain's length (ctx.h,
+    // kBuiltWords).  nullptr: scout_u, if any, already holds the values (SINA_HIP_TEST=scout_set=)
+    const uint16_t *chain_rows;
+    const uint32_t *chain_sizes;
+    uint32_t chain_ncap;
 };
 
 struct BtArgs {
@@ -384,11 +393,6 @@ int dp_max_ring(const DpGeom &g);  // deepest LDS ring the slot allocators suppo
 size_t dp_default_lds_budget(const DpGeom &g);  // LDS per workgroup that keeps the register-limited occupancy
 int launch_mesh_dp(const DpGeom &g, bool weighted, bool forbid, const DpArgs &a, uint32_t nq,
                    size_t lds_bytes, hipStream_t s);
-// the scout pass (scout.hip): per query the cost of its banded alignment (kScoutBand columns per row) against the chain
-// of its family's first member -- a real path of the mesh, the first attempt's bound U
-constexpr int kScoutBand = 8;
-int launch_chain_scout(const DpArgs &a, uint32_t nq, const uint32_t *ref_ab, const uint64_t *ref_off,
-                       const uint32_t *chain_ref /* device: [nq] reference ids */, float *out_u /* [nq] */, hipStream_t s);
 int launch_backtrack(const BtArgs &a, hipStream_t s);
 bool backtrack_by_lanes(const BtArgs &a);  // one lane per query (large launches of 16S-long queries), else one wave per query
 int launch_assemble(const BtArgs &a, hipStream_t s);  // (after launch_backtrack, same stream)
@@ -409,11 +413,12 @@ struct sina_hip_ctx;
 namespace sina_hip {
 int plan_dp(sina_hip_ctx *c, uint32_t maxL, DpPlan *pl);
 int upload_weights(sina_hip_ctx *c, const sina_hip_align_params *p);
-// chain_ref: per query the reference id of its family's first member (host; nullptr: the DAGs are the caller's, no scout)
+// chain_ncap: node entries per DAG of the device-built DAGs whose first member's chain the build left in the
+// context (ctx.h, scout); 0: the DAGs are the caller's or profiles -- no chain, no scout pass
 int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint32_t bq, uint64_t n_node_entries,
                   uint64_t tb_cells, uint64_t spill_rows, uint64_t cells, uint64_t nqm, const sina_hip_align_params *p, uint32_t width,
                   sina_hip_align_out *out, uint32_t *out_pos, bool want_dbg_value, const PrunePlan &pp,
-                  const uint32_t *chain_ref = nullptr);
+                  uint32_t chain_ncap = 0);
 // What a launch may skip rows with (api.hip): the scoring of `p` (non-negative gap costs, the simple scheme), the
 // largest and smallest node weight it will see, its longest query.  SINA_HIP_DP_PRUNE=0: never.
 PrunePlan prune_plan(const sina_hip_align_params *p, float wmax, float wmin, uint32_t maxL, bool profile_batch);

@@ -117,7 +117,7 @@ struct sina_hip_ctx {
     // the trace-back pool above, allocated by the first query that needs it
     sina_hip::DevBuf wide_in, wide_planes;
     uint64_t wide_queries = 0;        // queries the wide kernel has aligned on this context (sina_hip_wide_queries)
-    sina_hip::DevBuf scout, scout_u;  // the scout pass (scout.hip): its band rows, and its result -- a bound U per query
+    sina_hip::DevBuf scout, scout_u;  // the scout pass (mesh_dp.hip): the DAG build's chain rows (u16 [DAGs][ncap]), and its result -- a bound U per query
     sina_hip::HostBuf h_res;          // pinned copy of a launch's DpResults (row-skip statistics, the next launch's guess)
     bool profile_batch = false;       // the launch being prepared is one (set by sina_hip_align_graphs)
     void *last_tb = nullptr;  // the plane of the last launch (debug read-back: sina_hip_debug_mesh)
@@ -482,10 +482,10 @@ struct heavy_launch {
                     return o;
                 };
                 // (round 6: a DAG build, then a k-mer search, goes before a DP launch WHENEVER one waits, not only
-                // behind a DP launch: a batch's scout pass runs between its DAG build and its DP launch, on the
-                // context's own stream -- with the build scheduled right in front of the batch's own DP launch the
-                // FIFO sat idle for the scout's 4.5 ms every step (profiles/r06_heavy_gaps_before.txt); built a DP
-                // launch earlier, the scout runs beside the DP launch of the batch before)
+                // behind a DP launch: a batch's scout pass then ran as a kernel between its DAG build and its DP
+                // launch, and with the build scheduled right in front of the batch's own DP launch the FIFO sat idle
+                // for the scout's 4.5 ms every step (profiles/r06_heavy_gaps_before.txt).  The scout has since moved
+                // into the DP wave (mesh_dp.hip, chain_scout_wave); the order is kept)
                 const sina_hip_store::heavy_waiter *pick = oldest_of(kHeavyGraph);
                 if (!pick) pick = oldest_of(kHeavyKmer);
                 if (!pick) pick = oldest_of(-1);
@@ -578,13 +578,12 @@ namespace sina_hip {
 // ---- alignment against device-built templates: sina_hip_align_families (the family as a DAG, graph_build.hip) and
 // sina_hip_align_profiles (the family as a profile, profile_build.hip) differ in the builder only
 constexpr int kFamilyMax = 128;  // members of a family the device builders take (their per-member LDS records)
-constexpr int kBuiltWords = 8;   // u32 words a builder reports per family (BuiltGraphs::sizes)
 // What a builder left in the context's rec / node_pos / succ_minpos / pred (/ rgain, prof16) buffers for the n distinct
 // families of a chunk: family u's node arrays start at u * ncap, its predecessor entries at pred_off[u].
 struct BuiltGraphs {
     uint32_t ncap = 0;
     std::vector<uint64_t> pred_off;  // per family, into c->pred
-    std::vector<uint32_t> sizes;     // per family: kBuiltWords words -- N, raw edge entries, n_spill, status, first sink row, gmin
+    std::vector<uint32_t> sizes;     // per family: kBuiltWords words -- N, raw edge entries, n_spill, status, first sink row, gmin, bases of member 0 (its chain: GraphArgs::chain_rows)
 };
 // Builds the templates of families q0 .. q0 + n - 1 (fam_off is absolute); pp: the row skip the launches will run with
 using family_builder = int (*)(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t q0, uint32_t n,

@@ -27,7 +27,8 @@
 //      over from earlier tiles); member count and raw edge count of the node by atomicAdd; the
 //      predecessor as ONE BIT of a 64-bit word per node (bit d-1: the node d ids back -- ids ascend
 //      with the column, so the set bits from the top down are the predecessors ascending and unique);
-//      the few predecessors further back than 64 ids (long deletions) by rounds of atomicMin;
+//      the few predecessors further back than 64 ids (long deletions) by rounds of atomicMin; the entries of
+//      member 0 also leave their node in chain_rows -- the chain the DP wave's scout pass walks (mesh_dp.hip);
 //   5. one thread per node writes record and predecessor list; atomicMin / atomicMax collect the
 //      successor minimum column (for --insertion=forbid) and the last successor;
 //   6. sinks and fence flags; LDS-slot / spill-row assignment for the DP kernel by liveness
@@ -90,7 +91,8 @@ struct GraphArgs {
     uint32_t *succ_min;        // [nq][ncap]
     uint32_t *far_mark;        // [nq][ncap] last successor row of every node (0: none)
     uint32_t *pred;            // per query area of total-family-bases entries
-    uint32_t *sizes;           // [nq][kSz]: N, raw edge entries, n_spill, status (0 ok, 2 N cap, 4 spill rows), first sink row
+    uint32_t *sizes;           // [nq][kSz]: N, raw edge entries, n_spill, status (0 ok, 2 N cap, 4 spill rows), first sink row, gmin, chain length
+    uint16_t *chain_rows;      // [nq][ncap]: the node of every base of member 0, in base order (the DP wave's scout pass walks this chain)
     uint32_t width, ncap;
     uint32_t tile_bytes;       // LDS bytes of the tile tables (reused by the slot allocation) = bitmap_off
     uint32_t bitmap_off;       // LDS offset of the occupied-column bitmap (behind the tile tables)
@@ -381,6 +383,7 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
     uint32_t *smin = a.succ_min + (size_t)q * a.ncap;
     uint32_t *last = a.far_mark + (size_t)q * a.ncap;
     uint32_t *pred = a.pred + a.pred_off[q];
+    uint16_t *chain_rows = a.chain_rows + (size_t)q * a.ncap;
     // (smin / last of a node are initialised by the tile that creates it, right before the first successor can
     // touch them: clearing all ncap entries up front wrote four times what a 16S DAG uses)
     const float *wt = a.wtab + (size_t)F * (kMaxFam + 1);
@@ -477,6 +480,9 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
                     const bool first = (ev & kEFirst) != 0;
                     atomicAdd(&wA[ln - w0], first ? 1u : 0x10001u);
                     if (mb[j].cur + slot + 1 == mb[j].curn) mb[j].carryn = node;
+                    // (member 0's chain: entry `slot` of the tile is its base cur + slot; a member has at most one base
+                    // per column, so the index stays below the node count -- and below ncap unless the build overflows)
+                    if (j == 0 && mb[0].cur + slot < a.ncap) chain_rows[mb[0].cur + slot] = (uint16_t)node;
                     if (!first) {
                         if (slot && (lane == 0 || !left_mine)) lnp = node_of(eE[j * (uint32_t)kTC + slot - 1]);
                         const uint32_t pn = slot ? N + lnp : mb[j].carry;
@@ -662,6 +668,7 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
             sz[2] = tot;
             sz[3] = (tot > kMaxSpillRows) ? 4u : 0u;
             sz[4] = s_tmp[kGT / 64 + 1];
+            sz[kBuiltChainLen] = mb[0].len;
         }
     }
     __syncthreads();
@@ -788,6 +795,7 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
             c->rec.reserve(sizeof(uint4) * (uint64_t)bq * ncap) || c->node_pos.reserve(4 * (uint64_t)bq * ncap) ||
             c->succ_minpos.reserve(4 * (uint64_t)bq * ncap) || c->g_tmp3.reserve(4 * (uint64_t)bq * ncap) ||
             c->pred.reserve(4 * pred_total) || c->g_sizes.reserve(4 * kSz * (uint64_t)bq) ||
+            c->scout.reserve(2 * (uint64_t)bq * ncap) ||
             (kappa64 > 0.f && c->rgain.reserve(8 * (uint64_t)bq * ncap)))
             return 1;
         if (upload(c, 1, c->g_fam_ids.p, fam_ids + fam_off[q0], 4 * foff[bq], s) ||
@@ -807,6 +815,7 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
         ga.far_mark = c->g_tmp3.as<uint32_t>();
         ga.pred = c->pred.as<uint32_t>();
         ga.sizes = c->g_sizes.as<uint32_t>();
+        ga.chain_rows = c->scout.as<uint16_t>();
         ga.width = c->st->width;
         ga.ncap = ncap;
         ga.bitmap_off = (uint32_t)graph_bitmap_off(max_f);
@@ -988,7 +997,6 @@ int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build,
             uint64_t tbc = 0, sprows = 0, cells = 0;
             uint32_t erec_cursor = 0;
             std::vector<QDesc> qd;
-            std::vector<uint32_t> chain_ref;  // per query: its family's first member (the scout's chain, scout.hip)
             while (r1 < bq) {
                 const uint32_t u = dag_of[r1];  // (this query's DAG among the chunk's distinct ones)
                 const uint32_t N = bg.sizes[kSz * u];
@@ -1007,7 +1015,6 @@ int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build,
                 d.erec_off = erec_cursor;
                 erec_cursor += dp_edge_entries(N);
                 qd.push_back(d);
-                chain_ref.push_back(fam_ids[fam_off[q0 + r1]]);
                 tbc += (uint64_t)N * Lp;
                 sprows += d.n_spill;
                 cells += (uint64_t)N * d.L;
@@ -1021,7 +1028,6 @@ int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build,
                     cells -= (uint64_t)qd[r - r0].N * qd[r - r0].L;
                 }
                 qd.resize(r1r - r0);
-                chain_ref.resize(r1r - r0);
                 r1 = r1r;
             }
             const uint32_t rq = r1 - r0;
@@ -1032,7 +1038,7 @@ int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build,
             c->profile_batch = profile_batch;  // (the DP reads the builder's prof16, the walk the entry point's self16)
             c->out_pos_base = qbase - qoff[0];
             if (run_dp_device(c, pl, qd.data(), rq, (uint64_t)n_dags * bg.ncap, tbc, sprows, cells, nqm, p, c->st->width,
-                              out + q0 + r0, out_pos ? out_pos + qbase : nullptr, false, pp, profile_batch ? nullptr : chain_ref.data()))
+                              out + q0 + r0, out_pos ? out_pos + qbase : nullptr, false, pp, profile_batch ? 0u : bg.ncap))
                 return 1;
             r0 = r1;
         }

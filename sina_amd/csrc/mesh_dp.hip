@@ -1013,6 +1013,135 @@ mesh_dp_kernel(const QDesc *__restrict__ qdv, const uint32_t *__restrict__ order
 // Everything else (weighted scheme, --insertion=forbid, gap_open < gap_extend, huge gap costs) runs
 // mesh_dp_kernel.  Results are bit-identical between the two: tests/test_gpu_parity.py runs every
 // simple-scheme plane test through both (SINA_HIP_TEST=generic=1 forces the generic kernel).
+// ---------------------------------------------------------------- the scout pass, inside the DP wave
+// A bound U on the optimum from a real path: the query against the CHAIN of its family's first member
+// -- the reference famfinder ranked first, its nearest relative.  Every member is a path through the family's DAG (its
+// bases' nodes, consecutive ones linked: mseq.cpp:47-118), so a banded alignment against that chain, scored with the
+// DAG's node weights and the operators of mesh.h:307-374 restricted to one predecessor per row, costs what some path
+// of the full mesh costs.  Nothing depends on how good it is: the skipping kernel certifies its result against U
+// whatever U is, and a failed certificate costs a second sweep, never a different result.
+//
+// How it maps to the hardware: the query's own DP wave does it before its first strip.  The band is 64 columns, one
+// cell per lane, fixed on the diagonal: lane k of chain row i holds query column i + k + c0.  The match term then
+// reads the lane's own previous value, the deletion term the right neighbour's (one DPP move each), and the query
+// bases move one lane to the left per row (one DPP move; the base entering at lane 63 comes from a vector the wave
+// loads once per 64 rows).  The chain's rows come 64 at a time too -- the node ids the DAG build left
+// (GraphArgs::chain_rows), then their records by one gather -- and reach a row by v_readlane: no LDS, no scalar
+// load per row.  The insertion chain along the row is the plain affine-gap one as a prefix minimum over the lanes
+// (six DPP steps): cell s = min(local, min over t < s of local[t] + gap_open + (s - t - 1) gap_extend).  No
+// re-centring: a query that leaves the band gets a poor U, and the guard of the store's guess takes over.
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ float dpp_mov(float old, float x) {  // lanes without a source (or outside ROW_MASK) keep `old`
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(x), CTRL, ROW_MASK, 0xf, false));
+}
+constexpr int kDppRowShr = 0x110, kDppWaveShl1 = 0x130, kDppWaveShr1 = 0x138, kDppBcast15 = 0x142, kDppBcast31 = 0x143;
+__device__ __forceinline__ float lane_value(float x, uint32_t k) {  // x of lane k (k wave-uniform): v_readlane
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), (int)k));
+}
+
+// chain: the node ids of member 0's bases [M]; rec: the DAG's N row records; qm: the query's L base masks
+__device__ __forceinline__ float chain_scout_wave(const uint4 *__restrict__ rec, const uint16_t *__restrict__ chain, uint32_t M,
+                                                  uint32_t N, uint32_t L, const uint8_t *__restrict__ qm, float ms, float mms,
+                                                  float gp, float gpe, int lane) {
+    constexpr float kUnreached = 1000000.0f;  // the reference's initial cell value (mesh.h:290)
+    const float inf = __builtin_inff();
+    // the diagonal the band sits on: through the middle of what the query is longer or shorter than its relative
+    int off = ((int)L - (int)M) / 2;
+    off = off < -24 ? -24 : (off > 24 ? 24 : off);
+    const int c0 = off - 32;
+    const float kg = (float)lane * gpe;  // what a gap that runs up to my lane has paid in extensions since lane 0
+    const float open = gp - gpe;
+    float pv = kUnreached, pg = kUnreached;  // the row before: value and gapm_val of the cell in my LANE (one column to the left)
+    float best = inf;
+    // (the base's four bits are taken where it is used: the load is then waited for there, not where it is issued)
+    auto q_at = [&](int s) -> uint32_t { return (s >= 0 && (uint32_t)s < L) ? (uint32_t)qm[s] : 0u; };
+    uint32_t q = q_at(lane + c0);  // my column's base in row 0
+    // 64 rows of the chain: match / mismatch score and record word z of row base + lane, and the base that enters
+    // the band at lane 63 in the row behind it (row i's lane 63 is column i + 63 + c0)
+    struct Block {
+        float vM, vX;
+        uint32_t z, qe;
+    };
+    auto load_rows = [&](uint32_t base) -> uint32_t {  // (clamped into the chain)
+        const uint32_t ci = base + (uint32_t)lane;
+        return chain[ci < M ? ci : M - 1u];
+    };
+    auto load_block = [&](uint32_t base, uint32_t row) {
+        const uint32_t ci = base + (uint32_t)lane;
+        row = row < N ? row : N - 1u;  // (clamped into the DAG)
+        const uint4 r = rec[row];
+        const float wgt = __uint_as_float(r.y);
+        Block b;
+        b.vM = ms * wgt;  // scoring_schemes.h:154
+        b.vX = mms * wgt;
+        b.z = r.z;
+        b.qe = q_at((int)ci + 1 + 63 + c0);
+        return b;
+    };
+    // (the node ids two blocks ahead, their records one block ahead: a block never waits for a load it has just issued)
+    Block cur = load_block(0, load_rows(0));
+    uint32_t rows_nxt = load_rows(64u < M ? 64u : 0u);
+    for (uint32_t base = 0; base < M; base += 64u) {
+        const uint32_t b1 = base + 64u < M ? base + 64u : base, b2 = base + 128u < M ? base + 128u : base;
+        const Block nxt = load_block(b1, rows_nxt);
+        rows_nxt = load_rows(b2);
+        const uint32_t n_rows = M - base < 64u ? M - base : 64u;
+        for (uint32_t j = 0; j < n_rows; ++j) {
+            const int i = (int)(base + j);
+            const float vM = lane_value(cur.vM, j), vX = lane_value(cur.vX, j);
+            const uint32_t z = (uint32_t)__builtin_amdgcn_readlane((int)cur.z, (int)j);
+            const float csel = (q & ((z >> 8) & 0xfu)) != 0u ? vM : vX;  // comp(): aligned_base.h:153 (z's mask has four bits: q's upper ones meet zeros)
+            // deletion (mesh.h:307-330): my column in the row before is my right neighbour's cell
+            const float nv = dpp_mov<kDppWaveShl1>(kUnreached, pv), ng = dpp_mov<kDppWaveShl1>(kUnreached, pg);
+            float cand = __builtin_fminf(nv + gp, ng + gpe);
+            float loc = __builtin_fminf(pv + csel, cand);  // ... or a match from (row before, column - 1): my own lane (:360-374)
+            // the insertion chain (mesh.h:332-358) as a prefix minimum of local - (lane's extensions)
+            float p = loc - kg;
+            const int k0 = -i - c0;  // the lane of query column 0: initial value 1, no match step, no insertion
+            if ((uint32_t)k0 < 64u) {  // (the first rows only: row 0 always is one of them)
+                asm volatile("" : "+v"(loc));  // (keeps this a branch: as selects it would cost every row seven instructions)
+                if (i == 0) {
+                    // the chain's first node: a source row of the DAG starts at 1 everywhere (init_edge); any other row can
+                    // be entered for free at column 0 only -- its predecessors are not of the chain
+                    const bool source = (z & 0xffu) == 0u;
+                    loc = cand = ((source && lane >= k0) || lane == k0) ? 1.0f : kUnreached;
+                } else if (lane == k0) {
+                    loc = __builtin_fminf(cand, 1.0f);
+                }
+                p = loc - kg;
+                // (column 0 keeps gaps_val = 1: a gap from it extends iff its value is 1)
+                if (lane == k0 && loc == 1.0f) p -= open;
+            }
+            // (a lane without a source keeps its own value: the minimum with itself)
+            p = __builtin_fminf(p, dpp_mov<kDppRowShr + 1>(p, p));
+            p = __builtin_fminf(p, dpp_mov<kDppRowShr + 2>(p, p));
+            p = __builtin_fminf(p, dpp_mov<kDppRowShr + 4>(p, p));
+            p = __builtin_fminf(p, dpp_mov<kDppRowShr + 8>(p, p));
+            p = __builtin_fminf(p, dpp_mov<kDppBcast15, 0xa>(p, p));
+            p = __builtin_fminf(p, dpp_mov<kDppBcast31, 0xc>(p, p));
+            const float gs = (dpp_mov<kDppWaveShr1>(inf, p) + kg) + open;  // the best gap arriving from my left
+            const float fv = __builtin_fminf(loc, gs);
+            // the end candidates (mesh.h:569-592): the last query column in any row, any real column of a sink row
+            const int kl = (int)L - 1 - i - c0;
+            if (kl >= 0 && kl < 64) best = __builtin_fminf(best, lane_value(fv, (uint32_t)kl));
+            if (z & kRecSink) {
+                const int s = i + lane + c0;
+                float v = (s >= 0 && (uint32_t)s < L) ? fv : inf;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) v = __builtin_fminf(v, __shfl_xor(v, o));
+                best = __builtin_fminf(best, v);
+            }
+            pv = fv;
+            pg = cand;
+            // the bases move with their columns: one lane to the left, the next one enters at lane 63
+            const uint32_t qn = (uint32_t)__builtin_amdgcn_readlane((int)cur.qe, (int)j);
+            q = (uint32_t)__builtin_amdgcn_update_dpp((int)qn, (int)q, kDppWaveShl1, 0xf, 0xf, false);
+        }
+        cur = nxt;
+    }
+    return __uint_as_float(uniform(__float_as_uint(best)));
+}
+
 template <int B, bool DBG, bool PRUNE>
 __global__ void __launch_bounds__(64, (B <= 4 ? 4 : (B <= 8 ? SINA_DP_SIMPLE_WAVES8 : 2)))
 mesh_dp_simple_kernel(const QDesc *__restrict__ qdv, const uint32_t *__restrict__ orderv, const uint4 *__restrict__ recv,
@@ -1020,7 +1149,8 @@ mesh_dp_simple_kernel(const QDesc *__restrict__ qdv, const uint32_t *__restrict_
                       float *__restrict__ dbg_value, float *spillv, EdgeRec *edgev, uint64_t edge_stride,
                       uint32_t n_strips, DpResult *__restrict__ resv, float ms, float mms, float gp, float gpe, DryArgs dry,
                       const uint2 *__restrict__ reachv, float prune_rho, uint32_t prune_amax, uint32_t n_slots,
-                      const float *__restrict__ scout_uv, float scout_bias) {
+                      float *__restrict__ scout_uv, float scout_bias, const uint16_t *__restrict__ chain_rowsv,
+                      const uint32_t *__restrict__ chain_sizesv, uint32_t chain_ncap) {
     static_assert(B % 4 == 0, "16-byte accesses per array");
     constexpr int kStrip = 64 * B;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1077,7 +1207,7 @@ mesh_dp_simple_kernel(const QDesc *__restrict__ qdv, const uint32_t *__restrict_
         const uint32_t g0 = g_cols < g_len ? g_cols : g_len;
         gain0 = (float)g0 * kPruneUnit;
         U64 = -(int32_t)uniform((uint32_t)(int32_t)(prune_rho * (float)g0));  // (rounded towards zero: the looser side)
-        // ... or, better than any guess, what the scout pass found: the cost of a real path of THIS query (scout.hip:
+        // ... or, better than any guess, what the scout pass found: the cost of a real path of THIS query (chain_scout_wave:
         // its alignment against the chain of its nearest relative), rounded up to a unit.  (Beyond +-1e5 the units leave float32's exact
         // integers: the guess stands.)  The store's guess stays as a guard, six per cent looser than it is used alone:
         // a scout that lost the query (a long gap its relative does not share: a path found, but a poor one) would have
@@ -1085,7 +1215,19 @@ mesh_dp_simple_kernel(const QDesc *__restrict__ qdv, const uint32_t *__restrict_
         // this query -- a query much further from its family than the store's others -- the first attempt dies early
         // and cheaply, and the second runs under the scout's value (below).
         if (scout_uv != nullptr) {
-            const float su = __uint_as_float(uniform(__float_as_uint(scout_uv[qi]))) + scout_bias;  // (bias: a test hook, 0)
+            float su;
+            if (chain_rowsv != nullptr) {
+                // (the DAG's number among the build's: its chain's length sits with the build's other sizes)
+                const uint32_t dag = (uint32_t)(node_off / chain_ncap);
+                uint32_t M = uniform(chain_sizesv[(size_t)dag * kBuiltWords + kBuiltChainLen]);
+                M = M < N ? M : N;  // (a base per column at most: never more than nodes -- the array's bound)
+                su = M > 0 ? chain_scout_wave(rec, chain_rowsv + node_off, M, N, L, qmaskv + q_off, ms, mms, gp, gpe, lane)
+                           : __builtin_inff();
+                if (lane == 0) scout_uv[qi] = su;  // (read back by the debug accessor)
+            } else {
+                su = __uint_as_float(uniform(__float_as_uint(scout_uv[qi])));  // (uploaded: SINA_HIP_TEST=scout_set=)
+            }
+            su += scout_bias;  // (a test hook, 0)
             if (su > -100000.0f && su < 100000.0f) {
                 const float up = su * 64.0f;
                 int32_t u = (int32_t)up;
@@ -2242,7 +2384,8 @@ int launch_tb(bool weighted, bool forbid, const DpArgs &a, uint32_t nq, uint32_t
         if (allow_full_lds(reinterpret_cast<const void *>(kfn))) return 1;
         hipLaunchKernelGGL(kfn, dim3(nq), dim3(64), lds, s, a.qd, a.order, a.rec, a.pred, a.qmask, a.tb, a.dbg_value, a.spill,
                            a.edge, a.edge_stride, n_strips, a.res, a.ms, a.mms, a.gp, a.gpe, a.dry, a.reach, a.prune_rho,
-                           a.prune_amax, (uint32_t)(lds / dp_slot_bytes(DpGeom{64 * (int)n_strips, B})), prune ? a.scout_u : nullptr, a.scout_bias);
+                           a.prune_amax, (uint32_t)(lds / dp_slot_bytes(DpGeom{64 * (int)n_strips, B})), prune ? a.scout_u : nullptr, a.scout_bias,
+                           prune ? a.chain_rows : nullptr, a.chain_sizes, a.chain_ncap);
     } else if (!weighted && !forbid && a.below_init) SH_LAUNCH(false, false, true);
     else if (!weighted && !forbid) SH_LAUNCH(false, false, false);
     else if (weighted && !forbid) SH_LAUNCH(true, false, false);
