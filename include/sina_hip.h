@@ -127,6 +127,18 @@ int sina_hip_kmer_topk(sina_hip_ctx *ctx, const uint8_t *qmask, const uint64_t *
  * against every reference; for tests and the search_filter stage. */
 int sina_hip_kmer_scores(sina_hip_ctx *ctx, const uint8_t *qmask, uint32_t qlen, int16_t *scores);
 
+/* The same two calls (arguments, result layout) for queries of 1..SINA_HIP_MAX_LONG_QUERY_LEN bases, as
+ * sina_hip_align_graphs_any is to sina_hip_align_graphs.  Routing is per query: a query of up to
+ * SINA_HIP_MAX_QUERY_LEN bases runs on the fast kernel, its results bit for bit those of sina_hip_kmer_topk; the
+ * longer ones are counted by the long kernel in a launch range of their own (chunks of SINA_HIP_KMER_LONG_CHUNK
+ * windows summed into the score row).  Results come back in the caller's order.  A query beyond
+ * SINA_HIP_MAX_LONG_QUERY_LEN fails the call as a limit (sina_hip_last_error_is_limit() == 1). */
+int sina_hip_kmer_topk_any(sina_hip_ctx *ctx, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq,
+                           uint32_t max, uint32_t *out_ids, float *out_scores, uint32_t *out_n);
+int sina_hip_kmer_scores_any(sina_hip_ctx *ctx, const uint8_t *qmask, uint32_t qlen, int16_t *scores);
+/* Queries the long count kernel has counted on this context since init / fork. */
+int sina_hip_long_queries(sina_hip_ctx *ctx, uint64_t *n);
+
 /* ------------------------------------------------------------- search stage
  * Replaces the per-candidate cseq_comparator::operator() calls of search_filter::operator()
  * (src/search_filter.cpp:311-313 and :274-276; traverse + match_counter,
@@ -183,11 +195,22 @@ void sina_hip_align_params_default(sina_hip_align_params *p);
  * by the context; valid until the next align call on this context (or its destruction). */
 const uint32_t *sina_hip_staged_out_pos(sina_hip_ctx *ctx);
 
-/* Longest query (bases) any entry point takes: k-mer search, family alignment, graph alignment.
- * (The k-mer count kernel keeps a query's k-mer cursors in LDS beside its 64 KiB score tile: 9 bytes
- * per base; the DP itself takes any number of 512-column strips.)  The reference aligns any length
- * (src/mesh.h:76,119-121); the stage functors fail a longer query softly, alone. */
+/* Longest query (bases) the fast paths take: sina_hip_kmer_topk / sina_hip_kmer_scores, family and profile
+ * alignment, sina_hip_align_graphs.  (The fast k-mer count kernel keeps a query's k-mer cursors in LDS beside its
+ * 64 KiB score tile: 9 bytes per base; the fast DP kernel's trace-back cell has 14 bits for the query index.)  The
+ * reference aligns any length (src/mesh.h:76,119-121): sina_hip_kmer_topk_any / sina_hip_kmer_scores_any search
+ * queries of up to SINA_HIP_MAX_LONG_QUERY_LEN bases and sina_hip_align_graphs_any aligns them; the stage functors
+ * fail a query beyond the limit their options leave softly, alone (famfinder `long-queries`, aligner
+ * `wide-fallback`). */
 #define SINA_HIP_MAX_QUERY_LEN 10240u
+
+/* Longest query (bases) the k-mer search takes at all (the _any entries).  A k-mer score is an int16_t -- in the
+ * reference too, unguarded (src/idset.h:315-337): a reference that holds all k-mers of a longer query would wrap
+ * there --, and the count kernels' LDS counters are 16-bit halves of a word.  A longer query is refused with
+ * sina_hip_last_error_is_limit() == 1; nothing is truncated. */
+#define SINA_HIP_MAX_LONG_QUERY_LEN 32767u
+/* The long count kernel takes a query's k-mer windows (by the index of their last base) in chunks of this many. */
+#define SINA_HIP_KMER_LONG_CHUNK 10240u
 
 /* A batch of family DAGs in CSR form (node id == topological rank == mesh row).
  * All arrays are concatenated over the nq queries of the batch.  Limits of sina_hip_align_graphs (the call fails,

@@ -30,7 +30,14 @@ ABI_SYMBOLS = [
     "sina_hip_align_profiles", "sina_hip_debug_family_profile",
     "sina_hip_debug_mesh", "sina_hip_debug_family_graph", "sina_hip_debug_dp_info", "sina_hip_debug_rgain", "sina_hip_debug_chain_rows", "sina_hip_get_stats",
     "sina_hip_align_graphs_any", "sina_hip_debug_mesh_wide", "sina_hip_wide_queries", "sina_hip_last_error_is_limit",
+    "sina_hip_kmer_topk_any", "sina_hip_kmer_scores_any", "sina_hip_long_queries",
 ]
+
+# include/sina_hip.h: the fast k-mer / DP paths' query limit, the _any k-mer entries' limit, and the number of k-mer
+# windows (by the index of their last base) the long count kernel takes per chunk
+MAX_QUERY_LEN = 10240
+MAX_LONG_QUERY_LEN = 32767
+KMER_LONG_CHUNK = 10240
 
 
 class AlignParams(C.Structure):
@@ -125,6 +132,9 @@ def load():
                                         C.POINTER(AlignOut), u32p]
     L.sina_hip_align_graphs_any.argtypes = L.sina_hip_align_graphs.argtypes
     L.sina_hip_wide_queries.argtypes = [vp, u64p]
+    L.sina_hip_kmer_topk_any.argtypes = L.sina_hip_kmer_topk.argtypes
+    L.sina_hip_kmer_scores_any.argtypes = L.sina_hip_kmer_scores.argtypes
+    L.sina_hip_long_queries.argtypes = [vp, u64p]
     L.sina_hip_last_error_is_limit.restype = C.c_int
     L.sina_hip_debug_mesh_wide.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
                                            u32p, u32p, f32p]
@@ -225,7 +235,7 @@ class Context:
         return view
 
     # ---- k-mer search
-    def kmer_topk(self, qmask, qoff, mx):
+    def kmer_topk(self, qmask, qoff, mx, long_ok=False):
         qmask = _c(qmask, np.uint8)
         qoff = _c(qoff, np.uint64)
         nq = len(qoff) - 1
@@ -233,15 +243,29 @@ class Context:
         ids = np.zeros((nq, mx_eff), np.uint32)
         sc = np.zeros((nq, mx_eff), np.float32)
         n = np.zeros(nq, np.uint32)
-        self._check(self.L.sina_hip_kmer_topk(self.h, _ptr(qmask, u8p), _ptr(qoff, u64p), nq, mx, _ptr(ids, u32p),
-                                              _ptr(sc, f32p), _ptr(n, u32p)))
+        fn = self.L.sina_hip_kmer_topk_any if long_ok else self.L.sina_hip_kmer_topk
+        self._check(fn(self.h, _ptr(qmask, u8p), _ptr(qoff, u64p), nq, mx, _ptr(ids, u32p), _ptr(sc, f32p), _ptr(n, u32p)))
         return ids, sc, n
 
-    def kmer_scores(self, qmask):
+    def kmer_scores(self, qmask, long_ok=False):
         qmask = _c(qmask, np.uint8)
         s = np.zeros(self.n_refs, np.int16)
-        self._check(self.L.sina_hip_kmer_scores(self.h, _ptr(qmask, u8p), len(qmask), _ptr(s, i16p)))
+        fn = self.L.sina_hip_kmer_scores_any if long_ok else self.L.sina_hip_kmer_scores
+        self._check(fn(self.h, _ptr(qmask, u8p), len(qmask), _ptr(s, i16p)))
         return s
+
+    def kmer_topk_any(self, qmask, qoff, mx):
+        """kmer_topk for queries of up to MAX_LONG_QUERY_LEN bases (the longer ones on the long count kernel)."""
+        return self.kmer_topk(qmask, qoff, mx, long_ok=True)
+
+    def kmer_scores_any(self, qmask):
+        return self.kmer_scores(qmask, long_ok=True)
+
+    def long_queries(self):
+        """Queries the long k-mer count kernel has counted on this context so far."""
+        n = C.c_uint64()
+        self._check(self.L.sina_hip_long_queries(self.h, C.byref(n)))
+        return int(n.value)
 
     # ---- alignment
     @staticmethod

@@ -117,6 +117,7 @@ struct sina_hip_ctx {
     // the trace-back pool above, allocated by the first query that needs it
     sina_hip::DevBuf wide_in, wide_planes;
     uint64_t wide_queries = 0;        // queries the wide kernel has aligned on this context (sina_hip_wide_queries)
+    uint64_t long_queries = 0;        // queries the long k-mer count kernel has counted on this context (sina_hip_long_queries)
     sina_hip::DevBuf scout, scout_u;  // the scout pass (mesh_dp.hip): the DAG build's chain rows (u16 [DAGs][ncap]), and its result -- a bound U per query
     sina_hip::HostBuf h_res;          // pinned copy of a launch's DpResults (row-skip statistics, the next launch's guess)
     bool profile_batch = false;       // the launch being prepared is one (set by sina_hip_align_graphs)

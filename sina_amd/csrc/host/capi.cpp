@@ -268,6 +268,14 @@ void *sina_host_store_ctx(const char *key) {
         return nullptr;
     }
 }
+int sina_host_store_slow_path_queries(const char *key, uint64_t *wide, uint64_t *long_kmer) {
+    try {
+        reference_store::get(key)->slow_path_queries(wide, long_kmer);
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
 int sina_host_store_build_index(const char *key, unsigned k, int nofast) {
     try {
         reference_store::get(key)->ensure_index(k, nofast != 0);

@@ -575,6 +575,21 @@ void reference_store::reserve_workers(device_role role, unsigned n) {
     }
     for (sina_hip_ctx *c : pool) hip_check(sina_hip_prewarm(c, (int)role), "sina_hip_prewarm");
 }
+void reference_store::slow_path_queries(uint64_t *wide, uint64_t *long_kmer) {
+    sina_hip_ctx *root = device();
+    std::lock_guard<std::mutex> lk(gpu_mu);
+    *wide = *long_kmer = 0;
+    auto add = [&](sina_hip_ctx *c) {
+        uint64_t w = 0, l = 0;
+        hip_check(sina_hip_wide_queries(c, &w), "sina_hip_wide_queries");
+        hip_check(sina_hip_long_queries(c, &l), "sina_hip_long_queries");
+        *wide += w;
+        *long_kmer += l;
+    };
+    add(root);
+    for (auto &pool : idle_forks)
+        for (sina_hip_ctx *c : pool) add(c);
+}
 reference_store::lease::~lease() {
     if (!c) return;
     std::lock_guard<std::mutex> lk(st->gpu_mu);
@@ -954,7 +969,9 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
         std::vector<uint32_t> cnt(nu);
         {
             scoped_phase ph("ff.kmer_topk(C-ABI)");
-            hip_check(sina_hip_kmer_topk(ctx, dev_mask, dev_off, (uint32_t)nu, max, ids, sc, cnt.data()), "kmer_topk");
+            // (the _any entry: the class has no length limit of its own, as the reference's -- a query beyond the fast count
+            // kernel's goes to the long one, per query)
+            hip_check(sina_hip_kmer_topk_any(ctx, dev_mask, dev_off, (uint32_t)nu, max, ids, sc, cnt.data()), "kmer_topk");
         }
         parallel_for(queries.size(), [&](size_t i) {
             const size_t u = slot_of[i];
@@ -970,8 +987,8 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
         using pair = std::pair<int16_t, int>;
         std::vector<pair> ranks(n);
         for (size_t i = 0; i < queries.size(); i++) {
-            hip_check(sina_hip_kmer_scores(ctx, qmask + qoff[i], (uint32_t)(qoff[i + 1] - qoff[i]),
-                                           scores.data()),
+            hip_check(sina_hip_kmer_scores_any(ctx, qmask + qoff[i], (uint32_t)(qoff[i + 1] - qoff[i]),
+                                               scores.data()),
                       "kmer_scores");
             for (unsigned r = 0; r < n; r++) ranks[r] = pair(scores[r], (int)r);
             std::partial_sort(ranks.begin(), ranks.begin() + max, ranks.end(), std::greater<pair>());
@@ -995,6 +1012,7 @@ struct ff_options {
     bool fs_no_fast;
     unsigned int fs_kmer_len, fs_min_len, fs_cover_gene;
     std::string database;
+    bool long_queries;  // search queries of up to SINA_HIP_MAX_LONG_QUERY_LEN bases (default off: SINA_HIP_MAX_QUERY_LEN)
 };
 ff_options ff_defaults() {  // src/famfinder.cpp:144-203
     ff_options o;
@@ -1013,6 +1031,7 @@ ff_options ff_defaults() {  // src/famfinder.cpp:144-203
     o.fs_kmer_len = 10;
     o.fs_min_len = 150;
     o.fs_cover_gene = 0;
+    o.long_queries = false;
     return o;
 }
 ff_options ff_opts = ff_defaults();
@@ -1080,6 +1099,7 @@ void famfinder::set_option(const std::string &name, const std::string &value) {
     else if (name == "fs-leave-query-out") o.fs_leave_query_out = to_bool(value);
     else if (name == "fs-cover-gene") o.fs_cover_gene = (unsigned)std::stoul(value);
     else if (name == "filter") o.posvar_filter = value;
+    else if (name == "long-queries") o.long_queries = to_bool(value);
     else throw std::logic_error("famfinder: unknown option " + name);
 }
 
@@ -1265,12 +1285,14 @@ void render_family_list(const void *owner, const uint64_t *items, size_t n, std:
 void famfinder::impl::run(std::vector<tray *> &batch) {
     const ff_options &o = ff_opts;
     std::vector<tray *> todo;
-    // (the device takes queries of up to SINA_HIP_MAX_QUERY_LEN bases; a longer one fails alone, softly,
+    // (the device takes queries of up to SINA_HIP_MAX_QUERY_LEN bases -- with long-queries, which lets the k-mer search
+    // send the longer ones to its long count kernel, SINA_HIP_MAX_LONG_QUERY_LEN; a longer one fails alone, softly,
     // like a sequence without relatives -- not the whole batch)
+    const unsigned max_len = o.long_queries ? SINA_HIP_MAX_LONG_QUERY_LEN : SINA_HIP_MAX_QUERY_LEN;
     std::vector<tray *> searchable;
     for (tray *t : batch) {
-        if (t->input_sequence->size() > SINA_HIP_MAX_QUERY_LEN) {
-            t->log << "unable to align: sequence longer than " << SINA_HIP_MAX_QUERY_LEN << " bases;";
+        if (t->input_sequence->size() > max_len) {
+            t->log << "unable to align: sequence longer than " << max_len << " bases;";
             t->input_sequence->set_attr(fn::turn, "turn-check disabled");
         } else {
             searchable.push_back(t);
@@ -1736,9 +1758,12 @@ static unsigned query_kmer_count(const cseq &c, int stamp) {
 // gives true if it needs the DP, false if it is done: nothing to align, too long, or its alignment copied from a relative.
 static bool prepare_tray(tray &t, const aligner::options &o, reference_store *prep_store) {
     if (t.input_sequence == nullptr || t.alignment_reference == nullptr || t.astats == nullptr) return false;  // :310-318
-    if (t.input_sequence->size() > SINA_HIP_MAX_QUERY_LEN) {  // (device limit: soft failure of this tray)
+    // (device limit: soft failure of this tray.  With wide-fallback a query beyond the fast DP path's length is aligned
+    // by the wide kernel -- up to the length the k-mer search can have found its family for)
+    const unsigned max_len = o.wide_fallback ? SINA_HIP_MAX_LONG_QUERY_LEN : SINA_HIP_MAX_QUERY_LEN;
+    if (t.input_sequence->size() > max_len) {
         t.log << "unable to align: sequence of " << t.input_sequence->size() << " bases (device limit "
-              << SINA_HIP_MAX_QUERY_LEN << ");";
+              << max_len << ");";
         return false;
     }
     uint64_t tk = host_tsc();
@@ -1931,9 +1956,10 @@ static device_slots distinct_slots(const std::vector<dp_job *> &members) {
 
 // The host-graph route: the slots' families as DAGs (--fs-no-graph: profiles) built by the host twins of the device
 // builders and handed over as graphs -- with wide-fallback through sina_hip_align_graphs_any, which takes a DAG of
-// any size.  Fills out[slot] and the context's staged columns; gives the graphs' width.
+// any size.  Fills out[slot] and the context's staged columns; gives the graphs' width.  max_cells (if asked for, and
+// before the device is called): the largest wide mesh among the slots, in cells as SINA_HIP_WIDE_CELLS counts them.
 static uint32_t align_host_graphs(sina_hip_ctx *ctx, const aligner::options &o, const sina_hip_align_params &p,
-                                  const device_slots &s, sina_hip_align_out *out) {
+                                  const device_slots &s, sina_hip_align_out *out, uint64_t *max_cells = nullptr) {
     const size_t n = s.dnq;
     std::vector<host_graph> gs(n);
     {
@@ -1943,6 +1969,11 @@ static uint32_t align_host_graphs(sina_hip_ctx *ctx, const aligner::options &o, 
             else build_family_graph(s.job(u).family(), o.fs_weight, &gs[u]);
         });
     }
+    if (max_cells)
+        for (size_t u = 0; u < n; u++) {
+            const uint64_t N = gs[u].pos.size(), L = s.dqoff[u + 1] - s.dqoff[u];
+            *max_cells = std::max(*max_cells, (N + L - 1) * std::min(N, L));
+        }
     sina_hip_graph_batch gb;
     std::vector<uint64_t> node_off(n + 1, 0), edge_off(n + 1, 0);
     std::vector<uint32_t> npos, pred, poff, smin;
@@ -2233,16 +2264,22 @@ void aligner::operator()(std::vector<tray> &batch) {
     // ... and by where the family's DAG is built: on the device (families of up to 128 members: the
     // DAG-build kernel's LDS tables) or, for the rare larger family (--fs-max beyond 128), by the host
     // twin of that kernel (build_family_graph) and handed over as a graph (sina_hip_align_graphs)
+    // ... and, with wide-fallback, by length: a query beyond the fast DP path's SINA_HIP_MAX_QUERY_LEN is taken out of
+    // its group up front -- size alone decides it -- into a group on the host-graph route (sina_hip_align_graphs_any
+    // sends it through the wide kernel).  Left in a device-built group, the limit refusal of sina_hip_align_families /
+    // _profiles would send the whole group, thousands of ordinary queries, back over host-built graphs.
     constexpr size_t kDeviceFamilyMax = 128;
-    std::map<std::pair<std::vector<float>, bool>, std::vector<dp_job *>> groups;
+    enum route { route_host_graphs = 0, route_device = 1, route_long = 2 };
+    std::map<std::pair<std::vector<float>, int>, std::vector<dp_job *>> groups;
     // (--fs-no-graph: the family as a profile, built by build_family_profile on the host or -- with device-profile on,
     // under the conditions a DAG is built on the device -- by sina_hip_align_profiles; scoring_scheme_profile takes no
     // positional weights, src/align.cpp:428-433)
     for (dp_job &jb : jobs)
         if (jb.t != nullptr) {
             const bool on_device = o.device_graph && jb.family_size() <= kDeviceFamilyMax;
-            if (o.fs_no_graph) groups[{std::vector<float>(), on_device && o.device_profile}].push_back(&jb);
-            else groups[{jb.t->astats->getWeights(), on_device}].push_back(&jb);
+            const bool is_long = jb.t->input_sequence->size() > SINA_HIP_MAX_QUERY_LEN;  // (prepare_tray: only with wide-fallback)
+            if (o.fs_no_graph) groups[{std::vector<float>(), is_long ? route_long : on_device && o.device_profile ? route_device : route_host_graphs}].push_back(&jb);
+            else groups[{jb.t->astats->getWeights(), is_long ? route_long : on_device ? route_device : route_host_graphs}].push_back(&jb);
         }
     if (!groups.empty() && !store) store = reference_store::get(db);  // (the DP needs the store: this throws what the lookup above met)
 
@@ -2254,7 +2291,43 @@ void aligner::operator()(std::vector<tray> &batch) {
         // (the aligned columns are read where the device copied them, in the context's pinned staging buffer:
         // sina_hip_staged_out_pos -- the context stays leased until the group's last tray is finished)
         auto dev = store->worker_device(reference_store::dev_align);
-        const uint32_t width = align_slots(dev.get(), *store, o, p, slots, grp.first.second, out.data());
+        if (grp.first.second == route_long) {
+            // One call per slot: a wide mesh of this size fills a launch of the wide kernel nearly alone anyway, and a
+            // query whose mesh exceeds SINA_HIP_WIDE_CELLS -- the one thing a call refuses a well-formed query for --
+            // then fails alone, softly, with the call's message in its log.  The trays of a slot are finished before
+            // the next call reuses the context's staged columns.
+            std::vector<dp_job *> aligned;
+            for (size_t u = 0; u < slots.dnq; u++) {
+                device_slots one;
+                one.dnq = 1;
+                one.members = &members;
+                one.first.assign(1, slots.first.empty() ? (uint32_t)u : slots.first[u]);
+                one.dqoff = {0, slots.dqoff[u + 1] - slots.dqoff[u]};
+                one.dqmask = slots.dqmask + slots.dqoff[u];
+                uint64_t cells = 0;
+                uint32_t width = 0;
+                std::string refused;
+                try {
+                    width = align_host_graphs(dev.get(), o, p, one, &out[u], &cells);
+                } catch (const std::runtime_error &e) {
+                    if (cells <= SINA_HIP_WIDE_CELLS) throw;
+                    refused = e.what();
+                }
+                const uint32_t *const pos = sina_hip_staged_out_pos(dev.get());
+                for (size_t x = 0; x < members.size(); x++) {
+                    if (slots.slot_of[x] != u) continue;
+                    if (!refused.empty()) {
+                        members[x]->t->log << "unable to align: " << refused << ";";
+                        continue;
+                    }
+                    finish_tray(*members[x], out[u], pos, width, o, defer_score_line);
+                    aligned.push_back(members[x]);
+                }
+            }
+            if (o.calc_idty && !aligned.empty()) set_family_identity(aligned, *store);
+            continue;
+        }
+        const uint32_t width = align_slots(dev.get(), *store, o, p, slots, grp.first.second == route_device, out.data());
         const uint32_t *const staged_pos = sina_hip_staged_out_pos(dev.get());
         {
             scoped_phase ph("al.finish(NAST,log)");

@@ -297,6 +297,9 @@ public:
     // at least `n` contexts of that kind exist and are warm (sina_hip_prewarm) -- called by a driver BEFORE it starts
     // the threads that will lease them: a context made, or grown, in the middle of a run stalls the device
     void reserve_workers(device_role role, unsigned n);
+    // queries the wide DP kernel / the long k-mer count kernel have taken on this store's contexts (the root and the
+    // idle forks: call it between runs) -- sina_hip_wide_queries, sina_hip_long_queries
+    void slow_path_queries(uint64_t *wide, uint64_t *long_kmer);
 
 private:
     reference_store() = default;

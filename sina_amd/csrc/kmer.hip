@@ -40,6 +40,14 @@ constexpr int kTileRefs = 32768;            // refs per LDS histogram tile (64 K
 constexpr int kWide = 2;                    // 1 KiB loads a wave of the count kernel keeps in flight
 constexpr int kMaxQueryLen = (int)SINA_HIP_MAX_QUERY_LEN;  // k-mer list capacity in LDS: 64 KiB tile + 9 B per base <= 160 KiB
 static_assert((size_t)kTileRefs * 2 + ((size_t)kMaxQueryLen + 63) / 64 * 64 * 9 + 64 <= 160 * 1024, "LDS of the count kernel");
+// the long count kernel: a query of up to SINA_HIP_MAX_LONG_QUERY_LEN bases in chunks of
+// kLongChunk windows, each chunk with the k-mer list capacity of the fast kernel -- and its k - 1 <= 11 bases before
+// the chunk's first window end in qb[] (the 64 bytes more)
+constexpr int kMaxLongQueryLen = (int)SINA_HIP_MAX_LONG_QUERY_LEN;
+constexpr int kLongChunk = (int)SINA_HIP_KMER_LONG_CHUNK;
+constexpr int kLongQbExtra = 64;
+static_assert(kLongChunk <= kMaxQueryLen && kMaxLongQueryLen <= 32767, "a chunk fits the fast kernel's lists; int16 scores");
+static_assert((size_t)kTileRefs * 2 + (size_t)kMaxQueryLen * 9 + 64 + kLongQbExtra <= 160 * 1024, "LDS of the long count kernel");
 constexpr int kSelThreads = 256;
 constexpr int kSelMax = 4096;               // candidates sortable in LDS
 
@@ -226,163 +234,7 @@ __global__ void __launch_bounds__(kCountThreads) __attribute__((amdgpu_waves_per
     for (uint32_t t = 0; t < ntiles; t++) {
         const uint32_t tile_lo = t * kTileRefs;
         const uint32_t tile_hi = min(tile_lo + (uint32_t)kTileRefs, a.n_refs);
-        for (uint32_t i = tid; i < kTileRefs / 8; i += kCountThreads) reinterpret_cast<uint4 *>(hist)[i] = uint4{0u, 0u, 0u, 0u};
-        if (tid == 0) next_kmer = 0;
-        __syncthreads();
-        for (uint32_t guard = 0; guard < (1u << 22); guard++) {
-            uint32_t i = 0;
-            if (lane == 0) i = atomicAdd(&next_kmer, 1u);
-            i = __builtin_amdgcn_readfirstlane(i);
-            if (i >= nk) break;
-            uint32_t c = cur[i];
-            const uint32_t e = end[i];
-            // First a probe of 64 postings, one per lane.  Most visits end here: 1250 of a query's ~1330 cursor lists
-            // are short -- ~130 postings at 500 000 references, eight or so per tile -- and the wide loop below costs
-            // such a visit a hundred instructions (the kernel is bound by instruction issue, not by the round trips:
-            // 32 waves per CU hide those).  The lists are ascending: the postings of this tile are a prefix.
-            {
-                const uint32_t x = c + (uint32_t)lane;
-                const uint32_t id = x < e ? a.idx_ids[x] : 0xFFFFFFFFu;
-                const bool in = id < tile_hi;
-                if (in) {
-                    const uint32_t r = id - tile_lo;
-                    atomicAdd(&hist[r >> 1], 1u << (16 * (r & 1)));
-                }
-                const uint32_t cnt = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(in));
-                c += cnt;
-                if (cnt < 64u) {
-                    if (lane == 0) cur[i] = c;
-                    continue;
-                }
-            }
-            // kWide x 1 KiB in flight per wave: every lane reads four consecutive postings per load
-            // (most postings sit in a few hundred long lists -- k-mers of conserved regions -- and
-            // one wave streams each of them: bytes in flight are what bounds it)
-            for (uint32_t g2 = 0; c < e && g2 < (1u << 22); g2++) {
-                uint32_t id[kWide][4];
-#pragma unroll
-                for (int u = 0; u < kWide; u++) {
-                    const uint32_t x = c + 4u * (uint32_t)lane + 256u * u;
-                    if (x + 4u <= e) {
-                        const uint32_t *src = a.idx_ids + x;  // (4-byte aligned: three dwords + one, or one 16-byte load)
-                        id[u][0] = src[0];
-                        id[u][1] = src[1];
-                        id[u][2] = src[2];
-                        id[u][3] = src[3];
-                    } else {
-#pragma unroll
-                        for (int v = 0; v < 4; v++) id[u][v] = (x + v < e) ? a.idx_ids[x + v] : 0xFFFFFFFFu;
-                    }
-                }
-                uint32_t cnt = 0;
-#pragma unroll
-                for (int u = 0; u < kWide; u++) {
-#pragma unroll
-                    for (int v = 0; v < 4; v++) {
-                        if (id[u][v] < tile_hi) {
-                            const uint32_t r = id[u][v] - tile_lo;
-                            atomicAdd(&hist[r >> 1], 1u << (16 * (r & 1)));
-                            cnt++;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-                c += cnt;
-                if (cnt < 256u * kWide) break;
-            }
-            if (lane == 0) cur[i] = c;
-        }
-        __syncthreads();
-        // Dense k-mers: thread t owns the 32 references of bitmap word t of this tile and counts, for
-        // each of them, in how many of the query's dense bitmaps its bit is set -- bit-sliced: the
-        // planes hold one bit of all 32 counters each; eight bitmap words go in with seven carry-save
-        // adders (ones / twos / fours) and one ripple of the resulting eights (7 operations per word,
-        // no atomics, nothing but registers).
-        if (nd) {
-            // (the planes above the fours: as many as the query's number of dense k-mers has bits beyond three -- a
-            // hundred bitmaps need four of the seven; the ripple and the unpacking below are compiled for each count)
-            auto dense_path = [&](auto nhi_c) {
-                constexpr int NHI = decltype(nhi_c)::value;
-                const uint32_t *bw = a.dense_bits + (size_t)(tile_lo >> 5) + tid;
-                uint32_t ones = 0, twos = 0, fours = 0, hi[NHI > 0 ? NHI : 1] = {0};  // hi[p]: weight 8 << p
-                auto csa = [](uint32_t &h, uint32_t &l, uint32_t x, uint32_t y, uint32_t z) {
-                    const uint32_t u = x ^ y;
-                    h = (x & y) | (u & z);
-                    l = u ^ z;
-                };
-                for (uint32_t i = 0; i < nd; i += 8) {
-                    uint32_t w[8];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) w[u] = (i + u < nd) ? bw[(size_t)*(dtop - (i + u)) * a.dense_words] : 0u;
-                    uint32_t twosA, twosB, foursA, foursB, eights;
-                    csa(twosA, ones, ones, w[0], w[1]);
-                    csa(twosB, ones, ones, w[2], w[3]);
-                    csa(foursA, twos, twos, twosA, twosB);
-                    csa(twosA, ones, ones, w[4], w[5]);
-                    csa(twosB, ones, ones, w[6], w[7]);
-                    csa(foursB, twos, twos, twosA, twosB);
-                    csa(eights, fours, fours, foursA, foursB);
-                    uint32_t carry = eights;
-#pragma unroll
-                    for (int p = 0; p < NHI; p++) {
-                        const uint32_t t2 = hi[p] & carry;
-                        hi[p] ^= carry;
-                        carry = t2;
-                    }
-                }
-                // add my 32 counts to the tile's counters: words 16 t .. 16 t + 15 are mine alone now
-                if constexpr (NHI <= 5) {
-                    // counts below 256: four references at a time -- their bits of a plane are a nibble, one
-                    // multiplication spreads the nibble's bits over the four bytes of a word (bit i to bit 8 i), the
-                    // planes are or-ed in at their weights; two byte shuffles make the counters' two 16-bit pairs.
-                    // (group g of lane l in step (g - l) mod 8, a 64-bit access each: the lanes of a wave spread over
-                    // the LDS banks)
-#pragma unroll 2
-                    for (int gg = 0; gg < 8; gg++) {
-                        const int g = (gg + lane) & 7;
-                        const int b = 4 * g;
-                        auto spread = [&](uint32_t plane) -> uint32_t { return (((plane >> b) & 0xFu) * 0x00204081u) & 0x01010101u; };
-                        uint32_t acc = spread(ones) | (spread(twos) << 1) | (spread(fours) << 2);
-#pragma unroll
-                        for (int p = 0; p < NHI; p++) acc |= spread(hi[p]) << (3 + p);
-                        uint2 *hw = reinterpret_cast<uint2 *>(&hist[16 * tid + 2 * g]);
-                        uint2 v = *hw;
-                        v.x += (acc & 0xFFu) | ((acc & 0xFF00u) << 8);
-                        v.y += ((acc >> 16) & 0xFFu) | ((acc >> 24) << 16);
-                        *hw = v;
-                    }
-                } else {
-                    // (word j of lane l in step (j - l) mod 16: the lanes of a wave spread over the LDS banks)
-#pragma unroll 4
-                    for (int jj = 0; jj < 16; jj++) {
-                        const int j = (jj + lane) & 15;
-                        const int b0 = 2 * j, b1 = 2 * j + 1;
-                        uint32_t cl = ((ones >> b0) & 1u) | (((twos >> b0) & 1u) << 1) | (((fours >> b0) & 1u) << 2);
-                        uint32_t ch = ((ones >> b1) & 1u) | (((twos >> b1) & 1u) << 1) | (((fours >> b1) & 1u) << 2);
-#pragma unroll
-                        for (int p = 0; p < NHI; p++) {
-                            cl |= ((hi[p] >> b0) & 1u) << (3 + p);
-                            ch |= ((hi[p] >> b1) & 1u) << (3 + p);
-                        }
-                        hist[16 * tid + j] += cl | (ch << 16);
-                    }
-                }
-            };
-            // (counts up to nd: 32 - clz(nd) bits, three of them in ones / twos / fours)
-            const int bits = 32 - __builtin_clz(nd);
-            switch (bits > 3 ? bits - 3 : 0) {
-            case 0: dense_path(std::integral_constant<int, 0>()); break;
-            case 1: dense_path(std::integral_constant<int, 1>()); break;
-            case 2: dense_path(std::integral_constant<int, 2>()); break;
-            case 3: dense_path(std::integral_constant<int, 3>()); break;
-            case 4: dense_path(std::integral_constant<int, 4>()); break;
-            case 5: dense_path(std::integral_constant<int, 5>()); break;
-            case 6: dense_path(std::integral_constant<int, 6>()); break;
-            default: dense_path(std::integral_constant<int, 7>()); break;
-            }
-            __syncthreads();
-        }
+#include "kmer_count_tile.inc"
         if constexpr (!CAND) {
             // tile scores out: two int16 per 32-bit store (row stride is even)
             uint32_t *dst = reinterpret_cast<uint32_t *>(row + tile_lo);
@@ -470,6 +322,78 @@ __global__ void __launch_bounds__(kCountThreads) __attribute__((amdgpu_waves_per
     if (tid == 0) a.nkq[q] = (uint32_t)((len > a.k) ? len - a.k : 0);
 }
 
+// Queries of more than kMaxQueryLen bases.  The scores are sums over the query's windows, so the windows are counted
+// in chunks of kLongChunk (by the index of their last base: a window belongs to the chunk of that base and reads the up
+// to k - 1 bases before the chunk with it, so an ambiguous base there invalidates it as anywhere).  Per chunk the
+// cursor / bitmap lists are built anew in the LDS of a fast-kernel query of kMaxQueryLen bases, the tiles are counted
+// as there, and the chunks after the first ADD their tile to the score row: a 32-bit add of two 16-bit counters --
+// no total exceeds 32767, the low half never carries -- on a row that sits in L2.  Score rows only (no CAND).  (Its
+// LDS leaves room for one workgroup per CU, four waves per SIMD: no cap at 64 VGPRs as the fast kernel has for its two.)
+__global__ void __launch_bounds__(kCountThreads) kmer_count_long_kernel(CountArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ uint32_t n_kmers, next_kmer, n_dense_q;
+    uint32_t *hist = reinterpret_cast<uint32_t *>(smem);                         // as in kmer_count_kernel, kmax = kMaxQueryLen
+    uint32_t *cur = hist + kTileRefs / 2;
+    uint32_t *end = cur + a.kmax;
+    uint8_t *qb = reinterpret_cast<uint8_t *>(end + a.kmax);                     // [kmax + kLongQbExtra]
+    uint32_t *dtop = cur + a.kmax - 1;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63;
+    const uint8_t *qm = a.qmask + a.qoff[q];
+    const uint32_t len = (uint32_t)(a.qoff[q + 1] - a.qoff[q]);
+    const uint32_t ntiles = (a.n_refs + kTileRefs - 1) / kTileRefs;
+    int16_t *row = a.scores + (size_t)q * a.stride;
+    unsigned long long mine = 0;
+    for (uint32_t e0 = 0; e0 < len; e0 += kLongChunk) {
+        // windows ending on bases e0 .. e1 - 1; qb[] holds bases b0 .. e1 - 1
+        const uint32_t e1 = min(len, e0 + (uint32_t)kLongChunk);
+        const uint32_t b0 = e0 + 1 >= a.k ? e0 + 1 - a.k : 0u;
+        if (tid == 0) n_kmers = n_dense_q = 0;  // (every thread has read the last chunk's: the tile loop synchronises)
+        for (uint32_t i = b0 + tid; i < e1; i += kCountThreads) qb[i - b0] = qm[i];
+        __syncthreads();
+        for (uint32_t e = e0 + tid; e < e1; e += kCountThreads) {
+            uint32_t v;
+            // (len - b0, e - b0: the window on the query's last base is dropped, none at an inner chunk end)
+            if (kmer_at(qb, len - b0, e - b0, a.k, a.fast != 0, &v)) {
+                const uint32_t lo = a.idx_off[v], hi = a.idx_off[v + 1];
+                if (lo != hi) {
+                    const uint32_t did = a.dense_id ? a.dense_id[v] : kNoDense;
+                    uint32_t dslot = kMaxDenseQ;
+                    if (did != kNoDense) dslot = atomicAdd(&n_dense_q, 1u);
+                    if (dslot < kMaxDenseQ) {
+                        *(dtop - dslot) = did;
+                    } else {
+                        const uint32_t slot = atomicAdd(&n_kmers, 1u);
+                        cur[slot] = lo;
+                        end[slot] = hi;
+                    }
+                    mine += hi - lo;
+                }
+            }
+        }
+        __syncthreads();
+        const uint32_t nk = n_kmers;
+        const uint32_t nd = min(n_dense_q, kMaxDenseQ);
+        for (uint32_t t = 0; t < ntiles; t++) {
+            const uint32_t tile_lo = t * kTileRefs;
+            const uint32_t tile_hi = min(tile_lo + (uint32_t)kTileRefs, a.n_refs);
+#include "kmer_count_tile.inc"
+            uint32_t *dst = reinterpret_cast<uint32_t *>(row + tile_lo);
+            const uint32_t words = (tile_hi - tile_lo + 1) / 2;
+            if (e0 == 0) {
+                for (uint32_t i = tid; i < words; i += kCountThreads) dst[i] = hist[i];
+            } else {
+                for (uint32_t i = tid; i < words; i += kCountThreads) dst[i] += hist[i];
+            }
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+    if (lane == 0 && mine) atomicAdd(a.postings, mine);
+    if (tid == 0) a.nkq[q] = (uint32_t)((len > a.k) ? len - a.k : 0);
+}
+
 // ---------------------------------------------------------------- select
 
 struct SelectArgs {
@@ -507,6 +431,8 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum, 
 // on "how many scores are >= t" -- pure reductions over 16-byte vector loads of a row that sits in
 // L2 (200 KB for 100k references), no atomics on a histogram whose low bins every lane hits --
 // then one ordered pass emits everything above the cut plus the ties with the LARGEST ids.
+// (kTopMax: the largest score a row can hold -- the fast count kernel's query length, or the long one's)
+template <int kTopMax>
 __global__ void __launch_bounds__(kSelThreads) kmer_select_kernel(SelectArgs a) {
     __shared__ unsigned long long cand[kSelMax];
     __shared__ uint32_t wsum[kSelThreads / 64];
@@ -518,7 +444,7 @@ __global__ void __launch_bounds__(kSelThreads) kmer_select_kernel(SelectArgs a) 
     const uint4 *sc8 = reinterpret_cast<const uint4 *>(sc);
     const uint32_t nvec = (n_refs + 7) / 8;
     const uint32_t M = min(a.max, n_refs);
-    const int top = (int)min(a.nkq[q], (uint32_t)kMaxQueryLen);  // no score can exceed the k-mer count
+    const int top = (int)min(a.nkq[q], (uint32_t)kTopMax);  // no score can exceed the k-mer count
 
     // f(value, index) over the 8 scores of vector i; entries past n_refs are skipped
     auto for8 = [&](uint32_t i, auto &&f) {
@@ -872,8 +798,10 @@ constexpr uint32_t kCandCap = 4096, kCandMaxM = 128;
 static bool kmer_cand_path(const sina_hip_ctx *c, uint32_t max) {
     return max <= kCandMaxM && c->st->n_refs >= 2u * (uint32_t)kTileRefs && atoi(test_knob("kmer_rows").c_str()) == 0;
 }
+// long_path: the queries of this range are longer than kMaxQueryLen -- the long count kernel and its select kernel,
+// score rows only
 static int kmer_topk_device(sina_hip_ctx *c, const uint8_t *d_qmask, const uint64_t *d_qoff, uint32_t nq,
-                            uint32_t max, uint32_t max_qlen, bool want_scores_only, bool cand_path) {
+                            uint32_t max, uint32_t max_qlen, bool want_scores_only, bool cand_path, bool long_path = false) {
     hipStream_t s = c->stream;
     const uint32_t stride = (c->st->n_refs + 7u) & ~7u;  // rows 16-byte aligned (vector loads in the select kernel)
     if ((!cand_path && c->k_scores.reserve((size_t)nq * stride * 2 + 64)) || c->k_tmp2.reserve(8) || c->k_tmp0.reserve(4 * (size_t)nq) ||
@@ -890,7 +818,7 @@ static int kmer_topk_device(sina_hip_ctx *c, const uint8_t *d_qmask, const uint6
     ca.postings = c->k_tmp2.as<unsigned long long>();
     ca.n_refs = c->st->n_refs;
     ca.stride = stride;
-    ca.kmax = (max_qlen + 63u) & ~63u;
+    ca.kmax = long_path ? (uint32_t)kMaxQueryLen : (max_qlen + 63u) & ~63u;
     ca.k = c->st->k;
     ca.fast = c->st->nofast ? 0 : 1;
     if (ensure_dense(c)) return 1;
@@ -901,14 +829,16 @@ static int kmer_topk_device(sina_hip_ctx *c, const uint8_t *d_qmask, const uint6
     ca.cand_n = cand_path ? c->k_out_n.as<uint32_t>() : nullptr;  // (kmer_select_cand_kernel turns it into out_n in place)
     ca.cand_cap = kCandCap;
     ca.topm = max;
-    const size_t clds = (size_t)kTileRefs * 2 + (size_t)ca.kmax * 9 + 64;
+    const size_t clds = (size_t)kTileRefs * 2 + (size_t)ca.kmax * 9 + 64 + (long_path ? kLongQbExtra : 0);
     if (allow_full_lds(reinterpret_cast<const void *>(kmer_count_kernel<false>)) ||
-        allow_full_lds(reinterpret_cast<const void *>(kmer_count_kernel<true>)))
+        allow_full_lds(reinterpret_cast<const void *>(kmer_count_kernel<true>)) ||
+        (long_path && allow_full_lds(reinterpret_cast<const void *>(kmer_count_long_kernel))))
         return 1;
     heavy_launch hl(c, s, kHeavyKmer);  // (count + select: device-filling kernels, ctx.h)
     const hipStream_t hs = hl.stream();
     SH_CHECK(hipEventRecord(c->ev[3], hs));
-    if (cand_path) hipLaunchKernelGGL(kmer_count_kernel<true>, dim3(nq), dim3(kCountThreads), clds, hs, ca);
+    if (long_path) hipLaunchKernelGGL(kmer_count_long_kernel, dim3(nq), dim3(kCountThreads), clds, hs, ca);
+    else if (cand_path) hipLaunchKernelGGL(kmer_count_kernel<true>, dim3(nq), dim3(kCountThreads), clds, hs, ca);
     else hipLaunchKernelGGL(kmer_count_kernel<false>, dim3(nq), dim3(kCountThreads), clds, hs, ca);
     SH_CHECK(hipGetLastError());
     SH_CHECK(hipEventRecord(c->ev[4], hs));
@@ -937,7 +867,9 @@ static int kmer_topk_device(sina_hip_ctx *c, const uint8_t *d_qmask, const uint6
         sa.out_n = c->k_out_n.as<uint32_t>();
         sa.n_refs = c->st->n_refs;
         sa.max = max;
-        hipLaunchKernelGGL(kmer_select_kernel, dim3(nq), dim3(kSelThreads), 0, hs, sa);
+        // (the rows of the long count kernel hold scores of up to 32757: the search for the cut starts above them)
+        if (long_path) hipLaunchKernelGGL(kmer_select_kernel<kMaxLongQueryLen>, dim3(nq), dim3(kSelThreads), 0, hs, sa);
+        else hipLaunchKernelGGL(kmer_select_kernel<kMaxQueryLen>, dim3(nq), dim3(kSelThreads), 0, hs, sa);
         SH_CHECK(hipGetLastError());
     }
     SH_CHECK(hipEventRecord(c->ev[5], hs));
@@ -1071,25 +1003,13 @@ int sina_hip_build_index(sina_hip_ctx *c, unsigned k, int nofast) {
     return rc;
 }
 
-int sina_hip_kmer_topk(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max,
-                       uint32_t *out_ids, float *out_scores, uint32_t *out_n) {
-    if (!c || !qmask || !qoff || !out_ids || !out_scores || !out_n) SH_FAIL("kmer_topk: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    sina_hip_hint_guard hints(c);
-    if (index_ready(c)) return 1;
-    if (nq == 0) return 0;
-    SH_CHECK(hipSetDevice(c->device));
-    if (max > c->st->n_refs) max = c->st->n_refs;
-    if (max == 0) {
-        memset(out_n, 0, sizeof(uint32_t) * nq);
-        return 0;
-    }
-    if (max > (uint32_t)kSelMax) SH_FAIL("kmer_topk: max > 4096 not supported by the LDS select kernel");
+// sina_hip_kmer_topk / _any behind their checks (c->mu held, 1 <= max <= kSelMax): queries 0 .. n_fast - 1 on the fast
+// count kernel (none of them longer than kMaxQueryLen), queries n_fast .. nq - 1 -- every one of them longer -- on the
+// long kernel, in launch ranges of their own
+static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t n_fast,
+                         uint32_t max, uint32_t *out_ids, float *out_scores, uint32_t *out_n) {
     uint32_t max_qlen = 1;
-    for (uint32_t q = 0; q < nq; q++) {
-        if (qoff[q + 1] - qoff[q] > (uint64_t)kMaxQueryLen) SH_FAIL("kmer_topk: query longer than SINA_HIP_MAX_QUERY_LEN bases");
-        max_qlen = std::max<uint32_t>(max_qlen, (uint32_t)(qoff[q + 1] - qoff[q]));
-    }
+    for (uint32_t q = 0; q < n_fast; q++) max_qlen = std::max<uint32_t>(max_qlen, (uint32_t)(qoff[q + 1] - qoff[q]));
     hipStream_t s = c->stream;
     const uint64_t nqm = qoff[nq] - qoff[0];
     // sub-batches bound the [nq][n_refs] int16 score matrix to ~2 GiB
@@ -1101,8 +1021,8 @@ int sina_hip_kmer_topk(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qo
         return 1;
     // one launch range: kernels, results back through pinned staging, statistics; *overflow = a candidate list of the
     // range did not hold its query's candidates (nothing was copied out then: the caller repeats the range with rows)
-    auto run_range = [&](uint32_t q0, uint32_t bq, bool cand_path, bool *overflow) -> int {
-        if (kmer_topk_device(c, c->qmask.as<uint8_t>(), c->k_qoff.as<uint64_t>() + q0, bq, max, max_qlen, false, cand_path)) return 1;
+    auto run_range = [&](uint32_t q0, uint32_t bq, bool cand_path, bool *overflow, bool long_path = false) -> int {
+        if (kmer_topk_device(c, c->qmask.as<uint8_t>(), c->k_qoff.as<uint64_t>() + q0, bq, max, max_qlen, false, cand_path, long_path)) return 1;
         // (the kernels have finished: kmer_topk_device waits for the heavy stream)
         if (download(c, 9, c->k_out_ids.p, (size_t)bq * max * 4, s) || download(c, 10, c->k_out_scores.p, (size_t)bq * max * 4, s) ||
             download(c, 11, c->k_out_n.p, (size_t)bq * 4, s) || download(c, 0, c->k_tmp2.p, 8, s))
@@ -1129,6 +1049,7 @@ int sina_hip_kmer_topk(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qo
             }
         }
         if (*overflow) return 0;
+        if (long_path) c->long_queries += bq;
         memcpy(out_ids + (size_t)q0 * max, c->h_stage[9].p, (size_t)bq * max * 4);
         memcpy(out_scores + (size_t)q0 * max, c->h_stage[10].p, (size_t)bq * max * 4);
         memcpy(out_n + q0, c->h_stage[11].p, (size_t)bq * 4);
@@ -1136,8 +1057,8 @@ int sina_hip_kmer_topk(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qo
     };
     const bool cand_path = kmer_cand_path(c, max);
     const uint32_t per_cand = 16384;  // (candidate lists: 32 KB per query)
-    for (uint32_t q0 = 0; q0 < nq; q0 += cand_path ? per_cand : per) {
-        const uint32_t bq = std::min(cand_path ? per_cand : per, nq - q0);
+    for (uint32_t q0 = 0; q0 < n_fast; q0 += cand_path ? per_cand : per) {
+        const uint32_t bq = std::min(cand_path ? per_cand : per, n_fast - q0);
         bool overflow = false;
         if (run_range(q0, bq, cand_path, &overflow)) return 1;
         if (overflow)  // a giant group of equal scores somewhere in the range: the score rows and the full select
@@ -1146,23 +1067,93 @@ int sina_hip_kmer_topk(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qo
                 if (run_range(r0, std::min(per, q0 + bq - r0), false, &dummy)) return 1;
             }
     }
+    for (uint32_t q0 = n_fast; q0 < nq; q0 += per) {
+        bool dummy = false;
+        if (run_range(q0, std::min(per, nq - q0), false, &dummy, true)) return 1;
+    }
     return 0;
 }
 
-int sina_hip_kmer_scores(sina_hip_ctx *c, const uint8_t *qmask, uint32_t qlen, int16_t *scores) {
+// any: queries of up to kMaxLongQueryLen bases (sina_hip_kmer_topk_any), the longer ones behind the others for
+// kmer_topk_run and back into the caller's order
+static int kmer_topk_checked(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max,
+                             uint32_t *out_ids, float *out_scores, uint32_t *out_n, bool any) {
+    if (!c || !qmask || !qoff || !out_ids || !out_scores || !out_n) SH_FAIL("kmer_topk: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    sina_hip_hint_guard hints(c);
+    if (index_ready(c)) return 1;
+    if (nq == 0) return 0;
+    SH_CHECK(hipSetDevice(c->device));
+    if (max > c->st->n_refs) max = c->st->n_refs;
+    if (max == 0) {
+        memset(out_n, 0, sizeof(uint32_t) * nq);
+        return 0;
+    }
+    if (max > (uint32_t)kSelMax) SH_FAIL("kmer_topk: max > 4096 not supported by the LDS select kernel");
+    uint32_t n_long = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        const uint64_t len = qoff[q + 1] - qoff[q];
+        if (!any && len > (uint64_t)kMaxQueryLen) SH_FAIL("kmer_topk: query longer than SINA_HIP_MAX_QUERY_LEN bases");
+        if (len > (uint64_t)kMaxLongQueryLen) SH_FAIL_LIMIT("kmer_topk_any: query longer than SINA_HIP_MAX_LONG_QUERY_LEN bases");
+        n_long += len > (uint64_t)kMaxQueryLen;
+    }
+    if (n_long == 0) return kmer_topk_run(c, qmask, qoff, nq, nq, max, out_ids, out_scores, out_n);
+    const uint32_t n_fast = nq - n_long;
+    std::vector<uint32_t> order(nq);  // order[slot] = the caller's query
+    for (uint32_t q = 0, f = 0, l = n_fast; q < nq; q++) order[qoff[q + 1] - qoff[q] > (uint64_t)kMaxQueryLen ? l++ : f++] = q;
+    std::vector<uint64_t> off(nq + 1, 0);
+    for (uint32_t x = 0; x < nq; x++) off[x + 1] = off[x] + (qoff[order[x] + 1] - qoff[order[x]]);
+    std::vector<uint8_t> mask(off[nq]);
+    for (uint32_t x = 0; x < nq; x++) memcpy(mask.data() + off[x], qmask + qoff[order[x]], off[x + 1] - off[x]);
+    std::vector<uint32_t> ids((size_t)nq * max), n(nq);
+    std::vector<float> sc((size_t)nq * max);
+    if (kmer_topk_run(c, mask.data(), off.data(), nq, n_fast, max, ids.data(), sc.data(), n.data())) return 1;
+    for (uint32_t x = 0; x < nq; x++) {
+        memcpy(out_ids + (size_t)order[x] * max, ids.data() + (size_t)x * max, (size_t)max * 4);
+        memcpy(out_scores + (size_t)order[x] * max, sc.data() + (size_t)x * max, (size_t)max * 4);
+        out_n[order[x]] = n[x];
+    }
+    return 0;
+}
+
+static int kmer_scores_checked(sina_hip_ctx *c, const uint8_t *qmask, uint32_t qlen, int16_t *scores, bool any) {
     if (!c || !qmask || !scores) SH_FAIL("kmer_scores: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
     if (index_ready(c)) return 1;
-    if (qlen > (uint32_t)kMaxQueryLen) SH_FAIL("kmer_scores: query longer than SINA_HIP_MAX_QUERY_LEN bases");
+    if (!any && qlen > (uint32_t)kMaxQueryLen) SH_FAIL("kmer_scores: query longer than SINA_HIP_MAX_QUERY_LEN bases");
+    if (qlen > (uint32_t)kMaxLongQueryLen) SH_FAIL_LIMIT("kmer_scores_any: query longer than SINA_HIP_MAX_LONG_QUERY_LEN bases");
+    const bool long_path = qlen > (uint32_t)kMaxQueryLen;
     SH_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const uint64_t rel[2] = {0, qlen};
     if (c->qmask.reserve(std::max<uint32_t>(qlen, 1)) || c->k_qoff.reserve(16)) return 1;
     SH_CHECK(hipMemcpyAsync(c->qmask.p, qmask, qlen, hipMemcpyHostToDevice, s));
     SH_CHECK(hipMemcpyAsync(c->k_qoff.p, rel, 16, hipMemcpyHostToDevice, s));
-    if (kmer_topk_device(c, c->qmask.as<uint8_t>(), c->k_qoff.as<uint64_t>(), 1, 1, std::max<uint32_t>(qlen, 1), true, false)) return 1;
+    if (kmer_topk_device(c, c->qmask.as<uint8_t>(), c->k_qoff.as<uint64_t>(), 1, 1, std::max<uint32_t>(qlen, 1), true, false, long_path)) return 1;
+    if (long_path) c->long_queries++;
     SH_CHECK(hipMemcpyAsync(scores, c->k_scores.p, (size_t)c->st->n_refs * 2, hipMemcpyDeviceToHost, s));
     SH_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int sina_hip_kmer_topk(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max,
+                       uint32_t *out_ids, float *out_scores, uint32_t *out_n) {
+    return kmer_topk_checked(c, qmask, qoff, nq, max, out_ids, out_scores, out_n, false);
+}
+int sina_hip_kmer_topk_any(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max,
+                           uint32_t *out_ids, float *out_scores, uint32_t *out_n) {
+    return kmer_topk_checked(c, qmask, qoff, nq, max, out_ids, out_scores, out_n, true);
+}
+int sina_hip_kmer_scores(sina_hip_ctx *c, const uint8_t *qmask, uint32_t qlen, int16_t *scores) {
+    return kmer_scores_checked(c, qmask, qlen, scores, false);
+}
+int sina_hip_kmer_scores_any(sina_hip_ctx *c, const uint8_t *qmask, uint32_t qlen, int16_t *scores) {
+    return kmer_scores_checked(c, qmask, qlen, scores, true);
+}
+int sina_hip_long_queries(sina_hip_ctx *c, uint64_t *n) {
+    if (!c || !n) SH_FAIL("long_queries: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *n = c->long_queries;
     return 0;
 }
 

@@ -57,6 +57,7 @@ def load_host():
     H.sina_host_store_ctx.restype = vp
     H.sina_host_store_ctx.argtypes = [C.c_char_p]
     H.sina_host_store_build_index.argtypes = [C.c_char_p, C.c_uint, C.c_int]
+    H.sina_host_store_slow_path_queries.argtypes = [C.c_char_p, capi.u64p, capi.u64p]
     H.sina_host_store_index_ready.argtypes = [C.c_char_p, C.c_uint, C.c_int]
     H.sina_host_store_set_attr.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_char_p]
     H.sina_host_sidx_load.argtypes = [C.c_char_p, C.c_uint, C.c_int, capi.u32p, capi.u32p, capi.u32p, C.c_uint64,
@@ -207,6 +208,13 @@ class Store:
         if capi.load().sina_hip_get_stats(self.ctx_handle(), C.byref(s)) != 0:
             raise HostError("get_stats failed")
         return {f[0]: getattr(s, f[0]) for f in capi.Stats._fields_}
+
+    def slow_path_queries(self):
+        """(queries the wide DP kernel has aligned, queries the long k-mer count kernel has counted) on this store's
+        contexts so far -- between runs, when none of them is leased."""
+        w, l = C.c_uint64(), C.c_uint64()
+        _chk(self.H.sina_host_store_slow_path_queries(self.key.encode(), C.byref(w), C.byref(l)))
+        return int(w.value), int(l.value)
 
     def close(self):
         self.H.sina_host_store_close(self.key.encode())

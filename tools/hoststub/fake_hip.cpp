@@ -69,6 +69,13 @@ int sina_hip_kmer_topk(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qo
     return 0;
 }
 int sina_hip_kmer_scores(sina_hip_ctx *, const uint8_t *, uint32_t, int16_t *) { g_err = "stub"; return 1; }
+int sina_hip_kmer_topk_any(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max,
+                           uint32_t *out_ids, float *out_scores, uint32_t *out_n) {
+    return sina_hip_kmer_topk(c, qmask, qoff, nq, max, out_ids, out_scores, out_n);
+}
+int sina_hip_kmer_scores_any(sina_hip_ctx *, const uint8_t *, uint32_t, int16_t *) { g_err = "stub"; return 1; }
+int sina_hip_long_queries(sina_hip_ctx *, uint64_t *n) { *n = 0; return 0; }
+int sina_hip_wide_queries(sina_hip_ctx *, uint64_t *n) { *n = 0; return 0; }
 int sina_hip_compare(sina_hip_ctx *, const uint32_t *, const uint64_t *, uint32_t, const uint32_t *, const uint64_t *,
                      int, int, sina_hip_match_counts *) { g_err = "stub"; return 1; }
 void sina_hip_align_params_default(sina_hip_align_params *p) {
