@@ -184,7 +184,7 @@ typedef struct sina_hip_align_params {
     int32_t overhang;       /* SINA_OVERHANG_*  */
     int32_t lowercase;      /* SINA_LOWERCASE_* */
     int32_t insertion;      /* SINA_INSERTION_* */
-    const float *weights;   /* posvar weights => scoring_scheme_weighted, or NULL */
+    const float *weights;   /* posvar weights => scoring_scheme_weighted, or NULL (the _wsets entries: n_sets vectors) */
     uint32_t n_weights;
     int32_t assemble;       /* 1: also do the cseq container steps of backtrack() on the device where they
                              * are plain (see sina_hip_align_out::assembled); 0 (default): columns only */
@@ -304,6 +304,26 @@ int sina_hip_align_families(sina_hip_ctx *ctx, const uint32_t *fam_ids, const ui
                             uint32_t nq, const uint8_t *qmask, const uint64_t *qoff,
                             const sina_hip_align_params *p, sina_hip_align_out *out,
                             uint32_t *out_pos);
+
+/* sina_hip_align_graphs / sina_hip_align_families with a positional weight vector PER QUERY, in one launch: the
+ * reference weights every query with the filter of the group most of its relatives belong to (--auto-filter-field,
+ * src/famfinder.cpp:397-429), so the queries of one batch may differ in theirs.
+ *   p->weights : n_sets vectors of p->n_weights floats, one after the other (required: n_sets >= 1 vectors)
+ *   weight_set : [nq] weight_set[q] < n_sets names query q's vector; NULL: every query takes the first
+ * Everything else -- arguments, limits, refusals, result layout, out_pos == NULL with the staged columns, assemble --
+ * is as for the entry without the suffix, and with n_sets == 1 or weight_set == NULL its bytes are returned.  A
+ * vector's last entry stands for every column beyond it, within the query's own vector.  A set id that is not below
+ * n_sets fails the call before anything runs (not a limit: sina_hip_last_error_is_limit() == 0); a profile batch
+ * (node_score16) takes no weights and so no sets.  Queries with the same ordered family still share one DAG -- it
+ * holds no positional weights -- and each reads its own vector.  sina_hip_align_graphs_any and
+ * sina_hip_align_profiles keep one vector per call. */
+int sina_hip_align_graphs_wsets(sina_hip_ctx *ctx, const sina_hip_graph_batch *g, const uint8_t *qmask,
+                                const uint64_t *qoff, const sina_hip_align_params *p, const uint32_t *weight_set,
+                                uint32_t n_sets, sina_hip_align_out *out, uint32_t *out_pos);
+int sina_hip_align_families_wsets(sina_hip_ctx *ctx, const uint32_t *fam_ids, const uint64_t *fam_off,
+                                  uint32_t nq, const uint8_t *qmask, const uint64_t *qoff,
+                                  const sina_hip_align_params *p, const uint32_t *weight_set, uint32_t n_sets,
+                                  sina_hip_align_out *out, uint32_t *out_pos);
 
 /* Same, but the family is the template as a PROFILE (--fs-no-graph: pseq p(vcp.begin(), vcp.end()) and
  * scoring_scheme_profile, src/align.cpp:428-433; src/pseq.cpp, base_profile and base_profile::comp,

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "sina_hip_debug_mesh", "sina_hip_debug_family_graph", "sina_hip_debug_dp_info", "sina_hip_debug_rgain", "sina_hip_debug_chain_rows", "sina_hip_get_stats",
     "sina_hip_align_graphs_any", "sina_hip_debug_mesh_wide", "sina_hip_wide_queries", "sina_hip_last_error_is_limit",
     "sina_hip_kmer_topk_any", "sina_hip_kmer_scores_any", "sina_hip_long_queries",
+    "sina_hip_align_graphs_wsets", "sina_hip_align_families_wsets",
 ]
 
 # include/sina_hip.h: the fast k-mer / DP paths' query limit, the _any k-mer entries' limit, and the number of k-mer
@@ -141,6 +142,10 @@ def load():
     L.sina_hip_align_families.argtypes = [vp, u32p, u64p, C.c_uint32, u8p, u64p, C.POINTER(AlignParams),
                                           C.POINTER(AlignOut), u32p]
     L.sina_hip_align_profiles.argtypes = L.sina_hip_align_families.argtypes
+    L.sina_hip_align_graphs_wsets.argtypes = [vp, C.POINTER(GraphBatch), u8p, u64p, C.POINTER(AlignParams), u32p, C.c_uint32,
+                                              C.POINTER(AlignOut), u32p]
+    L.sina_hip_align_families_wsets.argtypes = [vp, u32p, u64p, C.c_uint32, u8p, u64p, C.POINTER(AlignParams), u32p,
+                                                C.c_uint32, C.POINTER(AlignOut), u32p]
     L.sina_hip_debug_family_profile.argtypes = [vp, u32p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, u32p, u32p,
                                                 f32p, f32p, C.c_uint32]
     L.sina_hip_debug_mesh.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
@@ -394,6 +399,43 @@ class Context:
         self._check(self.L.sina_hip_align_families(self.h, _ptr(fam_ids, u32p), _ptr(fam_off, u64p), nq,
                                                    _ptr(qmask, u8p), _ptr(qoff, u64p), C.byref(params),
                                                    out.ctypes.data_as(C.POINTER(AlignOut)), _ptr(pos, u32p)))
+        return out, pos
+
+    @staticmethod
+    def params_wsets(weight_sets, **kw):
+        """params() for the _wsets entries: weight_sets is [n_sets, n_weights], one positional weight vector per row."""
+        ws = _c(weight_sets, np.float32)
+        assert ws.ndim == 2 and ws.shape[0] >= 1
+        p = Context.params(weights=ws.reshape(-1), **kw)
+        p.n_weights = ws.shape[1]
+        return p
+
+    def align_graphs_wsets(self, gb, qmask, qoff, params, weight_set, n_sets):
+        """align_graphs with a weight vector per query: params from params_wsets, weight_set[q] < n_sets (or None)."""
+        qmask = _c(qmask, np.uint8)
+        qoff = _c(qoff, np.uint64)
+        ws = None if weight_set is None else _c(weight_set, np.uint32)
+        out = np.zeros(gb.nq, ALIGN_OUT_DTYPE)
+        pos = np.zeros(max(len(qmask), 1), np.uint32)
+        self._check(self.L.sina_hip_align_graphs_wsets(self.h, C.byref(gb), _ptr(qmask, u8p), _ptr(qoff, u64p),
+                                                       C.byref(params), None if ws is None else _ptr(ws, u32p), n_sets,
+                                                       out.ctypes.data_as(C.POINTER(AlignOut)), _ptr(pos, u32p)))
+        return out, pos
+
+    def align_families_wsets(self, fam_ids, fam_off, qmask, qoff, params, weight_set, n_sets):
+        """align_families with a weight vector per query (see align_graphs_wsets)."""
+        fam_ids = _c(fam_ids, np.uint32)
+        fam_off = _c(fam_off, np.uint64)
+        qmask = _c(qmask, np.uint8)
+        qoff = _c(qoff, np.uint64)
+        ws = None if weight_set is None else _c(weight_set, np.uint32)
+        nq = len(qoff) - 1
+        out = np.zeros(nq, ALIGN_OUT_DTYPE)
+        pos = np.zeros(max(len(qmask), 1), np.uint32)
+        self._check(self.L.sina_hip_align_families_wsets(self.h, _ptr(fam_ids, u32p), _ptr(fam_off, u64p), nq,
+                                                         _ptr(qmask, u8p), _ptr(qoff, u64p), C.byref(params),
+                                                         None if ws is None else _ptr(ws, u32p), n_sets,
+                                                         out.ctypes.data_as(C.POINTER(AlignOut)), _ptr(pos, u32p)))
         return out, pos
 
     def align_profiles(self, fam_ids, fam_off, qmask, qoff, params=None):

@@ -219,7 +219,7 @@ static int prep_range(const sina_hip_graph_batch *g, const uint64_t *qoff, uint3
 int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint32_t bq, uint64_t n_node_entries,
                   uint64_t tb_cells, uint64_t spill_rows, uint64_t cells, uint64_t nqm, const sina_hip_align_params *p, uint32_t width,
                   sina_hip_align_out *out, uint32_t *out_pos, bool want_dbg_value, const PrunePlan &pp,
-                  uint32_t chain_ncap) {
+                  uint32_t chain_ncap, const uint32_t *wset_host) {
     hipStream_t s = c->stream;
     const int Lp = pl.geom.Lp();
     const bool weighted = p->weights != nullptr && p->n_weights > 0;
@@ -259,6 +259,12 @@ int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint3
     a.res = c->res.as<DpResult>();
     a.weights = weighted ? c->weights.as<float>() : nullptr;
     a.n_weights = weighted ? p->n_weights : 0;
+    a.wset = nullptr;
+    if (weighted && wset_host != nullptr) {  // (indexed like qd: the launch's own reordering goes through `order`)
+        if (c->wset.reserve(4 * (size_t)bq)) return 1;
+        if (upload(c, 9, c->wset.p, wset_host, 4 * (size_t)bq, s)) return 1;
+        a.wset = c->wset.as<uint32_t>();
+    }
     a.ms = -p->match_score;  // scoring_scheme_*(-match, -mismatch, gap, gapext), align.cpp:406-414
     a.mms = -p->mismatch_score;
     a.gp = p->gap_penalty;
@@ -344,6 +350,7 @@ int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint3
     b.res = a.res;
     b.weights = a.weights;
     b.n_weights = a.n_weights;
+    b.wset = a.wset;
     b.out = c->out.as<sina_hip_align_out>();
     b.out_pos = c->out_pos.as<uint32_t>();
     b.nq = bq;
@@ -495,12 +502,26 @@ int make_streams(sina_hip_ctx *c) {
     return 0;
 }
 
-int upload_weights(sina_hip_ctx *c, const sina_hip_align_params *p) {
+int upload_weights(sina_hip_ctx *c, const sina_hip_align_params *p, uint32_t n_sets) {
     if (p->weights != nullptr && p->n_weights > 0) {
-        if (c->weights.reserve(sizeof(float) * p->n_weights)) return 1;
-        SH_CHECK(hipMemcpyAsync(c->weights.p, p->weights, sizeof(float) * p->n_weights, hipMemcpyHostToDevice,
-                                c->stream));
+        const size_t bytes = sizeof(float) * (size_t)p->n_weights * std::max<uint32_t>(n_sets, 1);
+        if (c->weights.reserve(bytes)) return 1;
+        SH_CHECK(hipMemcpyAsync(c->weights.p, p->weights, bytes, hipMemcpyHostToDevice, c->stream));
     }
+    return 0;
+}
+
+// A set id out of range would read beyond the uploaded vectors: looked for before anything runs.  Not a limit of the
+// path (no other entry takes such a call): a plain error.
+int check_weight_sets(const char *who, const sina_hip_align_params *p, const uint32_t *weight_set, uint32_t n_sets, uint32_t nq) {
+    const std::string w(who);
+    if (n_sets == 0) SH_FAIL(w + ": n_sets must be at least 1");
+    if (weight_set == nullptr) return 0;  // (every query takes the first vector)
+    if (p->weights == nullptr || p->n_weights == 0) SH_FAIL(w + ": weight sets need positional weights (p->weights, p->n_weights)");
+    for (uint32_t q = 0; q < nq; q++)
+        if (weight_set[q] >= n_sets)
+            SH_FAIL(w + ": weight set " + std::to_string(weight_set[q]) + " of query " + std::to_string(q) + " is not below n_sets = " +
+                    std::to_string(n_sets));
     return 0;
 }
 
@@ -513,9 +534,17 @@ static bool weighted_scheme(const sina_hip_align_params *p) { return p->weights 
 static int align_graphs_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask,
                              const uint64_t *qoff, const sina_hip_align_params *p, sina_hip_align_out *out,
                              uint32_t *out_pos, float *dbg_value_host, uint32_t *dbg_vm, uint32_t *dbg_vs,
-                             uint32_t qa = 0, uint32_t qb = 0, uint32_t *done_to = nullptr, uint32_t *spill_q = nullptr) {
+                             uint32_t qa = 0, uint32_t qb = 0, uint32_t *done_to = nullptr, uint32_t *spill_q = nullptr,
+                             const uint32_t *weight_set = nullptr, uint32_t n_sets = 1) {
     if (!c || !g || !qmask || !qoff || !p || !out) SH_FAIL("align_graphs: null argument");
     const uint32_t nq = g->nq;
+    if (check_weight_sets("align_graphs_wsets", p, weight_set, n_sets, nq)) return 1;
+    if (weight_set != nullptr && g->node_score16 != nullptr)
+        SH_FAIL("align_graphs_wsets: a profile batch takes no positional weights (scoring_scheme_profile)");
+    if (weight_set == nullptr || n_sets == 1) {  // (one vector for all: the call of the entry without the suffix)
+        weight_set = nullptr;
+        n_sets = 1;
+    }
     if (nq == 0) return 0;
     if (qb == 0) qb = nq;
     if (done_to) *done_to = qa;
@@ -534,7 +563,7 @@ static int align_graphs_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, con
     DpPlan pl;
     if (plan_dp(c, maxL, &pl)) return 1;
     const int Lp = pl.geom.Lp();
-    if (upload_weights(c, p)) return 1;
+    if (upload_weights(c, p, n_sets)) return 1;
     float wmax = 0.f, wmin = 0.f;
     if (!g->node_score16 && g->node_weight) {
         const uint64_t n_all = g->node_off[qb] - g->node_off[qa];
@@ -595,7 +624,8 @@ static int align_graphs_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, con
         }
         c->out_pos_base = qbase - qoff[0];
         if (run_dp_device(c, pl, hp.qd.data(), bq, nn, hp.tb_cells, hp.spill_rows, hp.cells, nqm, p, g->width, out + q0,
-                          out_pos ? out_pos + qbase : nullptr, dbg_value_host != nullptr, pp_launch))
+                          out_pos ? out_pos + qbase : nullptr, dbg_value_host != nullptr, pp_launch, 0,
+                          weight_set ? weight_set + q0 : nullptr))
             return 1;
         if (dbg_vm) {  // single-query debug: unpack the planes
             const QDesc &d = hp.qd[0];
@@ -924,6 +954,17 @@ int sina_hip_align_graphs(sina_hip_ctx *c, const sina_hip_graph_batch *g, const 
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
     return align_graphs_impl(c, g, qmask, qoff, p, out, out_pos, nullptr, nullptr, nullptr);
+}
+
+int sina_hip_align_graphs_wsets(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask,
+                                const uint64_t *qoff, const sina_hip_align_params *p, const uint32_t *weight_set,
+                                uint32_t n_sets, sina_hip_align_out *out, uint32_t *out_pos) {
+    if (!c) SH_FAIL("align_graphs_wsets: null ctx");
+    if (p && !(p->weights != nullptr && p->n_weights > 0)) SH_FAIL("align_graphs_wsets: weight sets need positional weights (p->weights, p->n_weights)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    sina_hip_hint_guard hints(c);
+    return align_graphs_impl(c, g, qmask, qoff, p, out, out_pos, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, weight_set,
+                             n_sets);
 }
 
 int sina_hip_align_graphs_any(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask,

@@ -331,6 +331,7 @@ struct DpArgs {
     DpResult *res;
     const float *weights;       // posvar weights (device) or nullptr
     uint32_t n_weights;
+    const uint32_t *wset;       // per query, indexed like qd: its vector among the n_weights-float vectors at `weights`; nullptr: the first
     float ms, mms, gp, gpe;     // scheme ctor args: -match, -mismatch, gap, gapext
     const float *prof16;        // --fs-no-graph: match term per node and query mask [16 * node + mask], else nullptr
     DryArgs dry;                // (heavy_launch::dry(): tells the next launch when this one's queue has run dry)
@@ -360,6 +361,7 @@ struct BtArgs {
     const DpResult *res;
     const float *weights;
     uint32_t n_weights;
+    const uint32_t *wset;  // as DpArgs::wset
     sina_hip_align_out *out;
     uint32_t *out_pos;
     uint32_t nq, width, Lp;
@@ -412,13 +414,16 @@ struct sina_hip_ctx;
 
 namespace sina_hip {
 int plan_dp(sina_hip_ctx *c, uint32_t maxL, DpPlan *pl);
-int upload_weights(sina_hip_ctx *c, const sina_hip_align_params *p);
+int upload_weights(sina_hip_ctx *c, const sina_hip_align_params *p, uint32_t n_sets = 1);  // n_sets vectors of p->n_weights floats
+// (the _wsets entries) weight_set[q] < n_sets for the call's nq queries, and weights to choose from
+int check_weight_sets(const char *who, const sina_hip_align_params *p, const uint32_t *weight_set, uint32_t n_sets, uint32_t nq);
 // chain_ncap: node entries per DAG of the device-built DAGs whose first member's chain the build left in the
 // context (ctx.h, scout); 0: the DAGs are the caller's or profiles -- no chain, no scout pass
+// wset_host: the weight vector of each of the bq queries (the _wsets entries), or nullptr: one vector for all
 int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint32_t bq, uint64_t n_node_entries,
                   uint64_t tb_cells, uint64_t spill_rows, uint64_t cells, uint64_t nqm, const sina_hip_align_params *p, uint32_t width,
                   sina_hip_align_out *out, uint32_t *out_pos, bool want_dbg_value, const PrunePlan &pp,
-                  uint32_t chain_ncap = 0);
+                  uint32_t chain_ncap = 0, const uint32_t *wset_host = nullptr);
 // What a launch may skip rows with (api.hip): the scoring of `p` (non-negative gap costs, the simple scheme), the
 // largest and smallest node weight it will see, its longest query.  SINA_HIP_DP_PRUNE=0: never.
 PrunePlan prune_plan(const sina_hip_align_params *p, float wmax, float wmin, uint32_t maxL, bool profile_batch);

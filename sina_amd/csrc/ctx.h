@@ -113,6 +113,7 @@ struct sina_hip_ctx {
     sina_hip::DevBuf qd, order, rec, node_pos, pred, succ_minpos, qmask, spill, edge, res, weights, out, out_pos, dbg;
     sina_hip::DevBuf prof16, self16;  // --fs-no-graph: match-term tables of a profile batch (sina_hip_graph_batch)
     sina_hip::DevBuf rgain;           // per DAG node: bound on the gain still to come (the DP kernel's row skip, common.h)
+    sina_hip::DevBuf wset;            // per query of a launch: which of the call's weight vectors is its own (the _wsets entries)
     // the wide path (mesh_wide.hip): a launch's inputs, and its mesh -- every cell's fields in HBM; grow-only, apart from
     // the trace-back pool above, allocated by the first query that needs it
     sina_hip::DevBuf wide_in, wide_planes;
@@ -139,7 +140,7 @@ struct sina_hip_ctx {
 
     size_t lds_budget = 0;  // LDS per DP workgroup; 0 = what keeps the register-limited occupancy (dp_default_lds_budget)
 
-    static constexpr int kNumScratch = 39;
+    static constexpr int kNumScratch = 40;
     static_assert(kNumScratch <= 64, "sina_hip_store::cap_hint is too short");
     void scratch(sina_hip::DevBuf **all) {
         sina_hip::DevBuf *list[kNumScratch] = {&qd, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &res,
@@ -147,7 +148,7 @@ struct sina_hip_ctx {
                                                &k_out_scores, &k_out_n, &k_tmp0, &k_tmp1, &k_tmp2, &g_fam_ids,
                                                &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &order,
                                                &s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &edge, &prof16, &self16, &rgain,
-                                               &scout, &scout_u};
+                                               &scout, &scout_u, &wset};
         for (int i = 0; i < kNumScratch; i++) all[i] = list[i];
     }
     void publish_hints() {  // after a call: remember how big my buffers had to be
@@ -175,7 +176,7 @@ struct sina_hip_ctx {
         sina_hip::DevBuf *search[] = {&k_qoff, &k_scores, &k_out_ids, &k_out_scores, &k_out_n, &k_tmp0, &k_tmp1, &k_tmp2, &qmask};
         sina_hip::DevBuf *align[] = {&qd, &order, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &edge, &res, &weights, &out,
                                      &out_pos, &g_fam_ids, &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &rgain, &scout, &scout_u,
-                                     &prof16, &self16};
+                                     &prof16, &self16, &wset};
         sina_hip::DevBuf *compare[] = {&s_qab, &s_qoff, &s_cand, &s_coff, &s_out};
         sina_hip::DevBuf **list = kind == 0 ? search : (kind == 1 ? align : compare);
         const size_t n = kind == 0 ? sizeof search / sizeof *search : (kind == 1 ? sizeof align / sizeof *align : sizeof compare / sizeof *compare);
@@ -591,9 +592,11 @@ using family_builder = int (*)(sina_hip_ctx *c, const uint32_t *fam_ids, const u
                                const sina_hip_align_params *p, int W, const PrunePlan &pp, BuiltGraphs *bg);
 // The launch loop both entry points share (graph_build.hip): argument checks, one build per DISTINCT ordered family of a
 // chunk, DP launches in sub-ranges under the trace-back budget.  `who` names the entry point in error messages.
+// weight_set / n_sets: sina_hip_align_families_wsets (p->weights holds n_sets vectors, weight_set[q] names query q's).
 int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build, bool profile_batch, const uint32_t *fam_ids,
                          const uint64_t *fam_off, uint32_t nq, const uint8_t *qmask, const uint64_t *qoff,
-                         const sina_hip_align_params *p, sina_hip_align_out *out, uint32_t *out_pos);
+                         const sina_hip_align_params *p, sina_hip_align_out *out, uint32_t *out_pos,
+                         const uint32_t *weight_set = nullptr, uint32_t n_sets = 1);
 }  // namespace sina_hip
 
 namespace sina_hip {

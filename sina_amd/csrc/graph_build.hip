@@ -880,10 +880,16 @@ namespace sina_hip {
 
 int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build, bool profile_batch, const uint32_t *fam_ids,
                          const uint64_t *fam_off, uint32_t nq, const uint8_t *qmask, const uint64_t *qoff,
-                         const sina_hip_align_params *p, sina_hip_align_out *out, uint32_t *out_pos) {
+                         const sina_hip_align_params *p, sina_hip_align_out *out, uint32_t *out_pos,
+                         const uint32_t *weight_set, uint32_t n_sets) {
     const std::string w(who);
     if (!c || !fam_ids || !fam_off || !qmask || !qoff || !p || !out)
         SH_FAIL(w + ": null argument");
+    if (check_weight_sets(who, p, weight_set, n_sets, nq)) return 1;
+    if (weight_set == nullptr || n_sets == 1) {  // (one vector for all: the call of the entry without the suffix)
+        weight_set = nullptr;
+        n_sets = 1;
+    }
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
     if (!c->st->have_refs) SH_FAIL(w + ": upload references first");
@@ -904,7 +910,7 @@ int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build,
     DpPlan pl;
     if (plan_dp(c, maxL, &pl)) return 1;
     const int Lp = pl.geom.Lp();
-    if (upload_weights(c, p)) return 1;
+    if (upload_weights(c, p, n_sets)) return 1;
     if (c->h_out_pos.reserve(4 * std::max<uint64_t>(qoff[nq] - qoff[0], 1))) return 1;
 
     const uint64_t tb_budget_cells = tb_plane_budget(c) / tb_cell_bytes(p->insertion == SINA_INSERTION_FORBID);
@@ -923,7 +929,7 @@ int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build,
         // Queries with the same ORDERED family share one DAG (node order, weights, predecessor lists and the DP's
         // row-slot assignment depend on nothing else): amplicons of one region against one reference clade.  The
         // DAG is built once per distinct family of the chunk; every query keeps its own trace-back cells, spill
-        // rows and edge records.
+        // rows and edge records -- and its own positional weights (weight_set): the DAG holds none.
         dag_of.assign(bq, 0);
         uint32_t n_dags = bq;
         const uint32_t *b_ids = fam_ids;
@@ -1038,7 +1044,8 @@ int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build,
             c->profile_batch = profile_batch;  // (the DP reads the builder's prof16, the walk the entry point's self16)
             c->out_pos_base = qbase - qoff[0];
             if (run_dp_device(c, pl, qd.data(), rq, (uint64_t)n_dags * bg.ncap, tbc, sprows, cells, nqm, p, c->st->width,
-                              out + q0 + r0, out_pos ? out_pos + qbase : nullptr, false, pp, profile_batch ? 0u : bg.ncap))
+                              out + q0 + r0, out_pos ? out_pos + qbase : nullptr, false, pp, profile_batch ? 0u : bg.ncap,
+                              weight_set ? weight_set + q0 + r0 : nullptr))
                 return 1;
             r0 = r1;
         }
@@ -1054,6 +1061,14 @@ int sina_hip_align_families(sina_hip_ctx *c, const uint32_t *fam_ids, const uint
                             const uint8_t *qmask, const uint64_t *qoff, const sina_hip_align_params *p,
                             sina_hip_align_out *out, uint32_t *out_pos) {
     return align_family_batches(c, "align_families", build_graphs_for_launch, false, fam_ids, fam_off, nq, qmask, qoff, p, out, out_pos);
+}
+
+int sina_hip_align_families_wsets(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t nq,
+                                  const uint8_t *qmask, const uint64_t *qoff, const sina_hip_align_params *p,
+                                  const uint32_t *weight_set, uint32_t n_sets, sina_hip_align_out *out, uint32_t *out_pos) {
+    if (p && !(p->weights != nullptr && p->n_weights > 0)) SH_FAIL("align_families_wsets: weight sets need positional weights (p->weights, p->n_weights)");
+    return align_family_batches(c, "align_families_wsets", build_graphs_for_launch, false, fam_ids, fam_off, nq, qmask, qoff, p, out,
+                                out_pos, weight_set, n_sets);
 }
 
 #ifdef SINA_DP_PROFILE

@@ -154,7 +154,8 @@ void extract_tray(pipeline *p, tray &t, result &r, uint32_t query_bases) {
         // one walk over the attributes, the stages' own keys told by their interned addresses
         struct keys_t {
             const std::string *qual = cseq::attr_key(fn::qual), *head = cseq::attr_key(fn::head), *tail = cseq::attr_key(fn::tail),
-                              *idty = cseq::attr_key(fn::idty), *nearest = cseq::attr_key(search_filter::fn_nearest);
+                              *idty = cseq::attr_key(fn::idty), *nearest = cseq::attr_key(search_filter::fn_nearest),
+                              *filter = cseq::attr_key(fn::filter);
         };
         static const keys_t keys;
         r.idty = -1.f;
@@ -164,7 +165,10 @@ void extract_tray(pipeline *p, tray &t, result &r, uint32_t query_bases) {
             else if (kv.name == keys.head) r.head = iv ? *iv : c.get_attr<int>(fn::head);
             else if (kv.name == keys.tail) r.tail = iv ? *iv : c.get_attr<int>(fn::tail);
             else if (kv.name == keys.idty) r.idty = c.get_attr<float>(fn::idty);
-            else {
+            else if (kv.name == keys.filter) {  // (align_filter_slv: kept where a filter was chosen; absent reads as "")
+                const std::string *f = std::get_if<std::string>(&kv.second);
+                if (f && !f->empty()) r.attrs[fn::filter].assign(*f);
+            } else {
                 const std::string &k = kv.key();
                 if (kv.name == keys.nearest || k.compare(0, 4, "lca_") == 0 || k.compare(0, 5, "copy_") == 0)
                     r.attrs[k] = c.get_attr<std::string>(k);
@@ -251,6 +255,29 @@ int sina_host_add_filter(const char *key, const char *name, const float *weights
     try {
         reference_store::get(key)->getAlignmentStats().emplace_back(std::string(name),
                                                                     std::vector<float>(weights, weights + n));
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
+
+// Test hook, no device involved: the --auto-filter-field vote (autofilter_vote, stages.h) of a family given as
+// reference ids over the store's registered filters and its references' `field`.  *chosen: the filter's number in
+// registration order, or -1 (no match); its name goes to name_out (if given; empty for no match).  A negative
+// threshold stands for famfinder's --auto-filter-threshold as it is set.
+int sina_host_autofilter_vote(const char *key, const uint32_t *ids, uint32_t n, const char *field, const char *prefix,
+                              float threshold, int *chosen, char *name_out, uint32_t name_cap) {
+    try {
+        auto st = reference_store::get(key);
+        std::vector<std::string> names, fields;
+        for (const alignment_stats &as : st->getAlignmentStats()) names.push_back(as.getName());
+        for (uint32_t x = 0; x < n; x++) {
+            if (ids[x] >= st->size()) throw std::logic_error("autofilter_vote: no such reference");
+            fields.push_back(st->getCseq(ids[x]).get_attr<std::string>(field));
+        }
+        const int best = autofilter_vote(names, fields, prefix, threshold < 0.f ? famfinder::auto_filter_threshold() : threshold);
+        if (chosen) *chosen = best;
+        if (name_out && name_cap) snprintf(name_out, name_cap, "%s", best >= 0 ? names[(size_t)best].c_str() : "");
         return 0;
     } catch (const std::exception &e) {
         return fail(e);
@@ -1044,7 +1071,8 @@ const char *sina_host_result_family(void *pp, uint32_t q) {
     return r.family.c_str();
 }
 // search stage: number of results (-1: stage did not run for this query), ids/scores best first,
-// string attributes it set on the sequence (nearest_slv, lca_<field>, copy_<acc>_<field>; "" if absent)
+// string attributes it set on the sequence (nearest_slv, lca_<field>, copy_<acc>_<field>; "" if absent) -- and the
+// aligner's align_filter_slv
 int sina_host_result_search(void *pp, uint32_t q, uint32_t *ids, float *scores, uint32_t cap) {
     const result &r = result_at(pp, q);
     if (!r.searched) return -1;

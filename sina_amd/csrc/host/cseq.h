@@ -244,6 +244,8 @@ public:
     // writes out only if the field is asked for: composing it for every query was the largest single item of the
     // host's time per query.  `items` and `owner` mean what `render` takes them to mean; reading the attribute any
     // way (get_attr, string_attr, has_attr, get_attrs) renders it into its slot first.
+    // `owner` must outlive the sequence: famfinder's is the reference store, which outlives the trays of its queries
+    // (the filter a tray points at, tray::astats in stages.h, relies on the same).
     struct lazy_text {
         const std::string *name = nullptr;  // interned key of the attribute it stands for (nullptr: none pending)
         std::vector<uint64_t> items;

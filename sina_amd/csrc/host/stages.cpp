@@ -19,6 +19,7 @@
 #include <sys/stat.h>
 #include <chrono>
 #include <map>
+#include <tuple>
 #include <unordered_map>
 
 namespace sina {
@@ -444,7 +445,7 @@ void tray::destroy() {  // (src/tray.cpp:77-86; the objects go back to their cac
     object_cache<cseq, cache_aligned_seq>::give(aligned_sequence);
     object_cache<search::result_vector>::give(alignment_reference);
     object_cache<search::result_vector>::give(search_result);
-    if (astats != alignment_stats::shared_default()) delete astats;
+    // (astats is the store's or the shared default: not the tray's to delete, stages.h)
     input_sequence = aligned_sequence = nullptr;
     alignment_reference = search_result = nullptr;
     astats = nullptr;
@@ -1005,6 +1006,8 @@ struct ff_options {
     TURN_TYPE turn_which;
     ENGINE_TYPE engine;
     std::string posvar_filter;
+    std::string posvar_autofilter_field;  // --auto-filter-field: empty = off
+    float posvar_autofilter_thres;        // --auto-filter-threshold
     unsigned int fs_min, fs_max;
     float fs_msc, fs_msc_max;
     bool fs_leave_query_out;
@@ -1032,6 +1035,7 @@ ff_options ff_defaults() {  // src/famfinder.cpp:144-203
     o.fs_min_len = 150;
     o.fs_cover_gene = 0;
     o.long_queries = false;
+    o.posvar_autofilter_thres = 0.8f;  // src/famfinder.cpp:205-208
     return o;
 }
 ff_options ff_opts = ff_defaults();
@@ -1099,6 +1103,8 @@ void famfinder::set_option(const std::string &name, const std::string &value) {
     else if (name == "fs-leave-query-out") o.fs_leave_query_out = to_bool(value);
     else if (name == "fs-cover-gene") o.fs_cover_gene = (unsigned)std::stoul(value);
     else if (name == "filter") o.posvar_filter = value;
+    else if (name == "auto-filter-field") o.posvar_autofilter_field = value;
+    else if (name == "auto-filter-threshold") o.posvar_autofilter_thres = std::stof(value);
     else if (name == "long-queries") o.long_queries = to_bool(value);
     else throw std::logic_error("famfinder: unknown option " + name);
 }
@@ -1110,6 +1116,7 @@ void famfinder::validate_options() {  // src/famfinder.cpp:213-239
         throw std::logic_error("Family Finder: fs-kmer-len must be in 1..12 on this engine");
 }
 ENGINE_TYPE famfinder::get_engine() { return ff_opts.engine; }
+float famfinder::auto_filter_threshold() { return ff_opts.posvar_autofilter_thres; }
 
 class famfinder::impl {
 public:
@@ -1196,14 +1203,60 @@ void famfinder::impl::orient_batch(std::vector<tray *> &batch) {
     }
 }
 
-// src/famfinder.cpp:381-436 without the auto-filter (needs ARB fields)
+int autofilter_vote(const std::vector<std::string> &filter_names, const std::vector<std::string> &field_texts,
+                    const std::string &prefix, float threshold) {
+    auto istarts_with = [](const std::string &text, const std::string &head) {
+        if (head.size() > text.size()) return false;
+        for (size_t i = 0; i < head.size(); i++)
+            if (tolower((unsigned char)text[i]) != tolower((unsigned char)head[i])) return false;
+        return true;
+    };
+    std::vector<std::string> texts;
+    texts.reserve(field_texts.size());
+    for (const std::string &f : field_texts) texts.push_back(prefix + ":" + f);
+    int best_count = 0, best = -1;
+    for (size_t x = 0; x < filter_names.size(); x++) {
+        int n = 0;
+        for (const std::string &f : texts)
+            if (istarts_with(f, filter_names[x])) ++n;
+        if (n > best_count) {  // (strictly: the first registered of equals stays -- the reference's "fixme")
+            best_count = n;
+            best = (int)x;
+        }
+    }
+    // (int > size_t * float in the reference: both sides as float, the product rounded to float)
+    const float quorum = (float)field_texts.size() * threshold;
+    return (float)best_count > quorum ? best : -1;
+}
+
+// src/famfinder.cpp:381-436.  The tray points at the store's filter (stages.h, tray::astats); the fields the
+// auto-filter reads are the store's per-reference database fields (reference_store::set_attr), a relative without
+// the field contributing the empty string.
 void famfinder::impl::select_astats(tray &t) {
     alignment_stats *astats = nullptr;
+    std::deque<alignment_stats> &vastats = arb->getAlignmentStats();
     if (!ff_opts.posvar_filter.empty()) {
-        for (alignment_stats &as : arb->getAlignmentStats()) {
+        for (alignment_stats &as : vastats) {
             if (as.getName() == ff_opts.posvar_filter || as.getName() == ff_opts.posvar_filter + ":ALL" ||
                 as.getName() == ff_opts.posvar_filter + ":all")
-                astats = new alignment_stats(as);  // trays own (and delete) their astats
+                astats = &as;
+        }
+    }
+    if (!ff_opts.posvar_autofilter_field.empty() && t.alignment_reference != nullptr) {
+        std::vector<std::string> names, fields;
+        names.reserve(vastats.size());
+        for (const alignment_stats &as : vastats) names.push_back(as.getName());
+        fields.reserve(t.alignment_reference->size());
+        for (const auto &r : *t.alignment_reference) {
+            arb->loadKey(*r.sequence, ff_opts.posvar_autofilter_field);
+            fields.push_back(r.sequence->get_attr<std::string>(ff_opts.posvar_autofilter_field));
+        }
+        const int best = autofilter_vote(names, fields, ff_opts.posvar_filter, ff_opts.posvar_autofilter_thres);
+        if (best >= 0) {
+            t.log << "autofilter: " << vastats[(size_t)best].getName() << ";";
+            astats = &vastats[(size_t)best];
+        } else {
+            t.log << "autofilter: no match;";
         }
     }
     if (astats == nullptr) astats = alignment_stats::shared_default();
@@ -1594,6 +1647,9 @@ static aligner::options al_defaults() {  // src/align.cpp:231-274
     o.gap_ext_penalty = 2.0f;
     o.debug_graph = o.write_used_rels = o.use_subst_matrix = false;
     o.device_graph = true;  // family DAGs are built on the GPU (sina_hip_align_families)
+    // the weighted trays of a batch go to the device in one call whatever filters they chose (--auto-filter-field):
+    // sina_hip_align_families_wsets; off: one call per filter
+    o.weight_sets = true;
     // --fs-no-graph profiles are built on the GPU (sina_hip_align_profiles) only on request: the device route gives the
     // host route's bytes, but the two have not been timed against each other yet (tools/perf_profile.py), so the
     // route that has always been taken stays the default
@@ -1641,6 +1697,7 @@ void aligner::set_option(const std::string &name, const std::string &value) {
     } else if (name == "device-graph") o.device_graph = to_bool(value);
     else if (name == "device-profile") o.device_profile = to_bool(value);
     else if (name == "wide-fallback") o.wide_fallback = to_bool(value);
+    else if (name == "weight-sets") o.weight_sets = to_bool(value);
     else if (name == "db") o.database = value;
     else throw std::logic_error("aligner: unknown option " + name);
 }
@@ -1851,8 +1908,9 @@ static bool prepare_tray(tray &t, const aligner::options &o, reference_store *pr
     return true;
 }
 
-// Takes the options and a group's positional weights (empty: simple scheme; they outlive the result); gives the device call's parameters.
-static sina_hip_align_params make_align_params(const aligner::options &o, const std::vector<float> &weights) {
+// Takes the options and a group's positional weights (none: simple scheme; they outlive the result; a group of several
+// filters: their vectors of n_weights floats one after the other); gives the device call's parameters.
+static sina_hip_align_params make_align_params(const aligner::options &o, const float *weights, size_t n_weights) {
     sina_hip_align_params p;
     sina_hip_align_params_default(&p);
     p.match_score = o.match_score;
@@ -1863,8 +1921,8 @@ static sina_hip_align_params make_align_params(const aligner::options &o, const 
     p.overhang = (int)o.overhang;
     p.lowercase = (int)o.lowercase;
     p.insertion = (int)o.insertion;
-    p.weights = weights.empty() ? nullptr : weights.data();
-    p.n_weights = (uint32_t)weights.size();
+    p.weights = n_weights == 0 ? nullptr : weights;
+    p.n_weights = (uint32_t)n_weights;
     p.assemble = 1;  // (the device finishes what it can: sina_hip_align_out::assembled)
     return p;
 }
@@ -1887,7 +1945,7 @@ static const uint8_t *pack_group_queries(const std::vector<dp_job *> &members, s
     return qmask;
 }
 
-// What the device is given of a group: one SLOT per distinct (query, ordered family); every member reads one slot's results.
+// What the device is given of a group: one SLOT per distinct (query, ordered family, filter); every member reads one slot's results.
 struct device_slots {
     size_t dnq = 0;                   // number of slots
     std::vector<uint32_t> slot_of;    // [members] slot of group member x
@@ -1896,10 +1954,13 @@ struct device_slots {
     const std::vector<dp_job *> *members = nullptr;
     std::vector<uint32_t> first;  // [dnq] first member of slot u; empty if nothing repeats (slot u is member u)
     const dp_job &job(size_t u) const { return *(*members)[first.empty() ? u : first[u]]; }  // the job slot u is aligned for
+    // a group of several filters (sina_hip_align_families_wsets): the vector of slot u among the call's; empty: one for all
+    std::vector<uint32_t> set_of;
+    uint32_t n_sets = 1;
 };
 
-// Repeated queries -- the same bases in the same case against the same ordered family: amplicon runs are full of
-// them -- are aligned ONCE (one DAG, one DP, one walk); every tray then finishes from the device results of its first
+// Repeated queries -- the same bases in the same case against the same ordered family under the same filter: amplicon
+// runs are full of them -- are aligned ONCE (one DAG, one DP, one walk); every tray then finishes from the device results of its first
 // occurrence, with its own name, log and attributes (group_equal_items above).  Takes a group, packs its queries
 // (pack_group_queries); gives the slots.  Where nothing repeats the packing is handed on as it is: nothing is copied.
 static device_slots distinct_slots(const std::vector<dp_job *> &members) {
@@ -1919,11 +1980,12 @@ static device_slots distinct_slots(const std::vector<dp_job *> &members) {
                 hf = (hf ^ (uint64_t)reinterpret_cast<uintptr_t>(jb.member(y))) * 0x100000001b3ull;
                 hf ^= hf >> 29;
             }
+            hf = (hf ^ (uint64_t)reinterpret_cast<uintptr_t>(jb.t->astats)) * 0x100000001b3ull;  // (a group may hold several filters)
             return hash_ends(qmask + qoff[x], qoff[x + 1] - qoff[x], hf);
         },
         [&](size_t a, size_t b) {
             const dp_job &ja = *members[a], &jb = *members[b];
-            if (qoff[a + 1] - qoff[a] != qoff[b + 1] - qoff[b] || ja.family_size() != jb.family_size()) return false;
+            if (qoff[a + 1] - qoff[a] != qoff[b + 1] - qoff[b] || ja.family_size() != jb.family_size() || ja.t->astats != jb.t->astats) return false;
             for (size_t y = 0; y < ja.family_size(); y++)
                 if (ja.member(y) != jb.member(y)) return false;
             return memcmp(qmask + qoff[a], qmask + qoff[b], qoff[a + 1] - qoff[a]) == 0;
@@ -2045,6 +2107,11 @@ static uint32_t align_family_ids(sina_hip_ctx *ctx, reference_store &store, cons
     if (o.fs_no_graph) {
         scoped_phase ph("al.align_profiles(C-ABI)");
         rc = sina_hip_align_profiles(ctx, fids.data(), foff.data(), (uint32_t)n, s.dqmask, s.dqoff.data(), &p, out, nullptr);
+    } else if (!s.set_of.empty()) {
+        scoped_phase ph("al.align_families(C-ABI)");
+        rc = sina_hip_align_families_wsets(ctx, fids.data(), foff.data(), (uint32_t)n, s.dqmask, s.dqoff.data(), &p, s.set_of.data(), s.n_sets,
+                                           out, nullptr);
+        hip_check(rc, "align_families_wsets");  // (a group of several filters is not formed with wide-fallback: no second route)
     } else {
         scoped_phase ph("al.align_families(C-ABI)");
         rc = sina_hip_align_families(ctx, fids.data(), foff.data(), (uint32_t)n, s.dqmask, s.dqoff.data(), &p, out, nullptr);
@@ -2270,7 +2337,21 @@ void aligner::operator()(std::vector<tray> &batch) {
     // _profiles would send the whole group, thousands of ordinary queries, back over host-built graphs.
     constexpr size_t kDeviceFamilyMax = 128;
     enum route { route_host_graphs = 0, route_device = 1, route_long = 2 };
-    std::map<std::pair<std::vector<float>, int>, std::vector<dp_job *>> groups;
+    // A group's key: the scheme -- the width of the positional weights, 0 = simple --, the filter and the route.  The
+    // filter is its IDENTITY (the trays point at the store's filters, stages.h), numbered by first appearance in
+    // the batch; weight-sets: the weighted trays on the device route whose filters have the same width are ONE
+    // group whatever the filter (kAnyFilter) -- one DAG build and one DP launch for a batch whose queries chose
+    // several (sina_hip_align_families_wsets).  Not with wide-fallback, whose second route (host-built graphs
+    // after a limit refusal) takes one vector per call.
+    constexpr int kAnyFilter = -2, kNoFilter = -1;
+    std::vector<const alignment_stats *> filters_seen;
+    auto filter_no = [&](const alignment_stats *a) {
+        for (size_t x = 0; x < filters_seen.size(); x++)
+            if (filters_seen[x] == a) return (int)x;
+        filters_seen.push_back(a);
+        return (int)filters_seen.size() - 1;
+    };
+    std::map<std::tuple<size_t, int, int>, std::vector<dp_job *>> groups;
     // (--fs-no-graph: the family as a profile, built by build_family_profile on the host or -- with device-profile on,
     // under the conditions a DAG is built on the device -- by sina_hip_align_profiles; scoring_scheme_profile takes no
     // positional weights, src/align.cpp:428-433)
@@ -2278,20 +2359,55 @@ void aligner::operator()(std::vector<tray> &batch) {
         if (jb.t != nullptr) {
             const bool on_device = o.device_graph && jb.family_size() <= kDeviceFamilyMax;
             const bool is_long = jb.t->input_sequence->size() > SINA_HIP_MAX_QUERY_LEN;  // (prepare_tray: only with wide-fallback)
-            if (o.fs_no_graph) groups[{std::vector<float>(), is_long ? route_long : on_device && o.device_profile ? route_device : route_host_graphs}].push_back(&jb);
-            else groups[{jb.t->astats->getWeights(), is_long ? route_long : on_device ? route_device : route_host_graphs}].push_back(&jb);
+            const size_t w = jb.t->astats->getWeights().size();
+            if (o.fs_no_graph || w == 0) {
+                const int r = is_long ? route_long : on_device && (!o.fs_no_graph || o.device_profile) ? route_device : route_host_graphs;
+                groups[{0, kNoFilter, r}].push_back(&jb);
+            } else {
+                const int r = is_long ? route_long : on_device ? route_device : route_host_graphs;
+                const bool any = r == route_device && o.weight_sets && !o.wide_fallback;
+                groups[{w, any ? kAnyFilter : filter_no(jb.t->astats), r}].push_back(&jb);
+            }
         }
     if (!groups.empty() && !store) store = reference_store::get(db);  // (the DP needs the store: this throws what the lookup above met)
 
     for (auto &grp : groups) {
         const std::vector<dp_job *> &members = grp.second;
-        const sina_hip_align_params p = make_align_params(o, grp.first.first);
-        const device_slots slots = distinct_slots(members);
+        const int grp_route = std::get<2>(grp.first);
+        device_slots slots = distinct_slots(members);
+        // the group's positional weights: its one filter's, in place -- or, where its slots chose several, the distinct
+        // ones copied one after the other, with every slot's number among them
+        const float *weights = nullptr;
+        const size_t n_weights = std::get<0>(grp.first);
+        std::vector<float> several;
+        if (n_weights != 0 && !o.fs_no_graph) {
+            weights = members[0]->t->astats->getWeights().data();
+            if (std::get<1>(grp.first) == kAnyFilter) {
+                std::vector<const alignment_stats *> sets;
+                slots.set_of.resize(slots.dnq);
+                for (size_t u = 0; u < slots.dnq; u++) {
+                    const alignment_stats *a = slots.job(u).t->astats;
+                    size_t x = 0;
+                    while (x < sets.size() && sets[x] != a) x++;
+                    if (x == sets.size()) sets.push_back(a);
+                    slots.set_of[u] = (uint32_t)x;
+                }
+                slots.n_sets = (uint32_t)sets.size();
+                if (sets.size() > 1) {
+                    several.resize(sets.size() * n_weights);
+                    for (size_t x = 0; x < sets.size(); x++) memcpy(several.data() + x * n_weights, sets[x]->getWeights().data(), 4 * n_weights);
+                    weights = several.data();
+                } else {
+                    slots.set_of.clear();  // (one filter after all: the call without sets)
+                }
+            }
+        }
+        const sina_hip_align_params p = make_align_params(o, weights, n_weights);
         std::vector<sina_hip_align_out> out(slots.dnq);
         // (the aligned columns are read where the device copied them, in the context's pinned staging buffer:
         // sina_hip_staged_out_pos -- the context stays leased until the group's last tray is finished)
         auto dev = store->worker_device(reference_store::dev_align);
-        if (grp.first.second == route_long) {
+        if (grp_route == route_long) {
             // One call per slot: a wide mesh of this size fills a launch of the wide kernel nearly alone anyway, and a
             // query whose mesh exceeds SINA_HIP_WIDE_CELLS -- the one thing a call refuses a well-formed query for --
             // then fails alone, softly, with the call's message in its log.  The trays of a slot are finished before
@@ -2327,7 +2443,7 @@ void aligner::operator()(std::vector<tray> &batch) {
             if (o.calc_idty && !aligned.empty()) set_family_identity(aligned, *store);
             continue;
         }
-        const uint32_t width = align_slots(dev.get(), *store, o, p, slots, grp.first.second == route_device, out.data());
+        const uint32_t width = align_slots(dev.get(), *store, o, p, slots, grp_route == route_device, out.data());
         const uint32_t *const staged_pos = sina_hip_staged_out_pos(dev.get());
         {
             scoped_phase ph("al.finish(NAST,log)");

@@ -17,6 +17,7 @@
 #pragma once
 
 #include <condition_variable>
+#include <deque>
 #include <atomic>
 #include <functional>
 #include <future>
@@ -172,6 +173,11 @@ public:
     search::result_vector *alignment_reference{nullptr};
     search::result_vector *search_result{nullptr};
     std::stringstream log;
+    // the positional-variability filter famfinder chose for this query: one of the store's registered filters
+    // (reference_store::getAlignmentStats -- the reference points into its vastats the same way,
+    // src/famfinder.cpp:392,425) or alignment_stats::shared_default().  Not owned: the store outlives its trays, as
+    // it does for the family list a query's align_family_slv is rendered from (cseq.h lazy_text, whose owner is
+    // the store too), and a registered filter never moves or changes.
     alignment_stats *astats{nullptr};
     // set by famfinder when the scores of alignment_reference are raw k-mer counts of its internal
     // engine (value: k, negative with --fs-kmer-no-fast); 0 = unknown.  The aligner's containment
@@ -248,7 +254,9 @@ public:
     const ref_meta &meta(unsigned int id) const { return metas[id]; }
     std::vector<std::string> getSequenceNames() const;
     void loadKey(const cseq &c, const std::string &key) const;  // acc := name, start := "0" if absent
-    std::vector<alignment_stats> &getAlignmentStats() { return vastats; }
+    // the registered filters, in registration order (sina_host_add_filter; before the stages run).  A deque: trays
+    // point at its elements (tray::astats), which therefore must not move when another filter is registered
+    std::deque<alignment_stats> &getAlignmentStats() { return vastats; }
     // field of a reference sequence (what loadKey would fetch from the ARB database: version, start,
     // stop, taxonomy paths ...); set before the stages run
     // (database fields of a reference; not while a pipeline is running)
@@ -308,7 +316,7 @@ private:
     std::vector<ref_meta> metas;
     void fill_metas();
     unsigned int width{0};
-    std::vector<alignment_stats> vastats;
+    std::deque<alignment_stats> vastats;
     int device_id{0};
     bool refs_by_broadcast{false};
     sina_hip_ctx *ctx{nullptr};
@@ -375,12 +383,21 @@ public:
 
     // option names as on the SINA command line: "db", "turn", "fs-kmer-len", "fs-req", "fs-min",
     // "fs-max", "fs-msc", "fs-req-full", "fs-full-len", "fs-req-gaps", "fs-min-len",
-    // "fs-kmer-no-fast", "fs-msc-max", "fs-leave-query-out", "fs-cover-gene", "filter"
+    // "fs-kmer-no-fast", "fs-msc-max", "fs-leave-query-out", "fs-cover-gene", "filter", "auto-filter-field",
+    // "auto-filter-threshold"
     static void set_option(const std::string &name, const std::string &value);
     static void reset_options();
     static void validate_options();
     static ENGINE_TYPE get_engine();
+    static float auto_filter_threshold();  // --auto-filter-threshold as it stands (default 0.8)
 };
+
+// The vote of --auto-filter-field (src/famfinder.cpp:397-429): every relative's text is prefix + ":" + its field;
+// a filter counts the relatives whose text starts with the filter's name, case-insensitively; the filters are
+// visited in the order given and only a strictly larger count displaces the best; the best is taken iff its count
+// exceeds (float)relatives * threshold, strictly.  Gives the index of the chosen filter, or -1 (no match).
+int autofilter_vote(const std::vector<std::string> &filter_names, const std::vector<std::string> &field_texts,
+                    const std::string &prefix, float threshold);
 
 // ---------------------------------------------------------------- aligner
 enum OVERHANG_TYPE { OVERHANG_ATTACH, OVERHANG_REMOVE, OVERHANG_EDGE };
@@ -402,6 +419,8 @@ public:
         bool wide_fallback;   // families beyond the fast DP path's limits go through sina_hip_align_graphs_any (default off)
         bool device_profile;  // fs_no_graph: build the family profile on the GPU too (needs device_graph; default off: see stages.cpp)
         bool device_graph;  // build the family DAG on the GPU (default) or on the host
+        bool weight_sets;   // device-built DAGs: the weighted trays of a batch in ONE call whatever their filters
+                            // (sina_hip_align_families_wsets; default on) instead of one call per filter
         std::string database;  // reference store the DAGs are built from (same as famfinder "db")
     };
     static options *opts;
@@ -418,7 +437,7 @@ public:
     void operator()(std::vector<tray> &batch);
 
     // "realign", "overhang", "lowercase", "insertion", "fs-weight", "match-score",
-    // "mismatch-score", "pen-gap", "pen-gapext", "write-used-rels", "calc-idty", "db"
+    // "mismatch-score", "pen-gap", "pen-gapext", "write-used-rels", "calc-idty", "db", "weight-sets"
     static void set_option(const std::string &name, const std::string &value);
     static void reset_options();
     static void validate_options();

@@ -262,10 +262,10 @@ template <int B, bool WEIGHTED, bool FORBID, bool BELOW_INIT, bool DBG>
 __global__ void __launch_bounds__(64, (B <= 4 ? 4 : (B <= 8 ? 3 : 2)))
 mesh_dp_kernel(const QDesc *__restrict__ qdv, const uint32_t *__restrict__ orderv, const uint4 *__restrict__ recv, const uint32_t *__restrict__ predv,
                const uint32_t *__restrict__ node_posv, const uint32_t *__restrict__ succ_minposv,
-               const uint8_t *__restrict__ qmaskv, const float *__restrict__ weights, uint32_t n_weights,
-               void *__restrict__ tbv, float *__restrict__ dbg_value, float *spillv, EdgeRec *edgev,
-               uint64_t edge_stride, uint32_t n_strips, DpResult *__restrict__ resv, float ms, float mms, float gp,
-               float gpe, const float *__restrict__ prof16v, DryArgs dry) {
+               const uint8_t *__restrict__ qmaskv, const float *__restrict__ weightsv, uint32_t n_weights,
+               const uint32_t *__restrict__ wsetv, void *__restrict__ tbv, float *__restrict__ dbg_value, float *spillv,
+               EdgeRec *edgev, uint64_t edge_stride, uint32_t n_strips, DpResult *__restrict__ resv, float ms, float mms,
+               float gp, float gpe, const float *__restrict__ prof16v, DryArgs dry) {
     static_assert(B % 4 == 0, "16-byte accesses per array");
     constexpr int kStrip = 64 * B;  // columns per strip
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -299,6 +299,12 @@ mesh_dp_kernel(const QDesc *__restrict__ qdv, const uint32_t *__restrict__ order
     TbCell *__restrict__ tb = reinterpret_cast<TbCell *>(tbv) + uniform(d.tb_off);
     float *spill = spillv + uniform(d.spill_off) * (size_t)(2 * Lp);
     const uint64_t q_off = uniform(d.q_off);
+    // the query's own positional weights: one of the launch's vectors of n_weights floats (the _wsets entries; the
+    // clamp at a vector's end then stays inside it)
+    const float *__restrict__ weights = weightsv;
+    if constexpr (WEIGHTED) {
+        if (wsetv != nullptr) weights = weightsv + (size_t)uniform(wsetv[qi]) * n_weights;
+    }
 
     // end-cell search (mesh.h:567-592), accumulated over the strips
     const uint32_t strip_last = (L - 1) / (uint32_t)kStrip;         // the strip that owns column L-1
@@ -2118,13 +2124,16 @@ __device__ __forceinline__ void walk_query(const BtArgs &a, uint32_t q, const QD
         }
     }
     const uint8_t *qmb = a.qmask + d.q_off;
+    // (the query's own positional weights, as in mesh_dp_kernel)
+    const float *wts = a.weights;
+    if (wts != nullptr && a.wset != nullptr) wts += (size_t)a.wset[q] * a.n_weights;
     auto mscore_at = [&](const uint4 &rx, uint32_t si) -> float {  // tr.s.match(sum, ab2, ab1) with comp()==true
         // (--fs-no-graph: the master copy takes the slave's base, its profile is compared with itself)
         if (a.self16 != nullptr) return a.self16[qmb[si] & 0xfu];
         const float wgt = __uint_as_float(rx.y);
-        if (a.weights != nullptr) {
+        if (wts != nullptr) {
             const uint32_t nw1 = a.n_weights - 1;
-            return a.ms * a.weights[rx.w < nw1 ? rx.w : nw1] * wgt;
+            return a.ms * wts[rx.w < nw1 ? rx.w : nw1] * wgt;
         }
         return a.ms * wgt;
     };
@@ -2369,7 +2378,7 @@ int launch_tb(bool weighted, bool forbid, const DpArgs &a, uint32_t nq, uint32_t
         auto kfn = a.dbg_value ? mesh_dp_kernel<B, WG, FB, BL, true> : mesh_dp_kernel<B, WG, FB, BL, false>;     \
         if (allow_full_lds(reinterpret_cast<const void *>(kfn))) return 1;                               \
         hipLaunchKernelGGL(kfn, dim3(nq), dim3(64), lds, s, a.qd, a.order, a.rec, a.pred, a.node_pos, a.succ_minpos, \
-                           a.qmask, a.weights, a.n_weights, a.tb, a.dbg_value, a.spill, a.edge, a.edge_stride, \
+                           a.qmask, a.weights, a.n_weights, a.wset, a.tb, a.dbg_value, a.spill, a.edge, a.edge_stride, \
                            n_strips, a.res, a.ms, a.mms, a.gp, a.gpe, a.prof16, a.dry);                  \
     } while (0)
     // the simple scheme with gap_open >= gap_extend in a launch below the initial value (every BASELINE

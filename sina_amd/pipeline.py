@@ -30,6 +30,8 @@ def load_host():
     H.sina_host_store_close.argtypes = [C.c_char_p]
     H.sina_host_add_filter.argtypes = [C.c_char_p, C.c_char_p, capi.f32p, C.c_uint32]
     H.sina_host_set_option.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]
+    H.sina_host_autofilter_vote.argtypes = [C.c_char_p, capi.u32p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_float,
+                                            C.POINTER(C.c_int), C.c_char_p, C.c_uint32]
     H.sina_host_pipeline_create.restype = vp
     H.sina_host_pipeline_destroy.argtypes = [vp]
     H.sina_host_pipeline_destroy.restype = None
@@ -153,6 +155,17 @@ class Store:
     def add_filter(self, name, weights):
         w = np.ascontiguousarray(weights, np.float32)
         _chk(self.H.sina_host_add_filter(self.key.encode(), name.encode(), w.ctypes.data_as(capi.f32p), len(w)))
+
+    def autofilter_vote(self, ids, field, prefix="", threshold=-1.0):
+        """famfinder's --auto-filter-field vote for a family given as reference ids (no device involved): (number of the
+        chosen filter in registration order or -1, its name or "").  threshold < 0: famfinder's auto-filter-threshold
+        as it is set."""
+        ids = np.ascontiguousarray(ids, np.uint32)
+        chosen = C.c_int()
+        name = C.create_string_buffer(512)
+        _chk(self.H.sina_host_autofilter_vote(self.key.encode(), ids.ctypes.data_as(capi.u32p), len(ids), field.encode(),
+                                              prefix.encode(), threshold, C.byref(chosen), name, 512))
+        return chosen.value, name.value.decode()
 
     def build_profile(self, ids, match, mismatch, gap, gap_ext, cap=200000):
         """--fs-no-graph: (columns, match-term table [n, 16], self table [16]) of a family as the aligner builds them."""

@@ -107,6 +107,16 @@ int sina_hip_align_families(sina_hip_ctx *c, const uint32_t *, const uint64_t *,
     }
     return 0;
 }
+int sina_hip_align_families_wsets(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t nq, const uint8_t *qmask,
+                                  const uint64_t *qoff, const sina_hip_align_params *p, const uint32_t *, uint32_t,
+                                  sina_hip_align_out *out, uint32_t *out_pos) {
+    return sina_hip_align_families(c, fam_ids, fam_off, nq, qmask, qoff, p, out, out_pos);
+}
+int sina_hip_align_graphs_wsets(sina_hip_ctx *, const sina_hip_graph_batch *, const uint8_t *, const uint64_t *,
+                                const sina_hip_align_params *, const uint32_t *, uint32_t, sina_hip_align_out *, uint32_t *) {
+    g_err = "stub";
+    return 1;
+}
 int sina_hip_align_graphs(sina_hip_ctx *, const sina_hip_graph_batch *, const uint8_t *, const uint64_t *,
                           const sina_hip_align_params *, sina_hip_align_out *, uint32_t *) { g_err = "stub"; return 1; }
 int sina_hip_align_graphs_any(sina_hip_ctx *, const sina_hip_graph_batch *, const uint8_t *, const uint64_t *,
