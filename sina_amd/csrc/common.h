@@ -311,8 +311,11 @@ inline bool dp_below_init(uint32_t max_n, float gp, float gpe) {
     return gp >= 0.f && gpe >= 0.f && 1.0f + (float)max_n * gp * 1.01f + gp + gpe < 900000.0f;
 }
 
-constexpr int kBuiltWords = 8;     // u32 words a device builder reports per family (BuiltGraphs::sizes, ctx.h)
-constexpr int kBuiltChainLen = 6;  // ... of which this one is the number of bases of member 0: the length of its chain
+// u32 words a device builder reports per family (BuiltGraphs::sizes, dp_plan.h): nodes, raw edge entries, spill rows,
+// status, QDesc::first_sink, QDesc::gmin, bases of member 0 (the length of its chain)
+constexpr int kBuiltWords = 8;
+constexpr int kBuiltN = 0, kBuiltEdges = 1, kBuiltSpill = 2, kBuiltStatus = 3, kBuiltFirstSink = 4, kBuiltGmin = 5, kBuiltChainLen = 6;
+constexpr uint32_t kBuiltNodeCap = 2, kBuiltSpillCap = 4;  // status, if not 0: more nodes than the arrays hold (or 65535) / too many spill rows
 
 struct DpArgs {
     const QDesc *qd;
@@ -413,18 +416,32 @@ struct DpPlan {
 struct sina_hip_ctx;
 
 namespace sina_hip {
+// ---- the DP driver (dp_launch.hip)
+inline bool weighted_scheme(const sina_hip_align_params *p) { return p->weights != nullptr && p->n_weights > 0; }
 int plan_dp(sina_hip_ctx *c, uint32_t maxL, DpPlan *pl);
 int upload_weights(sina_hip_ctx *c, const sina_hip_align_params *p, uint32_t n_sets = 1);  // n_sets vectors of p->n_weights floats
-// (the _wsets entries) weight_set[q] < n_sets for the call's nq queries, and weights to choose from
-int check_weight_sets(const char *who, const sina_hip_align_params *p, const uint32_t *weight_set, uint32_t n_sets, uint32_t nq);
-// chain_ncap: node entries per DAG of the device-built DAGs whose first member's chain the build left in the
-// context (ctx.h, scout); 0: the DAGs are the caller's or profiles -- no chain, no scout pass
-// wset_host: the weight vector of each of the bq queries (the _wsets entries), or nullptr: one vector for all
-int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const QDesc *qd_host, uint32_t bq, uint64_t n_node_entries,
-                  uint64_t tb_cells, uint64_t spill_rows, uint64_t cells, uint64_t nqm, const sina_hip_align_params *p, uint32_t width,
-                  sina_hip_align_out *out, uint32_t *out_pos, bool want_dbg_value, const PrunePlan &pp,
-                  uint32_t chain_ncap = 0, const uint32_t *wset_host = nullptr);
-// What a launch may skip rows with (api.hip): the scoring of `p` (non-negative gap costs, the simple scheme), the
+// (the _wsets entries) weight_set[q] < n_sets for the call's nq queries, and weights to choose from.  One vector for
+// all -- the call of the entry without the suffix -- leaves as weight_set = nullptr, n_sets = 1.
+int check_weight_sets(const char *who, const sina_hip_align_params *p, const uint32_t **weight_set, uint32_t *n_sets, uint32_t nq);
+// One DP launch: bq queries whose graphs (qd, rec, pred, node_pos, succ_minpos) and query masks are already in the
+// context's device buffers.
+struct DpLaunch {
+    const QDesc *qd = nullptr;  // host copy of what the context's qd buffer holds
+    uint32_t bq = 0, width = 0;
+    uint64_t nqm = 0;  // query bases of the launch
+    sina_hip_align_out *out = nullptr;
+    uint32_t *out_pos = nullptr;  // (optional) the launch's place in the caller's array, and ...
+    uint64_t out_pos_base = 0;    // ... in the context's staged columns (ctx.h, h_out_pos)
+    bool profile_batch = false;   // the DP reads the context's prof16, the walk its self16
+    bool debug_planes = false, want_dbg_value = false;  // sina_hip_debug_mesh: planes to unpack, a plane of cell values
+    // node entries per DAG of the device-built DAGs whose first member's chain the build left in the context (ctx.h,
+    // scout); 0: the DAGs are the caller's or profiles -- no chain, no scout pass
+    uint32_t chain_ncap = 0;
+    const uint32_t *wset = nullptr;  // the weight vector of each of the bq queries (the _wsets entries), or nullptr: one vector for all
+};
+// Runs DP + backtrack for the launch and copies the results back.
+int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const sina_hip_align_params *p, const DpLaunch &l);
+// What a launch may skip rows with: the scoring of `p` (non-negative gap costs, the simple scheme), the
 // largest and smallest node weight it will see, its longest query.  SINA_HIP_DP_PRUNE=0: never.
 PrunePlan prune_plan(const sina_hip_align_params *p, float wmax, float wmin, uint32_t maxL, bool profile_batch);
 

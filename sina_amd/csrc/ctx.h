@@ -7,7 +7,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "common.h"
+#include "dp_plan.h"
 
 // Reference store + k-mer index (HBM-resident) and the cumulative counters.  Owned by the context
 // sina_hip_init() made; contexts made by sina_hip_fork() point at their parent's.
@@ -73,7 +73,7 @@ struct sina_hip_store {
     // these at once (hipMalloc / hipFree synchronise the device; never in steady state)
     std::atomic<size_t> cap_hint[64] = {};  // (indexed like sina_hip_ctx::scratch(): kNumScratch entries; read without a lock)
     // certified row skip of the DP kernel (mesh_dp.hip PRUNE): the guess rho of "optimum / bound on the whole gain"
-    // the next launch starts its queries with, learnt from the queries aligned so far (run_dp_device; under stats_mu).
+    // the next launch starts its queries with, learnt from the queries aligned so far (dp_launch.hip, account_launch; under stats_mu).
     // Results never depend on it: a guess that is too bold costs the queries it fails a second sweep, a timid one
     // a wider band.
     float prune_rho = 0.80f;        // the guess a launch WITHOUT a scout pass starts from (below the smallest ratio seen)
@@ -121,10 +121,7 @@ struct sina_hip_ctx {
     uint64_t long_queries = 0;        // queries the long k-mer count kernel has counted on this context (sina_hip_long_queries)
     sina_hip::DevBuf scout, scout_u;  // the scout pass (mesh_dp.hip): the DAG build's chain rows (u16 [DAGs][ncap]), and its result -- a bound U per query
     sina_hip::HostBuf h_res;          // pinned copy of a launch's DpResults (row-skip statistics, the next launch's guess)
-    bool profile_batch = false;       // the launch being prepared is one (set by sina_hip_align_graphs)
     void *last_tb = nullptr;  // the plane of the last launch (debug read-back: sina_hip_debug_mesh)
-    bool dbg_planes = false;  // the launch being prepared is sina_hip_debug_mesh's: its planes are unpacked cell by cell
-    bool no_prune = false;    // ... and it asked for a sweep of every row (sina_hip_debug_mesh, prune = 0)
     bool last_scout = false;  // the last launch's bounds came from the scout pass
     uint32_t last_bq = 0, last_prune_step = 0;  // queries / assumed largest step gain of the last launch (sina_hip_debug_dp_info)
     sina_hip::DevBuf k_qoff, k_scores, k_out_ids, k_out_scores, k_out_n, k_tmp0, k_tmp1, k_tmp2;
@@ -132,8 +129,7 @@ struct sina_hip_ctx {
     sina_hip::DevBuf s_qab, s_qoff, s_cand, s_coff, s_out;  // search-stage comparison
     sina_hip::HostBuf h_out, h_out_pos;  // pinned staging for the DP results
     // h_out_pos holds the aligned columns of a whole align call (laid out like the caller's out_pos): a launch
-    // range writes at out_pos_base, callers that pass no out_pos read them here (sina_hip_staged_out_pos)
-    uint64_t out_pos_base = 0;
+    // range writes at DpLaunch::out_pos_base, callers that pass no out_pos read them here (sina_hip_staged_out_pos)
     sina_hip::HostBuf h_stage[12];       // pinned staging of the per-batch uploads / downloads (sina_hip::upload)
     float wtab_fs_weight = NAN;  // fs_weight the device weight table was computed for
     uint32_t prof_ncap = 0;      // nodes per profile the profile builds (profile_build.hip) size their arrays for: the largest seen so far
@@ -243,9 +239,8 @@ inline uint64_t tb_plane_budget(sina_hip_ctx *c) {
     // has to grow is freed first).  Two stores on one device, or two ranks sharing a GPU, each decided their budget
     // when most of the memory was free; the one that comes second splits its launches to what is left instead of
     // failing in hipMalloc.  (SINA_HIP_TB_GB still wins: an explicit size is taken as given.)
-    // (asked only while the pool is still being built: once every plane exists launches repeat their sizes, and
-    // hipMemGetInfo is not a call to make per batch)
-    // (asked while the pool is still being built -- and latched per number of planes made so far: with one context in
+    // (asked while the pool is still being built -- once every plane exists launches repeat their sizes, and
+    // hipMemGetInfo is not a call to make per batch -- and latched per number of planes made so far: with one context in
     // flight the second plane is never made, and a budget that moved with the free memory on every call made the
     // launch sizes stop repeating)
     int made = 0;
@@ -336,12 +331,6 @@ namespace sina_hip {
 // 3072 queries 27.7 ms, 4096 41.1 ms, 6144 49.7 ms).
 inline uint32_t dp_wave_slots(const sina_hip_ctx *c, int B) {
     return (uint32_t)(dp_waves_per_simd(B) * 4 * (c->n_cu > 0 ? c->n_cu : 256));
-}
-// End of a DP launch range that the trace-back budget cut short (q1 < limit): whole rounds of wave
-// slots if it holds at least one.
-inline uint32_t dp_round_range(uint32_t q0, uint32_t q1, uint32_t limit, uint32_t slots) {
-    const uint32_t n = q1 - q0;
-    return (q1 < limit && n > slots) ? q0 + n / slots * slots : q1;
 }
 }  // namespace sina_hip
 
@@ -580,23 +569,27 @@ namespace sina_hip {
 // ---- alignment against device-built templates: sina_hip_align_families (the family as a DAG, graph_build.hip) and
 // sina_hip_align_profiles (the family as a profile, profile_build.hip) differ in the builder only
 constexpr int kFamilyMax = 128;  // members of a family the device builders take (their per-member LDS records)
-// What a builder left in the context's rec / node_pos / succ_minpos / pred (/ rgain, prof16) buffers for the n distinct
-// families of a chunk: family u's node arrays start at u * ncap, its predecessor entries at pred_off[u].
-struct BuiltGraphs {
-    uint32_t ncap = 0;
-    std::vector<uint64_t> pred_off;  // per family, into c->pred
-    std::vector<uint32_t> sizes;     // per family: kBuiltWords words -- N, raw edge entries, n_spill, status, first sink row, gmin, bases of member 0 (its chain: GraphArgs::chain_rows)
-};
 // Builds the templates of families q0 .. q0 + n - 1 (fam_off is absolute); pp: the row skip the launches will run with
 using family_builder = int (*)(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t q0, uint32_t n,
                                const sina_hip_align_params *p, int W, const PrunePlan &pp, BuiltGraphs *bg);
-// The launch loop both entry points share (graph_build.hip): argument checks, one build per DISTINCT ordered family of a
-// chunk, DP launches in sub-ranges under the trace-back budget.  `who` names the entry point in error messages.
-// weight_set / n_sets: sina_hip_align_families_wsets (p->weights holds n_sets vectors, weight_set[q] names query q's).
-int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build, bool profile_batch, const uint32_t *fam_ids,
-                         const uint64_t *fam_off, uint32_t nq, const uint8_t *qmask, const uint64_t *qoff,
-                         const sina_hip_align_params *p, sina_hip_align_out *out, uint32_t *out_pos,
-                         const uint32_t *weight_set = nullptr, uint32_t n_sets = 1);
+// The launch loop both entry points share (dp_launch.hip): argument checks, one build per DISTINCT ordered family of a
+// chunk, DP launches in sub-ranges under the trace-back budget.
+struct FamilyCall {
+    const char *who;  // names the entry point in error messages
+    family_builder build;
+    bool profile_batch;
+    const uint32_t *fam_ids;
+    const uint64_t *fam_off;
+    uint32_t nq;
+    const uint8_t *qmask;
+    const uint64_t *qoff;
+    const sina_hip_align_params *p;
+    sina_hip_align_out *out;
+    uint32_t *out_pos;
+    const uint32_t *weight_set = nullptr;  // sina_hip_align_families_wsets: p->weights holds n_sets vectors, weight_set[q] names query q's
+    uint32_t n_sets = 1;
+};
+int align_family_batches(sina_hip_ctx *c, const FamilyCall &f);
 }  // namespace sina_hip
 
 namespace sina_hip {

@@ -55,7 +55,6 @@ namespace {
 constexpr int kGT = SINA_GRAPH_THREADS;  // threads per workgroup (the phases are latency-bound: more loads in flight per LDS byte)
 constexpr uint32_t kNoPrev = 0xFFFFu;
 constexpr int kMaxFam = kFamilyMax;
-constexpr int kSz = kBuiltWords;  // u32 words the kernel reports per query (GraphArgs::sizes)
 #ifndef SINA_GRAPH_KTC
 #define SINA_GRAPH_KTC 128  // (a multiple of 64: a wave takes 64 consecutive entry slots of one member)
 #endif
@@ -91,7 +90,7 @@ struct GraphArgs {
     uint32_t *succ_min;        // [nq][ncap]
     uint32_t *far_mark;        // [nq][ncap] last successor row of every node (0: none)
     uint32_t *pred;            // per query area of total-family-bases entries
-    uint32_t *sizes;           // [nq][kSz]: N, raw edge entries, n_spill, status (0 ok, 2 N cap, 4 spill rows), first sink row, gmin, chain length
+    uint32_t *sizes;           // [nq][kBuiltWords]: N, raw edge entries, n_spill, status, first sink row, gmin, chain length (common.h, kBuiltN ...)
     uint16_t *chain_rows;      // [nq][ncap]: the node of every base of member 0, in base order (the DP wave's scout pass walks this chain)
     uint32_t width, ncap;
     uint32_t tile_bytes;       // LDS bytes of the tile tables (reused by the slot allocation) = bitmap_off
@@ -304,7 +303,7 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_tasks = F * kCH;  // (member, 64 slots) pairs, a wave each
 
-    uint32_t *sz = a.sizes + kSz * (size_t)q;
+    uint32_t *sz = a.sizes + kBuiltWords * (size_t)q;
     for (uint32_t j = tid; j < F; j += kGT) {
         const uint32_t id = a.fam_ids[f0 + j];
         mb[j].id = id;
@@ -369,9 +368,9 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
     const uint32_t NC = s_tmp[kGT / 64];
     if (NC > 65535u) {  // (cannot be a valid DAG for the DP kernel anyway: more columns than row ids)
         if (tid == 0) {
-            sz[0] = NC;
-            sz[1] = sz[2] = 0;
-            sz[3] = 2;
+            sz[kBuiltN] = NC;
+            sz[kBuiltEdges] = sz[kBuiltSpill] = 0;
+            sz[kBuiltStatus] = kBuiltNodeCap;
         }
         return;
     }
@@ -569,9 +568,9 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
     }
     if (N > a.ncap || N > 65535u) {
         if (tid == 0) {
-            sz[0] = N;
-            sz[1] = sz[2] = 0;
-            sz[3] = 2;
+            sz[kBuiltN] = N;
+            sz[kBuiltEdges] = sz[kBuiltSpill] = 0;
+            sz[kBuiltStatus] = kBuiltNodeCap;
         }
         return;
     }
@@ -663,11 +662,11 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
             if (in_lds) codeL[i] = w;  // (read again by step 8)
         }
         if (tid == 0) {
-            sz[0] = N;
-            sz[1] = E;
-            sz[2] = tot;
-            sz[3] = (tot > kMaxSpillRows) ? 4u : 0u;
-            sz[4] = s_tmp[kGT / 64 + 1];
+            sz[kBuiltN] = N;
+            sz[kBuiltEdges] = E;
+            sz[kBuiltSpill] = tot;
+            sz[kBuiltStatus] = (tot > kMaxSpillRows) ? kBuiltSpillCap : 0u;
+            sz[kBuiltFirstSink] = s_tmp[kGT / 64 + 1];
             sz[kBuiltChainLen] = mb[0].len;
         }
     }
@@ -717,7 +716,7 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
             atomicMin(&s_tmp[kGT / 64 + 2], mx);
         }
         __syncthreads();
-        if (tid == 0) sz[5] = s_tmp[kGT / 64 + 2];
+        if (tid == 0) sz[kBuiltGmin] = s_tmp[kGT / 64 + 2];
         const uint32_t total = block_exscan(cw, cw, N, s_tmp);
         for (uint32_t i = tid; i < N; i += kGT) {
             const uint32_t pos = node_pos[i];
@@ -794,7 +793,7 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
             c->g_tmp1.reserve(8 * (uint64_t)bq) ||
             c->rec.reserve(sizeof(uint4) * (uint64_t)bq * ncap) || c->node_pos.reserve(4 * (uint64_t)bq * ncap) ||
             c->succ_minpos.reserve(4 * (uint64_t)bq * ncap) || c->g_tmp3.reserve(4 * (uint64_t)bq * ncap) ||
-            c->pred.reserve(4 * pred_total) || c->g_sizes.reserve(4 * kSz * (uint64_t)bq) ||
+            c->pred.reserve(4 * pred_total) || c->g_sizes.reserve(4 * kBuiltWords * (uint64_t)bq) ||
             c->scout.reserve(2 * (uint64_t)bq * ncap) ||
             (kappa64 > 0.f && c->rgain.reserve(8 * (uint64_t)bq * ncap)))
             return 1;
@@ -828,7 +827,7 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
         ga.reach = kappa64 > 0.f ? c->rgain.as<uint2>() : nullptr;
         ga.kappa64 = kappa64;
         if (allow_full_lds(reinterpret_cast<const void *>(family_graph_kernel))) return 1;
-        bg->sizes.resize(kSz * (size_t)bq);
+        bg->sizes.resize(kBuiltWords * (size_t)bq);
         {
             heavy_launch hl(c, s, kHeavyGraph);  // (a device-filling kernel: ctx.h)
             SH_CHECK(hipEventRecord(c->ev[6], hl.stream()));
@@ -840,15 +839,16 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
             SH_CHECK(hipEventRecord(c->ev[7], hl.stream()));
             if (hl.done()) return 1;
         }
-        if (download(c, 4, c->g_sizes.p, 4 * kSz * (uint64_t)bq, s)) return 1;
+        if (download(c, 4, c->g_sizes.p, 4 * kBuiltWords * (uint64_t)bq, s)) return 1;
         SH_CHECK(wait_stream(c, s));
-        memcpy(bg->sizes.data(), c->h_stage[4].p, 4 * kSz * (uint64_t)bq);
+        memcpy(bg->sizes.data(), c->h_stage[4].p, 4 * kBuiltWords * (uint64_t)bq);
         float gms = 0;
         SH_CHECK(hipEventElapsedTime(&gms, c->ev[6], c->ev[7]));
         {
             uint64_t bytes = 0;  // algorithmic: the families' bases in, the DAGs out
             for (uint32_t q = 0; q < bq; q++)
-                bytes += 4 * elems[q] + (uint64_t)bg->sizes[kSz * q] * (16 + 4 + (kappa64 > 0.f ? 8 : 0)) + 4 * (uint64_t)bg->sizes[kSz * q + 1];
+                bytes += 4 * elems[q] + (uint64_t)bg->sizes[kBuiltWords * q + kBuiltN] * (16 + 4 + (kappa64 > 0.f ? 8 : 0)) +
+                         4 * (uint64_t)bg->sizes[kBuiltWords * q + kBuiltEdges];
             std::lock_guard<std::mutex> slk(c->st->stats_mu);
             c->st->stats.graph_ms += gms;
             c->st->stats.graph_bytes += bytes;
@@ -856,8 +856,9 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
         }
         uint32_t need_n = 0;
         for (uint32_t q = 0; q < bq; q++) {
-            if (bg->sizes[kSz * q + 3] == 2) need_n = std::max(need_n, bg->sizes[kSz * q]);
-            if (bg->sizes[kSz * q + 3] == 4) SH_FAIL_LIMIT("align_families: too many spill rows for one query");
+            const uint32_t status = bg->sizes[kBuiltWords * q + kBuiltStatus];
+            if (status == kBuiltNodeCap) need_n = std::max(need_n, bg->sizes[kBuiltWords * q + kBuiltN]);
+            if (status == kBuiltSpillCap) SH_FAIL_LIMIT("align_families: too many spill rows for one query");
         }
         if (!need_n) break;
         if (attempt >= 3 || need_n > 65535u) SH_FAIL_LIMIT("align_families: family DAG exceeds device limits");
@@ -876,199 +877,20 @@ int build_graphs_for_launch(sina_hip_ctx *c, const uint32_t *fam_ids, const uint
 
 }  // namespace
 
-namespace sina_hip {
-
-int align_family_batches(sina_hip_ctx *c, const char *who, family_builder build, bool profile_batch, const uint32_t *fam_ids,
-                         const uint64_t *fam_off, uint32_t nq, const uint8_t *qmask, const uint64_t *qoff,
-                         const sina_hip_align_params *p, sina_hip_align_out *out, uint32_t *out_pos,
-                         const uint32_t *weight_set, uint32_t n_sets) {
-    const std::string w(who);
-    if (!c || !fam_ids || !fam_off || !qmask || !qoff || !p || !out)
-        SH_FAIL(w + ": null argument");
-    if (check_weight_sets(who, p, weight_set, n_sets, nq)) return 1;
-    if (weight_set == nullptr || n_sets == 1) {  // (one vector for all: the call of the entry without the suffix)
-        weight_set = nullptr;
-        n_sets = 1;
-    }
-    std::lock_guard<std::mutex> lk(c->mu);
-    sina_hip_hint_guard hints(c);
-    if (!c->st->have_refs) SH_FAIL(w + ": upload references first");
-    if (nq == 0) return 0;
-    SH_CHECK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (c->st->width > 524288u) SH_FAIL_LIMIT(w + ": alignment wider than 524288 columns (use align_graphs)");
-    // (scoring_scheme_profile takes no positional weights, src/align.cpp:428-433: refused like a profile batch of align_graphs)
-    if (profile_batch && p->weights != nullptr && p->n_weights > 0)
-        SH_FAIL(w + ": a profile batch takes no positional weights (scoring_scheme_profile)");
-    uint32_t maxL = 0;
-    for (uint32_t q = 0; q < nq; q++) {
-        const uint64_t L = qoff[q + 1] - qoff[q], F = fam_off[q + 1] - fam_off[q];
-        if (L == 0 || L > 65535) SH_FAIL(w + ": query length must be in 1..65535");
-        if (F == 0 || F > (uint64_t)kMaxFam) SH_FAIL(w + ": family size must be in 1..128");
-        maxL = std::max<uint32_t>(maxL, (uint32_t)L);
-    }
-    DpPlan pl;
-    if (plan_dp(c, maxL, &pl)) return 1;
-    const int Lp = pl.geom.Lp();
-    if (upload_weights(c, p, n_sets)) return 1;
-    if (c->h_out_pos.reserve(4 * std::max<uint64_t>(qoff[nq] - qoff[0], 1))) return 1;
-
-    const uint64_t tb_budget_cells = tb_plane_budget(c) / tb_cell_bytes(p->insertion == SINA_INSERTION_FORBID);
-    // queries per DAG build and DP launch: up to three rounds of DP wave slots (one DP wave per query) -- a DP
-    // launch ends with ~4.4 ms of draining device whatever its size, so a third round makes it 3 % faster per
-    // query than two (a fourth adds 2 % and another 22 GB per trace-back plane); the DP
-    // launches below are whole rounds where the trace-back budget cuts a chunk
-    const uint32_t slots = dp_wave_slots(c, pl.geom.B);
-    const uint32_t chunk_q = 3 * slots;
-    BuiltGraphs bg;
-    std::vector<uint32_t> dag_of;      // per query of the chunk: which of the chunk's distinct DAGs is its family's
-    std::vector<uint32_t> ufam_ids;    // the distinct families, concatenated
-    std::vector<uint64_t> ufam_off;
-    for (uint32_t q0 = 0; q0 < nq; q0 += chunk_q) {
-        const uint32_t bq = std::min(chunk_q, nq - q0);
-        // Queries with the same ORDERED family share one DAG (node order, weights, predecessor lists and the DP's
-        // row-slot assignment depend on nothing else): amplicons of one region against one reference clade.  The
-        // DAG is built once per distinct family of the chunk; every query keeps its own trace-back cells, spill
-        // rows and edge records -- and its own positional weights (weight_set): the DAG holds none.
-        dag_of.assign(bq, 0);
-        uint32_t n_dags = bq;
-        const uint32_t *b_ids = fam_ids;
-        const uint64_t *b_off = fam_off;
-        uint32_t b_q0 = q0;
-        if (bq > 1) {
-            auto fam_hash = [&](uint32_t q) {
-                uint64_t h = 0xcbf29ce484222325ull ^ (fam_off[q + 1] - fam_off[q]);
-                for (uint64_t x = fam_off[q]; x < fam_off[q + 1]; x++) {
-                    h = (h ^ fam_ids[x]) * 0x100000001b3ull;
-                    h ^= h >> 31;
-                }
-                return h;
-            };
-            size_t cap = 16;
-            while (cap < 2 * (size_t)bq) cap <<= 1;
-            std::vector<uint32_t> slot(cap, 0xFFFFFFFFu), first;  // first[u] = first query (in the chunk) of DAG u
-            std::vector<uint64_t> hq(bq);
-            for (uint32_t q = 0; q < bq; q++) {
-                hq[q] = fam_hash(q0 + q);
-                size_t at = (size_t)(hq[q] >> 17) & (cap - 1);
-                for (;;) {
-                    const uint32_t u = slot[at];
-                    if (u == 0xFFFFFFFFu) {
-                        slot[at] = (uint32_t)first.size();
-                        dag_of[q] = (uint32_t)first.size();
-                        first.push_back(q);
-                        break;
-                    }
-                    const uint32_t f = first[u];
-                    const uint64_t la = fam_off[q0 + q + 1] - fam_off[q0 + q], lb = fam_off[q0 + f + 1] - fam_off[q0 + f];
-                    if (hq[f] == hq[q] && la == lb && memcmp(fam_ids + fam_off[q0 + q], fam_ids + fam_off[q0 + f], 4 * la) == 0) {
-                        dag_of[q] = u;
-                        break;
-                    }
-                    at = (at + 1) & (cap - 1);
-                }
-            }
-            n_dags = (uint32_t)first.size();
-            if (n_dags < bq) {  // the distinct families, packed for the build
-                ufam_off.assign((size_t)n_dags + 1, 0);
-                for (uint32_t u = 0; u < n_dags; u++)
-                    ufam_off[u + 1] = ufam_off[u] + (fam_off[q0 + first[u] + 1] - fam_off[q0 + first[u]]);
-                ufam_ids.resize(ufam_off[n_dags]);
-                for (uint32_t u = 0; u < n_dags; u++)
-                    memcpy(ufam_ids.data() + ufam_off[u], fam_ids + fam_off[q0 + first[u]], 4 * (ufam_off[u + 1] - ufam_off[u]));
-                b_ids = ufam_ids.data();
-                b_off = ufam_off.data();
-                b_q0 = 0;
-            } else {
-                for (uint32_t q = 0; q < bq; q++) dag_of[q] = q;
-            }
-        } else {
-            for (uint32_t q = 0; q < bq; q++) dag_of[q] = q;
-        }
-        // (certified row skip of the DP kernel: the DAG build adds every node's bound on the gain still to come; a
-        // profile launch runs without it and without the scout)
-        PrunePlan pp;
-        if (!profile_batch)
-            pp = prune_plan(p, (float)(1.0 / (double)(p->fs_weight + 1) + (double)p->fs_weight), p->fs_weight >= 0.f ? 0.f : -1.f, maxL, false);
-        if (build(c, b_ids, b_off, b_q0, n_dags, p, pl.W, pp, &bg)) return 1;
-        {
-            std::lock_guard<std::mutex> slk(c->st->stats_mu);
-            c->st->stats.dags_built += n_dags;
-            c->st->stats.dags_used += bq;
-        }
-        // DP in sub-ranges that fit the trace-back budget
-        uint32_t r0 = 0;
-        while (r0 < bq) {
-            uint32_t r1 = r0;
-            uint64_t tbc = 0, sprows = 0, cells = 0;
-            uint32_t erec_cursor = 0;
-            std::vector<QDesc> qd;
-            while (r1 < bq) {
-                const uint32_t u = dag_of[r1];  // (this query's DAG among the chunk's distinct ones)
-                const uint32_t N = bg.sizes[kSz * u];
-                if (r1 > r0 && tbc + (uint64_t)N * Lp > tb_budget_cells) break;
-                QDesc d;
-                d.node_off = (uint64_t)u * bg.ncap;
-                d.edge_off = bg.pred_off[u];
-                d.q_off = qoff[q0 + r1] - qoff[q0 + r0];
-                d.tb_off = tbc;
-                d.spill_off = sprows;
-                d.N = N;
-                d.L = (uint32_t)(qoff[q0 + r1 + 1] - qoff[q0 + r1]);
-                d.n_spill = bg.sizes[kSz * u + 2];
-                d.first_sink = bg.sizes[kSz * u + 4];
-                d.gmin = bg.sizes[kSz * u + 5];
-                d.erec_off = erec_cursor;
-                erec_cursor += dp_edge_entries(N);
-                qd.push_back(d);
-                tbc += (uint64_t)N * Lp;
-                sprows += d.n_spill;
-                cells += (uint64_t)N * d.L;
-                r1++;
-            }
-            {
-                const uint32_t r1r = dp_round_range(r0, r1, bq, slots);
-                for (uint32_t r = r1r; r < r1; r++) {  // (the queries handed back to the next launch)
-                    tbc -= (uint64_t)qd[r - r0].N * Lp;
-                    sprows -= qd[r - r0].n_spill;
-                    cells -= (uint64_t)qd[r - r0].N * qd[r - r0].L;
-                }
-                qd.resize(r1r - r0);
-                r1 = r1r;
-            }
-            const uint32_t rq = r1 - r0;
-            const uint64_t qbase = qoff[q0 + r0], nqm = qoff[q0 + r1] - qbase;
-            if (c->qd.reserve(sizeof(QDesc) * rq) || c->qmask.reserve(std::max<uint64_t>(nqm, 1))) return 1;
-            if (upload(c, 5, c->qd.p, qd.data(), sizeof(QDesc) * rq, s) || upload(c, 6, c->qmask.p, qmask + qbase, nqm, s))
-                return 1;
-            c->profile_batch = profile_batch;  // (the DP reads the builder's prof16, the walk the entry point's self16)
-            c->out_pos_base = qbase - qoff[0];
-            if (run_dp_device(c, pl, qd.data(), rq, (uint64_t)n_dags * bg.ncap, tbc, sprows, cells, nqm, p, c->st->width,
-                              out + q0 + r0, out_pos ? out_pos + qbase : nullptr, false, pp, profile_batch ? 0u : bg.ncap,
-                              weight_set ? weight_set + q0 + r0 : nullptr))
-                return 1;
-            r0 = r1;
-        }
-    }
-    return 0;
-}
-
-}  // namespace sina_hip
-
 extern "C" {
 
 int sina_hip_align_families(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t nq,
                             const uint8_t *qmask, const uint64_t *qoff, const sina_hip_align_params *p,
                             sina_hip_align_out *out, uint32_t *out_pos) {
-    return align_family_batches(c, "align_families", build_graphs_for_launch, false, fam_ids, fam_off, nq, qmask, qoff, p, out, out_pos);
+    return align_family_batches(c, FamilyCall{"align_families", build_graphs_for_launch, false, fam_ids, fam_off, nq, qmask, qoff, p, out, out_pos});
 }
 
 int sina_hip_align_families_wsets(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t nq,
                                   const uint8_t *qmask, const uint64_t *qoff, const sina_hip_align_params *p,
                                   const uint32_t *weight_set, uint32_t n_sets, sina_hip_align_out *out, uint32_t *out_pos) {
-    if (p && !(p->weights != nullptr && p->n_weights > 0)) SH_FAIL("align_families_wsets: weight sets need positional weights (p->weights, p->n_weights)");
-    return align_family_batches(c, "align_families_wsets", build_graphs_for_launch, false, fam_ids, fam_off, nq, qmask, qoff, p, out,
-                                out_pos, weight_set, n_sets);
+    if (p && !weighted_scheme(p)) SH_FAIL("align_families_wsets: weight sets need positional weights (p->weights, p->n_weights)");
+    return align_family_batches(c, FamilyCall{"align_families_wsets", build_graphs_for_launch, false, fam_ids, fam_off, nq, qmask, qoff, p,
+                                             out, out_pos, weight_set, n_sets});
 }
 
 #ifdef SINA_DP_PROFILE
@@ -1096,9 +918,9 @@ int sina_hip_debug_family_graph(sina_hip_ctx *c, const uint32_t *fam_ids, uint32
     BuiltGraphs bg;
     // (with the row-skip bound for the default scoring: sina_hip_debug_rgain reads it back)
     if (build_family_graphs(c, fam_ids, foff, 0, 1, fs_weight, (int)ring_depth, &bg, true, fs_weight >= 0.f ? 64.0f * 1.0001f * 2.0f : 0.f)) return 1;
-    const uint32_t N = bg.sizes[0];
+    const uint32_t N = bg.sizes[kBuiltN];
     std::vector<uint4> rec(N);
-    std::vector<uint32_t> pr(bg.sizes[1] + 8);
+    std::vector<uint32_t> pr(bg.sizes[kBuiltEdges] + 8);
     SH_CHECK(hipMemcpy(rec.data(), c->rec.p, sizeof(uint4) * N, hipMemcpyDeviceToHost));
     SH_CHECK(hipMemcpy(pr.data(), c->pred.p, 4 * pr.size(), hipMemcpyDeviceToHost));
     uint32_t E = 0;

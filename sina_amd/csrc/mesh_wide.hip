@@ -376,7 +376,7 @@ int run_wide(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmas
              uint32_t *dbg_vm, uint32_t *dbg_vs, float *dbg_value) {
     if (n == 0) return 0;
     hipStream_t s = c->stream;
-    const bool weighted = p->weights != nullptr && p->n_weights > 0;
+    const bool weighted = weighted_scheme(p);
     const bool forbid = p->insertion == SINA_INSERTION_FORBID;
     const bool profile = g->node_score16 != nullptr;
     const int n_planes = forbid ? kWidePlanesForbid : kWidePlanes;
@@ -389,7 +389,7 @@ int run_wide(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmas
     }
     auto cells_of = [&](uint32_t q) -> uint64_t {
         const uint64_t N = g->node_off[q + 1] - g->node_off[q], L = qoff[q + 1] - qoff[q];
-        return (N + L - 1) * std::min(N, L);  // (below 2^63: classify_any, api.hip)
+        return (N + L - 1) * std::min(N, L);  // (below 2^63: classify_any, dp_plan.h)
     };
     std::vector<uint32_t> snk;
     std::vector<uint8_t> has_succ;

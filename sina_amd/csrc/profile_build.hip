@@ -16,7 +16,7 @@
 // How it maps to the hardware: one workgroup per distinct ordered family, like the DAG build (graph_build.hip).
 //   1. occupied-column bitmap in LDS (atomicOr per base; bit 0 is set whatever the family says), prefix popcount ->
 //      the node of every alignment column -- the DAG build's steps 1 and 2;
-//   2. columns, row records, predecessor entries of the chain: what prep_range() (api.hip) makes of the host-built
+//   2. columns, row records, predecessor entries of the chain: what prep_range() (dp_plan.h) makes of the host-built
 //      chain -- every finished row is handed to the next one in registers, no spill rows;
 //   3. per tile of nodes (all of them for a 16S family): one thread per BASE of the family.  Its points go to its
 //      node's counters; the absent stretch behind it -- the nodes up to its member's next base -- opens at the first
@@ -79,7 +79,7 @@ struct ProfileArgs {
     uint32_t *succ_min;       // [n][ncap]
     uint32_t *pred;           // [n][pred_stride]
     float *prof16;            // [n][ncap][16]
-    uint32_t *sizes;          // [n][kBuiltWords]: N, edges, 0, status (0 ok, 2: more than ncap or 65535 nodes), first sink row, 0
+    uint32_t *sizes;          // [n][kBuiltWords]: N, edges, 0, status (0 or kBuiltNodeCap: more than ncap or 65535 nodes), first sink row, 0
     uint32_t width, ncap, pred_stride;
     uint32_t tile_nodes;      // nodes per LDS tile
     uint32_t bitmap_off;      // LDS offset of the occupied-column bitmap (behind the three counter arrays)
@@ -173,10 +173,10 @@ __global__ void __launch_bounds__(kPT) family_profile_kernel(ProfileArgs a) {
     const uint32_t N = s_tmp[kPT / 64];
     if (N > a.ncap || N > 65535u) {  // (nothing has been written: the host grows the arrays and comes again, or gives up)
         if (tid == 0) {
-            sz[0] = N;
-            sz[1] = sz[2] = 0;
-            sz[3] = 2;
-            sz[4] = sz[5] = 0;
+            sz[kBuiltN] = N;
+            sz[kBuiltEdges] = sz[kBuiltSpill] = 0;
+            sz[kBuiltStatus] = kBuiltNodeCap;
+            sz[kBuiltFirstSink] = sz[kBuiltGmin] = 0;
         }
         return;
     }
@@ -211,12 +211,12 @@ __global__ void __launch_bounds__(kPT) family_profile_kernel(ProfileArgs a) {
         }
         if (tid == 0) {
             smin[N - 1] = 1000000u;  // "no successor" sentinel of mesh.h:480
-            sz[0] = N;
-            sz[1] = N - 1u;
-            sz[2] = 0;
-            sz[3] = 0;
-            sz[4] = N - 1u;
-            sz[5] = 0;
+            sz[kBuiltN] = N;
+            sz[kBuiltEdges] = N - 1u;
+            sz[kBuiltSpill] = 0;
+            sz[kBuiltStatus] = 0;
+            sz[kBuiltFirstSink] = N - 1u;
+            sz[kBuiltGmin] = 0;
         }
     }
 
@@ -452,8 +452,8 @@ int build_family_profiles(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64
         uint64_t nodes = 0;
         max_n = 1;
         for (uint32_t q = 0; q < n; q++) {
-            const uint32_t N = bg->sizes[kBuiltWords * q];
-            if (bg->sizes[kBuiltWords * q + 3] == 2) need_n = std::max(need_n, N);
+            const uint32_t N = bg->sizes[kBuiltWords * q + kBuiltN];
+            if (bg->sizes[kBuiltWords * q + kBuiltStatus] == kBuiltNodeCap) need_n = std::max(need_n, N);
             else nodes += N;
             max_n = std::max(max_n, N);
         }
@@ -491,7 +491,7 @@ extern "C" {
 int sina_hip_align_profiles(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t nq,
                             const uint8_t *qmask, const uint64_t *qoff, const sina_hip_align_params *p,
                             sina_hip_align_out *out, uint32_t *out_pos) {
-    return align_family_batches(c, "align_profiles", build_family_profiles, true, fam_ids, fam_off, nq, qmask, qoff, p, out, out_pos);
+    return align_family_batches(c, FamilyCall{"align_profiles", build_family_profiles, true, fam_ids, fam_off, nq, qmask, qoff, p, out, out_pos});
 }
 
 int sina_hip_debug_family_profile(sina_hip_ctx *c, const uint32_t *fam_ids, uint32_t F, float match, float mismatch,
@@ -512,7 +512,7 @@ int sina_hip_debug_family_profile(sina_hip_ctx *c, const uint32_t *fam_ids, uint
     const uint64_t foff[2] = {0, F};
     BuiltGraphs bg;
     if (build_family_profiles(c, fam_ids, foff, 0, 1, &p, 0, PrunePlan(), &bg)) return 1;
-    const uint32_t N = bg.sizes[0];
+    const uint32_t N = bg.sizes[kBuiltN];
     *n_nodes = N;
     if (N > cap_nodes) SH_FAIL("debug_family_profile: output buffers too small");
     SH_CHECK(hipMemcpy(pos, c->node_pos.p, 4 * (size_t)N, hipMemcpyDeviceToHost));

@@ -257,3 +257,73 @@ def test_malformed_graphs_are_rejected(oracle, gpu_ctx):
                 pred_off=poff, pred=np.array(pred, np.uint32), succ_minpos=np.arange(1, n + 1, dtype=np.uint32))
     with pytest.raises(capi.SinaHipError):
         gpu_ctx.align_graphs(gpu_ctx.graph_batch([wide], 400), q, qoff, gpu_ctx.params())
+
+
+def test_calls_on_one_context_do_not_depend_on_the_call_before(oracle, monkeypatch):
+    """Five different alignment calls in a row on ONE context -- profiles, families, the debug planes without the row
+    skip, caller-built DAGs with the columns left in the staging buffer, families with weight sets -- each give, byte
+    for byte, what the same call gives on a fresh context; and the row skip that debug_mesh(prune=0) switched off for
+    its own launch is on again in the next one.  (geom=128,4: a 300-base query takes two strips, the row skip runs.)"""
+    import ctypes as C
+    util.set_knobs(monkeypatch, geom="128,4")
+    refs = synth.make_refs(10, length=300, width=2000, seed=361)
+    cs = util.cseqs_from_refs(refs)
+    rng = np.random.default_rng(362)
+    lens = (300, 150, 211, 260)
+    masks = []
+    for i, L in enumerate(lens):
+        m = np.resize((refs.seq(i) >> 24) & 0x0f, L).astype(np.uint8)
+        m[m == 0] = 1
+        mut = rng.random(L) < 0.05
+        m[mut] = rng.choice([1, 2, 4, 8], size=int(mut.sum()))
+        masks.append(m)
+    flat = np.concatenate(masks)
+    qoff = np.zeros(len(lens) + 1, np.uint64)
+    qoff[1:] = np.cumsum(lens)
+    fams = [np.array(f, np.uint32) for f in ((0, 3, 5, 7), (1, 2, 8), (0, 3, 5, 7), (9, 4, 6, 2, 1))]   # (two share a DAG)
+    fam_ids = np.concatenate(fams)
+    foff = np.zeros(len(fams) + 1, np.uint64)
+    foff[1:] = np.cumsum([len(f) for f in fams])
+    graphs = [util.graph_dict([cs[int(i)] for i in f]) for f in fams]
+    wsets = rng.uniform(0.2, 2.0, size=(2, refs.width + max(lens) + 8)).astype(np.float32)
+
+    def staged_align_graphs(ctx):   # out_pos == NULL: the columns stay in the context's staging buffer
+        gb = ctx.graph_batch(graphs, refs.width)
+        out = np.zeros(gb.nq, capi.ALIGN_OUT_DTYPE)
+        p = ctx.params()
+        ctx._check(ctx.L.sina_hip_align_graphs(ctx.h, C.byref(gb), capi._ptr(flat, capi.u8p), capi._ptr(qoff, capi.u64p),
+                                               C.byref(p), out.ctypes.data_as(C.POINTER(capi.AlignOut)), None))
+        staged = np.ctypeslib.as_array(ctx.L.sina_hip_staged_out_pos(ctx.h), shape=(len(flat),))
+        return out, staged.copy()
+
+    steps = [
+        lambda ctx: ctx.align_profiles(fam_ids, foff, flat, qoff, ctx.params()),
+        lambda ctx: ctx.align_families(fam_ids, foff, flat, qoff, ctx.params()),
+        lambda ctx: ctx.debug_mesh(ctx.graph_batch(graphs[:1], refs.width), masks[0], ctx.params(), prune=False),
+        staged_align_graphs,
+        lambda ctx: ctx.align_families_wsets(fam_ids, foff, flat, qoff, ctx.params_wsets(wsets), np.array([1, 0, 0, 1], np.uint32), 2),
+    ]
+
+    def fresh():
+        ctx = capi.Context(0)
+        ctx.upload_refs(refs.ab, refs.off, refs.width)
+        return ctx
+
+    one = fresh()
+    try:
+        for i, step in enumerate(steps):
+            got = step(one)
+            if i == 3:
+                assert one.dp_info(0)["attempts"] >= 1    # the two-strip query: swept with the row skip
+            other = fresh()
+            try:
+                want = step(other)
+            finally:
+                other.close()
+            assert len(got) == len(want)
+            for g, w in zip(got, want):
+                assert np.asarray(g).tobytes() == np.asarray(w).tobytes(), "step %d" % (i + 1)
+            if i != 2:
+                assert (got[0]["status"] == 0).all()
+    finally:
+        one.close()

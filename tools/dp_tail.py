@@ -29,7 +29,7 @@ info = [ctx.dp_info(q) for q in range(nq)]
 # DAG rows of a family = its distinct (column, character) words; the launch order is by rows x length, largest first
 N = np.array([len(np.unique(np.concatenate([refs.ab[int(refs.off[r]):int(refs.off[r + 1])] for r in f]))) for f in fam], np.float64)
 L = np.diff(qs.off).astype(np.float64)
-order = np.array(sorted(range(nq), key=lambda q: -(N[q] * L[q])), dtype=np.int64)  # (stable, like api.hip's)
+order = np.array(sorted(range(nq), key=lambda q: -(N[q] * L[q])), dtype=np.int64)  # (stable, like dp_launch.hip's)
 sp = (ctypes.c_ulonglong * (2 * nq))()
 if not hasattr(lib, "sina_hip_debug_dp_spans") or lib.sina_hip_debug_dp_spans(sp, nq) != 0:
     raise SystemExit("no spans: not the profiling build")
