@@ -84,7 +84,17 @@ int sina_hip_build_index(sina_hip_ctx *ctx, unsigned k, int nofast);
  * (kmer_search::impl::store, src/kmer_search.cpp:279-304). */
 int sina_hip_download_index(sina_hip_ctx *ctx, uint32_t *offsets, uint32_t *ids);
 
-/* Alternative to build_index: adopt a host-built CSR index. */
+/* Alternative to build_index: adopt a host-built CSR index.  The index is taken as it is -- nothing is
+ * checked against the references -- and the search kernels rely on this contract:
+ *   - offsets has 4^k + 1 entries, starts at 0, never decreases, and offsets[4^k] == n_postings;
+ *   - the ids of one list (offsets[v] .. offsets[v + 1] - 1) are strictly ascending: no duplicates -- a list is
+ *     read as a sorted set, its postings of one reference tile being a prefix of what is left of it;
+ *   - every id is below the number of uploaded references;
+ *   - with nofast == 0 only the lists of k-mers that start with A are ever read.
+ * Under it no score exceeds the query's number of windows (len - k) nor 32767, which the 16-bit counters and
+ * the select kernel's histogram need.  An index outside the contract gives undefined results and can make
+ * the count kernel write outside its counters: validate a foreign index on the host first
+ * (tests/kmer_cases.py check_csr is such a check). */
 int sina_hip_upload_index(sina_hip_ctx *ctx, unsigned k, int nofast, const uint32_t *offsets,
                           const uint32_t *ids, uint64_t n_postings);
 
