@@ -5,13 +5,12 @@
 #include <malloc.h>
 #include <sys/mman.h>
 #include <atomic>
-#include <condition_variable>
-#include <deque>
 #include <charconv>
 #include <chrono>
 #include <cstring>
 
 #include "stages.h"
+#include "flow.h"
 #include "id_order.h"
 
 #include <fstream>
@@ -211,6 +210,36 @@ void fill_query_tray(tray &t, uint32_t q, const uint8_t *qmask, const uint64_t *
     t.input_sequence->setDenseMasks(qmask + qoff[q], n_bases);
     host_tick("build: bases", tk);
 }
+
+// ---- what the staged drivers below share (the runner itself: flow.h)
+// what a queue does with a batch nobody will take any more
+void destroy_trays(std::vector<tray> &trays) {
+    for (auto &t : trays) t.destroy();
+}
+// f(), its wall time added to ns
+template <class F>
+void timed(std::atomic<uint64_t> &ns, F &&f) {
+    const auto a = std::chrono::steady_clock::now();
+    f();
+    ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - a).count();
+}
+// The device contexts that n_find famfinder threads and n_align aligner (+ search) threads will lease, made and
+// warmed before any of them starts.  search_store(): the search stage's store, or null without that stage.
+template <class SearchStore>
+void reserve_workers(SearchStore &&search_store, unsigned n_find, unsigned n_align) {
+    try {
+        const auto store = reference_store::get(aligner::opts->database);
+        const std::shared_ptr<reference_store> sstore = search_store();
+        store->reserve_workers(reference_store::dev_search, n_find + (sstore == store ? n_align : 0));
+        store->reserve_workers(reference_store::dev_align, n_align);
+        if (sstore) {
+            if (sstore != store) sstore->reserve_workers(reference_store::dev_search, n_align);
+            sstore->reserve_workers(reference_store::dev_compare, n_align);
+        }
+    } catch (const std::exception &) {
+        // (a store that cannot be opened yet, or no room to warm: the stage that needs it will say so itself)
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -372,17 +401,17 @@ struct fasta_run {
 };
 }  // namespace
 
-int sina_host_run_fasta_serial(const char *in_path, const char *out_path, const char *log_path, int do_search,
-                               int show_dist, uint32_t batch, double *summary7) {
+// One run of either kind.  The stages are the same four; what differs is how they are driven (staged: a thread
+// each, so one batch is read while the one before it is searched and the one before that aligned; serial: batch
+// after batch on this thread) and the sink: the staged one renders and composes on the loop pool and keeps only
+// the hand-over serial, the serial one is SINA's node after node, which the tests compare the staged one with.
+static int run_fasta(const char *in_path, const char *out_path, const char *log_path, int do_search, int show_dist,
+                     uint32_t batch, double *summary7, bool staged) {
     try {
         fasta_run r(in_path, out_path, log_path, do_search, show_dist);
         if (batch == 0) batch = 1024;
-        std::vector<tray> trays;
-        while (r.read_batch(trays, batch)) {
-            r.n_read += (int)trays.size();
-            r.ff(trays);
-            r.al(trays);
-            if (r.sf) (*r.sf)(trays);
+        std::vector<log_printer::report> reports;
+        auto sink_serial = [&](std::vector<tray> &trays) {
             for (auto &t : trays) {  // serial, in input order (Log::printer and the writer are serial nodes)
                 if (t.aligned_sequence) r.n_aligned++;
                 t = (*r.lp)(t, r.log());
@@ -390,7 +419,37 @@ int sina_host_run_fasta_serial(const char *in_path, const char *out_path, const 
                 t.destroy();
                 r.devnull.str("");
             }
-        }
+        };
+        auto sink_staged = [&](std::vector<tray> &trays) {
+            reports.resize(trays.size());
+            parallel_for(trays.size(), [&](size_t i) { r.lp->render(trays[i], reports[i]); });
+            r.wr->precompose(trays);  // (after render: the reports' attributes are part of the records' meta data)
+            for (size_t i = 0; i < trays.size(); i++) {
+                tray &t = trays[i];
+                if (t.aligned_sequence) r.n_aligned++;
+                r.lp->commit(reports[i], r.log());
+                t = (*r.wr)(t);
+                r.devnull.str("");
+            }
+            parallel_for(trays.size(), [&](size_t i) { trays[i].destroy(); });
+        };
+        // one thread per node and FIFO queues: the batches stay in input order
+        flow::runner<std::vector<tray>> run(destroy_trays);
+        run.source("reader", 1, [&](std::vector<tray> &trays) {
+               if (!r.read_batch(trays, batch)) return false;
+               r.n_read += (int)trays.size();
+               return true;
+           })
+            .then(2, "famfinder", 1, [&](std::vector<tray> &trays) { r.ff(trays); })
+            .then(2, "aligner", 1, [&](std::vector<tray> &trays) {
+                r.al(trays);
+                if (r.sf) (*r.sf)(trays);
+            });
+        if (staged) {
+            tune_allocator();
+            reserve_workers([&] { return do_search ? reference_store::get(search_filter_database()) : nullptr; }, 1, 1);
+            run.then(2, "sink", 1, sink_staged).staged();
+        } else run.then(2, "sink", 1, sink_serial).inline_();
         r.finish(summary7);
         return 0;
     } catch (const std::exception &e) {
@@ -398,132 +457,13 @@ int sina_host_run_fasta_serial(const char *in_path, const char *out_path, const 
     }
 }
 
+int sina_host_run_fasta_serial(const char *in_path, const char *out_path, const char *log_path, int do_search,
+                               int show_dist, uint32_t batch, double *summary7) {
+    return run_fasta(in_path, out_path, log_path, do_search, show_dist, batch, summary7, false);
+}
 int sina_host_run_fasta(const char *in_path, const char *out_path, const char *log_path, int do_search,
                         int show_dist, uint32_t batch, double *summary7) {
-    try {
-        fasta_run r(in_path, out_path, log_path, do_search, show_dist);
-        if (batch == 0) batch = 1024;
-        tune_allocator();
-        try {  // the contexts the node threads below will lease, made and warmed before any of them starts
-            const auto store = reference_store::get(aligner::opts->database);
-            const auto sstore = do_search ? reference_store::get(search_filter_database()) : nullptr;
-            store->reserve_workers(reference_store::dev_search, 1 + (sstore == store ? 1 : 0));
-            store->reserve_workers(reference_store::dev_align, 1);
-            if (sstore) {
-                if (sstore != store) sstore->reserve_workers(reference_store::dev_search, 1);
-                sstore->reserve_workers(reference_store::dev_compare, 1);
-            }
-        } catch (const std::exception &) {
-            // (a store that cannot be opened yet is reported by the stage that needs it)
-        }
-        // bounded hand-over between the nodes; batches stay in input order (one thread per node: FIFO)
-        struct chan {
-            std::mutex mu;
-            std::condition_variable cv;
-            std::deque<std::vector<tray>> q;
-            bool closed = false, abort = false;
-            void push(std::vector<tray> &&b) {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return q.size() < 2 || abort; });
-                if (abort) {
-                    for (auto &t : b) t.destroy();
-                    return;
-                }
-                q.push_back(std::move(b));
-                cv.notify_all();
-            }
-            bool pop(std::vector<tray> &b) {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return !q.empty() || closed || abort; });
-                if (abort || q.empty()) return false;
-                b = std::move(q.front());
-                q.pop_front();
-                cv.notify_all();
-                return true;
-            }
-            void close() {
-                std::lock_guard<std::mutex> lk(mu);
-                closed = true;
-                cv.notify_all();
-            }
-            void stop() {
-                std::lock_guard<std::mutex> lk(mu);
-                abort = true;
-                for (auto &b : q)
-                    for (auto &t : b) t.destroy();
-                q.clear();
-                cv.notify_all();
-            }
-        };
-        chan read_q, found_q, aligned_q;
-        std::exception_ptr err;
-        std::mutex err_mu;
-        auto on_error = [&] {
-            { std::lock_guard<std::mutex> lk(err_mu); if (!err) err = std::current_exception(); }
-            read_q.stop();
-            found_q.stop();
-            aligned_q.stop();
-        };
-        std::thread reader([&] {
-            try {
-                std::vector<tray> trays;
-                while (r.read_batch(trays, batch)) {
-                    r.n_read += (int)trays.size();
-                    read_q.push(std::move(trays));
-                    trays = std::vector<tray>();
-                }
-            } catch (...) { on_error(); }
-            read_q.close();
-        });
-        std::thread finder([&] {
-            try {
-                std::vector<tray> trays;
-                while (read_q.pop(trays)) {
-                    r.ff(trays);
-                    found_q.push(std::move(trays));
-                    trays = std::vector<tray>();
-                }
-            } catch (...) { on_error(); }
-            found_q.close();
-        });
-        std::thread align([&] {
-            try {
-                std::vector<tray> trays;
-                while (found_q.pop(trays)) {
-                    r.al(trays);
-                    if (r.sf) (*r.sf)(trays);
-                    aligned_q.push(std::move(trays));
-                    trays = std::vector<tray>();
-                }
-            } catch (...) { on_error(); }
-            aligned_q.close();
-        });
-        try {  // the sink: this thread
-            std::vector<tray> trays;
-            std::vector<log_printer::report> reports;
-            while (aligned_q.pop(trays)) {
-                reports.resize(trays.size());
-                parallel_for(trays.size(), [&](size_t i) { r.lp->render(trays[i], reports[i]); });
-                r.wr->precompose(trays);  // (after render: the reports' attributes are part of the records' meta data)
-                for (size_t i = 0; i < trays.size(); i++) {
-                    tray &t = trays[i];
-                    if (t.aligned_sequence) r.n_aligned++;
-                    r.lp->commit(reports[i], r.log());
-                    t = (*r.wr)(t);
-                    r.devnull.str("");
-                }
-                parallel_for(trays.size(), [&](size_t i) { trays[i].destroy(); });
-            }
-        } catch (...) { on_error(); }
-        reader.join();
-        finder.join();
-        align.join();
-        if (err) std::rethrow_exception(err);
-        r.finish(summary7);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    return run_fasta(in_path, out_path, log_path, do_search, show_dist, batch, summary7, true);
 }
 
 // FASTA reader + writer alone (no GPU): reads every sequence of in_path and writes it back, the
@@ -746,14 +686,18 @@ int sina_host_pipeline_run(void *pp, const uint8_t *qmask, const uint64_t *qoff,
         if (inflight == 0) inflight = 1;
         std::atomic<uint32_t> next{0};
         std::atomic<uint64_t> ff_ns{0}, al_ns{0}, sf_ns{0};
-        std::exception_ptr err;
-        std::mutex err_mu;
         const auto t0 = std::chrono::steady_clock::now();
         host_profile_mark("MARK:run-threads-start");
         // One batch travelling through the stages (what a tray is in SINA's TBB flow graph, times `batch`).
         struct item {
             uint32_t b0 = 0, b1 = 0;
             std::vector<tray> trays;
+        };
+        auto take = [&](item &it) -> bool {
+            it.b0 = next.fetch_add(batch);
+            if (it.b0 >= nq) return false;
+            it.b1 = std::min(nq, it.b0 + batch);
+            return true;
         };
         auto build_and_find = [&](item &it) {  // source + famfinder node
             it.trays = p->take_trays();
@@ -764,177 +708,49 @@ int sina_host_pipeline_run(void *pp, const uint8_t *qmask, const uint64_t *qoff,
                     fill_query_tray(it.trays[i], it.b0 + (uint32_t)i, qmask, qoff);
                 });
             }
-            const auto a = std::chrono::steady_clock::now();
-            p->ff(it.trays);
-            ff_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - a)
-                         .count();
+            timed(ff_ns, [&] { p->ff(it.trays); });
         };
         auto align_and_search = [&](item &it) {  // aligner node (+ search node)
-            const auto b = std::chrono::steady_clock::now();
-            p->al(it.trays);
-            const auto c = std::chrono::steady_clock::now();
-            al_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(c - b).count();
-            if (p->sf) {
-                (*p->sf)(it.trays);
-                sf_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
-                             std::chrono::steady_clock::now() - c)
-                             .count();
-            }
+            timed(al_ns, [&] { p->al(it.trays); });
+            if (p->sf) timed(sf_ns, [&] { (*p->sf)(it.trays); });
         };
         auto extract = [&](item &it) {  // sink
-            host_phase hp("drv.extract");
-            const uint32_t b0 = it.b0;
-            std::vector<tray> &trays = it.trays;
-            pipeline::result_chunk &chunk = p->chunks[b0 / batch];
-            chunk.results.resize(it.b1 - it.b0);
-            chunk.run = p->run_no;
-            parallel_for(it.b1 - it.b0, [&](size_t i) {  // (what SINA's writer stage does per sequence)
-                const uint32_t q = b0 + (uint32_t)i;
-                extract_tray(p, trays[i], chunk.results[i], (uint32_t)(qoff[q + 1] - qoff[q]));
-            });
-        };
-        auto take = [&](item &it) -> bool {
-            it.b0 = next.fetch_add(batch);
-            if (it.b0 >= nq) return false;
-            it.b1 = std::min(nq, it.b0 + batch);
-            return true;
-        };
-        auto guarded = [&](auto &&body) {
-            try {
-                body();
-            } catch (...) {
-                std::lock_guard<std::mutex> lk(err_mu);
-                if (!err) err = std::current_exception();
+            {
+                host_phase hp("drv.extract");
+                pipeline::result_chunk &chunk = p->chunks[it.b0 / batch];
+                chunk.results.resize(it.b1 - it.b0);
+                chunk.run = p->run_no;
+                parallel_for(it.b1 - it.b0, [&](size_t i) {  // (what SINA's writer stage does per sequence)
+                    const uint32_t q = it.b0 + (uint32_t)i;
+                    extract_tray(p, it.trays[i], chunk.results[i], (uint32_t)(qoff[q + 1] - qoff[q]));
+                });
             }
+            p->give_trays(std::move(it.trays));
         };
-        if (inflight == 1) {
-            // one batch at a time, stage after stage (kernel timings taken this way are undisturbed)
-            guarded([&] {
-                item it;
-                while (take(it)) {
-                    build_and_find(it);
-                    align_and_search(it);
-                    extract(it);
-                    p->give_trays(std::move(it.trays));
-                }
-            });
-        } else {
-            // The stages as nodes with their own threads and bounded hand-over queues, as SINA wires them
-            // (src/sina.cpp:452-586: source -> famfinder -> aligner -> search -> sink).  `inflight`
-            // aligner threads keep the GPU's DP slot busy (graph build of one batch beside the DP of
-            // another); the famfinder threads run ahead by at most two finished batches, so an aligner
-            // thread never waits for a k-mer search to start.
-            struct handover {
-                std::mutex mu;
-                std::condition_variable cv;
-                std::deque<item> q;
-                size_t cap = 2;
-                int producers = 0;
-                bool abort = false;
-                void push(item &&it) {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return q.size() < cap || abort; });
-                    if (abort) {
-                        for (auto &t : it.trays) t.destroy();
-                        return;
-                    }
-                    q.push_back(std::move(it));
-                    cv.notify_all();
-                }
-                bool pop(item &it) {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return !q.empty() || producers == 0 || abort; });
-                    if (q.empty()) return false;
-                    it = std::move(q.front());
-                    q.pop_front();
-                    cv.notify_all();
-                    return true;
-                }
-                void producer_done() {
-                    std::lock_guard<std::mutex> lk(mu);
-                    if (--producers == 0) cv.notify_all();
-                }
-                void stop() {
-                    std::lock_guard<std::mutex> lk(mu);
-                    abort = true;
-                    for (auto &it : q)
-                        for (auto &t : it.trays) t.destroy();
-                    q.clear();
-                    cv.notify_all();
-                }
-            };
-            handover found, aligned;
-            // (famfinder threads; they run ahead by `found.cap` finished batches)
-            const uint32_t n_find = inflight >= 4 ? 3 : (inflight >= 3 ? 2 : 1);
-            const uint32_t n_align = inflight, n_sink = 1;
-            try {  // the contexts the threads below will lease, made and warmed before any of them starts
-                const auto store = reference_store::get(aligner::opts->database);
-                store->reserve_workers(reference_store::dev_search, n_find + (p->sf && p->search_store == store ? n_align : 0));
-                store->reserve_workers(reference_store::dev_align, n_align);
-                if (p->sf && p->search_store) {
-                    if (p->search_store != store) p->search_store->reserve_workers(reference_store::dev_search, n_align);
-                    p->search_store->reserve_workers(reference_store::dev_compare, n_align);
-                }
-            } catch (const std::exception &) {
-                // (no store registered under the aligner's name, or no room to warm: the stages will say so themselves)
+        // The stages as nodes with their own threads and bounded hand-over queues, as SINA wires them
+        // (src/sina.cpp:452-586: source -> famfinder -> aligner -> search -> sink).  `inflight` aligner threads
+        // keep the GPU's DP slot busy (graph build of one batch beside the DP of another); the famfinder threads
+        // run ahead by at most `n_find` finished batches, so an aligner thread never waits for a k-mer search to
+        // start.  inflight == 1: one batch at a time, stage after stage on this thread (kernel timings taken this
+        // way are undisturbed).
+        const uint32_t n_find = inflight >= 4 ? 3 : (inflight >= 3 ? 2 : 1), n_align = inflight;
+        flow::runner<item> run([](item &it) { destroy_trays(it.trays); });
+        run.source("finder", n_find, [&](item &it) {
+               if (!take(it)) return false;
+               build_and_find(it);
+               return true;
+           }, [] { host_profile_thread_exit("thread: finder (whole run)"); })
+            .then(n_find, "aligner", n_align, align_and_search, [] { host_profile_thread_exit("thread: aligner (whole run)"); })
+            .then(2, "sink", 1, extract, [] { host_profile_thread_exit("thread: sink (whole run)"); });
+        std::exception_ptr err;
+        try {
+            if (inflight == 1) run.inline_();
+            else {
+                reserve_workers([&] { return p->sf ? p->search_store : nullptr; }, n_find, n_align);
+                run.staged();
             }
-            found.cap = n_find;
-            found.producers = (int)n_find;
-            aligned.producers = (int)n_align;
-            auto on_error = [&] {
-                found.stop();
-                aligned.stop();
-                next.store(nq);
-            };
-            std::vector<std::thread> th;
-            for (uint32_t i = 0; i < n_find; i++)
-                th.emplace_back([&] {
-                    struct cpu_report { ~cpu_report() { host_profile_thread_exit("thread: finder (whole run)"); } } rep;
-                    try {
-                        item it;
-                        while (take(it)) {
-                            build_and_find(it);
-                            found.push(std::move(it));
-                            it = item();
-                        }
-                    } catch (...) {
-                        { std::lock_guard<std::mutex> lk(err_mu); if (!err) err = std::current_exception(); }
-                        on_error();
-                    }
-                    found.producer_done();
-                });
-            for (uint32_t i = 0; i < n_align; i++)
-                th.emplace_back([&] {
-                    struct cpu_report { ~cpu_report() { host_profile_thread_exit("thread: aligner (whole run)"); } } rep;
-                    try {
-                        item it;
-                        while (found.pop(it)) {
-                            align_and_search(it);
-                            aligned.push(std::move(it));
-                            it = item();
-                        }
-                    } catch (...) {
-                        { std::lock_guard<std::mutex> lk(err_mu); if (!err) err = std::current_exception(); }
-                        on_error();
-                    }
-                    aligned.producer_done();
-                });
-            for (uint32_t i = 0; i < n_sink; i++)
-                th.emplace_back([&] {
-                    struct cpu_report { ~cpu_report() { host_profile_thread_exit("thread: sink (whole run)"); } } rep;
-                    try {
-                        item it;
-                        while (aligned.pop(it)) {
-                            extract(it);
-                            p->give_trays(std::move(it.trays));
-                            it = item();
-                        }
-                    } catch (...) {
-                        { std::lock_guard<std::mutex> lk(err_mu); if (!err) err = std::current_exception(); }
-                        on_error();
-                    }
-                });
-            for (auto &t : th) t.join();
+        } catch (...) {
+            err = std::current_exception();
         }
         p->wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         p->ff_s = ff_ns.load() * 1e-9;
