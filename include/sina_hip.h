@@ -148,6 +148,14 @@ int sina_hip_kmer_topk_any(sina_hip_ctx *ctx, const uint8_t *qmask, const uint64
 int sina_hip_kmer_scores_any(sina_hip_ctx *ctx, const uint8_t *qmask, uint32_t qlen, int16_t *scores);
 /* Queries the long count kernel has counted on this context since init / fork. */
 int sina_hip_long_queries(sina_hip_ctx *ctx, uint64_t *n);
+/* `max` of the two top-k calls is any number >= 1 (0 gives out_n = 0 everywhere).  With M = min(max, n_refs) up to
+ * 4096 a query's candidates are sorted in LDS; a larger M goes through the big select: the same cut score and tie
+ * rule (the ties at the cut with the LARGEST ids), the survivors sorted by one segmented radix sort per launch range,
+ * results bit for bit the same order (score desc, id desc), out_n = M.  Its launch ranges hold at most 1 GiB of keys
+ * and outputs (24 bytes per candidate), one query at least.
+ * sina_hip_big_select_queries: queries the big select has ranked on this context since init / fork -- a call with
+ * M <= 4096 leaves it alone. */
+int sina_hip_big_select_queries(sina_hip_ctx *ctx, uint64_t *n);
 
 /* ------------------------------------------------------------- search stage
  * Replaces the per-candidate cseq_comparator::operator() calls of search_filter::operator()

@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "sina_hip_align_profiles", "sina_hip_debug_family_profile",
     "sina_hip_debug_mesh", "sina_hip_debug_family_graph", "sina_hip_debug_dp_info", "sina_hip_debug_rgain", "sina_hip_debug_chain_rows", "sina_hip_get_stats",
     "sina_hip_align_graphs_any", "sina_hip_debug_mesh_wide", "sina_hip_wide_queries", "sina_hip_last_error_is_limit",
-    "sina_hip_kmer_topk_any", "sina_hip_kmer_scores_any", "sina_hip_long_queries",
+    "sina_hip_kmer_topk_any", "sina_hip_kmer_scores_any", "sina_hip_long_queries", "sina_hip_big_select_queries",
     "sina_hip_align_graphs_wsets", "sina_hip_align_families_wsets",
 ]
 
@@ -136,6 +136,7 @@ def load():
     L.sina_hip_kmer_topk_any.argtypes = L.sina_hip_kmer_topk.argtypes
     L.sina_hip_kmer_scores_any.argtypes = L.sina_hip_kmer_scores.argtypes
     L.sina_hip_long_queries.argtypes = [vp, u64p]
+    L.sina_hip_big_select_queries.argtypes = [vp, u64p]
     L.sina_hip_last_error_is_limit.restype = C.c_int
     L.sina_hip_debug_mesh_wide.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
                                            u32p, u32p, f32p]
@@ -270,6 +271,12 @@ class Context:
         """Queries the long k-mer count kernel has counted on this context so far."""
         n = C.c_uint64()
         self._check(self.L.sina_hip_long_queries(self.h, C.byref(n)))
+        return int(n.value)
+
+    def big_select_queries(self):
+        """Queries the big select (more than 4096 candidates per query) has ranked on this context so far."""
+        n = C.c_uint64()
+        self._check(self.L.sina_hip_big_select_queries(self.h, C.byref(n)))
         return int(n.value)
 
     # ---- alignment

@@ -119,6 +119,10 @@ struct sina_hip_ctx {
     sina_hip::DevBuf wide_in, wide_planes;
     uint64_t wide_queries = 0;        // queries the wide kernel has aligned on this context (sina_hip_wide_queries)
     uint64_t long_queries = 0;        // queries the long k-mer count kernel has counted on this context (sina_hip_long_queries)
+    uint64_t big_select_queries = 0;  // queries the big select has ranked on this context (sina_hip_big_select_queries)
+    // the big select (kmer.hip): a launch range's keys with their double buffer, and the segmented sort's temporary
+    // storage -- grow-only, allocated by the first search that wants more than 4096 candidates
+    sina_hip::DevBuf k_big_keys, k_big_tmp;
     sina_hip::DevBuf scout, scout_u;  // the scout pass (mesh_dp.hip): the DAG build's chain rows (u16 [DAGs][ncap]), and its result -- a bound U per query
     sina_hip::HostBuf h_res;          // pinned copy of a launch's DpResults (row-skip statistics, the next launch's guess)
     void *last_tb = nullptr;  // the plane of the last launch (debug read-back: sina_hip_debug_mesh)
@@ -190,6 +194,8 @@ struct sina_hip_ctx {
         dbg.release();
         wide_in.release();
         wide_planes.release();
+        k_big_keys.release();
+        k_big_tmp.release();
         h_out.release();
         h_out_pos.release();
         h_res.release();

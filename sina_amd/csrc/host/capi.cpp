@@ -332,6 +332,14 @@ int sina_host_store_slow_path_queries(const char *key, uint64_t *wide, uint64_t 
         return fail(e);
     }
 }
+int sina_host_store_big_select_queries(const char *key, uint64_t *n) {
+    try {
+        reference_store::get(key)->big_select_queries(n);
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
 int sina_host_store_build_index(const char *key, unsigned k, int nofast) {
     try {
         reference_store::get(key)->ensure_index(k, nofast != 0);

@@ -7,6 +7,7 @@
 #include <sys/resource.h>
 #include <immintrin.h>
 #include "id_order.h"
+#include "../kmer_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -591,6 +592,19 @@ void reference_store::slow_path_queries(uint64_t *wide, uint64_t *long_kmer) {
     for (auto &pool : idle_forks)
         for (sina_hip_ctx *c : pool) add(c);
 }
+void reference_store::big_select_queries(uint64_t *n) {
+    sina_hip_ctx *root = device();
+    std::lock_guard<std::mutex> lk(gpu_mu);
+    *n = 0;
+    auto add = [&](sina_hip_ctx *c) {
+        uint64_t b = 0;
+        hip_check(sina_hip_big_select_queries(c, &b), "sina_hip_big_select_queries");
+        *n += b;
+    };
+    add(root);
+    for (auto &pool : idle_forks)
+        for (sina_hip_ctx *c : pool) add(c);
+}
 reference_store::lease::~lease() {
     if (!c) return;
     std::lock_guard<std::mutex> lk(st->gpu_mu);
@@ -927,75 +941,67 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
     });
     auto dev = st.worker_device(reference_store::dev_search);
     sina_hip_ctx *ctx = dev.get();
-    if (max <= 4096) {
-        // repeated queries (same bases, same case: the packed mask bytes) are searched once
-        std::vector<uint32_t> rep;
-        const size_t nu = group_equal_items(
-            queries.size(),
-            [&](size_t i) { return hash_ends(qmask + qoff[i], qoff[i + 1] - qoff[i], qoff[i + 1] - qoff[i]); },
-            [&](size_t a, size_t b) {
-                return qoff[a + 1] - qoff[a] == qoff[b + 1] - qoff[b] &&
-                       memcmp(qmask + qoff[a], qmask + qoff[b], qoff[a + 1] - qoff[a]) == 0;
-            },
-            rep);
-        std::vector<uint32_t> slot_of(queries.size());
-        const uint8_t *dev_mask = qmask;
-        const uint64_t *dev_off = qoff.data();
-        std::vector<uint64_t> uoff;
-        thread_local batch_scratch<uint8_t> umask_buf;
-        if (nu == queries.size()) {
-            for (size_t i = 0; i < queries.size(); i++) slot_of[i] = (uint32_t)i;
-        } else {  // the distinct queries, packed again for the device
-            uoff.assign(nu + 1, 0);
-            std::vector<uint32_t> firsts;
-            firsts.reserve(nu);
-            for (size_t i = 0; i < queries.size(); i++) {
-                if (rep[i] == i) {
-                    slot_of[i] = (uint32_t)firsts.size();
-                    uoff[firsts.size() + 1] = uoff[firsts.size()] + (qoff[i + 1] - qoff[i]);
-                    firsts.push_back((uint32_t)i);
-                } else {
-                    slot_of[i] = slot_of[rep[i]];
-                }
+    // repeated queries (same bases, same case: the packed mask bytes) are searched once
+    std::vector<uint32_t> rep;
+    const size_t nu = group_equal_items(
+        queries.size(),
+        [&](size_t i) { return hash_ends(qmask + qoff[i], qoff[i + 1] - qoff[i], qoff[i + 1] - qoff[i]); },
+        [&](size_t a, size_t b) {
+            return qoff[a + 1] - qoff[a] == qoff[b + 1] - qoff[b] &&
+                   memcmp(qmask + qoff[a], qmask + qoff[b], qoff[a + 1] - qoff[a]) == 0;
+        },
+        rep);
+    std::vector<uint32_t> slot_of(queries.size());
+    const uint8_t *dev_mask = qmask;
+    const uint64_t *dev_off = qoff.data();
+    std::vector<uint64_t> uoff;
+    thread_local batch_scratch<uint8_t> umask_buf;
+    if (nu == queries.size()) {
+        for (size_t i = 0; i < queries.size(); i++) slot_of[i] = (uint32_t)i;
+    } else {  // the distinct queries, packed again for the device
+        uoff.assign(nu + 1, 0);
+        std::vector<uint32_t> firsts;
+        firsts.reserve(nu);
+        for (size_t i = 0; i < queries.size(); i++) {
+            if (rep[i] == i) {
+                slot_of[i] = (uint32_t)firsts.size();
+                uoff[firsts.size() + 1] = uoff[firsts.size()] + (qoff[i + 1] - qoff[i]);
+                firsts.push_back((uint32_t)i);
+            } else {
+                slot_of[i] = slot_of[rep[i]];
             }
-            uint8_t *const um = umask_buf.get(uoff.back() + 1);
-            parallel_for(nu, [&](size_t u) { memcpy(um + uoff[u], qmask + qoff[firsts[u]], uoff[u + 1] - uoff[u]); });
-            dev_mask = um;
-            dev_off = uoff.data();
         }
-        thread_local batch_scratch<uint32_t> ids_buf;
-        thread_local batch_scratch<float> sc_buf;
-        uint32_t *const ids = ids_buf.get(nu * max);
-        float *const sc = sc_buf.get(nu * max);
-        std::vector<uint32_t> cnt(nu);
+        uint8_t *const um = umask_buf.get(uoff.back() + 1);
+        parallel_for(nu, [&](size_t u) { memcpy(um + uoff[u], qmask + qoff[firsts[u]], uoff[u + 1] - uoff[u]); });
+        dev_mask = um;
+        dev_off = uoff.data();
+    }
+    // Up to 4096 candidates per query the distinct queries go to the device in one call, as ever.  More (famfinder
+    // widening its list tenfold per round, a large search-kmer-candidates): nu * max ids and scores are no longer one
+    // scratch block -- the distinct queries are taken in slices of as many as one launch range of the device's big
+    // select holds (kmer_plan.h: the same function, the same budget, so a slice is one launch), and `results` is filled
+    // slice by slice.
+    const size_t slice = max > sina_hip::kKmerSelMax ? sina_hip::big_select_range((uint32_t)nu, max, sina_hip::kBigSelBudget) : nu;
+    thread_local batch_scratch<uint32_t> ids_buf;
+    thread_local batch_scratch<float> sc_buf;
+    uint32_t *const ids = ids_buf.get(slice * max);
+    float *const sc = sc_buf.get(slice * max);
+    std::vector<uint32_t> cnt(slice);
+    for (size_t u0 = 0; u0 < nu; u0 += slice) {
+        const size_t u1 = std::min(nu, u0 + slice);
         {
             scoped_phase ph("ff.kmer_topk(C-ABI)");
             // (the _any entry: the class has no length limit of its own, as the reference's -- a query beyond the fast count
-            // kernel's goes to the long one, per query)
-            hip_check(sina_hip_kmer_topk_any(ctx, dev_mask, dev_off, (uint32_t)nu, max, ids, sc, cnt.data()), "kmer_topk");
+            // kernel's goes to the long one, per query; offsets are absolute, so a slice starts at dev_off + u0)
+            hip_check(sina_hip_kmer_topk_any(ctx, dev_mask, dev_off + u0, (uint32_t)(u1 - u0), max, ids, sc, cnt.data()), "kmer_topk");
         }
         parallel_for(queries.size(), [&](size_t i) {
             const size_t u = slot_of[i];
-            results[i].reserve(cnt[u]);
-            for (uint32_t x = 0; x < cnt[u]; x++)
-                results[i].emplace_back(sc[u * max + x], &st.getCseq(ids[u * max + x]));
+            if (u < u0 || u >= u1) return;
+            const size_t at = (u - u0) * max;
+            results[i].reserve(cnt[u - u0]);
+            for (uint32_t x = 0; x < cnt[u - u0]; x++) results[i].emplace_back(sc[at + x], &st.getCseq(ids[at + x]));
         });
-    } else {
-        // rare escalation (famfinder asks for >4096 candidates): the GPU still does the
-        // counting; ranking the full score vector is the reference's own partial_sort
-        // (src/kmer_search.cpp:405-418).
-        std::vector<int16_t> scores(n);
-        using pair = std::pair<int16_t, int>;
-        std::vector<pair> ranks(n);
-        for (size_t i = 0; i < queries.size(); i++) {
-            hip_check(sina_hip_kmer_scores_any(ctx, qmask + qoff[i], (uint32_t)(qoff[i + 1] - qoff[i]),
-                                               scores.data()),
-                      "kmer_scores");
-            for (unsigned r = 0; r < n; r++) ranks[r] = pair(scores[r], (int)r);
-            std::partial_sort(ranks.begin(), ranks.begin() + max, ranks.end(), std::greater<pair>());
-            results[i].reserve(max);
-            for (unsigned x = 0; x < max; x++) results[i].emplace_back(ranks[x].first, &st.getCseq(ranks[x].second));
-        }
     }
 }
 

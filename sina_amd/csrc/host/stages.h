@@ -308,6 +308,8 @@ public:
     // queries the wide DP kernel / the long k-mer count kernel have taken on this store's contexts (the root and the
     // idle forks: call it between runs) -- sina_hip_wide_queries, sina_hip_long_queries
     void slow_path_queries(uint64_t *wide, uint64_t *long_kmer);
+    // ... and queries the k-mer search's big select (more than 4096 candidates) has ranked -- sina_hip_big_select_queries
+    void big_select_queries(uint64_t *n);
 
 private:
     reference_store() = default;

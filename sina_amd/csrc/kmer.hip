@@ -20,10 +20,15 @@
 //   select: one workgroup per query: the cut score by an 8-way search on "how many scores are >= t"
 //           (reductions over 16-byte loads; an LDS histogram serialises on the few low bins every
 //           lane hits) -> ordered compaction (ties keep the LARGEST ids) -> bitonic sort of the
-//           <= 4096 survivors.
+//           <= 4096 survivors.  More than 4096 wanted: the same cut search and ordered compaction leave the survivors
+//           as 64-bit keys in a per-query segment in HBM, one segmented radix sort orders every segment of the
+//           launch range, a small kernel unpacks the keys (kmer_select_big_kernel).
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -31,6 +36,7 @@
 
 #include "common.h"
 #include "ctx.h"
+#include "kmer_plan.h"
 
 namespace sina_hip {
 namespace {
@@ -49,7 +55,7 @@ constexpr int kLongQbExtra = 64;
 static_assert(kLongChunk <= kMaxQueryLen && kMaxLongQueryLen <= 32767, "a chunk fits the fast kernel's lists; int16 scores");
 static_assert((size_t)kTileRefs * 2 + (size_t)kMaxQueryLen * 9 + 64 + kLongQbExtra <= 160 * 1024, "LDS of the long count kernel");
 constexpr int kSelThreads = 256;
-constexpr int kSelMax = 4096;               // candidates sortable in LDS
+constexpr int kSelMax = (int)kKmerSelMax;      // candidates sortable in LDS
 
 __device__ __forceinline__ bool ambig(uint32_t m) { return __popc(m & 0xfu) > 1; }
 
@@ -403,6 +409,7 @@ struct SelectArgs {
     float *out_scores;
     uint32_t *out_n;
     uint32_t n_refs, stride, max;
+    unsigned long long *keys;  // kmer_select_big_kernel: [nq][max] survivors, unordered
 };
 
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum, uint32_t *total) {
@@ -432,8 +439,11 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum, 
 // L2 (200 KB for 100k references), no atomics on a histogram whose low bins every lane hits --
 // then one ordered pass emits everything above the cut plus the ties with the LARGEST ids.
 // (kTopMax: the largest score a row can hold -- the fast count kernel's query length, or the long one's)
-template <int kTopMax>
-__global__ void __launch_bounds__(kSelThreads) kmer_select_kernel(SelectArgs a) {
+// BIG (kmer_select_big_kernel, M > kSelMax): the same cut, the same ordered pass -- the survivors, exactly M of them,
+// go to the query's segment of a.keys instead of cand[] (which only serves the short cut's histogram then), a wave
+// taking one run of slots per 64 vectors; sorting and unpacking are left to the launches behind the kernel.
+template <int kTopMax, bool BIG>
+__device__ __forceinline__ void kmer_select_body(const SelectArgs &a) {
     __shared__ unsigned long long cand[kSelMax];
     __shared__ uint32_t wsum[kSelThreads / 64];
     __shared__ uint32_t sh_slot;
@@ -596,7 +606,7 @@ __global__ void __launch_bounds__(kSelThreads) kmer_select_kernel(SelectArgs a) 
     // Few enough scores at or above the cut to sort them all: take every one of them -- the sort below
     // orders by (score, id) descending, so the first M are the ones above the cut plus the ties with
     // the LARGEST ids -- in one unordered pass.
-    const bool take_all = n_ge_cut != 0 && n_ge_cut <= (uint32_t)kSelMax;
+    const bool take_all = !BIG && n_ge_cut != 0 && n_ge_cut <= (uint32_t)kSelMax;
     if (take_all) {
         __syncthreads();
         if (tid == 0) sh_slot = 0;
@@ -642,6 +652,37 @@ __global__ void __launch_bounds__(kSelThreads) kmer_select_kernel(SelectArgs a) 
         }
         uint32_t eq_rank = run + incl - c;
         run += __shfl(incl, 63);
+        if constexpr (BIG) {
+            // how many this lane's vector gives -> its run of slots in the segment: one atomic per wave and iteration
+            uint32_t mine = 0, er = eq_rank;
+            if (i < w1)
+                for8(i, [&](int v, uint32_t) {
+                    bool take = v > cut;
+                    if (v == cut) take = er++ >= skip_eq;
+                    mine += take ? 1u : 0u;
+                });
+            uint32_t tin = mine;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t y = __shfl_up(tin, off);
+                if (lane >= off) tin += y;
+            }
+            const uint32_t wave_n = __shfl(tin, 63);
+            uint32_t base = 0;
+            if (lane == 0 && wave_n) base = atomicAdd(&sh_slot, wave_n);
+            uint32_t slot = __shfl(base, 0) + tin - mine;
+            unsigned long long *seg = a.keys + (size_t)q * M;
+            if (i < w1 && mine)
+                for8(i, [&](int v, uint32_t id) {
+                    bool take = v > cut;
+                    if (v == cut) take = eq_rank++ >= skip_eq;
+                    if (take) {
+                        if (slot < M) seg[slot] = ((unsigned long long)(uint32_t)(v + 32768) << 32) | id;
+                        slot++;
+                    }
+                });
+            continue;
+        }
         if (i < w1)
             for8(i, [&](int v, uint32_t id) {
                 bool take = v > cut;
@@ -657,6 +698,7 @@ __global__ void __launch_bounds__(kSelThreads) kmer_select_kernel(SelectArgs a) 
             });
     }
     }
+    if constexpr (BIG) return;  // (sorted and unpacked behind the kernel; the unpack kernel writes out_n)
     __syncthreads();
     const uint32_t out_base = sh_slot;
     const uint32_t n = min(out_base, (uint32_t)kSelMax);
@@ -690,6 +732,32 @@ __global__ void __launch_bounds__(kSelThreads) kmer_select_kernel(SelectArgs a) 
     }
     if (threadIdx.x == 0) a.out_n[q] = n < M ? n : M;
 }
+template <int kTopMax>
+__global__ void __launch_bounds__(kSelThreads) kmer_select_kernel(SelectArgs a) {
+    kmer_select_body<kTopMax, false>(a);
+}
+template <int kTopMax>
+__global__ void __launch_bounds__(kSelThreads) kmer_select_big_kernel(SelectArgs a) {
+    kmer_select_body<kTopMax, true>(a);
+}
+// sorted keys of a launch range ([nq][M], every segment descending) -> ids, scores, out_n
+__global__ void kmer_unpack_keys(const unsigned long long *keys, uint32_t nq, uint32_t M, uint32_t *out_ids, float *out_scores,
+                                 uint32_t *out_n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nq) out_n[i] = M;
+    if (i >= (uint64_t)nq * M) return;
+    const unsigned long long c = keys[i];
+    out_ids[i] = (uint32_t)c;
+    out_scores[i] = (float)((int)(uint32_t)(c >> 32) - 32768);
+}
+// segment q of the keys: [q M, (q + 1) M)
+struct BigSegOffset {
+    uint32_t M;
+    __host__ __device__ uint32_t operator()(uint32_t q) const { return q * M; }
+};
+// every segment is longer than any warp or block sort takes: one workgroup per segment, radix passes of 8 bits, and no
+// partition of the segments by length (which reads its counts back on the host in the middle of the launch)
+using BigSortConfig = rocprim::segmented_radix_sort_config<8, rocprim::kernel_config<256, 16>>;
 
 // Top-M out of the candidate list kmer_count_kernel<true> left for the query: a bitonic sort of its keys (score,
 // id) descending.  out_n = 0xFFFFFFFF: the list overflowed -- the host repeats the launch with the score rows.
@@ -800,10 +868,27 @@ static bool kmer_cand_path(const sina_hip_ctx *c, uint32_t max) {
 }
 // long_path: the queries of this range are longer than kMaxQueryLen -- the long count kernel and its select kernel,
 // score rows only
+// big select (max > kSelMax; the caller has clipped max to n_refs, so M = max): kmer_select_big_kernel leaves every
+// query's M survivors as keys in its segment, one segmented radix sort -- descending over the 48 bits a key can have
+// -- orders all segments of the range, kmer_unpack_keys writes ids, scores and out_n.  Keys, their double buffer and
+// rocPRIM's temporary storage are context buffers that only grow: sized here, before anything is launched.
 static int kmer_topk_device(sina_hip_ctx *c, const uint8_t *d_qmask, const uint64_t *d_qoff, uint32_t nq,
                             uint32_t max, uint32_t max_qlen, bool want_scores_only, bool cand_path, bool long_path = false) {
     hipStream_t s = c->stream;
     const uint32_t stride = (c->st->n_refs + 7u) & ~7u;  // rows 16-byte aligned (vector loads in the select kernel)
+    const bool big = !want_scores_only && !cand_path && max > (uint32_t)kSelMax;
+    using seg_iter = rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, BigSegOffset, uint32_t>;
+    const seg_iter seg_begin(rocprim::counting_iterator<uint32_t>(0), BigSegOffset{max});
+    const size_t n_keys = (size_t)nq * max;
+    size_t sort_tmp = 0;
+    if (big) {
+        if (n_keys > 0x7FFFFFFFull) SH_FAIL("kmer_topk: a launch range of the big select holds more than 2^31 candidates");
+        if (c->k_big_keys.reserve(2 * 8 * n_keys)) return 1;
+        rocprim::double_buffer<unsigned long long> kb(c->k_big_keys.as<unsigned long long>(), c->k_big_keys.as<unsigned long long>() + n_keys);
+        SH_CHECK(rocprim::segmented_radix_sort_keys_desc<BigSortConfig>(nullptr, sort_tmp, kb, (unsigned)n_keys, nq, seg_begin,
+                                                                        seg_begin + 1, 0u, 48u, s));
+        if (c->k_big_tmp.reserve(sort_tmp + 16)) return 1;
+    }
     if ((!cand_path && c->k_scores.reserve((size_t)nq * stride * 2 + 64)) || c->k_tmp2.reserve(8) || c->k_tmp0.reserve(4 * (size_t)nq) ||
         (cand_path && (c->k_tmp1.reserve(8 * (size_t)nq * kCandCap) || c->k_out_n.reserve((size_t)nq * 4))))
         return 1;
@@ -867,10 +952,21 @@ static int kmer_topk_device(sina_hip_ctx *c, const uint8_t *d_qmask, const uint6
         sa.out_n = c->k_out_n.as<uint32_t>();
         sa.n_refs = c->st->n_refs;
         sa.max = max;
+        sa.keys = big ? c->k_big_keys.as<unsigned long long>() : nullptr;
         // (the rows of the long count kernel hold scores of up to 32757: the search for the cut starts above them)
-        if (long_path) hipLaunchKernelGGL(kmer_select_kernel<kMaxLongQueryLen>, dim3(nq), dim3(kSelThreads), 0, hs, sa);
+        if (big && long_path) hipLaunchKernelGGL(kmer_select_big_kernel<kMaxLongQueryLen>, dim3(nq), dim3(kSelThreads), 0, hs, sa);
+        else if (big) hipLaunchKernelGGL(kmer_select_big_kernel<kMaxQueryLen>, dim3(nq), dim3(kSelThreads), 0, hs, sa);
+        else if (long_path) hipLaunchKernelGGL(kmer_select_kernel<kMaxLongQueryLen>, dim3(nq), dim3(kSelThreads), 0, hs, sa);
         else hipLaunchKernelGGL(kmer_select_kernel<kMaxQueryLen>, dim3(nq), dim3(kSelThreads), 0, hs, sa);
         SH_CHECK(hipGetLastError());
+        if (big) {
+            rocprim::double_buffer<unsigned long long> kb(sa.keys, sa.keys + n_keys);
+            SH_CHECK(rocprim::segmented_radix_sort_keys_desc<BigSortConfig>(c->k_big_tmp.p, sort_tmp, kb, (unsigned)n_keys, nq, seg_begin,
+                                                                            seg_begin + 1, 0u, 48u, hs));
+            hipLaunchKernelGGL(kmer_unpack_keys, dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, hs, kb.current(), nq, max,
+                               sa.out_ids, sa.out_scores, sa.out_n);
+            SH_CHECK(hipGetLastError());
+        }
     }
     SH_CHECK(hipEventRecord(c->ev[5], hs));
     return hl.done();
@@ -1003,7 +1099,7 @@ int sina_hip_build_index(sina_hip_ctx *c, unsigned k, int nofast) {
     return rc;
 }
 
-// sina_hip_kmer_topk / _any behind their checks (c->mu held, 1 <= max <= kSelMax): queries 0 .. n_fast - 1 on the fast
+// sina_hip_kmer_topk / _any behind their checks (c->mu held, 1 <= max <= n_refs): queries 0 .. n_fast - 1 on the fast
 // count kernel (none of them longer than kMaxQueryLen), queries n_fast .. nq - 1 -- every one of them longer -- on the
 // long kernel, in launch ranges of their own
 static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t n_fast,
@@ -1013,7 +1109,14 @@ static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *
     hipStream_t s = c->stream;
     const uint64_t nqm = qoff[nq] - qoff[0];
     // sub-batches bound the [nq][n_refs] int16 score matrix to ~2 GiB
-    const uint32_t per = (uint32_t)std::max<uint64_t>(1, ((uint64_t)2 << 30) / (2ull * std::max<uint32_t>(c->st->n_refs, 1)));
+    uint32_t per = (uint32_t)std::max<uint64_t>(1, ((uint64_t)2 << 30) / (2ull * std::max<uint32_t>(c->st->n_refs, 1)));
+    // ... and, for the big select, keys + outputs to kBigSelBudget (kmer_plan.h; SINA_HIP_TEST=big_sel_bytes=N: a test's budget)
+    const bool big = max > (uint32_t)kSelMax;
+    if (big) {
+        uint64_t budget = kBigSelBudget;
+        if (const std::string e_ = test_knob("big_sel_bytes"); !e_.empty()) budget = std::min<uint64_t>(kBigSelBudget, strtoull(e_.c_str(), nullptr, 10));
+        per = std::min(per, big_select_range(nq, max, budget));
+    }
     if (c->qmask.reserve(std::max<uint64_t>(nqm, 1)) || c->k_qoff.reserve(8 * ((uint64_t)nq + 1))) return 1;
     std::vector<uint64_t> rel(nq + 1);
     for (uint32_t q = 0; q <= nq; q++) rel[q] = qoff[q] - qoff[0];
@@ -1050,6 +1153,7 @@ static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *
         }
         if (*overflow) return 0;
         if (long_path) c->long_queries += bq;
+        if (big) c->big_select_queries += bq;
         memcpy(out_ids + (size_t)q0 * max, c->h_stage[9].p, (size_t)bq * max * 4);
         memcpy(out_scores + (size_t)q0 * max, c->h_stage[10].p, (size_t)bq * max * 4);
         memcpy(out_n + q0, c->h_stage[11].p, (size_t)bq * 4);
@@ -1089,7 +1193,6 @@ static int kmer_topk_checked(sina_hip_ctx *c, const uint8_t *qmask, const uint64
         memset(out_n, 0, sizeof(uint32_t) * nq);
         return 0;
     }
-    if (max > (uint32_t)kSelMax) SH_FAIL("kmer_topk: max > 4096 not supported by the LDS select kernel");
     uint32_t n_long = 0;
     for (uint32_t q = 0; q < nq; q++) {
         const uint64_t len = qoff[q + 1] - qoff[q];
@@ -1154,6 +1257,13 @@ int sina_hip_long_queries(sina_hip_ctx *c, uint64_t *n) {
     if (!c || !n) SH_FAIL("long_queries: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
     *n = c->long_queries;
+    return 0;
+}
+
+int sina_hip_big_select_queries(sina_hip_ctx *c, uint64_t *n) {
+    if (!c || !n) SH_FAIL("big_select_queries: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *n = c->big_select_queries;
     return 0;
 }
 

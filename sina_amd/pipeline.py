@@ -60,6 +60,7 @@ def load_host():
     H.sina_host_store_ctx.argtypes = [C.c_char_p]
     H.sina_host_store_build_index.argtypes = [C.c_char_p, C.c_uint, C.c_int]
     H.sina_host_store_slow_path_queries.argtypes = [C.c_char_p, capi.u64p, capi.u64p]
+    H.sina_host_store_big_select_queries.argtypes = [C.c_char_p, capi.u64p]
     H.sina_host_store_index_ready.argtypes = [C.c_char_p, C.c_uint, C.c_int]
     H.sina_host_store_set_attr.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_char_p]
     H.sina_host_sidx_load.argtypes = [C.c_char_p, C.c_uint, C.c_int, capi.u32p, capi.u32p, capi.u32p, C.c_uint64,
@@ -228,6 +229,13 @@ class Store:
         w, l = C.c_uint64(), C.c_uint64()
         _chk(self.H.sina_host_store_slow_path_queries(self.key.encode(), C.byref(w), C.byref(l)))
         return int(w.value), int(l.value)
+
+    def big_select_queries(self):
+        """Queries the k-mer search's big select (more than 4096 candidates per query) has ranked on this store's
+        contexts so far -- between runs, like slow_path_queries()."""
+        n = C.c_uint64()
+        _chk(self.H.sina_host_store_big_select_queries(self.key.encode(), C.byref(n)))
+        return int(n.value)
 
     def close(self):
         self.H.sina_host_store_close(self.key.encode())

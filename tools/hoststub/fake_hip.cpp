@@ -75,6 +75,7 @@ int sina_hip_kmer_topk_any(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t
 }
 int sina_hip_kmer_scores_any(sina_hip_ctx *, const uint8_t *, uint32_t, int16_t *) { g_err = "stub"; return 1; }
 int sina_hip_long_queries(sina_hip_ctx *, uint64_t *n) { *n = 0; return 0; }
+int sina_hip_big_select_queries(sina_hip_ctx *, uint64_t *n) { *n = 0; return 0; }
 int sina_hip_wide_queries(sina_hip_ctx *, uint64_t *n) { *n = 0; return 0; }
 int sina_hip_compare(sina_hip_ctx *, const uint32_t *, const uint64_t *, uint32_t, const uint32_t *, const uint64_t *,
                      int, int, sina_hip_match_counts *) { g_err = "stub"; return 1; }
