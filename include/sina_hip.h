@@ -182,6 +182,33 @@ int sina_hip_compare(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint64_t *q_
                      const uint32_t *cand_ids, const uint64_t *cand_off, int iupac_rule, int filter_lowercase,
                      sina_hip_match_counts *out);
 
+/* ------------------------------------------------------------- famfinder's identity filter (--fs-msc-max)
+ * The `match` counter alone, under base_comp_optimistic and without the lower-case filter, for many more candidates
+ * than the search stage compares: out_match[i] = number of columns where query and candidate i both have a base and
+ * (mask_q & mask_c & 0xF) != 0.  Whenever both have a base, the identity the filter tests is
+ * (float)match / (float)(bases of the query).
+ *
+ * sina_hip_match_count (singular: sina_hip_match_counts is the counter struct above): arguments as sina_hip_compare's (sub-ranges of larger offset arrays included);
+ *   out_match : [cand_off[nq]] counts, written at cand_off[0] .. cand_off[nq] - 1
+ * Refused with a message, before anything runs and with out_match untouched: a null argument, a reference id out of
+ * range, a query of more than 65535 bases, a query whose columns do not ascend strictly.  An alignment too wide for
+ * the kernel's LDS table (more than 327 680 columns) is refused as a limit (sina_hip_last_error_is_limit() == 1).
+ *
+ * sina_hip_kmer_topk_match: sina_hip_kmer_topk_any for queries given as packed aligned bases (the mask bytes the
+ * k-mer count reads are bits 24..31 of each word), plus the match count of every candidate returned:
+ *   out_ids, out_scores, out_n : bit for bit what sina_hip_kmer_topk_any gives for those mask bytes
+ *   out_match : [nq * min(max, n_refs)], out_match[q * M + i] belongs to out_ids[q * M + i], i < out_n[q]
+ * The counts are computed from the select's ids where they lie in device memory.  A query whose columns do not
+ * ascend strictly fails the call (not a limit); a store too wide fails it as a limit.
+ *
+ * sina_hip_match_stats: the match-count kernel's own time (events around its launches) and volume on this context
+ * since init / fork: pairs counted, bases of their candidates, launches. */
+int sina_hip_match_count(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq,
+                          const uint32_t *cand_ids, const uint64_t *cand_off, uint16_t *out_match);
+int sina_hip_kmer_topk_match(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t max,
+                             uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint16_t *out_match);
+int sina_hip_match_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches);
+
 /* ------------------------------------------------------------- alignment
  * Replaces, for a batch of queries: mseq::mseq + sort + reduce_edges
  * (src/mseq.cpp:47-118, src/graph.h:451-488) when given family ids, compute()

@@ -19,6 +19,7 @@ u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
 f32p = C.POINTER(C.c_float)
 i16p = C.POINTER(C.c_int16)
+u16p = C.POINTER(C.c_uint16)
 
 # every extern "C" symbol include/sina_hip.h declares
 ABI_SYMBOLS = [
@@ -32,6 +33,7 @@ ABI_SYMBOLS = [
     "sina_hip_align_graphs_any", "sina_hip_debug_mesh_wide", "sina_hip_wide_queries", "sina_hip_last_error_is_limit",
     "sina_hip_kmer_topk_any", "sina_hip_kmer_scores_any", "sina_hip_long_queries", "sina_hip_big_select_queries",
     "sina_hip_align_graphs_wsets", "sina_hip_align_families_wsets",
+    "sina_hip_match_count", "sina_hip_kmer_topk_match", "sina_hip_match_stats",
 ]
 
 # include/sina_hip.h: the fast k-mer / DP paths' query limit, the _any k-mer entries' limit, and the number of k-mer
@@ -137,6 +139,9 @@ def load():
     L.sina_hip_kmer_scores_any.argtypes = L.sina_hip_kmer_scores.argtypes
     L.sina_hip_long_queries.argtypes = [vp, u64p]
     L.sina_hip_big_select_queries.argtypes = [vp, u64p]
+    L.sina_hip_match_count.argtypes = [vp, u32p, u64p, C.c_uint32, u32p, u64p, u16p]
+    L.sina_hip_kmer_topk_match.argtypes = [vp, u32p, u64p, C.c_uint32, C.c_uint32, u32p, f32p, u32p, u16p]
+    L.sina_hip_match_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
     L.sina_hip_last_error_is_limit.restype = C.c_int
     L.sina_hip_debug_mesh_wide.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
                                            u32p, u32p, f32p]
@@ -393,6 +398,40 @@ class Context:
                                             _ptr(cand_ids, u32p), _ptr(cand_off, u64p), int(iupac),
                                             int(filter_lc), out.ctypes.data_as(C.c_void_p)))
         return out[:len(cand_ids)]
+
+    def match_counts(self, q_ab, q_off, cand_ids, cand_off):
+        """Famfinder's identity filter: uint16 [n candidates] = the `match` counter (optimistic IUPAC rule, no
+        lower-case filter) of every (query, candidate) pair; identity = float32(match) / float32(len(query))."""
+        q_ab = _c(q_ab, np.uint32)
+        q_off = _c(q_off, np.uint64)
+        cand_ids = _c(cand_ids, np.uint32)
+        cand_off = _c(cand_off, np.uint64)
+        out = np.zeros(max(len(cand_ids), 1), np.uint16)
+        self._check(self.L.sina_hip_match_count(self.h, _ptr(q_ab, u32p), _ptr(q_off, u64p), len(q_off) - 1,
+                                                 _ptr(cand_ids, u32p), _ptr(cand_off, u64p), _ptr(out, u16p)))
+        return out[:len(cand_ids)]
+
+    def kmer_topk_match(self, q_ab, q_off, mx):
+        """kmer_topk_any for queries given as packed aligned bases (column | mask << 24), plus the match count of
+        every candidate returned: (ids, scores, n, match), match uint16 [nq, min(mx, n_refs)]."""
+        q_ab = _c(q_ab, np.uint32)
+        q_off = _c(q_off, np.uint64)
+        nq = len(q_off) - 1
+        mx_eff = max(1, min(mx, self.n_refs))
+        ids = np.zeros((nq, mx_eff), np.uint32)
+        sc = np.zeros((nq, mx_eff), np.float32)
+        n = np.zeros(nq, np.uint32)
+        mt = np.zeros((nq, mx_eff), np.uint16)
+        self._check(self.L.sina_hip_kmer_topk_match(self.h, _ptr(q_ab, u32p), _ptr(q_off, u64p), nq, mx, _ptr(ids, u32p),
+                                                    _ptr(sc, f32p), _ptr(n, u32p), _ptr(mt, u16p)))
+        return ids, sc, n, mt
+
+    def match_stats(self):
+        """The match-count kernel on this context so far: dict(kernel_ms, pairs, cand_bases, launches)."""
+        ms = C.c_double()
+        pairs, bases, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.sina_hip_match_stats(self.h, C.byref(ms), C.byref(pairs), C.byref(bases), C.byref(launches)))
+        return dict(kernel_ms=float(ms.value), pairs=int(pairs.value), cand_bases=int(bases.value), launches=int(launches.value))
 
     def align_families(self, fam_ids, fam_off, qmask, qoff, params=None):
         params = params or self.params()

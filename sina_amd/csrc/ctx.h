@@ -131,6 +131,11 @@ struct sina_hip_ctx {
     sina_hip::DevBuf k_qoff, k_scores, k_out_ids, k_out_scores, k_out_n, k_tmp0, k_tmp1, k_tmp2;
     sina_hip::DevBuf g_fam_ids, g_fam_off, g_tmp0, g_tmp1, g_tmp2, g_tmp3, g_sizes, g_wtab;
     sina_hip::DevBuf s_qab, s_qoff, s_cand, s_coff, s_out;  // search-stage comparison
+    // the match-count kernel (match.hip): its rows of counts and, for caller-given lists, their lengths; its own time
+    // and volume on this context (sina_hip_match_stats)
+    sina_hip::DevBuf m_out, m_n;
+    double match_ms = 0;
+    uint64_t match_pairs = 0, match_bases = 0, match_launches = 0;
     sina_hip::HostBuf h_out, h_out_pos;  // pinned staging for the DP results
     // h_out_pos holds the aligned columns of a whole align call (laid out like the caller's out_pos): a launch
     // range writes at DpLaunch::out_pos_base, callers that pass no out_pos read them here (sina_hip_staged_out_pos)
@@ -140,7 +145,7 @@ struct sina_hip_ctx {
 
     size_t lds_budget = 0;  // LDS per DP workgroup; 0 = what keeps the register-limited occupancy (dp_default_lds_budget)
 
-    static constexpr int kNumScratch = 40;
+    static constexpr int kNumScratch = 42;
     static_assert(kNumScratch <= 64, "sina_hip_store::cap_hint is too short");
     void scratch(sina_hip::DevBuf **all) {
         sina_hip::DevBuf *list[kNumScratch] = {&qd, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &res,
@@ -148,7 +153,7 @@ struct sina_hip_ctx {
                                                &k_out_scores, &k_out_n, &k_tmp0, &k_tmp1, &k_tmp2, &g_fam_ids,
                                                &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &order,
                                                &s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &edge, &prof16, &self16, &rgain,
-                                               &scout, &scout_u, &wset};
+                                               &scout, &scout_u, &wset, &m_out, &m_n};
         for (int i = 0; i < kNumScratch; i++) all[i] = list[i];
     }
     void publish_hints() {  // after a call: remember how big my buffers had to be
@@ -177,7 +182,7 @@ struct sina_hip_ctx {
         sina_hip::DevBuf *align[] = {&qd, &order, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &edge, &res, &weights, &out,
                                      &out_pos, &g_fam_ids, &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &rgain, &scout, &scout_u,
                                      &prof16, &self16, &wset};
-        sina_hip::DevBuf *compare[] = {&s_qab, &s_qoff, &s_cand, &s_coff, &s_out};
+        sina_hip::DevBuf *compare[] = {&s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &m_out, &m_n};
         sina_hip::DevBuf **list = kind == 0 ? search : (kind == 1 ? align : compare);
         const size_t n = kind == 0 ? sizeof search / sizeof *search : (kind == 1 ? sizeof align / sizeof *align : sizeof compare / sizeof *compare);
         for (size_t i = 0; i < n; i++) {
@@ -606,6 +611,16 @@ uint64_t wide_budget_cells();
 int run_wide(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask, const uint64_t *qoff,
              const sina_hip_align_params *p, const uint32_t *qs, uint32_t n, sina_hip_align_out *out, uint32_t *out_pos,
              uint32_t *dbg_vm = nullptr, uint32_t *dbg_vs = nullptr, float *dbg_value = nullptr);
+}  // namespace sina_hip
+
+namespace sina_hip {
+// ---- the match-count kernel (match.hip): nq queries (packed aligned bases d_qab at d_qoff[q], device memory) against
+// the candidates d_ids[q * stride + i], i < d_n[q] (0xFFFFFFFF = 0), counts into d_out[q * stride + i]; returns when
+// the kernel has ended.  h_ids / h_n: the same lists on the host (volume counters).
+int match_launch(sina_hip_ctx *c, const uint32_t *d_qab, const uint64_t *d_qoff, uint32_t nq, const uint32_t *d_ids,
+                 const uint32_t *d_n, uint32_t stride, uint16_t *d_out, const uint32_t *h_ids, const uint32_t *h_n);
+// fails unless every query has at most 65535 bases in strictly ascending columns
+int match_check_queries(const char *who, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq);
 }  // namespace sina_hip
 
 // publishes the context's scratch capacities when an API call ends (see sina_hip_store::cap_hint)

@@ -211,6 +211,20 @@ void fill_query_tray(tray &t, uint32_t q, const uint8_t *qmask, const uint64_t *
     host_tick("build: bases", tk);
 }
 
+// An ALIGNED query under its own name: packed aligned bases (column | mask << 24) as a reader of aligned input hands
+// them over -- what the identity filter (--fs-msc-max) and --fs-leave-query-out look at.
+void fill_aligned_query_tray(tray &t, uint32_t q, const uint32_t *q_ab, const uint64_t *q_off, const char *name, uint32_t width) {
+    t.seqno = q;
+    t.clear_log();
+    t.input_sequence = object_cache<cseq, cache_query_seq>::take();
+    t.input_sequence->setName(std::string_view(name));
+    static_assert(sizeof(aligned_base) == 4, "packed words");
+    t.input_sequence->setAlignedBases(reinterpret_cast<const aligned_base *>(q_ab + q_off[q]), (size_t)(q_off[q + 1] - q_off[q]));
+    uint32_t cols = width;  // (a base beyond the store's alignment stays where it is)
+    for (uint64_t i = q_off[q]; i < q_off[q + 1]; i++) cols = std::max(cols, (q_ab[i] & 0xFFFFFFu) + 1u);
+    t.input_sequence->setWidth(cols);
+}
+
 // ---- what the staged drivers below share (the runner itself: flow.h)
 // what a queue does with a batch nobody will take any more
 void destroy_trays(std::vector<tray> &trays) {
@@ -335,6 +349,14 @@ int sina_host_store_slow_path_queries(const char *key, uint64_t *wide, uint64_t 
 int sina_host_store_big_select_queries(const char *key, uint64_t *n) {
     try {
         reference_store::get(key)->big_select_queries(n);
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
+int sina_host_store_match_stats(const char *key, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches) {
+    try {
+        reference_store::get(key)->match_stats(kernel_ms, pairs, cand_bases, launches);
         return 0;
     } catch (const std::exception &e) {
         return fail(e);
@@ -671,15 +693,15 @@ void *sina_host_pipeline_create_search(void) {
 }
 void sina_host_pipeline_destroy(void *p) { delete (pipeline *)p; }
 
-// Feeds nq unaligned queries (iupac masks) through famfinder -> aligner in batches
-// of `batch`, with `inflight` batches being worked on concurrently (host stages of
-// one batch overlap GPU work of another).
 // marks of the bench in the SINA_HOST_TRACE file: 0 = timed region starts, 1 = ends
 void sina_host_profile_mark(int which) { host_profile_mark(which == 0 ? "MARK:timed-start" : "MARK:timed-end"); }
+}  // extern "C"
 
-int sina_host_pipeline_run(void *pp, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t batch,
-                           uint32_t inflight) {
-    pipeline *p = (pipeline *)pp;
+// Feeds nq queries through famfinder -> aligner in batches of `batch`, with `inflight` batches being worked on
+// concurrently (host stages of one batch overlap GPU work of another).  fill(tray, q): the source's part -- query q
+// as the reader stage would hand it over.
+template <class Fill>
+static int run_queries(pipeline *p, uint32_t nq, const uint64_t *qoff, uint32_t batch, uint32_t inflight, Fill &&fill) {
     try {
         host_profile_mark("MARK:run-entered");
         if (batch == 0) batch = nq ? nq : 1;
@@ -713,7 +735,7 @@ int sina_host_pipeline_run(void *pp, const uint8_t *qmask, const uint64_t *qoff,
             {
                 host_phase hp("drv.build_trays");
                 parallel_for(it.b1 - it.b0, [&](size_t i) {  // (what SINA's reader stage does per sequence)
-                    fill_query_tray(it.trays[i], it.b0 + (uint32_t)i, qmask, qoff);
+                    fill(it.trays[i], it.b0 + (uint32_t)i);
                 });
             }
             timed(ff_ns, [&] { p->ff(it.trays); });
@@ -769,6 +791,31 @@ int sina_host_pipeline_run(void *pp, const uint8_t *qmask, const uint64_t *qoff,
     } catch (const std::exception &e) {
         return fail(e);
     }
+}
+
+extern "C" {
+// nq unaligned queries (iupac masks): base i in column i, named queryN
+int sina_host_pipeline_run(void *pp, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t batch,
+                           uint32_t inflight) {
+    return run_queries((pipeline *)pp, nq, qoff, batch, inflight,
+                       [&](tray &t, uint32_t q) { fill_query_tray(t, q, qmask, qoff); });
+}
+
+// The same run for ALIGNED queries under their own names: q_ab / q_off the packed aligned bases (column | mask << 24),
+// names[q] the sequence's name.  What reaches --fs-msc-max and --fs-leave-query-out (a leave-out run: queries taken from
+// the references themselves).  Results through sina_host_result(q) as ever.
+int sina_host_pipeline_run_aligned(void *pp, const uint32_t *q_ab, const uint64_t *q_off, const char *const *names,
+                                   uint32_t nq, uint32_t batch, uint32_t inflight) {
+    pipeline *p = (pipeline *)pp;
+    uint32_t width = 0;
+    try {
+        if (!q_ab || !q_off || !names) throw std::logic_error("pipeline_run_aligned: null argument");
+        width = reference_store::get(aligner::opts->database)->getAlignmentWidth();
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+    return run_queries(p, nq, q_off, batch, inflight,
+                       [&](tray &t, uint32_t q) { fill_aligned_query_tray(t, q, q_ab, q_off, names[q], width); });
 }
 
 // The boundary as INTEGRATION.md binds it (src/sina.cpp:497-519): `n_threads` callers -- TBB workers of

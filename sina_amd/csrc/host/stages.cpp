@@ -8,6 +8,7 @@
 #include <immintrin.h>
 #include "id_order.h"
 #include "../kmer_plan.h"
+#include "../match_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -605,6 +606,31 @@ void reference_store::big_select_queries(uint64_t *n) {
     for (auto &pool : idle_forks)
         for (sina_hip_ctx *c : pool) add(c);
 }
+void reference_store::match_stats(double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches) {
+    sina_hip_ctx *root = device();
+    std::lock_guard<std::mutex> lk(gpu_mu);
+    *kernel_ms = 0;
+    *pairs = *cand_bases = *launches = 0;
+    auto add = [&](sina_hip_ctx *c) {
+        double ms = 0;
+        uint64_t p = 0, b = 0, l = 0;
+        hip_check(sina_hip_match_stats(c, &ms, &p, &b, &l), "sina_hip_match_stats");
+        *kernel_ms += ms;
+        *pairs += p;
+        *cand_bases += b;
+        *launches += l;
+    };
+    add(root);
+    for (auto &pool : idle_forks)
+        for (sina_hip_ctx *c : pool) add(c);
+}
+bool reference_store::match_counts_too_wide() {
+    if (sina_hip::match_table_bytes(width) <= sina_hip::kMatchMaxLds) return false;
+    if (!too_wide_said.exchange(true))
+        fprintf(stderr, "famfinder: device-msc: the alignment's %u columns are more than the device's match count takes; "
+                        "identities stay with the host walk\n", width);
+    return true;
+}
 reference_store::lease::~lease() {
     if (!c) return;
     std::lock_guard<std::mutex> lk(st->gpu_mu);
@@ -914,15 +940,63 @@ static uint64_t hash_bytes(const void *p, size_t n, uint64_t seed) {  // (FNV-1a
     return h ^ (h >> 32);
 }
 
+// true if the sequence's columns ascend strictly (what the device's match count asks of a query)
+static bool columns_ascend(const cseq &c) {
+    if (c.denseMasks()) return true;  // (base i in column i)
+    const uint32_t *ab = c.packed();
+    for (size_t i = 1, n = c.size(); i < n; i++)
+        if ((ab[i] & 0xFFFFFFu) <= (ab[i - 1] & 0xFFFFFFu)) return false;
+    return true;
+}
+
 void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vector<result_vector> &results,
-                             unsigned int max, std::vector<uint32_t> *kmer_counts) {
+                             unsigned int max, std::vector<uint32_t> *kmer_counts, std::vector<std::vector<uint16_t>> *match_rows) {
     reference_store &st = *pimpl->store;
     const unsigned n = st.size();
     // (the callers' vectors are kept -- famfinder hands in recycled ones -- and only emptied)
     results.resize(queries.size());
     for (auto &r : results) r.clear();
+    if (match_rows) {
+        match_rows->resize(queries.size());
+        for (auto &r : *match_rows) r.clear();
+    }
     if (max > n) max = n;
     if (max == 0 || queries.empty()) return;
+    // The device's match counts (famfinder's device-msc): kept from a store too wide for the kernel's table -- said
+    // once, then every query keeps the host walk -- and from a query whose columns do not ascend strictly: those are
+    // searched through the entry without counts, in a call of their own, and their rows stay empty.
+    if (match_rows && st.match_counts_too_wide()) match_rows = nullptr;
+    if (match_rows) {
+        std::vector<size_t> plain;
+        for (size_t i = 0; i < queries.size(); i++)
+            if (!columns_ascend(*queries[i])) plain.push_back(i);
+        if (!plain.empty()) {
+            std::vector<char> is_plain(queries.size(), 0);
+            for (size_t i : plain) is_plain[i] = 1;
+            for (int pass = 0; pass < 2; pass++) {
+                std::vector<size_t> at;
+                std::vector<const cseq *> sub;
+                for (size_t i = 0; i < queries.size(); i++)
+                    if ((is_plain[i] != 0) == (pass == 1)) {
+                        at.push_back(i);
+                        sub.push_back(queries[i]);
+                    }
+                if (sub.empty()) continue;
+                std::vector<result_vector> sub_results(sub.size());
+                for (size_t x = 0; x < sub.size(); x++) sub_results[x].swap(results[at[x]]);
+                std::vector<uint32_t> sub_counts;
+                std::vector<std::vector<uint16_t>> sub_rows;
+                find_batch(sub, sub_results, max, kmer_counts ? &sub_counts : nullptr, pass == 0 ? &sub_rows : nullptr);
+                if (kmer_counts && kmer_counts->size() != queries.size()) kmer_counts->assign(queries.size(), 0);
+                for (size_t x = 0; x < sub.size(); x++) {
+                    results[at[x]].swap(sub_results[x]);
+                    if (kmer_counts) (*kmer_counts)[at[x]] = sub_counts[x];
+                    if (pass == 0) (*match_rows)[at[x]].swap(sub_rows[x]);
+                }
+            }
+            return;
+        }
+    }
     st.ensure_index(pimpl->k, pimpl->nofast);
     std::vector<uint64_t> qoff(queries.size() + 1, 0);
     for (size_t i = 0; i < queries.size(); i++) qoff[i + 1] = qoff[i] + queries[i]->size();
@@ -939,16 +1013,30 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
         else masks_of_packed(dst, queries[i]->packed(), nb);
         if (kmer_counts) (*kmer_counts)[i] = count_query_kmers(dst, nb, kk, count_all);
     });
+    // with match counts the device takes the queries as packed aligned bases (a dense query's: base i in column i)
+    thread_local batch_scratch<uint32_t> qab_buf;
+    uint32_t *const qab = match_rows ? qab_buf.get(qoff.back() + 1) : nullptr;
+    if (match_rows)
+        parallel_for(queries.size(), [&](size_t i) {
+            const size_t nb = queries[i]->size();
+            if (queries[i]->denseMasks()) packed_of_masks(qab + qoff[i], qmask + qoff[i], nb);
+            else memcpy(qab + qoff[i], queries[i]->packed(), 4 * nb);
+        });
     auto dev = st.worker_device(reference_store::dev_search);
     sina_hip_ctx *ctx = dev.get();
     // repeated queries (same bases, same case: the packed mask bytes) are searched once
     std::vector<uint32_t> rep;
     const size_t nu = group_equal_items(
         queries.size(),
-        [&](size_t i) { return hash_ends(qmask + qoff[i], qoff[i + 1] - qoff[i], qoff[i + 1] - qoff[i]); },
+        // (with match counts: same PACKED WORDS -- equal bases in other columns are another query there)
+        [&](size_t i) {
+            return qab ? hash_ends(qab + qoff[i], 4 * (qoff[i + 1] - qoff[i]), qoff[i + 1] - qoff[i])
+                       : hash_ends(qmask + qoff[i], qoff[i + 1] - qoff[i], qoff[i + 1] - qoff[i]);
+        },
         [&](size_t a, size_t b) {
-            return qoff[a + 1] - qoff[a] == qoff[b + 1] - qoff[b] &&
-                   memcmp(qmask + qoff[a], qmask + qoff[b], qoff[a + 1] - qoff[a]) == 0;
+            if (qoff[a + 1] - qoff[a] != qoff[b + 1] - qoff[b]) return false;
+            return qab ? memcmp(qab + qoff[a], qab + qoff[b], 4 * (qoff[a + 1] - qoff[a])) == 0
+                       : memcmp(qmask + qoff[a], qmask + qoff[b], qoff[a + 1] - qoff[a]) == 0;
         },
         rep);
     std::vector<uint32_t> slot_of(queries.size());
@@ -956,6 +1044,8 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
     const uint64_t *dev_off = qoff.data();
     std::vector<uint64_t> uoff;
     thread_local batch_scratch<uint8_t> umask_buf;
+    const uint32_t *dev_ab = qab;
+    thread_local batch_scratch<uint32_t> uab_buf;
     if (nu == queries.size()) {
         for (size_t i = 0; i < queries.size(); i++) slot_of[i] = (uint32_t)i;
     } else {  // the distinct queries, packed again for the device
@@ -975,6 +1065,11 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
         parallel_for(nu, [&](size_t u) { memcpy(um + uoff[u], qmask + qoff[firsts[u]], uoff[u + 1] - uoff[u]); });
         dev_mask = um;
         dev_off = uoff.data();
+        if (qab) {
+            uint32_t *const ua = uab_buf.get(uoff.back() + 1);
+            parallel_for(nu, [&](size_t u) { memcpy(ua + uoff[u], qab + qoff[firsts[u]], 4 * (uoff[u + 1] - uoff[u])); });
+            dev_ab = ua;
+        }
     }
     // Up to 4096 candidates per query the distinct queries go to the device in one call, as ever.  More (famfinder
     // widening its list tenfold per round, a large search-kmer-candidates): nu * max ids and scores are no longer one
@@ -987,13 +1082,18 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
     uint32_t *const ids = ids_buf.get(slice * max);
     float *const sc = sc_buf.get(slice * max);
     std::vector<uint32_t> cnt(slice);
+    thread_local batch_scratch<uint16_t> mt_buf;
+    uint16_t *const mt = match_rows ? mt_buf.get(slice * max) : nullptr;
     for (size_t u0 = 0; u0 < nu; u0 += slice) {
         const size_t u1 = std::min(nu, u0 + slice);
         {
             scoped_phase ph("ff.kmer_topk(C-ABI)");
             // (the _any entry: the class has no length limit of its own, as the reference's -- a query beyond the fast count
             // kernel's goes to the long one, per query; offsets are absolute, so a slice starts at dev_off + u0)
-            hip_check(sina_hip_kmer_topk_any(ctx, dev_mask, dev_off + u0, (uint32_t)(u1 - u0), max, ids, sc, cnt.data()), "kmer_topk");
+            if (match_rows)
+                hip_check(sina_hip_kmer_topk_match(ctx, dev_ab, dev_off + u0, (uint32_t)(u1 - u0), max, ids, sc, cnt.data(), mt), "kmer_topk_match");
+            else
+                hip_check(sina_hip_kmer_topk_any(ctx, dev_mask, dev_off + u0, (uint32_t)(u1 - u0), max, ids, sc, cnt.data()), "kmer_topk");
         }
         parallel_for(queries.size(), [&](size_t i) {
             const size_t u = slot_of[i];
@@ -1001,6 +1101,7 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
             const size_t at = (u - u0) * max;
             results[i].reserve(cnt[u - u0]);
             for (uint32_t x = 0; x < cnt[u - u0]; x++) results[i].emplace_back(sc[at + x], &st.getCseq(ids[at + x]));
+            if (match_rows) (*match_rows)[i].assign(mt + at, mt + at + cnt[u - u0]);
         });
     }
 }
@@ -1022,6 +1123,7 @@ struct ff_options {
     unsigned int fs_kmer_len, fs_min_len, fs_cover_gene;
     std::string database;
     bool long_queries;  // search queries of up to SINA_HIP_MAX_LONG_QUERY_LEN bases (default off: SINA_HIP_MAX_QUERY_LEN)
+    bool device_msc;    // fs-msc-max < 1: the candidates' identities from the device's match counts (default off: the host walk)
 };
 ff_options ff_defaults() {  // src/famfinder.cpp:144-203
     ff_options o;
@@ -1041,6 +1143,7 @@ ff_options ff_defaults() {  // src/famfinder.cpp:144-203
     o.fs_min_len = 150;
     o.fs_cover_gene = 0;
     o.long_queries = false;
+    o.device_msc = false;
     o.posvar_autofilter_thres = 0.8f;  // src/famfinder.cpp:205-208
     return o;
 }
@@ -1112,6 +1215,7 @@ void famfinder::set_option(const std::string &name, const std::string &value) {
     else if (name == "auto-filter-field") o.posvar_autofilter_field = value;
     else if (name == "auto-filter-threshold") o.posvar_autofilter_thres = std::stof(value);
     else if (name == "long-queries") o.long_queries = to_bool(value);
+    else if (name == "device-msc") o.device_msc = to_bool(value);
     else throw std::logic_error("famfinder: unknown option " + name);
 }
 
@@ -1276,11 +1380,15 @@ namespace {
 struct match_state {
     size_t have = 0, have_full = 0, have_cover_left = 0, have_cover_right = 0;
 };
-bool match_pass(search::result_vector &results, const cseq &query, match_state &st, const reference_store *store) {
+// match_row (device-msc; else null): the device's match count of every candidate, by its rank in the list as it came
+// from the search -- the identity is then match / |query| instead of the walk
+bool match_pass(search::result_vector &results, const cseq &query, match_state &st, const reference_store *store,
+                const uint16_t *match_row = nullptr) {
     const ff_options &o = ff_opts;
     const size_t range_begin = 0, range_end = 0;
     st = match_state();
-    auto remove = [&](const search::result_item &r) {
+    const float query_bases = (float)query.size();
+    auto remove_ranked = [&](const search::result_item &r, const uint16_t *match) {
         const cseq &s = *r.sequence;
         // (size, first and last column: out of the store's table for its own sequences)
         reference_store::ref_meta m;
@@ -1292,7 +1400,10 @@ bool match_pass(search::result_vector &results, const cseq &query, match_state &
         const bool is_right = m.size && m.last_pos >= range_end;
         if (m.size < o.fs_min_len) return true;
         if (o.fs_leave_query_out && query.name_ref() == s.name_ref()) return true;
-        if (o.fs_msc_max <= 2 && o.fs_msc_max < 1 && identity_cover_query(query, s) > o.fs_msc_max) return true;
+        if (o.fs_msc_max <= 2 && o.fs_msc_max < 1) {
+            const float identity = match ? (query.size() ? (float)*match / query_bases : 0.f) : identity_cover_query(query, s);
+            if (identity > o.fs_msc_max) return true;
+        }
         const bool min_reached = st.have >= o.fs_min, max_reached = st.have >= o.fs_max;
         const bool score_good = r.score < o.fs_msc;  // sic (src/famfinder.cpp:565-567)
         const bool adds_to_full = o.fs_req_full && st.have_full < o.fs_req_full && is_full;
@@ -1309,7 +1420,18 @@ bool match_pass(search::result_vector &results, const cseq &query, match_state &
     if (store)
         for (const auto &r : results)
             if (store->owns(r.sequence)) __builtin_prefetch(&store->meta(store->id_of(r.sequence)));
-    results.erase(std::remove_if(results.begin(), results.end(), remove), results.end());
+    if (match_row) {  // (the row is indexed by the rank before anything was removed: an explicit loop)
+        size_t kept = 0;
+        for (size_t i = 0; i < results.size(); i++) {
+            if (remove_ranked(results[i], match_row + i)) continue;
+            if (kept != i) results[kept] = std::move(results[i]);
+            ++kept;
+        }
+        results.erase(results.begin() + (std::ptrdiff_t)kept, results.end());
+    } else {
+        auto remove = [&](const search::result_item &r) { return remove_ranked(r, nullptr); };
+        results.erase(std::remove_if(results.begin(), results.end(), remove), results.end());
+    }
     return !(st.have < o.fs_max || st.have_full < o.fs_req_full || st.have_cover_left < o.fs_cover_gene ||
              st.have_cover_right < o.fs_cover_gene);
 }
@@ -1373,10 +1495,13 @@ void famfinder::impl::run(std::vector<tray *> &batch) {
         std::vector<search::result_vector> found(todo.size());
         for (size_t i = 0; i < todo.size(); i++) found[i].swap(*todo[i]->alignment_reference);  // (their heap blocks, recycled)
         std::vector<uint32_t> nk;
+        // device-msc: every candidate's match count comes with the ids (an empty row: that query keeps the walk)
+        const bool device_msc = o.device_msc && o.fs_msc_max < 1;
+        std::vector<std::vector<uint16_t>> match_rows;
         {
             scoped_phase ph_find("ff.find_batch");
             index->find_batch(qs, found, (unsigned)std::min<size_t>(max_results, isize),
-                              o.engine == ENGINE_SINA_KMER ? &nk : nullptr);
+                              o.engine == ENGINE_SINA_KMER ? &nk : nullptr, device_msc ? &match_rows : nullptr);
         }
         for (size_t i = 0; i < nk.size(); i++) todo[i]->query_kmer_count = (int)nk[i];
         std::vector<char> done(todo.size(), 0);
@@ -1389,7 +1514,8 @@ void famfinder::impl::run(std::vector<tray *> &batch) {
                 return;
             }
             match_state st;
-            const bool enough = match_pass(res, *todo[i]->input_sequence, st, arb.get());
+            const uint16_t *row = device_msc && match_rows[i].size() == res.size() ? match_rows[i].data() : nullptr;
+            const bool enough = match_pass(res, *todo[i]->input_sequence, st, arb.get(), row);
             done[i] = (enough || max_results >= isize) ? 1 : 0;
         });
         std::vector<tray *> next;

@@ -310,6 +310,10 @@ public:
     void slow_path_queries(uint64_t *wide, uint64_t *long_kmer);
     // ... and queries the k-mer search's big select (more than 4096 candidates) has ranked -- sina_hip_big_select_queries
     void big_select_queries(uint64_t *n);
+    // ... and the match-count kernel's time and volume (famfinder's device-msc) -- sina_hip_match_stats
+    void match_stats(double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches);
+    // the alignment is wider than the match-count kernel's table takes: said once (stderr), then true every time
+    bool match_counts_too_wide();
 
 private:
     reference_store() = default;
@@ -332,6 +336,7 @@ private:
     std::mutex labels_mu;
     std::atomic<bool> labels_ready{false};
     std::mutex gpu_mu;
+    std::atomic<bool> too_wide_said{false};
 };
 
 // ---------------------------------------------------------------- .sidx index cache
@@ -355,8 +360,12 @@ public:
     // one launch for many queries; results[i] gets min(max, size()) items
     // (kmer_counts, optional: the number of k-mers of every query, with multiplicity -- what a reference
     // holding all of them scores; counted in the pass that packs the queries for the device)
+    // (match_rows, optional: famfinder's device-msc -- per query the device's match count of every result, by rank;
+    // the row of a query whose columns do not ascend strictly, and every row of a store too wide for the kernel, stays
+    // empty: those identities are the host walk's)
     void find_batch(const std::vector<const cseq *> &queries, std::vector<result_vector> &results,
-                    unsigned int max, std::vector<uint32_t> *kmer_counts = nullptr);
+                    unsigned int max, std::vector<uint32_t> *kmer_counts = nullptr,
+                    std::vector<std::vector<uint16_t>> *match_rows = nullptr);
     unsigned int size() const override;
     ~kmer_search() override;
 
@@ -386,7 +395,7 @@ public:
     // option names as on the SINA command line: "db", "turn", "fs-kmer-len", "fs-req", "fs-min",
     // "fs-max", "fs-msc", "fs-req-full", "fs-full-len", "fs-req-gaps", "fs-min-len",
     // "fs-kmer-no-fast", "fs-msc-max", "fs-leave-query-out", "fs-cover-gene", "filter", "auto-filter-field",
-    // "auto-filter-threshold"
+    // "auto-filter-threshold", "long-queries", "device-msc" (fs-msc-max < 1: identities from the device's match counts)
     static void set_option(const std::string &name, const std::string &value);
     static void reset_options();
     static void validate_options();

@@ -37,6 +37,7 @@
 #include "common.h"
 #include "ctx.h"
 #include "kmer_plan.h"
+#include "match_plan.h"
 
 namespace sina_hip {
 namespace {
@@ -1102,8 +1103,11 @@ int sina_hip_build_index(sina_hip_ctx *c, unsigned k, int nofast) {
 // sina_hip_kmer_topk / _any behind their checks (c->mu held, 1 <= max <= n_refs): queries 0 .. n_fast - 1 on the fast
 // count kernel (none of them longer than kMaxQueryLen), queries n_fast .. nq - 1 -- every one of them longer -- on the
 // long kernel, in launch ranges of their own
+// q_ab / out_match (sina_hip_kmer_topk_match; else null): the queries' packed aligned bases, one per mask byte, and
+// where every range's match counts go (match.hip), [nq * max] like out_ids
 static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t n_fast,
-                         uint32_t max, uint32_t *out_ids, float *out_scores, uint32_t *out_n) {
+                         uint32_t max, uint32_t *out_ids, float *out_scores, uint32_t *out_n, const uint32_t *q_ab = nullptr,
+                         uint16_t *out_match = nullptr) {
     uint32_t max_qlen = 1;
     for (uint32_t q = 0; q < n_fast; q++) max_qlen = std::max<uint32_t>(max_qlen, (uint32_t)(qoff[q + 1] - qoff[q]));
     hipStream_t s = c->stream;
@@ -1122,6 +1126,7 @@ static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *
     for (uint32_t q = 0; q <= nq; q++) rel[q] = qoff[q] - qoff[0];
     if (upload(c, 7, c->qmask.p, qmask + qoff[0], nqm, s) || upload(c, 8, c->k_qoff.p, rel.data(), 8 * ((uint64_t)nq + 1), s))
         return 1;
+    if (out_match && (c->s_qab.reserve(4 * std::max<uint64_t>(nqm, 1)) || upload(c, 1, c->s_qab.p, q_ab + qoff[0], 4 * nqm, s))) return 1;
     // one launch range: kernels, results back through pinned staging, statistics; *overflow = a candidate list of the
     // range did not hold its query's candidates (nothing was copied out then: the caller repeats the range with rows)
     auto run_range = [&](uint32_t q0, uint32_t bq, bool cand_path, bool *overflow, bool long_path = false) -> int {
@@ -1157,6 +1162,18 @@ static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *
         memcpy(out_ids + (size_t)q0 * max, c->h_stage[9].p, (size_t)bq * max * 4);
         memcpy(out_scores + (size_t)q0 * max, c->h_stage[10].p, (size_t)bq * max * 4);
         memcpy(out_n + q0, c->h_stage[11].p, (size_t)bq * 4);
+        if (out_match) {  // the range's select is final: its candidates' match counts, ids and lengths read where they lie
+            const size_t row_bytes = (size_t)bq * max * 2;
+            if (c->m_out.reserve(row_bytes)) return 1;
+            SH_CHECK(hipMemsetAsync(c->m_out.p, 0, row_bytes, s));
+            if (match_launch(c, c->s_qab.as<uint32_t>(), c->k_qoff.as<uint64_t>() + q0, bq, c->k_out_ids.as<uint32_t>(),
+                             c->k_out_n.as<uint32_t>(), max, c->m_out.as<uint16_t>(), static_cast<const uint32_t *>(c->h_stage[9].p),
+                             static_cast<const uint32_t *>(c->h_stage[11].p)) ||
+                download(c, 5, c->m_out.p, row_bytes, s))
+                return 1;
+            SH_CHECK(wait_stream(c, s));
+            memcpy(out_match + (size_t)q0 * max, c->h_stage[5].p, row_bytes);
+        }
         return 0;
     };
     const bool cand_path = kmer_cand_path(c, max);
@@ -1181,11 +1198,14 @@ static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *
 // any: queries of up to kMaxLongQueryLen bases (sina_hip_kmer_topk_any), the longer ones behind the others for
 // kmer_topk_run and back into the caller's order
 static int kmer_topk_checked(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max,
-                             uint32_t *out_ids, float *out_scores, uint32_t *out_n, bool any) {
+                             uint32_t *out_ids, float *out_scores, uint32_t *out_n, bool any, const uint32_t *q_ab = nullptr,
+                             uint16_t *out_match = nullptr) {
     if (!c || !qmask || !qoff || !out_ids || !out_scores || !out_n) SH_FAIL("kmer_topk: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
     if (index_ready(c)) return 1;
+    if (out_match && match_table_bytes(c->st->width) > kMatchMaxLds)
+        SH_FAIL_LIMIT("kmer_topk_match: alignment too wide for the device match count");
     if (nq == 0) return 0;
     SH_CHECK(hipSetDevice(c->device));
     if (max > c->st->n_refs) max = c->st->n_refs;
@@ -1200,7 +1220,7 @@ static int kmer_topk_checked(sina_hip_ctx *c, const uint8_t *qmask, const uint64
         if (len > (uint64_t)kMaxLongQueryLen) SH_FAIL_LIMIT("kmer_topk_any: query longer than SINA_HIP_MAX_LONG_QUERY_LEN bases");
         n_long += len > (uint64_t)kMaxQueryLen;
     }
-    if (n_long == 0) return kmer_topk_run(c, qmask, qoff, nq, nq, max, out_ids, out_scores, out_n);
+    if (n_long == 0) return kmer_topk_run(c, qmask, qoff, nq, nq, max, out_ids, out_scores, out_n, q_ab, out_match);
     const uint32_t n_fast = nq - n_long;
     std::vector<uint32_t> order(nq);  // order[slot] = the caller's query
     for (uint32_t q = 0, f = 0, l = n_fast; q < nq; q++) order[qoff[q + 1] - qoff[q] > (uint64_t)kMaxQueryLen ? l++ : f++] = q;
@@ -1210,8 +1230,15 @@ static int kmer_topk_checked(sina_hip_ctx *c, const uint8_t *qmask, const uint64
     for (uint32_t x = 0; x < nq; x++) memcpy(mask.data() + off[x], qmask + qoff[order[x]], off[x + 1] - off[x]);
     std::vector<uint32_t> ids((size_t)nq * max), n(nq);
     std::vector<float> sc((size_t)nq * max);
-    if (kmer_topk_run(c, mask.data(), off.data(), nq, n_fast, max, ids.data(), sc.data(), n.data())) return 1;
+    std::vector<uint32_t> ab(out_match ? off[nq] : 0);  // (the packed bases and the match rows move with their queries)
+    std::vector<uint16_t> mt(out_match ? (size_t)nq * max : 0);
+    if (out_match)
+        for (uint32_t x = 0; x < nq; x++) memcpy(ab.data() + off[x], q_ab + qoff[order[x]], 4 * (off[x + 1] - off[x]));
+    if (kmer_topk_run(c, mask.data(), off.data(), nq, n_fast, max, ids.data(), sc.data(), n.data(), out_match ? ab.data() : nullptr,
+                      out_match ? mt.data() : nullptr))
+        return 1;
     for (uint32_t x = 0; x < nq; x++) {
+        if (out_match) memcpy(out_match + (size_t)order[x] * max, mt.data() + (size_t)x * max, (size_t)max * 2);
         memcpy(out_ids + (size_t)order[x] * max, ids.data() + (size_t)x * max, (size_t)max * 4);
         memcpy(out_scores + (size_t)order[x] * max, sc.data() + (size_t)x * max, (size_t)max * 4);
         out_n[order[x]] = n[x];
@@ -1246,6 +1273,18 @@ int sina_hip_kmer_topk(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qo
 int sina_hip_kmer_topk_any(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max,
                            uint32_t *out_ids, float *out_scores, uint32_t *out_n) {
     return kmer_topk_checked(c, qmask, qoff, nq, max, out_ids, out_scores, out_n, true);
+}
+int sina_hip_kmer_topk_match(sina_hip_ctx *c, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t max,
+                             uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint16_t *out_match) {
+    if (!c || !q_ab || !q_off || !out_ids || !out_scores || !out_n || !out_match) SH_FAIL("kmer_topk_match: null argument");
+    if (match_check_queries("kmer_topk_match", q_ab, q_off, nq)) return 1;
+    // the mask bytes the count kernel reads, one per packed word; offsets from the first query's first base
+    const uint64_t b = q_off[0], e = q_off[nq];
+    std::vector<uint8_t> mask(e - b + 1);
+    for (uint64_t i = b; i < e; i++) mask[i - b] = (uint8_t)(q_ab[i] >> 24);
+    std::vector<uint64_t> rel(nq + 1);
+    for (uint32_t q = 0; q <= nq; q++) rel[q] = q_off[q] - b;
+    return kmer_topk_checked(c, mask.data(), rel.data(), nq, max, out_ids, out_scores, out_n, true, q_ab + b, out_match);
 }
 int sina_hip_kmer_scores(sina_hip_ctx *c, const uint8_t *qmask, uint32_t qlen, int16_t *scores) {
     return kmer_scores_checked(c, qmask, qlen, scores, false);

@@ -36,6 +36,9 @@ def load_host():
     H.sina_host_pipeline_destroy.argtypes = [vp]
     H.sina_host_pipeline_destroy.restype = None
     H.sina_host_pipeline_run.argtypes = [vp, capi.u8p, capi.u64p, C.c_uint32, C.c_uint32, C.c_uint32]
+    H.sina_host_pipeline_run_aligned.argtypes = [vp, capi.u32p, capi.u64p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32,
+                                                 C.c_uint32]
+    H.sina_host_store_match_stats.argtypes = [C.c_char_p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_pipeline_run_single_trays.argtypes = [vp, capi.u8p, capi.u64p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                       C.c_uint32, C.c_int32, capi.u8p, C.c_char_p, C.c_uint32]
     H.sina_host_result.argtypes = [vp, C.c_uint32] + [C.POINTER(C.c_int)] * 4 + [capi.u32p, capi.u32p]
@@ -237,6 +240,16 @@ class Store:
         _chk(self.H.sina_host_store_big_select_queries(self.key.encode(), C.byref(n)))
         return int(n.value)
 
+    def match_stats(self):
+        """The match-count kernel (famfinder's device-msc) on this store's contexts so far: dict(kernel_ms, pairs,
+        cand_bases, launches) -- between runs, like big_select_queries()."""
+        ms = C.c_double()
+        pairs, bases, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _chk(self.H.sina_host_store_match_stats(self.key.encode(), C.byref(ms), C.byref(pairs), C.byref(bases),
+                                                C.byref(launches)))
+        return dict(kernel_ms=float(ms.value), pairs=int(pairs.value), cand_bases=int(bases.value),
+                    launches=int(launches.value))
+
     def close(self):
         self.H.sina_host_store_close(self.key.encode())
 
@@ -280,6 +293,20 @@ class Pipeline:
         self.nq = len(qoff) - 1
         _chk(self.H.sina_host_pipeline_run(self.h, qmask.ctypes.data_as(capi.u8p), qoff.ctypes.data_as(capi.u64p),
                                            self.nq, batch, inflight))
+        return self.timings()
+
+    def run_aligned(self, q_ab, q_off, names, batch=1024, inflight=2):
+        """run() for ALIGNED queries under their own names: q_ab / q_off the packed aligned bases (column | mask << 24)
+        of every query, names[q] its name.  This is what reaches famfinder's identity filter (fs-msc-max) and
+        fs-leave-query-out -- a leave-out run takes its queries from the references themselves.  Results through
+        result(q)."""
+        q_ab = np.ascontiguousarray(q_ab, np.uint32)
+        q_off = np.ascontiguousarray(q_off, np.uint64)
+        self.nq = len(q_off) - 1
+        assert len(names) == self.nq
+        arr = (C.c_char_p * max(self.nq, 1))(*[n.encode() for n in names])
+        _chk(self.H.sina_host_pipeline_run_aligned(self.h, q_ab.ctypes.data_as(capi.u32p), q_off.ctypes.data_as(capi.u64p),
+                                                   arr, self.nq, batch, inflight))
         return self.timings()
 
     def run_single_trays(self, qmask, qoff, threads=32, max_batch=1024, linger_us=300, poison=-1):

@@ -79,6 +79,27 @@ int sina_hip_big_select_queries(sina_hip_ctx *, uint64_t *n) { *n = 0; return 0;
 int sina_hip_wide_queries(sina_hip_ctx *, uint64_t *n) { *n = 0; return 0; }
 int sina_hip_compare(sina_hip_ctx *, const uint32_t *, const uint64_t *, uint32_t, const uint32_t *, const uint64_t *,
                      int, int, sina_hip_match_counts *) { g_err = "stub"; return 1; }
+int sina_hip_match_count(sina_hip_ctx *, const uint32_t *, const uint64_t *, uint32_t, const uint32_t *, const uint64_t *,
+                          uint16_t *) { g_err = "stub"; return 1; }
+// (every candidate "matches" in three quarters of the query's bases: below any usual --fs-msc-max)
+int sina_hip_kmer_topk_match(sina_hip_ctx *c, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t max,
+                             uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint16_t *out_match) {
+    const uint64_t b = q_off[0];
+    std::vector<uint8_t> mask(q_off[nq] - b + 1);
+    std::vector<uint64_t> rel(nq + 1);
+    for (uint64_t i = b; i < q_off[nq]; i++) mask[i - b] = (uint8_t)(q_ab[i] >> 24);
+    for (uint32_t q = 0; q <= nq; q++) rel[q] = q_off[q] - b;
+    if (sina_hip_kmer_topk(c, mask.data(), rel.data(), nq, max, out_ids, out_scores, out_n)) return 1;
+    if (max > c->root->n_refs) max = c->root->n_refs;
+    for (uint32_t q = 0; q < nq; q++)
+        for (uint32_t x = 0; x < max; x++) out_match[(size_t)q * max + x] = (uint16_t)((rel[q + 1] - rel[q]) * 3 / 4);
+    return 0;
+}
+int sina_hip_match_stats(sina_hip_ctx *, double *ms, uint64_t *pairs, uint64_t *bases, uint64_t *launches) {
+    *ms = 0;
+    *pairs = *bases = *launches = 0;
+    return 0;
+}
 void sina_hip_align_params_default(sina_hip_align_params *p) {
     memset(p, 0, sizeof(*p));
     p->match_score = 2;
