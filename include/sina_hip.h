@@ -50,7 +50,7 @@ int sina_hip_init(int device, sina_hip_ctx **ctx);
  * store (upload_refs / build_index / upload_index fail on it); destroy forks before the parent,
  * and do not change the parent's store while forks are in use. */
 int sina_hip_fork(sina_hip_ctx *parent, sina_hip_ctx **ctx);
-/* Brings the scratch buffers ONE kind of call uses (0: k-mer search, 1: alignment, 2: search-stage comparison) to the
+/* Brings the scratch buffers ONE kind of call uses (0: k-mer search, 1: alignment, 2: search-stage comparison and ranking) to the
  * largest sizes any context of the store has needed for them so far: device allocations stall every stream of the
  * device, so a host that runs a pipeline makes its worker contexts, and warms them, before the run -- not in it
  * (the reference sizes its per-thread state the same way: one famfinder / aligner copy per worker, made before the
@@ -208,6 +208,60 @@ int sina_hip_match_count(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint64_t
 int sina_hip_kmer_topk_match(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t max,
                              uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint16_t *out_match);
 int sina_hip_match_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches);
+
+/* ------------------------------------------------------------- search stage: score and rank on the device
+ * What search_filter::operator() does with the counters above (src/search_filter.cpp:271-331): the score
+ * (float)match / denom of every candidate, denom the integer the cover rule picks (cseq_comparator::score,
+ * src/cseq_comparator.cpp:240-296; no Jukes-Cantor correction), and the max_result best by
+ * std::greater<result_item> (src/search.h:56-68): score descending, equal scores by the reference's NAME descending
+ * (byte-wise std::string order).  Only those rows come back.
+ *
+ * sina_hip_upload_name_order: rank[id] = position of reference id's name in ascending byte-wise order, n = the number
+ * of uploaded references.  Anything but a permutation of 0..n_refs-1 is refused before anything runs; a forked context
+ * cannot call it; sina_hip_upload_refs (and sina_hip_store_alloc_like) forget it.  The identity permutation gives
+ * "score descending, id descending", sina_hip_kmer_topk's own tie rule.
+ *
+ * sina_hip_compare_rank: arguments as sina_hip_compare's (sub-ranges of larger offset arrays included), plus
+ *   cand_ids == NULL : every reference of the store, in id order, for every query (cand_off is not read; no id list
+ *                      is uploaded)
+ *   cover_rule       : SINA_CMP_COVER_* (CMP_COVER_TYPE's order, src/cseq_comparator.h)
+ *   max_result       : 1..64 rows per query
+ *   out_ids, out_scores : [nq * max_result], row q best first; entries from out_n[q] on are 0
+ *   out_n            : [nq] min(max_result, candidates of q minus those left out)
+ *   out_flag         : [nq] bit 0: some candidate of q had denom == 0 (the host's 0 / 0 = NaN).  That candidate is
+ *                      left out; the caller ranks such a query itself, its rows are unspecified.
+ * Scores are the correctly rounded float32 quotient, bit for bit the host's.  A duplicated id in a list is allowed:
+ * both copies compete.  Refused with a message, before anything runs and with the outputs untouched: a null argument,
+ * a reference id out of range, max_result outside 1..64, an unknown rule, no name order uploaded, a query whose columns
+ * do not ascend strictly, a query of more than 65535 bases.  An alignment too wide for the kernel's LDS tables is
+ * refused as a limit (sina_hip_last_error_is_limit() == 1).
+ *
+ * sina_hip_kmer_topk_rank: to sina_hip_compare_rank what sina_hip_kmer_topk_match is to sina_hip_match_count -- the
+ * queries as packed aligned bases, the k-mer search sina_hip_kmer_topk_any's for their mask bytes with
+ * max = kmer_candidates, and the candidates ranked from the select's id rows where they lie in device memory: no id
+ * and no k-mer score crosses the bus.  More than 4096 candidates per query (min(kmer_candidates, n_refs)) are refused as
+ * a limit.
+ *
+ * sina_hip_rank_stats: the rank (and merge) kernels' own time (events around their launches) and volume on this
+ * context since init / fork: pairs scored, bases of their candidates, launches. */
+#define SINA_CMP_COVER_ABS 0
+#define SINA_CMP_COVER_QUERY 1
+#define SINA_CMP_COVER_TARGET 2
+#define SINA_CMP_COVER_OVERLAP 3
+#define SINA_CMP_COVER_ALL 4
+#define SINA_CMP_COVER_AVERAGE 5
+#define SINA_CMP_COVER_MIN 6
+#define SINA_CMP_COVER_MAX 7
+#define SINA_CMP_COVER_NOGAP 8
+int sina_hip_upload_name_order(sina_hip_ctx *ctx, const uint32_t *rank, uint32_t n);
+int sina_hip_compare_rank(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq,
+                          const uint32_t *cand_ids, const uint64_t *cand_off, int iupac_rule, int filter_lowercase,
+                          int cover_rule, uint32_t max_result, uint32_t *out_ids, float *out_scores, uint32_t *out_n,
+                          uint32_t *out_flag);
+int sina_hip_kmer_topk_rank(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq,
+                            uint32_t kmer_candidates, int iupac_rule, int filter_lowercase, int cover_rule,
+                            uint32_t max_result, uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint32_t *out_flag);
+int sina_hip_rank_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches);
 
 /* ------------------------------------------------------------- alignment
  * Replaces, for a batch of queries: mseq::mseq + sort + reduce_edges

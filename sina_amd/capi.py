@@ -34,7 +34,12 @@ ABI_SYMBOLS = [
     "sina_hip_kmer_topk_any", "sina_hip_kmer_scores_any", "sina_hip_long_queries", "sina_hip_big_select_queries",
     "sina_hip_align_graphs_wsets", "sina_hip_align_families_wsets",
     "sina_hip_match_count", "sina_hip_kmer_topk_match", "sina_hip_match_stats",
+    "sina_hip_upload_name_order", "sina_hip_compare_rank", "sina_hip_kmer_topk_rank", "sina_hip_rank_stats",
 ]
+
+# include/sina_hip.h: SINA_CMP_COVER_*, in CMP_COVER_TYPE's order
+COVER_RULES = ("abs", "query", "target", "overlap", "all", "average", "min", "max", "nogap")
+RANK_MAX_RESULT = 64
 
 # include/sina_hip.h: the fast k-mer / DP paths' query limit, the _any k-mer entries' limit, and the number of k-mer
 # windows (by the index of their last base) the long count kernel takes per chunk
@@ -142,6 +147,12 @@ def load():
     L.sina_hip_match_count.argtypes = [vp, u32p, u64p, C.c_uint32, u32p, u64p, u16p]
     L.sina_hip_kmer_topk_match.argtypes = [vp, u32p, u64p, C.c_uint32, C.c_uint32, u32p, f32p, u32p, u16p]
     L.sina_hip_match_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
+    L.sina_hip_upload_name_order.argtypes = [vp, u32p, C.c_uint32]
+    L.sina_hip_compare_rank.argtypes = [vp, u32p, u64p, C.c_uint32, u32p, u64p, C.c_int, C.c_int, C.c_int, C.c_uint32, u32p, f32p,
+                                        u32p, u32p]
+    L.sina_hip_kmer_topk_rank.argtypes = [vp, u32p, u64p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32, u32p,
+                                          f32p, u32p, u32p]
+    L.sina_hip_rank_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
     L.sina_hip_last_error_is_limit.restype = C.c_int
     L.sina_hip_debug_mesh_wide.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
                                            u32p, u32p, f32p]
@@ -431,6 +442,59 @@ class Context:
         ms = C.c_double()
         pairs, bases, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.sina_hip_match_stats(self.h, C.byref(ms), C.byref(pairs), C.byref(bases), C.byref(launches)))
+        return dict(kernel_ms=float(ms.value), pairs=int(pairs.value), cand_bases=int(bases.value), launches=int(launches.value))
+
+    def upload_name_order(self, rank):
+        """rank[id] = position of reference id's name in ascending byte-wise order (a permutation of 0..n_refs-1)."""
+        rank = _c(rank, np.uint32)
+        self._check(self.L.sina_hip_upload_name_order(self.h, _ptr(rank, u32p), len(rank)))
+
+    @staticmethod
+    def _cover(cover):
+        return COVER_RULES.index(cover) if isinstance(cover, str) else int(cover)
+
+    def compare_rank(self, q_ab, q_off, cand_ids, cand_off, iupac=0, filter_lc=False, cover="query", max_result=10, out=None):
+        """Search-stage comparison, scored and ranked on the device: (ids uint32 [nq, max_result], scores float32
+        [nq, max_result], n uint32 [nq], flag uint32 [nq]).  cand_ids None: every reference for every query.
+        out: the four arrays to write into (a test of "outputs untouched")."""
+        q_ab = _c(q_ab, np.uint32)
+        q_off = _c(q_off, np.uint64)
+        nq = len(q_off) - 1
+        rows = max(int(max_result), 1)
+        ids, sc, n, flag = out if out is not None else (np.zeros((nq, rows), np.uint32), np.zeros((nq, rows), np.float32),
+                                                        np.zeros(nq, np.uint32), np.zeros(nq, np.uint32))
+        if cand_ids is None:
+            cp, op = None, None
+        else:
+            cand_ids = _c(cand_ids, np.uint32)
+            cand_off = _c(cand_off, np.uint64)
+            cp, op = _ptr(cand_ids, u32p), _ptr(cand_off, u64p)
+        self._check(self.L.sina_hip_compare_rank(self.h, _ptr(q_ab, u32p), _ptr(q_off, u64p), nq, cp, op, int(iupac), int(filter_lc),
+                                                 self._cover(cover), int(max_result), _ptr(ids, u32p), _ptr(sc, f32p),
+                                                 _ptr(n, u32p), _ptr(flag, u32p)))
+        return ids, sc, n, flag
+
+    def kmer_topk_rank(self, q_ab, q_off, kmer_candidates, iupac=0, filter_lc=False, cover="query", max_result=10):
+        """kmer_topk_any for queries given as packed aligned bases, its candidates ranked as compare_rank ranks them,
+        from the select's id rows on the device: (ids, scores, n, flag) as compare_rank's."""
+        q_ab = _c(q_ab, np.uint32)
+        q_off = _c(q_off, np.uint64)
+        nq = len(q_off) - 1
+        rows = max(int(max_result), 1)
+        ids = np.zeros((nq, rows), np.uint32)
+        sc = np.zeros((nq, rows), np.float32)
+        n = np.zeros(nq, np.uint32)
+        flag = np.zeros(nq, np.uint32)
+        self._check(self.L.sina_hip_kmer_topk_rank(self.h, _ptr(q_ab, u32p), _ptr(q_off, u64p), nq, int(kmer_candidates), int(iupac),
+                                                   int(filter_lc), self._cover(cover), int(max_result), _ptr(ids, u32p),
+                                                   _ptr(sc, f32p), _ptr(n, u32p), _ptr(flag, u32p)))
+        return ids, sc, n, flag
+
+    def rank_stats(self):
+        """The rank kernels on this context so far: dict(kernel_ms, pairs, cand_bases, launches)."""
+        ms = C.c_double()
+        pairs, bases, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.sina_hip_rank_stats(self.h, C.byref(ms), C.byref(pairs), C.byref(bases), C.byref(launches)))
         return dict(kernel_ms=float(ms.value), pairs=int(pairs.value), cand_bases=int(bases.value), launches=int(launches.value))
 
     def align_families(self, fam_ids, fam_off, qmask, qoff, params=None):

@@ -432,6 +432,7 @@ int sina_hip_upload_refs(sina_hip_ctx *c, const uint32_t *ab, const uint64_t *of
     c->st->width = width;
     c->st->total_bases = total;
     c->st->have_refs = true;
+    c->st->have_name_order = false;  // (sina_hip_upload_name_order: the order belonged to the references before)
     return 0;
 }
 

@@ -27,6 +27,10 @@ struct sina_hip_store {
     sina_hip::DevBuf dense_id, dense_bits;  // u32 [4^k]: bitmap number or ~0; u32 [n_dense][dense_words]
     uint32_t n_dense = 0, dense_words = 0;
     std::atomic<bool> dense_ready{false};
+    // The references' name order for the rank kernel (rank.hip, sina_hip_upload_name_order): u32 [n_refs] position of
+    // every reference's name in ascending order, and its inverse; forgotten when the references change
+    sina_hip::DevBuf name_rank, name_inv;
+    bool have_name_order = false;
     std::mutex aux_mu;
     std::mutex stats_mu;
     // The device-filling kernels of all contexts (k-mer count/select, DAG build, DP) go through ONE
@@ -136,6 +140,11 @@ struct sina_hip_ctx {
     sina_hip::DevBuf m_out, m_n;
     double match_ms = 0;
     uint64_t match_pairs = 0, match_bases = 0, match_launches = 0;
+    // the rank kernel (rank.hip): the chunks' key rows, the final rows on their way to the host, the flags and the
+    // volume counters the kernel keeps; its own time and volume on this context (sina_hip_rank_stats)
+    sina_hip::DevBuf r_keys, r_ids, r_scores, r_n, r_flag, r_cnt;
+    double rank_ms = 0;
+    uint64_t rank_pairs = 0, rank_bases = 0, rank_launches = 0;
     sina_hip::HostBuf h_out, h_out_pos;  // pinned staging for the DP results
     // h_out_pos holds the aligned columns of a whole align call (laid out like the caller's out_pos): a launch
     // range writes at DpLaunch::out_pos_base, callers that pass no out_pos read them here (sina_hip_staged_out_pos)
@@ -145,7 +154,7 @@ struct sina_hip_ctx {
 
     size_t lds_budget = 0;  // LDS per DP workgroup; 0 = what keeps the register-limited occupancy (dp_default_lds_budget)
 
-    static constexpr int kNumScratch = 42;
+    static constexpr int kNumScratch = 48;
     static_assert(kNumScratch <= 64, "sina_hip_store::cap_hint is too short");
     void scratch(sina_hip::DevBuf **all) {
         sina_hip::DevBuf *list[kNumScratch] = {&qd, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &res,
@@ -153,7 +162,8 @@ struct sina_hip_ctx {
                                                &k_out_scores, &k_out_n, &k_tmp0, &k_tmp1, &k_tmp2, &g_fam_ids,
                                                &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &order,
                                                &s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &edge, &prof16, &self16, &rgain,
-                                               &scout, &scout_u, &wset, &m_out, &m_n};
+                                               &scout, &scout_u, &wset, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag,
+                                               &r_cnt};
         for (int i = 0; i < kNumScratch; i++) all[i] = list[i];
     }
     void publish_hints() {  // after a call: remember how big my buffers had to be
@@ -178,11 +188,12 @@ struct sina_hip_ctx {
     // What one KIND of call uses, brought to the hinted sizes now (sina_hip_prewarm): 0 k-mer search,
     // 1 alignment (DAG build, DP, walk), 2 search-stage comparison.
     int prewarm(int kind) {
-        sina_hip::DevBuf *search[] = {&k_qoff, &k_scores, &k_out_ids, &k_out_scores, &k_out_n, &k_tmp0, &k_tmp1, &k_tmp2, &qmask};
+        sina_hip::DevBuf *search[] = {&k_qoff, &k_scores, &k_out_ids, &k_out_scores, &k_out_n, &k_tmp0, &k_tmp1, &k_tmp2, &qmask,
+                                      &s_qab, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};  // (s_qab, r_*: sina_hip_kmer_topk_rank)
         sina_hip::DevBuf *align[] = {&qd, &order, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &edge, &res, &weights, &out,
                                      &out_pos, &g_fam_ids, &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &rgain, &scout, &scout_u,
                                      &prof16, &self16, &wset};
-        sina_hip::DevBuf *compare[] = {&s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &m_out, &m_n};
+        sina_hip::DevBuf *compare[] = {&s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};
         sina_hip::DevBuf **list = kind == 0 ? search : (kind == 1 ? align : compare);
         const size_t n = kind == 0 ? sizeof search / sizeof *search : (kind == 1 ? sizeof align / sizeof *align : sizeof compare / sizeof *compare);
         for (size_t i = 0; i < n; i++) {
@@ -220,6 +231,8 @@ struct sina_hip_ctx {
             st->idx_ids.release();
             st->dense_id.release();
             st->dense_bits.release();
+            st->name_rank.release();
+            st->name_inv.release();
             for (auto &pl : st->tb_pool.plane) pl.release();
             delete st;
         }
@@ -621,6 +634,18 @@ int match_launch(sina_hip_ctx *c, const uint32_t *d_qab, const uint64_t *d_qoff,
                  const uint32_t *d_n, uint32_t stride, uint16_t *d_out, const uint32_t *h_ids, const uint32_t *h_n);
 // fails unless every query has at most 65535 bases in strictly ascending columns
 int match_check_queries(const char *who, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq);
+}  // namespace sina_hip
+
+namespace sina_hip {
+// ---- the rank kernel (rank.hip): the N best candidates of nq queries (packed aligned bases d_qab at d_qoff[q], device
+// memory; none longer than max_la) under the given rules.  A query's candidates: d_ids + d_coff (lists), d_ids + d_rown
+// with `stride` (rows as the k-mer select leaves them; 0xFFFFFFFF = 0), or neither (every reference); M: the most any
+// query has.  Rows into out_ids / out_scores [nq * N], out_n / out_flag [nq] on the host; returns when they are there.
+int rank_launch(sina_hip_ctx *c, const uint32_t *d_qab, const uint64_t *d_qoff, uint32_t nq, const uint32_t *d_ids,
+                const uint64_t *d_coff, const uint32_t *d_rown, uint32_t stride, uint32_t M, uint32_t max_la, int iupac,
+                int filter_lc, int cover, uint32_t N, uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint32_t *out_flag);
+// fails on an unknown rule, max_result outside 1..64, a store without references or without a name order
+int rank_check_rules(const char *who, sina_hip_ctx *c, int iupac_rule, int cover_rule, uint32_t max_result);
 }  // namespace sina_hip
 
 // publishes the context's scratch capacities when an API call ends (see sina_hip_store::cap_hint)

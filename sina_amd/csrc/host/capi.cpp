@@ -362,6 +362,17 @@ int sina_host_store_match_stats(const char *key, double *kernel_ms, uint64_t *pa
         return fail(e);
     }
 }
+// search_filter's device-rank on this store: queries ranked on the device, queries sent back to the host path, and the
+// rank kernel's time and volume (sina_hip_rank_stats) on its contexts -- between runs, like the counters above
+int sina_host_store_rank_stats(const char *key, uint64_t *ranked, uint64_t *fallen_back, double *kernel_ms, uint64_t *pairs,
+                               uint64_t *cand_bases, uint64_t *launches) {
+    try {
+        reference_store::get(key)->rank_stats(ranked, fallen_back, kernel_ms, pairs, cand_bases, launches);
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
 int sina_host_store_build_index(const char *key, unsigned k, int nofast) {
     try {
         reference_store::get(key)->ensure_index(k, nofast != 0);

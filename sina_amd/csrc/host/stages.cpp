@@ -9,6 +9,7 @@
 #include "id_order.h"
 #include "../kmer_plan.h"
 #include "../match_plan.h"
+#include "../rank_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -615,6 +616,50 @@ void reference_store::match_stats(double *kernel_ms, uint64_t *pairs, uint64_t *
         double ms = 0;
         uint64_t p = 0, b = 0, l = 0;
         hip_check(sina_hip_match_stats(c, &ms, &p, &b, &l), "sina_hip_match_stats");
+        *kernel_ms += ms;
+        *pairs += p;
+        *cand_bases += b;
+        *launches += l;
+    };
+    add(root);
+    for (auto &pool : idle_forks)
+        for (sina_hip_ctx *c : pool) add(c);
+}
+bool reference_store::name_order_ready() {
+    int state = name_order_state.load(std::memory_order_acquire);
+    if (state == 0) {
+        sina_hip_ctx *root = device();
+        std::lock_guard<std::mutex> lk(gpu_mu);
+        state = name_order_state.load(std::memory_order_relaxed);
+        if (state == 0) {
+            const uint32_t n = (uint32_t)seqs.size();
+            std::vector<uint32_t> by_name(n), rank(n);
+            for (uint32_t i = 0; i < n; i++) by_name[i] = i;
+            std::sort(by_name.begin(), by_name.end(), [&](uint32_t a, uint32_t b) { return seqs[a].getName() < seqs[b].getName(); });
+            bool unique = true;
+            for (uint32_t i = 0; i < n; i++) {
+                rank[by_name[i]] = i;
+                if (i && seqs[by_name[i]].getName() == seqs[by_name[i - 1]].getName()) unique = false;
+            }
+            if (unique) hip_check(sina_hip_upload_name_order(root, rank.data(), n), "sina_hip_upload_name_order");
+            state = unique ? 1 : 2;
+            name_order_state.store(state, std::memory_order_release);
+        }
+    }
+    return state == 1;
+}
+void reference_store::rank_stats(uint64_t *ranked, uint64_t *fallen_back, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases,
+                                 uint64_t *launches) {
+    sina_hip_ctx *root = device();
+    std::lock_guard<std::mutex> lk(gpu_mu);
+    *ranked = n_ranked.load(std::memory_order_relaxed);
+    *fallen_back = n_rank_host.load(std::memory_order_relaxed);
+    *kernel_ms = 0;
+    *pairs = *cand_bases = *launches = 0;
+    auto add = [&](sina_hip_ctx *c) {
+        double ms = 0;
+        uint64_t p = 0, b = 0, l = 0;
+        hip_check(sina_hip_rank_stats(c, &ms, &p, &b, &l), "sina_hip_rank_stats");
         *kernel_ms += ms;
         *pairs += p;
         *cand_bases += b;
@@ -2689,6 +2734,7 @@ struct search_filter::options {
     std::string copy_fields;
     std::vector<std::string> v_copy_fields;
     cseq_comparator comparator;
+    bool device_rank;  // the candidates scored and ranked on the device, only the max_result best coming down (default off)
 };
 search_filter::options *search_filter::opts = nullptr;
 
@@ -2702,6 +2748,7 @@ static search_filter::options sf_defaults() {  // src/search_filter.cpp:91-126, 
     o.ignore_super = false;
     o.max_result = 10;
     o.lca_quorum = .7f;
+    o.device_rank = false;
     return o;
 }
 static search_filter::options &sf_opts() {
@@ -2726,6 +2773,7 @@ void search_filter::set_option(const std::string &name, const std::string &value
     else if (name == "search-kmer-len") o.fs_kmer_len = std::stoi(value);
     else if (name == "search-ignore-super") o.ignore_super = to_bool(value);
     else if (name == "search-copy-fields") o.copy_fields = value;
+    else if (name == "device-rank") o.device_rank = to_bool(value);
     else if (name == "search-iupac") {  // validate(), cseq_comparator.cpp:301-318: istarts_with(name, value)
         auto starts = [&](const char *full) { return !v.empty() && std::string(full).compare(0, v.size(), v) == 0; };
         if (starts("optimistic")) o.comparator.iupac_rule = CMP_IUPAC_OPTIMISTIC;
@@ -2789,6 +2837,8 @@ search_filter::search_filter() : data(new priv_data) {
     if (o.pt_database.empty()) throw std::logic_error("need search-db to search");
     data->arb = reference_store::get(o.pt_database);
     if (!o.search_all) data->index = kmer_search::get_kmer_search(o.pt_database, o.fs_kmer_len, o.fs_no_fast);
+    // device-rank: the store's name order, computed and uploaded once (a store filled by broadcast: by the first batch)
+    if (o.device_rank && !data->arb->filled_by_broadcast()) data->arb->name_order_ready();
 }
 search_filter::search_filter(const search_filter &) = default;
 search_filter &search_filter::operator=(const search_filter &) = default;
@@ -2852,7 +2902,8 @@ std::string lca_vote(const std::vector<std::vector<std::string>> &paths, size_t 
 }  // namespace
 
 // src/search_filter.cpp:244-412 for a batch of trays: the k-mer search and the comparisons of the
-// whole batch are one GPU call each (sina_hip_kmer_topk, sina_hip_compare).
+// whole batch are one GPU call each (sina_hip_kmer_topk, sina_hip_compare) -- or, with device-rank, one call for
+// both that brings down the max_result best only (sina_hip_kmer_topk_rank; search-all: sina_hip_compare_rank).
 void search_filter::operator()(std::vector<tray> &batch) {
     const options &o = sf_opts();
     reference_store &st = *data->arb;
@@ -2871,107 +2922,225 @@ void search_filter::operator()(std::vector<tray> &batch) {
         idx.push_back(i);
     }
     if (idx.empty()) return;
-    const size_t nq = idx.size();
     const unsigned n_refs = st.size();
 
-    // ---- candidates
-    std::vector<search::result_vector> cand(nq);
-    if (!o.search_all) {
-        scoped_phase ph("sf.find_batch");
-        std::vector<const cseq *> qs(nq);
-        for (size_t x = 0; x < nq; x++) qs[x] = batch[idx[x]].aligned_sequence;
-        data->index->find_batch(qs, cand, (unsigned)o.kmer_candidates);
-        if (o.ignore_super) {  // sic: partition() moves the containing ones to the front and the REST is erased
-            parallel_for(nq, [&](size_t x) {
-                const cseq &c = *batch[idx[x]].aligned_sequence;
-                search::result_vector kept;
-                for (auto &r : cand[x])
-                    if (contains_query(*r.sequence, c)) kept.push_back(r);
-                cand[x].swap(kept);
-            });
-        }
-    }
-
-    // ---- scores: one comparison launch per slice of the batch
-    {
-        scoped_phase ph("sf.compare(C-ABI)");
-        auto dev = st.worker_device(reference_store::dev_compare);
-        const uint64_t max_pairs = 8u << 20;
-        size_t x0 = 0;
-        while (x0 < nq) {
-            size_t x1 = x0;
-            uint64_t pairs = 0;
-            while (x1 < nq) {
-                const uint64_t k = o.search_all ? n_refs : cand[x1].size();
-                if (x1 > x0 && pairs + k > max_pairs) break;
-                pairs += k;
-                x1++;
+    // ---- candidates, scores and ranking on the host: fills the search_result of trays `sub` (indices into batch)
+    auto host_rank = [&](const std::vector<size_t> &sub) {
+        const size_t nq = sub.size();
+        if (nq == 0) return;
+        std::vector<search::result_vector> cand(nq);
+        if (!o.search_all) {
+            scoped_phase ph("sf.find_batch");
+            std::vector<const cseq *> qs(nq);
+            for (size_t x = 0; x < nq; x++) qs[x] = batch[sub[x]].aligned_sequence;
+            data->index->find_batch(qs, cand, (unsigned)o.kmer_candidates);
+            if (o.ignore_super) {  // sic: partition() moves the containing ones to the front and the REST is erased
+                parallel_for(nq, [&](size_t x) {
+                    const cseq &c = *batch[sub[x]].aligned_sequence;
+                    search::result_vector kept;
+                    for (auto &r : cand[x])
+                        if (contains_query(*r.sequence, c)) kept.push_back(r);
+                    cand[x].swap(kept);
+                });
             }
-            if (pairs) {  // (a slice without a single candidate is not sent -- and has no scores to take)
-                const pair_counts pc = compare_packed(
-                    dev.get(), x1 - x0, [&](size_t x) -> const cseq & { return *batch[idx[x0 + x]].aligned_sequence; },
-                    [&](size_t x) { return o.search_all ? (size_t)n_refs : cand[x0 + x].size(); },
-                    [&](size_t x, uint32_t *dst) {
+        }
+
+        // ---- scores: one comparison launch per slice of the batch
+        {
+            scoped_phase ph("sf.compare(C-ABI)");
+            auto dev = st.worker_device(reference_store::dev_compare);
+            const uint64_t max_pairs = 8u << 20;
+            size_t x0 = 0;
+            while (x0 < nq) {
+                size_t x1 = x0;
+                uint64_t pairs = 0;
+                while (x1 < nq) {
+                    const uint64_t k = o.search_all ? n_refs : cand[x1].size();
+                    if (x1 > x0 && pairs + k > max_pairs) break;
+                    pairs += k;
+                    x1++;
+                }
+                if (pairs) {  // (a slice without a single candidate is not sent -- and has no scores to take)
+                    const pair_counts pc = compare_packed(
+                        dev.get(), x1 - x0, [&](size_t x) -> const cseq & { return *batch[sub[x0 + x]].aligned_sequence; },
+                        [&](size_t x) { return o.search_all ? (size_t)n_refs : cand[x0 + x].size(); },
+                        [&](size_t x, uint32_t *dst) {
+                            if (o.search_all) {
+                                for (unsigned r = 0; r < n_refs; r++) dst[r] = r;
+                            } else {
+                                for (size_t r = 0; r < cand[x0 + x].size(); r++) dst[r] = st.id_of(cand[x0 + x][r].sequence);
+                            }
+                        },
+                        (int)o.comparator.iupac_rule, o.comparator.filter_lc_rule ? 1 : 0);
+                    for (size_t x = x0; x < x1; x++) {
+                        const sina_hip_match_counts *m = pc.counts.data() + pc.coff[x - x0];
                         if (o.search_all) {
-                            for (unsigned r = 0; r < n_refs; r++) dst[r] = r;
+                            cand[x].clear();
+                            cand[x].reserve(n_refs);
+                            for (unsigned r = 0; r < n_refs; r++) cand[x].emplace_back(o.comparator.score(m[r]), &st.getCseq(r));
                         } else {
-                            for (size_t r = 0; r < cand[x0 + x].size(); r++) dst[r] = st.id_of(cand[x0 + x][r].sequence);
+                            for (size_t r = 0; r < cand[x].size(); r++) cand[x][r].score = o.comparator.score(m[r]);
                         }
-                    },
-                    (int)o.comparator.iupac_rule, o.comparator.filter_lc_rule ? 1 : 0);
-                for (size_t x = x0; x < x1; x++) {
-                    const sina_hip_match_counts *m = pc.counts.data() + pc.coff[x - x0];
-                    if (o.search_all) {
-                        cand[x].clear();
-                        cand[x].reserve(n_refs);
-                        for (unsigned r = 0; r < n_refs; r++) cand[x].emplace_back(o.comparator.score(m[r]), &st.getCseq(r));
-                    } else {
-                        for (size_t r = 0; r < cand[x].size(); r++) cand[x][r].score = o.comparator.score(m[r]);
                     }
                 }
+                x0 = x1;
             }
-            x0 = x1;
+        }
+
+        // ---- ranking, per tray
+        scoped_phase ph("sf.rank+lca");
+        parallel_for(nq, [&](size_t x) {
+            tray &t = batch[sub[x]];
+            cseq *c = t.aligned_sequence;
+            auto &vc = *t.search_result;
+            if (o.search_all) {
+                // every reference was compared: the `max_result` best that are not super-strings of the
+                // query (--search-ignore-super), if above --search-min-sim (behaviour of src/
+                // search_filter.cpp:271-296).  The sequence of libstdc++ calls is the contract here:
+                // the window is re-sorted from the first kept candidate to the PREVIOUS window end, then
+                // widened again, so std::partition also sees entries std::partial_sort left unordered.
+                search::result_vector &all = cand[x];
+                const auto stop = all.end();
+                auto first_kept = all.begin();
+                auto window_end = first_kept + (std::ptrdiff_t)std::min<size_t>((size_t)o.max_result, all.size());
+                for (;;) {
+                    std::partial_sort(first_kept, window_end, stop, std::greater<search::result_item>());
+                    if (o.ignore_super) {
+                        window_end = first_kept + (std::ptrdiff_t)std::min<size_t>((size_t)o.max_result, (size_t)(stop - first_kept));
+                        first_kept = std::partition(first_kept, window_end, [&](search::result_item &item) {
+                            return contains_query(*item.sequence, *c);
+                        });
+                    }
+                    const bool window_full = first_kept + o.max_result <= window_end;
+                    if (window_end == stop || window_full) break;
+                }
+                for (auto it = first_kept; it != window_end && it->score > o.min_sim; ++it) vc.push_back(*it);
+            } else {  // :297-331
+                vc.swap(cand[x]);
+                auto it = vc.begin();
+                auto middle = vc.begin() + std::min<size_t>((size_t)o.max_result, vc.size());
+                auto end = vc.end();
+                std::partial_sort(it, middle, end, std::greater<search::result_item>());
+                while (it != middle && it->score > o.min_sim) ++it;
+                vc.erase(it, vc.end());
+            }
+        });
+    };
+
+    // ---- device-rank: score and rank on the device, the rows above min-sim into search_result.  The whole stage
+    // keeps the host path for what the device does not rank as the host does (Jukes-Cantor: rounding can merge ratios
+    // into ties; ignore-super; more rows than a wave has lanes; names that repeat; more k-mer candidates than the LDS
+    // select sorts) and when the device refuses as a limit; a query of a call goes back to it, alone, when the device
+    // flags a 0 / 0 among its candidates or cannot take the query as it is.  Nothing of this reaches a tray's log.
+    std::vector<size_t> host_trays;
+    bool on_device = o.device_rank && o.comparator.dist_rule == CMP_DIST_NONE && !o.ignore_super && o.max_result >= 1 &&
+                     o.max_result <= (int)sina_hip::kRankMaxResult &&
+                     (o.search_all || std::min<uint64_t>((uint64_t)std::max(o.kmer_candidates, 0), n_refs) <= sina_hip::kKmerSelMax) &&
+                     st.name_order_ready();
+    if (on_device) {
+        std::vector<size_t> dev_trays;  // (the device takes strictly ascending columns, at most 65535 bases)
+        for (size_t i : idx) {
+            const cseq &c = *batch[i].aligned_sequence;
+            (c.size() <= 65535 && columns_ascend(c) ? dev_trays : host_trays).push_back(i);
+        }
+        const size_t nd = dev_trays.size();
+        const uint32_t N = (uint32_t)o.max_result;
+        std::vector<uint64_t> qoff(nd + 1, 0);
+        for (size_t x = 0; x < nd; x++) qoff[x + 1] = qoff[x] + batch[dev_trays[x]].aligned_sequence->size();
+        std::vector<uint32_t> qab(qoff.back() + 1);
+        parallel_for(nd, [&](size_t x) {
+            const cseq &c = *batch[dev_trays[x]].aligned_sequence;
+            memcpy(qab.data() + qoff[x], c.packed(), 4 * (size_t)c.size());
+        });
+        // rows of the distinct queries (identical queries are sent once, as find_batch sends them)
+        std::vector<uint32_t> rep, slot_of(nd), firsts;
+        const size_t nu = group_equal_items(
+            nd, [&](size_t i) { return hash_ends(qab.data() + qoff[i], 4 * (qoff[i + 1] - qoff[i]), qoff[i + 1] - qoff[i]); },
+            [&](size_t a, size_t b) {
+                return qoff[a + 1] - qoff[a] == qoff[b + 1] - qoff[b] &&
+                       memcmp(qab.data() + qoff[a], qab.data() + qoff[b], 4 * (qoff[a + 1] - qoff[a])) == 0;
+            },
+            rep);
+        std::vector<uint64_t> uoff(nu + 1, 0);
+        for (size_t i = 0; i < nd; i++) {
+            if (rep[i] == i) {
+                slot_of[i] = (uint32_t)firsts.size();
+                uoff[firsts.size() + 1] = uoff[firsts.size()] + (qoff[i + 1] - qoff[i]);
+                firsts.push_back((uint32_t)i);
+            } else {
+                slot_of[i] = slot_of[rep[i]];
+            }
+        }
+        std::vector<uint32_t> uab_store;
+        const uint32_t *uab = qab.data();
+        if (nu != nd) {
+            uab_store.resize(uoff.back() + 1);
+            parallel_for(nu, [&](size_t u) { memcpy(uab_store.data() + uoff[u], qab.data() + qoff[firsts[u]], 4 * (uoff[u + 1] - uoff[u])); });
+            uab = uab_store.data();
+        }
+        std::vector<uint32_t> ids(nu * N + 1), cnt(nu + 1), flag(nu + 1);
+        std::vector<float> sc(nu * N + 1);
+        bool limit = false;
+        auto call = [&](int rc, const char *what) {  // a limit sends the stage back to the host path; anything else is an error
+            if (rc == 0) return true;
+            if (sina_hip_last_error_is_limit() != 1) hip_check(rc, what);
+            limit = true;
+            return false;
+        };
+        if (nu) {
+            scoped_phase ph("sf.device_rank(C-ABI)");
+            if (!o.search_all) {
+                st.ensure_index((unsigned)o.fs_kmer_len, o.fs_no_fast);
+                auto dev = st.worker_device(reference_store::dev_search);
+                call(sina_hip_kmer_topk_rank(dev.get(), uab, uoff.data(), (uint32_t)nu, (uint32_t)o.kmer_candidates,
+                                             (int)o.comparator.iupac_rule, o.comparator.filter_lc_rule ? 1 : 0, (int)o.comparator.cover_rule,
+                                             N, ids.data(), sc.data(), cnt.data(), flag.data()),
+                     "sina_hip_kmer_topk_rank");
+            } else {
+                auto dev = st.worker_device(reference_store::dev_compare);
+                const uint64_t max_pairs = 8u << 20;  // (slices as the host path cuts them)
+                const size_t per = (size_t)std::max<uint64_t>(1, max_pairs / std::max(n_refs, 1u));
+                for (size_t u0 = 0; u0 < nu && !limit; u0 += per) {
+                    const size_t u1 = std::min(nu, u0 + per);
+                    call(sina_hip_compare_rank(dev.get(), uab, uoff.data() + u0, (uint32_t)(u1 - u0), nullptr, nullptr,
+                                               (int)o.comparator.iupac_rule, o.comparator.filter_lc_rule ? 1 : 0,
+                                               (int)o.comparator.cover_rule, N, ids.data() + u0 * N, sc.data() + u0 * N, cnt.data() + u0,
+                                               flag.data() + u0),
+                         "sina_hip_compare_rank");
+                }
+            }
+        }
+        if (limit) {
+            on_device = false;
+        } else {
+            uint64_t ranked = 0;
+            for (size_t x = 0; x < nd; x++) {
+                const size_t u = slot_of[x];
+                if (flag[u] & 1u) {
+                    host_trays.push_back(dev_trays[x]);
+                    continue;
+                }
+                auto &vc = *batch[dev_trays[x]].search_result;
+                for (uint32_t r = 0; r < cnt[u] && sc[u * N + r] > o.min_sim; r++) vc.emplace_back(sc[u * N + r], &st.getCseq(ids[u * N + r]));
+                ranked++;
+            }
+            st.count_ranked(ranked, host_trays.size());
+            // (a flagged query "alone, in a call of its own": its candidates hold the NaN the host orders as it does)
+            std::sort(host_trays.begin(), host_trays.end());
+            for (size_t i : host_trays) host_rank(std::vector<size_t>{i});
         }
     }
+    if (!on_device) {
+        if (o.device_rank) st.count_ranked(0, idx.size());
+        host_rank(idx);
+    }
 
-    // ---- ranking + attributes, per tray
+    // ---- attributes, per tray
     scoped_phase ph("sf.rank+lca");
-    parallel_for(nq, [&](size_t x) {
+    parallel_for(idx.size(), [&](size_t x) {
         tray &t = batch[idx[x]];
         cseq *c = t.aligned_sequence;
         auto &vc = *t.search_result;
-        if (o.search_all) {
-            // every reference was compared: the `max_result` best that are not super-strings of the
-            // query (--search-ignore-super), if above --search-min-sim (behaviour of src/
-            // search_filter.cpp:271-296).  The sequence of libstdc++ calls is the contract here:
-            // the window is re-sorted from the first kept candidate to the PREVIOUS window end, then
-            // widened again, so std::partition also sees entries std::partial_sort left unordered.
-            search::result_vector &all = cand[x];
-            const auto stop = all.end();
-            auto first_kept = all.begin();
-            auto window_end = first_kept + (std::ptrdiff_t)std::min<size_t>((size_t)o.max_result, all.size());
-            for (;;) {
-                std::partial_sort(first_kept, window_end, stop, std::greater<search::result_item>());
-                if (o.ignore_super) {
-                    window_end = first_kept + (std::ptrdiff_t)std::min<size_t>((size_t)o.max_result, (size_t)(stop - first_kept));
-                    first_kept = std::partition(first_kept, window_end, [&](search::result_item &item) {
-                        return contains_query(*item.sequence, *c);
-                    });
-                }
-                const bool window_full = first_kept + o.max_result <= window_end;
-                if (window_end == stop || window_full) break;
-            }
-            for (auto it = first_kept; it != window_end && it->score > o.min_sim; ++it) vc.push_back(*it);
-        } else {  // :297-331
-            vc.swap(cand[x]);
-            auto it = vc.begin();
-            auto middle = vc.begin() + std::min<size_t>((size_t)o.max_result, vc.size());
-            auto end = vc.end();
-            std::partial_sort(it, middle, end, std::greater<search::result_item>());
-            while (it != middle && it->score > o.min_sim) ++it;
-            vc.erase(it, vc.end());
-        }
-
         std::string nearest;
         std::map<std::string, std::vector<std::vector<std::string>>> group_names_map;
         for (auto &i : vc) {

@@ -271,6 +271,7 @@ public:
     // ranks other than 0 of a multi-GPU run: the device copy of the references (and the index) arrives by
     // broadcast into buffers made by sina_hip_store_alloc_like -- device() then uploads nothing
     void expect_broadcast() { refs_by_broadcast = true; }
+    bool filled_by_broadcast() const { return refs_by_broadcast; }
     sina_hip_ctx *device();                    // lazily creates the context and uploads the references
     void ensure_index(unsigned k, bool nofast);  // builds the k-mer index on the GPU once per (k, nofast)
     void adopt_index(unsigned k, bool nofast) {  // index already in HBM (broadcast from another rank)
@@ -314,6 +315,16 @@ public:
     void match_stats(double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches);
     // the alignment is wider than the match-count kernel's table takes: said once (stderr), then true every time
     bool match_counts_too_wide();
+    // search_filter's device-rank: the references' name order is on the device (computed and uploaded by the first
+    // call -- sina_hip_upload_name_order); false, every time, if two references share a name
+    bool name_order_ready();
+    // ... its queries ranked on the device / sent back to the host path since the store was opened, and the rank
+    // kernel's time and volume on the store's contexts -- sina_hip_rank_stats
+    void count_ranked(uint64_t on_device, uint64_t on_host) {
+        n_ranked.fetch_add(on_device, std::memory_order_relaxed);
+        n_rank_host.fetch_add(on_host, std::memory_order_relaxed);
+    }
+    void rank_stats(uint64_t *ranked, uint64_t *fallen_back, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches);
 
 private:
     reference_store() = default;
@@ -337,6 +348,8 @@ private:
     std::atomic<bool> labels_ready{false};
     std::mutex gpu_mu;
     std::atomic<bool> too_wide_said{false};
+    std::atomic<int> name_order_state{0};  // 0: not looked at, 1: uploaded, 2: names repeat
+    std::atomic<uint64_t> n_ranked{0}, n_rank_host{0};
 };
 
 // ---------------------------------------------------------------- .sidx index cache
@@ -497,7 +510,8 @@ public:
     // "search-db", "search-min-sim", "search-max-result", "lca-fields", "lca-quorum", "search-all",
     // "search-no-fast", "search-kmer-candidates", "search-kmer-len", "search-ignore-super",
     // "search-copy-fields", "search-iupac", "search-correction", "search-cover",
-    // "search-filter-lowercase", "db" (fallback for search-db)
+    // "search-filter-lowercase", "db" (fallback for search-db), "device-rank" (score and rank the candidates on the
+    // device, sina_hip_kmer_topk_rank / sina_hip_compare_rank; default off)
     static void set_option(const std::string &name, const std::string &value);
     static void reset_options();
     static void validate_options();

@@ -38,6 +38,8 @@
 #include "ctx.h"
 #include "kmer_plan.h"
 #include "match_plan.h"
+#include "compare_dev.h"
+#include "rank_plan.h"
 
 namespace sina_hip {
 namespace {
@@ -1105,9 +1107,17 @@ int sina_hip_build_index(sina_hip_ctx *c, unsigned k, int nofast) {
 // long kernel, in launch ranges of their own
 // q_ab / out_match (sina_hip_kmer_topk_match; else null): the queries' packed aligned bases, one per mask byte, and
 // where every range's match counts go (match.hip), [nq * max] like out_ids
+// rk (sina_hip_kmer_topk_rank; else null): the rules under which every range's candidates are ranked where the select
+// left them (rank.hip); out_ids / out_scores are then [nq * rk->N] rows of the rank kernel, out_n its counts, and no id
+// or k-mer score of the select is copied out
+struct RankReq {
+    int iupac, filter_lc, cover;
+    uint32_t N;
+    uint32_t *out_flag;  // [nq]
+};
 static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t n_fast,
                          uint32_t max, uint32_t *out_ids, float *out_scores, uint32_t *out_n, const uint32_t *q_ab = nullptr,
-                         uint16_t *out_match = nullptr) {
+                         uint16_t *out_match = nullptr, const RankReq *rk = nullptr) {
     uint32_t max_qlen = 1;
     for (uint32_t q = 0; q < n_fast; q++) max_qlen = std::max<uint32_t>(max_qlen, (uint32_t)(qoff[q + 1] - qoff[q]));
     hipStream_t s = c->stream;
@@ -1126,13 +1136,13 @@ static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *
     for (uint32_t q = 0; q <= nq; q++) rel[q] = qoff[q] - qoff[0];
     if (upload(c, 7, c->qmask.p, qmask + qoff[0], nqm, s) || upload(c, 8, c->k_qoff.p, rel.data(), 8 * ((uint64_t)nq + 1), s))
         return 1;
-    if (out_match && (c->s_qab.reserve(4 * std::max<uint64_t>(nqm, 1)) || upload(c, 1, c->s_qab.p, q_ab + qoff[0], 4 * nqm, s))) return 1;
+    if ((out_match || rk) && (c->s_qab.reserve(4 * std::max<uint64_t>(nqm, 1)) || upload(c, 1, c->s_qab.p, q_ab + qoff[0], 4 * nqm, s))) return 1;
     // one launch range: kernels, results back through pinned staging, statistics; *overflow = a candidate list of the
     // range did not hold its query's candidates (nothing was copied out then: the caller repeats the range with rows)
     auto run_range = [&](uint32_t q0, uint32_t bq, bool cand_path, bool *overflow, bool long_path = false) -> int {
         if (kmer_topk_device(c, c->qmask.as<uint8_t>(), c->k_qoff.as<uint64_t>() + q0, bq, max, max_qlen, false, cand_path, long_path)) return 1;
         // (the kernels have finished: kmer_topk_device waits for the heavy stream)
-        if (download(c, 9, c->k_out_ids.p, (size_t)bq * max * 4, s) || download(c, 10, c->k_out_scores.p, (size_t)bq * max * 4, s) ||
+        if ((!rk && (download(c, 9, c->k_out_ids.p, (size_t)bq * max * 4, s) || download(c, 10, c->k_out_scores.p, (size_t)bq * max * 4, s))) ||
             download(c, 11, c->k_out_n.p, (size_t)bq * 4, s) || download(c, 0, c->k_tmp2.p, 8, s))
             return 1;
         SH_CHECK(wait_stream(c, s));
@@ -1159,6 +1169,13 @@ static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *
         if (*overflow) return 0;
         if (long_path) c->long_queries += bq;
         if (big) c->big_select_queries += bq;
+        if (rk) {  // the range's select is final: its candidates ranked, ids and lengths read where they lie
+            uint32_t max_la = 0;
+            for (uint32_t q = q0; q < q0 + bq; q++) max_la = std::max<uint32_t>(max_la, (uint32_t)(qoff[q + 1] - qoff[q]));
+            return rank_launch(c, c->s_qab.as<uint32_t>(), c->k_qoff.as<uint64_t>() + q0, bq, c->k_out_ids.as<uint32_t>(), nullptr,
+                               c->k_out_n.as<uint32_t>(), max, max, max_la, rk->iupac, rk->filter_lc, rk->cover, rk->N,
+                               out_ids + (size_t)q0 * rk->N, out_scores + (size_t)q0 * rk->N, out_n + q0, rk->out_flag + q0);
+        }
         memcpy(out_ids + (size_t)q0 * max, c->h_stage[9].p, (size_t)bq * max * 4);
         memcpy(out_scores + (size_t)q0 * max, c->h_stage[10].p, (size_t)bq * max * 4);
         memcpy(out_n + q0, c->h_stage[11].p, (size_t)bq * 4);
@@ -1199,18 +1216,28 @@ static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *
 // kmer_topk_run and back into the caller's order
 static int kmer_topk_checked(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max,
                              uint32_t *out_ids, float *out_scores, uint32_t *out_n, bool any, const uint32_t *q_ab = nullptr,
-                             uint16_t *out_match = nullptr) {
+                             uint16_t *out_match = nullptr, const RankReq *rk = nullptr) {
     if (!c || !qmask || !qoff || !out_ids || !out_scores || !out_n) SH_FAIL("kmer_topk: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
     if (index_ready(c)) return 1;
     if (out_match && match_table_bytes(c->st->width) > kMatchMaxLds)
         SH_FAIL_LIMIT("kmer_topk_match: alignment too wide for the device match count");
+    if (rk) {
+        if (rank_check_rules("kmer_topk_rank", c, rk->iupac, rk->cover, rk->N)) return 1;
+        uint32_t max_la = 0;
+        for (uint32_t q = 0; q < nq; q++) max_la = std::max<uint32_t>(max_la, (uint32_t)(qoff[q + 1] - qoff[q]));
+        if (compare_table_bytes(c->st->width, max_la) > kCompareMaxLds)
+            SH_FAIL_LIMIT("kmer_topk_rank: alignment too wide for the device comparison");
+        if (std::min(max, c->st->n_refs) > (uint32_t)kSelMax)
+            SH_FAIL_LIMIT("kmer_topk_rank: more than 4096 candidates per query");
+    }
     if (nq == 0) return 0;
     SH_CHECK(hipSetDevice(c->device));
     if (max > c->st->n_refs) max = c->st->n_refs;
     if (max == 0) {
         memset(out_n, 0, sizeof(uint32_t) * nq);
+        if (rk) memset(rk->out_flag, 0, sizeof(uint32_t) * nq);
         return 0;
     }
     uint32_t n_long = 0;
@@ -1220,28 +1247,35 @@ static int kmer_topk_checked(sina_hip_ctx *c, const uint8_t *qmask, const uint64
         if (len > (uint64_t)kMaxLongQueryLen) SH_FAIL_LIMIT("kmer_topk_any: query longer than SINA_HIP_MAX_LONG_QUERY_LEN bases");
         n_long += len > (uint64_t)kMaxQueryLen;
     }
-    if (n_long == 0) return kmer_topk_run(c, qmask, qoff, nq, nq, max, out_ids, out_scores, out_n, q_ab, out_match);
+    if (n_long == 0) return kmer_topk_run(c, qmask, qoff, nq, nq, max, out_ids, out_scores, out_n, q_ab, out_match, rk);
     const uint32_t n_fast = nq - n_long;
+    const uint32_t row = rk ? rk->N : max;  // entries of an output row
     std::vector<uint32_t> order(nq);  // order[slot] = the caller's query
     for (uint32_t q = 0, f = 0, l = n_fast; q < nq; q++) order[qoff[q + 1] - qoff[q] > (uint64_t)kMaxQueryLen ? l++ : f++] = q;
     std::vector<uint64_t> off(nq + 1, 0);
     for (uint32_t x = 0; x < nq; x++) off[x + 1] = off[x] + (qoff[order[x] + 1] - qoff[order[x]]);
     std::vector<uint8_t> mask(off[nq]);
     for (uint32_t x = 0; x < nq; x++) memcpy(mask.data() + off[x], qmask + qoff[order[x]], off[x + 1] - off[x]);
-    std::vector<uint32_t> ids((size_t)nq * max), n(nq);
-    std::vector<float> sc((size_t)nq * max);
-    std::vector<uint32_t> ab(out_match ? off[nq] : 0);  // (the packed bases and the match rows move with their queries)
+    std::vector<uint32_t> ids((size_t)nq * row), n(nq), fl(rk ? nq : 0);
+    std::vector<float> sc((size_t)nq * row);
+    std::vector<uint32_t> ab(q_ab ? off[nq] : 0);  // (the packed bases and the match rows move with their queries)
     std::vector<uint16_t> mt(out_match ? (size_t)nq * max : 0);
-    if (out_match)
+    if (q_ab)
         for (uint32_t x = 0; x < nq; x++) memcpy(ab.data() + off[x], q_ab + qoff[order[x]], 4 * (off[x + 1] - off[x]));
-    if (kmer_topk_run(c, mask.data(), off.data(), nq, n_fast, max, ids.data(), sc.data(), n.data(), out_match ? ab.data() : nullptr,
-                      out_match ? mt.data() : nullptr))
+    RankReq rk2;
+    if (rk) {
+        rk2 = *rk;
+        rk2.out_flag = fl.data();
+    }
+    if (kmer_topk_run(c, mask.data(), off.data(), nq, n_fast, max, ids.data(), sc.data(), n.data(), q_ab ? ab.data() : nullptr,
+                      out_match ? mt.data() : nullptr, rk ? &rk2 : nullptr))
         return 1;
     for (uint32_t x = 0; x < nq; x++) {
         if (out_match) memcpy(out_match + (size_t)order[x] * max, mt.data() + (size_t)x * max, (size_t)max * 2);
-        memcpy(out_ids + (size_t)order[x] * max, ids.data() + (size_t)x * max, (size_t)max * 4);
-        memcpy(out_scores + (size_t)order[x] * max, sc.data() + (size_t)x * max, (size_t)max * 4);
+        memcpy(out_ids + (size_t)order[x] * row, ids.data() + (size_t)x * row, (size_t)row * 4);
+        memcpy(out_scores + (size_t)order[x] * row, sc.data() + (size_t)x * row, (size_t)row * 4);
         out_n[order[x]] = n[x];
+        if (rk) rk->out_flag[order[x]] = fl[x];
     }
     return 0;
 }
@@ -1285,6 +1319,28 @@ int sina_hip_kmer_topk_match(sina_hip_ctx *c, const uint32_t *q_ab, const uint64
     std::vector<uint64_t> rel(nq + 1);
     for (uint32_t q = 0; q <= nq; q++) rel[q] = q_off[q] - b;
     return kmer_topk_checked(c, mask.data(), rel.data(), nq, max, out_ids, out_scores, out_n, true, q_ab + b, out_match);
+}
+int sina_hip_kmer_topk_rank(sina_hip_ctx *c, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t kmer_candidates,
+                            int iupac_rule, int filter_lowercase, int cover_rule, uint32_t max_result, uint32_t *out_ids,
+                            float *out_scores, uint32_t *out_n, uint32_t *out_flag) {
+    if (!c || !q_ab || !q_off || !out_ids || !out_scores || !out_n || !out_flag) SH_FAIL("kmer_topk_rank: null argument");
+    if (match_check_queries("kmer_topk_rank", q_ab, q_off, nq)) return 1;
+    const uint64_t b = q_off[0], e = q_off[nq];
+    std::vector<uint8_t> mask(e - b + 1);
+    for (uint64_t i = b; i < e; i++) mask[i - b] = (uint8_t)(q_ab[i] >> 24);
+    std::vector<uint64_t> rel(nq + 1);
+    for (uint32_t q = 0; q <= nq; q++) rel[q] = q_off[q] - b;
+    // (results through vectors of the call's own: the outputs stay untouched if a range fails)
+    std::vector<uint32_t> ids((size_t)nq * std::max(max_result, 1u)), n(nq), fl(nq);
+    std::vector<float> sc(ids.size());
+    const RankReq rk{iupac_rule, filter_lowercase ? 1 : 0, cover_rule, max_result, fl.data()};
+    if (kmer_topk_checked(c, mask.data(), rel.data(), nq, kmer_candidates, ids.data(), sc.data(), n.data(), true, q_ab + b, nullptr, &rk))
+        return 1;
+    memcpy(out_ids, ids.data(), 4 * (size_t)nq * max_result);
+    memcpy(out_scores, sc.data(), 4 * (size_t)nq * max_result);
+    memcpy(out_n, n.data(), 4 * (size_t)nq);
+    memcpy(out_flag, fl.data(), 4 * (size_t)nq);
+    return 0;
 }
 int sina_hip_kmer_scores(sina_hip_ctx *c, const uint8_t *qmask, uint32_t qlen, int16_t *scores) {
     return kmer_scores_checked(c, qmask, qlen, scores, false);
@@ -1348,6 +1404,7 @@ int sina_hip_store_alloc_like(sina_hip_ctx *c, sina_hip_store_view *v) {
     c->st->nofast = v->nofast;
     c->st->n_postings = v->n_postings;
     c->st->have_refs = c->st->have_index = true;
+    c->st->have_name_order = false;
     c->st->dense_ready = false;  // (the index arrives by broadcast after this call: built by the first search)
     {   // re-read from the device, once, after the broadcast filled it (ensure_ref_off_host)
         std::lock_guard<std::mutex> alk(c->st->aux_mu);

@@ -39,6 +39,7 @@ def load_host():
     H.sina_host_pipeline_run_aligned.argtypes = [vp, capi.u32p, capi.u64p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32,
                                                  C.c_uint32]
     H.sina_host_store_match_stats.argtypes = [C.c_char_p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_store_rank_stats.argtypes = [C.c_char_p, capi.u64p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_pipeline_run_single_trays.argtypes = [vp, capi.u8p, capi.u64p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                       C.c_uint32, C.c_int32, capi.u8p, C.c_char_p, C.c_uint32]
     H.sina_host_result.argtypes = [vp, C.c_uint32] + [C.POINTER(C.c_int)] * 4 + [capi.u32p, capi.u32p]
@@ -249,6 +250,18 @@ class Store:
                                                 C.byref(launches)))
         return dict(kernel_ms=float(ms.value), pairs=int(pairs.value), cand_bases=int(bases.value),
                     launches=int(launches.value))
+
+    def rank_stats(self):
+        """The search stage's device-rank on this store so far: dict(ranked, fallen_back, kernel_ms, pairs, cand_bases,
+        launches) -- queries ranked on the device, queries sent back to the host path, and the rank kernel's time and
+        volume on the store's contexts; between runs, like big_select_queries()."""
+        ranked, back = C.c_uint64(), C.c_uint64()
+        ms = C.c_double()
+        pairs, bases, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _chk(self.H.sina_host_store_rank_stats(self.key.encode(), C.byref(ranked), C.byref(back), C.byref(ms), C.byref(pairs),
+                                               C.byref(bases), C.byref(launches)))
+        return dict(ranked=int(ranked.value), fallen_back=int(back.value), kernel_ms=float(ms.value), pairs=int(pairs.value),
+                    cand_bases=int(bases.value), launches=int(launches.value))
 
     def close(self):
         self.H.sina_host_store_close(self.key.encode())

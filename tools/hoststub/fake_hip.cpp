@@ -100,6 +100,16 @@ int sina_hip_match_stats(sina_hip_ctx *, double *ms, uint64_t *pairs, uint64_t *
     *pairs = *bases = *launches = 0;
     return 0;
 }
+int sina_hip_upload_name_order(sina_hip_ctx *, const uint32_t *, uint32_t) { return 0; }
+int sina_hip_compare_rank(sina_hip_ctx *, const uint32_t *, const uint64_t *, uint32_t, const uint32_t *, const uint64_t *, int, int,
+                          int, uint32_t, uint32_t *, float *, uint32_t *, uint32_t *) { g_err = "stub"; return 1; }
+int sina_hip_kmer_topk_rank(sina_hip_ctx *, const uint32_t *, const uint64_t *, uint32_t, uint32_t, int, int, int, uint32_t,
+                            uint32_t *, float *, uint32_t *, uint32_t *) { g_err = "stub"; return 1; }
+int sina_hip_rank_stats(sina_hip_ctx *, double *ms, uint64_t *pairs, uint64_t *bases, uint64_t *launches) {
+    *ms = 0;
+    *pairs = *bases = *launches = 0;
+    return 0;
+}
 void sina_hip_align_params_default(sina_hip_align_params *p) {
     memset(p, 0, sizeof(*p));
     p->match_score = 2;
