@@ -7,6 +7,7 @@
 #include <sys/resource.h>
 #include <immintrin.h>
 #include "id_order.h"
+#include "distinct.h"
 #include "../kmer_plan.h"
 #include "../match_plan.h"
 #include "../rank_plan.h"
@@ -25,36 +26,16 @@
 #include <tuple>
 #include <unordered_map>
 
+// (two fill constructors the library has always exported out of line: its exported names stay as they were whatever
+// the compiler now inlines)
+template std::vector<uint32_t>::vector(size_type, const uint32_t &, const std::allocator<uint32_t> &);
+template std::vector<uint64_t>::vector(size_type, const uint64_t &, const std::allocator<uint64_t> &);
+
 namespace sina {
 
 static void hip_check(int rc, const char *what) {
     if (rc != 0) throw std::runtime_error(std::string(what) + ": " + sina_hip_last_error());
 }
-
-// The big per-batch arrays of a stage call (packed queries, aligned columns coming back: tens of MB): a
-// std::vector of that size is a fresh mmap every batch -- zero-filled by the kernel page by page, then
-// zero-filled again by the constructor -- 46 MB and 11 000 page faults per 6144-query batch.  One grow-only,
-// uninitialised block per calling thread and use instead.
-template <typename T> struct batch_scratch {
-    T *p = nullptr;
-    size_t cap = 0;
-    T *get(size_t n) {
-        if (n > cap) {
-            free(p);
-            cap = n + n / 4 + 1024;
-            p = static_cast<T *>(malloc(cap * sizeof(T)));
-            if (!p) {
-                cap = 0;
-                throw std::bad_alloc();
-            }
-        }
-        return p;
-    }
-    ~batch_scratch() { free(p); }
-    batch_scratch() = default;
-    batch_scratch(const batch_scratch &) = delete;
-    batch_scratch &operator=(const batch_scratch &) = delete;
-};
 
 // ================================================================ phase profiler (SINA_HOST_PROFILE=1)
 
@@ -920,69 +901,39 @@ static unsigned count_query_kmers(const uint8_t *m, size_t n, unsigned k, bool c
     return total;
 }
 
-// Batch-level memoisation of repeated queries.  The reference's kmer_search::find keeps the scored list of the
-// base strings it has just seen (src/kmer_search.cpp:105,377-378,419: a cache of 32 keyed by getBases()) -- real
-// amplicon runs are dominated by repeats.  A GPU batch is thousands of queries wide, so the analogue is inside the
-// batch: items with the same key bytes (and, for the aligner, the same family) go to the device ONCE, and every
-// item reads the slot of its first occurrence.  rep[i] = index of the first item equal to item i; returns the
-// number of distinct items.  set_batch_dedup(false) switches it off (tests compare both ways).
-static std::atomic<int> g_dedup{1};  // (set_batch_dedup(false): tests compare against the un-deduplicated run)
+// Batch-level memoisation of repeated queries (distinct.h): items with the same key bytes go to the device once.
+// set_batch_dedup(false) switches it off (tests compare against the un-deduplicated run).
+static std::atomic<int> g_dedup{1};
 void set_batch_dedup(bool on) { g_dedup.store(on ? 1 : 0); }
 static bool dedup_enabled() { return g_dedup.load(std::memory_order_relaxed) != 0; }
-template <class Hash, class Equal>
-static size_t group_equal_items(size_t n, Hash &&hash_of, Equal &&equal, std::vector<uint32_t> &rep) {
-    rep.resize(n);
-    if (!dedup_enabled() || n < 2) {
-        for (size_t i = 0; i < n; i++) rep[i] = (uint32_t)i;
-        return n;
-    }
-    std::vector<uint64_t> h(n);
-    parallel_for(n, [&](size_t i) { h[i] = hash_of(i); });
-    // open addressing over the first occurrences (a batch is a few thousand items)
-    size_t cap = 16;
-    while (cap < 2 * n) cap <<= 1;
-    std::vector<uint32_t> slot(cap, 0xFFFFFFFFu);
-    size_t distinct = 0;
-    for (size_t i = 0; i < n; i++) {
-        size_t at = (size_t)(h[i] * 0x9E3779B97F4A7C15ull >> 20) & (cap - 1);
-        for (;;) {
-            const uint32_t j = slot[at];
-            if (j == 0xFFFFFFFFu) {
-                slot[at] = (uint32_t)i;
-                rep[i] = (uint32_t)i;
-                distinct++;
-                break;
-            }
-            if (h[j] == h[i] && equal(j, i)) {
-                rep[i] = j;
-                break;
-            }
-            at = (at + 1) & (cap - 1);
-        }
-    }
-    return distinct;
+
+// Takes n sequences seq_of(x) and where each starts, qoff [n + 1] (offsets_of); writes sequence x's mask bytes to
+// dst + qoff[x] (an unaligned query's as its reader left them; case is kept).  then(x, bytes, n_bytes), if given, sees
+// every sequence's bytes right after they are written, in the same pass.
+template <class SeqOf, class Then = void (*)(size_t, const uint8_t *, size_t)>
+static void pack_masks(size_t n, SeqOf &&seq_of, const uint64_t *qoff, uint8_t *dst, Then &&then = [](size_t, const uint8_t *, size_t) {}) {
+    static_assert(sizeof(aligned_base) == 4, "packed words");
+    parallel_for(n, [&](size_t x) {
+        const cseq &c = seq_of(x);
+        const size_t nb = c.size();
+        if (const uint8_t *dense = c.denseMasks()) memcpy(dst + qoff[x], dense, nb);
+        else masks_of_packed(dst + qoff[x], c.packed(), nb);
+        then(x, dst + qoff[x], nb);
+    });
 }
-// hash of a query's mask bytes for the grouping of repeats: its two ends (64 bytes each) and its length.  Equal
-// queries hash equal; unequal ones that agree there are told apart by the byte comparison that follows a hash match
-// -- hashing all 1500 bytes, in famfinder and again in the aligner, was 0.4 us per query.
-static uint64_t hash_bytes(const void *p, size_t n, uint64_t seed);
-static uint64_t hash_ends(const void *p, size_t n, uint64_t seed) {
-    if (n <= 160) return hash_bytes(p, n, seed);
-    const unsigned char *b = static_cast<const unsigned char *>(p);
-    return hash_bytes(b + n - 64, 64, hash_bytes(b, 64, seed ^ n));
+// The same, as packed aligned bases (a dense query's: base i in column i).
+template <class SeqOf> static void pack_words(size_t n, SeqOf &&seq_of, const uint64_t *qoff, uint32_t *dst) {
+    parallel_for(n, [&](size_t x) {
+        const cseq &c = seq_of(x);
+        if (const uint8_t *dense = c.denseMasks()) packed_of_masks(dst + qoff[x], dense, c.size());
+        else memcpy(dst + qoff[x], c.packed(), 4 * (size_t)c.size());
+    });
 }
-static uint64_t hash_bytes(const void *p, size_t n, uint64_t seed) {  // (FNV-1a over 8-byte words + tail)
-    const unsigned char *b = static_cast<const unsigned char *>(p);
-    uint64_t h = 0xcbf29ce484222325ull ^ seed;
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8) {
-        uint64_t w;
-        memcpy(&w, b + i, 8);
-        h = (h ^ w) * 0x100000001b3ull;
-        h ^= h >> 29;
-    }
-    for (; i < n; i++) h = (h ^ b[i]) * 0x100000001b3ull;
-    return h ^ (h >> 32);
+// Takes n sequences; gives qoff [n + 1], qoff[x + 1] - qoff[x] the number of bases of sequence x.
+template <class SeqOf> static std::vector<uint64_t> offsets_of(size_t n, SeqOf &&seq_of) {
+    std::vector<uint64_t> qoff(n + 1, 0);
+    for (size_t x = 0; x < n; x++) qoff[x + 1] = qoff[x] + seq_of(x).size();
+    return qoff;
 }
 
 // true if the sequence's columns ascend strictly (what the device's match count asks of a query)
@@ -994,133 +945,46 @@ static bool columns_ascend(const cseq &c) {
     return true;
 }
 
-void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vector<result_vector> &results,
-                             unsigned int max, std::vector<uint32_t> *kmer_counts, std::vector<std::vector<uint16_t>> *match_rows) {
-    reference_store &st = *pimpl->store;
-    const unsigned n = st.size();
-    // (the callers' vectors are kept -- famfinder hands in recycled ones -- and only emptied)
-    results.resize(queries.size());
-    for (auto &r : results) r.clear();
-    if (match_rows) {
-        match_rows->resize(queries.size());
-        for (auto &r : *match_rows) r.clear();
-    }
-    if (max > n) max = n;
-    if (max == 0 || queries.empty()) return;
-    // The device's match counts (famfinder's device-msc): kept from a store too wide for the kernel's table -- said
-    // once, then every query keeps the host walk -- and from a query whose columns do not ascend strictly: those are
-    // searched through the entry without counts, in a call of their own, and their rows stay empty.
-    if (match_rows && st.match_counts_too_wide()) match_rows = nullptr;
-    if (match_rows) {
-        std::vector<size_t> plain;
+// The device's match counts ask for strictly ascending columns.  Takes a batch in which is_plain marks the queries
+// without them; searches the others with counts and those through the entry without, each kind in a call of its own
+// (find_batch again), and puts every result back at its query's place.  The rows of the marked queries stay empty.
+static void find_by_columns(kmer_search &ks, const std::vector<const cseq *> &queries, const std::vector<char> &is_plain,
+                            std::vector<search::result_vector> &results, unsigned int max, std::vector<uint32_t> *kmer_counts,
+                            std::vector<std::vector<uint16_t>> &match_rows) {
+    for (int pass = 0; pass < 2; pass++) {
+        std::vector<size_t> at;
+        std::vector<const cseq *> sub;
         for (size_t i = 0; i < queries.size(); i++)
-            if (!columns_ascend(*queries[i])) plain.push_back(i);
-        if (!plain.empty()) {
-            std::vector<char> is_plain(queries.size(), 0);
-            for (size_t i : plain) is_plain[i] = 1;
-            for (int pass = 0; pass < 2; pass++) {
-                std::vector<size_t> at;
-                std::vector<const cseq *> sub;
-                for (size_t i = 0; i < queries.size(); i++)
-                    if ((is_plain[i] != 0) == (pass == 1)) {
-                        at.push_back(i);
-                        sub.push_back(queries[i]);
-                    }
-                if (sub.empty()) continue;
-                std::vector<result_vector> sub_results(sub.size());
-                for (size_t x = 0; x < sub.size(); x++) sub_results[x].swap(results[at[x]]);
-                std::vector<uint32_t> sub_counts;
-                std::vector<std::vector<uint16_t>> sub_rows;
-                find_batch(sub, sub_results, max, kmer_counts ? &sub_counts : nullptr, pass == 0 ? &sub_rows : nullptr);
-                if (kmer_counts && kmer_counts->size() != queries.size()) kmer_counts->assign(queries.size(), 0);
-                for (size_t x = 0; x < sub.size(); x++) {
-                    results[at[x]].swap(sub_results[x]);
-                    if (kmer_counts) (*kmer_counts)[at[x]] = sub_counts[x];
-                    if (pass == 0) (*match_rows)[at[x]].swap(sub_rows[x]);
-                }
+            if ((is_plain[i] != 0) == (pass == 1)) {
+                at.push_back(i);
+                sub.push_back(queries[i]);
             }
-            return;
+        if (sub.empty()) continue;
+        std::vector<search::result_vector> sub_results(sub.size());
+        for (size_t x = 0; x < sub.size(); x++) sub_results[x].swap(results[at[x]]);
+        std::vector<uint32_t> sub_counts;
+        std::vector<std::vector<uint16_t>> sub_rows;
+        ks.find_batch(sub, sub_results, max, kmer_counts ? &sub_counts : nullptr, pass == 0 ? &sub_rows : nullptr);
+        if (kmer_counts && kmer_counts->size() != queries.size()) kmer_counts->assign(queries.size(), 0);
+        for (size_t x = 0; x < sub.size(); x++) {
+            results[at[x]].swap(sub_results[x]);
+            if (kmer_counts) (*kmer_counts)[at[x]] = sub_counts[x];
+            if (pass == 0) match_rows[at[x]].swap(sub_rows[x]);
         }
     }
-    st.ensure_index(pimpl->k, pimpl->nofast);
-    std::vector<uint64_t> qoff(queries.size() + 1, 0);
-    for (size_t i = 0; i < queries.size(); i++) qoff[i + 1] = qoff[i] + queries[i]->size();
-    thread_local batch_scratch<uint8_t> qmask_buf;
-    uint8_t *const qmask = qmask_buf.get(qoff.back() + 1);
-    if (kmer_counts) kmer_counts->assign(queries.size(), 0);
-    const unsigned kk = pimpl->k;
-    const bool count_all = pimpl->nofast;
-    parallel_for(queries.size(), [&](size_t i) {
-        uint8_t *dst = qmask + qoff[i];
-        const size_t nb = queries[i]->size();
-        static_assert(sizeof(aligned_base) == 4, "packed words");
-        if (const uint8_t *dense = queries[i]->denseMasks()) memcpy(dst, dense, nb);  // (an unaligned query as its reader left it)
-        else masks_of_packed(dst, queries[i]->packed(), nb);
-        if (kmer_counts) (*kmer_counts)[i] = count_query_kmers(dst, nb, kk, count_all);
-    });
-    // with match counts the device takes the queries as packed aligned bases (a dense query's: base i in column i)
-    thread_local batch_scratch<uint32_t> qab_buf;
-    uint32_t *const qab = match_rows ? qab_buf.get(qoff.back() + 1) : nullptr;
-    if (match_rows)
-        parallel_for(queries.size(), [&](size_t i) {
-            const size_t nb = queries[i]->size();
-            if (queries[i]->denseMasks()) packed_of_masks(qab + qoff[i], qmask + qoff[i], nb);
-            else memcpy(qab + qoff[i], queries[i]->packed(), 4 * nb);
-        });
-    auto dev = st.worker_device(reference_store::dev_search);
-    sina_hip_ctx *ctx = dev.get();
-    // repeated queries (same bases, same case: the packed mask bytes) are searched once
-    std::vector<uint32_t> rep;
-    const size_t nu = group_equal_items(
-        queries.size(),
-        // (with match counts: same PACKED WORDS -- equal bases in other columns are another query there)
-        [&](size_t i) {
-            return qab ? hash_ends(qab + qoff[i], 4 * (qoff[i + 1] - qoff[i]), qoff[i + 1] - qoff[i])
-                       : hash_ends(qmask + qoff[i], qoff[i + 1] - qoff[i], qoff[i + 1] - qoff[i]);
-        },
-        [&](size_t a, size_t b) {
-            if (qoff[a + 1] - qoff[a] != qoff[b + 1] - qoff[b]) return false;
-            return qab ? memcmp(qab + qoff[a], qab + qoff[b], 4 * (qoff[a + 1] - qoff[a])) == 0
-                       : memcmp(qmask + qoff[a], qmask + qoff[b], qoff[a + 1] - qoff[a]) == 0;
-        },
-        rep);
-    std::vector<uint32_t> slot_of(queries.size());
-    const uint8_t *dev_mask = qmask;
-    const uint64_t *dev_off = qoff.data();
-    std::vector<uint64_t> uoff;
-    thread_local batch_scratch<uint8_t> umask_buf;
-    const uint32_t *dev_ab = qab;
-    thread_local batch_scratch<uint32_t> uab_buf;
-    if (nu == queries.size()) {
-        for (size_t i = 0; i < queries.size(); i++) slot_of[i] = (uint32_t)i;
-    } else {  // the distinct queries, packed again for the device
-        uoff.assign(nu + 1, 0);
-        std::vector<uint32_t> firsts;
-        firsts.reserve(nu);
-        for (size_t i = 0; i < queries.size(); i++) {
-            if (rep[i] == i) {
-                slot_of[i] = (uint32_t)firsts.size();
-                uoff[firsts.size() + 1] = uoff[firsts.size()] + (qoff[i + 1] - qoff[i]);
-                firsts.push_back((uint32_t)i);
-            } else {
-                slot_of[i] = slot_of[rep[i]];
-            }
-        }
-        uint8_t *const um = umask_buf.get(uoff.back() + 1);
-        parallel_for(nu, [&](size_t u) { memcpy(um + uoff[u], qmask + qoff[firsts[u]], uoff[u + 1] - uoff[u]); });
-        dev_mask = um;
-        dev_off = uoff.data();
-        if (qab) {
-            uint32_t *const ua = uab_buf.get(uoff.back() + 1);
-            parallel_for(nu, [&](size_t u) { memcpy(ua + uoff[u], qab + qoff[firsts[u]], 4 * (uoff[u + 1] - uoff[u])); });
-            dev_ab = ua;
-        }
-    }
-    // Up to 4096 candidates per query the distinct queries go to the device in one call, as ever.  More (famfinder
-    // widening its list tenfold per round, a large search-kmer-candidates): nu * max ids and scores are no longer one
-    // scratch block -- the distinct queries are taken in slices of as many as one launch range of the device's big
-    // select holds (kmer_plan.h: the same function, the same budget, so a slice is one launch), and `results` is filled
-    // slice by slice.
+}
+
+// Takes the distinct queries as the device reads them -- mask bytes, or packed words where match counts are asked for
+// (dev_ab and match_rows both set) -- and searches them; gives every query the `max` best of its slot: results[i], and
+// the match counts by rank in (*match_rows)[i].
+// Up to 4096 candidates per query the distinct queries go to the device in one call, as ever.  More (famfinder
+// widening its list tenfold per round, a large search-kmer-candidates): d.n * max ids and scores are no longer one
+// scratch block -- the distinct queries are taken in slices of as many as one launch range of the device's big
+// select holds (kmer_plan.h: the same function, the same budget, so a slice is one launch), and `results` is filled
+// slice by slice.
+static void search_slices(reference_store &st, sina_hip_ctx *ctx, const distinct_items &d, const uint8_t *dev_mask, const uint32_t *dev_ab,
+                          unsigned int max, std::vector<search::result_vector> &results, std::vector<std::vector<uint16_t>> *match_rows) {
+    const size_t nu = d.n;
     const size_t slice = max > sina_hip::kKmerSelMax ? sina_hip::big_select_range((uint32_t)nu, max, sina_hip::kBigSelBudget) : nu;
     thread_local batch_scratch<uint32_t> ids_buf;
     thread_local batch_scratch<float> sc_buf;
@@ -1134,14 +998,14 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
         {
             scoped_phase ph("ff.kmer_topk(C-ABI)");
             // (the _any entry: the class has no length limit of its own, as the reference's -- a query beyond the fast count
-            // kernel's goes to the long one, per query; offsets are absolute, so a slice starts at dev_off + u0)
+            // kernel's goes to the long one, per query; offsets are absolute, so a slice starts at d.off + u0)
             if (match_rows)
-                hip_check(sina_hip_kmer_topk_match(ctx, dev_ab, dev_off + u0, (uint32_t)(u1 - u0), max, ids, sc, cnt.data(), mt), "kmer_topk_match");
+                hip_check(sina_hip_kmer_topk_match(ctx, dev_ab, d.off.data() + u0, (uint32_t)(u1 - u0), max, ids, sc, cnt.data(), mt), "kmer_topk_match");
             else
-                hip_check(sina_hip_kmer_topk_any(ctx, dev_mask, dev_off + u0, (uint32_t)(u1 - u0), max, ids, sc, cnt.data()), "kmer_topk");
+                hip_check(sina_hip_kmer_topk_any(ctx, dev_mask, d.off.data() + u0, (uint32_t)(u1 - u0), max, ids, sc, cnt.data()), "kmer_topk");
         }
-        parallel_for(queries.size(), [&](size_t i) {
-            const size_t u = slot_of[i];
+        parallel_for(results.size(), [&](size_t i) {
+            const size_t u = d.slot_of[i];
             if (u < u0 || u >= u1) return;
             const size_t at = (u - u0) * max;
             results[i].reserve(cnt[u - u0]);
@@ -1149,6 +1013,54 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
             if (match_rows) (*match_rows)[i].assign(mt + at, mt + at + cnt[u - u0]);
         });
     }
+}
+
+// Clears the outputs, packs the queries, finds the distinct ones, searches those and scatters what they found.
+void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vector<result_vector> &results,
+                             unsigned int max, std::vector<uint32_t> *kmer_counts, std::vector<std::vector<uint16_t>> *match_rows) {
+    reference_store &st = *pimpl->store;
+    const size_t nq = queries.size();
+    // (the callers' vectors are kept -- famfinder hands in recycled ones -- and only emptied)
+    results.resize(nq);
+    for (auto &r : results) r.clear();
+    if (match_rows) {
+        match_rows->resize(nq);
+        for (auto &r : *match_rows) r.clear();
+    }
+    if (max > st.size()) max = st.size();
+    if (max == 0 || queries.empty()) return;
+    // The device's match counts (famfinder's device-msc): kept from a store too wide for the kernel's table -- said
+    // once, then every query keeps the host walk -- and from a query whose columns do not ascend strictly.
+    if (match_rows && st.match_counts_too_wide()) match_rows = nullptr;
+    if (match_rows) {
+        std::vector<char> is_plain(nq, 0);
+        bool any_plain = false;
+        for (size_t i = 0; i < nq; i++) any_plain |= (is_plain[i] = !columns_ascend(*queries[i]));
+        if (any_plain) return find_by_columns(*this, queries, is_plain, results, max, kmer_counts, *match_rows);
+    }
+    st.ensure_index(pimpl->k, pimpl->nofast);
+    auto seq_of = [&](size_t i) -> const cseq & { return *queries[i]; };
+    const std::vector<uint64_t> qoff = offsets_of(nq, seq_of);
+    thread_local batch_scratch<uint8_t> qmask_buf;
+    uint8_t *const qmask = qmask_buf.get(qoff.back() + 1);
+    if (kmer_counts) kmer_counts->assign(nq, 0);
+    pack_masks(nq, seq_of, qoff.data(), qmask, [&, kk = pimpl->k, count_all = pimpl->nofast](size_t i, const uint8_t *m, size_t nb) {
+        if (kmer_counts) (*kmer_counts)[i] = count_query_kmers(m, nb, kk, count_all);
+    });
+    // with match counts the device takes the queries as packed aligned bases
+    thread_local batch_scratch<uint32_t> qab_buf;
+    uint32_t *const qab = match_rows ? qab_buf.get(qoff.back() + 1) : nullptr;
+    if (match_rows) pack_words(nq, seq_of, qoff.data(), qab);
+    auto dev = st.worker_device(reference_store::dev_search);
+    // repeated queries (same bases, same case: the packed mask bytes) are searched once
+    // (with match counts: same PACKED WORDS -- equal bases in other columns are another query there)
+    const distinct_items d = qab ? distinct_spans(dedup_enabled(), parallel_for, qab, qoff.data(), nq)
+                                 : distinct_spans(dedup_enabled(), parallel_for, qmask, qoff.data(), nq);
+    thread_local batch_scratch<uint8_t> umask_buf;
+    thread_local batch_scratch<uint32_t> uab_buf;
+    const uint8_t *const dev_mask = gather_distinct(d, parallel_for, qmask, qoff.data(), umask_buf);
+    const uint32_t *const dev_ab = qab ? gather_distinct(d, parallel_for, qab, qoff.data(), uab_buf) : nullptr;
+    search_slices(st, dev.get(), d, dev_mask, dev_ab, max, results, match_rows);
 }
 
 // ================================================================ famfinder
@@ -2104,30 +2016,12 @@ static sina_hip_align_params make_align_params(const aligner::options &o, const 
     return p;
 }
 
-// Takes a group; gives its queries' mask bytes, member x at qoff[x] .. qoff[x + 1], in a buffer of the calling thread
-// that is valid until the next call.
-static const uint8_t *pack_group_queries(const std::vector<dp_job *> &members, std::vector<uint64_t> &qoff) {
-    const size_t nq = members.size();
-    qoff.assign(nq + 1, 0);
-    for (size_t x = 0; x < nq; x++) qoff[x + 1] = qoff[x] + members[x]->t->input_sequence->size();
-    thread_local batch_scratch<uint8_t> qmask_buf;
-    uint8_t *const qmask = qmask_buf.get(qoff.back() + 1);
-    parallel_for(nq, [&](size_t x) {  // (the DP looks at the four base bits only: case does not matter)
-        const cseq &qs = *members[x]->t->input_sequence;
-        const size_t nb = qs.size();
-        uint8_t *dst = qmask + qoff[x];
-        if (const uint8_t *dense = qs.denseMasks()) memcpy(dst, dense, nb);
-        else masks_of_packed(dst, qs.packed(), nb);
-    });
-    return qmask;
-}
-
 // What the device is given of a group: one SLOT per distinct (query, ordered family, filter); every member reads one slot's results.
 struct device_slots {
     size_t dnq = 0;                   // number of slots
     std::vector<uint32_t> slot_of;    // [members] slot of group member x
     std::vector<uint64_t> dqoff;      // [dnq + 1] slot u's mask bytes -- and its aligned columns coming back -- start at dqoff[u]
-    const uint8_t *dqmask = nullptr;  // the slots' mask bytes (a thread's scratch buffer: pack_group_queries, distinct_slots)
+    const uint8_t *dqmask = nullptr;  // the slots' mask bytes (a thread's scratch buffer: distinct_slots)
     const std::vector<dp_job *> *members = nullptr;
     std::vector<uint32_t> first;  // [dnq] first member of slot u; empty if nothing repeats (slot u is member u)
     const dp_job &job(size_t u) const { return *(*members)[first.empty() ? u : first[u]]; }  // the job slot u is aligned for
@@ -2138,18 +2032,19 @@ struct device_slots {
 
 // Repeated queries -- the same bases in the same case against the same ordered family under the same filter: amplicon
 // runs are full of them -- are aligned ONCE (one DAG, one DP, one walk); every tray then finishes from the device results of its first
-// occurrence, with its own name, log and attributes (group_equal_items above).  Takes a group, packs its queries
-// (pack_group_queries); gives the slots.  Where nothing repeats the packing is handed on as it is: nothing is copied.
+// occurrence, with its own name, log and attributes (distinct.h).  Takes a group, packs its queries' mask bytes (the DP
+// looks at the four base bits only: case does not matter); gives the slots.  Where nothing repeats the packing is
+// handed on as it is: nothing is copied.
 static device_slots distinct_slots(const std::vector<dp_job *> &members) {
     scoped_phase ph("al.pack_queries");
     const size_t nq = members.size();
-    std::vector<uint64_t> qoff;
-    const uint8_t *const qmask = pack_group_queries(members, qoff);
-    device_slots s;
-    s.members = &members;
-    std::vector<uint32_t> rep;
-    s.dnq = group_equal_items(
-        nq,
+    auto seq_of = [&](size_t x) -> const cseq & { return *members[x]->t->input_sequence; };
+    const std::vector<uint64_t> qoff = offsets_of(nq, seq_of);
+    thread_local batch_scratch<uint8_t> qmask_buf;
+    uint8_t *const qmask = qmask_buf.get(qoff.back() + 1);
+    pack_masks(nq, seq_of, qoff.data(), qmask);
+    distinct_items d = distinct_spans(
+        dedup_enabled(), parallel_for, qmask, qoff.data(), nq,
         [&](size_t x) {
             const dp_job &jb = *members[x];
             uint64_t hf = 0xcbf29ce484222325ull ^ jb.family_size();
@@ -2157,39 +2052,23 @@ static device_slots distinct_slots(const std::vector<dp_job *> &members) {
                 hf = (hf ^ (uint64_t)reinterpret_cast<uintptr_t>(jb.member(y))) * 0x100000001b3ull;
                 hf ^= hf >> 29;
             }
-            hf = (hf ^ (uint64_t)reinterpret_cast<uintptr_t>(jb.t->astats)) * 0x100000001b3ull;  // (a group may hold several filters)
-            return hash_ends(qmask + qoff[x], qoff[x + 1] - qoff[x], hf);
+            return (hf ^ (uint64_t)reinterpret_cast<uintptr_t>(jb.t->astats)) * 0x100000001b3ull;  // (a group may hold several filters)
         },
         [&](size_t a, size_t b) {
             const dp_job &ja = *members[a], &jb = *members[b];
-            if (qoff[a + 1] - qoff[a] != qoff[b + 1] - qoff[b] || ja.family_size() != jb.family_size() || ja.t->astats != jb.t->astats) return false;
+            if (ja.family_size() != jb.family_size() || ja.t->astats != jb.t->astats) return false;
             for (size_t y = 0; y < ja.family_size(); y++)
                 if (ja.member(y) != jb.member(y)) return false;
-            return memcmp(qmask + qoff[a], qmask + qoff[b], qoff[a + 1] - qoff[a]) == 0;
-        },
-        rep);
-    s.slot_of.resize(nq);
-    if (s.dnq == nq) {
-        for (size_t x = 0; x < nq; x++) s.slot_of[x] = (uint32_t)x;
-        s.dqoff = std::move(qoff);
-        s.dqmask = qmask;
-        return s;
-    }
-    s.first.reserve(s.dnq);
-    s.dqoff.assign(s.dnq + 1, 0);
-    for (size_t x = 0; x < nq; x++) {
-        if (rep[x] == x) {
-            s.slot_of[x] = (uint32_t)s.first.size();
-            s.dqoff[s.first.size() + 1] = s.dqoff[s.first.size()] + (qoff[x + 1] - qoff[x]);
-            s.first.push_back((uint32_t)x);
-        } else {
-            s.slot_of[x] = s.slot_of[rep[x]];
-        }
-    }
+            return true;
+        });
     thread_local batch_scratch<uint8_t> dqmask_buf;  // (not the packing's buffer: that one is being read)
-    uint8_t *const um = dqmask_buf.get(s.dqoff.back() + 1);
-    parallel_for(s.dnq, [&](size_t u) { memcpy(um + s.dqoff[u], qmask + qoff[s.first[u]], s.dqoff[u + 1] - s.dqoff[u]); });
-    s.dqmask = um;
+    device_slots s;
+    s.members = &members;
+    s.dqmask = gather_distinct(d, parallel_for, qmask, qoff.data(), dqmask_buf);
+    s.dnq = d.n;
+    s.slot_of = std::move(d.slot_of);
+    s.dqoff = std::move(d.off);
+    s.first = std::move(d.first);
     return s;
 }
 
@@ -2431,6 +2310,9 @@ static void finish_tray(dp_job &jb, const sina_hip_align_out &r, const uint32_t 
     host_tick("finish: attributes", tk);
 }
 
+// most pairs of one comparison launch: a batch with more is compared in slices of whole queries
+constexpr uint64_t kComparePairsPerSlice = 8u << 20;
+
 // Takes n aligned sequences seq_of(x) and for each the n_ids_of(x) reference ids that put_ids(x, dst) writes, packs both and
 // compares them in ONE launch; gives the counters of sequence x against its candidate r at counts[coff[x] + r].
 struct pair_counts {
@@ -2441,12 +2323,9 @@ template <class SeqOf, class NIdsOf, class PutIds>
 static pair_counts compare_packed(sina_hip_ctx *ctx, size_t n, SeqOf &&seq_of, NIdsOf &&n_ids_of, PutIds &&put_ids, int iupac_rule,
                                   int filter_lowercase) {
     pair_counts pc;
-    std::vector<uint64_t> qoff(n + 1, 0);
+    const std::vector<uint64_t> qoff = offsets_of(n, seq_of);
     pc.coff.assign(n + 1, 0);
-    for (size_t x = 0; x < n; x++) {
-        qoff[x + 1] = qoff[x] + seq_of(x).size();
-        pc.coff[x + 1] = pc.coff[x] + n_ids_of(x);
-    }
+    for (size_t x = 0; x < n; x++) pc.coff[x + 1] = pc.coff[x] + n_ids_of(x);
     std::vector<uint32_t> qab(qoff.back() ? qoff.back() : 1), cids(pc.coff.back() ? pc.coff.back() : 1);
     for (size_t x = 0; x < n; x++) {
         const cseq &c = seq_of(x);
@@ -2899,15 +2778,20 @@ std::string lca_vote(const std::vector<std::vector<std::string>> &paths, size_t 
                          (agreed.size() > 1 && agreed.compare(agreed.size() - 2, 2, ";;") == 0);
     return nothing ? "Unclassified;" : agreed;
 }
-}  // namespace
 
-// src/search_filter.cpp:244-412 for a batch of trays: the k-mer search and the comparisons of the
-// whole batch are one GPU call each (sina_hip_kmer_topk, sina_hip_compare) -- or, with device-rank, one call for
-// both that brings down the max_result best only (sina_hip_kmer_topk_rank; search-all: sina_hip_compare_rank).
-void search_filter::operator()(std::vector<tray> &batch) {
-    const options &o = sf_opts();
-    reference_store &st = *data->arb;
-    std::vector<size_t> idx;  // trays that are searched
+// What the steps of a search-stage call share: the options, the store, the k-mer index (none: search-all), the batch.
+struct search_call {
+    const search_filter::options &o;
+    reference_store &st;
+    kmer_search *index;
+    std::vector<tray> &batch;
+    const cseq &query(size_t i) const { return *batch[i].aligned_sequence; }
+};
+
+// Takes the batch; gives the indices of the trays that are searched, each with an empty search_result -- a tray
+// without a sequence, or with one of fewer than 20 bases, gets a log line instead.
+std::vector<size_t> searched_trays(std::vector<tray> &batch) {
+    std::vector<size_t> idx;
     for (size_t i = 0; i < batch.size(); i++) {
         tray &t = batch[i];
         if (t.aligned_sequence == nullptr) {
@@ -2921,266 +2805,274 @@ void search_filter::operator()(std::vector<tray> &batch) {
         t.search_result = new search::result_vector();
         idx.push_back(i);
     }
-    if (idx.empty()) return;
-    const unsigned n_refs = st.size();
+    return idx;
+}
 
-    // ---- candidates, scores and ranking on the host: fills the search_result of trays `sub` (indices into batch)
-    auto host_rank = [&](const std::vector<size_t> &sub) {
-        const size_t nq = sub.size();
-        if (nq == 0) return;
-        std::vector<search::result_vector> cand(nq);
-        if (!o.search_all) {
-            scoped_phase ph("sf.find_batch");
-            std::vector<const cseq *> qs(nq);
-            for (size_t x = 0; x < nq; x++) qs[x] = batch[sub[x]].aligned_sequence;
-            data->index->find_batch(qs, cand, (unsigned)o.kmer_candidates);
-            if (o.ignore_super) {  // sic: partition() moves the containing ones to the front and the REST is erased
-                parallel_for(nq, [&](size_t x) {
-                    const cseq &c = *batch[sub[x]].aligned_sequence;
-                    search::result_vector kept;
-                    for (auto &r : cand[x])
-                        if (contains_query(*r.sequence, c)) kept.push_back(r);
-                    cand[x].swap(kept);
-                });
-            }
-        }
-
-        // ---- scores: one comparison launch per slice of the batch
-        {
-            scoped_phase ph("sf.compare(C-ABI)");
-            auto dev = st.worker_device(reference_store::dev_compare);
-            const uint64_t max_pairs = 8u << 20;
-            size_t x0 = 0;
-            while (x0 < nq) {
-                size_t x1 = x0;
-                uint64_t pairs = 0;
-                while (x1 < nq) {
-                    const uint64_t k = o.search_all ? n_refs : cand[x1].size();
-                    if (x1 > x0 && pairs + k > max_pairs) break;
-                    pairs += k;
-                    x1++;
-                }
-                if (pairs) {  // (a slice without a single candidate is not sent -- and has no scores to take)
-                    const pair_counts pc = compare_packed(
-                        dev.get(), x1 - x0, [&](size_t x) -> const cseq & { return *batch[sub[x0 + x]].aligned_sequence; },
-                        [&](size_t x) { return o.search_all ? (size_t)n_refs : cand[x0 + x].size(); },
-                        [&](size_t x, uint32_t *dst) {
-                            if (o.search_all) {
-                                for (unsigned r = 0; r < n_refs; r++) dst[r] = r;
-                            } else {
-                                for (size_t r = 0; r < cand[x0 + x].size(); r++) dst[r] = st.id_of(cand[x0 + x][r].sequence);
-                            }
-                        },
-                        (int)o.comparator.iupac_rule, o.comparator.filter_lc_rule ? 1 : 0);
-                    for (size_t x = x0; x < x1; x++) {
-                        const sina_hip_match_counts *m = pc.counts.data() + pc.coff[x - x0];
-                        if (o.search_all) {
-                            cand[x].clear();
-                            cand[x].reserve(n_refs);
-                            for (unsigned r = 0; r < n_refs; r++) cand[x].emplace_back(o.comparator.score(m[r]), &st.getCseq(r));
-                        } else {
-                            for (size_t r = 0; r < cand[x].size(); r++) cand[x][r].score = o.comparator.score(m[r]);
-                        }
-                    }
-                }
-                x0 = x1;
-            }
-        }
-
-        // ---- ranking, per tray
-        scoped_phase ph("sf.rank+lca");
+// Takes trays `sub` (indices into the batch); gives each its k-mer candidates, unscored: one find_batch for all, then
+// --search-ignore-super keeps those that contain the query.
+std::vector<search::result_vector> host_candidates(const search_call &s, const std::vector<size_t> &sub) {
+    scoped_phase ph("sf.find_batch");
+    const size_t nq = sub.size();
+    std::vector<search::result_vector> cand(nq);
+    std::vector<const cseq *> qs(nq);
+    for (size_t x = 0; x < nq; x++) qs[x] = &s.query(sub[x]);
+    s.index->find_batch(qs, cand, (unsigned)s.o.kmer_candidates);
+    if (s.o.ignore_super) {  // sic: partition() moves the containing ones to the front and the REST is erased
         parallel_for(nq, [&](size_t x) {
-            tray &t = batch[sub[x]];
-            cseq *c = t.aligned_sequence;
-            auto &vc = *t.search_result;
-            if (o.search_all) {
-                // every reference was compared: the `max_result` best that are not super-strings of the
-                // query (--search-ignore-super), if above --search-min-sim (behaviour of src/
-                // search_filter.cpp:271-296).  The sequence of libstdc++ calls is the contract here:
-                // the window is re-sorted from the first kept candidate to the PREVIOUS window end, then
-                // widened again, so std::partition also sees entries std::partial_sort left unordered.
-                search::result_vector &all = cand[x];
-                const auto stop = all.end();
-                auto first_kept = all.begin();
-                auto window_end = first_kept + (std::ptrdiff_t)std::min<size_t>((size_t)o.max_result, all.size());
-                for (;;) {
-                    std::partial_sort(first_kept, window_end, stop, std::greater<search::result_item>());
-                    if (o.ignore_super) {
-                        window_end = first_kept + (std::ptrdiff_t)std::min<size_t>((size_t)o.max_result, (size_t)(stop - first_kept));
-                        first_kept = std::partition(first_kept, window_end, [&](search::result_item &item) {
-                            return contains_query(*item.sequence, *c);
-                        });
-                    }
-                    const bool window_full = first_kept + o.max_result <= window_end;
-                    if (window_end == stop || window_full) break;
-                }
-                for (auto it = first_kept; it != window_end && it->score > o.min_sim; ++it) vc.push_back(*it);
-            } else {  // :297-331
-                vc.swap(cand[x]);
-                auto it = vc.begin();
-                auto middle = vc.begin() + std::min<size_t>((size_t)o.max_result, vc.size());
-                auto end = vc.end();
-                std::partial_sort(it, middle, end, std::greater<search::result_item>());
-                while (it != middle && it->score > o.min_sim) ++it;
-                vc.erase(it, vc.end());
-            }
+            search::result_vector kept;
+            for (auto &r : cand[x])
+                if (contains_query(*r.sequence, s.query(sub[x]))) kept.push_back(r);
+            cand[x].swap(kept);
         });
-    };
-
-    // ---- device-rank: score and rank on the device, the rows above min-sim into search_result.  The whole stage
-    // keeps the host path for what the device does not rank as the host does (Jukes-Cantor: rounding can merge ratios
-    // into ties; ignore-super; more rows than a wave has lanes; names that repeat; more k-mer candidates than the LDS
-    // select sorts) and when the device refuses as a limit; a query of a call goes back to it, alone, when the device
-    // flags a 0 / 0 among its candidates or cannot take the query as it is.  Nothing of this reaches a tray's log.
-    std::vector<size_t> host_trays;
-    bool on_device = o.device_rank && o.comparator.dist_rule == CMP_DIST_NONE && !o.ignore_super && o.max_result >= 1 &&
-                     o.max_result <= (int)sina_hip::kRankMaxResult &&
-                     (o.search_all || std::min<uint64_t>((uint64_t)std::max(o.kmer_candidates, 0), n_refs) <= sina_hip::kKmerSelMax) &&
-                     st.name_order_ready();
-    if (on_device) {
-        std::vector<size_t> dev_trays;  // (the device takes strictly ascending columns, at most 65535 bases)
-        for (size_t i : idx) {
-            const cseq &c = *batch[i].aligned_sequence;
-            (c.size() <= 65535 && columns_ascend(c) ? dev_trays : host_trays).push_back(i);
-        }
-        const size_t nd = dev_trays.size();
-        const uint32_t N = (uint32_t)o.max_result;
-        std::vector<uint64_t> qoff(nd + 1, 0);
-        for (size_t x = 0; x < nd; x++) qoff[x + 1] = qoff[x] + batch[dev_trays[x]].aligned_sequence->size();
-        std::vector<uint32_t> qab(qoff.back() + 1);
-        parallel_for(nd, [&](size_t x) {
-            const cseq &c = *batch[dev_trays[x]].aligned_sequence;
-            memcpy(qab.data() + qoff[x], c.packed(), 4 * (size_t)c.size());
-        });
-        // rows of the distinct queries (identical queries are sent once, as find_batch sends them)
-        std::vector<uint32_t> rep, slot_of(nd), firsts;
-        const size_t nu = group_equal_items(
-            nd, [&](size_t i) { return hash_ends(qab.data() + qoff[i], 4 * (qoff[i + 1] - qoff[i]), qoff[i + 1] - qoff[i]); },
-            [&](size_t a, size_t b) {
-                return qoff[a + 1] - qoff[a] == qoff[b + 1] - qoff[b] &&
-                       memcmp(qab.data() + qoff[a], qab.data() + qoff[b], 4 * (qoff[a + 1] - qoff[a])) == 0;
-            },
-            rep);
-        std::vector<uint64_t> uoff(nu + 1, 0);
-        for (size_t i = 0; i < nd; i++) {
-            if (rep[i] == i) {
-                slot_of[i] = (uint32_t)firsts.size();
-                uoff[firsts.size() + 1] = uoff[firsts.size()] + (qoff[i + 1] - qoff[i]);
-                firsts.push_back((uint32_t)i);
-            } else {
-                slot_of[i] = slot_of[rep[i]];
-            }
-        }
-        std::vector<uint32_t> uab_store;
-        const uint32_t *uab = qab.data();
-        if (nu != nd) {
-            uab_store.resize(uoff.back() + 1);
-            parallel_for(nu, [&](size_t u) { memcpy(uab_store.data() + uoff[u], qab.data() + qoff[firsts[u]], 4 * (uoff[u + 1] - uoff[u])); });
-            uab = uab_store.data();
-        }
-        std::vector<uint32_t> ids(nu * N + 1), cnt(nu + 1), flag(nu + 1);
-        std::vector<float> sc(nu * N + 1);
-        bool limit = false;
-        auto call = [&](int rc, const char *what) {  // a limit sends the stage back to the host path; anything else is an error
-            if (rc == 0) return true;
-            if (sina_hip_last_error_is_limit() != 1) hip_check(rc, what);
-            limit = true;
-            return false;
-        };
-        if (nu) {
-            scoped_phase ph("sf.device_rank(C-ABI)");
-            if (!o.search_all) {
-                st.ensure_index((unsigned)o.fs_kmer_len, o.fs_no_fast);
-                auto dev = st.worker_device(reference_store::dev_search);
-                call(sina_hip_kmer_topk_rank(dev.get(), uab, uoff.data(), (uint32_t)nu, (uint32_t)o.kmer_candidates,
-                                             (int)o.comparator.iupac_rule, o.comparator.filter_lc_rule ? 1 : 0, (int)o.comparator.cover_rule,
-                                             N, ids.data(), sc.data(), cnt.data(), flag.data()),
-                     "sina_hip_kmer_topk_rank");
-            } else {
-                auto dev = st.worker_device(reference_store::dev_compare);
-                const uint64_t max_pairs = 8u << 20;  // (slices as the host path cuts them)
-                const size_t per = (size_t)std::max<uint64_t>(1, max_pairs / std::max(n_refs, 1u));
-                for (size_t u0 = 0; u0 < nu && !limit; u0 += per) {
-                    const size_t u1 = std::min(nu, u0 + per);
-                    call(sina_hip_compare_rank(dev.get(), uab, uoff.data() + u0, (uint32_t)(u1 - u0), nullptr, nullptr,
-                                               (int)o.comparator.iupac_rule, o.comparator.filter_lc_rule ? 1 : 0,
-                                               (int)o.comparator.cover_rule, N, ids.data() + u0 * N, sc.data() + u0 * N, cnt.data() + u0,
-                                               flag.data() + u0),
-                         "sina_hip_compare_rank");
-                }
-            }
-        }
-        if (limit) {
-            on_device = false;
-        } else {
-            uint64_t ranked = 0;
-            for (size_t x = 0; x < nd; x++) {
-                const size_t u = slot_of[x];
-                if (flag[u] & 1u) {
-                    host_trays.push_back(dev_trays[x]);
-                    continue;
-                }
-                auto &vc = *batch[dev_trays[x]].search_result;
-                for (uint32_t r = 0; r < cnt[u] && sc[u * N + r] > o.min_sim; r++) vc.emplace_back(sc[u * N + r], &st.getCseq(ids[u * N + r]));
-                ranked++;
-            }
-            st.count_ranked(ranked, host_trays.size());
-            // (a flagged query "alone, in a call of its own": its candidates hold the NaN the host orders as it does)
-            std::sort(host_trays.begin(), host_trays.end());
-            for (size_t i : host_trays) host_rank(std::vector<size_t>{i});
-        }
     }
-    if (!on_device) {
-        if (o.device_rank) st.count_ranked(0, idx.size());
-        host_rank(idx);
-    }
+    return cand;
+}
 
-    // ---- attributes, per tray
-    scoped_phase ph("sf.rank+lca");
-    parallel_for(idx.size(), [&](size_t x) {
-        tray &t = batch[idx[x]];
-        cseq *c = t.aligned_sequence;
-        auto &vc = *t.search_result;
-        std::string nearest;
-        std::map<std::string, std::vector<std::vector<std::string>>> group_names_map;
-        for (auto &i : vc) {
-            const cseq &r = *i.sequence;
-            st.loadKey(r, "acc");
-            st.loadKey(r, "version");
-            st.loadKey(r, "start");
-            st.loadKey(r, "stop");
-            for (const std::string &s : o.v_lca_fields) {
-                st.loadKey(r, s);
-                std::string tax_path = r.get_attr<std::string>(s);
-                if (tax_path == "Unclassified;") continue;
-                std::vector<std::string> group_names;  // boost::split(..., is_any_of(";"))
-                std::string cur;
-                for (char ch : tax_path) {
-                    if (ch == ';') {
-                        group_names.push_back(cur);
-                        cur.clear();
+// Takes trays `sub` and their candidates; gives every candidate its score -- search-all: fills cand[x] with every
+// reference of the store, scored.  One comparison launch per slice of kComparePairsPerSlice pairs.
+void host_scores(const search_call &s, const std::vector<size_t> &sub, std::vector<search::result_vector> &cand) {
+    scoped_phase ph("sf.compare(C-ABI)");
+    const search_filter::options &o = s.o;
+    const unsigned n_refs = s.st.size();
+    const size_t nq = sub.size();
+    auto dev = s.st.worker_device(reference_store::dev_compare);
+    for (size_t x0 = 0, x1; x0 < nq; x0 = x1) {
+        uint64_t pairs = 0;
+        x1 = x0;
+        while (x1 < nq) {
+            const uint64_t k = o.search_all ? n_refs : cand[x1].size();
+            if (x1 > x0 && pairs + k > kComparePairsPerSlice) break;
+            pairs += k;
+            x1++;
+        }
+        if (pairs) {  // (a slice without a single candidate is not sent -- and has no scores to take)
+            const pair_counts pc = compare_packed(
+                dev.get(), x1 - x0, [&](size_t x) -> const cseq & { return s.query(sub[x0 + x]); },
+                [&](size_t x) { return o.search_all ? (size_t)n_refs : cand[x0 + x].size(); },
+                [&](size_t x, uint32_t *dst) {
+                    if (o.search_all) {
+                        for (unsigned r = 0; r < n_refs; r++) dst[r] = r;
                     } else {
-                        cur += ch;
+                        for (size_t r = 0; r < cand[x0 + x].size(); r++) dst[r] = s.st.id_of(cand[x0 + x][r].sequence);
                     }
+                },
+                (int)o.comparator.iupac_rule, o.comparator.filter_lc_rule ? 1 : 0);
+            for (size_t x = x0; x < x1; x++) {
+                const sina_hip_match_counts *m = pc.counts.data() + pc.coff[x - x0];
+                if (o.search_all) {
+                    cand[x].clear();
+                    cand[x].reserve(n_refs);
+                    for (unsigned r = 0; r < n_refs; r++) cand[x].emplace_back(o.comparator.score(m[r]), &s.st.getCseq(r));
+                } else {
+                    for (size_t r = 0; r < cand[x].size(); r++) cand[x][r].score = o.comparator.score(m[r]);
                 }
-                group_names.push_back(cur);
-                if (group_names.back().empty() || group_names.back() == " ") group_names.pop_back();
-                group_names_map[s].push_back(group_names);
-            }
-            char buf[64];
-            snprintf(buf, sizeof buf, "~%.3f ", (double)i.score);  // fmt "{}.{}.{}.{}~{:.3f} "
-            nearest += r.get_attr<std::string>("acc") + "." + r.get_attr<std::string>("version") + "." +
-                       r.get_attr<std::string>("start") + "." + r.get_attr<std::string>("stop") + buf;
-            const std::string acc = r.get_attr<std::string>("acc");
-            for (const std::string &s : o.v_copy_fields) {
-                st.loadKey(r, s);
-                c->set_attr<std::string>(std::string("copy_") + acc + std::string("_") + s, r.get_attr<std::string>(s));
             }
         }
-        c->set_attr<std::string>(fn_nearest, nearest);
-        for (const std::string &s : o.v_lca_fields)
-            c->set_attr<std::string>(std::string("lca_") + s, lca_vote(group_names_map[s], vc.size(), o.lca_quorum));
+    }
+}
+
+// Search-all.  Takes query c and every reference of the store, scored (`all`, reordered); appends the result rows to vc.
+void rank_all(const search_filter::options &o, const cseq &c, search::result_vector &all, search::result_vector &vc) {
+    // every reference was compared: the `max_result` best that are not super-strings of the
+    // query (--search-ignore-super), if above --search-min-sim (behaviour of src/
+    // search_filter.cpp:271-296).  The sequence of libstdc++ calls is the contract here:
+    // the window is re-sorted from the first kept candidate to the PREVIOUS window end, then
+    // widened again, so std::partition also sees entries std::partial_sort left unordered.
+    const auto stop = all.end();
+    auto first_kept = all.begin();
+    auto window_end = first_kept + (std::ptrdiff_t)std::min<size_t>((size_t)o.max_result, all.size());
+    for (;;) {
+        std::partial_sort(first_kept, window_end, stop, std::greater<search::result_item>());
+        if (o.ignore_super) {
+            window_end = first_kept + (std::ptrdiff_t)std::min<size_t>((size_t)o.max_result, (size_t)(stop - first_kept));
+            first_kept = std::partition(first_kept, window_end, [&](search::result_item &item) {
+                return contains_query(*item.sequence, c);
+            });
+        }
+        const bool window_full = first_kept + o.max_result <= window_end;
+        if (window_end == stop || window_full) break;
+    }
+    for (auto it = first_kept; it != window_end && it->score > o.min_sim; ++it) vc.push_back(*it);
+}
+
+// src/search_filter.cpp:297-331.  Takes a query's scored k-mer candidates (taken over); gives vc the `max_result` best
+// in order, cut at the first not above --search-min-sim.
+void rank_candidates(const search_filter::options &o, search::result_vector &cand, search::result_vector &vc) {
+    vc.swap(cand);
+    auto it = vc.begin();
+    auto middle = vc.begin() + std::min<size_t>((size_t)o.max_result, vc.size());
+    auto end = vc.end();
+    std::partial_sort(it, middle, end, std::greater<search::result_item>());
+    while (it != middle && it->score > o.min_sim) ++it;
+    vc.erase(it, vc.end());
+}
+
+// Candidates, scores and ranking on the host: fills the search_result of trays `sub` (indices into the batch).
+void host_rank(const search_call &s, const std::vector<size_t> &sub) {
+    const size_t nq = sub.size();
+    if (nq == 0) return;
+    std::vector<search::result_vector> cand = s.o.search_all ? std::vector<search::result_vector>(nq) : host_candidates(s, sub);
+    host_scores(s, sub, cand);
+    scoped_phase ph("sf.rank+lca");
+    parallel_for(nq, [&](size_t x) {
+        search::result_vector &vc = *s.batch[sub[x]].search_result;
+        if (s.o.search_all) rank_all(s.o, s.query(sub[x]), cand[x], vc);
+        else rank_candidates(s.o, cand[x], vc);
     });
+}
+
+// What comes back from the device's ranking, per distinct query u: cnt[u] rows at ids / sc [u * N], best first, and
+// flag[u] (bit 0: a 0 / 0 among its candidates, or a query the device cannot take as it is).
+struct device_rows {
+    std::vector<uint32_t> ids, cnt, flag;
+    std::vector<float> sc;
+    device_rows(size_t nu, uint32_t N) : ids(nu * N + 1), cnt(nu + 1), flag(nu + 1), sc(nu * N + 1) {}
+};
+
+// Takes the distinct queries as packed words (slot u at uab + d.off[u]) and ranks them on the device: one call of
+// sina_hip_kmer_topk_rank for all, or -- search-all -- sina_hip_compare_rank per slice as the host path cuts them.
+// Gives the rows, and false if the device refused as a limit (anything else it reports is an error).
+bool device_rank_calls(const search_call &s, const distinct_items &d, const uint32_t *uab, uint32_t N, device_rows &rows) {
+    const search_filter::options &o = s.o;
+    const size_t nu = d.n;
+    auto ok = [](int rc, const char *what) {  // a limit sends the stage back to the host path; anything else is an error
+        if (rc != 0 && sina_hip_last_error_is_limit() != 1) hip_check(rc, what);
+        return rc == 0;
+    };
+    if (nu == 0) return true;
+    scoped_phase ph("sf.device_rank(C-ABI)");
+    if (!o.search_all) {
+        s.st.ensure_index((unsigned)o.fs_kmer_len, o.fs_no_fast);
+        auto dev = s.st.worker_device(reference_store::dev_search);
+        return ok(sina_hip_kmer_topk_rank(dev.get(), uab, d.off.data(), (uint32_t)nu, (uint32_t)o.kmer_candidates,
+                                          (int)o.comparator.iupac_rule, o.comparator.filter_lc_rule ? 1 : 0, (int)o.comparator.cover_rule,
+                                          N, rows.ids.data(), rows.sc.data(), rows.cnt.data(), rows.flag.data()),
+                  "sina_hip_kmer_topk_rank");
+    }
+    auto dev = s.st.worker_device(reference_store::dev_compare);
+    const size_t per = (size_t)std::max<uint64_t>(1, kComparePairsPerSlice / std::max(s.st.size(), 1u));
+    for (size_t u0 = 0; u0 < nu; u0 += per) {
+        const size_t u1 = std::min(nu, u0 + per);
+        if (!ok(sina_hip_compare_rank(dev.get(), uab, d.off.data() + u0, (uint32_t)(u1 - u0), nullptr, nullptr,
+                                      (int)o.comparator.iupac_rule, o.comparator.filter_lc_rule ? 1 : 0, (int)o.comparator.cover_rule,
+                                      N, rows.ids.data() + u0 * N, rows.sc.data() + u0 * N, rows.cnt.data() + u0, rows.flag.data() + u0),
+                "sina_hip_compare_rank"))
+            return false;
+    }
+    return true;
+}
+
+// device-rank: score and rank on the device, the rows above min-sim into search_result.  Takes the searched trays;
+// fills their results and gives true -- or false, with nothing filled: the whole stage then keeps the host path, for
+// what the device does not rank as the host does (Jukes-Cantor: rounding can merge ratios into ties; ignore-super;
+// more rows than a wave has lanes; names that repeat; more k-mer candidates than the LDS select sorts) and when the
+// device refuses as a limit.  A query goes back to the host path, alone, when its columns do not ascend strictly, it
+// has more than 65535 bases, or the device flags it.  Nothing of this reaches a tray's log.
+bool device_rank(const search_call &s, const std::vector<size_t> &idx) {
+    const search_filter::options &o = s.o;
+    if (!(o.device_rank && o.comparator.dist_rule == CMP_DIST_NONE && !o.ignore_super && o.max_result >= 1 &&
+          o.max_result <= (int)sina_hip::kRankMaxResult &&
+          (o.search_all || std::min<uint64_t>((uint64_t)std::max(o.kmer_candidates, 0), s.st.size()) <= sina_hip::kKmerSelMax) &&
+          s.st.name_order_ready()))
+        return false;
+    std::vector<size_t> dev_trays, host_trays;
+    for (size_t i : idx) {
+        const cseq &c = s.query(i);
+        (c.size() <= 65535 && columns_ascend(c) ? dev_trays : host_trays).push_back(i);
+    }
+    const size_t nd = dev_trays.size();
+    const uint32_t N = (uint32_t)s.o.max_result;
+    auto seq_of = [&](size_t x) -> const cseq & { return s.query(dev_trays[x]); };
+    const std::vector<uint64_t> qoff = offsets_of(nd, seq_of);
+    batch_scratch<uint32_t> qab_buf, uab_buf;
+    uint32_t *const qab = qab_buf.get(qoff.back() + 1);
+    pack_words(nd, seq_of, qoff.data(), qab);
+    // rows of the distinct queries (identical queries are sent once, as find_batch sends them)
+    const distinct_items d = distinct_spans(dedup_enabled(), parallel_for, qab, qoff.data(), nd);
+    const uint32_t *const uab = gather_distinct(d, parallel_for, qab, qoff.data(), uab_buf);
+    device_rows rows(d.n, N);
+    if (!device_rank_calls(s, d, uab, N, rows)) return false;
+    uint64_t ranked = 0;
+    for (size_t x = 0; x < nd; x++) {
+        const size_t u = d.slot_of[x];
+        if (rows.flag[u] & 1u) {
+            host_trays.push_back(dev_trays[x]);
+            continue;
+        }
+        auto &vc = *s.batch[dev_trays[x]].search_result;
+        for (uint32_t r = 0; r < rows.cnt[u] && rows.sc[u * N + r] > s.o.min_sim; r++)
+            vc.emplace_back(rows.sc[u * N + r], &s.st.getCseq(rows.ids[u * N + r]));
+        ranked++;
+    }
+    s.st.count_ranked(ranked, host_trays.size());
+    // (a flagged query "alone, in a call of its own": its candidates hold the NaN the host orders as it does)
+    std::sort(host_trays.begin(), host_trays.end());
+    for (size_t i : host_trays) host_rank(s, std::vector<size_t>{i});
+    return true;
+}
+
+// boost::split(..., is_any_of(";")) of a taxonomy path, without the empty (or " ") group after the last ';'
+void split_tax_path(const std::string &tax_path, std::vector<std::string> &group_names) {
+    std::string cur;
+    for (char ch : tax_path) {
+        if (ch == ';') {
+            group_names.push_back(cur);
+            cur.clear();
+        } else {
+            cur += ch;
+        }
+    }
+    group_names.push_back(cur);
+    if (group_names.back().empty() || group_names.back() == " ") group_names.pop_back();
+}
+
+// Takes a searched tray with its result rows; gives its sequence nearest_slv, the copied fields of every row's
+// reference and the LCA classification per --lca-fields field (src/search_filter.cpp:333-411).
+void annotate_tray(const search_filter::options &o, reference_store &st, tray &t) {
+    cseq *c = t.aligned_sequence;
+    auto &vc = *t.search_result;
+    std::string nearest;
+    std::map<std::string, std::vector<std::vector<std::string>>> group_names_map;
+    for (auto &i : vc) {
+        const cseq &r = *i.sequence;
+        for (const char *key : {"acc", "version", "start", "stop"}) st.loadKey(r, key);
+        for (const std::string &s : o.v_lca_fields) {
+            st.loadKey(r, s);
+            std::string tax_path = r.get_attr<std::string>(s);
+            if (tax_path == "Unclassified;") continue;
+            std::vector<std::string> group_names;
+            split_tax_path(tax_path, group_names);
+            group_names_map[s].push_back(group_names);
+        }
+        char buf[64];
+        snprintf(buf, sizeof buf, "~%.3f ", (double)i.score);  // fmt "{}.{}.{}.{}~{:.3f} "
+        nearest += r.get_attr<std::string>("acc") + "." + r.get_attr<std::string>("version") + "." +
+                   r.get_attr<std::string>("start") + "." + r.get_attr<std::string>("stop") + buf;
+        const std::string acc = r.get_attr<std::string>("acc");
+        for (const std::string &s : o.v_copy_fields) {
+            st.loadKey(r, s);
+            c->set_attr<std::string>(std::string("copy_") + acc + std::string("_") + s, r.get_attr<std::string>(s));
+        }
+    }
+    c->set_attr<std::string>(search_filter::fn_nearest, nearest);
+    for (const std::string &s : o.v_lca_fields)
+        c->set_attr<std::string>(std::string("lca_") + s, lca_vote(group_names_map[s], vc.size(), o.lca_quorum));
+}
+}  // namespace
+
+// src/search_filter.cpp:244-412 for a batch of trays: the k-mer search and the comparisons of the
+// whole batch are one GPU call each (sina_hip_kmer_topk, sina_hip_compare) -- or, with device-rank, one call for
+// both that brings down the max_result best only (sina_hip_kmer_topk_rank; search-all: sina_hip_compare_rank).
+void search_filter::operator()(std::vector<tray> &batch) {
+    const search_call s{sf_opts(), *data->arb, data->index, batch};
+    const std::vector<size_t> idx = searched_trays(batch);
+    if (idx.empty()) return;
+    if (!device_rank(s, idx)) {
+        if (s.o.device_rank) s.st.count_ranked(0, idx.size());
+        host_rank(s, idx);
+    }
+    scoped_phase ph("sf.rank+lca");
+    parallel_for(idx.size(), [&](size_t x) { annotate_tray(s.o, s.st, batch[idx[x]]); });
 }
 
 }  // namespace sina

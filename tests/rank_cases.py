@@ -353,3 +353,21 @@ def stage_reference_run(name):
             assert [rank_ref.bits(x) for x in want_sc] == r_bits[:cut], (name, qi)
         out.append(dict(ids=want_ids, scores=want_sc, nan=nan))
     return out
+
+
+# ---------------------------------------------------------------- repeated queries (one batch, dedup is per batch)
+# kind of queries -> the stage case it runs under.  30 trays of which 12 are distinct, all in one batch.
+REPEAT_STAGE = {"full": "query", "fragments": "overlap_fragments"}
+REPEAT_SEED = 660
+
+
+def stage_repeat_pick(kind):
+    """(distinct, pick): twelve of the kind's queries, ascending, and the 30 trays -- every one of the twelve at least
+    once, eighteen more drawn among them, shuffled.  tests/test_rank_cpu.py asserts that the fragments' pick repeats a
+    query the reference flags."""
+    n = stage_queries(kind, 300).n
+    rng = np.random.default_rng(REPEAT_SEED)
+    distinct = np.sort(rng.choice(n, 12, replace=False))
+    pick = np.concatenate([distinct, rng.choice(distinct, 18)])
+    rng.shuffle(pick)
+    return distinct, pick

@@ -14,9 +14,10 @@ from tests import msc_cases as mc
 pytestmark = pytest.mark.gpu
 
 
-def _run(st, ff, batch):
+def _run(st, ff, batch, copies=1, dedup=True):
     names, seqs, _ = mc.leaveout_queries()
-    pl = pipeline.Pipeline(st, famfinder=ff)
+    names, seqs = names * copies, seqs * copies
+    pl = pipeline.Pipeline(st, famfinder=ff, dedup=dedup)
     try:
         s0 = st.match_stats()
         pl.run_aligned(cc.flat(seqs), cc.offsets(seqs), names, batch=batch, inflight=1)
@@ -117,3 +118,28 @@ def test_nothing_is_launched_without_an_identity_limit(world):
     got, d = _run(st, ff, 3)
     assert d["pairs"] == 0 and d["launches"] == 0
     assert all(len(r["family"]) for r in got)
+
+
+def test_repeated_queries_are_searched_once(world, runs):
+    """The query list followed by a second copy of itself, same names, in one batch: every tray is what the single list
+    gave -- the shifted query (equal mask bytes at other columns) does not merge with the member it was made from, the
+    query with equal columns takes the pass without counts -- with device-msc off and on, the batch's repeats grouped
+    and not.  Grouped, the device counts the pairs of the single list; not grouped, twice that: the same set of
+    distinct queries is in every escalation round."""
+    st = world[0]
+    names, seqs, kinds = mc.leaveout_queries()
+    assert isinstance(names, list) and isinstance(seqs, list) and {"shifted", "equal_columns"} <= set(kinds)
+    base, _ = runs[0, len(names)]
+    single = runs[1, len(names)][1]["pairs"]
+    assert single > 0
+    for on in (0, 1):
+        for dedup in (True, False):
+            got, d = _run(st, dict(mc.LEAVEOUT_FF, **{"device-msc": on}), 2 * len(names), copies=2, dedup=dedup)
+            assert len(got) == 2 * len(names)
+            for t, b in enumerate(got):
+                a = base[t % len(names)]
+                tag = (on, dedup, t, names[t % len(names)], kinds[t % len(names)])
+                assert a["status"] == b["status"] and a["family"] == b["family"] and a["log"] == b["log"], tag
+                assert a["packed"].tobytes() == b["packed"].tobytes() and a["qual"] == b["qual"], tag
+                assert (a["head"], a["tail"], a["width"]) == (b["head"], b["tail"], b["width"]), tag
+            assert d["pairs"] == (0 if not on else single if dedup else 2 * single), (on, dedup, d, single)

@@ -21,13 +21,13 @@ def _annotate(st, n):
         st.set_attr(i, "tax_slv", rc.stage_taxonomy(i))
 
 
-def _run(st, qs, sopts, device_rank):
+def _run(st, qs, sopts, device_rank, batch=10, inflight=2, dedup=True):
     search = dict({"lca-fields": "tax_slv"}, **sopts)
     if device_rank is not None:
         search["device-rank"] = device_rank
     before = st.rank_stats()
-    pl = pipeline.Pipeline(st, famfinder=rc.STAGE_FF, aligner={"realign": True}, search=search)
-    pl.run(qs.mask, qs.off, batch=10, inflight=2)
+    pl = pipeline.Pipeline(st, famfinder=rc.STAGE_FF, aligner={"realign": True}, search=search, dedup=dedup)
+    pl.run(qs.mask, qs.off, batch=batch, inflight=inflight)
     out = []
     for q in range(qs.n):
         r = pl.result(q)
@@ -119,5 +119,50 @@ def test_stage_repeated_name_keeps_the_host_path(tmp_path):
         on, d = _run(st, qs, {"search-min-sim": 0.0}, True)
         _same(off, on)
         assert d["ranked"] == 0 and d["launches"] == 0 and d["fallen_back"] == sum(1 for r in on if r["ids"] is not None) >= 10
+    finally:
+        st.close()
+
+
+@pytest.mark.parametrize("kind", sorted(rc.REPEAT_STAGE))
+def test_stage_repeated_queries_go_to_the_device_once(kind):
+    """30 trays in one batch of which 12 are distinct (rc.stage_repeat_pick): device-rank off and on, each with the
+    batch's repeats grouped and not, give the same trays -- for the whole queries the reference's, row for row through
+    the pick.  With the repeats grouped the device compares what a run over the twelve alone compares, without them
+    more; every searched tray counts as ranked or sent back, and a flag on a slot sends every tray that reads the slot
+    back to the host."""
+    name = rc.REPEAT_STAGE[kind]
+    sopts = rc.STAGE[name][0]
+    refs = rc.stage_refs(300)
+    base = rc.stage_queries(kind, 300)
+    distinct, pick = rc.stage_repeat_pick(kind)
+    qs = synth.pick_queries(base, pick)
+    ref_run = rc.stage_reference_run(name)
+    assert qs.n == 30 and len(distinct) == 12
+    st = pipeline.Store(":mem:rank-stage-repeats-%s" % kind, refs)
+    try:
+        _annotate(st, refs.n)
+        runs = {(on, dedup): _run(st, qs, sopts, on, batch=30, inflight=1, dedup=dedup) for on in (False, True) for dedup in (True, False)}
+        first = runs[False, True][0]
+        for got, _ in runs.values():
+            _same(first, got)
+        searched = sum(1 for r in first if r["ids"] is not None)
+        assert searched == sum(1 for q in pick if ref_run[q] is not None) >= 10
+        if kind == "full":
+            for t, q in enumerate(pick):
+                r = ref_run[q]
+                assert (first[t]["ids"] is None) == (r is None), t
+                if r is not None:
+                    assert first[t]["ids"].tolist() == list(r["ids"]), t
+                    assert util.f32_bits(first[t]["scores"]).tolist() == util.f32_bits(r["scores"]).tolist(), t
+        _, alone = _run(st, synth.pick_queries(base, distinct), sopts, True, batch=12, inflight=1, dedup=True)
+        d_on, d_off = runs[True, True][1], runs[True, False][1]
+        assert d_on["pairs"] == alone["pairs"] > 0 and d_off["pairs"] > alone["pairs"]
+        flagged = sum(1 for q in pick if ref_run[q] is not None and ref_run[q]["nan"])
+        assert (flagged > 0) == (kind == "fragments")
+        for d in (d_on, d_off):
+            assert d["ranked"] + d["fallen_back"] == searched and d["fallen_back"] == flagged
+        for dedup in (True, False):
+            d = runs[False, dedup][1]
+            assert d["ranked"] == 0 and d["fallen_back"] == 0 and d["pairs"] == 0
     finally:
         st.close()

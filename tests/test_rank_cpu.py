@@ -132,6 +132,24 @@ def test_stage_worlds_against_the_reference(oracle, name):
         assert flagged == 0
 
 
+def test_repeat_pick_repeats_a_flagged_query(oracle):
+    """The precondition of test_gpu_rank_stage.py's test of repeated queries: 30 trays, 12 distinct queries, and among
+    the fragments' a query that the reference flags (a NaN among its candidates' scores) is picked more than once --
+    so is one that it does not flag."""
+    for kind, name in rc.REPEAT_STAGE.items():
+        distinct, pick = rc.stage_repeat_pick(kind)
+        assert len(pick) == 30 and len(distinct) == 12 and sorted(set(pick.tolist())) == distinct.tolist()
+        run = rc.stage_reference_run(name)
+        times = np.bincount(pick, minlength=len(run))
+        assert all(run[q] is not None for q in distinct)
+        flagged = [int(q) for q in distinct if run[q]["nan"]]
+        if kind == "fragments":
+            assert any(times[q] >= 2 for q in flagged)
+            assert any(times[q] >= 2 for q in distinct if not run[q]["nan"])
+        else:
+            assert not flagged
+
+
 def test_rank_plan_against_plain_arithmetic(tmp_path):
     cxx = shutil.which("g++")
     if not cxx:
