@@ -263,6 +263,35 @@ int sina_hip_kmer_topk_rank(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint6
                             uint32_t max_result, uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint32_t *out_flag);
 int sina_hip_rank_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches);
 
+/* ------------------------------------------------------------- helix base-pair score (align_bp_score_slv)
+ * The counting behind cseq_base::calcPairScore (src/cseq.cpp:651-733), which Log::printer::operator() calls for every
+ * aligned sequence (src/log.cpp:383-385): for every column i the helix map pairs with a column p = pairs[i] != 0, the
+ * characters the sequence shows at i and at p -- its base's RNA IUPAC character, '-' where no word holds that column
+ * (a partner of 2^24 or more included), '.' for a word without mask bits.  A visit counts unless one side is '.' or
+ * both are '-'; of the counted visits the kernel tells the unordered pairs AG, AU, CG, GG, GU of upper-case
+ * unambiguous bases apart (every other combination weighs nothing).  The weighted sum and the float division stay
+ * with the caller (host/cseq.h, pair_score_from_counts).  The map need not be symmetric, nor as long as the alignment
+ * is wide; a symmetric map visits every pair twice and both visits count.
+ *
+ * sina_hip_upload_pairs: the helix map, pairs[i] = partner column of column i or 0 (unpaired), compacted on the host
+ * to the paired columns (csrc/pair_plan.h) and kept with the store: forked contexts see it, a forked context cannot
+ * call it, a second upload replaces the first, n == 0 or an all-zero map removes it.  sina_hip_upload_refs leaves it
+ * alone.  Not while pair counts are in flight on the store's contexts.
+ *
+ * sina_hip_pair_counts: nq finished aligned sequences as packed words (q_ab / q_off as sina_hip_match_count takes
+ * them, sub-ranges of larger offset arrays included) -> counts [nq][6] = num, AG, AU, CG, GG, GU.  A word's column
+ * is found by lower_bound: columns must ascend, equal neighbours are fine (the first of them is the one that is
+ * read).  Refused with a message, before anything runs and with counts untouched: a null argument, no map uploaded,
+ * offsets or a sequence's columns that descend.  nq == 0 succeeds and touches nothing.  One launch per range of
+ * sequences (csrc/pair_plan.h: 2^26 words at most, one sequence at least).
+ *
+ * sina_hip_pair_stats: the pair-count kernel's own time (events around its launches) and volume on this context since
+ * init / fork: sequences counted, map entries visited (sequences x entries), launches. */
+int sina_hip_upload_pairs(sina_hip_ctx *ctx, const uint32_t *pairs, uint32_t n);
+int sina_hip_pair_counts(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t *counts);
+int sina_hip_pair_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *sequences, uint64_t *entries_visited,
+                        uint64_t *launches);
+
 /* ------------------------------------------------------------- alignment
  * Replaces, for a batch of queries: mseq::mseq + sort + reduce_edges
  * (src/mseq.cpp:47-118, src/graph.h:451-488) when given family ids, compute()

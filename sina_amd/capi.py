@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "sina_hip_align_graphs_wsets", "sina_hip_align_families_wsets",
     "sina_hip_match_count", "sina_hip_kmer_topk_match", "sina_hip_match_stats",
     "sina_hip_upload_name_order", "sina_hip_compare_rank", "sina_hip_kmer_topk_rank", "sina_hip_rank_stats",
+    "sina_hip_upload_pairs", "sina_hip_pair_counts", "sina_hip_pair_stats",
 ]
 
 # include/sina_hip.h: SINA_CMP_COVER_*, in CMP_COVER_TYPE's order
@@ -153,6 +154,9 @@ def load():
     L.sina_hip_kmer_topk_rank.argtypes = [vp, u32p, u64p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32, u32p,
                                           f32p, u32p, u32p]
     L.sina_hip_rank_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
+    L.sina_hip_upload_pairs.argtypes = [vp, u32p, C.c_uint32]
+    L.sina_hip_pair_counts.argtypes = [vp, u32p, u64p, C.c_uint32, u32p]
+    L.sina_hip_pair_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
     L.sina_hip_last_error_is_limit.restype = C.c_int
     L.sina_hip_debug_mesh_wide.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
                                            u32p, u32p, f32p]
@@ -496,6 +500,29 @@ class Context:
         pairs, bases, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.sina_hip_rank_stats(self.h, C.byref(ms), C.byref(pairs), C.byref(bases), C.byref(launches)))
         return dict(kernel_ms=float(ms.value), pairs=int(pairs.value), cand_bases=int(bases.value), launches=int(launches.value))
+
+    def upload_pairs(self, pairs):
+        """The helix map for pair_counts: pairs[i] = partner column of column i, 0 = unpaired.  Empty or all zero: no map."""
+        pairs = _c(pairs, np.uint32)
+        self._check(self.L.sina_hip_upload_pairs(self.h, _ptr(pairs, u32p), len(pairs)))
+
+    def pair_counts(self, q_ab, q_off, out=None):
+        """The counters behind align_bp_score_slv: uint32 [nq, 6] = num, AG, AU, CG, GG, GU of every finished aligned
+        sequence (packed words column | mask << 24, columns ascending).  out: the array to write into."""
+        q_ab = _c(q_ab, np.uint32)
+        q_off = _c(q_off, np.uint64)
+        nq = len(q_off) - 1
+        counts = out if out is not None else np.zeros((nq, 6), np.uint32)
+        self._check(self.L.sina_hip_pair_counts(self.h, _ptr(q_ab, u32p), _ptr(q_off, u64p), nq, _ptr(counts, u32p)))
+        return counts
+
+    def pair_stats(self):
+        """The pair-count kernel on this context so far: dict(kernel_ms, sequences, entries_visited, launches)."""
+        ms = C.c_double()
+        seqs, ent, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.sina_hip_pair_stats(self.h, C.byref(ms), C.byref(seqs), C.byref(ent), C.byref(launches)))
+        return dict(kernel_ms=float(ms.value), sequences=int(seqs.value), entries_visited=int(ent.value),
+                    launches=int(launches.value))
 
     def align_families(self, fam_ids, fam_off, qmask, qoff, params=None):
         params = params or self.params()

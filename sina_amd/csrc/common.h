@@ -31,6 +31,7 @@ void set_limit_error(const std::string &msg);
 //   SINA_HIP_TEST="key=value;..."        test hooks (tests/ only): geom=T,B  generic=1  dense_div=N  lds_kb=N  rho=X  kmer_rows=1  bt_lanes=0/1  scout=0  scout_add=X  scout_set=X
 //                                        wide=1 (every query of sina_hip_align_graphs_any takes the wide kernel)  wide_cells=N (its budget, cells per launch)
 //                                        match_floor=N  match_loads=1 (the match-count kernel's chunk floor / one load in flight: tools/perf_msc.py)
+//                                        pair_words=N (words per launch range of the pair-count kernel, pairs.hip)
 // value of `key` in SINA_HIP_TEST ("" if absent); read every time: tests change it between calls
 inline std::string test_knob(const char *key) {
     const char *e = getenv("SINA_HIP_TEST");

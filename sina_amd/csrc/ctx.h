@@ -31,6 +31,10 @@ struct sina_hip_store {
     // every reference's name in ascending order, and its inverse; forgotten when the references change
     sina_hip::DevBuf name_rank, name_inv;
     bool have_name_order = false;
+    // The helix map for the base-pair count (pairs.hip, sina_hip_upload_pairs): (column, partner) of every paired
+    // column, ascending in the column; n_pair_ent == 0: no map.  Kept when the references change (it describes columns)
+    sina_hip::DevBuf pair_ent;
+    uint32_t n_pair_ent = 0;
     std::mutex aux_mu;
     std::mutex stats_mu;
     // The device-filling kernels of all contexts (k-mer count/select, DAG build, DP) go through ONE
@@ -145,6 +149,10 @@ struct sina_hip_ctx {
     sina_hip::DevBuf r_keys, r_ids, r_scores, r_n, r_flag, r_cnt;
     double rank_ms = 0;
     uint64_t rank_pairs = 0, rank_bases = 0, rank_launches = 0;
+    // the pair-count kernel (pairs.hip; it borrows s_qab, s_qoff and s_out): its own time and volume on this context
+    // (sina_hip_pair_stats)
+    double pair_ms = 0;
+    uint64_t pair_seqs = 0, pair_entries = 0, pair_launches = 0;
     sina_hip::HostBuf h_out, h_out_pos;  // pinned staging for the DP results
     // h_out_pos holds the aligned columns of a whole align call (laid out like the caller's out_pos): a launch
     // range writes at DpLaunch::out_pos_base, callers that pass no out_pos read them here (sina_hip_staged_out_pos)
@@ -233,6 +241,7 @@ struct sina_hip_ctx {
             st->dense_bits.release();
             st->name_rank.release();
             st->name_inv.release();
+            st->pair_ent.release();
             for (auto &pl : st->tb_pool.plane) pl.release();
             delete st;
         }

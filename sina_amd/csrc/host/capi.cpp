@@ -23,6 +23,7 @@ using namespace sina;
 
 namespace {
 thread_local std::string g_err;
+std::atomic<double> g_last_avg_bps{0.0};  // avg_bps of the last finished FASTA run (sina_host_last_avg_bps)
 int fail(const std::exception &e) {
     g_err = e.what();
     return 1;
@@ -43,6 +44,7 @@ struct result {
         family_items.clear();
         family_render = nullptr;
         idty = -1.f;
+        bps = 0.f;
         searched = false;
         sr_ids.clear();
         sr_scores.clear();
@@ -67,6 +69,7 @@ struct result {
     const void *family_owner = nullptr;
     void (*family_render)(const void *, const uint64_t *, size_t, std::string &) = nullptr;
     float idty = -1.f;              // align_ident_slv (--calc-idty), -1 if not computed
+    float bps = 0.f;                // the helix base-pair score (align_bp_score_slv = (int)(100 * bps)); 0 without a helix map
     bool searched = false;          // search stage ran and produced a result vector
     std::vector<uint32_t> sr_ids;   // search results, best first
     std::vector<float> sr_scores;
@@ -132,7 +135,8 @@ struct pipeline {
 // aligned bases go into the result record (a DP alignment has exactly the query's bases, a copied one its
 // reference's: never more than the query, which the copy short-cut requires to be contained in it) -- and the
 // tray gives its objects back.
-void extract_tray(pipeline *p, tray &t, result &r, uint32_t query_bases) {
+// (helix: the store's helix map, for a tray that no pair step has scored -- or null)
+void extract_tray(pipeline *p, tray &t, result &r, uint32_t query_bases, const reference_store::pair_map &helix) {
     r.reset();
     uint64_t tk = host_tsc();
     r.log.assign(t.log.view());  // (no temporary: the result's string keeps its block between runs)
@@ -148,6 +152,7 @@ void extract_tray(pipeline *p, tray &t, result &r, uint32_t query_bases) {
     tk = host_tick("extract: log + family + turn", tk);
     if (t.aligned_sequence) {
         cseq &c = *t.aligned_sequence;
+        r.bps = tray_pair_score(t, helix);
         r.width = c.getWidth();
         r.status = (r.log.find("copied alignment from") != std::string::npos) ? 1 : 0;
         // one walk over the attributes, the stages' own keys told by their interned addresses
@@ -246,6 +251,7 @@ void reserve_workers(SearchStore &&search_store, unsigned n_find, unsigned n_ali
         const std::shared_ptr<reference_store> sstore = search_store();
         store->reserve_workers(reference_store::dev_search, n_find + (sstore == store ? n_align : 0));
         store->reserve_workers(reference_store::dev_align, n_align);
+        if (store->pairs() && sstore != store) store->reserve_workers(reference_store::dev_compare, n_align);  // (the pair step)
         if (sstore) {
             if (sstore != store) sstore->reserve_workers(reference_store::dev_search, n_align);
             sstore->reserve_workers(reference_store::dev_compare, n_align);
@@ -373,6 +379,85 @@ int sina_host_store_rank_stats(const char *key, uint64_t *ranked, uint64_t *fall
         return fail(e);
     }
 }
+// The helix map of a store (reference_store::set_pairs): pairs[i] = partner column of column i, 0 = unpaired; n == 0 or
+// all zero removes it.  Before the stages run, like sina_host_add_filter.
+int sina_host_store_set_pairs(const char *key, const uint32_t *pairs, uint32_t n) {
+    try {
+        if (!pairs && n) throw std::logic_error("store_set_pairs: null argument");
+        reference_store::get(key)->set_pairs(pairs, n);
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
+// ... and the pair-count kernel's time and volume on the store's contexts (sina_hip_pair_stats) -- between runs
+int sina_host_store_pair_stats(const char *key, double *kernel_ms, uint64_t *sequences, uint64_t *entries_visited, uint64_t *launches) {
+    try {
+        reference_store::get(key)->pair_stats(kernel_ms, sequences, entries_visited, launches);
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
+// The host walk (cseq_base::calcPairScore), no device involved, of an aligned string.  counts6 (optional): num, AG,
+// AU, CG, GG, GU.
+int sina_host_pair_score(const char *aligned_text, const uint32_t *pairs, uint32_t n, float *score, uint32_t *counts6) {
+    try {
+        if (!aligned_text || (!pairs && n) || !score) throw std::logic_error("pair_score: null argument");
+        const cseq c("", aligned_text);
+        *score = c.calcPairScore(std::vector<uint32_t>(pairs, pairs + n), counts6);
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
+// ... and of a batch of sequences as packed words, taken as they are (mask 0, equal or descending columns included; q_ab /
+// q_off as sina_hip_pair_counts takes them), one after the other on the calling thread; counts6 (optional): [nq][6];
+// seconds (optional): the walk's wall time, the map already in place (tools/perf_bps.py)
+int sina_host_pair_scores_packed(const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, const uint32_t *pairs, uint32_t n,
+                                 float *scores, uint32_t *counts6, double *seconds) {
+    try {
+        if (!q_ab || !q_off || (!pairs && n) || !scores) throw std::logic_error("pair_scores_packed: null argument");
+        const std::vector<uint32_t> map(pairs, pairs + n);
+        std::vector<cseq> seqs(nq);
+        for (uint32_t q = 0; q < nq; q++)
+            seqs[q].setAlignedBases(reinterpret_cast<const aligned_base *>(q_ab + q_off[q]), (size_t)(q_off[q + 1] - q_off[q]));
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint32_t q = 0; q < nq; q++) scores[q] = seqs[q].calcPairScore(map, counts6 ? counts6 + 6 * (size_t)q : nullptr);
+        if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
+// pair_score_from_counts and the attribute made of it, for tests
+float sina_host_pair_score_from_counts(const uint32_t *counts6, int *attr) {
+    const float s = pair_score_from_counts(counts6);
+    if (attr) *attr = pair_score_attr(s);
+    return s;
+}
+// Log::printer alone (no device): n aligned strings as trays seq0, seq1, ... through one log_printer, in order; the
+// reports' text into out (truncated at cap), the run's avg_bps.  The helix map is the one of the aligner's "db".
+int sina_host_log_reports(const char *const *aligned_texts, uint32_t n, char *out, uint32_t cap, double *avg_bps) {
+    try {
+        log_printer lp(false);
+        std::ostringstream text;
+        for (uint32_t i = 0; i < n; i++) {
+            tray t;
+            t.seqno = i;
+            const std::string name = "seq" + std::to_string(i);
+            t.input_sequence = new cseq(name.c_str(), aligned_texts[i]);
+            t.aligned_sequence = new cseq(*t.input_sequence);
+            t = lp(t, text);
+            t.destroy();
+        }
+        if (out && cap) snprintf(out, cap, "%s", text.str().c_str());
+        if (avg_bps) *avg_bps = lp.totals().avg_bps;
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
 int sina_host_store_build_index(const char *key, unsigned k, int nofast) {
     try {
         reference_store::get(key)->ensure_index(k, nofast != 0);
@@ -438,6 +523,7 @@ struct fasta_run {
         summary7[4] = sm.avg_sps;
         summary7[5] = sm.avg_cpm;
         summary7[6] = sm.avg_idty;
+        g_last_avg_bps.store(sm.avg_bps);
     }
 };
 }  // namespace
@@ -485,6 +571,7 @@ static int run_fasta(const char *in_path, const char *out_path, const char *log_
             .then(2, "aligner", 1, [&](std::vector<tray> &trays) {
                 r.al(trays);
                 if (r.sf) (*r.sf)(trays);
+                pair_score_batch(trays);
             });
         if (staged) {
             tune_allocator();
@@ -506,6 +593,10 @@ int sina_host_run_fasta(const char *in_path, const char *out_path, const char *l
                         int show_dist, uint32_t batch, double *summary7) {
     return run_fasta(in_path, out_path, log_path, do_search, show_dist, batch, summary7, true);
 }
+
+// avg_bps of the last sina_host_run_fasta / _serial that finished: the sum of the aligned trays' base-pair scores, in
+// tray order, over their number (Log::printer's avg_bps, src/log.cpp:358).  The summary array keeps its seven values.
+double sina_host_last_avg_bps(void) { return g_last_avg_bps.load(); }
 
 // FASTA reader + writer alone (no GPU): reads every sequence of in_path and writes it back, the
 // input sequence standing in for the aligned one; returns the counts.  For CPU tests of the I/O rules.
@@ -754,6 +845,7 @@ static int run_queries(pipeline *p, uint32_t nq, const uint64_t *qoff, uint32_t 
         auto align_and_search = [&](item &it) {  // aligner node (+ search node)
             timed(al_ns, [&] { p->al(it.trays); });
             if (p->sf) timed(sf_ns, [&] { (*p->sf)(it.trays); });
+            pair_score_batch(it.trays);  // (nothing without a helix map)
         };
         auto extract = [&](item &it) {  // sink
             {
@@ -761,9 +853,10 @@ static int run_queries(pipeline *p, uint32_t nq, const uint64_t *qoff, uint32_t 
                 pipeline::result_chunk &chunk = p->chunks[it.b0 / batch];
                 chunk.results.resize(it.b1 - it.b0);
                 chunk.run = p->run_no;
+                const reference_store::pair_map helix = aligner_pair_map();
                 parallel_for(it.b1 - it.b0, [&](size_t i) {  // (what SINA's writer stage does per sequence)
                     const uint32_t q = it.b0 + (uint32_t)i;
-                    extract_tray(p, it.trays[i], chunk.results[i], (uint32_t)(qoff[q + 1] - qoff[q]));
+                    extract_tray(p, it.trays[i], chunk.results[i], (uint32_t)(qoff[q + 1] - qoff[q]), helix);
                 });
             }
             p->give_trays(std::move(it.trays));
@@ -865,6 +958,8 @@ int sina_host_pipeline_run_single_trays(void *pp, const uint8_t *qmask, const ui
             foreign.append("ACGU");
             foreign.setWidth(store->getAlignmentWidth());
         }
+        // (trays that come one at a time meet no pair step: their base-pair score is the host walk's, in the sink)
+        const reference_store::pair_map helix = aligner_pair_map();
         std::atomic<uint32_t> next{0};
         std::mutex err_mu;
         std::exception_ptr fatal;
@@ -894,7 +989,7 @@ int sina_host_pipeline_run_single_trays(void *pp, const uint8_t *qmask, const ui
                             keep.destroy();
                             continue;
                         }
-                        extract_tray(p, t, chunk.results[q], (uint32_t)(qoff[q + 1] - qoff[q]));
+                        extract_tray(p, t, chunk.results[q], (uint32_t)(qoff[q + 1] - qoff[q]), helix);
                     } catch (...) {
                         std::lock_guard<std::mutex> lk(err_mu);
                         if (!fatal) fatal = std::current_exception();
@@ -971,6 +1066,15 @@ const char *sina_host_result_attr(void *pp, uint32_t q, const char *name) {
 }
 double sina_host_search_seconds(void *pp) { return ((pipeline *)pp)->sf_s; }
 float sina_host_result_idty(void *pp, uint32_t q) { return result_at(pp, q).idty; }
+// the helix base-pair score of query q and align_bp_score_slv made of it; 0 and 0 without a helix map or an alignment
+int sina_host_result_bps(void *pp, uint32_t q, float *score, int *attr) {
+    pipeline *p = (pipeline *)pp;
+    if (q >= p->n_results) return 1;
+    const result &r = result_at(pp, q);
+    if (score) *score = r.bps;
+    if (attr) *attr = pair_score_attr(r.bps);
+    return 0;
+}
 void sina_host_timings(void *pp, double *wall_s, double *famfinder_s, double *aligner_s) {
     pipeline *p = (pipeline *)pp;
     *wall_s = p->wall_s;

@@ -357,6 +357,34 @@ char cseq_base::operator[](vidx_type i) const {
     return '-';
 }
 
+float pair_score_from_counts(const uint32_t counts[6]) {
+    if (counts[0] == 0) return 0.f;
+    float score = (float)(counts[1] * .5 + counts[2] * 1.1 + counts[3] * 1.5 + counts[4] * .4 + counts[5] * .9);
+    score /= (float)counts[0];
+    return score;
+}
+
+float cseq_base::calcPairScore(const std::vector<uint32_t> &pairs, uint32_t counts_out[6]) const {
+    uint32_t counts[6] = {0, 0, 0, 0, 0, 0};
+    auto char_at = [&](uint32_t col) -> unsigned char {
+        return col > 0xFFFFFFu ? (unsigned char)'-' : (unsigned char)operator[](col);  // (operator[] keeps 24 bits of it)
+    };
+    for (size_t i = 0; i < pairs.size(); i++) {
+        if (pairs[i] == 0) continue;  // (no helix partner)
+        unsigned char left = char_at((uint32_t)i), right = char_at(pairs[i]);
+        if (left == '.' || right == '.' || (left == '-' && right == '-')) continue;
+        counts[0]++;
+        if (left > right) std::swap(left, right);
+        if (left == 'A' && right == 'G') counts[1]++;
+        else if (left == 'A' && right == 'U') counts[2]++;
+        else if (left == 'C' && right == 'G') counts[3]++;
+        else if (left == 'G' && right == 'G') counts[4]++;
+        else if (left == 'G' && right == 'U') counts[5]++;
+    }
+    if (counts_out) memcpy(counts_out, counts, sizeof counts);
+    return pair_score_from_counts(counts);
+}
+
 std::ostream &operator<<(std::ostream &out, const cseq_base &c) { return out << c.getName(); }
 
 // ---- attribute names, interned.  A per-thread table in front of the process-wide one: the few dozen

@@ -193,6 +193,12 @@ public:
     const_reverse_iterator rend() const { unpack(); return bases.rend(); }
     const aligned_base &getById(idx_type i) const { unpack(); return bases[i]; }
     char operator[](vidx_type i) const;
+    // The helix base-pair score behind align_bp_score_slv (src/cseq.cpp:651-733): for every column i with a partner
+    // pairs[i] != 0 the characters operator[] shows at i and at pairs[i] (a partner of 2^24 or more: '-', no word
+    // holds that column); a visit counts unless one side is '.' or both are '-'.  counts (optional): num, AG, AU, CG,
+    // GG, GU -- the six numbers the device's pair count gives (sina_hip_pair_counts); the score is
+    // pair_score_from_counts() of them.
+    float calcPairScore(const std::vector<uint32_t> &pairs, uint32_t counts[6] = nullptr) const;
 
     bool operator==(const cseq_base &rhs) const { return name == rhs.name && getAlignedBases() == rhs.getAlignedBases(); }
     bool operator!=(const cseq_base &rhs) const { return !(*this == rhs); }
@@ -224,6 +230,14 @@ private:
 };
 
 std::ostream &operator<<(std::ostream &out, const cseq_base &c);
+
+// The score of counts = num, AG, AU, CG, GG, GU (src/cseq.cpp:695-732): the weighted sum in double, added left to
+// right, rounded once to float, then a float division by (float)num.  num == 0 gives 0 -- the reference divides 0 by 0
+// there and casts the NaN to int.  The only place that does this arithmetic: the host walk and the
+// device's counts both end here.
+float pair_score_from_counts(const uint32_t counts[6]);
+// ... and align_bp_score_slv of a score: (int)(100 * score), a float product, truncated (src/log.cpp:383-385)
+inline int pair_score_attr(float score) { return (int)(100 * score); }
 
 // attribute map of annotated_cseq (src/cseq.h:233-272); boost::variant -> std::variant.
 // The reference keeps a std::map<string, variant>.  Here: a short vector of {key, value} sorted by key

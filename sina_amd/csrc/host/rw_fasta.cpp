@@ -710,8 +710,11 @@ void log_printer::render(tray &t, report &out) const {
     }
     out.aligned = true;
     cseq &aligned = *t.aligned_sequence;
-    // (helix pairing comes from the ARB database: no pairs, bp score 0)
-    aligned.set_attr("align_bp_score_slv", 0);
+    // src/log.cpp:383-385: the helix base-pair score.  The batch drivers' pair step has left it in the tray; a tray
+    // that comes one at a time (operator(), the batching shim's callers) takes the host walk here; a store without a
+    // helix map gives 0
+    out.bps = tray_pair_score(t, t.bp_score_set ? reference_store::pair_map() : aligner_pair_map());
+    aligned.set_attr("align_bp_score_slv", pair_score_attr(out.bps));
     aligned.set_attr(fn::align_log, t.log_text());
     aligned.set_attr("nuc", (int)aligned.size());
     if (aligned.size() != 0u) {
@@ -740,6 +743,7 @@ void log_printer::commit(const report &r, std::ostream &log) {
     log << r.text;
     if (!r.aligned) return;
     ++data->sequence_num;
+    data->total_bps += r.bps;
     if (r.has_sps) data->total_sps += r.sps;
     if (r.has_closest) {
         data->total_idty += r.idty;

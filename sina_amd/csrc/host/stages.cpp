@@ -368,7 +368,8 @@ unsigned host_threads() { return pool::get().size(); }
 tray::tray(const tray &o)
     : seqno(o.seqno), input_sequence(o.input_sequence), aligned_sequence(o.aligned_sequence),
       alignment_reference(o.alignment_reference), search_result(o.search_result), astats(o.astats),
-      family_scores_kmer_k(o.family_scores_kmer_k), query_kmer_count(o.query_kmer_count) {
+      family_scores_kmer_k(o.family_scores_kmer_k), query_kmer_count(o.query_kmer_count), bp_score(o.bp_score),
+      bp_score_set(o.bp_score_set) {
     log.str(o.log.str());
     log.seekp(0, std::ios_base::end);
     pending_score = o.pending_score;
@@ -418,6 +419,8 @@ tray &tray::operator=(const tray &o) {
     astats = o.astats;
     family_scores_kmer_k = o.family_scores_kmer_k;
     query_kmer_count = o.query_kmer_count;
+    bp_score = o.bp_score;
+    bp_score_set = o.bp_score_set;
     return *this;
 }
 alignment_stats *alignment_stats::shared_default() {
@@ -433,6 +436,8 @@ void tray::destroy() {  // (src/tray.cpp:77-86; the objects go back to their cac
     input_sequence = aligned_sequence = nullptr;
     alignment_reference = search_result = nullptr;
     astats = nullptr;
+    bp_score = 0.f;
+    bp_score_set = false;
 }
 
 // ================================================================ reference_store
@@ -449,6 +454,11 @@ std::shared_ptr<reference_store> reference_store::get(const std::string &path) {
         if (it != stores.end()) return it->second;
     }
     return open(path);
+}
+std::shared_ptr<reference_store> reference_store::find(const std::string &path) {
+    std::lock_guard<std::mutex> lk(stores_mu);
+    auto it = stores.find(path);
+    return it != stores.end() ? it->second : nullptr;
 }
 void reference_store::close(const std::string &path) {
     std::lock_guard<std::mutex> lk(stores_mu);
@@ -650,6 +660,38 @@ void reference_store::rank_stats(uint64_t *ranked, uint64_t *fallen_back, double
     for (auto &pool : idle_forks)
         for (sina_hip_ctx *c : pool) add(c);
 }
+void reference_store::set_pairs(const uint32_t *pairs, uint32_t n) {
+    bool any = false;
+    for (uint32_t i = 0; i < n && !any; i++) any = pairs[i] != 0;
+    {
+        std::lock_guard<std::mutex> lk(helix_mu);
+        helix = any ? std::make_shared<const std::vector<uint32_t>>(pairs, pairs + n) : nullptr;
+    }
+    std::lock_guard<std::mutex> lk(gpu_mu);  // (a context made later uploads it itself: device())
+    if (ctx) hip_check(sina_hip_upload_pairs(ctx, pairs, any ? n : 0), "sina_hip_upload_pairs");
+}
+reference_store::pair_map reference_store::pairs() {
+    std::lock_guard<std::mutex> lk(helix_mu);
+    return helix;
+}
+void reference_store::pair_stats(double *kernel_ms, uint64_t *sequences, uint64_t *entries_visited, uint64_t *launches) {
+    sina_hip_ctx *root = device();
+    std::lock_guard<std::mutex> lk(gpu_mu);
+    *kernel_ms = 0;
+    *sequences = *entries_visited = *launches = 0;
+    auto add = [&](sina_hip_ctx *c) {
+        double ms = 0;
+        uint64_t n = 0, e = 0, l = 0;
+        hip_check(sina_hip_pair_stats(c, &ms, &n, &e, &l), "sina_hip_pair_stats");
+        *kernel_ms += ms;
+        *sequences += n;
+        *entries_visited += e;
+        *launches += l;
+    };
+    add(root);
+    for (auto &pool : idle_forks)
+        for (sina_hip_ctx *c : pool) add(c);
+}
 bool reference_store::match_counts_too_wide() {
     if (sina_hip::match_table_bytes(width) <= sina_hip::kMatchMaxLds) return false;
     if (!too_wide_said.exchange(true))
@@ -708,6 +750,7 @@ sina_hip_ctx *reference_store::device() {
     std::lock_guard<std::mutex> lk(gpu_mu);
     if (ctx) return ctx;
     hip_check(sina_hip_init(device_id, &ctx), "sina_hip_init");
+    if (const pair_map m = pairs()) hip_check(sina_hip_upload_pairs(ctx, m->data(), (uint32_t)m->size()), "sina_hip_upload_pairs");
     if (refs_by_broadcast) return ctx;  // (filled in place by the start-up broadcast, sina_amd/dist.py)
     std::vector<uint32_t> ab;
     std::vector<uint64_t> off(seqs.size() + 1, 0);
@@ -3073,6 +3116,67 @@ void search_filter::operator()(std::vector<tray> &batch) {
     }
     scoped_phase ph("sf.rank+lca");
     parallel_for(idx.size(), [&](size_t x) { annotate_tray(s.o, s.st, batch[idx[x]]); });
+}
+
+// ================================================================ helix base-pair score (align_bp_score_slv)
+
+reference_store::pair_map aligner_pair_map() {
+    if (aligner::opts == nullptr || aligner::opts->database.empty()) return nullptr;
+    const std::shared_ptr<reference_store> st = reference_store::find(aligner::opts->database);
+    return st ? st->pairs() : nullptr;
+}
+
+float tray_pair_score(const tray &t, const reference_store::pair_map &map) {
+    if (t.aligned_sequence == nullptr) return 0.f;
+    if (t.bp_score_set) return t.bp_score;
+    return map ? t.aligned_sequence->calcPairScore(*map) : 0.f;
+}
+
+void pair_score_batch(std::vector<tray> &batch) {
+    if (aligner::opts == nullptr || aligner::opts->database.empty()) return;
+    const std::shared_ptr<reference_store> st = reference_store::find(aligner::opts->database);
+    if (!st) return;
+    const reference_store::pair_map map = st->pairs();
+    if (!map) return;
+    // the trays the device takes (columns ascending: the kernel finds a column by bisection), and the others
+    std::vector<size_t> dev;
+    std::vector<uint64_t> off(1, 0);
+    std::vector<uint32_t> words;
+    {
+        scoped_phase ph("bp.pack");
+        std::vector<char> kind(batch.size(), 0);  // 1: device, 2: host walk
+        parallel_for(batch.size(), [&](size_t i) {
+            tray &t = batch[i];
+            if (t.aligned_sequence == nullptr) return;
+            if (columns_ascend(*t.aligned_sequence)) kind[i] = 1;
+            else {
+                t.bp_score = t.aligned_sequence->calcPairScore(*map);
+                t.bp_score_set = true;
+            }
+        });
+        for (size_t i = 0; i < batch.size(); i++)
+            if (kind[i] == 1) {
+                dev.push_back(i);
+                off.push_back(off.back() + batch[i].aligned_sequence->size());
+            }
+        words.resize((size_t)off.back());
+        parallel_for(dev.size(), [&](size_t x) {
+            const cseq &c = *batch[dev[x]].aligned_sequence;
+            if (c.size()) memcpy(words.data() + off[x], c.packed(), 4 * (size_t)c.size());
+        });
+    }
+    if (dev.empty()) return;
+    std::vector<uint32_t> counts(6 * dev.size(), 0);
+    {
+        scoped_phase ph("bp.pair_counts(C-ABI)");
+        reference_store::lease dv = st->worker_device(reference_store::dev_compare);
+        hip_check(sina_hip_pair_counts(dv.get(), words.data(), off.data(), (uint32_t)dev.size(), counts.data()), "sina_hip_pair_counts");
+    }
+    for (size_t x = 0; x < dev.size(); x++) {
+        tray &t = batch[dev[x]];
+        t.bp_score = pair_score_from_counts(counts.data() + 6 * x);
+        t.bp_score_set = true;
+    }
 }
 
 }  // namespace sina

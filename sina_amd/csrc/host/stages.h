@@ -200,6 +200,11 @@ public:
         void merge_into(std::string &log_text) const;
     };
     score_note pending_score;
+    // The helix base-pair score of aligned_sequence (cseq_base::calcPairScore) where a batch driver's pair step
+    // (pair_score_batch) has computed it; not set: the sink takes the host walk if the store has a helix map, and 0
+    // if it has none (tray_pair_score).
+    float bp_score{0.f};
+    bool bp_score_set{false};
     std::string log_text() const;   // log, with a pending score line rendered in its place
     void clear_log() {
         log.str(std::string());
@@ -229,6 +234,7 @@ public:
                                                          const uint64_t *off, uint32_t n, uint32_t width,
                                                          const char *const *names = nullptr);
     static std::shared_ptr<reference_store> get(const std::string &path);
+    static std::shared_ptr<reference_store> find(const std::string &path);  // ... or null: opens nothing
     static void close(const std::string &path);
 
     ~reference_store();
@@ -325,6 +331,16 @@ public:
         n_rank_host.fetch_add(on_host, std::memory_order_relaxed);
     }
     void rank_stats(uint64_t *ranked, uint64_t *fallen_back, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches);
+    // The helix map align_bp_score_slv is computed from: pairs[i] = partner column of column i, 0 = unpaired.  The
+    // reference reads it from the HELIX data of its --orig-db ARB database (src/log.cpp:383); here the caller hands it
+    // over, like a filter, and it belongs to the store the aligner's "db" names.  set_pairs keeps it and uploads it
+    // (sina_hip_upload_pairs: now if the device context exists, else when it is made); an empty or all-zero map
+    // removes it.  Before the stages run, like the filters.
+    using pair_map = std::shared_ptr<const std::vector<uint32_t>>;
+    void set_pairs(const uint32_t *pairs, uint32_t n);
+    pair_map pairs();  // null: no map
+    // ... and the pair-count kernel's time and volume on the store's contexts -- sina_hip_pair_stats
+    void pair_stats(double *kernel_ms, uint64_t *sequences, uint64_t *entries_visited, uint64_t *launches);
 
 private:
     reference_store() = default;
@@ -350,6 +366,8 @@ private:
     std::atomic<bool> too_wide_said{false};
     std::atomic<int> name_order_state{0};  // 0: not looked at, 1: uploaded, 2: names repeat
     std::atomic<uint64_t> n_ranked{0}, n_rank_host{0};
+    pair_map helix;
+    std::mutex helix_mu;
 };
 
 // ---------------------------------------------------------------- .sidx index cache
@@ -578,7 +596,7 @@ public:
     struct report {
         std::string text;
         bool aligned = false, has_sps = false, has_closest = false;
-        float sps = 0, idty = 0, cpm = 0;
+        float sps = 0, idty = 0, cpm = 0, bps = 0;
     };
     explicit log_printer(bool show_dist);
     log_printer(const log_printer &);
@@ -589,6 +607,16 @@ public:
     void commit(const report &r, std::ostream &log);  // in sequence order
     summary totals() const;
 };
+
+// ---------------------------------------------------------------- helix base-pair score (align_bp_score_slv)
+// the helix map of the store the aligner's "db" names, or null (no such store registered, or it has no map)
+reference_store::pair_map aligner_pair_map();
+// The pair step of a batch driver, after the aligner (and the search stage): if the store has a helix map, every
+// tray with an aligned sequence gets its bp_score -- the trays whose columns ascend strictly from ONE
+// sina_hip_pair_counts call, the others from the host walk.  Without a map: nothing is packed, called or launched.
+void pair_score_batch(std::vector<tray> &batch);
+// a tray's score for its sink: the field if set, else the host walk over `map`, else (no map, or not aligned) 0
+float tray_pair_score(const tray &t, const reference_store::pair_map &map);
 
 // text of a family attribute kept as a list (annotated_cseq::lazy_text; famfinder sets it, sinks may keep the list)
 void render_family_list(const void *store, const uint64_t *items, size_t n, std::string &out);

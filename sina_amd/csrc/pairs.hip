@@ -1,0 +1,179 @@
+// The helix base-pair score on the GPU: pair_count_kernel + sina_hip_upload_pairs,
+// sina_hip_pair_counts, sina_hip_pair_stats.
+//
+// What it computes: for every finished aligned sequence the counters behind align_bp_score_slv
+// (cseq_base::calcPairScore, src/cseq.cpp:651-733): for every column i that the helix map pairs with a column p, the
+// characters the sequence shows at i and at p -- a base, '-' where it has none, '.' for a word without mask bits --,
+// the number of such visits that count (neither side '.', not both '-') and, of those, how many are the unordered
+// pairs AG, AU, CG, GG, GU of upper-case unambiguous bases.  The weighted sum and the division stay with the host
+// (host/cseq.cpp, pair_score_from_counts): six integers per sequence are all that crosses back.
+//
+// How it maps to the hardware: one wave per sequence, its lanes striding over the compacted map (pair_plan.h); a lane
+// finds each of its two columns by a branch-free binary search over the sequence's packed words in global memory (6 KB
+// for 16S: they stay in L1 / L2; every lane of the wave takes the same number of steps), classifies the pair and keeps
+// six counters in registers; the wave adds them up across lanes and lane 0 stores the six words.  No LDS, no atomics.
+#include <algorithm>
+#include <cstring>
+
+#include "common.h"
+#include "ctx.h"
+#include "pair_plan.h"
+
+namespace sina_hip {
+namespace {
+
+constexpr int kPT = 64 * (int)kPairWaves;  // threads per workgroup
+
+struct PairArgs {
+    const uint32_t *q_ab;   // the range's packed words
+    const uint64_t *q_off;  // [n + 1], relative to q_ab
+    const uint2 *ent;       // [n_ent] (column, partner)
+    uint32_t *out;          // [n][6]: num, AG, AU, CG, GG, GU
+    uint32_t n, n_ent;
+};
+
+constexpr uint32_t kGap = 32;  // "no base in that column": beside the 5-bit masks 0..31
+
+// What the sequence shows in column c: the five mask bits of the first word whose column is >= c if that column is c,
+// else kGap.  (A column of 2^24 or more is beyond every word: the search ends at len.)
+__device__ __forceinline__ uint32_t mask_at(const uint32_t *W, uint32_t len, uint32_t c) {
+    if (len == 0) return kGap;
+    uint32_t base = 0, n = len;
+    while (n > 1) {  // (lower_bound without a branch on the data: answer in [base, base + n])
+        const uint32_t half = n >> 1;
+        base = (W[base + half] & 0xFFFFFFu) < c ? base + half : base;
+        n -= half;
+    }
+    const uint32_t w0 = W[base];
+    const uint32_t at = base + ((w0 & 0xFFFFFFu) < c ? 1u : 0u);
+    const uint32_t w = at < len ? W[at] : 0xFFFFFFFFu;  // (at <= len; at == len: no word at or after c)
+    return (at < len && (w & 0xFFFFFFu) == c) ? ((w >> 24) & 31u) : kGap;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(kPT) pair_count_kernel(PairArgs a) {
+    const uint32_t seq = blockIdx.x * kPairWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (seq >= a.n) return;  // (whole waves)
+    const uint64_t b = a.q_off[seq];
+    const uint32_t len = (uint32_t)(a.q_off[seq + 1] - b);
+    const uint32_t *W = a.q_ab + b;
+    uint32_t num = 0, ag = 0, au = 0, cg = 0, gg = 0, gu = 0;
+    for (uint32_t e = lane; e < a.n_ent; e += 64) {
+        const uint2 en = a.ent[e];
+        const uint32_t l = mask_at(W, len, en.x), r = mask_at(W, len, en.y);
+        // '.': a word without mask bits, either case
+        const bool dot = (l != kGap && (l & 15u) == 0) || (r != kGap && (r & 15u) == 0);
+        const bool counted = !dot && !(l == kGap && r == kGap);
+        num += counted ? 1u : 0u;
+        // the weighted classes: two upper-case bases of one bit each (A 1, G 2, C 4, U 8)
+        const bool plain = counted && l < 16u && r < 16u && __popc(l) == 1 && __popc(r) == 1;
+        const uint32_t both = l | r;
+        ag += (plain && both == 3u) ? 1u : 0u;
+        au += (plain && both == 9u) ? 1u : 0u;
+        cg += (plain && both == 6u) ? 1u : 0u;
+        gg += (plain && l == 2u && r == 2u) ? 1u : 0u;
+        gu += (plain && both == 10u) ? 1u : 0u;
+    }
+    num = wave_sum(num);
+    ag = wave_sum(ag);
+    au = wave_sum(au);
+    cg = wave_sum(cg);
+    gg = wave_sum(gg);
+    gu = wave_sum(gu);
+    if (lane == 0) {
+        uint32_t *o = a.out + (size_t)seq * 6;
+        o[0] = num;
+        o[1] = ag;
+        o[2] = au;
+        o[3] = cg;
+        o[4] = gg;
+        o[5] = gu;
+    }
+}
+
+}  // namespace
+}  // namespace sina_hip
+
+using namespace sina_hip;
+
+extern "C" int sina_hip_upload_pairs(sina_hip_ctx *c, const uint32_t *pairs, uint32_t n) {
+    if (!c || (!pairs && n != 0)) SH_FAIL("upload_pairs: null argument");
+    if (!c->owns_store) SH_FAIL("upload_pairs: a forked context cannot change the reference store");
+    std::lock_guard<std::mutex> lk(c->mu);
+    const std::vector<uint32_t> ent = pair_compact(pairs, n);
+    c->st->n_pair_ent = 0;
+    if (ent.empty()) return 0;  // (an empty or all-zero map: no map)
+    SH_CHECK(hipSetDevice(c->device));
+    if (c->st->pair_ent.reserve(4 * ent.size())) return 1;
+    SH_CHECK(hipMemcpy(c->st->pair_ent.p, ent.data(), 4 * ent.size(), hipMemcpyHostToDevice));
+    c->st->n_pair_ent = (uint32_t)(ent.size() / 2);
+    return 0;
+}
+
+extern "C" int sina_hip_pair_counts(sina_hip_ctx *c, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t *counts) {
+    if (!c) SH_FAIL("pair_counts: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    sina_hip_hint_guard hints(c);
+    const uint32_t n_ent = c->st->n_pair_ent;
+    if (n_ent == 0) SH_FAIL("pair_counts: upload a helix map first");
+    if (nq == 0) return 0;
+    if (!q_ab || !q_off || !counts) SH_FAIL("pair_counts: null argument");
+    for (uint32_t q = 0; q < nq; q++) {
+        if (q_off[q + 1] < q_off[q]) SH_FAIL("pair_counts: sequence offsets descend");
+        if (q_off[q + 1] - q_off[q] > 0x7FFFFFFFull) SH_FAIL("pair_counts: sequence longer than 2^31 - 1 words");
+    }
+    if (pair_first_descending(q_ab, q_off, nq) != nq) SH_FAIL("pair_counts: a sequence's columns descend");
+    SH_CHECK(hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    // (SINA_HIP_TEST=pair_words=N: launch ranges of N words, so that a small call takes several)
+    const std::string words_knob = test_knob("pair_words");
+    const uint64_t max_words = words_knob.empty() ? kPairRangeWords : std::max<uint64_t>(1, strtoull(words_knob.c_str(), nullptr, 10));
+    std::vector<uint64_t> rel;
+    for (const PairRange &r : pair_ranges(q_off, nq, max_words)) {
+        const uint32_t n = r.q1 - r.q0;
+        const uint64_t words = q_off[r.q1] - q_off[r.q0];
+        rel.resize((size_t)n + 1);
+        for (uint32_t q = 0; q <= n; q++) rel[q] = q_off[r.q0 + q] - q_off[r.q0];
+        if (c->s_qab.reserve(4 * std::max<uint64_t>(words, 1)) || c->s_qoff.reserve(8 * ((uint64_t)n + 1)) ||
+            c->s_out.reserve(24 * (uint64_t)n))
+            return 1;
+        if (upload(c, 1, c->s_qab.p, q_ab + q_off[r.q0], 4 * words, s) || upload(c, 2, c->s_qoff.p, rel.data(), 8 * ((uint64_t)n + 1), s))
+            return 1;
+        PairArgs a;
+        a.q_ab = c->s_qab.as<uint32_t>();
+        a.q_off = c->s_qoff.as<uint64_t>();
+        a.ent = c->st->pair_ent.as<uint2>();
+        a.out = c->s_out.as<uint32_t>();
+        a.n = n;
+        a.n_ent = n_ent;
+        // (a thin kernel beside whatever is resident: on the context's own stream, like the trace-back walk -- ctx.h)
+        SH_CHECK(hipEventRecord(c->ev[6], s));
+        hipLaunchKernelGGL(pair_count_kernel, dim3(pair_grid(n)), dim3(kPT), 0, s, a);
+        SH_CHECK(hipGetLastError());
+        SH_CHECK(hipEventRecord(c->ev[7], s));
+        if (download(c, 5, c->s_out.p, 24 * (size_t)n, s)) return 1;
+        SH_CHECK(wait_stream(c, s));
+        float ms = 0;
+        SH_CHECK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
+        memcpy(counts + (size_t)r.q0 * 6, c->h_stage[5].p, 24 * (size_t)n);
+        c->pair_ms += ms;
+        c->pair_seqs += n;
+        c->pair_entries += (uint64_t)n * n_ent;
+        c->pair_launches++;
+    }
+    return 0;
+}
+
+extern "C" int sina_hip_pair_stats(sina_hip_ctx *c, double *kernel_ms, uint64_t *sequences, uint64_t *entries_visited, uint64_t *launches) {
+    if (!c || !kernel_ms || !sequences || !entries_visited || !launches) SH_FAIL("pair_stats: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *kernel_ms = c->pair_ms;
+    *sequences = c->pair_seqs;
+    *entries_visited = c->pair_entries;
+    *launches = c->pair_launches;
+    return 0;
+}

@@ -95,6 +95,17 @@ def load_host():
     H.sina_host_result_idty.restype = C.c_float
     H.sina_host_result_idty.argtypes = [vp, C.c_uint32]
     H.sina_host_search_seconds.argtypes = [vp]
+    H.sina_host_store_set_pairs.argtypes = [C.c_char_p, capi.u32p, C.c_uint32]
+    H.sina_host_store_pair_stats.argtypes = [C.c_char_p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_pair_score.argtypes = [C.c_char_p, capi.u32p, C.c_uint32, capi.f32p, capi.u32p]
+    H.sina_host_pair_scores_packed.argtypes = [capi.u32p, capi.u64p, C.c_uint32, capi.u32p, C.c_uint32, capi.f32p, capi.u32p,
+                                               C.POINTER(C.c_double)]
+    H.sina_host_pair_score_from_counts.restype = C.c_float
+    H.sina_host_pair_score_from_counts.argtypes = [capi.u32p, C.POINTER(C.c_int)]
+    H.sina_host_log_reports.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_double)]
+    H.sina_host_last_avg_bps.restype = C.c_double
+    H.sina_host_last_avg_bps.argtypes = []
+    H.sina_host_result_bps.argtypes = [vp, C.c_uint32, capi.f32p, C.POINTER(C.c_int)]
     _host = H
     return H
 
@@ -263,6 +274,22 @@ class Store:
         return dict(ranked=int(ranked.value), fallen_back=int(back.value), kernel_ms=float(ms.value), pairs=int(pairs.value),
                     cand_bases=int(bases.value), launches=int(launches.value))
 
+    def set_pairs(self, pairs):
+        """The helix map align_bp_score_slv is computed from: pairs[i] = partner column of column i, 0 = unpaired
+        (pairs.pairs_from_brackets makes one from a dot-bracket line).  Empty or all zero: no map, the score is 0.
+        Before the pipelines run, like add_filter."""
+        m = np.ascontiguousarray(pairs, np.uint32)
+        _chk(self.H.sina_host_store_set_pairs(self.key.encode(), m.ctypes.data_as(capi.u32p), len(m)))
+
+    def pair_stats(self):
+        """The pair-count kernel (the helix base-pair score) on this store's contexts so far: dict(kernel_ms, sequences,
+        entries_visited, launches) -- between runs, like match_stats()."""
+        ms = C.c_double()
+        seqs, ent, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _chk(self.H.sina_host_store_pair_stats(self.key.encode(), C.byref(ms), C.byref(seqs), C.byref(ent), C.byref(launches)))
+        return dict(kernel_ms=float(ms.value), sequences=int(seqs.value), entries_visited=int(ent.value),
+                    launches=int(launches.value))
+
     def close(self):
         self.H.sina_host_store_close(self.key.encode())
 
@@ -358,6 +385,10 @@ class Pipeline:
                  log=self.H.sina_host_result_log(self.h, q).decode(),
                  family=self.H.sina_host_result_family(self.h, q).decode(),
                  idty=np.float32(self.H.sina_host_result_idty(self.h, q)))
+        bps, bp_attr = C.c_float(), C.c_int()
+        _chk(self.H.sina_host_result_bps(self.h, q, C.byref(bps), C.byref(bp_attr)))
+        d["bps"] = np.float32(bps.value)  # the helix base-pair score; 0 without a helix map (Store.set_pairs)
+        d["bp_score"] = bp_attr.value     # align_bp_score_slv
         if self.has_search:
             ids = np.zeros(4096, np.uint32)
             sc = np.zeros(4096, np.float32)
@@ -396,6 +427,61 @@ def host_compare(a_aligned, b_aligned, iupac=0, dist=0, cover=1, filter_lc=False
     return np.float32(sc.value), tuple(cnt)
 
 
+def host_pair_score(aligned, pairs):
+    """The host walk behind align_bp_score_slv (cseq_base::calcPairScore), no device involved: (score float32, counters
+    uint32 [6] = num, AG, AU, CG, GG, GU).  aligned: an aligned string, or packed words (column | mask << 24) as an
+    integer array."""
+    if not isinstance(aligned, str):
+        sc, cnt, _ = host_pair_scores(aligned, np.array([0, len(aligned)], np.uint64), pairs)
+        return np.float32(sc[0]), cnt[0]
+    H = load_host()
+    m = np.ascontiguousarray(pairs, np.uint32)
+    sc = C.c_float()
+    cnt = np.zeros(6, np.uint32)
+    _chk(H.sina_host_pair_score(aligned.encode(), m.ctypes.data_as(capi.u32p), len(m), C.byref(sc), cnt.ctypes.data_as(capi.u32p)))
+    return np.float32(sc.value), cnt
+
+
+def host_pair_scores(q_ab, q_off, pairs):
+    """host_pair_score for a batch of packed sequences, one after the other on the calling thread: (scores float32 [nq],
+    counters uint32 [nq, 6], the walk's wall seconds)."""
+    H = load_host()
+    q_ab = np.ascontiguousarray(q_ab, np.uint32)
+    q_off = np.ascontiguousarray(q_off, np.uint64)
+    m = np.ascontiguousarray(pairs, np.uint32)
+    nq = len(q_off) - 1
+    sc = np.zeros(max(nq, 1), np.float32)
+    cnt = np.zeros((max(nq, 1), 6), np.uint32)
+    sec = C.c_double()
+    _chk(H.sina_host_pair_scores_packed(q_ab.ctypes.data_as(capi.u32p), q_off.ctypes.data_as(capi.u64p), nq,
+                                        m.ctypes.data_as(capi.u32p), len(m), sc.ctypes.data_as(capi.f32p),
+                                        cnt.ctypes.data_as(capi.u32p), C.byref(sec)))
+    return sc[:nq], cnt[:nq], sec.value
+
+
+def pair_score_from_counts(counts):
+    """(score float32, align_bp_score_slv) of six counters num, AG, AU, CG, GG, GU -- the one place both routes end in."""
+    cnt = np.ascontiguousarray(counts, np.uint32)
+    assert len(cnt) == 6
+    attr = C.c_int()
+    H = load_host()
+    s = H.sina_host_pair_score_from_counts(cnt.ctypes.data_as(capi.u32p), C.byref(attr))
+    return np.float32(s), attr.value
+
+
+def log_reports(aligned_texts):
+    """Log::printer alone (no device) over aligned strings as sequences seq0, seq1, ...: (the reports' text, avg_bps).
+    The helix map is the one of the store the aligner's "db" option names."""
+    H = load_host()
+    n = len(aligned_texts)
+    arr = (C.c_char_p * max(n, 1))(*[t.encode() for t in aligned_texts])
+    cap = 1 << 20
+    out = C.create_string_buffer(cap)
+    avg = C.c_double()
+    _chk(H.sina_host_log_reports(arr, n, out, cap, C.byref(avg)))
+    return out.value.decode(), avg.value
+
+
 def sidx_load(path, k=10, nofast=False, ids_cap=1 << 26):
     """The reference's .sidx index cache as CSR: (n_sequences, offsets[4^k+1], ids)."""
     H = load_host()
@@ -426,7 +512,8 @@ def _set_options(H, stage, opts):
 def run_fasta(store, in_path, out_path, famfinder=None, aligner=None, search=None, fasta=None, show_dist=False,
               log_path="", batch=1024, serial=False):
     """`sina -i in_path -o out_path --db <store> [--search] [--show-dist]`: FASTA in, aligned FASTA out, through
-    the stage mirror.  Returns dict(read, aligned, written, skipped, avg_sps, avg_cpm, avg_idty)."""
+    the stage mirror.  Returns dict(read, aligned, written, skipped, avg_sps, avg_cpm, avg_idty, avg_bps); avg_bps is
+    0 unless the store has a helix map (Store.set_pairs)."""
     H = load_host()
     H.sina_host_reset_options()
     _set_options(H, "famfinder", dict({"db": store.key}, **(famfinder or {})))
@@ -440,7 +527,7 @@ def run_fasta(store, in_path, out_path, famfinder=None, aligner=None, search=Non
     run = H.sina_host_run_fasta_serial if serial else H.sina_host_run_fasta
     _chk(run(in_path.encode(), out_path.encode(), log_path.encode(), int(search is not None), int(show_dist), batch, out))
     return dict(read=int(out[0]), aligned=int(out[1]), written=int(out[2]), skipped=int(out[3]), avg_sps=out[4],
-                avg_cpm=out[5], avg_idty=out[6])
+                avg_cpm=out[5], avg_idty=out[6], avg_bps=float(H.sina_host_last_avg_bps()))
 
 
 def fasta_roundtrip(in_path, out_path, fasta=None):
