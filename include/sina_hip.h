@@ -292,6 +292,26 @@ int sina_hip_pair_counts(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint64_t
 int sina_hip_pair_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *sequences, uint64_t *entries_visited,
                         uint64_t *launches);
 
+/* The same six counters where the device assembles the alignment: an align call with p->assemble leaves the finished
+ * words of its assembled queries in device memory, and a second kernel queued right behind the assembly counts over
+ * them there -- nothing is packed, staged or uploaded again, 24 bytes per query come back with the results.
+ *
+ * sina_hip_align_count_pairs: the switch, per context, off after init and after fork.  With it on, every align call on
+ * this context (sina_hip_align_graphs, _graphs_wsets, _graphs_any, _families, _families_wsets, _profiles) that runs
+ * with p->assemble on a store that has a helix map counts: one launch per DP launch range.
+ *
+ * sina_hip_staged_pair_counts: [nq][6] = num, AG, AU, CG, GG, GU of the context's last align call, laid out like that
+ * call's `out`.  Host memory owned by the context, valid until its next align call.  NULL if that call counted nothing:
+ * the switch was off, the store had no map, or p->assemble was 0.  Row q is query q's counters where
+ * out[q].assembled == 1 -- equal to what sina_hip_pair_counts gives for the same words -- and six zeros elsewhere (a
+ * query the host finishes, a failed one, every query of the wide path).
+ *
+ * sina_hip_pair_inplace_stats: this kernel's own time (events around its launches) and volume on this context since
+ * init / fork: assembled queries counted, launches.  sina_hip_pair_stats counts the re-upload route only. */
+int sina_hip_align_count_pairs(sina_hip_ctx *ctx, int on);
+const uint32_t *sina_hip_staged_pair_counts(sina_hip_ctx *ctx);
+int sina_hip_pair_inplace_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *sequences, uint64_t *launches);
+
 /* ------------------------------------------------------------- alignment
  * Replaces, for a batch of queries: mseq::mseq + sort + reduce_edges
  * (src/mseq.cpp:47-118, src/graph.h:451-488) when given family ids, compute()

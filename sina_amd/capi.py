@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "sina_hip_match_count", "sina_hip_kmer_topk_match", "sina_hip_match_stats",
     "sina_hip_upload_name_order", "sina_hip_compare_rank", "sina_hip_kmer_topk_rank", "sina_hip_rank_stats",
     "sina_hip_upload_pairs", "sina_hip_pair_counts", "sina_hip_pair_stats",
+    "sina_hip_align_count_pairs", "sina_hip_staged_pair_counts", "sina_hip_pair_inplace_stats",
 ]
 
 # include/sina_hip.h: SINA_CMP_COVER_*, in CMP_COVER_TYPE's order
@@ -157,6 +158,10 @@ def load():
     L.sina_hip_upload_pairs.argtypes = [vp, u32p, C.c_uint32]
     L.sina_hip_pair_counts.argtypes = [vp, u32p, u64p, C.c_uint32, u32p]
     L.sina_hip_pair_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
+    L.sina_hip_align_count_pairs.argtypes = [vp, C.c_int]
+    L.sina_hip_staged_pair_counts.restype = C.POINTER(C.c_uint32)
+    L.sina_hip_staged_pair_counts.argtypes = [vp]
+    L.sina_hip_pair_inplace_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p]
     L.sina_hip_last_error_is_limit.restype = C.c_int
     L.sina_hip_debug_mesh_wide.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
                                            u32p, u32p, f32p]
@@ -354,6 +359,7 @@ class Context:
         params = params or self.params()
         qmask = _c(qmask, np.uint8)
         qoff = _c(qoff, np.uint64)
+        self._align_nq = len(qoff) - 1                  # (staged_pair_counts: rows of the last align call)
         out = np.zeros(gb.nq, ALIGN_OUT_DTYPE)
         pos = np.zeros(max(len(qmask), 1), np.uint32)
         self._check(self.L.sina_hip_align_graphs(self.h, C.byref(gb), _ptr(qmask, u8p), _ptr(qoff, u64p),
@@ -367,6 +373,7 @@ class Context:
         params = params or self.params()
         qmask = _c(qmask, np.uint8)
         qoff = _c(qoff, np.uint64)
+        self._align_nq = len(qoff) - 1                  # (staged_pair_counts: rows of the last align call)
         out = np.zeros(gb.nq, ALIGN_OUT_DTYPE)
         pos = np.zeros(max(len(qmask), 1), np.uint32)
         self._check(self.L.sina_hip_align_graphs_any(self.h, C.byref(gb), _ptr(qmask, u8p), _ptr(qoff, u64p),
@@ -524,12 +531,36 @@ class Context:
         return dict(kernel_ms=float(ms.value), sequences=int(seqs.value), entries_visited=int(ent.value),
                     launches=int(launches.value))
 
+    def count_pairs(self, on=True):
+        """The switch of the in-place pair count: with it on, an align call with assemble=1 on a store with a helix map
+        also counts the helix base pairs of every query it assembles (staged_pair_counts).  Off after init and fork."""
+        self._check(self.L.sina_hip_align_count_pairs(self.h, 1 if on else 0))
+
+    def staged_pair_counts(self):
+        """uint32 [nq, 6] = num, AG, AU, CG, GG, GU of this context's last align call (a copy), rows laid out like its
+        `out`: a query's counters where out[q].assembled == 1, six zeros elsewhere.  None if that call counted nothing
+        (switch off, no helix map, assemble=0)."""
+        p = self.L.sina_hip_staged_pair_counts(self.h)
+        if not p:
+            return None
+        nq = getattr(self, "_align_nq", 0)
+        return np.ctypeslib.as_array(p, shape=(max(nq, 1), 6))[:nq].copy()
+
+    def pair_inplace_stats(self):
+        """The in-place pair-count kernel on this context so far: dict(kernel_ms, sequences, launches); sequences
+        counts assembled queries only."""
+        ms = C.c_double()
+        seqs, launches = C.c_uint64(), C.c_uint64()
+        self._check(self.L.sina_hip_pair_inplace_stats(self.h, C.byref(ms), C.byref(seqs), C.byref(launches)))
+        return dict(kernel_ms=float(ms.value), sequences=int(seqs.value), launches=int(launches.value))
+
     def align_families(self, fam_ids, fam_off, qmask, qoff, params=None):
         params = params or self.params()
         fam_ids = _c(fam_ids, np.uint32)
         fam_off = _c(fam_off, np.uint64)
         qmask = _c(qmask, np.uint8)
         qoff = _c(qoff, np.uint64)
+        self._align_nq = len(qoff) - 1                  # (staged_pair_counts: rows of the last align call)
         nq = len(qoff) - 1
         out = np.zeros(nq, ALIGN_OUT_DTYPE)
         pos = np.zeros(max(len(qmask), 1), np.uint32)
@@ -551,6 +582,7 @@ class Context:
         """align_graphs with a weight vector per query: params from params_wsets, weight_set[q] < n_sets (or None)."""
         qmask = _c(qmask, np.uint8)
         qoff = _c(qoff, np.uint64)
+        self._align_nq = len(qoff) - 1                  # (staged_pair_counts: rows of the last align call)
         ws = None if weight_set is None else _c(weight_set, np.uint32)
         out = np.zeros(gb.nq, ALIGN_OUT_DTYPE)
         pos = np.zeros(max(len(qmask), 1), np.uint32)
@@ -565,6 +597,7 @@ class Context:
         fam_off = _c(fam_off, np.uint64)
         qmask = _c(qmask, np.uint8)
         qoff = _c(qoff, np.uint64)
+        self._align_nq = len(qoff) - 1                  # (staged_pair_counts: rows of the last align call)
         ws = None if weight_set is None else _c(weight_set, np.uint32)
         nq = len(qoff) - 1
         out = np.zeros(nq, ALIGN_OUT_DTYPE)
@@ -582,6 +615,7 @@ class Context:
         fam_off = _c(fam_off, np.uint64)
         qmask = _c(qmask, np.uint8)
         qoff = _c(qoff, np.uint64)
+        self._align_nq = len(qoff) - 1                  # (staged_pair_counts: rows of the last align call)
         nq = len(qoff) - 1
         out = np.zeros(nq, ALIGN_OUT_DTYPE)
         pos = np.zeros(max(len(qmask), 1), np.uint32)

@@ -151,11 +151,14 @@ static int align_graphs_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, con
 
     const uint64_t tb_budget_cells = tb_plane_budget(c) / tb_cell_bytes(forbid);
     const uint32_t slots = dp_wave_slots(c, pl.geom.B);
+    // (SINA_HIP_TEST=dp_range_q=N: at most N queries per DP launch range, so that a small call takes several)
+    const uint32_t range_q = (uint32_t)strtoul(test_knob("dp_range_q").c_str(), nullptr, 10);
     auto nodes_of = [&](uint32_t q) { return g->node_off[q + 1] - g->node_off[q]; };
     HostPrep hp;
     for (uint32_t q0 = qa, q1; q0 < qb; q0 = q1) {
         // largest sub-batch whose trace-back plane fits the budget
         q1 = dbg ? q0 + 1 : dp_cut_range(nodes_of, q0, qb, Lp, tb_budget_cells, slots);
+        if (range_q != 0) q1 = std::min(q1, q0 + range_q);
         if (prep_range(g, qoff, q0, q1, Lp, pl.W, &hp, pp.on ? pp.kappa64 : 0.f, spill_q)) return 1;
         const uint32_t bq = q1 - q0;
         const uint64_t nbase = g->node_off[q0], nn = g->node_off[q1] - nbase;
@@ -191,6 +194,7 @@ static int align_graphs_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, con
         l.out = out + q0;
         l.out_pos = out_pos ? out_pos + qbase : nullptr;
         l.out_pos_base = qbase - qoff[0];
+        l.q_base = q0;
         l.profile_batch = profile_batch;
         l.debug_planes = dbg != nullptr;
         l.want_dbg_value = dbg && dbg->value;
@@ -355,6 +359,7 @@ int sina_hip_fork(sina_hip_ctx *parent, sina_hip_ctx **ctx) {
     c->owns_store = false;
     c->lds_budget = parent->lds_budget;
     c->n_cu = parent->n_cu;
+    // (count_pairs stays off: the switch is per context, sina_hip_align_count_pairs)
     c->bind_hints();
     if (finish_ctx(c)) {
         const std::string why = sina_hip_last_error();
@@ -442,6 +447,7 @@ int sina_hip_align_graphs(sina_hip_ctx *c, const sina_hip_graph_batch *g, const 
     if (!c) SH_FAIL("align_graphs: null ctx");
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
+    if (pair_inplace_begin(c, p, g ? g->nq : 0)) return 1;
     return align_graphs_impl(c, g, qmask, qoff, p, out, out_pos);
 }
 
@@ -452,6 +458,7 @@ int sina_hip_align_graphs_wsets(sina_hip_ctx *c, const sina_hip_graph_batch *g, 
     if (p && !weighted_scheme(p)) SH_FAIL("align_graphs_wsets: weight sets need positional weights (p->weights, p->n_weights)");
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
+    if (pair_inplace_begin(c, p, g ? g->nq : 0)) return 1;
     return align_graphs_impl(c, g, qmask, qoff, p, out, out_pos, nullptr, 0, 0, nullptr, nullptr, weight_set, n_sets);
 }
 
@@ -461,6 +468,7 @@ int sina_hip_align_graphs_any(sina_hip_ctx *c, const sina_hip_graph_batch *g, co
     if (!c) SH_FAIL("align_graphs_any: null ctx");
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
+    if (pair_inplace_begin(c, p, g ? g->nq : 0)) return 1;
     return align_graphs_any_impl(c, g, qmask, qoff, p, out, out_pos);
 }
 
@@ -475,6 +483,7 @@ int sina_hip_debug_mesh_wide(sina_hip_ctx *c, const sina_hip_graph_batch *g, con
                              const sina_hip_align_params *p, uint32_t *tb_vm, uint32_t *tb_vs, float *value) {
     if (!c || !g || g->nq != 1 || !qmask || !p || !tb_vm || !tb_vs) SH_FAIL("debug_mesh_wide: needs exactly one query");
     std::lock_guard<std::mutex> lk(c->mu);
+    c->pc_active = false;  // (a debug call counts no pairs)
     SH_CHECK(hipSetDevice(c->device));
     if (p->insertion == SINA_INSERTION_FORBID && !g->succ_minpos) SH_FAIL("debug_mesh_wide: insertion=forbid needs succ_minpos");
     if (g->node_score16 != nullptr && (!g->self_score16 || weighted_scheme(p)))
@@ -492,6 +501,7 @@ int sina_hip_debug_mesh(sina_hip_ctx *c, const sina_hip_graph_batch *g, const ui
                         const sina_hip_align_params *p, uint32_t *tb_vm, uint32_t *tb_vs, float *value, int prune) {
     if (!c || !g || g->nq != 1 || !tb_vm || !tb_vs) SH_FAIL("debug_mesh: needs exactly one query");
     std::lock_guard<std::mutex> lk(c->mu);
+    c->pc_active = false;  // (a debug call counts no pairs)
     const uint64_t qoff[2] = {0, qlen};
     sina_hip_align_out o;
     std::vector<uint32_t> pos(qlen);

@@ -32,6 +32,7 @@ void set_limit_error(const std::string &msg);
 //                                        wide=1 (every query of sina_hip_align_graphs_any takes the wide kernel)  wide_cells=N (its budget, cells per launch)
 //                                        match_floor=N  match_loads=1 (the match-count kernel's chunk floor / one load in flight: tools/perf_msc.py)
 //                                        pair_words=N (words per launch range of the pair-count kernel, pairs.hip)
+//                                        dp_range_q=N (at most N queries per DP launch range: a small call takes several)
 // value of `key` in SINA_HIP_TEST ("" if absent); read every time: tests change it between calls
 inline std::string test_knob(const char *key) {
     const char *e = getenv("SINA_HIP_TEST");
@@ -403,6 +404,9 @@ int launch_mesh_dp(const DpGeom &g, bool weighted, bool forbid, const DpArgs &a,
 int launch_backtrack(const BtArgs &a, hipStream_t s);
 bool backtrack_by_lanes(const BtArgs &a);  // one lane per query (large launches of 16S-long queries), else one wave per query
 int launch_assemble(const BtArgs &a, hipStream_t s);  // (after launch_backtrack, same stream)
+// (after launch_assemble, same stream; pairs.hip) the helix base-pair counters of the launch's queries from the words
+// assemble_kernel left: counts [a.nq][6]; ent: the store's n_ent (column, partner) entries
+int launch_pair_count_assembled(const BtArgs &a, const void *ent, uint32_t n_ent, uint32_t *counts, hipStream_t s);
 // raises a kernel's dynamic-LDS ceiling to a CU's 160 KB, once per kernel and process (mesh_dp.hip)
 int allow_full_lds(const void *kernel);
 
@@ -434,6 +438,7 @@ struct DpLaunch {
     sina_hip_align_out *out = nullptr;
     uint32_t *out_pos = nullptr;  // (optional) the launch's place in the caller's array, and ...
     uint64_t out_pos_base = 0;    // ... in the context's staged columns (ctx.h, h_out_pos)
+    uint32_t q_base = 0;          // the launch's first query among the call's (its rows in the context's staged pair counts, ctx.h, h_pc)
     bool profile_batch = false;   // the DP reads the context's prof16, the walk its self16
     bool debug_planes = false, want_dbg_value = false;  // sina_hip_debug_mesh: planes to unpack, a plane of cell values
     // node entries per DAG of the device-built DAGs whose first member's chain the build left in the context (ctx.h,

@@ -35,6 +35,7 @@ struct sina_hip_store {
     // column, ascending in the column; n_pair_ent == 0: no map.  Kept when the references change (it describes columns)
     sina_hip::DevBuf pair_ent;
     uint32_t n_pair_ent = 0;
+    std::atomic<size_t> pc_rows_hint{0};  // bytes of pinned counter rows the largest counted align call took (sina_hip_ctx::h_pc)
     std::mutex aux_mu;
     std::mutex stats_mu;
     // The device-filling kernels of all contexts (k-mer count/select, DAG build, DP) go through ONE
@@ -112,7 +113,7 @@ struct sina_hip_ctx {
     hipStream_t stream = nullptr;     // uploads, k-mer searches' copies ... (see make_streams)
     hipStream_t stream_dp = nullptr;  // DP hand-over, result copies
     std::mutex mu;
-    hipEvent_t ev[12];  // [10], [11]: hand-over to / from the store's heavy stream
+    hipEvent_t ev[13];  // [10], [11]: hand-over to / from the store's heavy stream; [12]: end of the in-place pair count
 
     sina_hip_store *st = nullptr;
     bool owns_store = false;
@@ -153,6 +154,16 @@ struct sina_hip_ctx {
     // (sina_hip_pair_stats)
     double pair_ms = 0;
     uint64_t pair_seqs = 0, pair_entries = 0, pair_launches = 0;
+    // the pair count of an align call (pairs.hip, pair_count_assembled_kernel; sina_hip_align_count_pairs): the switch;
+    // whether the call in progress -- afterwards: the last one -- counts (pair_inplace_begin); a launch range's rows on
+    // the device; the whole call's rows in pinned memory, laid out like the call's `out` (a range writes at
+    // DpLaunch::q_base; sina_hip_staged_pair_counts); its own time and volume on this context
+    // (sina_hip_pair_inplace_stats)
+    bool count_pairs = false, pc_active = false;
+    sina_hip::DevBuf pc_out;
+    sina_hip::HostBuf h_pc;
+    double pc_ms = 0;
+    uint64_t pc_seqs = 0, pc_launches = 0;
     sina_hip::HostBuf h_out, h_out_pos;  // pinned staging for the DP results
     // h_out_pos holds the aligned columns of a whole align call (laid out like the caller's out_pos): a launch
     // range writes at DpLaunch::out_pos_base, callers that pass no out_pos read them here (sina_hip_staged_out_pos)
@@ -162,7 +173,7 @@ struct sina_hip_ctx {
 
     size_t lds_budget = 0;  // LDS per DP workgroup; 0 = what keeps the register-limited occupancy (dp_default_lds_budget)
 
-    static constexpr int kNumScratch = 48;
+    static constexpr int kNumScratch = 49;
     static_assert(kNumScratch <= 64, "sina_hip_store::cap_hint is too short");
     void scratch(sina_hip::DevBuf **all) {
         sina_hip::DevBuf *list[kNumScratch] = {&qd, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &res,
@@ -171,7 +182,7 @@ struct sina_hip_ctx {
                                                &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &order,
                                                &s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &edge, &prof16, &self16, &rgain,
                                                &scout, &scout_u, &wset, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag,
-                                               &r_cnt};
+                                               &r_cnt, &pc_out};
         for (int i = 0; i < kNumScratch; i++) all[i] = list[i];
     }
     void publish_hints() {  // after a call: remember how big my buffers had to be
@@ -200,7 +211,7 @@ struct sina_hip_ctx {
                                       &s_qab, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};  // (s_qab, r_*: sina_hip_kmer_topk_rank)
         sina_hip::DevBuf *align[] = {&qd, &order, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &edge, &res, &weights, &out,
                                      &out_pos, &g_fam_ids, &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &rgain, &scout, &scout_u,
-                                     &prof16, &self16, &wset};
+                                     &prof16, &self16, &wset, &pc_out};
         sina_hip::DevBuf *compare[] = {&s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};
         sina_hip::DevBuf **list = kind == 0 ? search : (kind == 1 ? align : compare);
         const size_t n = kind == 0 ? sizeof search / sizeof *search : (kind == 1 ? sizeof align / sizeof *align : sizeof compare / sizeof *compare);
@@ -208,6 +219,9 @@ struct sina_hip_ctx {
             const size_t want = list[i]->hint ? list[i]->hint->load(std::memory_order_relaxed) : 0;
             if (want > list[i]->cap && list[i]->reserve_exact(want)) return 1;
         }
+        // (the pinned rows of the in-place pair count: as many as any context of the store has needed -- none, and
+        // nothing is reserved, on a store whose contexts have not counted)
+        if (kind == 1 && h_pc.reserve(st->pc_rows_hint.load(std::memory_order_relaxed))) return 1;
         return 0;
     }
     void free_all() {
@@ -222,6 +236,7 @@ struct sina_hip_ctx {
         k_big_tmp.release();
         h_out.release();
         h_out_pos.release();
+        h_pc.release();
         h_res.release();
         for (auto &h : h_stage) h.release();
         if (owns_store && st) {
@@ -655,6 +670,27 @@ int rank_launch(sina_hip_ctx *c, const uint32_t *d_qab, const uint64_t *d_qoff, 
                 int filter_lc, int cover, uint32_t N, uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint32_t *out_flag);
 // fails on an unknown rule, max_result outside 1..64, a store without references or without a name order
 int rank_check_rules(const char *who, sina_hip_ctx *c, int iupac_rule, int cover_rule, uint32_t max_result);
+}  // namespace sina_hip
+
+namespace sina_hip {
+// ---- the pair count of an align call (sina_hip_align_count_pairs).  Every align entry calls this first, for its nq
+// queries: the call counts if the switch is on, the call assembles and the store has a helix map; then the pinned rows
+// are there for the whole call and zero -- a launch range fills its queries' rows (fetch_results), the queries that
+// never see a DP launch range (the wide path) keep the zeros.  A call that does not count forgets the rows of the one
+// before (sina_hip_staged_pair_counts: NULL).
+inline int pair_inplace_begin(sina_hip_ctx *c, const sina_hip_align_params *p, uint32_t nq) {
+    c->pc_active = false;
+    if (!c->count_pairs || !p || !p->assemble || nq == 0 || c->st->n_pair_ent == 0) return 0;
+    const size_t bytes = 24 * (size_t)nq;
+    SH_CHECK(hipSetDevice(c->device));
+    if (c->h_pc.reserve(bytes)) return 1;
+    size_t seen = c->st->pc_rows_hint.load(std::memory_order_relaxed);
+    while (bytes > seen && !c->st->pc_rows_hint.compare_exchange_weak(seen, bytes, std::memory_order_relaxed)) {
+    }
+    memset(c->h_pc.p, 0, bytes);
+    c->pc_active = true;
+    return 0;
+}
 }  // namespace sina_hip
 
 // publishes the context's scratch capacities when an API call ends (see sina_hip_store::cap_hint)

@@ -85,7 +85,7 @@ int reserve_launch_buffers(sina_hip_ctx *c, const DpPlan &pl, const DpLaunch &l,
     if (c->spill.reserve(std::max<uint64_t>(sums.spill_rows, 1) * 8 * (uint64_t)pl.geom.Lp()) ||
         c->edge.reserve(std::max<uint64_t>(1, (uint64_t)(pl.geom.T / 64 - 1) * sums.edge_entries) * sizeof(EdgeRec)) ||
         c->res.reserve(sizeof(DpResult) * l.bq) || c->out.reserve(sizeof(sina_hip_align_out) * l.bq) ||
-        c->out_pos.reserve(4 * std::max<uint64_t>(l.nqm, 1)))
+        c->out_pos.reserve(4 * std::max<uint64_t>(l.nqm, 1)) || (c->pc_active && c->pc_out.reserve(24 * (size_t)l.bq)))
         return 1;
     if (l.want_dbg_value && c->dbg.reserve(4 * sums.tb_cells)) return 1;
     return 0;
@@ -209,6 +209,16 @@ int choose_bound(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const s
     return 0;
 }
 
+// The pair count of a call that counts (ctx.h, pair_inplace_begin): right behind the assembly, on its stream, over the
+// words it left.  Like launch_assemble it takes no part in the FIFO's dry signal -- the DP kernel gives that --, and
+// ev[2] (the walk's and the assembly's end) to ev[12] is its own time.
+static int launch_pair_count(sina_hip_ctx *c, const BtArgs &b, hipStream_t s) {
+    if (!c->pc_active) return 0;
+    if (launch_pair_count_assembled(b, c->st->pair_ent.p, c->st->n_pair_ent, c->pc_out.as<uint32_t>(), s)) return 1;
+    SH_CHECK(hipEventRecord(c->ev[12], s));
+    return 0;
+}
+
 // Queues the DP kernel, the walk and the assembly; *dp_no: this launch's number among the store's DP launches (~0: none).
 // With chained launches the walk and the assembly are queued right behind their DP kernel on the same FIFO stream: they
 // start the moment it ends, run beside the launch that started in its drain (the other FIFO stream), and the launch
@@ -239,6 +249,7 @@ int launch_dp_and_walk(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_p
             if (launch_backtrack(b, hl.stream())) return 1;
             if (p->assemble && launch_assemble(b, hl.stream())) return 1;
             SH_CHECK(hipEventRecord(c->ev[2], hl.stream()));
+            if (p->assemble && launch_pair_count(c, b, hl.stream())) return 1;
             bt_done = true;
         }
         if (hl.done()) return 1;
@@ -247,11 +258,13 @@ int launch_dp_and_walk(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_p
         if (launch_backtrack(b, s)) return 1;
         if (p->assemble && launch_assemble(b, s)) return 1;
         SH_CHECK(hipEventRecord(c->ev[2], s));
+        if (p->assemble && launch_pair_count(c, b, s)) return 1;
     }
     return 0;
 }
 
-// (h_out_pos was sized for the whole call by the entry point; this range's columns go to their place in it)
+// (h_out_pos was sized for the whole call by the entry point; this range's columns go to their place in it -- and so
+// do its pair counters in h_pc, if the call counts)
 int fetch_results(sina_hip_ctx *c, const DpLaunch &l) {
     hipStream_t s = c->stream_dp;
     if (c->h_out.reserve(sizeof(sina_hip_align_out) * l.bq) || c->h_res.reserve(sizeof(DpResult) * l.bq)) return 1;
@@ -259,6 +272,8 @@ int fetch_results(sina_hip_ctx *c, const DpLaunch &l) {
     SH_CHECK(hipMemcpyAsync(c->h_out.p, c->out.p, sizeof(sina_hip_align_out) * l.bq, hipMemcpyDeviceToHost, s));
     SH_CHECK(hipMemcpyAsync(c->h_res.p, c->res.p, sizeof(DpResult) * l.bq, hipMemcpyDeviceToHost, s));
     SH_CHECK(hipMemcpyAsync(staged_pos, c->out_pos.p, 4 * l.nqm, hipMemcpyDeviceToHost, s));
+    if (c->pc_active)
+        SH_CHECK(hipMemcpyAsync(c->h_pc.as<uint32_t>() + 6 * (size_t)l.q_base, c->pc_out.p, 24 * (size_t)l.bq, hipMemcpyDeviceToHost, s));
     SH_CHECK(wait_stream(c, s));
     memcpy(l.out, c->h_out.p, sizeof(sina_hip_align_out) * l.bq);
     if (l.out_pos) memcpy(l.out_pos, staged_pos, 4 * l.nqm);
@@ -288,6 +303,12 @@ int account_launch(sina_hip_ctx *c, const DpPlan &pl, const DpLaunch &l, uint64_
     st.dp_busy_ms += ms - shared;
     SH_CHECK(hipEventElapsedTime(&ms, c->ev[1], c->ev[2]));
     st.backtrack_ms += ms;
+    if (c->pc_active) {  // (the context's own counters: its caller holds its mutex)
+        SH_CHECK(hipEventElapsedTime(&ms, c->ev[2], c->ev[12]));
+        c->pc_ms += ms;
+        c->pc_launches++;
+        for (uint32_t q = 0; q < l.bq; q++) c->pc_seqs += (l.out[q].status == 0 && l.out[q].assembled != 0) ? 1u : 0u;
+    }
     st.dp_cells += cells;
     st.dp_launches++;
     st.dp_rows += sw.rows_nominal;
@@ -340,6 +361,7 @@ int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {
     if (check_weight_sets(f.who, p, &weight_set, &n_sets, nq)) return 1;
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
+    c->pc_active = false;  // (until pair_inplace_begin says otherwise: a call that ends early has counted nothing)
     if (!c->st->have_refs) SH_FAIL(w + ": upload references first");
     if (nq == 0) return 0;
     SH_CHECK(hipSetDevice(c->device));
@@ -359,6 +381,9 @@ int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {
     const int Lp = pl.geom.Lp();
     if (upload_weights(c, p, n_sets)) return 1;
     if (c->h_out_pos.reserve(4 * std::max<uint64_t>(qoff[nq] - qoff[0], 1))) return 1;
+    if (pair_inplace_begin(c, p, nq)) return 1;
+    // (SINA_HIP_TEST=dp_range_q=N: at most N queries per DP launch range, so that a small call takes several)
+    const uint32_t range_q = (uint32_t)strtoul(test_knob("dp_range_q").c_str(), nullptr, 10);
 
     const uint64_t tb_budget_cells = tb_plane_budget(c) / tb_cell_bytes(p->insertion == SINA_INSERTION_FORBID);
     // queries per DAG build and DP launch: up to three rounds of DP wave slots (one DP wave per query) -- a DP
@@ -396,6 +421,7 @@ int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {
         auto nodes_of = [&](uint32_t r) { return bg.sizes[(size_t)kBuiltWords * dag_of[r] + kBuiltN]; };
         for (uint32_t r0 = 0, r1; r0 < bq; r0 = r1) {
             r1 = dp_cut_range(nodes_of, r0, bq, Lp, tb_budget_cells, slots);
+            if (range_q != 0) r1 = std::min(r1, r0 + range_q);
             family_qdescs(bg, dag_of.data(), qoff, q0, r0, r1, Lp, &qd);
             const uint32_t rq = r1 - r0;
             const uint64_t qbase = qoff[q0 + r0], nqm = qoff[q0 + r1] - qbase;
@@ -410,6 +436,7 @@ int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {
             l.out = f.out + q0 + r0;
             l.out_pos = f.out_pos ? f.out_pos + qbase : nullptr;
             l.out_pos_base = qbase - qoff[0];
+            l.q_base = q0 + r0;
             l.profile_batch = f.profile_batch;  // (the DP reads the builder's prof16, the walk the entry point's self16)
             l.chain_ncap = f.profile_batch ? 0u : bg.ncap;
             l.wset = weight_set ? weight_set + q0 + r0 : nullptr;

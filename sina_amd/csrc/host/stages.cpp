@@ -692,6 +692,24 @@ void reference_store::pair_stats(double *kernel_ms, uint64_t *sequences, uint64_
     for (auto &pool : idle_forks)
         for (sina_hip_ctx *c : pool) add(c);
 }
+void reference_store::pair_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *launches) {
+    sina_hip_ctx *root = device();
+    std::lock_guard<std::mutex> lk(gpu_mu);
+    *trays = n_bp_inplace.load(std::memory_order_relaxed);
+    *kernel_ms = 0;
+    *sequences = *launches = 0;
+    auto add = [&](sina_hip_ctx *c) {
+        double ms = 0;
+        uint64_t n = 0, l = 0;
+        hip_check(sina_hip_pair_inplace_stats(c, &ms, &n, &l), "sina_hip_pair_inplace_stats");
+        *kernel_ms += ms;
+        *sequences += n;
+        *launches += l;
+    };
+    add(root);
+    for (auto &pool : idle_forks)
+        for (sina_hip_ctx *c : pool) add(c);
+}
 bool reference_store::match_counts_too_wide() {
     if (sina_hip::match_table_bytes(width) <= sina_hip::kMatchMaxLds) return false;
     if (!too_wide_said.exchange(true))
@@ -1789,6 +1807,9 @@ static aligner::options al_defaults() {  // src/align.cpp:231-274
     // families beyond the fast DP path's limits (sina_hip.h) through sina_hip_align_graphs_any and its wide kernel:
     // on request
     o.wide_fallback = false;
+    // the helix base-pair score from the align call itself (sina_hip_align_count_pairs) instead of a second trip with
+    // the finished alignments (pair_score_batch): on request, until it has been decided on measurements
+    o.device_bps = false;
     return o;
 }
 static aligner::options &al_opts() {
@@ -1830,6 +1851,7 @@ void aligner::set_option(const std::string &name, const std::string &value) {
     else if (name == "device-profile") o.device_profile = to_bool(value);
     else if (name == "wide-fallback") o.wide_fallback = to_bool(value);
     else if (name == "weight-sets") o.weight_sets = to_bool(value);
+    else if (name == "device-bps") o.device_bps = to_bool(value);
     else if (name == "db") o.database = value;
     else throw std::logic_error("aligner: unknown option " + name);
 }
@@ -2287,8 +2309,10 @@ static uint64_t assemble_on_host(tray &t, cseq &c, const sina_hip_align_out &r, 
 
 // Takes a job, its slot's device result `r` and aligned columns `pos`; gives the tray its aligned sequence, attributes and log
 // (backtrack()'s container steps, src/mesh.h:603-736, + do_align's attributes, src/align.cpp:507-509).  Throws on a failed query.
-static void finish_tray(dp_job &jb, const sina_hip_align_out &r, const uint32_t *pos, uint32_t width, const aligner::options &o,
-                        bool defer_score_line) {
+// pair_row (device-bps; else null): the six helix base-pair counters the align call counted for the slot -- the tray's
+// score if the device assembled the alignment (only then the counters are of the finished words); gives whether it was taken.
+static bool finish_tray(dp_job &jb, const sina_hip_align_out &r, const uint32_t *pos, uint32_t width, const aligner::options &o,
+                        bool defer_score_line, const uint32_t *pair_row = nullptr) {
     tray &t = *jb.t;
     if (r.status != 0) throw std::runtime_error("device alignment failed for " + t.input_sequence->getName());
     uint64_t tk = host_tsc();
@@ -2329,6 +2353,10 @@ static void finish_tray(dp_job &jb, const sina_hip_align_out &r, const uint32_t 
             t.log << "total inserted bases=" << r.nast_total << ";"
                   << "longest insertion=" << r.nast_longest << ";"
                   << "total inserted bases before shifting=" << r.nast_last_run << ";";
+        if (pair_row != nullptr) {
+            t.bp_score = pair_score_from_counts(pair_row);
+            t.bp_score_set = true;
+        }
     } else {
         tk = assemble_on_host(t, c, r, pos, width, o, tk);
     }
@@ -2351,6 +2379,7 @@ static void finish_tray(dp_job &jb, const sina_hip_align_out &r, const uint32_t 
     }
     t.aligned_sequence = &c;
     host_tick("finish: attributes", tk);
+    return r.assembled && pair_row != nullptr;
 }
 
 // most pairs of one comparison launch: a batch with more is compared in slices of whole queries
@@ -2405,7 +2434,9 @@ static void set_family_identity(const std::vector<dp_job *> &members, reference_
 
 // src/align.cpp:307-460 for a batch of trays: prepare every tray, group those that need the DP, then per group pack
 // the queries, find the distinct ones, align them on the device, finish every tray and -- on request -- its identity.
-void aligner::operator()(std::vector<tray> &batch) {
+void aligner::operator()(std::vector<tray> &batch) { align_batch(batch, true); }
+
+void aligner::align_batch(std::vector<tray> &batch, bool batch_driver) {
     const options &o = al_opts();
     std::vector<dp_job> jobs(batch.size());  // (a tray that needs the DP has its job's `t` set)
     const std::string db = o.database.empty() ? ff_opts.database : o.database;
@@ -2506,6 +2537,11 @@ void aligner::operator()(std::vector<tray> &batch) {
         // (the aligned columns are read where the device copied them, in the context's pinned staging buffer:
         // sina_hip_staged_out_pos -- the context stays leased until the group's last tray is finished)
         auto dev = store->worker_device(reference_store::dev_align);
+        // device-bps: the call counts the helix base pairs of the queries it assembles.  Set either way -- the leased
+        // context keeps the switch of whoever had it before -- and never for the one-slot calls of the long route (the
+        // wide path assembles nothing) or a single tray (its sink takes the host walk, as before).
+        const bool count_pairs = o.device_bps && batch_driver && grp_route != route_long && store->pairs() != nullptr && p.assemble != 0;
+        hip_check(sina_hip_align_count_pairs(dev.get(), count_pairs ? 1 : 0), "sina_hip_align_count_pairs");
         if (grp_route == route_long) {
             // One call per slot: a wide mesh of this size fills a launch of the wide kernel nearly alone anyway, and a
             // query whose mesh exceeds SINA_HIP_WIDE_CELLS -- the one thing a call refuses a well-formed query for --
@@ -2544,12 +2580,18 @@ void aligner::operator()(std::vector<tray> &batch) {
         }
         const uint32_t width = align_slots(dev.get(), *store, o, p, slots, grp_route == route_device, out.data());
         const uint32_t *const staged_pos = sina_hip_staged_out_pos(dev.get());
+        // (null unless this call counted; the trays of a slot share its row)
+        const uint32_t *const staged_pairs = count_pairs ? sina_hip_staged_pair_counts(dev.get()) : nullptr;
         {
             scoped_phase ph("al.finish(NAST,log)");
+            std::atomic<uint64_t> scored{0};
             parallel_for(members.size(), [&](size_t x) {
                 const uint32_t u = slots.slot_of[x];
-                finish_tray(*members[x], out[u], staged_pos + slots.dqoff[u], width, o, defer_score_line);
+                if (finish_tray(*members[x], out[u], staged_pos + slots.dqoff[u], width, o, defer_score_line,
+                                staged_pairs ? staged_pairs + 6 * (size_t)u : nullptr))
+                    scored.fetch_add(1, std::memory_order_relaxed);
             });
+            if (staged_pairs) store->count_pairs_inplace(scored.load());
         }
         if (o.calc_idty) set_family_identity(members, *store);  // (its own context, while this group's is still leased)
     }
@@ -2557,7 +2599,7 @@ void aligner::operator()(std::vector<tray> &batch) {
 
 tray aligner::operator()(tray t) {
     std::vector<tray> b{t};
-    (*this)(b);
+    align_batch(b, false);
     return b[0];
 }
 
@@ -3147,7 +3189,7 @@ void pair_score_batch(std::vector<tray> &batch) {
         std::vector<char> kind(batch.size(), 0);  // 1: device, 2: host walk
         parallel_for(batch.size(), [&](size_t i) {
             tray &t = batch[i];
-            if (t.aligned_sequence == nullptr) return;
+            if (t.aligned_sequence == nullptr || t.bp_score_set) return;  // (set: the aligner's device-bps has scored it)
             if (columns_ascend(*t.aligned_sequence)) kind[i] = 1;
             else {
                 t.bp_score = t.aligned_sequence->calcPairScore(*map);

@@ -341,6 +341,11 @@ public:
     pair_map pairs();  // null: no map
     // ... and the pair-count kernel's time and volume on the store's contexts -- sina_hip_pair_stats
     void pair_stats(double *kernel_ms, uint64_t *sequences, uint64_t *entries_visited, uint64_t *launches);
+    // the aligner's device-bps: trays that took their score from the counters their align call brought back (no
+    // second trip) since the store was opened, and the in-place kernel's time and volume on the store's contexts --
+    // sina_hip_pair_inplace_stats
+    void count_pairs_inplace(uint64_t trays) { n_bp_inplace.fetch_add(trays, std::memory_order_relaxed); }
+    void pair_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *launches);
 
 private:
     reference_store() = default;
@@ -366,6 +371,7 @@ private:
     std::atomic<bool> too_wide_said{false};
     std::atomic<int> name_order_state{0};  // 0: not looked at, 1: uploaded, 2: names repeat
     std::atomic<uint64_t> n_ranked{0}, n_rank_host{0};
+    std::atomic<uint64_t> n_bp_inplace{0};
     pair_map helix;
     std::mutex helix_mu;
 };
@@ -463,6 +469,8 @@ public:
         bool device_graph;  // build the family DAG on the GPU (default) or on the host
         bool weight_sets;   // device-built DAGs: the weighted trays of a batch in ONE call whatever their filters
                             // (sina_hip_align_families_wsets; default on) instead of one call per filter
+        bool device_bps;    // a store with a helix map: the align call counts the base pairs of the queries it assembles and
+                            // their trays leave the aligner scored (sina_hip_align_count_pairs; default off)
         std::string database;  // reference store the DAGs are built from (same as famfinder "db")
     };
     static options *opts;
@@ -477,6 +485,8 @@ public:
     aligner &operator=(const aligner &rhs);
     tray operator()(tray t);
     void operator()(std::vector<tray> &batch);
+    // (batch_driver: the trays go on to pair_score_batch -- device-bps may score them here; a single tray's sink walks)
+    void align_batch(std::vector<tray> &batch, bool batch_driver);
 
     // "realign", "overhang", "lowercase", "insertion", "fs-weight", "match-score",
     // "mismatch-score", "pen-gap", "pen-gapext", "write-used-rels", "calc-idty", "db", "weight-sets"
@@ -614,6 +624,7 @@ reference_store::pair_map aligner_pair_map();
 // The pair step of a batch driver, after the aligner (and the search stage): if the store has a helix map, every
 // tray with an aligned sequence gets its bp_score -- the trays whose columns ascend strictly from ONE
 // sina_hip_pair_counts call, the others from the host walk.  Without a map: nothing is packed, called or launched.
+// A tray that already has its score (the aligner's device-bps) is left alone.
 void pair_score_batch(std::vector<tray> &batch);
 // a tray's score for its sink: the field if set, else the host walk over `map`, else (no map, or not aligned) 0
 float tray_pair_score(const tray &t, const reference_store::pair_map &map);

@@ -1,5 +1,8 @@
 // The helix base-pair score on the GPU: pair_count_kernel + sina_hip_upload_pairs,
-// sina_hip_pair_counts, sina_hip_pair_stats.
+// sina_hip_pair_counts, sina_hip_pair_stats over finished alignments a caller hands in; pair_count_assembled_kernel +
+// sina_hip_align_count_pairs, sina_hip_staged_pair_counts, sina_hip_pair_inplace_stats over the alignments an align
+// call has just assembled on the device (launched by dp_launch.hip).  The look-up and the classification are one
+// piece of device code for both (pair_dev.h).
 //
 // What it computes: for every finished aligned sequence the counters behind align_bp_score_slv
 // (cseq_base::calcPairScore, src/cseq.cpp:651-733): for every column i that the helix map pairs with a column p, the
@@ -17,6 +20,7 @@
 
 #include "common.h"
 #include "ctx.h"
+#include "pair_dev.h"
 #include "pair_plan.h"
 
 namespace sina_hip {
@@ -32,70 +36,58 @@ struct PairArgs {
     uint32_t n, n_ent;
 };
 
-constexpr uint32_t kGap = 32;  // "no base in that column": beside the 5-bit masks 0..31
-
-// What the sequence shows in column c: the five mask bits of the first word whose column is >= c if that column is c,
-// else kGap.  (A column of 2^24 or more is beyond every word: the search ends at len.)
-__device__ __forceinline__ uint32_t mask_at(const uint32_t *W, uint32_t len, uint32_t c) {
-    if (len == 0) return kGap;
-    uint32_t base = 0, n = len;
-    while (n > 1) {  // (lower_bound without a branch on the data: answer in [base, base + n])
-        const uint32_t half = n >> 1;
-        base = (W[base + half] & 0xFFFFFFu) < c ? base + half : base;
-        n -= half;
-    }
-    const uint32_t w0 = W[base];
-    const uint32_t at = base + ((w0 & 0xFFFFFFu) < c ? 1u : 0u);
-    const uint32_t w = at < len ? W[at] : 0xFFFFFFFFu;  // (at <= len; at == len: no word at or after c)
-    return (at < len && (w & 0xFFFFFFu) == c) ? ((w >> 24) & 31u) : kGap;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 __global__ void __launch_bounds__(kPT) pair_count_kernel(PairArgs a) {
     const uint32_t seq = blockIdx.x * kPairWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (seq >= a.n) return;  // (whole waves)
     const uint64_t b = a.q_off[seq];
     const uint32_t len = (uint32_t)(a.q_off[seq + 1] - b);
     const uint32_t *W = a.q_ab + b;
-    uint32_t num = 0, ag = 0, au = 0, cg = 0, gg = 0, gu = 0;
-    for (uint32_t e = lane; e < a.n_ent; e += 64) {
-        const uint2 en = a.ent[e];
-        const uint32_t l = mask_at(W, len, en.x), r = mask_at(W, len, en.y);
-        // '.': a word without mask bits, either case
-        const bool dot = (l != kGap && (l & 15u) == 0) || (r != kGap && (r & 15u) == 0);
-        const bool counted = !dot && !(l == kGap && r == kGap);
-        num += counted ? 1u : 0u;
-        // the weighted classes: two upper-case bases of one bit each (A 1, G 2, C 4, U 8)
-        const bool plain = counted && l < 16u && r < 16u && __popc(l) == 1 && __popc(r) == 1;
-        const uint32_t both = l | r;
-        ag += (plain && both == 3u) ? 1u : 0u;
-        au += (plain && both == 9u) ? 1u : 0u;
-        cg += (plain && both == 6u) ? 1u : 0u;
-        gg += (plain && l == 2u && r == 2u) ? 1u : 0u;
-        gu += (plain && both == 10u) ? 1u : 0u;
+    pair_count_wave(W, len, a.ent, a.n_ent, lane, a.out + (size_t)seq * 6);
+}
+
+// The same count where the words already lie: behind assemble_kernel (mesh_dp.hip) on its stream, over the words it
+// left in BtArgs::out_pos -- no packing, no staging, no upload.  One wave per query of the DP launch range; a query
+// the device did not finish (assembled == 0) or that failed (status != 0) gets six zeros, so every row is defined.
+// There is no check of the columns here, as pair_first_descending is one for words a caller hands in: assembled == 1
+// says that every insertion fitted its gap and every column is below the width (assemble_kernel), so the n_out words
+// are the query's bases in strictly ascending columns -- what mask_at's search needs.
+struct PairAsmArgs {
+    const QDesc *qd;
+    const sina_hip_align_out *out;
+    const uint32_t *out_pos;
+    const uint2 *ent;  // [n_ent] (column, partner)
+    uint32_t *counts;  // [n][6]
+    uint32_t n, n_ent;
+};
+
+__global__ void __launch_bounds__(kPT) pair_count_assembled_kernel(PairAsmArgs a) {
+    const uint32_t q = blockIdx.x * kPairWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (q >= a.n) return;  // (whole waves)
+    const sina_hip_align_out *o = a.out + q;
+    uint32_t *row = a.counts + (size_t)q * 6;
+    if (o->status != 0 || o->assembled == 0) {  // (the same for every lane of the wave)
+        if (lane < 6) row[lane] = 0;
+        return;
     }
-    num = wave_sum(num);
-    ag = wave_sum(ag);
-    au = wave_sum(au);
-    cg = wave_sum(cg);
-    gg = wave_sum(gg);
-    gu = wave_sum(gu);
-    if (lane == 0) {
-        uint32_t *o = a.out + (size_t)seq * 6;
-        o[0] = num;
-        o[1] = ag;
-        o[2] = au;
-        o[3] = cg;
-        o[4] = gg;
-        o[5] = gu;
-    }
+    pair_count_wave(a.out_pos + a.qd[q].q_off, o->n_out, a.ent, a.n_ent, lane, row);
 }
 
 }  // namespace
+
+int launch_pair_count_assembled(const BtArgs &b, const void *ent, uint32_t n_ent, uint32_t *counts, hipStream_t s) {
+    PairAsmArgs a;
+    a.qd = b.qd;
+    a.out = b.out;
+    a.out_pos = b.out_pos;
+    a.ent = static_cast<const uint2 *>(ent);
+    a.counts = counts;
+    a.n = b.nq;
+    a.n_ent = n_ent;
+    hipLaunchKernelGGL(pair_count_assembled_kernel, dim3(pair_grid(b.nq)), dim3(kPT), 0, s, a);
+    SH_CHECK(hipGetLastError());
+    return 0;
+}
+
 }  // namespace sina_hip
 
 using namespace sina_hip;
@@ -175,5 +167,30 @@ extern "C" int sina_hip_pair_stats(sina_hip_ctx *c, double *kernel_ms, uint64_t 
     *sequences = c->pair_seqs;
     *entries_visited = c->pair_entries;
     *launches = c->pair_launches;
+    return 0;
+}
+
+extern "C" int sina_hip_align_count_pairs(sina_hip_ctx *c, int on) {
+    if (!c) SH_FAIL("align_count_pairs: null ctx");
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->count_pairs = on != 0;
+    return 0;
+}
+
+extern "C" const uint32_t *sina_hip_staged_pair_counts(sina_hip_ctx *c) {
+    if (!c) {
+        set_error("staged_pair_counts: null ctx");
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    return c->pc_active ? c->h_pc.as<uint32_t>() : nullptr;
+}
+
+extern "C" int sina_hip_pair_inplace_stats(sina_hip_ctx *c, double *kernel_ms, uint64_t *sequences, uint64_t *launches) {
+    if (!c || !kernel_ms || !sequences || !launches) SH_FAIL("pair_inplace_stats: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *kernel_ms = c->pc_ms;
+    *sequences = c->pc_seqs;
+    *launches = c->pc_launches;
     return 0;
 }

@@ -97,6 +97,7 @@ def load_host():
     H.sina_host_search_seconds.argtypes = [vp]
     H.sina_host_store_set_pairs.argtypes = [C.c_char_p, capi.u32p, C.c_uint32]
     H.sina_host_store_pair_stats.argtypes = [C.c_char_p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_store_pair_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p]
     H.sina_host_pair_score.argtypes = [C.c_char_p, capi.u32p, C.c_uint32, capi.f32p, capi.u32p]
     H.sina_host_pair_scores_packed.argtypes = [capi.u32p, capi.u64p, C.c_uint32, capi.u32p, C.c_uint32, capi.f32p, capi.u32p,
                                                C.POINTER(C.c_double)]
@@ -289,6 +290,15 @@ class Store:
         _chk(self.H.sina_host_store_pair_stats(self.key.encode(), C.byref(ms), C.byref(seqs), C.byref(ent), C.byref(launches)))
         return dict(kernel_ms=float(ms.value), sequences=int(seqs.value), entries_visited=int(ent.value),
                     launches=int(launches.value))
+
+    def pair_inplace_stats(self):
+        """The aligner's device-bps on this store so far: dict(trays, sequences, launches, kernel_ms) -- trays that took
+        their score from the counters their align call brought back, and the in-place kernel's assembled queries,
+        launches and time on the store's contexts -- between runs, like pair_stats()."""
+        ms = C.c_double()
+        trays, seqs, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _chk(self.H.sina_host_store_pair_inplace_stats(self.key.encode(), C.byref(trays), C.byref(ms), C.byref(seqs), C.byref(launches)))
+        return dict(trays=int(trays.value), sequences=int(seqs.value), launches=int(launches.value), kernel_ms=float(ms.value))
 
     def close(self):
         self.H.sina_host_store_close(self.key.encode())

@@ -110,6 +110,14 @@ int sina_hip_rank_stats(sina_hip_ctx *, double *ms, uint64_t *pairs, uint64_t *b
     *pairs = *bases = *launches = 0;
     return 0;
 }
+// (the switch is taken and nothing is counted: an align call of the stub leaves no rows)
+int sina_hip_align_count_pairs(sina_hip_ctx *, int) { return 0; }
+const uint32_t *sina_hip_staged_pair_counts(sina_hip_ctx *) { return nullptr; }
+int sina_hip_pair_inplace_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, uint64_t *launches) {
+    *ms = 0;
+    *seqs = *launches = 0;
+    return 0;
+}
 void sina_hip_align_params_default(sina_hip_align_params *p) {
     memset(p, 0, sizeof(*p));
     p->match_score = 2;

@@ -4,7 +4,10 @@ sina_amd/synth.py, a nested random helix map of about 450 pairs.
     python tools/perf_bps.py host     [--seqs 2000] [--out FILE]     the host walk per sequence on one core (no GPU)
     python tools/perf_bps.py kernel   [--seqs 9216] [--out FILE]     pair_count_kernel alone, and the call around it
     python tools/perf_bps.py pipeline [--queries 9216] [--steps 4] [--refs 100000] [--rounds 2] [--out FILE]
-                                                                     Pipeline.run with and without a helix map
+                                                                     Pipeline.run without a helix map, with one
+                                                                     (the finished alignments uploaded again) and with
+                                                                     one counted where the device assembles them
+                                                                     (aligner device-bps); the three legs alternate
 
 Every mode prints JSON lines; --out appends them to FILE (profiles/perf_bps.txt)."""
 import argparse
@@ -89,26 +92,32 @@ def pipeline_mode(a):
     m = helix_map()
     pl = pipeline.Pipeline(store)
 
-    def run(with_map, tag):
+    def run(with_map, tag, in_place=False):
         store.set_pairs(m if with_map else np.zeros(0, np.uint32))
-        p0 = store.pair_stats()
+        pl._set("aligner", "device-bps", bool(in_place))
+        p0, i0 = store.pair_stats(), store.pair_inplace_stats()
         c0, t0 = os.times(), time.perf_counter()
         pl.run(qs.mask, qs.off, batch=a.queries, inflight=a.inflight)
         wall = time.perf_counter() - t0
         c1 = os.times()
-        p1 = store.pair_stats()
+        p1, i1 = store.pair_stats(), store.pair_inplace_stats()
         cpu = (c1.user - c0.user) + (c1.system - c0.system)
         nz = sum(1 for q in range(0, qs.n, 97) if pl.result(q)["bp_score"] != 0)
-        emit(dict(mode="pipeline", tag=tag, helix_map=bool(with_map), queries=qs.n, batch=a.queries, inflight=a.inflight,
-                  refs=refs.n, wall_s=wall, sequences_per_s=qs.n / wall, busy_host_cores=cpu / wall,
+        emit(dict(mode="pipeline", tag=tag, helix_map=bool(with_map), device_bps=bool(in_place), queries=qs.n, batch=a.queries,
+                  inflight=a.inflight, refs=refs.n, wall_s=wall, sequences_per_s=qs.n / wall, busy_host_cores=cpu / wall,
                   pair_launches=p1["launches"] - p0["launches"], pair_kernel_ms=p1["kernel_ms"] - p0["kernel_ms"],
-                  pair_sequences=p1["sequences"] - p0["sequences"], sampled_results_with_a_score=nz), a.out)
+                  pair_sequences=p1["sequences"] - p0["sequences"],
+                  inplace_trays=i1["trays"] - i0["trays"], inplace_launches=i1["launches"] - i0["launches"],
+                  inplace_kernel_ms=i1["kernel_ms"] - i0["kernel_ms"], inplace_sequences=i1["sequences"] - i0["sequences"],
+                  sampled_results_with_a_score=nz), a.out)
 
     run(False, "warm-up")
     run(True, "warm-up")
+    run(True, "warm-up", in_place=True)
     for rnd in range(a.rounds):
         run(False, "round %d" % rnd)
         run(True, "round %d" % rnd)
+        run(True, "round %d" % rnd, in_place=True)
     pl.close()
     store.close()
 
