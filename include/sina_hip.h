@@ -507,7 +507,17 @@ int sina_hip_debug_mesh_wide(sina_hip_ctx *ctx, const sina_hip_graph_batch *g, c
  * (attempts 0: that launch swept everything), and the first n entries of the per-node bound R(m) the last launch /
  * the last sina_hip_debug_family_graph left on the device (units of 1/64; entry i belongs to node i of the launch's
  * first DAG) with C(m), the number of occupied columns right of the node's.  prune_step = the largest gain of one
- * match step the launch assumed, prune_gmin = the smallest column maximum of query q's DAG, same units. */
+ * match step the launch assumed, prune_gmin = the smallest column maximum of query q's DAG, same units.
+ * kernel = which DP kernel the launch ran: the specialised one, without or with the row skip, or the generic kernel's
+ * instance (simple scheme below / not below the initial value, positional weights, insertion=forbid, both). */
+#define SINA_DP_KERNEL_NONE 0u
+#define SINA_DP_KERNEL_SIMPLE 1u
+#define SINA_DP_KERNEL_SIMPLE_SKIP 2u
+#define SINA_DP_KERNEL_GENERIC_BELOW 3u
+#define SINA_DP_KERNEL_GENERIC 4u
+#define SINA_DP_KERNEL_WEIGHTED 5u
+#define SINA_DP_KERNEL_FORBID 6u
+#define SINA_DP_KERNEL_WEIGHTED_FORBID 7u
 typedef struct sina_hip_dp_info {
     uint32_t end_m, end_s;
     float raw;
@@ -517,6 +527,7 @@ typedef struct sina_hip_dp_info {
     uint32_t prune_step, prune_gmin;
     float scout;  /* what the scout pass found for this query (the first attempt's bound U; +inf: the band never met the
                    * query's last column); NaN: the launch had none */
+    uint32_t kernel;  /* SINA_DP_KERNEL_* of the context's last launch */
 } sina_hip_dp_info;
 int sina_hip_debug_dp_info(sina_hip_ctx *ctx, uint32_t q, sina_hip_dp_info *out);
 int sina_hip_debug_rgain(sina_hip_ctx *ctx, uint32_t n, uint32_t *out, uint32_t *cols_right /* C(m), may be NULL */);

@@ -526,6 +526,7 @@ int sina_hip_debug_dp_info(sina_hip_ctx *c, uint32_t q, sina_hip_dp_info *out) {
     out->gain0 = r.gain0;
     out->ubound = r.ubound;
     out->prune_step = c->last_prune_step;
+    out->kernel = c->last_kernel;
     QDesc d;
     SH_CHECK(hipMemcpy(&d, c->qd.as<QDesc>() + q, sizeof d, hipMemcpyDeviceToHost));
     out->prune_gmin = d.gmin;

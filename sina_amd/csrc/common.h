@@ -300,6 +300,7 @@ __host__ __device__ inline uint32_t prune_gain_units(float w, float kappa64) {
     return u + 1u;
 }
 // what a launch may prune with: non-negative gap costs and weights, sums that stay exact
+constexpr uint32_t kPruneMaxStep = 250;  // the largest gain of one match step, in units, a launch may prune with
 struct PrunePlan {
     int on = 0;
     float kappa64 = 0.f;   // 64 * 1.0001 * max(-ms, -mms, 0): match gain per unit of node weight
@@ -399,8 +400,9 @@ size_t dp_slot_bytes(const DpGeom &g);
 size_t dp_fixed_lds_bytes(const DpGeom &g);
 int dp_max_ring(const DpGeom &g);  // deepest LDS ring the slot allocators support
 size_t dp_default_lds_budget(const DpGeom &g);  // LDS per workgroup that keeps the register-limited occupancy
+// (kind_out, if not null: the kernel it launched, SINA_DP_KERNEL_* -- dp_kernel_kind, dp_plan.h)
 int launch_mesh_dp(const DpGeom &g, bool weighted, bool forbid, const DpArgs &a, uint32_t nq,
-                   size_t lds_bytes, hipStream_t s);
+                   size_t lds_bytes, hipStream_t s, uint32_t *kind_out = nullptr);
 int launch_backtrack(const BtArgs &a, hipStream_t s);
 bool backtrack_by_lanes(const BtArgs &a);  // one lane per query (large launches of 16S-long queries), else one wave per query
 int launch_assemble(const BtArgs &a, hipStream_t s);  // (after launch_backtrack, same stream)

@@ -29,26 +29,11 @@ int plan_dp(sina_hip_ctx *c, uint32_t maxL, DpPlan *pl) {
 // SINA_HIP_TEST="rho=<x>" fixes the launches' guess of optimum / bound (tests: 2 = too bold for any query, every
 // query takes the second attempt; 0.01 = nearly no bound).  Read per launch.
 PrunePlan prune_plan(const sina_hip_align_params *p, float wmax, float wmin, uint32_t maxL, bool profile_batch) {
-    PrunePlan pp;
-    if (!std::isfinite(wmax) || !std::isfinite(wmin)) return pp;  // (a NaN weight: no bound holds)
     const char *off = getenv("SINA_HIP_DP_PRUNE");
-    if (off && off[0] == '0') return pp;
-    if (profile_batch || weighted_scheme(p) || p->insertion == SINA_INSERTION_FORBID) return pp;
-    // gaps must cost, node weights must not be negative (a match gains match_score * weight, nothing else gains)
-    if (!(p->gap_penalty >= 0.f) || !(p->gap_ext_penalty >= 0.f) || !(wmin >= 0.f) || !std::isfinite(wmax)) return pp;
-    const float kappa = std::max(0.f, std::max(p->match_score, p->mismatch_score));
-    if (!std::isfinite(kappa)) return pp;
-    pp.kappa64 = 64.0f * 1.0001f * kappa;
-    pp.amax = prune_gain_units(wmax, pp.kappa64);
-    // (the bounds are exact float32 integers in units of 1/64 only below 2^24)
-    if (pp.amax > 250u || (uint64_t)pp.amax * maxL >= (1u << 23)) return pp;
-    if (pp.kappa64 <= 0.f) pp.kappa64 = 1e-30f;  // (no step gains anything: every node's gain is the one unit of margin)
-    // (a launch whose queries fit ONE strip skips nothing -- column 0 keeps every row in play -- so nobody needs the
-    // bound: the DAG build leaves its step 9 out, 9 % of its time for V4 amplicons)
     DpGeom g;
-    if (pick_geom(maxL, &g) && g.T <= 64) return pp;
-    pp.on = 1;
-    return pp;
+    const bool single_strip = pick_geom(maxL, &g) && g.T <= 64;
+    return prune_plan_for(p->match_score, p->mismatch_score, p->gap_penalty, p->gap_ext_penalty, weighted_scheme(p),
+                          p->insertion == SINA_INSERTION_FORBID, profile_batch, wmax, wmin, maxL, off && off[0] == '0', single_strip);
 }
 
 int upload_weights(sina_hip_ctx *c, const sina_hip_align_params *p, uint32_t n_sets) {
@@ -191,8 +176,8 @@ int choose_bound(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const s
         if (upload(c, 7, c->scout_u.p, vals.data(), 4 * (size_t)l.bq, s)) return 1;
         a->scout_u = c->scout_u.as<float>();
         c->last_scout = true;
-    } else if (l.chain_ncap != 0 && !weighted && !forbid && pp.on && !rho_fixed && a->below_init && a->gp >= a->gpe && pl.geom.T > 64 &&
-               test_knob("scout") != "0" && atoi(test_knob("generic").c_str()) == 0) {
+    } else if (scout_allowed(l.chain_ncap != 0, weighted, forbid, pp.on != 0, rho_fixed, a->below_init != 0, a->gp, a->gpe, pl.geom.T,
+                             test_knob("scout") == "0", atoi(test_knob("generic").c_str()) != 0)) {
         if (c->scout_u.reserve(4 * (size_t)l.bq)) return 1;
         a->scout_u = c->scout_u.as<float>();
         a->chain_rows = c->scout.as<uint16_t>();
@@ -238,7 +223,7 @@ int launch_dp_and_walk(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_p
         heavy_launch hl(c, s, kHeavyDp);
         SH_CHECK(hipEventRecord(c->ev[0], hl.stream()));
         a.dry = hl.dry();
-        if (launch_mesh_dp(pl.geom, weighted, forbid, a, b.nq, pl.lds, hl.stream())) return 1;
+        if (launch_mesh_dp(pl.geom, weighted, forbid, a, b.nq, pl.lds, hl.stream(), &c->last_kernel)) return 1;
         SH_CHECK(hipEventRecord(c->ev[1], hl.stream()));
         if (hl.lk.owns_lock() && c->st->dp_end[0]) {  // (under the queue's lock: launch order = dp_seq order)
             *dp_no = c->st->dp_seq++;

@@ -12,6 +12,69 @@
 
 namespace sina_hip {
 
+// ---- the gates: which DP kernel a launch runs, whether it may skip rows, whether its waves scout
+// (tests/gate_check.cpp states each rule a second time, from the outside, and compares)
+// The kernel of a launch (mesh_dp.hip, launch_tb; reported as sina_hip_dp_info::kernel -- the numbers are
+// SINA_DP_KERNEL_* of sina_hip.h).  The specialised kernel takes the simple scheme with gap_open >= gap_extend in a
+// launch below the initial value (every BASELINE configuration), with the certified row skip where the launch has a
+// bound and two strips or more -- in a single strip column 0, where an alignment may start at any row for free,
+// keeps every row in play.  Everything else is an instance of the generic kernel.
+enum DpKernelKind : uint32_t {
+    kDpKernelNone = SINA_DP_KERNEL_NONE,
+    kDpKernelSimple = SINA_DP_KERNEL_SIMPLE,
+    kDpKernelSimpleSkip = SINA_DP_KERNEL_SIMPLE_SKIP,
+    kDpKernelGenericBelow = SINA_DP_KERNEL_GENERIC_BELOW,  // mesh_dp_kernel<B, false, false, true>
+    kDpKernelGeneric = SINA_DP_KERNEL_GENERIC,             // <B, false, false, false>
+    kDpKernelWeighted = SINA_DP_KERNEL_WEIGHTED,           // <B, true, false, false>
+    kDpKernelForbid = SINA_DP_KERNEL_FORBID,               // <B, false, true, false>
+    kDpKernelWeightedForbid = SINA_DP_KERNEL_WEIGHTED_FORBID,
+};
+inline DpKernelKind dp_kernel_kind(bool weighted, bool forbid, bool below_init, float gp, float gpe, bool generic_only,
+                                   bool profile_batch, bool prune_on, uint32_t n_strips) {
+    if (!weighted && !forbid && below_init && gp >= gpe && !generic_only && !profile_batch)
+        return (prune_on && n_strips >= 2) ? kDpKernelSimpleSkip : kDpKernelSimple;
+    if (!weighted && !forbid) return below_init ? kDpKernelGenericBelow : kDpKernelGeneric;
+    if (weighted) return forbid ? kDpKernelWeightedForbid : kDpKernelWeighted;
+    return kDpKernelForbid;
+}
+
+// The arithmetic of prune_plan (dp_launch.hip, which reads the environment and the geometry): what a launch may prune
+// with.  env_off: SINA_HIP_DP_PRUNE=0; single_strip: the launch's geometry has one strip.
+inline PrunePlan prune_plan_for(float match, float mismatch, float gp, float gpe, bool weighted, bool forbid,
+                                bool profile_batch, float wmax, float wmin, uint32_t maxL, bool env_off, bool single_strip) {
+    PrunePlan pp;
+    if (!std::isfinite(wmax) || !std::isfinite(wmin)) return pp;  // (a NaN weight: no bound holds)
+    if (env_off) return pp;
+    if (profile_batch || weighted || forbid) return pp;
+    // gaps must cost, node weights must not be negative (a match gains match_score * weight, nothing else gains)
+    if (!(gp >= 0.f) || !(gpe >= 0.f) || !(wmin >= 0.f)) return pp;
+    const float kappa = std::max(0.f, std::max(match, mismatch));
+    if (!std::isfinite(kappa)) return pp;
+    pp.kappa64 = 64.0f * 1.0001f * kappa;
+    pp.amax = prune_gain_units(wmax, pp.kappa64);
+    // (the bounds are exact float32 integers in units of 1/64 only below 2^24)
+    if (pp.amax > kPruneMaxStep || (uint64_t)pp.amax * maxL >= (1u << 23)) return pp;
+    // No step gains anything (kappa == 0): amax is the one unit of margin.  The builders, which see kappa64 = 1e-30, give
+    // every node TWO units (a product above 0 rounds up to 1, plus the margin).  Both stand: the bound is the smaller of
+    // two terms, a * r and the column term, each a bound on its own as long as its step is at least the true gain of
+    // a match (0 here) plus the unit of margin -- a and the node gains need not be equal (gate_check.cpp asserts this).
+    if (pp.kappa64 <= 0.f) pp.kappa64 = 1e-30f;
+    // (a launch whose queries fit ONE strip skips nothing -- column 0 keeps every row in play -- so nobody needs the
+    // bound: the DAG build leaves its step 9 out, 9 % of its time for V4 amplicons)
+    if (single_strip) return pp;
+    pp.on = 1;
+    return pp;
+}
+
+// Whether a launch's waves run the scout pass (mesh_dp.hip, chain_scout_wave) -- apart from the test hook that sets
+// every scout value: a chain to scout along (device-built DAGs), the kernel that has the pass (the specialised one, with
+// the skip on and two strips or more), and no fixed guess.  T: the geometry's virtual thread count (64 per strip).
+inline bool scout_allowed(bool has_chain, bool weighted, bool forbid, bool prune_on, bool rho_fixed, bool below_init, float gp,
+                          float gpe, int T, bool scout_knob_off, bool generic_only) {
+    return has_chain && !weighted && !forbid && prune_on && !rho_fixed && below_init && gp >= gpe && T > 64 && !scout_knob_off &&
+           !generic_only;
+}
+
 // ---- launch ranges
 // End of a DP launch range that the trace-back budget cut short (q1 < limit): whole rounds of wave
 // slots if it holds at least one.

@@ -50,6 +50,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dp_plan.h"
 
 namespace sina_hip {
 
@@ -1017,8 +1018,10 @@ mesh_dp_kernel(const QDesc *__restrict__ qdv, const uint32_t *__restrict__ order
 // a 4096-query launch); B = 12 (418); the relaxation's adds two at a time as v_pk_add_f32 (2.6 % fewer VALU
 // instructions, 592: a packed add issues slower than the two adds it replaces).
 // Everything else (weighted scheme, --insertion=forbid, gap_open < gap_extend, huge gap costs) runs
-// mesh_dp_kernel.  Results are bit-identical between the two: tests/test_gpu_parity.py runs every
-// simple-scheme plane test through both (SINA_HIP_TEST=generic=1 forces the generic kernel).
+// mesh_dp_kernel.  Results are bit-identical between the two (SINA_HIP_TEST=generic=1 forces the generic kernel): the
+// plane tests of the simple scheme run through both -- tests/test_gpu_parity.py (test_mesh_planes_bit_exact[simple],
+// test_mesh_planes_equal_reference_parts_hashes), tests/test_gpu_edges.py (test_scoring_parameter_sets_planes) and every
+// case of tests/test_gpu_gates.py, which also asserts which of the two ran (sina_hip_dp_info::kernel).
 // ---------------------------------------------------------------- the scout pass, inside the DP wave
 // A bound U on the optimum from a real path: the query against the CHAIN of its family's first member
 // -- the reference famfinder ranked first, its nearest relative.  Every member is a path through the family's DAG (its
@@ -2372,7 +2375,7 @@ __global__ void __launch_bounds__(64) assemble_kernel(BtArgs a) {
 }
 
 template <int B>
-int launch_tb(bool weighted, bool forbid, const DpArgs &a, uint32_t nq, uint32_t n_strips, size_t lds, hipStream_t s) {
+int launch_tb(bool weighted, bool forbid, const DpArgs &a, uint32_t nq, uint32_t n_strips, size_t lds, hipStream_t s, uint32_t *kind_out) {
 #define SH_LAUNCH(WG, FB, BL)                                                                              \
     do {                                                                                                \
         auto kfn = a.dbg_value ? mesh_dp_kernel<B, WG, FB, BL, true> : mesh_dp_kernel<B, WG, FB, BL, false>;     \
@@ -2381,13 +2384,13 @@ int launch_tb(bool weighted, bool forbid, const DpArgs &a, uint32_t nq, uint32_t
                            a.qmask, a.weights, a.n_weights, a.wset, a.tb, a.dbg_value, a.spill, a.edge, a.edge_stride, \
                            n_strips, a.res, a.ms, a.mms, a.gp, a.gpe, a.prof16, a.dry);                  \
     } while (0)
-    // the simple scheme with gap_open >= gap_extend in a launch below the initial value (every BASELINE
-    // configuration): the specialised kernel; SINA_HIP_TEST=generic=1 keeps the generic one (parity tests)
+    // which kernel: dp_kernel_kind (dp_plan.h); SINA_HIP_TEST=generic=1 keeps the generic one (parity tests)
     const bool generic_only = atoi(test_knob("generic").c_str()) != 0;
-    if (!weighted && !forbid && a.below_init && a.gp >= a.gpe && !generic_only && a.prof16 == nullptr) {
-        // (certified row skip: launches of two strips or more -- in a single strip column 0, where an alignment may
-        // start at any row for free, keeps every row in play)
-        const bool prune = a.prune && a.reach != nullptr && n_strips >= 2;
+    const DpKernelKind kind = dp_kernel_kind(weighted, forbid, a.below_init != 0, a.gp, a.gpe, generic_only, a.prof16 != nullptr,
+                                             a.prune && a.reach != nullptr, n_strips);
+    if (kind_out) *kind_out = kind;
+    if (kind == kDpKernelSimple || kind == kDpKernelSimpleSkip) {
+        const bool prune = kind == kDpKernelSimpleSkip;
         auto kfn = prune ? (a.dbg_value ? mesh_dp_simple_kernel<B, true, true> : mesh_dp_simple_kernel<B, false, true>)
                          : (a.dbg_value ? mesh_dp_simple_kernel<B, true, false> : mesh_dp_simple_kernel<B, false, false>);
         if (allow_full_lds(reinterpret_cast<const void *>(kfn))) return 1;
@@ -2395,10 +2398,10 @@ int launch_tb(bool weighted, bool forbid, const DpArgs &a, uint32_t nq, uint32_t
                            a.edge, a.edge_stride, n_strips, a.res, a.ms, a.mms, a.gp, a.gpe, a.dry, a.reach, a.prune_rho,
                            a.prune_amax, (uint32_t)(lds / dp_slot_bytes(DpGeom{64 * (int)n_strips, B})), prune ? a.scout_u : nullptr, a.scout_bias,
                            prune ? a.chain_rows : nullptr, a.chain_sizes, a.chain_ncap);
-    } else if (!weighted && !forbid && a.below_init) SH_LAUNCH(false, false, true);
-    else if (!weighted && !forbid) SH_LAUNCH(false, false, false);
-    else if (weighted && !forbid) SH_LAUNCH(true, false, false);
-    else if (!weighted && forbid) SH_LAUNCH(false, true, false);
+    } else if (kind == kDpKernelGenericBelow) SH_LAUNCH(false, false, true);
+    else if (kind == kDpKernelGeneric) SH_LAUNCH(false, false, false);
+    else if (kind == kDpKernelWeighted) SH_LAUNCH(true, false, false);
+    else if (kind == kDpKernelForbid) SH_LAUNCH(false, true, false);
     else SH_LAUNCH(true, true, false);
 #undef SH_LAUNCH
     SH_CHECK(hipGetLastError());
@@ -2483,11 +2486,11 @@ int dp_max_ring(const DpGeom &) { return 8; }  // the slot allocators keep 8 slo
 size_t dp_default_lds_budget(const DpGeom &g) { return (size_t)160 * 1024 / (4 * dp_waves_per_simd(g.B)) - 64; }
 
 int launch_mesh_dp(const DpGeom &g, bool weighted, bool forbid, const DpArgs &a, uint32_t nq,
-                   size_t lds, hipStream_t s) {
+                   size_t lds, hipStream_t s, uint32_t *kind_out) {
     const uint32_t n_strips = (uint32_t)g.T / 64;
-    if (g.B == 4) return launch_tb<4>(weighted, forbid, a, nq, n_strips, lds, s);
-    if (g.B == 8) return launch_tb<8>(weighted, forbid, a, nq, n_strips, lds, s);
-    if (g.B == 12) return launch_tb<12>(weighted, forbid, a, nq, n_strips, lds, s);
+    if (g.B == 4) return launch_tb<4>(weighted, forbid, a, nq, n_strips, lds, s, kind_out);
+    if (g.B == 8) return launch_tb<8>(weighted, forbid, a, nq, n_strips, lds, s, kind_out);
+    if (g.B == 12) return launch_tb<12>(weighted, forbid, a, nq, n_strips, lds, s, kind_out);
     SH_FAIL("mesh_dp: unsupported geometry");
 }
 

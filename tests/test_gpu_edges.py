@@ -210,11 +210,12 @@ def test_full_length_properties(oracle, gpu_ctx):
     (2.0, -1.0, 1.0, 3.0),          # extend > open: the general chain path
     (2.0, -1.0, 2000.0, 700.0),     # gap costs so large that values reach the 1e6 initial value of a cell
 ])
-def test_scoring_parameter_sets_planes(oracle, gpu_ctx, scores):
+def test_scoring_parameter_sets_planes(oracle, gpu_ctx, monkeypatch, scores):
     """All three planes bit-equal for scoring parameters that are not small integers (the insertion
     chain guesses run structure with single adds and must still end at the reference's repeated
     float adds), for a query with long insertions against its family, in a one-wave and a two-wave
-    geometry."""
+    geometry -- through the kernel the launch chooses and, a second time, through the generic kernel
+    (SINA_HIP_TEST=generic=1)."""
     ms, mms, gp, gpe = scores
     for length, width, seed in ((500, 4000, 331), (1450, 50000, 332)):
         refs = synth.make_refs(120, length=length, width=width, seed=seed)
@@ -230,6 +231,13 @@ def test_scoring_parameter_sets_planes(oracle, gpu_ctx, scores):
         q, qm = _cseq("ins%d" % length, qmask)
         _planes_equal(oracle, gpu_ctx, fam, q, qm, refs.width, match_score=ms, mismatch_score=mms,
                       gap_penalty=gp, gap_ext_penalty=gpe)
+        chosen = capi.DP_KERNELS[gpu_ctx.dp_info(0)["kernel"]]
+        assert chosen == ("simple" if gp >= gpe and gp < 1000 else "generic_below" if gp < 1000 else "generic")
+        util.set_knobs(monkeypatch, generic=1)
+        _planes_equal(oracle, gpu_ctx, fam, q, qm, refs.width, match_score=ms, mismatch_score=mms,
+                      gap_penalty=gp, gap_ext_penalty=gpe)
+        util.set_knobs(monkeypatch, generic=None)
+        assert capi.DP_KERNELS[gpu_ctx.dp_info(0)["kernel"]] == ("generic_below" if gp < 1000 else "generic")
 
 
 def test_malformed_graphs_are_rejected(oracle, gpu_ctx):

@@ -27,7 +27,9 @@ def small(oracle):
 
 
 @pytest.mark.parametrize("mode", ["simple", "weighted", "forbid", "weighted_forbid"])
-def test_mesh_planes_bit_exact(oracle, gpu_ctx, small, mode):
+def test_mesh_planes_bit_exact(oracle, gpu_ctx, small, monkeypatch, mode):
+    """... the simple scheme through both of its kernels: the specialised one, and under SINA_HIP_TEST=generic=1 the
+    generic kernel's simple-scheme instance; dp_info says which one ran."""
     refs, qs, cs, idx = small
     rng = np.random.default_rng(5)
     weights = rng.uniform(0.2, 1.5, size=refs.width).astype(np.float32) if "weighted" in mode else None
@@ -43,6 +45,15 @@ def test_mesh_planes_bit_exact(oracle, gpu_ctx, small, mode):
         assert (util.f32_bits(val) == util.f32_bits(cells["value"])).all()
         assert (vm == cells["value_midx"]).all()
         assert (vs == cells["value_sidx"]).all()
+        if mode == "simple":
+            assert capi.DP_KERNELS[gpu_ctx.dp_info(0)["kernel"]] == "simple"
+            util.set_knobs(monkeypatch, generic=1)
+            vm, vs, val = gpu_ctx.debug_mesh(gb, qm, gpu_ctx.params())
+            util.set_knobs(monkeypatch, generic=None)
+            assert capi.DP_KERNELS[gpu_ctx.dp_info(0)["kernel"]] == "generic_below"
+            assert (util.f32_bits(val) == util.f32_bits(cells["value"])).all()
+            assert (vm == cells["value_midx"]).all()
+            assert (vs == cells["value_sidx"]).all()
 
 
 @pytest.mark.parametrize("overhang,lowercase", [(0, 0), (1, 0), (2, 2), (0, 2)])
@@ -389,11 +400,12 @@ def test_queries_with_the_same_ordered_family_share_one_dag(oracle, gpu_ctx, sma
         assert s1["dags_used"] - s0["dags_used"] == 20 and s1["dags_built"] - s0["dags_built"] == 4
 
 
-def test_mesh_planes_equal_reference_parts_hashes(oracle, gpu_ctx):
+def test_mesh_planes_equal_reference_parts_hashes(oracle, gpu_ctx, monkeypatch):
     """The DP kernel against planes the REFERENCE's scoring schemes and dag<T> produced (oracle/_ref cell
     loop, tests/golden/make_ref_vectors.py): value / value_midx / value_sidx of 25 families -- 1..41
     members, fs-weight 0 / 1 / 2.5, simple and weighted scheme, --insertion=forbid, gap-open ==
-    gap-extend, one full-length 16S family -- compared by plane hash."""
+    gap-extend, one full-length 16S family -- compared by plane hash.  The simple-scheme cases run a second time
+    through the generic kernel (SINA_HIP_TEST=generic=1)."""
     import os
     ref = np.load(os.path.join(os.path.dirname(__file__), "golden", "ref_vectors.npz"))
     hashes = ref["mesh_case_hash"]
@@ -411,3 +423,12 @@ def test_mesh_planes_equal_reference_parts_hashes(oracle, gpu_ctx):
         assert util.plane_hash(val) == hashes[ci][col["value"]], (ci, case["scheme"])
         assert util.plane_hash(vm) == hashes[ci][col["value_midx"]], (ci, case["scheme"])
         assert util.plane_hash(vs) == hashes[ci][col["value_sidx"]], (ci, case["scheme"])
+        if not sch["weighted"] and not sch["forbid"]:
+            assert capi.DP_KERNELS[gpu_ctx.dp_info(0)["kernel"]] == "simple", (ci, case["scheme"])
+            util.set_knobs(monkeypatch, generic=1)
+            vm, vs, val = gpu_ctx.debug_mesh(gb, (qa >> 24).astype(np.uint8), p)
+            util.set_knobs(monkeypatch, generic=None)
+            assert capi.DP_KERNELS[gpu_ctx.dp_info(0)["kernel"]] == "generic_below", (ci, case["scheme"])
+            assert util.plane_hash(val) == hashes[ci][col["value"]], (ci, case["scheme"])
+            assert util.plane_hash(vm) == hashes[ci][col["value_midx"]], (ci, case["scheme"])
+            assert util.plane_hash(vs) == hashes[ci][col["value_sidx"]], (ci, case["scheme"])

@@ -9,34 +9,9 @@ import pytest
 
 from sina_amd import capi, pipeline, synth
 from tests import util
+from tests.prune_ref import _bound_plane, _check_planes  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-def _bound_plane(info, rg_cols, N, L):
-    """T(m, s) = U + min(a * r, R(m) - gmin * max(0, C(m) - r)), r = L-1-s, in units of 1/64, as float64 (common.h,
-    "the bound")."""
-    rg, cols = rg_cols
-    a, gmin = float(info["prune_step"]), float(info["prune_gmin"])
-    r = (L - 1 - np.arange(L, dtype=np.float64))[None, :]
-    second = rg.astype(np.float64)[:, None] - gmin * np.maximum(0.0, cols.astype(np.float64)[:, None] - r)
-    return info["ubound"] + np.minimum(a * r, second) / 64.0
-
-
-def _check_planes(ctx, cells, vm, vs, val):
-    N, L = val.shape
-    info = ctx.dp_info(0)
-    assert info["attempts"] >= 1, "the launch did not go through the skipping kernel"
-    if np.isinf(info["ubound"]):     # third attempt: swept in full
-        alive = np.ones((N, L), bool)
-    else:
-        T = _bound_plane(info, ctx.rgain(N), N, L)
-        alive = cells["value"].astype(np.float64) <= T
-        assert (val[~alive].astype(np.float64) > T[~alive]).all(), "a cell the reference has above its bound came out at or below it"
-    assert (util.f32_bits(val)[alive] == util.f32_bits(cells["value"])[alive]).all()
-    assert (vm[alive] == cells["value_midx"][alive]).all()
-    assert (vs[alive] == cells["value_sidx"][alive]).all()
-    return info, alive
 
 
 SIMPLE_CASES = [i for i, c in enumerate(util.MESH_CASES)
