@@ -312,6 +312,33 @@ int sina_hip_align_count_pairs(sina_hip_ctx *ctx, int on);
 const uint32_t *sina_hip_staged_pair_counts(sina_hip_ctx *ctx);
 int sina_hip_pair_inplace_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *sequences, uint64_t *launches);
 
+/* --calc-idty (align_ident_slv) where the device assembles the alignment.  Replaces, for the queries an align call
+ * assembles: the comparator of src/align.cpp:380-382 (cseq_comparator(CMP_IUPAC_OPTIMISTIC, CMP_DIST_NONE,
+ * CMP_COVER_OVERLAP, false)) and the loop of src/align.cpp:443-453 over the family's members that keeps the best
+ * score -- without the second trip of sina_hip_compare (finished words packed and uploaded again, six counters per
+ * (query, member) pair downloaded): the finished words, the store's references and the family lists are in device
+ * memory when the assembly ends, a kernel queued right behind it scores there, 8 bytes per query come back with the
+ * results.
+ *
+ * sina_hip_align_count_identity: the switch, per context, off after init and after fork.  With it on, every call of
+ * sina_hip_align_families, _families_wsets and _profiles on this context that runs with p->assemble counts: one launch
+ * per DP launch range.  The sina_hip_align_graphs* entries bring no family to the device and never count.
+ *
+ * sina_hip_staged_identity: [nq][2] of the context's last align call, laid out like that call's `out`.  Host memory
+ * owned by the context, valid until its next align call.  NULL if that call counted nothing: the switch was off,
+ * p->assemble was 0, it was a graphs entry, nq was 0, or it ended early.  Where out[q].assembled == 1, word 0 of row q
+ * is the bit pattern of the best float score, match / (match + mismatch + only_a + only_b) of sina_hip_compare's
+ * counters under SINA_CMP_IUPAC_OPTIMISTIC without the lower-case filter, over the members of query q's family (0 if
+ * no member has a score), and word 1 the number of members that have one (a denominator of 0, the host's NaN, has
+ * none); align_ident_slv is 100.f * the score.  Two zeros elsewhere (a query the host finishes, a failed one).
+ *
+ * sina_hip_identity_inplace_stats: this kernel's own time (events around its launches) and volume on this context
+ * since init / fork: assembled queries scored, their (query, member) pairs, launches. */
+int sina_hip_align_count_identity(sina_hip_ctx *ctx, int on);
+const uint32_t *sina_hip_staged_identity(sina_hip_ctx *ctx);
+int sina_hip_identity_inplace_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *sequences, uint64_t *pairs,
+                                    uint64_t *launches);
+
 /* ------------------------------------------------------------- alignment
  * Replaces, for a batch of queries: mseq::mseq + sort + reduce_edges
  * (src/mseq.cpp:47-118, src/graph.h:451-488) when given family ids, compute()

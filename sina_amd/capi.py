@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "sina_hip_upload_name_order", "sina_hip_compare_rank", "sina_hip_kmer_topk_rank", "sina_hip_rank_stats",
     "sina_hip_upload_pairs", "sina_hip_pair_counts", "sina_hip_pair_stats",
     "sina_hip_align_count_pairs", "sina_hip_staged_pair_counts", "sina_hip_pair_inplace_stats",
+    "sina_hip_align_count_identity", "sina_hip_staged_identity", "sina_hip_identity_inplace_stats",
 ]
 
 # include/sina_hip.h: SINA_CMP_COVER_*, in CMP_COVER_TYPE's order
@@ -166,6 +167,10 @@ def load():
     L.sina_hip_staged_pair_counts.restype = C.POINTER(C.c_uint32)
     L.sina_hip_staged_pair_counts.argtypes = [vp]
     L.sina_hip_pair_inplace_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p]
+    L.sina_hip_align_count_identity.argtypes = [vp, C.c_int]
+    L.sina_hip_staged_identity.restype = C.POINTER(C.c_uint32)
+    L.sina_hip_staged_identity.argtypes = [vp]
+    L.sina_hip_identity_inplace_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
     L.sina_hip_last_error_is_limit.restype = C.c_int
     L.sina_hip_debug_mesh_wide.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
                                            u32p, u32p, f32p]
@@ -557,6 +562,31 @@ class Context:
         seqs, launches = C.c_uint64(), C.c_uint64()
         self._check(self.L.sina_hip_pair_inplace_stats(self.h, C.byref(ms), C.byref(seqs), C.byref(launches)))
         return dict(kernel_ms=float(ms.value), sequences=int(seqs.value), launches=int(launches.value))
+
+    def count_identity(self, on=True):
+        """The switch of the in-place family identity (--calc-idty): with it on, align_families, align_families_wsets
+        and align_profiles with assemble=1 also score every query they assemble against its family's members
+        (staged_identity).  Off after init and fork."""
+        self._check(self.L.sina_hip_align_count_identity(self.h, 1 if on else 0))
+
+    def staged_identity(self):
+        """uint32 [nq, 2] of this context's last align call (a copy), rows laid out like its `out`: the float bits of the
+        best overlap score of the query with a member of its family and the number of members that have a score where
+        out[q].assembled == 1, two zeros elsewhere.  None if that call counted nothing (switch off, assemble=0, an
+        align_graphs call, no query)."""
+        p = self.L.sina_hip_staged_identity(self.h)
+        if not p:
+            return None
+        nq = getattr(self, "_align_nq", 0)
+        return np.ctypeslib.as_array(p, shape=(max(nq, 1), 2))[:nq].copy()
+
+    def identity_inplace_stats(self):
+        """The in-place family-identity kernel on this context so far: dict(kernel_ms, sequences, pairs, launches);
+        sequences counts assembled queries only, pairs their (query, member) pairs."""
+        ms = C.c_double()
+        seqs, prs, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.sina_hip_identity_inplace_stats(self.h, C.byref(ms), C.byref(seqs), C.byref(prs), C.byref(launches)))
+        return dict(kernel_ms=float(ms.value), sequences=int(seqs.value), pairs=int(prs.value), launches=int(launches.value))
 
     def align_families(self, fam_ids, fam_off, qmask, qoff, params=None):
         params = params or self.params()

@@ -33,6 +33,7 @@ void set_limit_error(const std::string &msg);
 //                                        match_floor=N  match_loads=1 (the match-count kernel's chunk floor / one load in flight: tools/perf_msc.py)
 //                                        pair_words=N (words per launch range of the pair-count kernel, pairs.hip)
 //                                        dp_range_q=N (at most N queries per DP launch range: a small call takes several)
+//                                        fam_chunk_q=N (at most N queries per DAG / profile build chunk of the family entries)
 // value of `key` in SINA_HIP_TEST ("" if absent); read every time: tests change it between calls
 inline std::string test_knob(const char *key) {
     const char *e = getenv("SINA_HIP_TEST");
@@ -447,7 +448,17 @@ struct DpLaunch {
     // scout); 0: the DAGs are the caller's or profiles -- no chain, no scout pass
     uint32_t chain_ncap = 0;
     const uint32_t *wset = nullptr;  // the weight vector of each of the bq queries (the _wsets entries), or nullptr: one vector for all
+    // the family entries: node entries per DAG of the chunk's build (DAGs and profiles alike; the in-place family
+    // identity finds a query's list with it, identity.hip) and the bq + 1 offsets of the queries' families in the
+    // caller's list (their sizes: the identity's volume counter); 0 / nullptr: the DAGs are the caller's
+    uint32_t fam_ncap = 0;
+    const uint64_t *fam_off = nullptr;
 };
+// (after launch_assemble, same stream; identity.hip) the best overlap identity of each of the launch's assembled
+// queries with a member of its family, from the words assemble_kernel left, the store's references and the family
+// lists the chunk's build left in the context: rows [a.nq][2].  ncap: node entries per DAG of that build; max_l: the
+// launch's longest query
+int launch_family_identity(sina_hip_ctx *c, const BtArgs &a, uint32_t ncap, uint32_t max_l, uint32_t *rows, hipStream_t s);
 // Runs DP + backtrack for the launch and copies the results back.
 int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const sina_hip_align_params *p, const DpLaunch &l);
 // What a launch may skip rows with: the scoring of `p` (non-negative gap costs, the simple scheme), the

@@ -1,6 +1,7 @@
-// Device code the search-stage comparison kernels share (search.hip: compare_kernel writes every pair's counters;
-// rank.hip: rank_kernel turns them into a score and keeps the best): the query's LDS tables and the classification of
-// one candidate's bases against them.  See search.hip for what the counters mean and why column membership decides them.
+// Device code the comparison kernels share (search.hip: compare_kernel writes every pair's counters; rank.hip:
+// rank_kernel turns them into a score and keeps the best; identity.hip: family_identity_kernel keeps the best overlap
+// score of an assembled query's family): the query's LDS tables, the classification of one candidate's bases against
+// them and the cover rule's denominator.  See search.hip for what the counters mean and why column membership decides them.
 #pragma once
 
 #include "common.h"
@@ -10,7 +11,7 @@ namespace sina_hip {
 constexpr int kCT = 256;  // threads per workgroup of both kernels
 
 // LDS a workgroup's tables take for an alignment of `width` columns and a query of `max_la` bases
-inline size_t compare_table_bytes(uint32_t width, uint32_t max_la) {
+constexpr size_t compare_table_bytes(uint32_t width, uint32_t max_la) {
     const size_t nwords = ((size_t)width + 31) / 32;
     return 4 * nwords + 2 * (nwords + 2) + ((size_t)max_la + 15) + 16;
 }
@@ -156,6 +157,24 @@ __device__ __forceinline__ sina_hip_match_counts classify_candidate(const QueryT
         m.only_a_overhang = (int32_t)t.nA - in_a;
     }
     return m;
+}
+
+// The denominator cseq_comparator::score divides the matches by, in int32 as there (SINA_CMP_COVER_* in
+// CMP_COVER_TYPE's order); 0: the host's 0 / 0.
+__device__ __forceinline__ int32_t cover_denominator(const sina_hip_match_counts &m, int cover) {
+    const int32_t paired = m.match + m.mismatch;
+    const int32_t a_alone = m.only_a + m.only_a_overhang, b_alone = m.only_b + m.only_b_overhang;
+    switch (cover) {
+    case SINA_CMP_COVER_ABS: return 1;
+    case SINA_CMP_COVER_QUERY: return paired + a_alone;
+    case SINA_CMP_COVER_TARGET: return paired + b_alone;
+    case SINA_CMP_COVER_OVERLAP: return paired + m.only_a + m.only_b;
+    case SINA_CMP_COVER_ALL: return paired + m.only_a + m.only_b + m.only_a_overhang + m.only_b_overhang;
+    case SINA_CMP_COVER_AVERAGE: return paired + (m.only_a + m.only_b + m.only_a_overhang + m.only_b_overhang) / 2;
+    case SINA_CMP_COVER_MIN: return paired + min(a_alone, b_alone);
+    case SINA_CMP_COVER_MAX: return paired + max(a_alone, b_alone);
+    default: return paired;  // SINA_CMP_COVER_NOGAP
+    }
 }
 
 }  // namespace sina_hip

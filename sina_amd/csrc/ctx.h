@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "dp_plan.h"
+#include "identity_plan.h"
 
 // Reference store + k-mer index (HBM-resident) and the cumulative counters.  Owned by the context
 // sina_hip_init() made; contexts made by sina_hip_fork() point at their parent's.
@@ -36,6 +37,7 @@ struct sina_hip_store {
     sina_hip::DevBuf pair_ent;
     uint32_t n_pair_ent = 0;
     std::atomic<size_t> pc_rows_hint{0};  // bytes of pinned counter rows the largest counted align call took (sina_hip_ctx::h_pc)
+    std::atomic<size_t> id_rows_hint{0};  // ... and of pinned identity rows (sina_hip_ctx::h_id)
     std::mutex aux_mu;
     std::mutex stats_mu;
     // The device-filling kernels of all contexts (k-mer count/select, DAG build, DP) go through ONE
@@ -113,7 +115,9 @@ struct sina_hip_ctx {
     hipStream_t stream = nullptr;     // uploads, k-mer searches' copies ... (see make_streams)
     hipStream_t stream_dp = nullptr;  // DP hand-over, result copies
     std::mutex mu;
-    hipEvent_t ev[13];  // [10], [11]: hand-over to / from the store's heavy stream; [12]: end of the in-place pair count
+    // [10], [11]: hand-over to / from the store's heavy stream; [12]: end of the in-place pair count; [13]: end of the
+    // in-place family identity
+    hipEvent_t ev[14];
 
     sina_hip_store *st = nullptr;
     bool owns_store = false;
@@ -165,6 +169,16 @@ struct sina_hip_ctx {
     sina_hip::HostBuf h_pc;
     double pc_ms = 0;
     uint64_t pc_seqs = 0, pc_launches = 0;
+    // the family identity of an align call (identity.hip, family_identity_kernel; sina_hip_align_count_identity), laid
+    // out like the pair count's: the switch; whether the call in progress -- afterwards: the last one -- counts
+    // (identity_inplace_begin); a launch range's rows on the device; the whole call's [nq][2] rows in pinned memory (a
+    // range writes at DpLaunch::q_base; sina_hip_staged_identity); its own time and volume on this context
+    // (sina_hip_identity_inplace_stats)
+    bool count_identity = false, id_active = false;
+    sina_hip::DevBuf id_out;
+    sina_hip::HostBuf h_id;
+    double id_ms = 0;
+    uint64_t id_seqs = 0, id_pairs = 0, id_launches = 0;
     sina_hip::HostBuf h_out, h_out_pos;  // pinned staging for the DP results
     // h_out_pos holds the aligned columns of a whole align call (laid out like the caller's out_pos): a launch
     // range writes at DpLaunch::out_pos_base, callers that pass no out_pos read them here (sina_hip_staged_out_pos)
@@ -174,7 +188,7 @@ struct sina_hip_ctx {
 
     size_t lds_budget = 0;  // LDS per DP workgroup; 0 = what keeps the register-limited occupancy (dp_default_lds_budget)
 
-    static constexpr int kNumScratch = 49;
+    static constexpr int kNumScratch = 50;
     static_assert(kNumScratch <= 64, "sina_hip_store::cap_hint is too short");
     void scratch(sina_hip::DevBuf **all) {
         sina_hip::DevBuf *list[kNumScratch] = {&qd, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &res,
@@ -183,7 +197,7 @@ struct sina_hip_ctx {
                                                &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &order,
                                                &s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &edge, &prof16, &self16, &rgain,
                                                &scout, &scout_u, &wset, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag,
-                                               &r_cnt, &pc_out};
+                                               &r_cnt, &pc_out, &id_out};
         for (int i = 0; i < kNumScratch; i++) all[i] = list[i];
     }
     void publish_hints() {  // after a call: remember how big my buffers had to be
@@ -212,7 +226,7 @@ struct sina_hip_ctx {
                                       &s_qab, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};  // (s_qab, r_*: sina_hip_kmer_topk_rank)
         sina_hip::DevBuf *align[] = {&qd, &order, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &edge, &res, &weights, &out,
                                      &out_pos, &g_fam_ids, &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &rgain, &scout, &scout_u,
-                                     &prof16, &self16, &wset, &pc_out};
+                                     &prof16, &self16, &wset, &pc_out, &id_out};
         sina_hip::DevBuf *compare[] = {&s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};
         sina_hip::DevBuf **list = kind == 0 ? search : (kind == 1 ? align : compare);
         const size_t n = kind == 0 ? sizeof search / sizeof *search : (kind == 1 ? sizeof align / sizeof *align : sizeof compare / sizeof *compare);
@@ -223,6 +237,7 @@ struct sina_hip_ctx {
         // (the pinned rows of the in-place pair count: as many as any context of the store has needed -- none, and
         // nothing is reserved, on a store whose contexts have not counted)
         if (kind == 1 && h_pc.reserve(st->pc_rows_hint.load(std::memory_order_relaxed))) return 1;
+        if (kind == 1 && h_id.reserve(st->id_rows_hint.load(std::memory_order_relaxed))) return 1;  // (the identity rows, likewise)
         return 0;
     }
     void free_all() {
@@ -238,6 +253,7 @@ struct sina_hip_ctx {
         h_out.release();
         h_out_pos.release();
         h_pc.release();
+        h_id.release();
         h_res.release();
         for (auto &h : h_stage) h.release();
         if (owns_store && st) {
@@ -690,6 +706,24 @@ inline int pair_inplace_begin(sina_hip_ctx *c, const sina_hip_align_params *p, u
     }
     memset(c->h_pc.p, 0, bytes);
     c->pc_active = true;
+    return 0;
+}
+
+// ---- the family identity of an align call (sina_hip_align_count_identity).  The entries that bring families to the
+// device (align_family_batches) call this for their nq queries; the call counts by identity_plan.h's rule, and then
+// the pinned rows are there for the whole call and zero.  Every other align entry clears id_active: the rows of the
+// call before are forgotten (sina_hip_staged_identity: NULL).
+inline int identity_inplace_begin(sina_hip_ctx *c, const sina_hip_align_params *p, uint32_t nq) {
+    c->id_active = false;
+    if (!identity_call_counts(c->count_identity, p && p->assemble, true, nq)) return 0;
+    const size_t bytes = identity_row_bytes(nq);
+    SH_CHECK(hipSetDevice(c->device));
+    if (c->h_id.reserve(bytes)) return 1;
+    size_t seen = c->st->id_rows_hint.load(std::memory_order_relaxed);
+    while (bytes > seen && !c->st->id_rows_hint.compare_exchange_weak(seen, bytes, std::memory_order_relaxed)) {
+    }
+    memset(c->h_id.p, 0, bytes);
+    c->id_active = true;
     return 0;
 }
 }  // namespace sina_hip

@@ -70,7 +70,8 @@ int reserve_launch_buffers(sina_hip_ctx *c, const DpPlan &pl, const DpLaunch &l,
     if (c->spill.reserve(std::max<uint64_t>(sums.spill_rows, 1) * 8 * (uint64_t)pl.geom.Lp()) ||
         c->edge.reserve(std::max<uint64_t>(1, (uint64_t)(pl.geom.T / 64 - 1) * sums.edge_entries) * sizeof(EdgeRec)) ||
         c->res.reserve(sizeof(DpResult) * l.bq) || c->out.reserve(sizeof(sina_hip_align_out) * l.bq) ||
-        c->out_pos.reserve(4 * std::max<uint64_t>(l.nqm, 1)) || (c->pc_active && c->pc_out.reserve(24 * (size_t)l.bq)))
+        c->out_pos.reserve(4 * std::max<uint64_t>(l.nqm, 1)) || (c->pc_active && c->pc_out.reserve(24 * (size_t)l.bq)) ||
+        (c->id_active && c->id_out.reserve(identity_row_bytes(l.bq))))
         return 1;
     if (l.want_dbg_value && c->dbg.reserve(4 * sums.tb_cells)) return 1;
     return 0;
@@ -204,6 +205,23 @@ static int launch_pair_count(sina_hip_ctx *c, const BtArgs &b, hipStream_t s) {
     return 0;
 }
 
+// The family identity of a call that counts (ctx.h, identity_inplace_begin): behind the assembly -- and behind the
+// in-place pair count when that runs -- on their stream, over the words the assembly left.  No part in the FIFO's dry
+// signal either; ev[12] if the pair count ran, else ev[2], to ev[13] is its own time.
+// Ordering: the kernel reads g_fam_ids / g_fam_off as the chunk's build uploaded them, and the next chunk's build
+// uploads over them.  That upload is issued by this host thread, and only after run_dp_device has returned for the
+// chunk's last range: in the chained branch heavy_launch::done() has the host wait for an event recorded on the FIFO
+// stream BEHIND this kernel, in the other branch the kernel goes to stream_dp and fetch_results waits for that stream
+// -- either way the kernel has ended before the range's results are down, and the context's mutex keeps every other
+// call off these buffers meanwhile.  The uploads between the build and the chunk's last range (qd, qmask, wset,
+// order, scout values) go to other buffers.
+static int launch_identity(sina_hip_ctx *c, const BtArgs &b, const DpLaunch &l, hipStream_t s) {
+    if (!c->id_active) return 0;
+    if (launch_family_identity(c, b, l.fam_ncap, b.asm_cap, c->id_out.as<uint32_t>(), s)) return 1;
+    SH_CHECK(hipEventRecord(c->ev[13], s));
+    return 0;
+}
+
 // Queues the DP kernel, the walk and the assembly; *dp_no: this launch's number among the store's DP launches (~0: none).
 // With chained launches the walk and the assembly are queued right behind their DP kernel on the same FIFO stream: they
 // start the moment it ends, run beside the launch that started in its drain (the other FIFO stream), and the launch
@@ -211,7 +229,8 @@ static int launch_pair_count(sina_hip_ctx *c, const BtArgs &b, hipStream_t s) {
 // context's stream once it has seen the kernel end can be late: if its hardware queue shares a dispatch pipe with the
 // FIFO's it starts 5 ms late, beside the NEXT DP launch, takes 17 ms there instead of 3 and stretches that launch by 10
 // (profiles/r04_bt_delay.txt).  A launch that is not chained walks on stream_dp.
-int launch_dp_and_walk(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_params *p, DpArgs &a, const BtArgs &b, uint64_t *dp_no) {
+int launch_dp_and_walk(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_params *p, const DpLaunch &l, DpArgs &a, const BtArgs &b,
+                       uint64_t *dp_no) {
     const bool weighted = weighted_scheme(p), forbid = p->insertion == SINA_INSERTION_FORBID;
     bool bt_done = false;
     hipStream_t s = c->stream_dp;
@@ -235,6 +254,7 @@ int launch_dp_and_walk(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_p
             if (p->assemble && launch_assemble(b, hl.stream())) return 1;
             SH_CHECK(hipEventRecord(c->ev[2], hl.stream()));
             if (p->assemble && launch_pair_count(c, b, hl.stream())) return 1;
+            if (p->assemble && launch_identity(c, b, l, hl.stream())) return 1;
             bt_done = true;
         }
         if (hl.done()) return 1;
@@ -244,6 +264,7 @@ int launch_dp_and_walk(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_p
         if (p->assemble && launch_assemble(b, s)) return 1;
         SH_CHECK(hipEventRecord(c->ev[2], s));
         if (p->assemble && launch_pair_count(c, b, s)) return 1;
+        if (p->assemble && launch_identity(c, b, l, s)) return 1;
     }
     return 0;
 }
@@ -259,6 +280,8 @@ int fetch_results(sina_hip_ctx *c, const DpLaunch &l) {
     SH_CHECK(hipMemcpyAsync(staged_pos, c->out_pos.p, 4 * l.nqm, hipMemcpyDeviceToHost, s));
     if (c->pc_active)
         SH_CHECK(hipMemcpyAsync(c->h_pc.as<uint32_t>() + 6 * (size_t)l.q_base, c->pc_out.p, 24 * (size_t)l.bq, hipMemcpyDeviceToHost, s));
+    if (c->id_active)
+        SH_CHECK(hipMemcpyAsync(c->h_id.as<uint32_t>() + 2 * (size_t)l.q_base, c->id_out.p, identity_row_bytes(l.bq), hipMemcpyDeviceToHost, s));
     SH_CHECK(wait_stream(c, s));
     memcpy(l.out, c->h_out.p, sizeof(sina_hip_align_out) * l.bq);
     if (l.out_pos) memcpy(l.out_pos, staged_pos, 4 * l.nqm);
@@ -293,6 +316,16 @@ int account_launch(sina_hip_ctx *c, const DpPlan &pl, const DpLaunch &l, uint64_
         c->pc_ms += ms;
         c->pc_launches++;
         for (uint32_t q = 0; q < l.bq; q++) c->pc_seqs += (l.out[q].status == 0 && l.out[q].assembled != 0) ? 1u : 0u;
+    }
+    if (c->id_active) {  // (likewise)
+        SH_CHECK(hipEventElapsedTime(&ms, c->ev[c->pc_active ? 12 : 2], c->ev[13]));
+        c->id_ms += ms;
+        c->id_launches++;
+        for (uint32_t q = 0; q < l.bq; q++)
+            if (l.out[q].status == 0 && l.out[q].assembled != 0) {
+                c->id_seqs++;
+                c->id_pairs += l.fam_off ? l.fam_off[q + 1] - l.fam_off[q] : 0;
+            }
     }
     st.dp_cells += cells;
     st.dp_launches++;
@@ -330,7 +363,7 @@ int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const 
     if (l.debug_planes && !forbid)
         SH_CHECK(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(plane.ptr), (unsigned short)kTbNone, sums.tb_cells, c->stream));
     uint64_t dp_no = ~0ull;
-    if (launch_dp_and_walk(c, pl, p, a, b, &dp_no) || fetch_results(c, l)) return 1;
+    if (launch_dp_and_walk(c, pl, p, l, a, b, &dp_no) || fetch_results(c, l)) return 1;
     return account_launch(c, pl, l, sums.cells, dp_no);
 }
 
@@ -347,6 +380,7 @@ int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
     c->pc_active = false;  // (until pair_inplace_begin says otherwise: a call that ends early has counted nothing)
+    c->id_active = false;  // (identity_inplace_begin, likewise)
     if (!c->st->have_refs) SH_FAIL(w + ": upload references first");
     if (nq == 0) return 0;
     SH_CHECK(hipSetDevice(c->device));
@@ -366,9 +400,11 @@ int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {
     const int Lp = pl.geom.Lp();
     if (upload_weights(c, p, n_sets)) return 1;
     if (c->h_out_pos.reserve(4 * std::max<uint64_t>(qoff[nq] - qoff[0], 1))) return 1;
-    if (pair_inplace_begin(c, p, nq)) return 1;
-    // (SINA_HIP_TEST=dp_range_q=N: at most N queries per DP launch range, so that a small call takes several)
+    if (pair_inplace_begin(c, p, nq) || identity_inplace_begin(c, p, nq)) return 1;
+    // (SINA_HIP_TEST=dp_range_q=N: at most N queries per DP launch range, so that a small call takes several;
+    // fam_chunk_q=N: at most N queries per build chunk, so that it spans several builds)
     const uint32_t range_q = (uint32_t)strtoul(test_knob("dp_range_q").c_str(), nullptr, 10);
+    const uint32_t forced_chunk_q = (uint32_t)strtoul(test_knob("fam_chunk_q").c_str(), nullptr, 10);
 
     const uint64_t tb_budget_cells = tb_plane_budget(c) / tb_cell_bytes(p->insertion == SINA_INSERTION_FORBID);
     // queries per DAG build and DP launch: up to three rounds of DP wave slots (one DP wave per query) -- a DP
@@ -376,7 +412,7 @@ int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {
     // query than two (a fourth adds 2 % and another 22 GB per trace-back plane); the DP
     // launches below are whole rounds where the trace-back budget cuts a chunk
     const uint32_t slots = dp_wave_slots(c, pl.geom.B);
-    const uint32_t chunk_q = 3 * slots;
+    const uint32_t chunk_q = forced_chunk_q != 0 ? std::min(forced_chunk_q, 3 * slots) : 3 * slots;
     BuiltGraphs bg;
     std::vector<uint32_t> dag_of;      // per query of the chunk: which of the chunk's distinct DAGs is its family's
     std::vector<uint32_t> ufam_ids;    // the distinct families, concatenated
@@ -425,6 +461,8 @@ int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {
             l.profile_batch = f.profile_batch;  // (the DP reads the builder's prof16, the walk the entry point's self16)
             l.chain_ncap = f.profile_batch ? 0u : bg.ncap;
             l.wset = weight_set ? weight_set + q0 + r0 : nullptr;
+            l.fam_ncap = bg.ncap;
+            l.fam_off = fam_off + q0 + r0;
             if (run_dp_device(c, pl, pp, p, l)) return 1;
         }
     }

@@ -410,6 +410,18 @@ int sina_host_store_pair_inplace_stats(const char *key, uint64_t *trays, double 
         return fail(e);
     }
 }
+// the aligner's device-idty on this store: trays that took their identity from the row their align call brought back,
+// and the in-place kernel's time and volume (sina_hip_identity_inplace_stats) on its contexts -- between runs
+int sina_host_store_identity_inplace_stats(const char *key, uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs,
+                                           uint64_t *launches) {
+    try {
+        if (!trays || !kernel_ms || !sequences || !pairs || !launches) throw std::logic_error("store_identity_inplace_stats: null argument");
+        reference_store::get(key)->identity_inplace_stats(trays, kernel_ms, sequences, pairs, launches);
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
 // The host walk (cseq_base::calcPairScore), no device involved, of an aligned string.  counts6 (optional): num, AG,
 // AU, CG, GG, GU.
 int sina_host_pair_score(const char *aligned_text, const uint32_t *pairs, uint32_t n, float *score, uint32_t *counts6) {

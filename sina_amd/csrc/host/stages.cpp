@@ -710,6 +710,25 @@ void reference_store::pair_inplace_stats(uint64_t *trays, double *kernel_ms, uin
     for (auto &pool : idle_forks)
         for (sina_hip_ctx *c : pool) add(c);
 }
+void reference_store::identity_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches) {
+    sina_hip_ctx *root = device();
+    std::lock_guard<std::mutex> lk(gpu_mu);
+    *trays = n_idty_inplace.load(std::memory_order_relaxed);
+    *kernel_ms = 0;
+    *sequences = *pairs = *launches = 0;
+    auto add = [&](sina_hip_ctx *c) {
+        double ms = 0;
+        uint64_t n = 0, p = 0, l = 0;
+        hip_check(sina_hip_identity_inplace_stats(c, &ms, &n, &p, &l), "sina_hip_identity_inplace_stats");
+        *kernel_ms += ms;
+        *sequences += n;
+        *pairs += p;
+        *launches += l;
+    };
+    add(root);
+    for (auto &pool : idle_forks)
+        for (sina_hip_ctx *c : pool) add(c);
+}
 bool reference_store::match_counts_too_wide() {
     if (sina_hip::match_table_bytes(width) <= sina_hip::kMatchMaxLds) return false;
     if (!too_wide_said.exchange(true))
@@ -1810,6 +1829,9 @@ static aligner::options al_defaults() {  // src/align.cpp:231-274
     // the helix base-pair score from the align call itself (sina_hip_align_count_pairs) instead of a second trip with
     // the finished alignments (pair_score_batch): on request, until it has been decided on measurements
     o.device_bps = false;
+    // calc-idty from the align call itself (sina_hip_align_count_identity) instead of a second trip with the finished
+    // alignments (set_family_identity): on request, until it has been decided on measurements
+    o.device_idty = false;
     return o;
 }
 static aligner::options &al_opts() {
@@ -1852,6 +1874,7 @@ void aligner::set_option(const std::string &name, const std::string &value) {
     else if (name == "wide-fallback") o.wide_fallback = to_bool(value);
     else if (name == "weight-sets") o.weight_sets = to_bool(value);
     else if (name == "device-bps") o.device_bps = to_bool(value);
+    else if (name == "device-idty") o.device_idty = to_bool(value);
     else if (name == "db") o.database = value;
     else throw std::logic_error("aligner: unknown option " + name);
 }
@@ -2542,6 +2565,11 @@ void aligner::align_batch(std::vector<tray> &batch, bool batch_driver) {
         // wide path assembles nothing) or a single tray (its sink takes the host walk, as before).
         const bool count_pairs = o.device_bps && batch_driver && grp_route != route_long && store->pairs() != nullptr && p.assemble != 0;
         hip_check(sina_hip_align_count_pairs(dev.get(), count_pairs ? 1 : 0), "sina_hip_align_count_pairs");
+        // device-idty: the call scores the queries it assembles against their families.  Set either way, like the switch
+        // above; only a group whose families go to the device can count (the batch driver's and a single tray's alike),
+        // and without calc-idty nothing is launched.
+        const bool count_idty = o.calc_idty && o.device_idty && grp_route == route_device && p.assemble != 0;
+        hip_check(sina_hip_align_count_identity(dev.get(), count_idty ? 1 : 0), "sina_hip_align_count_identity");
         if (grp_route == route_long) {
             // One call per slot: a wide mesh of this size fills a launch of the wide kernel nearly alone anyway, and a
             // query whose mesh exceeds SINA_HIP_WIDE_CELLS -- the one thing a call refuses a well-formed query for --
@@ -2593,7 +2621,30 @@ void aligner::align_batch(std::vector<tray> &batch, bool batch_driver) {
             });
             if (staged_pairs) store->count_pairs_inplace(scored.load());
         }
-        if (o.calc_idty) set_family_identity(members, *store);  // (its own context, while this group's is still leased)
+        if (!o.calc_idty) continue;
+        // (null unless this call counted -- a group redone over host-built graphs after a limit refusal has not)
+        const uint32_t *const staged_idty = count_idty ? sina_hip_staged_identity(dev.get()) : nullptr;
+        if (staged_idty == nullptr) {
+            set_family_identity(members, *store);  // (its own context, while this group's is still leased)
+            continue;
+        }
+        // device-idty: a tray whose slot the device assembled takes 100 x its slot's score (the trays of a slot share
+        // the row); the trays the host finished go the old way
+        std::vector<dp_job *> rest;
+        uint64_t scored = 0;
+        for (size_t x = 0; x < members.size(); x++) {
+            const uint32_t u = slots.slot_of[x];
+            if (!out[u].assembled) {
+                rest.push_back(members[x]);
+                continue;
+            }
+            float score;
+            memcpy(&score, staged_idty + 2 * (size_t)u, 4);
+            members[x]->c->set_attr(fn::idty, 100.f * score);
+            scored++;
+        }
+        store->count_identity_inplace(scored);
+        if (!rest.empty()) set_family_identity(rest, *store);
     }
 }
 

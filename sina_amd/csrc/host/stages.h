@@ -346,6 +346,10 @@ public:
     // sina_hip_pair_inplace_stats
     void count_pairs_inplace(uint64_t trays) { n_bp_inplace.fetch_add(trays, std::memory_order_relaxed); }
     void pair_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *launches);
+    // the aligner's device-idty, likewise: trays that took their identity from the row their align call brought back,
+    // and the in-place kernel's time and volume on the store's contexts -- sina_hip_identity_inplace_stats
+    void count_identity_inplace(uint64_t trays) { n_idty_inplace.fetch_add(trays, std::memory_order_relaxed); }
+    void identity_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches);
 
 private:
     reference_store() = default;
@@ -371,7 +375,7 @@ private:
     std::atomic<bool> too_wide_said{false};
     std::atomic<int> name_order_state{0};  // 0: not looked at, 1: uploaded, 2: names repeat
     std::atomic<uint64_t> n_ranked{0}, n_rank_host{0};
-    std::atomic<uint64_t> n_bp_inplace{0};
+    std::atomic<uint64_t> n_bp_inplace{0}, n_idty_inplace{0};
     pair_map helix;
     std::mutex helix_mu;
 };
@@ -471,6 +475,8 @@ public:
                             // (sina_hip_align_families_wsets; default on) instead of one call per filter
         bool device_bps;    // a store with a helix map: the align call counts the base pairs of the queries it assembles and
                             // their trays leave the aligner scored (sina_hip_align_count_pairs; default off)
+        bool device_idty;   // calc-idty: the align call of a device-built group scores the queries it assembles against their
+                            // families and their trays take that identity (sina_hip_align_count_identity; default off)
         std::string database;  // reference store the DAGs are built from (same as famfinder "db")
     };
     static options *opts;

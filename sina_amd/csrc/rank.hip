@@ -134,21 +134,7 @@ __global__ void __launch_bounds__(kCT) rank_kernel(RankArgs a) {
         if (!valid) continue;
         pairs++;
         bases += lb;
-        // cseq_comparator::score, in int32 as there (SINA_CMP_COVER_* in CMP_COVER_TYPE's order)
-        const int32_t paired = m.match + m.mismatch;
-        const int32_t a_alone = m.only_a + m.only_a_overhang, b_alone = m.only_b + m.only_b_overhang;
-        int32_t denom;
-        switch (a.cover) {
-        case SINA_CMP_COVER_ABS: denom = 1; break;
-        case SINA_CMP_COVER_QUERY: denom = paired + a_alone; break;
-        case SINA_CMP_COVER_TARGET: denom = paired + b_alone; break;
-        case SINA_CMP_COVER_OVERLAP: denom = paired + m.only_a + m.only_b; break;
-        case SINA_CMP_COVER_ALL: denom = paired + m.only_a + m.only_b + m.only_a_overhang + m.only_b_overhang; break;
-        case SINA_CMP_COVER_AVERAGE: denom = paired + (m.only_a + m.only_b + m.only_a_overhang + m.only_b_overhang) / 2; break;
-        case SINA_CMP_COVER_MIN: denom = paired + min(a_alone, b_alone); break;
-        case SINA_CMP_COVER_MAX: denom = paired + max(a_alone, b_alone); break;
-        default: denom = paired; break;  // SINA_CMP_COVER_NOGAP
-        }
+        const int32_t denom = cover_denominator(m, a.cover);  // (cseq_comparator::score: compare_dev.h)
         if (denom == 0) {  // the host's 0 / 0
             flagged = true;
             continue;

@@ -98,7 +98,8 @@ def load_host():
     H.sina_host_store_set_pairs.argtypes = [C.c_char_p, capi.u32p, C.c_uint32]
     H.sina_host_store_pair_stats.argtypes = [C.c_char_p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_store_pair_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p]
-    H.sina_host_pair_score.argtypes = [C.c_char_p, capi.u32p, C.c_uint32, capi.f32p, capi.u32p]
+    H.sina_host_store_identity_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_pair_score.argtypes =[C.c_char_p, capi.u32p, C.c_uint32, capi.f32p, capi.u32p]
     H.sina_host_pair_scores_packed.argtypes = [capi.u32p, capi.u64p, C.c_uint32, capi.u32p, C.c_uint32, capi.f32p, capi.u32p,
                                                C.POINTER(C.c_double)]
     H.sina_host_pair_score_from_counts.restype = C.c_float
@@ -299,6 +300,17 @@ class Store:
         trays, seqs, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _chk(self.H.sina_host_store_pair_inplace_stats(self.key.encode(), C.byref(trays), C.byref(ms), C.byref(seqs), C.byref(launches)))
         return dict(trays=int(trays.value), sequences=int(seqs.value), launches=int(launches.value), kernel_ms=float(ms.value))
+
+    def identity_inplace_stats(self):
+        """The aligner's device-idty on this store so far: dict(trays, sequences, pairs, launches, kernel_ms) -- trays that
+        took their identity from the row their align call brought back, and the in-place kernel's assembled queries,
+        (query, member) pairs, launches and time on the store's contexts -- between runs, like pair_inplace_stats()."""
+        ms = C.c_double()
+        trays, seqs, prs, launches = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _chk(self.H.sina_host_store_identity_inplace_stats(self.key.encode(), C.byref(trays), C.byref(ms), C.byref(seqs), C.byref(prs),
+                                                           C.byref(launches)))
+        return dict(trays=int(trays.value), sequences=int(seqs.value), pairs=int(prs.value), launches=int(launches.value),
+                    kernel_ms=float(ms.value))
 
     def close(self):
         self.H.sina_host_store_close(self.key.encode())

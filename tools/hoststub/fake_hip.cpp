@@ -118,6 +118,14 @@ int sina_hip_pair_inplace_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, uint
     *seqs = *launches = 0;
     return 0;
 }
+// (likewise: the switch is taken, an align call of the stub scores no family)
+int sina_hip_align_count_identity(sina_hip_ctx *, int) { return 0; }
+const uint32_t *sina_hip_staged_identity(sina_hip_ctx *) { return nullptr; }
+int sina_hip_identity_inplace_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, uint64_t *pairs, uint64_t *launches) {
+    *ms = 0;
+    *seqs = *pairs = *launches = 0;
+    return 0;
+}
 void sina_hip_align_params_default(sina_hip_align_params *p) {
     memset(p, 0, sizeof(*p));
     p->match_score = 2;
