@@ -474,6 +474,9 @@ int sina_hip_wide_queries(sina_hip_ctx *ctx, uint64_t *n);
 /* Same, but the DAGs are built on the GPU from family member ids into the
  * uploaded reference store (order of ids = family order = mseq input order).
  *   fam_ids/fam_off : concatenated reference ids, offsets [nq+1]
+ * A column's nodes are keyed by the base's character, as mseq keys them (src/mseq.cpp:92-96): iupac masks 0 and 16
+ * are both '.' and share a node, which keeps the mask of the first member to show it.  A family whose members hold no
+ * base at all has no DAG: the call fails ("a family without a single base") before anything is launched.
  */
 int sina_hip_align_families(sina_hip_ctx *ctx, const uint32_t *fam_ids, const uint64_t *fam_off,
                             uint32_t nq, const uint8_t *qmask, const uint64_t *qoff,
@@ -572,6 +575,15 @@ int sina_hip_debug_family_graph(sina_hip_ctx *ctx, const uint32_t *fam_ids, uint
                                 uint8_t *mask, float *weight, uint32_t *pred_off, uint32_t *pred,
                                 uint32_t *succ_minpos, uint8_t *sink, uint32_t *spill_idx, uint32_t cap_nodes,
                                 uint32_t cap_edges);
+/* Test hook: the same build, read back as the words the DP kernel is handed, unchanged: per node the row record's z
+ * (predecessors | iupac mask << 8 | sink << 16 | fence << 17 | min(distance to the furthest predecessor, 63) << 18 |
+ * (index of the first spilled predecessor + 1) << 24) and w (where the finished row is kept), the predecessor entries
+ * node by node (id | (LDS slot or spill row & 0x7fff) << 16 | spilled << 31) and the build's 8 size words (nodes, raw
+ * edge entries, spill rows, status, first sink row, smallest column gain, bases of the first member; the eighth is not used). */
+int sina_hip_debug_family_graph_words(sina_hip_ctx *ctx, const uint32_t *fam_ids, uint32_t F, float fs_weight,
+                                      uint32_t ring_depth, uint32_t *n_nodes, uint32_t *n_edges, uint32_t *rec_z,
+                                      uint32_t *rec_w, uint32_t *pred_entries, uint32_t *size_words /* [8] */,
+                                      uint32_t cap_nodes, uint32_t cap_edges);
 
 /* Test hook: the profile the GPU builds for ONE family (ids into the uploaded store, in family order), for
  * comparison with pseq (src/pseq.cpp) and base_profile::comp (src/pseq.h:100-113): the nodes' columns, the

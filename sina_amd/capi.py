@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "sina_hip_store_alloc_like", "sina_hip_kmer_topk", "sina_hip_kmer_scores", "sina_hip_compare",
     "sina_hip_align_params_default", "sina_hip_staged_out_pos", "sina_hip_align_graphs", "sina_hip_align_families",
     "sina_hip_align_profiles", "sina_hip_debug_family_profile",
-    "sina_hip_debug_mesh", "sina_hip_debug_family_graph", "sina_hip_debug_dp_info", "sina_hip_debug_rgain", "sina_hip_debug_chain_rows", "sina_hip_get_stats",
+    "sina_hip_debug_mesh", "sina_hip_debug_family_graph", "sina_hip_debug_family_graph_words", "sina_hip_debug_dp_info", "sina_hip_debug_rgain", "sina_hip_debug_chain_rows", "sina_hip_get_stats",
     "sina_hip_align_graphs_any", "sina_hip_debug_mesh_wide", "sina_hip_wide_queries", "sina_hip_last_error_is_limit",
     "sina_hip_kmer_topk_any", "sina_hip_kmer_scores_any", "sina_hip_long_queries", "sina_hip_big_select_queries",
     "sina_hip_align_graphs_wsets", "sina_hip_align_families_wsets",
@@ -187,6 +187,8 @@ def load():
                                       u32p, u32p, f32p, C.c_int]
     L.sina_hip_debug_family_graph.argtypes = [vp, u32p, C.c_uint32, C.c_float, C.c_uint32, u32p, u32p, u32p, u8p,
                                               f32p, u32p, u32p, u32p, u8p, u32p, C.c_uint32, C.c_uint32]
+    L.sina_hip_debug_family_graph_words.argtypes = [vp, u32p, C.c_uint32, C.c_float, C.c_uint32, u32p, u32p, u32p, u32p,
+                                                    u32p, u32p, C.c_uint32, C.c_uint32]
     L.sina_hip_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sina_hip_debug_dp_info.argtypes = [vp, C.c_uint32, C.POINTER(DpInfo)]
     L.sina_hip_debug_rgain.argtypes = [vp, C.c_uint32, u32p, u32p]
@@ -708,6 +710,23 @@ class Context:
         n, e = nn.value, ne.value
         return dict(n=n, pos=pos[:n].copy(), mask=mask[:n].copy(), weight=w[:n].copy(), pred_off=poff[:n + 1].copy(),
                     pred=pred[:e].copy(), succ_minpos=smin[:n].copy(), sink=sink[:n].copy(), spill=spill[:n].copy())
+
+    def debug_family_graph_words(self, fam_ids, fs_weight=1.0, ring_depth=4):
+        """The same build as the words the DP kernel reads: dict(n, z, store (rec.w), pred (the entries, node by node),
+        n_spill, first_sink, chain_len, status)."""
+        fam_ids = _c(fam_ids, np.uint32)
+        cap_n, cap_e = 65536, 400000
+        nn, ne = C.c_uint32(), C.c_uint32()
+        z = np.zeros(cap_n, np.uint32)
+        w = np.zeros(cap_n, np.uint32)
+        pred = np.zeros(cap_e, np.uint32)
+        sz = np.zeros(8, np.uint32)
+        self._check(self.L.sina_hip_debug_family_graph_words(self.h, _ptr(fam_ids, u32p), len(fam_ids), fs_weight,
+                                                             ring_depth, C.byref(nn), C.byref(ne), _ptr(z, u32p),
+                                                             _ptr(w, u32p), _ptr(pred, u32p), _ptr(sz, u32p), cap_n, cap_e))
+        n, e = nn.value, ne.value
+        return dict(n=int(sz[0]), z=z[:n].copy(), store=w[:n].copy(), pred=pred[:e].copy(), n_spill=int(sz[2]),
+                    status=int(sz[3]), first_sink=int(sz[4]), gmin=int(sz[5]), chain_len=int(sz[6]))
 
     def dp_info(self, q=0):
         """What the DP kernel reported for query q of this context's last launch (row-skip test hook)."""

@@ -127,6 +127,11 @@ constexpr uint32_t kONfar = kONn + kTC;
 constexpr uint32_t kOMask = kONfar + kTNW;
 constexpr uint32_t kONcol = kOMask + kTNW;
 constexpr uint32_t kOE = (kONcol + kTNW + 15) & ~15u;
+// A column's nodes are keyed by the base's CHARACTER (mseq.cpp:92-96), and masks 0 and 16 are both '.': where a column
+// shows both, merge_dot16 gives the entries of mask 16 the key 0 and this bit, "mask 16"; the spare word behind nbaseT's
+// kTC + 1 says that some column of the family so far was merged (reference stores hold no such bases)
+constexpr int kELower0Bit = 14;
+constexpr uint32_t kODot16 = kTC + 1;
 
 // exclusive scan of in[0..n) into out[0..n) (may alias if same type); returns the total.
 template <typename In, typename Out>
@@ -269,6 +274,33 @@ __device__ __forceinline__ uint32_t node_of_entry(uint32_t ev) {  // tile-local 
     const uint32_t b = nbaseT[c];
     return b + liOf[b + __popc(presT[c] & ((1u << m) - 1u))];
 }
+// The entries of mask 16 in the tile's merged columns (bit 16 of presT cleared while bit 0 is set) take the key 0.
+__device__ __attribute__((noinline)) void merge_dot16(uint32_t n_tasks) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const uint32_t *presT = reinterpret_cast<const uint32_t *>(smem + kOPres);
+    uint16_t *eE = reinterpret_cast<uint16_t *>(smem + kOE);
+    for (uint32_t e = threadIdx.x; e < n_tasks * 64u; e += kGT) {  // (entry e: member e / kTC, slot e % kTC)
+        const uint32_t ev = eE[e];
+        const uint32_t c = ev & 0xFFu;
+        if (c != 0xFFu && ((ev >> 8) & 31u) == 16u && !(presT[c] & 0x10000u)) eE[e] = (uint16_t)((ev & ~(31u << 8)) | (1u << kELower0Bit));
+    }
+}
+// A '.' node keeps the mask of its first member: 16, not 0, where that member shows it.  For the window of columns [ca, cb)
+// whose first node is w0, after step 3 (wC: the first member of every node's character).  Outlined: reference stores hold no
+// such base, and inlined the pass cost the kernel's hot loops registers.
+__device__ __attribute__((noinline)) void fix_dot16(uint32_t n_tasks, uint32_t ca, uint32_t cb, uint32_t w0) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const uint32_t *nbaseT = reinterpret_cast<const uint32_t *>(smem + kONbase);
+    const uint32_t *wC = reinterpret_cast<const uint32_t *>(smem + kOWC);
+    const uint16_t *eE = reinterpret_cast<const uint16_t *>(smem + kOE);
+    uint8_t *maskN = smem + kOMask;
+    for (uint32_t e = threadIdx.x; e < n_tasks * 64u; e += kGT) {  // (entry e: member e / kTC, slot e % kTC)
+        const uint32_t ev = eE[e];
+        const uint32_t c = ev & 0xFFu;
+        // (an entry has no bit above kELower0Bit; '.' is the first of its column's characters)
+        if (c >= ca && c < cb && (ev >> kELower0Bit) && wC[nbaseT[c] - w0] == e / (uint32_t)kTC) maskN[node_of_entry(ev) - w0] = 16;
+    }
+}
 __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_GRAPH_MINWAVES, SINA_GRAPH_MINWAVES))) family_graph_kernel(GraphArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint32_t s_tmp[kGT / 64 + 8];
@@ -281,7 +313,7 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
     // when every table had a run-time base).
     uint32_t *cposT = reinterpret_cast<uint32_t *>(smem + kOCpos);          // [kTC] alignment column
     uint32_t *nbaseT = reinterpret_cast<uint32_t *>(smem + kONbase);        // [kTC + 2] first node of the column (tile-local); [tc] = nodes of the tile
-    uint32_t *presT = reinterpret_cast<uint32_t *>(smem + kOPres);          // [kTC] the column's characters, bit m: mask value m occurs
+    uint32_t *presT = reinterpret_cast<uint32_t *>(smem + kOPres);          // [kTC] the column's characters, bit m: mask value m occurs (where masks 0 and 16 meet, both '.', bit 0 stands for both)
     uint32_t *wA = reinterpret_cast<uint32_t *>(smem + kOWA);               // [kTNW] per node of the window: members | raw edges << 16
     uint32_t *wC = reinterpret_cast<uint32_t *>(smem + kOWC);               // [kTNW] first member of the node's character; then: smallest far predecessor not yet listed
     uint32_t *wD = reinterpret_cast<uint32_t *>(smem + kOWD);               // [kTNW] start of the CSR segment (raw entries before it in the window)
@@ -291,7 +323,7 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
     uint8_t *nfarN = smem + kONfar;                                         // [kTNW] far predecessors listed so far
     uint8_t *maskN = smem + kOMask;                                         // [kTNW]
     uint8_t *ncolN = smem + kONcol;                                         // [kTNW] tile column of the node
-    // entry (member j, slot): tile column | mask << 8 | "first base of the member" << 13, kEAbsent (column 255): not in the tile
+    // entry (member j, slot): tile column | mask << 8 | "first base of the member" << 13 (merged columns: kELower0Bit above), kEAbsent (column 255): not in the tile
     uint16_t *eE = reinterpret_cast<uint16_t *>(smem + kOE);                // [fam_cap][kTC]
     // ... then what is sized by the launch: the occupied-column bitmap and its ranks, the family members
     uint32_t *bitmap = reinterpret_cast<uint32_t *>(smem + a.bitmap_off);   // [nwords]
@@ -313,6 +345,7 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
         mb[j].carry = mb[j].carryn = kNoPrev;
     }
     for (uint32_t i = tid; i < nwords; i += kGT) bitmap[i] = 0;
+    if (tid == 0) nbaseT[kODot16] = 0;
     __syncthreads();
     GP_DECL
 
@@ -398,8 +431,20 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
         // contiguous stretch of at most kTC bases)
         fill_tile(a.ref_ab, a.bitmap_off, a.member_off, nwords, n_tasks, c0, tc);
         __syncthreads();
-        for (uint32_t c = tid; c < tc; c += kGT) nn[c] = (uint8_t)__popc(presT[c]);
+        for (uint32_t c = tid; c < tc; c += kGT) {
+            uint32_t p = presT[c];
+            if ((p & 0x10001u) == 0x10001u) {  // masks 0 and 16 in one column: one character, one node
+                p &= ~0x10000u;
+                presT[c] = p;
+                nbaseT[kODot16] = 1u;
+            }
+            nn[c] = (uint8_t)__popc(p);
+        }
         __syncthreads();
+        if (nbaseT[kODot16]) {  // (uniform, rare)
+            merge_dot16(n_tasks);
+            __syncthreads();
+        }
         GP(3)
         const uint32_t tn = block_exscan(nn, nbaseT, tc, s_tmp);
         if (tid == 0) nbaseT[tc] = tn;
@@ -457,6 +502,10 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
                 }
             }
             __syncthreads();
+            if (nbaseT[kODot16]) {  // (uniform, rare) some member shows mask 16
+                fix_dot16(n_tasks, ca, cb, w0);
+                __syncthreads();
+            }
             GP(4)
             // 4. members and raw edges per node; the predecessor of every entry.  An entry's node: the column's first
             // node + the place of its character (liOf is complete for this window and the ones before: the entry to
@@ -751,9 +800,25 @@ namespace {
 // Builds the DAGs of bq families (fam_off is absolute, first family = q0) into the context's
 // rec / node_pos / succ_minpos / pred buffers; grows the per-query caps and retries on overflow.
 int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t q0,
-                        uint32_t bq, float fs_weight, int W, BuiltGraphs *bg, bool want_smin, float kappa64) {
+                        uint32_t bq, float fs_weight, int W, BuiltGraphs *bg, bool want_smin, float kappa64, bool for_dp) {
     hipStream_t s = c->stream;
     if (ensure_ref_off_host(c)) return 1;  // (a store that arrived by broadcast reads it back once)
+    std::vector<uint64_t> foff(bq + 1), elems(bq, 0);
+    uint32_t max_f = 1;
+    bg->pred_off.assign(bq, 0);
+    for (uint32_t q = 0; q <= bq; q++) foff[q] = fam_off[q0 + q] - fam_off[q0];
+    for (uint32_t q = 0; q < bq; q++) {
+        max_f = std::max<uint32_t>(max_f, (uint32_t)(foff[q + 1] - foff[q]));
+        for (uint64_t x = fam_off[q0 + q]; x < fam_off[q0 + q + 1]; x++) {
+            const uint32_t id = fam_ids[x];
+            if (id >= c->st->n_refs) SH_FAIL("align_families: reference id out of range");
+            elems[q] += c->st->ref_off_host[id + 1] - c->st->ref_off_host[id];
+        }
+        // (no base, no node: the DP wave would start its end-cell search at a row that does not exist -- refused here,
+        // before anything is copied or launched, like an empty graph handed to sina_hip_align_graphs; the debug entries,
+        // which align nothing, show the DAG of no node)
+        if (for_dp && elems[q] == 0) SH_FAIL("align_families: a family without a single base");
+    }
     // weight table: the reference's expression (mseq.cpp:113) evaluated on the host
     if (!(c->wtab_fs_weight == fs_weight) || !c->g_wtab.p) {
         std::vector<float> wt((size_t)(kMaxFam + 1) * (kMaxFam + 1), 0.f);
@@ -766,18 +831,6 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
         SH_CHECK(hipMemcpyAsync(c->g_wtab.p, wt.data(), wt.size() * 4, hipMemcpyHostToDevice, s));
         SH_CHECK(hipStreamSynchronize(s));
         c->wtab_fs_weight = fs_weight;
-    }
-    std::vector<uint64_t> foff(bq + 1), elems(bq, 0);
-    uint32_t max_f = 1;
-    bg->pred_off.assign(bq, 0);
-    for (uint32_t q = 0; q <= bq; q++) foff[q] = fam_off[q0 + q] - fam_off[q0];
-    for (uint32_t q = 0; q < bq; q++) {
-        max_f = std::max<uint32_t>(max_f, (uint32_t)(foff[q + 1] - foff[q]));
-        for (uint64_t x = fam_off[q0 + q]; x < fam_off[q0 + q + 1]; x++) {
-            const uint32_t id = fam_ids[x];
-            if (id >= c->st->n_refs) SH_FAIL("align_families: reference id out of range");
-            elems[q] += c->st->ref_off_host[id + 1] - c->st->ref_off_host[id];
-        }
     }
     uint32_t ncap = std::min<uint32_t>(65535, 12288);
     for (int attempt = 0;; attempt++) {
@@ -872,7 +925,7 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
 int build_graphs_for_launch(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t *fam_off, uint32_t q0, uint32_t n,
                             const sina_hip_align_params *p, int W, const PrunePlan &pp, BuiltGraphs *bg) {
     return build_family_graphs(c, fam_ids, fam_off, q0, n, p->fs_weight, W, bg, p->insertion == SINA_INSERTION_FORBID,
-                               pp.on ? pp.kappa64 : 0.f);
+                               pp.on ? pp.kappa64 : 0.f, true);
 }
 
 }  // namespace
@@ -917,7 +970,7 @@ int sina_hip_debug_family_graph(sina_hip_ctx *c, const uint32_t *fam_ids, uint32
     const uint64_t foff[2] = {0, F};
     BuiltGraphs bg;
     // (with the row-skip bound for the default scoring: sina_hip_debug_rgain reads it back)
-    if (build_family_graphs(c, fam_ids, foff, 0, 1, fs_weight, (int)ring_depth, &bg, true, fs_weight >= 0.f ? 64.0f * 1.0001f * 2.0f : 0.f)) return 1;
+    if (build_family_graphs(c, fam_ids, foff, 0, 1, fs_weight, (int)ring_depth, &bg, true, fs_weight >= 0.f ? 64.0f * 1.0001f * 2.0f : 0.f, false)) return 1;
     const uint32_t N = bg.sizes[kBuiltN];
     std::vector<uint4> rec(N);
     std::vector<uint32_t> pr(bg.sizes[kBuiltEdges] + 8);
@@ -940,6 +993,40 @@ int sina_hip_debug_family_graph(sina_hip_ctx *c, const uint32_t *fam_ids, uint32
         for (uint32_t x = 0; x < (rec[m].z & 0xffu); x++) pred[e++] = pr[rec[m].x + x] & 0xffffu;
     }
     pred_off[N] = e;
+    return 0;
+}
+
+int sina_hip_debug_family_graph_words(sina_hip_ctx *c, const uint32_t *fam_ids, uint32_t F, float fs_weight,
+                                      uint32_t ring_depth, uint32_t *n_nodes, uint32_t *n_edges, uint32_t *rec_z,
+                                      uint32_t *rec_w, uint32_t *pred_entries, uint32_t *size_words, uint32_t cap_nodes,
+                                      uint32_t cap_edges) {
+    if (!c || !fam_ids || !n_nodes || !n_edges || !rec_z || !rec_w || !pred_entries || !size_words)
+        SH_FAIL("debug_family_graph_words: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->st->have_refs) SH_FAIL("debug_family_graph_words: upload references first");
+    if (F == 0 || F > (uint32_t)kMaxFam) SH_FAIL("debug_family_graph_words: family size must be in 1..128");
+    SH_CHECK(hipSetDevice(c->device));
+    const uint64_t foff[2] = {0, F};
+    BuiltGraphs bg;
+    // (the same build as sina_hip_debug_family_graph's: successor minima and the row-skip bound of the default scoring)
+    if (build_family_graphs(c, fam_ids, foff, 0, 1, fs_weight, (int)ring_depth, &bg, true, fs_weight >= 0.f ? 64.0f * 1.0001f * 2.0f : 0.f, false)) return 1;
+    const uint32_t N = bg.sizes[kBuiltN];
+    std::vector<uint4> rec(N);
+    std::vector<uint32_t> pr(bg.sizes[kBuiltEdges] + 8);
+    if (N) SH_CHECK(hipMemcpy(rec.data(), c->rec.p, sizeof(uint4) * N, hipMemcpyDeviceToHost));
+    SH_CHECK(hipMemcpy(pr.data(), c->pred.p, 4 * pr.size(), hipMemcpyDeviceToHost));
+    uint32_t E = 0;
+    for (uint32_t m = 0; m < N; m++) E += rec[m].z & 0xffu;
+    *n_nodes = N;
+    *n_edges = E;
+    if (N > cap_nodes || E > cap_edges) SH_FAIL("debug_family_graph_words: output buffers too small");
+    uint32_t e = 0;
+    for (uint32_t m = 0; m < N; m++) {
+        rec_z[m] = rec[m].z;
+        rec_w[m] = rec[m].w;
+        for (uint32_t x = 0; x < (rec[m].z & 0xffu); x++) pred_entries[e++] = pr[rec[m].x + x];
+    }
+    memcpy(size_words, bg.sizes.data(), 4 * kBuiltWords);
     return 0;
 }
 

@@ -1759,10 +1759,13 @@ void build_family_graph(const std::vector<const cseq *> &fam, float fs_weight, h
             const auto &b = fam[j]->getAlignedBases();
             if (cur[j] < b.size() && b[cur[j]].getPosition() == col) {
                 const uint8_t m = b[cur[j]].getBase().mask() & 31;
-                int32_t node = node_of_mask[m];
+                // (mseq keys a column's nodes by the base's CHARACTER, mseq.cpp:92-96: masks 0 and 16 are both '.' and
+                // share a node, which keeps the base of the first member to show it)
+                const uint8_t key = m == 16 ? 0 : m;
+                int32_t node = node_of_mask[key];
                 if (node < 0) {
                     node = (int32_t)g->pos.size();
-                    node_of_mask[m] = node;
+                    node_of_mask[key] = node;
                     g->pos.push_back(col);
                     g->mask.push_back(m);
                     count.push_back(1.f);

@@ -392,6 +392,8 @@ int build_family_profiles(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64
             if (id >= c->st->n_refs) SH_FAIL("align_profiles: reference id out of range");
             bases += c->st->ref_off_host[id + 1] - c->st->ref_off_host[id];
         }
+        // (a family without a single base still has the node of column 0: unlike the DAG build, graph_build.hip, nothing
+        // to refuse here)
     }
     float self16[16];
     self_scores(p, self16);

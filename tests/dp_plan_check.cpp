@@ -525,7 +525,52 @@ NOINLINE static void test_classify() {
     CHECK(classify_any(b.batch(), b.qoff.data(), false, &wide) == 1 && g_err_limit == 0, "a malformed DAG is a plain error");
 }
 
-int main() {
+// ------------------------------------------------------------------------------------------------ --words
+// `dp_plan_check --words FILE RING`: prep_range's words of one DAG read from FILE, for tests/test_graph_cpu.py to compare
+// with tests/graph_ref.py dp_words.  FILE is text: N E, then N columns, N masks, N weights (float bits), N + 1 pred_off,
+// E predecessors.  The DAG passes the checks above first; then a line "sizes N spill-rows first-sink", a line "z w" per
+// row and a line per predecessor entry.
+NOINLINE static int print_words(const char *path, int W) {
+    g_case = "--words";
+    FILE *f = fopen(path, "r");
+    CHECK(f != nullptr, "cannot read %s", path);
+    unsigned n = 0, e = 0;
+    CHECK(fscanf(f, "%u %u", &n, &e) == 2 && W >= 1 && W <= kMaxRing, "header / ring");
+    Dag d;
+    d.pos.resize(n), d.mask.resize(n), d.weight.resize(n), d.pred_off.resize(n + 1), d.pred.resize(e);
+    auto read = [&](uint32_t *out) {
+        unsigned v;
+        CHECK(fscanf(f, "%u", &v) == 1, "short file");
+        *out = v;
+    };
+    for (auto &x : d.pos) read(&x);
+    for (auto &x : d.mask) {
+        uint32_t v;
+        read(&v);
+        x = (uint8_t)v;
+    }
+    for (auto &x : d.weight) {
+        uint32_t v;
+        read(&v);
+        memcpy(&x, &v, 4);
+    }
+    for (auto &x : d.pred_off) read(&x);
+    for (auto &x : d.pred) read(&x);
+    fclose(f);
+    CHECK(d.pred_off[0] == 0 && d.pred_off[n] == e, "pred_off");
+    Batch b;
+    b.add(d, 10);
+    check_prep(b, 0, 1, 512, W, 128.f);
+    HostPrep hp;
+    CHECK(prep_range(b.batch(), b.qoff.data(), 0, 1, 512, W, &hp, 0.f, nullptr) == 0, "prep_range failed: %s", g_err.c_str());
+    printf("sizes %u %u %u\n", hp.qd[0].N, hp.qd[0].n_spill, hp.qd[0].first_sink);
+    for (uint32_t m = 0; m < n; m++) printf("%u %u\n", hp.rec[m].z, hp.rec[m].w);
+    for (uint32_t x = 0; x < e; x++) printf("%u\n", hp.pred[x]);
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc == 4 && !strcmp(argv[1], "--words")) return print_words(argv[2], atoi(argv[3]));
     test_prep_range();
     test_prep_directed();
     test_cut_range();

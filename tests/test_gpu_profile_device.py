@@ -40,29 +40,8 @@ def _trimmed(refs, seed, drop_col0=True):
     return _refset(seqs, refs.width)
 
 
-def _oracle_tables(oracle, fam, ms, mms, gp, gpe):
-    o = oracle.pseq_build(fam)
-    n = o["n"]
-    assert n <= 65535                                       # (checked here, on the CPU: no case may be skipped)
-    tab = np.full((n, 16), np.inf, np.float32)
-    prof = np.asarray(o["prof"], np.float32).reshape(n, 6)
-    for node in range(n):
-        for m in range(1, 16):
-            tab[node, m] = oracle.profile_comp(prof[node], m, ms, mms, gp, gpe)
-    own = np.array([0.0] + [oracle.profile_comp(None, m, ms, mms, gp, gpe) for m in range(1, 16)], np.float32)
-    return o, tab, own
-
-
-def _check_hook(oracle, ctx, cs, ids, scores):
-    ms, mms, gp, gpe = scores
-    o, tab, own = _oracle_tables(oracle, [cs[int(i)] for i in ids], ms, mms, gp, gpe)
-    pos, sc, self16 = ctx.debug_family_profile(ids, ms, mms, gp, gpe)
-    assert len(pos) == o["n"] and (pos == o["pos"]).all()
-    assert np.isinf(sc[:, 0]).all() and (sc[:, 0] > 0).all()
-    bad = np.argwhere(util.f32_bits(sc[:, 1:]) != util.f32_bits(tab[:, 1:]))
-    assert len(bad) == 0, ("first difference at node %d, mask %d" % (bad[0][0], bad[0][1] + 1), len(ids), scores)
-    assert (util.f32_bits(self16[1:]) == util.f32_bits(own[1:])).all()
-    return o["n"]
+_oracle_tables = util.profile_oracle_tables   # (shared with test_gpu_graph.py)
+_check_hook = util.check_profile_hook
 
 
 def _uploaded(refs):

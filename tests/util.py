@@ -115,6 +115,37 @@ def row_store_model(pred_off, pred, n_slots, far_lds=192):
     return out
 
 
+# ---------------------------------------------------------------- the device profile build against the oracle
+# (test_gpu_profile_device.py and test_gpu_graph.py share these)
+
+def profile_oracle_tables(oracle, fam, ms, mms, gp, gpe):
+    """The oracle's pseq of the family, its [n, 16] table of match terms (base_profile::comp) and the 16 self terms."""
+    o = oracle.pseq_build(fam)
+    n = o["n"]
+    assert n <= 65535                                       # (checked here, on the CPU: no case may be skipped)
+    tab = np.full((n, 16), np.inf, np.float32)
+    prof = np.asarray(o["prof"], np.float32).reshape(n, 6)
+    for node in range(n):
+        for m in range(1, 16):
+            tab[node, m] = oracle.profile_comp(prof[node], m, ms, mms, gp, gpe)
+    own = np.array([0.0] + [oracle.profile_comp(None, m, ms, mms, gp, gpe) for m in range(1, 16)], np.float32)
+    return o, tab, own
+
+
+def check_profile_hook(oracle, ctx, cs, ids, scores):
+    """sina_hip_debug_family_profile of the family `ids` (into the cseqs `cs` of the uploaded store) against the
+    oracle, bit for bit; returns the number of nodes."""
+    ms, mms, gp, gpe = scores
+    o, tab, own = profile_oracle_tables(oracle, [cs[int(i)] for i in ids], ms, mms, gp, gpe)
+    pos, sc, self16 = ctx.debug_family_profile(ids, ms, mms, gp, gpe)
+    assert len(pos) == o["n"] and (pos == o["pos"]).all()
+    assert np.isinf(sc[:, 0]).all() and (sc[:, 0] > 0).all()
+    bad = np.argwhere(f32_bits(sc[:, 1:]) != f32_bits(tab[:, 1:]))
+    assert len(bad) == 0, ("first difference at node %d, mask %d" % (bad[0][0], bad[0][1] + 1), len(ids), scores)
+    assert (f32_bits(self16[1:]) == f32_bits(own[1:])).all()
+    return o["n"]
+
+
 # ---------------------------------------------------------------- reference-parts mesh cases
 # (tests/golden/make_ref_vectors.py computes the planes of these cases with the reference's own
 # scoring schemes and DAG and stores one hash per plane; the oracle and the GPU are checked against
