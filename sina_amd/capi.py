@@ -208,6 +208,21 @@ def _c(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
 
 
+def read_counters(fn, args, fields, check):
+    """Reads a C getter of counters: fn(*args, out...) with one out-parameter per (key, ctype) of `fields`, in their order;
+    its return code goes to `check`.  Returns dict(key=value) in that order, float for c_double and int otherwise."""
+    outs = [t() for _, t in fields]
+    check(fn(*args, *[C.byref(o) for o in outs]))
+    return {k: float(o.value) if t is C.c_double else int(o.value) for (k, t), o in zip(fields, outs)}
+
+
+KERNEL_MS = [("kernel_ms", C.c_double)]
+
+
+def u64_fields(*keys):
+    return [(k, C.c_uint64) for k in keys]
+
+
 class Context:
     """Owns one sina_hip_ctx (one GPU, one stream)."""
 
@@ -229,6 +244,9 @@ class Context:
     def _check(self, rc):
         if rc != 0:
             raise SinaHipError(self.L.sina_hip_last_error().decode())
+
+    def _counters(self, fn, fields):
+        return read_counters(fn, (self.h,), fields, self._check)
 
     def close(self):
         if self.h:
@@ -305,15 +323,11 @@ class Context:
 
     def long_queries(self):
         """Queries the long k-mer count kernel has counted on this context so far."""
-        n = C.c_uint64()
-        self._check(self.L.sina_hip_long_queries(self.h, C.byref(n)))
-        return int(n.value)
+        return self._counters(self.L.sina_hip_long_queries, u64_fields("n"))["n"]
 
     def big_select_queries(self):
         """Queries the big select (more than 4096 candidates per query) has ranked on this context so far."""
-        n = C.c_uint64()
-        self._check(self.L.sina_hip_big_select_queries(self.h, C.byref(n)))
-        return int(n.value)
+        return self._counters(self.L.sina_hip_big_select_queries, u64_fields("n"))["n"]
 
     # ---- alignment
     @staticmethod
@@ -397,9 +411,7 @@ class Context:
 
     def wide_queries(self):
         """Queries the wide kernel has aligned on this context so far."""
-        n = C.c_uint64()
-        self._check(self.L.sina_hip_wide_queries(self.h, C.byref(n)))
-        return int(n.value)
+        return self._counters(self.L.sina_hip_wide_queries, u64_fields("n"))["n"]
 
     def last_error_is_limit(self):
         """True if this thread's last failed call was refused for exceeding a documented limit of the fast path."""
@@ -461,10 +473,7 @@ class Context:
 
     def match_stats(self):
         """The match-count kernel on this context so far: dict(kernel_ms, pairs, cand_bases, launches)."""
-        ms = C.c_double()
-        pairs, bases, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self._check(self.L.sina_hip_match_stats(self.h, C.byref(ms), C.byref(pairs), C.byref(bases), C.byref(launches)))
-        return dict(kernel_ms=float(ms.value), pairs=int(pairs.value), cand_bases=int(bases.value), launches=int(launches.value))
+        return self._counters(self.L.sina_hip_match_stats, KERNEL_MS + u64_fields("pairs", "cand_bases", "launches"))
 
     def upload_name_order(self, rank):
         """rank[id] = position of reference id's name in ascending byte-wise order (a permutation of 0..n_refs-1)."""
@@ -514,10 +523,7 @@ class Context:
 
     def rank_stats(self):
         """The rank kernels on this context so far: dict(kernel_ms, pairs, cand_bases, launches)."""
-        ms = C.c_double()
-        pairs, bases, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self._check(self.L.sina_hip_rank_stats(self.h, C.byref(ms), C.byref(pairs), C.byref(bases), C.byref(launches)))
-        return dict(kernel_ms=float(ms.value), pairs=int(pairs.value), cand_bases=int(bases.value), launches=int(launches.value))
+        return self._counters(self.L.sina_hip_rank_stats, KERNEL_MS + u64_fields("pairs", "cand_bases", "launches"))
 
     def upload_pairs(self, pairs):
         """The helix map for pair_counts: pairs[i] = partner column of column i, 0 = unpaired.  Empty or all zero: no map."""
@@ -536,11 +542,7 @@ class Context:
 
     def pair_stats(self):
         """The pair-count kernel on this context so far: dict(kernel_ms, sequences, entries_visited, launches)."""
-        ms = C.c_double()
-        seqs, ent, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self._check(self.L.sina_hip_pair_stats(self.h, C.byref(ms), C.byref(seqs), C.byref(ent), C.byref(launches)))
-        return dict(kernel_ms=float(ms.value), sequences=int(seqs.value), entries_visited=int(ent.value),
-                    launches=int(launches.value))
+        return self._counters(self.L.sina_hip_pair_stats, KERNEL_MS + u64_fields("sequences", "entries_visited", "launches"))
 
     def count_pairs(self, on=True):
         """The switch of the in-place pair count: with it on, an align call with assemble=1 on a store with a helix map
@@ -560,10 +562,7 @@ class Context:
     def pair_inplace_stats(self):
         """The in-place pair-count kernel on this context so far: dict(kernel_ms, sequences, launches); sequences
         counts assembled queries only."""
-        ms = C.c_double()
-        seqs, launches = C.c_uint64(), C.c_uint64()
-        self._check(self.L.sina_hip_pair_inplace_stats(self.h, C.byref(ms), C.byref(seqs), C.byref(launches)))
-        return dict(kernel_ms=float(ms.value), sequences=int(seqs.value), launches=int(launches.value))
+        return self._counters(self.L.sina_hip_pair_inplace_stats, KERNEL_MS + u64_fields("sequences", "launches"))
 
     def count_identity(self, on=True):
         """The switch of the in-place family identity (--calc-idty): with it on, align_families, align_families_wsets
@@ -585,10 +584,7 @@ class Context:
     def identity_inplace_stats(self):
         """The in-place family-identity kernel on this context so far: dict(kernel_ms, sequences, pairs, launches);
         sequences counts assembled queries only, pairs their (query, member) pairs."""
-        ms = C.c_double()
-        seqs, prs, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self._check(self.L.sina_hip_identity_inplace_stats(self.h, C.byref(ms), C.byref(seqs), C.byref(prs), C.byref(launches)))
-        return dict(kernel_ms=float(ms.value), sequences=int(seqs.value), pairs=int(prs.value), launches=int(launches.value))
+        return self._counters(self.L.sina_hip_identity_inplace_stats, KERNEL_MS + u64_fields("sequences", "pairs", "launches"))
 
     def align_families(self, fam_ids, fam_off, qmask, qoff, params=None):
         params = params or self.params()

@@ -359,7 +359,7 @@ int sina_hip_fork(sina_hip_ctx *parent, sina_hip_ctx **ctx) {
     c->owns_store = false;
     c->lds_budget = parent->lds_budget;
     c->n_cu = parent->n_cu;
-    // (count_pairs and count_identity stay off: the switches are per context, sina_hip_align_count_pairs / _count_identity)
+    // (the in-place counts' switches stay off: they are per context, sina_hip_align_count_pairs / _count_identity)
     c->bind_hints();
     if (finish_ctx(c)) {
         const std::string why = sina_hip_last_error();
@@ -445,10 +445,9 @@ int sina_hip_align_graphs(sina_hip_ctx *c, const sina_hip_graph_batch *g, const 
                           const uint64_t *qoff, const sina_hip_align_params *p, sina_hip_align_out *out,
                           uint32_t *out_pos) {
     if (!c) SH_FAIL("align_graphs: null ctx");
-    std::lock_guard<std::mutex> lk(c->mu);
+    align_call call(c);
     sina_hip_hint_guard hints(c);
-    c->id_active = false;  // (no family comes to the device: sina_hip_staged_identity gives NULL)
-    if (pair_inplace_begin(c, p, g ? g->nq : 0)) return 1;
+    if (call.begin(kMayCountPairs, p, g ? g->nq : 0)) return 1;  // (no family comes to the device: no identity)
     return align_graphs_impl(c, g, qmask, qoff, p, out, out_pos);
 }
 
@@ -457,10 +456,9 @@ int sina_hip_align_graphs_wsets(sina_hip_ctx *c, const sina_hip_graph_batch *g, 
                                 uint32_t n_sets, sina_hip_align_out *out, uint32_t *out_pos) {
     if (!c) SH_FAIL("align_graphs_wsets: null ctx");
     if (p && !weighted_scheme(p)) SH_FAIL("align_graphs_wsets: weight sets need positional weights (p->weights, p->n_weights)");
-    std::lock_guard<std::mutex> lk(c->mu);
+    align_call call(c);
     sina_hip_hint_guard hints(c);
-    c->id_active = false;  // (no family comes to the device: sina_hip_staged_identity gives NULL)
-    if (pair_inplace_begin(c, p, g ? g->nq : 0)) return 1;
+    if (call.begin(kMayCountPairs, p, g ? g->nq : 0)) return 1;  // (no family comes to the device: no identity)
     return align_graphs_impl(c, g, qmask, qoff, p, out, out_pos, nullptr, 0, 0, nullptr, nullptr, weight_set, n_sets);
 }
 
@@ -468,25 +466,21 @@ int sina_hip_align_graphs_any(sina_hip_ctx *c, const sina_hip_graph_batch *g, co
                               const uint64_t *qoff, const sina_hip_align_params *p, sina_hip_align_out *out,
                               uint32_t *out_pos) {
     if (!c) SH_FAIL("align_graphs_any: null ctx");
-    std::lock_guard<std::mutex> lk(c->mu);
+    align_call call(c);
     sina_hip_hint_guard hints(c);
-    c->id_active = false;  // (no family comes to the device: sina_hip_staged_identity gives NULL)
-    if (pair_inplace_begin(c, p, g ? g->nq : 0)) return 1;
+    if (call.begin(kMayCountPairs, p, g ? g->nq : 0)) return 1;  // (no family comes to the device: no identity)
     return align_graphs_any_impl(c, g, qmask, qoff, p, out, out_pos);
 }
 
 int sina_hip_wide_queries(sina_hip_ctx *c, uint64_t *n) {
     if (!c || !n) SH_FAIL("wide_queries: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    *n = c->wide_queries;
-    return 0;
+    return read_path_queries(c, kPathWide, n);
 }
 
 int sina_hip_debug_mesh_wide(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask, uint32_t qlen,
                              const sina_hip_align_params *p, uint32_t *tb_vm, uint32_t *tb_vs, float *value) {
     if (!c || !g || g->nq != 1 || !qmask || !p || !tb_vm || !tb_vs) SH_FAIL("debug_mesh_wide: needs exactly one query");
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->pc_active = c->id_active = false;  // (a debug call counts no pairs and no identity)
+    align_call call(c);  // (a debug call counts no pairs and no identity: nothing begins)
     SH_CHECK(hipSetDevice(c->device));
     if (p->insertion == SINA_INSERTION_FORBID && !g->succ_minpos) SH_FAIL("debug_mesh_wide: insertion=forbid needs succ_minpos");
     if (g->node_score16 != nullptr && (!g->self_score16 || weighted_scheme(p)))
@@ -503,8 +497,7 @@ int sina_hip_debug_mesh_wide(sina_hip_ctx *c, const sina_hip_graph_batch *g, con
 int sina_hip_debug_mesh(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmask, uint32_t qlen,
                         const sina_hip_align_params *p, uint32_t *tb_vm, uint32_t *tb_vs, float *value, int prune) {
     if (!c || !g || g->nq != 1 || !tb_vm || !tb_vs) SH_FAIL("debug_mesh: needs exactly one query");
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->pc_active = c->id_active = false;  // (a debug call counts no pairs and no identity)
+    align_call call(c);  // (a debug call counts no pairs and no identity: nothing begins)
     const uint64_t qoff[2] = {0, qlen};
     sina_hip_align_out o;
     std::vector<uint32_t> pos(qlen);

@@ -441,7 +441,7 @@ struct DpLaunch {
     sina_hip_align_out *out = nullptr;
     uint32_t *out_pos = nullptr;  // (optional) the launch's place in the caller's array, and ...
     uint64_t out_pos_base = 0;    // ... in the context's staged columns (ctx.h, h_out_pos)
-    uint32_t q_base = 0;          // the launch's first query among the call's (its rows in the context's staged pair counts, ctx.h, h_pc)
+    uint32_t q_base = 0;          // the launch's first query among the call's (its rows in the context's staged in-place counts, ctx.h, InplaceCount::h_rows)
     bool profile_batch = false;   // the DP reads the context's prof16, the walk its self16
     bool debug_planes = false, want_dbg_value = false;  // sina_hip_debug_mesh: planes to unpack, a plane of cell values
     // node entries per DAG of the device-built DAGs whose first member's chain the build left in the context (ctx.h,

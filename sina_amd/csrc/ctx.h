@@ -36,8 +36,7 @@ struct sina_hip_store {
     // column, ascending in the column; n_pair_ent == 0: no map.  Kept when the references change (it describes columns)
     sina_hip::DevBuf pair_ent;
     uint32_t n_pair_ent = 0;
-    std::atomic<size_t> pc_rows_hint{0};  // bytes of pinned counter rows the largest counted align call took (sina_hip_ctx::h_pc)
-    std::atomic<size_t> id_rows_hint{0};  // ... and of pinned identity rows (sina_hip_ctx::h_id)
+    std::atomic<size_t> inplace_rows_hint[2] = {};  // bytes of pinned rows the largest counted align call took (InplaceCount::h_rows)
     std::mutex aux_mu;
     std::mutex stats_mu;
     // The device-filling kernels of all contexts (k-mer count/select, DAG build, DP) go through ONE
@@ -109,6 +108,70 @@ struct sina_hip_store {
     } tb_pool;
 };
 
+namespace sina_hip {
+// A kernel's own time and volume on a context (sina_hip_ctx::use), read by the sina_hip_*_stats getters through
+// read_use below.  What a and b count:
+//   kernel                 a          b                  getter
+//   kUseMatch              pairs      cand_bases         sina_hip_match_stats
+//   kUseRank               pairs      cand_bases         sina_hip_rank_stats
+//   kUsePairs              sequences  entries_visited    sina_hip_pair_stats
+//   kUsePairsInplace       sequences  --                 sina_hip_pair_inplace_stats
+//   kUseIdentityInplace    sequences  pairs              sina_hip_identity_inplace_stats
+struct KernelUse {
+    double ms = 0;
+    uint64_t a = 0, b = 0, launches = 0;
+    void add(double ms_, uint64_t a_, uint64_t b_, uint64_t launches_) {  // (by the context's caller, who holds its mutex)
+        ms += ms_;
+        a += a_;
+        b += b_;
+        launches += launches_;
+    }
+};
+enum kernel_use { kUseMatch, kUseRank, kUsePairs, kUsePairsInplace, kUseIdentityInplace, kNumKernelUse };
+// queries a path off the fast one has taken on a context (sina_hip_ctx::path_queries; sina_hip_wide_queries,
+// sina_hip_long_queries, sina_hip_big_select_queries): the wide DP kernel, the long k-mer count kernel, the big select
+enum slow_path { kPathWide, kPathLong, kPathBigSelect, kNumSlowPaths };
+
+// A count that rides on an align call, over the words the device assembly left: the helix base pairs (pairs.hip,
+// pair_count_assembled_kernel; sina_hip_align_count_pairs, sina_hip_staged_pair_counts) and the family identity
+// (identity.hip, family_identity_kernel; sina_hip_align_count_identity, sina_hip_staged_identity).
+struct InplaceCount {
+    const size_t row_bytes;  // of a query's row: six counters, or the best score's bits and the members that scored
+    const int kernel;        // its record in sina_hip_ctx::use
+    const int ev;            // the event of sina_hip_ctx::ev that ends its kernel
+    std::atomic<size_t> *hint = nullptr;  // bytes of h_rows the store's contexts have needed so far (bind_hints)
+    bool on = false;         // the switch, per context
+    bool active = false;     // the call in progress -- afterwards: the last one -- counts (align_call)
+    DevBuf rows;             // a launch range's rows on the device
+    HostBuf h_rows;          // the whole call's rows in pinned memory, laid out like the call's `out`
+    // Whether this call counts is the entry's to say (align_call::begin).  If it does, the pinned rows are there for
+    // the whole call and zero: a launch range fills its queries' rows (copy), the queries that never see a DP launch
+    // range (the wide path) keep the zeros.  A call that does not count forgets the rows of the one before.
+    int begin(bool counts, uint32_t nq) {
+        active = false;
+        if (!counts) return 0;
+        const size_t bytes = row_bytes * nq;
+        if (h_rows.reserve(bytes)) return 1;
+        size_t seen = hint->load(std::memory_order_relaxed);
+        while (bytes > seen && !hint->compare_exchange_weak(seen, bytes, std::memory_order_relaxed)) {
+        }
+        memset(h_rows.p, 0, bytes);
+        active = true;
+        return 0;
+    }
+    // the device rows of a launch range of bq queries
+    int reserve(uint32_t bq) { return active ? rows.reserve(row_bytes * bq) : 0; }
+    // ... on their way to their place in the call's rows, q_base being the range's first query among the call's
+    int copy(uint32_t q_base, uint32_t bq, hipStream_t s) {
+        if (!active) return 0;
+        SH_CHECK(hipMemcpyAsync(h_rows.as<unsigned char>() + row_bytes * q_base, rows.p, row_bytes * bq, hipMemcpyDeviceToHost, s));
+        return 0;
+    }
+    const uint32_t *staged() const { return active ? h_rows.as<uint32_t>() : nullptr; }
+};
+enum inplace_count { kInplacePairs, kInplaceIdentity, kNumInplace };
+}  // namespace sina_hip
+
 struct sina_hip_ctx {
     int device = 0;
     int n_cu = 256;  // compute units of the device (4 SIMDs each)
@@ -130,9 +193,8 @@ struct sina_hip_ctx {
     // the wide path (mesh_wide.hip): a launch's inputs, and its mesh -- every cell's fields in HBM; grow-only, apart from
     // the trace-back pool above, allocated by the first query that needs it
     sina_hip::DevBuf wide_in, wide_planes;
-    uint64_t wide_queries = 0;        // queries the wide kernel has aligned on this context (sina_hip_wide_queries)
-    uint64_t long_queries = 0;        // queries the long k-mer count kernel has counted on this context (sina_hip_long_queries)
-    uint64_t big_select_queries = 0;  // queries the big select has ranked on this context (sina_hip_big_select_queries)
+    uint64_t path_queries[sina_hip::kNumSlowPaths] = {};  // queries each slow path has taken on this context (read_path_queries)
+    sina_hip::KernelUse use[sina_hip::kNumKernelUse];      // the counted kernels' own time and volume on this context (read_use)
     // the big select (kmer.hip): a launch range's keys with their double buffer, and the segmented sort's temporary
     // storage -- grow-only, allocated by the first search that wants more than 4096 candidates
     sina_hip::DevBuf k_big_keys, k_big_tmp;
@@ -145,40 +207,15 @@ struct sina_hip_ctx {
     sina_hip::DevBuf k_qoff, k_scores, k_out_ids, k_out_scores, k_out_n, k_tmp0, k_tmp1, k_tmp2;
     sina_hip::DevBuf g_fam_ids, g_fam_off, g_tmp0, g_tmp1, g_tmp2, g_tmp3, g_sizes, g_wtab;
     sina_hip::DevBuf s_qab, s_qoff, s_cand, s_coff, s_out;  // search-stage comparison
-    // the match-count kernel (match.hip): its rows of counts and, for caller-given lists, their lengths; its own time
-    // and volume on this context (sina_hip_match_stats)
+    // the match-count kernel (match.hip): its rows of counts and, for caller-given lists, their lengths
     sina_hip::DevBuf m_out, m_n;
-    double match_ms = 0;
-    uint64_t match_pairs = 0, match_bases = 0, match_launches = 0;
     // the rank kernel (rank.hip): the chunks' key rows, the final rows on their way to the host, the flags and the
-    // volume counters the kernel keeps; its own time and volume on this context (sina_hip_rank_stats)
+    // volume counters the kernel keeps
     sina_hip::DevBuf r_keys, r_ids, r_scores, r_n, r_flag, r_cnt;
-    double rank_ms = 0;
-    uint64_t rank_pairs = 0, rank_bases = 0, rank_launches = 0;
-    // the pair-count kernel (pairs.hip; it borrows s_qab, s_qoff and s_out): its own time and volume on this context
-    // (sina_hip_pair_stats)
-    double pair_ms = 0;
-    uint64_t pair_seqs = 0, pair_entries = 0, pair_launches = 0;
-    // the pair count of an align call (pairs.hip, pair_count_assembled_kernel; sina_hip_align_count_pairs): the switch;
-    // whether the call in progress -- afterwards: the last one -- counts (pair_inplace_begin); a launch range's rows on
-    // the device; the whole call's rows in pinned memory, laid out like the call's `out` (a range writes at
-    // DpLaunch::q_base; sina_hip_staged_pair_counts); its own time and volume on this context
-    // (sina_hip_pair_inplace_stats)
-    bool count_pairs = false, pc_active = false;
-    sina_hip::DevBuf pc_out;
-    sina_hip::HostBuf h_pc;
-    double pc_ms = 0;
-    uint64_t pc_seqs = 0, pc_launches = 0;
-    // the family identity of an align call (identity.hip, family_identity_kernel; sina_hip_align_count_identity), laid
-    // out like the pair count's: the switch; whether the call in progress -- afterwards: the last one -- counts
-    // (identity_inplace_begin); a launch range's rows on the device; the whole call's [nq][2] rows in pinned memory (a
-    // range writes at DpLaunch::q_base; sina_hip_staged_identity); its own time and volume on this context
-    // (sina_hip_identity_inplace_stats)
-    bool count_identity = false, id_active = false;
-    sina_hip::DevBuf id_out;
-    sina_hip::HostBuf h_id;
-    double id_ms = 0;
-    uint64_t id_seqs = 0, id_pairs = 0, id_launches = 0;
+    // (the pair-count kernel, pairs.hip, borrows s_qab, s_qoff and s_out)
+    // the counts that ride on an align call: [n][6] pair counters in 24 bytes, [n][2] identity words in 8
+    sina_hip::InplaceCount inplace[sina_hip::kNumInplace] = {{24, sina_hip::kUsePairsInplace, 12},
+                                                             {sina_hip::identity_row_bytes(1), sina_hip::kUseIdentityInplace, 13}};
     sina_hip::HostBuf h_out, h_out_pos;  // pinned staging for the DP results
     // h_out_pos holds the aligned columns of a whole align call (laid out like the caller's out_pos): a launch
     // range writes at DpLaunch::out_pos_base, callers that pass no out_pos read them here (sina_hip_staged_out_pos)
@@ -197,7 +234,7 @@ struct sina_hip_ctx {
                                                &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &order,
                                                &s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &edge, &prof16, &self16, &rgain,
                                                &scout, &scout_u, &wset, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag,
-                                               &r_cnt, &pc_out, &id_out};
+                                               &r_cnt, &inplace[sina_hip::kInplacePairs].rows, &inplace[sina_hip::kInplaceIdentity].rows};
         for (int i = 0; i < kNumScratch; i++) all[i] = list[i];
     }
     void publish_hints() {  // after a call: remember how big my buffers had to be
@@ -218,6 +255,7 @@ struct sina_hip_ctx {
         sina_hip::DevBuf *all[kNumScratch];
         scratch(all);
         for (int i = 0; i < kNumScratch; i++) all[i]->hint = &st->cap_hint[i];
+        for (int i = 0; i < sina_hip::kNumInplace; i++) inplace[i].hint = &st->inplace_rows_hint[i];
     }
     // What one KIND of call uses, brought to the hinted sizes now (sina_hip_prewarm): 0 k-mer search,
     // 1 alignment (DAG build, DP, walk), 2 search-stage comparison.
@@ -226,7 +264,7 @@ struct sina_hip_ctx {
                                       &s_qab, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};  // (s_qab, r_*: sina_hip_kmer_topk_rank)
         sina_hip::DevBuf *align[] = {&qd, &order, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &edge, &res, &weights, &out,
                                      &out_pos, &g_fam_ids, &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &rgain, &scout, &scout_u,
-                                     &prof16, &self16, &wset, &pc_out, &id_out};
+                                     &prof16, &self16, &wset, &inplace[sina_hip::kInplacePairs].rows, &inplace[sina_hip::kInplaceIdentity].rows};
         sina_hip::DevBuf *compare[] = {&s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};
         sina_hip::DevBuf **list = kind == 0 ? search : (kind == 1 ? align : compare);
         const size_t n = kind == 0 ? sizeof search / sizeof *search : (kind == 1 ? sizeof align / sizeof *align : sizeof compare / sizeof *compare);
@@ -234,10 +272,10 @@ struct sina_hip_ctx {
             const size_t want = list[i]->hint ? list[i]->hint->load(std::memory_order_relaxed) : 0;
             if (want > list[i]->cap && list[i]->reserve_exact(want)) return 1;
         }
-        // (the pinned rows of the in-place pair count: as many as any context of the store has needed -- none, and
+        // (the pinned rows of the in-place counts: as many as any context of the store has needed -- none, and
         // nothing is reserved, on a store whose contexts have not counted)
-        if (kind == 1 && h_pc.reserve(st->pc_rows_hint.load(std::memory_order_relaxed))) return 1;
-        if (kind == 1 && h_id.reserve(st->id_rows_hint.load(std::memory_order_relaxed))) return 1;  // (the identity rows, likewise)
+        for (auto &ic : inplace)
+            if (kind == 1 && ic.h_rows.reserve(ic.hint->load(std::memory_order_relaxed))) return 1;
         return 0;
     }
     void free_all() {
@@ -252,8 +290,7 @@ struct sina_hip_ctx {
         k_big_tmp.release();
         h_out.release();
         h_out_pos.release();
-        h_pc.release();
-        h_id.release();
+        for (auto &ic : inplace) ic.h_rows.release();
         h_res.release();
         for (auto &h : h_stage) h.release();
         if (owns_store && st) {
@@ -690,40 +727,45 @@ int rank_check_rules(const char *who, sina_hip_ctx *c, int iupac_rule, int cover
 }  // namespace sina_hip
 
 namespace sina_hip {
-// ---- the pair count of an align call (sina_hip_align_count_pairs).  Every align entry calls this first, for its nq
-// queries: the call counts if the switch is on, the call assembles and the store has a helix map; then the pinned rows
-// are there for the whole call and zero -- a launch range fills its queries' rows (fetch_results), the queries that
-// never see a DP launch range (the wide path) keep the zeros.  A call that does not count forgets the rows of the one
-// before (sina_hip_staged_pair_counts: NULL).
-inline int pair_inplace_begin(sina_hip_ctx *c, const sina_hip_align_params *p, uint32_t nq) {
-    c->pc_active = false;
-    if (!c->count_pairs || !p || !p->assemble || nq == 0 || c->st->n_pair_ent == 0) return 0;
-    const size_t bytes = 24 * (size_t)nq;
-    SH_CHECK(hipSetDevice(c->device));
-    if (c->h_pc.reserve(bytes)) return 1;
-    size_t seen = c->st->pc_rows_hint.load(std::memory_order_relaxed);
-    while (bytes > seen && !c->st->pc_rows_hint.compare_exchange_weak(seen, bytes, std::memory_order_relaxed)) {
+// ---- the one way into an align call.  Every entry that can run the DP path (sina_hip_align_graphs, _graphs_wsets,
+// _graphs_any, align_family_batches, sina_hip_debug_mesh, _debug_mesh_wide) holds one for the call: it takes the
+// context's mutex and deactivates both in-place counts, so a call that ends early, or an entry that counts nothing (the
+// debug entries), has counted nothing and the staged getters give NULL.  begin() then activates what the entry may
+// count and this call does count, for its nq queries: the pairs if their switch is on, the call assembles and the store
+// has a helix map; the identity by identity_plan.h's rule -- only the entries that bring families to the device may.
+enum { kMayCountPairs = 1, kMayCountIdentity = 2 };
+struct align_call {
+    sina_hip_ctx *c;
+    std::lock_guard<std::mutex> lk;
+    explicit align_call(sina_hip_ctx *c_) : c(c_), lk(c_->mu) {
+        for (auto &ic : c->inplace) ic.active = false;
     }
-    memset(c->h_pc.p, 0, bytes);
-    c->pc_active = true;
+    int begin(int may, const sina_hip_align_params *p, uint32_t nq) {
+        const bool assemble = p && p->assemble;
+        const bool counts[kNumInplace] = {
+            (may & kMayCountPairs) && c->inplace[kInplacePairs].on && assemble && nq != 0 && c->st->n_pair_ent != 0,
+            identity_call_counts(c->inplace[kInplaceIdentity].on, assemble, (may & kMayCountIdentity) != 0, nq)};
+        if (counts[kInplacePairs] || counts[kInplaceIdentity]) SH_CHECK(hipSetDevice(c->device));  // (pinned memory)
+        for (int i = 0; i < kNumInplace; i++)
+            if (c->inplace[i].begin(counts[i], nq)) return 1;
+        return 0;
+    }
+};
+
+// ---- the counters' readers, under the context's mutex: what the public getters are shims over (they check their
+// arguments and keep their own messages).  b: null for a kernel whose record has no second volume.
+inline int read_use(sina_hip_ctx *c, kernel_use k, double *ms, uint64_t *a, uint64_t *b, uint64_t *launches) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    const KernelUse &u = c->use[k];
+    *ms = u.ms;
+    *a = u.a;
+    if (b) *b = u.b;
+    *launches = u.launches;
     return 0;
 }
-
-// ---- the family identity of an align call (sina_hip_align_count_identity).  The entries that bring families to the
-// device (align_family_batches) call this for their nq queries; the call counts by identity_plan.h's rule, and then
-// the pinned rows are there for the whole call and zero.  Every other align entry clears id_active: the rows of the
-// call before are forgotten (sina_hip_staged_identity: NULL).
-inline int identity_inplace_begin(sina_hip_ctx *c, const sina_hip_align_params *p, uint32_t nq) {
-    c->id_active = false;
-    if (!identity_call_counts(c->count_identity, p && p->assemble, true, nq)) return 0;
-    const size_t bytes = identity_row_bytes(nq);
-    SH_CHECK(hipSetDevice(c->device));
-    if (c->h_id.reserve(bytes)) return 1;
-    size_t seen = c->st->id_rows_hint.load(std::memory_order_relaxed);
-    while (bytes > seen && !c->st->id_rows_hint.compare_exchange_weak(seen, bytes, std::memory_order_relaxed)) {
-    }
-    memset(c->h_id.p, 0, bytes);
-    c->id_active = true;
+inline int read_path_queries(sina_hip_ctx *c, slow_path path, uint64_t *n) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    *n = c->path_queries[path];
     return 0;
 }
 }  // namespace sina_hip

@@ -70,9 +70,10 @@ int reserve_launch_buffers(sina_hip_ctx *c, const DpPlan &pl, const DpLaunch &l,
     if (c->spill.reserve(std::max<uint64_t>(sums.spill_rows, 1) * 8 * (uint64_t)pl.geom.Lp()) ||
         c->edge.reserve(std::max<uint64_t>(1, (uint64_t)(pl.geom.T / 64 - 1) * sums.edge_entries) * sizeof(EdgeRec)) ||
         c->res.reserve(sizeof(DpResult) * l.bq) || c->out.reserve(sizeof(sina_hip_align_out) * l.bq) ||
-        c->out_pos.reserve(4 * std::max<uint64_t>(l.nqm, 1)) || (c->pc_active && c->pc_out.reserve(24 * (size_t)l.bq)) ||
-        (c->id_active && c->id_out.reserve(identity_row_bytes(l.bq))))
+        c->out_pos.reserve(4 * std::max<uint64_t>(l.nqm, 1)))
         return 1;
+    for (InplaceCount &ic : c->inplace)
+        if (ic.reserve(l.bq)) return 1;
     if (l.want_dbg_value && c->dbg.reserve(4 * sums.tb_cells)) return 1;
     return 0;
 }
@@ -195,30 +196,28 @@ int choose_bound(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const s
     return 0;
 }
 
-// The pair count of a call that counts (ctx.h, pair_inplace_begin): right behind the assembly, on its stream, over the
-// words it left.  Like launch_assemble it takes no part in the FIFO's dry signal -- the DP kernel gives that --, and
-// ev[2] (the walk's and the assembly's end) to ev[12] is its own time.
-static int launch_pair_count(sina_hip_ctx *c, const BtArgs &b, hipStream_t s) {
-    if (!c->pc_active) return 0;
-    if (launch_pair_count_assembled(b, c->st->pair_ent.p, c->st->n_pair_ent, c->pc_out.as<uint32_t>(), s)) return 1;
-    SH_CHECK(hipEventRecord(c->ev[12], s));
-    return 0;
-}
-
-// The family identity of a call that counts (ctx.h, identity_inplace_begin): behind the assembly -- and behind the
-// in-place pair count when that runs -- on their stream, over the words the assembly left.  No part in the FIFO's dry
-// signal either; ev[12] if the pair count ran, else ev[2], to ev[13] is its own time.
-// Ordering: the kernel reads g_fam_ids / g_fam_off as the chunk's build uploaded them, and the next chunk's build
-// uploads over them.  That upload is issued by this host thread, and only after run_dp_device has returned for the
+// The in-place counts of a call that counts them (ctx.h, align_call): right behind the assembly, on its stream, over
+// the words it left -- the pair count, then the family identity.  Like launch_assemble they take no part in the FIFO's
+// dry signal -- the DP kernel gives that --, and each records its own event behind its kernel: from the event before
+// it (ev[2], the walk's and the assembly's end, or the event of the count that ran before) to that one is its own time
+// (account_launch).
+// Ordering: the identity kernel reads g_fam_ids / g_fam_off as the chunk's build uploaded them, and the next chunk's
+// build uploads over them.  That upload is issued by this host thread, and only after run_dp_device has returned for the
 // chunk's last range: in the chained branch heavy_launch::done() has the host wait for an event recorded on the FIFO
 // stream BEHIND this kernel, in the other branch the kernel goes to stream_dp and fetch_results waits for that stream
 // -- either way the kernel has ended before the range's results are down, and the context's mutex keeps every other
 // call off these buffers meanwhile.  The uploads between the build and the chunk's last range (qd, qmask, wset,
 // order, scout values) go to other buffers.
-static int launch_identity(sina_hip_ctx *c, const BtArgs &b, const DpLaunch &l, hipStream_t s) {
-    if (!c->id_active) return 0;
-    if (launch_family_identity(c, b, l.fam_ncap, b.asm_cap, c->id_out.as<uint32_t>(), s)) return 1;
-    SH_CHECK(hipEventRecord(c->ev[13], s));
+static int launch_inplace_counts(sina_hip_ctx *c, const BtArgs &b, const DpLaunch &l, hipStream_t s) {
+    InplaceCount &pc = c->inplace[kInplacePairs], &id = c->inplace[kInplaceIdentity];
+    if (pc.active) {
+        if (launch_pair_count_assembled(b, c->st->pair_ent.p, c->st->n_pair_ent, pc.rows.as<uint32_t>(), s)) return 1;
+        SH_CHECK(hipEventRecord(c->ev[pc.ev], s));
+    }
+    if (id.active) {
+        if (launch_family_identity(c, b, l.fam_ncap, b.asm_cap, id.rows.as<uint32_t>(), s)) return 1;
+        SH_CHECK(hipEventRecord(c->ev[id.ev], s));
+    }
     return 0;
 }
 
@@ -253,8 +252,7 @@ int launch_dp_and_walk(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_p
             if (launch_backtrack(b, hl.stream())) return 1;
             if (p->assemble && launch_assemble(b, hl.stream())) return 1;
             SH_CHECK(hipEventRecord(c->ev[2], hl.stream()));
-            if (p->assemble && launch_pair_count(c, b, hl.stream())) return 1;
-            if (p->assemble && launch_identity(c, b, l, hl.stream())) return 1;
+            if (p->assemble && launch_inplace_counts(c, b, l, hl.stream())) return 1;
             bt_done = true;
         }
         if (hl.done()) return 1;
@@ -263,14 +261,13 @@ int launch_dp_and_walk(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_p
         if (launch_backtrack(b, s)) return 1;
         if (p->assemble && launch_assemble(b, s)) return 1;
         SH_CHECK(hipEventRecord(c->ev[2], s));
-        if (p->assemble && launch_pair_count(c, b, s)) return 1;
-        if (p->assemble && launch_identity(c, b, l, s)) return 1;
+        if (p->assemble && launch_inplace_counts(c, b, l, s)) return 1;
     }
     return 0;
 }
 
 // (h_out_pos was sized for the whole call by the entry point; this range's columns go to their place in it -- and so
-// do its pair counters in h_pc, if the call counts)
+// do its rows of the in-place counts, InplaceCount::copy, if the call counts them)
 int fetch_results(sina_hip_ctx *c, const DpLaunch &l) {
     hipStream_t s = c->stream_dp;
     if (c->h_out.reserve(sizeof(sina_hip_align_out) * l.bq) || c->h_res.reserve(sizeof(DpResult) * l.bq)) return 1;
@@ -278,10 +275,8 @@ int fetch_results(sina_hip_ctx *c, const DpLaunch &l) {
     SH_CHECK(hipMemcpyAsync(c->h_out.p, c->out.p, sizeof(sina_hip_align_out) * l.bq, hipMemcpyDeviceToHost, s));
     SH_CHECK(hipMemcpyAsync(c->h_res.p, c->res.p, sizeof(DpResult) * l.bq, hipMemcpyDeviceToHost, s));
     SH_CHECK(hipMemcpyAsync(staged_pos, c->out_pos.p, 4 * l.nqm, hipMemcpyDeviceToHost, s));
-    if (c->pc_active)
-        SH_CHECK(hipMemcpyAsync(c->h_pc.as<uint32_t>() + 6 * (size_t)l.q_base, c->pc_out.p, 24 * (size_t)l.bq, hipMemcpyDeviceToHost, s));
-    if (c->id_active)
-        SH_CHECK(hipMemcpyAsync(c->h_id.as<uint32_t>() + 2 * (size_t)l.q_base, c->id_out.p, identity_row_bytes(l.bq), hipMemcpyDeviceToHost, s));
+    for (InplaceCount &ic : c->inplace)
+        if (ic.copy(l.q_base, l.bq, s)) return 1;
     SH_CHECK(wait_stream(c, s));
     memcpy(l.out, c->h_out.p, sizeof(sina_hip_align_out) * l.bq);
     if (l.out_pos) memcpy(l.out_pos, staged_pos, 4 * l.nqm);
@@ -311,22 +306,25 @@ int account_launch(sina_hip_ctx *c, const DpPlan &pl, const DpLaunch &l, uint64_
     st.dp_busy_ms += ms - shared;
     SH_CHECK(hipEventElapsedTime(&ms, c->ev[1], c->ev[2]));
     st.backtrack_ms += ms;
-    if (c->pc_active) {  // (the context's own counters: its caller holds its mutex)
-        SH_CHECK(hipEventElapsedTime(&ms, c->ev[2], c->ev[12]));
-        c->pc_ms += ms;
-        c->pc_launches++;
-        for (uint32_t q = 0; q < l.bq; q++) c->pc_seqs += (l.out[q].status == 0 && l.out[q].assembled != 0) ? 1u : 0u;
+    // (the context's own counters: its caller holds its mutex.  An in-place kernel's time runs from the last event
+    // recorded before it -- the assembly's, or the count's that ran before -- to its own)
+    int ev_before = 2;
+    for (const InplaceCount &ic : c->inplace) {
+        if (!ic.active) continue;
+        SH_CHECK(hipEventElapsedTime(&ms, c->ev[ev_before], c->ev[ic.ev]));
+        c->use[ic.kernel].add(ms, 0, 0, 1);
+        ev_before = ic.ev;
     }
-    if (c->id_active) {  // (likewise)
-        SH_CHECK(hipEventElapsedTime(&ms, c->ev[c->pc_active ? 12 : 2], c->ev[13]));
-        c->id_ms += ms;
-        c->id_launches++;
+    // (their volumes: the assembled queries, and for the identity those queries' family pairs)
+    auto assembled = [&](uint32_t q) { return l.out[q].status == 0 && l.out[q].assembled != 0; };
+    if (c->inplace[kInplacePairs].active)
+        for (uint32_t q = 0; q < l.bq; q++) c->use[kUsePairsInplace].a += assembled(q) ? 1u : 0u;
+    if (c->inplace[kInplaceIdentity].active)
         for (uint32_t q = 0; q < l.bq; q++)
-            if (l.out[q].status == 0 && l.out[q].assembled != 0) {
-                c->id_seqs++;
-                c->id_pairs += l.fam_off ? l.fam_off[q + 1] - l.fam_off[q] : 0;
+            if (assembled(q)) {
+                c->use[kUseIdentityInplace].a++;
+                c->use[kUseIdentityInplace].b += l.fam_off ? l.fam_off[q + 1] - l.fam_off[q] : 0;
             }
-    }
     st.dp_cells += cells;
     st.dp_launches++;
     st.dp_rows += sw.rows_nominal;
@@ -377,10 +375,8 @@ int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {
     const uint32_t *weight_set = f.weight_set;
     uint32_t n_sets = f.n_sets;
     if (check_weight_sets(f.who, p, &weight_set, &n_sets, nq)) return 1;
-    std::lock_guard<std::mutex> lk(c->mu);
+    align_call call(c);  // (nothing counts until call.begin below: a call that ends early has counted nothing)
     sina_hip_hint_guard hints(c);
-    c->pc_active = false;  // (until pair_inplace_begin says otherwise: a call that ends early has counted nothing)
-    c->id_active = false;  // (identity_inplace_begin, likewise)
     if (!c->st->have_refs) SH_FAIL(w + ": upload references first");
     if (nq == 0) return 0;
     SH_CHECK(hipSetDevice(c->device));
@@ -400,7 +396,7 @@ int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {
     const int Lp = pl.geom.Lp();
     if (upload_weights(c, p, n_sets)) return 1;
     if (c->h_out_pos.reserve(4 * std::max<uint64_t>(qoff[nq] - qoff[0], 1))) return 1;
-    if (pair_inplace_begin(c, p, nq) || identity_inplace_begin(c, p, nq)) return 1;
+    if (call.begin(kMayCountPairs | kMayCountIdentity, p, nq)) return 1;
     // (SINA_HIP_TEST=dp_range_q=N: at most N queries per DP launch range, so that a small call takes several;
     // fam_chunk_q=N: at most N queries per build chunk, so that it spans several builds)
     const uint32_t range_q = (uint32_t)strtoul(test_knob("dp_range_q").c_str(), nullptr, 10);

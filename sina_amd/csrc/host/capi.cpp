@@ -28,6 +28,16 @@ int fail(const std::exception &e) {
     g_err = e.what();
     return 1;
 }
+// The exception boundary of an exported function: f(), then 0 -- or 1, with what f threw kept for sina_host_last_error
+template <class F>
+int guarded(F &&f) {
+    try {
+        f();
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+}
 
 struct result {
     // (between runs a result keeps its heap blocks: fresh memory per query is a page fault per query)
@@ -269,45 +279,33 @@ const char *sina_host_last_error(void) { return g_err.c_str(); }
 
 int sina_host_store_from_packed(const char *key, const uint32_t *ab, const uint64_t *off, uint32_t n, uint32_t width,
                                 int device) {
-    try {
+    return guarded([&] {
         auto s = reference_store::from_packed(key, ab, off, n, width);
         s->set_device(device);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 // A store of a rank other than 0: its device buffers are allocated like rank 0's
 // (sina_hip_store_alloc_like) and filled by the start-up broadcast instead of an upload of its own.
 int sina_host_store_expect_broadcast(const char *key) {
-    try {
+    return guarded([&] {
         reference_store::get(key)->expect_broadcast();
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 int sina_host_store_close(const char *key) {
-    try {
+    return guarded([&] {
         for (int k = 1; k <= 12; k++)
             for (int nf = 0; nf < 2; nf++) kmer_search::release_kmer_search(key, k, nf != 0);
         reference_store::close(key);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 int sina_host_add_filter(const char *key, const char *name, const float *weights, uint32_t n) {
-    try {
+    return guarded([&] {
         reference_store::get(key)->getAlignmentStats().emplace_back(std::string(name),
                                                                     std::vector<float>(weights, weights + n));
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 // Test hook, no device involved: the --auto-filter-field vote (autofilter_vote, stages.h) of a family given as
@@ -316,7 +314,7 @@ int sina_host_add_filter(const char *key, const char *name, const float *weights
 // threshold stands for famfinder's --auto-filter-threshold as it is set.
 int sina_host_autofilter_vote(const char *key, const uint32_t *ids, uint32_t n, const char *field, const char *prefix,
                               float threshold, int *chosen, char *name_out, uint32_t name_cap) {
-    try {
+    return guarded([&] {
         auto st = reference_store::get(key);
         std::vector<std::string> names, fields;
         for (const alignment_stats &as : st->getAlignmentStats()) names.push_back(as.getName());
@@ -327,10 +325,7 @@ int sina_host_autofilter_vote(const char *key, const uint32_t *ids, uint32_t n, 
         const int best = autofilter_vote(names, fields, prefix, threshold < 0.f ? famfinder::auto_filter_threshold() : threshold);
         if (chosen) *chosen = best;
         if (name_out && name_cap) snprintf(name_out, name_cap, "%s", best >= 0 ? names[(size_t)best].c_str() : "");
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 // Device context of a store (creates it and uploads the references on first use): lets a
@@ -345,101 +340,74 @@ void *sina_host_store_ctx(const char *key) {
     }
 }
 int sina_host_store_slow_path_queries(const char *key, uint64_t *wide, uint64_t *long_kmer) {
-    try {
+    return guarded([&] {
         reference_store::get(key)->slow_path_queries(wide, long_kmer);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 int sina_host_store_big_select_queries(const char *key, uint64_t *n) {
-    try {
+    return guarded([&] {
         reference_store::get(key)->big_select_queries(n);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 int sina_host_store_match_stats(const char *key, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches) {
-    try {
+    return guarded([&] {
         reference_store::get(key)->match_stats(kernel_ms, pairs, cand_bases, launches);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // search_filter's device-rank on this store: queries ranked on the device, queries sent back to the host path, and the
 // rank kernel's time and volume (sina_hip_rank_stats) on its contexts -- between runs, like the counters above
 int sina_host_store_rank_stats(const char *key, uint64_t *ranked, uint64_t *fallen_back, double *kernel_ms, uint64_t *pairs,
                                uint64_t *cand_bases, uint64_t *launches) {
-    try {
+    return guarded([&] {
         reference_store::get(key)->rank_stats(ranked, fallen_back, kernel_ms, pairs, cand_bases, launches);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // The helix map of a store (reference_store::set_pairs): pairs[i] = partner column of column i, 0 = unpaired; n == 0 or
 // all zero removes it.  Before the stages run, like sina_host_add_filter.
 int sina_host_store_set_pairs(const char *key, const uint32_t *pairs, uint32_t n) {
-    try {
+    return guarded([&] {
         if (!pairs && n) throw std::logic_error("store_set_pairs: null argument");
         reference_store::get(key)->set_pairs(pairs, n);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // ... and the pair-count kernel's time and volume on the store's contexts (sina_hip_pair_stats) -- between runs
 int sina_host_store_pair_stats(const char *key, double *kernel_ms, uint64_t *sequences, uint64_t *entries_visited, uint64_t *launches) {
-    try {
+    return guarded([&] {
         reference_store::get(key)->pair_stats(kernel_ms, sequences, entries_visited, launches);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // the aligner's device-bps on this store: trays scored from the counters their align call brought back, and the
 // in-place kernel's time and volume (sina_hip_pair_inplace_stats) on its contexts -- between runs
 int sina_host_store_pair_inplace_stats(const char *key, uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *launches) {
-    try {
+    return guarded([&] {
         if (!trays || !kernel_ms || !sequences || !launches) throw std::logic_error("store_pair_inplace_stats: null argument");
         reference_store::get(key)->pair_inplace_stats(trays, kernel_ms, sequences, launches);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // the aligner's device-idty on this store: trays that took their identity from the row their align call brought back,
 // and the in-place kernel's time and volume (sina_hip_identity_inplace_stats) on its contexts -- between runs
 int sina_host_store_identity_inplace_stats(const char *key, uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs,
                                            uint64_t *launches) {
-    try {
+    return guarded([&] {
         if (!trays || !kernel_ms || !sequences || !pairs || !launches) throw std::logic_error("store_identity_inplace_stats: null argument");
         reference_store::get(key)->identity_inplace_stats(trays, kernel_ms, sequences, pairs, launches);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // The host walk (cseq_base::calcPairScore), no device involved, of an aligned string.  counts6 (optional): num, AG,
 // AU, CG, GG, GU.
 int sina_host_pair_score(const char *aligned_text, const uint32_t *pairs, uint32_t n, float *score, uint32_t *counts6) {
-    try {
+    return guarded([&] {
         if (!aligned_text || (!pairs && n) || !score) throw std::logic_error("pair_score: null argument");
         const cseq c("", aligned_text);
         *score = c.calcPairScore(std::vector<uint32_t>(pairs, pairs + n), counts6);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // ... and of a batch of sequences as packed words, taken as they are (mask 0, equal or descending columns included; q_ab /
 // q_off as sina_hip_pair_counts takes them), one after the other on the calling thread; counts6 (optional): [nq][6];
 // seconds (optional): the walk's wall time, the map already in place (tools/perf_bps.py)
 int sina_host_pair_scores_packed(const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, const uint32_t *pairs, uint32_t n,
                                  float *scores, uint32_t *counts6, double *seconds) {
-    try {
+    return guarded([&] {
         if (!q_ab || !q_off || (!pairs && n) || !scores) throw std::logic_error("pair_scores_packed: null argument");
         const std::vector<uint32_t> map(pairs, pairs + n);
         std::vector<cseq> seqs(nq);
@@ -448,10 +416,7 @@ int sina_host_pair_scores_packed(const uint32_t *q_ab, const uint64_t *q_off, ui
         const auto t0 = std::chrono::steady_clock::now();
         for (uint32_t q = 0; q < nq; q++) scores[q] = seqs[q].calcPairScore(map, counts6 ? counts6 + 6 * (size_t)q : nullptr);
         if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // pair_score_from_counts and the attribute made of it, for tests
 float sina_host_pair_score_from_counts(const uint32_t *counts6, int *attr) {
@@ -462,7 +427,7 @@ float sina_host_pair_score_from_counts(const uint32_t *counts6, int *attr) {
 // Log::printer alone (no device): n aligned strings as trays seq0, seq1, ... through one log_printer, in order; the
 // reports' text into out (truncated at cap), the run's avg_bps.  The helix map is the one of the aligner's "db".
 int sina_host_log_reports(const char *const *aligned_texts, uint32_t n, char *out, uint32_t cap, double *avg_bps) {
-    try {
+    return guarded([&] {
         log_printer lp(false);
         std::ostringstream text;
         for (uint32_t i = 0; i < n; i++) {
@@ -476,18 +441,12 @@ int sina_host_log_reports(const char *const *aligned_texts, uint32_t n, char *ou
         }
         if (out && cap) snprintf(out, cap, "%s", text.str().c_str());
         if (avg_bps) *avg_bps = lp.totals().avg_bps;
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 int sina_host_store_build_index(const char *key, unsigned k, int nofast) {
-    try {
+    return guarded([&] {
         reference_store::get(key)->ensure_index(k, nofast != 0);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // sina -i in.fasta -o out.fasta --db <key> [--search] [--show-dist]: FASTA reader -> famfinder -> aligner
 // [-> search_filter] -> log printer -> FASTA writer, in batches of `batch` sequences.  The stage
@@ -557,7 +516,7 @@ struct fasta_run {
 // the hand-over serial, the serial one is SINA's node after node, which the tests compare the staged one with.
 static int run_fasta(const char *in_path, const char *out_path, const char *log_path, int do_search, int show_dist,
                      uint32_t batch, double *summary7, bool staged) {
-    try {
+    return guarded([&] {
         fasta_run r(in_path, out_path, log_path, do_search, show_dist);
         if (batch == 0) batch = 1024;
         std::vector<log_printer::report> reports;
@@ -602,10 +561,7 @@ static int run_fasta(const char *in_path, const char *out_path, const char *log_
             run.then(2, "sink", 1, sink_staged).staged();
         } else run.then(2, "sink", 1, sink_serial).inline_();
         r.finish(summary7);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 int sina_host_run_fasta_serial(const char *in_path, const char *out_path, const char *log_path, int do_search,
@@ -624,7 +580,7 @@ double sina_host_last_avg_bps(void) { return g_last_avg_bps.load(); }
 // FASTA reader + writer alone (no GPU): reads every sequence of in_path and writes it back, the
 // input sequence standing in for the aligned one; returns the counts.  For CPU tests of the I/O rules.
 int sina_host_fasta_roundtrip(const char *in_path, const char *out_path, int *n_read, int *n_skipped) {
-    try {
+    return guarded([&] {
         rw_fasta::reader rd(in_path);
         rw_fasta::writer wr(out_path);
         int n = 0;
@@ -639,16 +595,13 @@ int sina_host_fasta_roundtrip(const char *in_path, const char *out_path, int *n_
         wr.flush();
         *n_read = n;
         *n_skipped = rd.skipped();
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 // .sidx <-> CSR without a GPU (tests): load into caller buffers / store from caller arrays
 int sina_host_sidx_load(const char *path, unsigned k, int nofast, uint32_t *n_sequences, uint32_t *offsets,
                         uint32_t *ids, uint64_t ids_cap, uint64_t *n_ids) {
-    try {
+    return guarded([&] {
         std::vector<std::string> names;
         std::vector<uint32_t> off, id;
         std::string why;
@@ -658,42 +611,30 @@ int sina_host_sidx_load(const char *path, unsigned k, int nofast, uint32_t *n_se
         if (id.size() > ids_cap) throw std::runtime_error("sidx_load: ids buffer too small");
         memcpy(offsets, off.data(), 4 * off.size());
         if (!id.empty()) memcpy(ids, id.data(), 4 * id.size());
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 int sina_host_sidx_store(const char *path, unsigned k, int nofast, uint32_t n_sequences, const uint32_t *offsets,
                          const uint32_t *ids, uint64_t n_ids) {
-    try {
+    return guarded([&] {
         std::vector<std::string> names;
         for (uint32_t i = 0; i < n_sequences; i++) names.push_back("ref" + std::to_string(i));
         sidx_store(path, k, nofast != 0, names, std::vector<uint32_t>(offsets, offsets + ((size_t)1 << (2 * k)) + 1),
                    std::vector<uint32_t>(ids, ids + n_ids));
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // opens an aligned-FASTA database by path (its index is cached in <path minus extension>.sidx)
 int sina_host_store_open(const char *path, int device) {
-    try {
+    return guarded([&] {
         auto s = reference_store::get(path);
         s->set_device(device);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // the same with the sequences numbered as the reference numbers an ARB database's (host/id_order.h)
 int sina_host_store_open_arb_order(const char *path, int device) {
-    try {
+    return guarded([&] {
         auto s = reference_store::open(path, true);
         s->set_device(device);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 // order[i] = database position of the sequence the reference gives id i (query_arb.cpp:160,470-474,732-739);
 // hashes[j] (optional) = boost::hash<std::string> of names[j]; returns the number of ids (distinct names)
@@ -732,12 +673,9 @@ const char *sina_host_store_index_origin(const char *key) {
 // After the index arrived by broadcast (sina_hip_store_alloc_like + RCCL): tell the store
 // not to rebuild it.
 int sina_host_store_index_ready(const char *key, unsigned k, int nofast) {
-    try {
+    return guarded([&] {
         reference_store::get(key)->adopt_index(k, nofast != 0);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 int sina_host_reset_options(void) {
@@ -750,16 +688,13 @@ int sina_host_reset_options(void) {
 
 // field of a reference sequence (stands in for the ARB database fields the search stage loads)
 int sina_host_store_set_attr(const char *key, uint32_t id, const char *field, const char *value) {
-    try {
+    return guarded([&] {
         reference_store::get(key)->set_attr(id, field, value);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 int sina_host_set_option(const char *stage, const char *name, const char *value) {
-    try {
+    return guarded([&] {
         if (!strcmp(stage, "famfinder")) famfinder::set_option(name, value);
         else if (!strcmp(stage, "aligner")) aligner::set_option(name, value);
         else if (!strcmp(stage, "search")) search_filter::set_option(name, value);
@@ -767,10 +702,7 @@ int sina_host_set_option(const char *stage, const char *name, const char *value)
         else if (!strcmp(stage, "host") && !strcmp(name, "threads")) set_host_threads((unsigned)atoi(value));
         else if (!strcmp(stage, "host") && !strcmp(name, "dedup")) set_batch_dedup(atoi(value) != 0);
         else throw std::logic_error(std::string("unknown stage ") + stage);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 // The driver allocates and frees tens of MB of trays per batch: keep what the allocator got from the
@@ -827,7 +759,7 @@ void sina_host_profile_mark(int which) { host_profile_mark(which == 0 ? "MARK:ti
 // as the reader stage would hand it over.
 template <class Fill>
 static int run_queries(pipeline *p, uint32_t nq, const uint64_t *qoff, uint32_t batch, uint32_t inflight, Fill &&fill) {
-    try {
+    return guarded([&] {
         host_profile_mark("MARK:run-entered");
         if (batch == 0) batch = nq ? nq : 1;
         if (p->chunk_q != batch) p->chunks.clear();  // (chunks follow the batch size)
@@ -914,10 +846,7 @@ static int run_queries(pipeline *p, uint32_t nq, const uint64_t *qoff, uint32_t 
         p->al_s = al_ns.load() * 1e-9;
         p->sf_s = sf_ns.load() * 1e-9;
         if (err) std::rethrow_exception(err);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 extern "C" {
@@ -1116,7 +1045,7 @@ const char *sina_host_profile(int reset) {
 int sina_host_build_graph(const char *key, const uint32_t *ids, uint32_t F, float fs_weight, uint32_t *n_nodes,
                           uint32_t *n_edges, uint32_t *pos, uint8_t *mask, float *weight, uint32_t *pred_off,
                           uint32_t *pred, uint32_t *succ_minpos, uint32_t cap_nodes, uint32_t cap_edges) {
-    try {
+    return guarded([&] {
         auto st = reference_store::get(key);
         std::vector<const cseq *> fam;
         for (uint32_t i = 0; i < F; i++) fam.push_back(&st->getCseq(ids[i]));
@@ -1131,10 +1060,7 @@ int sina_host_build_graph(const char *key, const uint32_t *ids, uint32_t F, floa
         std::copy(g.pred_off.begin(), g.pred_off.end(), pred_off);
         std::copy(g.pred.begin(), g.pred.end(), pred);
         std::copy(g.succ_minpos.begin(), g.succ_minpos.end(), succ_minpos);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 // the family as a profile (--fs-no-graph): columns and the match-term table the aligner hands to the device
@@ -1142,7 +1068,7 @@ int sina_host_build_graph(const char *key, const uint32_t *ids, uint32_t F, floa
 int sina_host_build_profile(const char *key, const uint32_t *ids, uint32_t F, float match, float mismatch, float gap,
                             float gap_ext, uint32_t *n_nodes, uint32_t *pos, float *score16, float *self16,
                             uint32_t cap_nodes) {
-    try {
+    return guarded([&] {
         auto st = reference_store::get(key);
         std::vector<const cseq *> fam;
         for (uint32_t i = 0; i < F; i++) fam.push_back(&st->getCseq(ids[i]));
@@ -1153,17 +1079,14 @@ int sina_host_build_profile(const char *key, const uint32_t *ids, uint32_t F, fl
         std::copy(g.pos.begin(), g.pos.end(), pos);
         std::copy(g.score16.begin(), g.score16.end(), score16);
         profile_self_scores(match, mismatch, gap, gap_ext, self16);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 // cseq_comparator on two aligned strings, for CPU-only tests against the reference's KAT table
 // (src/unit_tests/cseq_comparator_test.cpp); also returns the six counters
 int sina_host_compare(const char *a_aligned, const char *b_aligned, int iupac, int dist, int cover, int filter_lc,
                       float *score, int32_t *counts6) {
-    try {
+    return guarded([&] {
         cseq a("", a_aligned), b("", b_aligned);
         cseq_comparator cmp((CMP_IUPAC_TYPE)iupac, (CMP_DIST_TYPE)dist, (CMP_COVER_TYPE)cover, filter_lc != 0);
         sina_hip_match_counts m;
@@ -1171,10 +1094,7 @@ int sina_host_compare(const char *a_aligned, const char *b_aligned, int iupac, i
         *score = cmp.score(m);
         const int32_t v[6] = {m.only_a_overhang, m.only_b_overhang, m.only_a, m.only_b, m.match, m.mismatch};
         memcpy(counts6, v, sizeof v);
-        return 0;
-    } catch (const std::exception &e) {
-        return fail(e);
-    }
+    });
 }
 
 // Self-checks of the host containers' round-6 machinery, for the CPU suite (no GPU, no store): a "dense" sequence

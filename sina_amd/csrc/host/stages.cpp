@@ -570,51 +570,49 @@ void reference_store::reserve_workers(device_role role, unsigned n) {
     }
     for (sina_hip_ctx *c : pool) hip_check(sina_hip_prewarm(c, (int)role), "sina_hip_prewarm");
 }
-void reference_store::slow_path_queries(uint64_t *wide, uint64_t *long_kmer) {
+// (device() first: it takes gpu_mu itself)
+template <class F>
+void reference_store::for_each_context(F &&f) {
     sina_hip_ctx *root = device();
     std::lock_guard<std::mutex> lk(gpu_mu);
+    f(root);
+    for (auto &pool : idle_forks)
+        for (sina_hip_ctx *c : pool) f(c);
+}
+template <class Get>
+void reference_store::sum_kernel_use(const char *what, Get &&get, double *kernel_ms, uint64_t *a, uint64_t *b, uint64_t *launches) {
+    *kernel_ms = 0;
+    *a = *b = *launches = 0;
+    for_each_context([&](sina_hip_ctx *c) {
+        double ms = 0;
+        uint64_t ca = 0, cb = 0, l = 0;
+        hip_check(get(c, &ms, &ca, &cb, &l), what);
+        *kernel_ms += ms;
+        *a += ca;
+        *b += cb;
+        *launches += l;
+    });
+}
+void reference_store::slow_path_queries(uint64_t *wide, uint64_t *long_kmer) {
     *wide = *long_kmer = 0;
-    auto add = [&](sina_hip_ctx *c) {
+    for_each_context([&](sina_hip_ctx *c) {
         uint64_t w = 0, l = 0;
         hip_check(sina_hip_wide_queries(c, &w), "sina_hip_wide_queries");
         hip_check(sina_hip_long_queries(c, &l), "sina_hip_long_queries");
         *wide += w;
         *long_kmer += l;
-    };
-    add(root);
-    for (auto &pool : idle_forks)
-        for (sina_hip_ctx *c : pool) add(c);
+    });
 }
 void reference_store::big_select_queries(uint64_t *n) {
-    sina_hip_ctx *root = device();
-    std::lock_guard<std::mutex> lk(gpu_mu);
     *n = 0;
-    auto add = [&](sina_hip_ctx *c) {
+    for_each_context([&](sina_hip_ctx *c) {
         uint64_t b = 0;
         hip_check(sina_hip_big_select_queries(c, &b), "sina_hip_big_select_queries");
         *n += b;
-    };
-    add(root);
-    for (auto &pool : idle_forks)
-        for (sina_hip_ctx *c : pool) add(c);
+    });
 }
 void reference_store::match_stats(double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches) {
-    sina_hip_ctx *root = device();
-    std::lock_guard<std::mutex> lk(gpu_mu);
-    *kernel_ms = 0;
-    *pairs = *cand_bases = *launches = 0;
-    auto add = [&](sina_hip_ctx *c) {
-        double ms = 0;
-        uint64_t p = 0, b = 0, l = 0;
-        hip_check(sina_hip_match_stats(c, &ms, &p, &b, &l), "sina_hip_match_stats");
-        *kernel_ms += ms;
-        *pairs += p;
-        *cand_bases += b;
-        *launches += l;
-    };
-    add(root);
-    for (auto &pool : idle_forks)
-        for (sina_hip_ctx *c : pool) add(c);
+    sum_kernel_use("sina_hip_match_stats", sina_hip_match_stats, kernel_ms, pairs, cand_bases, launches);
 }
 bool reference_store::name_order_ready() {
     int state = name_order_state.load(std::memory_order_acquire);
@@ -641,24 +639,9 @@ bool reference_store::name_order_ready() {
 }
 void reference_store::rank_stats(uint64_t *ranked, uint64_t *fallen_back, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases,
                                  uint64_t *launches) {
-    sina_hip_ctx *root = device();
-    std::lock_guard<std::mutex> lk(gpu_mu);
+    sum_kernel_use("sina_hip_rank_stats", sina_hip_rank_stats, kernel_ms, pairs, cand_bases, launches);
     *ranked = n_ranked.load(std::memory_order_relaxed);
     *fallen_back = n_rank_host.load(std::memory_order_relaxed);
-    *kernel_ms = 0;
-    *pairs = *cand_bases = *launches = 0;
-    auto add = [&](sina_hip_ctx *c) {
-        double ms = 0;
-        uint64_t p = 0, b = 0, l = 0;
-        hip_check(sina_hip_rank_stats(c, &ms, &p, &b, &l), "sina_hip_rank_stats");
-        *kernel_ms += ms;
-        *pairs += p;
-        *cand_bases += b;
-        *launches += l;
-    };
-    add(root);
-    for (auto &pool : idle_forks)
-        for (sina_hip_ctx *c : pool) add(c);
 }
 void reference_store::set_pairs(const uint32_t *pairs, uint32_t n) {
     bool any = false;
@@ -675,59 +658,18 @@ reference_store::pair_map reference_store::pairs() {
     return helix;
 }
 void reference_store::pair_stats(double *kernel_ms, uint64_t *sequences, uint64_t *entries_visited, uint64_t *launches) {
-    sina_hip_ctx *root = device();
-    std::lock_guard<std::mutex> lk(gpu_mu);
-    *kernel_ms = 0;
-    *sequences = *entries_visited = *launches = 0;
-    auto add = [&](sina_hip_ctx *c) {
-        double ms = 0;
-        uint64_t n = 0, e = 0, l = 0;
-        hip_check(sina_hip_pair_stats(c, &ms, &n, &e, &l), "sina_hip_pair_stats");
-        *kernel_ms += ms;
-        *sequences += n;
-        *entries_visited += e;
-        *launches += l;
-    };
-    add(root);
-    for (auto &pool : idle_forks)
-        for (sina_hip_ctx *c : pool) add(c);
+    sum_kernel_use("sina_hip_pair_stats", sina_hip_pair_stats, kernel_ms, sequences, entries_visited, launches);
 }
 void reference_store::pair_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *launches) {
-    sina_hip_ctx *root = device();
-    std::lock_guard<std::mutex> lk(gpu_mu);
+    uint64_t none = 0;  // (this kernel's record has no second volume)
+    sum_kernel_use("sina_hip_pair_inplace_stats",
+                   [](sina_hip_ctx *c, double *ms, uint64_t *a, uint64_t *, uint64_t *l) { return sina_hip_pair_inplace_stats(c, ms, a, l); },
+                   kernel_ms, sequences, &none, launches);
     *trays = n_bp_inplace.load(std::memory_order_relaxed);
-    *kernel_ms = 0;
-    *sequences = *launches = 0;
-    auto add = [&](sina_hip_ctx *c) {
-        double ms = 0;
-        uint64_t n = 0, l = 0;
-        hip_check(sina_hip_pair_inplace_stats(c, &ms, &n, &l), "sina_hip_pair_inplace_stats");
-        *kernel_ms += ms;
-        *sequences += n;
-        *launches += l;
-    };
-    add(root);
-    for (auto &pool : idle_forks)
-        for (sina_hip_ctx *c : pool) add(c);
 }
 void reference_store::identity_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches) {
-    sina_hip_ctx *root = device();
-    std::lock_guard<std::mutex> lk(gpu_mu);
+    sum_kernel_use("sina_hip_identity_inplace_stats", sina_hip_identity_inplace_stats, kernel_ms, sequences, pairs, launches);
     *trays = n_idty_inplace.load(std::memory_order_relaxed);
-    *kernel_ms = 0;
-    *sequences = *pairs = *launches = 0;
-    auto add = [&](sina_hip_ctx *c) {
-        double ms = 0;
-        uint64_t n = 0, p = 0, l = 0;
-        hip_check(sina_hip_identity_inplace_stats(c, &ms, &n, &p, &l), "sina_hip_identity_inplace_stats");
-        *kernel_ms += ms;
-        *sequences += n;
-        *pairs += p;
-        *launches += l;
-    };
-    add(root);
-    for (auto &pool : idle_forks)
-        for (sina_hip_ctx *c : pool) add(c);
 }
 bool reference_store::match_counts_too_wide() {
     if (sina_hip::match_table_bytes(width) <= sina_hip::kMatchMaxLds) return false;

@@ -363,6 +363,12 @@ private:
     bool refs_by_broadcast{false};
     sina_hip_ctx *ctx{nullptr};
     std::vector<sina_hip_ctx *> idle_forks[dev_roles];  // guarded by gpu_mu
+    // f(context) on the root context and on every idle fork, under gpu_mu: what the counters above are summed with ...
+    template <class F>
+    void for_each_context(F &&f);
+    // ... and a kernel's (time, two volumes, launches) summed so; get: its sina_hip_*_stats getter
+    template <class Get>
+    void sum_kernel_use(const char *what, Get &&get, double *kernel_ms, uint64_t *a, uint64_t *b, uint64_t *launches);
     int idx_k{-1};
     bool idx_nofast{false};
     std::string idx_origin;

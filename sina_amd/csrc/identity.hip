@@ -1,6 +1,8 @@
 // --calc-idty where the device assembles the alignment: family_identity_kernel +
 // sina_hip_align_count_identity, sina_hip_staged_identity, sina_hip_identity_inplace_stats.  Launched by dp_launch.hip
-// behind assemble_kernel; the tables and the classification are compare_dev.h's, shared with search.hip and rank.hip.
+// (launch_inplace_counts) behind assemble_kernel; its switch, rows and event are the context's
+// inplace[kInplaceIdentity], its counters use[kUseIdentityInplace] (ctx.h).  The tables and the classification are
+// compare_dev.h's, shared with search.hip and rank.hip.
 //
 // What it computes: for every query of a DP launch range that the device assembled, the best overlap identity of its
 // finished sequence with a member of its family (align_ident_slv, src/align.cpp:443-453: cseq_comparator(
@@ -133,7 +135,7 @@ using namespace sina_hip;
 extern "C" int sina_hip_align_count_identity(sina_hip_ctx *c, int on) {
     if (!c) SH_FAIL("align_count_identity: null ctx");
     std::lock_guard<std::mutex> lk(c->mu);
-    c->count_identity = on != 0;
+    c->inplace[kInplaceIdentity].on = on != 0;
     return 0;
 }
 
@@ -143,15 +145,10 @@ extern "C" const uint32_t *sina_hip_staged_identity(sina_hip_ctx *c) {
         return nullptr;
     }
     std::lock_guard<std::mutex> lk(c->mu);
-    return c->id_active ? c->h_id.as<uint32_t>() : nullptr;
+    return c->inplace[kInplaceIdentity].staged();
 }
 
 extern "C" int sina_hip_identity_inplace_stats(sina_hip_ctx *c, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches) {
     if (!c || !kernel_ms || !sequences || !pairs || !launches) SH_FAIL("identity_inplace_stats: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    *kernel_ms = c->id_ms;
-    *sequences = c->id_seqs;
-    *pairs = c->id_pairs;
-    *launches = c->id_launches;
-    return 0;
+    return read_use(c, kUseIdentityInplace, kernel_ms, sequences, pairs, launches);
 }

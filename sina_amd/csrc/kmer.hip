@@ -1167,8 +1167,8 @@ static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *
             }
         }
         if (*overflow) return 0;
-        if (long_path) c->long_queries += bq;
-        if (big) c->big_select_queries += bq;
+        if (long_path) c->path_queries[kPathLong] += bq;
+        if (big) c->path_queries[kPathBigSelect] += bq;
         if (rk) {  // the range's select is final: its candidates ranked, ids and lengths read where they lie
             uint32_t max_la = 0;
             for (uint32_t q = q0; q < q0 + bq; q++) max_la = std::max<uint32_t>(max_la, (uint32_t)(qoff[q + 1] - qoff[q]));
@@ -1294,7 +1294,7 @@ static int kmer_scores_checked(sina_hip_ctx *c, const uint8_t *qmask, uint32_t q
     SH_CHECK(hipMemcpyAsync(c->qmask.p, qmask, qlen, hipMemcpyHostToDevice, s));
     SH_CHECK(hipMemcpyAsync(c->k_qoff.p, rel, 16, hipMemcpyHostToDevice, s));
     if (kmer_topk_device(c, c->qmask.as<uint8_t>(), c->k_qoff.as<uint64_t>(), 1, 1, std::max<uint32_t>(qlen, 1), true, false, long_path)) return 1;
-    if (long_path) c->long_queries++;
+    if (long_path) c->path_queries[kPathLong]++;
     SH_CHECK(hipMemcpyAsync(scores, c->k_scores.p, (size_t)c->st->n_refs * 2, hipMemcpyDeviceToHost, s));
     SH_CHECK(hipStreamSynchronize(s));
     return 0;
@@ -1350,16 +1350,12 @@ int sina_hip_kmer_scores_any(sina_hip_ctx *c, const uint8_t *qmask, uint32_t qle
 }
 int sina_hip_long_queries(sina_hip_ctx *c, uint64_t *n) {
     if (!c || !n) SH_FAIL("long_queries: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    *n = c->long_queries;
-    return 0;
+    return read_path_queries(c, kPathLong, n);
 }
 
 int sina_hip_big_select_queries(sina_hip_ctx *c, uint64_t *n) {
     if (!c || !n) SH_FAIL("big_select_queries: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    *n = c->big_select_queries;
-    return 0;
+    return read_path_queries(c, kPathBigSelect, n);
 }
 
 int sina_hip_store_view_get(sina_hip_ctx *c, sina_hip_store_view *v) {

@@ -144,10 +144,7 @@ int match_launch(sina_hip_ctx *c, const uint32_t *d_qab, const uint64_t *d_qoff,
                 if (id < c->st->n_refs) bases += c->st->ref_off_host[id + 1] - c->st->ref_off_host[id];
             }
     }
-    c->match_ms += ms;
-    c->match_pairs += pairs;
-    c->match_bases += bases;
-    c->match_launches++;
+    c->use[kUseMatch].add(ms, pairs, bases, 1);
     return 0;
 }
 
@@ -218,10 +215,5 @@ extern "C" int sina_hip_match_count(sina_hip_ctx *c, const uint32_t *q_ab, const
 
 extern "C" int sina_hip_match_stats(sina_hip_ctx *c, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches) {
     if (!c || !kernel_ms || !pairs || !cand_bases || !launches) SH_FAIL("match_stats: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    *kernel_ms = c->match_ms;
-    *pairs = c->match_pairs;
-    *cand_bases = c->match_bases;
-    *launches = c->match_launches;
-    return 0;
+    return read_use(c, kUseMatch, kernel_ms, pairs, cand_bases, launches);
 }

@@ -535,7 +535,7 @@ int run_wide(sina_hip_ctx *c, const sina_hip_graph_batch *g, const uint8_t *qmas
         float dp_ms = 0, bt_ms = 0;
         SH_CHECK(hipEventElapsedTime(&dp_ms, c->ev[0], c->ev[1]));
         SH_CHECK(hipEventElapsedTime(&bt_ms, c->ev[1], c->ev[2]));
-        c->wide_queries += bq;
+        c->path_queries[kPathWide] += bq;
         {
             std::lock_guard<std::mutex> slk(c->st->stats_mu);
             c->st->stats.dp_ms += dp_ms;

@@ -1,8 +1,9 @@
 // The helix base-pair score on the GPU: pair_count_kernel + sina_hip_upload_pairs,
 // sina_hip_pair_counts, sina_hip_pair_stats over finished alignments a caller hands in; pair_count_assembled_kernel +
 // sina_hip_align_count_pairs, sina_hip_staged_pair_counts, sina_hip_pair_inplace_stats over the alignments an align
-// call has just assembled on the device (launched by dp_launch.hip).  The look-up and the classification are one
-// piece of device code for both (pair_dev.h).
+// call has just assembled on the device (launched by dp_launch.hip, launch_inplace_counts; its switch, rows and event
+// are the context's inplace[kInplacePairs], ctx.h).  The look-up and the classification are one piece of device code
+// for both (pair_dev.h).  The kernels' counters are the context's use[kUsePairs] and use[kUsePairsInplace].
 //
 // What it computes: for every finished aligned sequence the counters behind align_bp_score_slv
 // (cseq_base::calcPairScore, src/cseq.cpp:651-733): for every column i that the helix map pairs with a column p, the
@@ -152,28 +153,20 @@ extern "C" int sina_hip_pair_counts(sina_hip_ctx *c, const uint32_t *q_ab, const
         float ms = 0;
         SH_CHECK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
         memcpy(counts + (size_t)r.q0 * 6, c->h_stage[5].p, 24 * (size_t)n);
-        c->pair_ms += ms;
-        c->pair_seqs += n;
-        c->pair_entries += (uint64_t)n * n_ent;
-        c->pair_launches++;
+        c->use[kUsePairs].add(ms, n, (uint64_t)n * n_ent, 1);
     }
     return 0;
 }
 
 extern "C" int sina_hip_pair_stats(sina_hip_ctx *c, double *kernel_ms, uint64_t *sequences, uint64_t *entries_visited, uint64_t *launches) {
     if (!c || !kernel_ms || !sequences || !entries_visited || !launches) SH_FAIL("pair_stats: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    *kernel_ms = c->pair_ms;
-    *sequences = c->pair_seqs;
-    *entries_visited = c->pair_entries;
-    *launches = c->pair_launches;
-    return 0;
+    return read_use(c, kUsePairs, kernel_ms, sequences, entries_visited, launches);
 }
 
 extern "C" int sina_hip_align_count_pairs(sina_hip_ctx *c, int on) {
     if (!c) SH_FAIL("align_count_pairs: null ctx");
     std::lock_guard<std::mutex> lk(c->mu);
-    c->count_pairs = on != 0;
+    c->inplace[kInplacePairs].on = on != 0;
     return 0;
 }
 
@@ -183,14 +176,10 @@ extern "C" const uint32_t *sina_hip_staged_pair_counts(sina_hip_ctx *c) {
         return nullptr;
     }
     std::lock_guard<std::mutex> lk(c->mu);
-    return c->pc_active ? c->h_pc.as<uint32_t>() : nullptr;
+    return c->inplace[kInplacePairs].staged();
 }
 
 extern "C" int sina_hip_pair_inplace_stats(sina_hip_ctx *c, double *kernel_ms, uint64_t *sequences, uint64_t *launches) {
     if (!c || !kernel_ms || !sequences || !launches) SH_FAIL("pair_inplace_stats: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    *kernel_ms = c->pc_ms;
-    *sequences = c->pc_seqs;
-    *launches = c->pc_launches;
-    return 0;
+    return read_use(c, kUsePairsInplace, kernel_ms, sequences, nullptr, launches);
 }

@@ -280,10 +280,7 @@ int rank_launch(sina_hip_ctx *c, const uint32_t *d_qab, const uint64_t *d_qoff, 
     memcpy(cnt, c->h_stage[5].p, 16);
     float ms = 0;
     SH_CHECK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
-    c->rank_ms += ms;
-    c->rank_pairs += cnt[0];
-    c->rank_bases += cnt[1];
-    c->rank_launches += pl.chunks > 1 ? 2 : 1;
+    c->use[kUseRank].add(ms, cnt[0], cnt[1], pl.chunks > 1 ? 2 : 1);
     return 0;
 }
 
@@ -381,10 +378,5 @@ extern "C" int sina_hip_compare_rank(sina_hip_ctx *c, const uint32_t *q_ab, cons
 
 extern "C" int sina_hip_rank_stats(sina_hip_ctx *c, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches) {
     if (!c || !kernel_ms || !pairs || !cand_bases || !launches) SH_FAIL("rank_stats: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    *kernel_ms = c->rank_ms;
-    *pairs = c->rank_pairs;
-    *cand_bases = c->rank_bases;
-    *launches = c->rank_launches;
-    return 0;
+    return read_use(c, kUseRank, kernel_ms, pairs, cand_bases, launches);
 }

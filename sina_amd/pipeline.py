@@ -240,41 +240,30 @@ class Store:
             raise HostError("get_stats failed")
         return {f[0]: getattr(s, f[0]) for f in capi.Stats._fields_}
 
+    def _counters(self, fn, fields):
+        return capi.read_counters(fn, (self.key.encode(),), fields, _chk)
+
     def slow_path_queries(self):
         """(queries the wide DP kernel has aligned, queries the long k-mer count kernel has counted) on this store's
         contexts so far -- between runs, when none of them is leased."""
-        w, l = C.c_uint64(), C.c_uint64()
-        _chk(self.H.sina_host_store_slow_path_queries(self.key.encode(), C.byref(w), C.byref(l)))
-        return int(w.value), int(l.value)
+        return tuple(self._counters(self.H.sina_host_store_slow_path_queries, capi.u64_fields("wide", "long")).values())
 
     def big_select_queries(self):
         """Queries the k-mer search's big select (more than 4096 candidates per query) has ranked on this store's
         contexts so far -- between runs, like slow_path_queries()."""
-        n = C.c_uint64()
-        _chk(self.H.sina_host_store_big_select_queries(self.key.encode(), C.byref(n)))
-        return int(n.value)
+        return self._counters(self.H.sina_host_store_big_select_queries, capi.u64_fields("n"))["n"]
 
     def match_stats(self):
         """The match-count kernel (famfinder's device-msc) on this store's contexts so far: dict(kernel_ms, pairs,
         cand_bases, launches) -- between runs, like big_select_queries()."""
-        ms = C.c_double()
-        pairs, bases, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _chk(self.H.sina_host_store_match_stats(self.key.encode(), C.byref(ms), C.byref(pairs), C.byref(bases),
-                                                C.byref(launches)))
-        return dict(kernel_ms=float(ms.value), pairs=int(pairs.value), cand_bases=int(bases.value),
-                    launches=int(launches.value))
+        return self._counters(self.H.sina_host_store_match_stats, capi.KERNEL_MS + capi.u64_fields("pairs", "cand_bases", "launches"))
 
     def rank_stats(self):
         """The search stage's device-rank on this store so far: dict(ranked, fallen_back, kernel_ms, pairs, cand_bases,
         launches) -- queries ranked on the device, queries sent back to the host path, and the rank kernel's time and
         volume on the store's contexts; between runs, like big_select_queries()."""
-        ranked, back = C.c_uint64(), C.c_uint64()
-        ms = C.c_double()
-        pairs, bases, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _chk(self.H.sina_host_store_rank_stats(self.key.encode(), C.byref(ranked), C.byref(back), C.byref(ms), C.byref(pairs),
-                                               C.byref(bases), C.byref(launches)))
-        return dict(ranked=int(ranked.value), fallen_back=int(back.value), kernel_ms=float(ms.value), pairs=int(pairs.value),
-                    cand_bases=int(bases.value), launches=int(launches.value))
+        return self._counters(self.H.sina_host_store_rank_stats, capi.u64_fields("ranked", "fallen_back") + capi.KERNEL_MS +
+                              capi.u64_fields("pairs", "cand_bases", "launches"))
 
     def set_pairs(self, pairs):
         """The helix map align_bp_score_slv is computed from: pairs[i] = partner column of column i, 0 = unpaired
@@ -286,31 +275,25 @@ class Store:
     def pair_stats(self):
         """The pair-count kernel (the helix base-pair score) on this store's contexts so far: dict(kernel_ms, sequences,
         entries_visited, launches) -- between runs, like match_stats()."""
-        ms = C.c_double()
-        seqs, ent, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _chk(self.H.sina_host_store_pair_stats(self.key.encode(), C.byref(ms), C.byref(seqs), C.byref(ent), C.byref(launches)))
-        return dict(kernel_ms=float(ms.value), sequences=int(seqs.value), entries_visited=int(ent.value),
-                    launches=int(launches.value))
+        return self._counters(self.H.sina_host_store_pair_stats, capi.KERNEL_MS + capi.u64_fields("sequences", "entries_visited", "launches"))
 
     def pair_inplace_stats(self):
         """The aligner's device-bps on this store so far: dict(trays, sequences, launches, kernel_ms) -- trays that took
         their score from the counters their align call brought back, and the in-place kernel's assembled queries,
         launches and time on the store's contexts -- between runs, like pair_stats()."""
-        ms = C.c_double()
-        trays, seqs, launches = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _chk(self.H.sina_host_store_pair_inplace_stats(self.key.encode(), C.byref(trays), C.byref(ms), C.byref(seqs), C.byref(launches)))
-        return dict(trays=int(trays.value), sequences=int(seqs.value), launches=int(launches.value), kernel_ms=float(ms.value))
+        d = self._counters(self.H.sina_host_store_pair_inplace_stats, capi.u64_fields("trays") + capi.KERNEL_MS +
+                           capi.u64_fields("sequences", "launches"))
+        d["kernel_ms"] = d.pop("kernel_ms")  # (the dict ends with it)
+        return d
 
     def identity_inplace_stats(self):
         """The aligner's device-idty on this store so far: dict(trays, sequences, pairs, launches, kernel_ms) -- trays that
         took their identity from the row their align call brought back, and the in-place kernel's assembled queries,
         (query, member) pairs, launches and time on the store's contexts -- between runs, like pair_inplace_stats()."""
-        ms = C.c_double()
-        trays, seqs, prs, launches = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _chk(self.H.sina_host_store_identity_inplace_stats(self.key.encode(), C.byref(trays), C.byref(ms), C.byref(seqs), C.byref(prs),
-                                                           C.byref(launches)))
-        return dict(trays=int(trays.value), sequences=int(seqs.value), pairs=int(prs.value), launches=int(launches.value),
-                    kernel_ms=float(ms.value))
+        d = self._counters(self.H.sina_host_store_identity_inplace_stats, capi.u64_fields("trays") + capi.KERNEL_MS +
+                           capi.u64_fields("sequences", "pairs", "launches"))
+        d["kernel_ms"] = d.pop("kernel_ms")  # (the dict ends with it)
+        return d
 
     def close(self):
         self.H.sina_host_store_close(self.key.encode())
