@@ -590,10 +590,21 @@ int sina_hip_debug_family_graph_words(sina_hip_ctx *ctx, const uint32_t *fam_ids
  * [n_nodes][16] table of match terms (entry 0 of a row: +inf) and the 16 self-comparison terms.  match,
  * mismatch, gap, gap_ext are the SCHEME's arguments (-match_score, -mismatch_score, pen_gap, pen_gapext,
  * src/align.cpp:428-433).  The node counters of up to 6144 nodes are in LDS at a time (fewer for alignments of
- * more than ~300 000 columns); a longer profile is swept in several tiles. */
+ * more than ~300 000 columns); a longer profile is swept in several tiles (SINA_HIP_TEST=profile_tile=N, tests
+ * only: tiles of at most N nodes).  The arrays start with room for 4096 nodes and keep the largest size a build of
+ * the context has needed; a family with more nodes has the kernel launched again, which counts as ONE launch in
+ * sina_hip_stats.  A column whose only bases have none of the four base bits has shares of 0 / 0. */
 int sina_hip_debug_family_profile(sina_hip_ctx *ctx, const uint32_t *fam_ids, uint32_t F, float match,
                                   float mismatch, float gap, float gap_ext, uint32_t *n_nodes, uint32_t *pos,
                                   float *score16, float *self16, uint32_t cap_nodes);
+/* Test hook: the same build, read back as the chain the DP kernel is handed, unchanged: per node the row record's four
+ * words (index of its predecessor entry; node weight and mask, 0; predecessors | sink << 16 | min(distance to the
+ * predecessor, 63: none) << 18; where the finished row is kept, 0xFFFFFFFF: handed on in registers) and the
+ * successor's column (1000000 on the last node), the n_nodes - 1 predecessor entries (entry n: node n + 1's, = n) and
+ * the build's 8 size words (nodes, edges, spill rows 0, status 0, first sink row, 0; the last two are not used). */
+int sina_hip_debug_family_profile_words(sina_hip_ctx *ctx, const uint32_t *fam_ids, uint32_t F, uint32_t *n_nodes,
+                                        uint32_t *rec_words /* [4 * cap_nodes] */, uint32_t *succ_min,
+                                        uint32_t *pred_entries, uint32_t *size_words /* [8] */, uint32_t cap_nodes);
 
 /* Cumulative statistics of this context and its forks since sina_hip_init (callers take
  * differences); kernel times come from HIP events on the context stream. */

@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "sina_hip_upload_refs", "sina_hip_build_index", "sina_hip_download_index", "sina_hip_upload_index", "sina_hip_store_view_get",
     "sina_hip_store_alloc_like", "sina_hip_kmer_topk", "sina_hip_kmer_scores", "sina_hip_compare",
     "sina_hip_align_params_default", "sina_hip_staged_out_pos", "sina_hip_align_graphs", "sina_hip_align_families",
-    "sina_hip_align_profiles", "sina_hip_debug_family_profile",
+    "sina_hip_align_profiles", "sina_hip_debug_family_profile", "sina_hip_debug_family_profile_words",
     "sina_hip_debug_mesh", "sina_hip_debug_family_graph", "sina_hip_debug_family_graph_words", "sina_hip_debug_dp_info", "sina_hip_debug_rgain", "sina_hip_debug_chain_rows", "sina_hip_get_stats",
     "sina_hip_align_graphs_any", "sina_hip_debug_mesh_wide", "sina_hip_wide_queries", "sina_hip_last_error_is_limit",
     "sina_hip_kmer_topk_any", "sina_hip_kmer_scores_any", "sina_hip_long_queries", "sina_hip_big_select_queries",
@@ -183,6 +183,7 @@ def load():
                                                 C.c_uint32, C.POINTER(AlignOut), u32p]
     L.sina_hip_debug_family_profile.argtypes = [vp, u32p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, u32p, u32p,
                                                 f32p, f32p, C.c_uint32]
+    L.sina_hip_debug_family_profile_words.argtypes = [vp, u32p, C.c_uint32, u32p, u32p, u32p, u32p, u32p, C.c_uint32]
     L.sina_hip_debug_mesh.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
                                       u32p, u32p, f32p, C.c_int]
     L.sina_hip_debug_family_graph.argtypes = [vp, u32p, C.c_uint32, C.c_float, C.c_uint32, u32p, u32p, u32p, u8p,
@@ -669,6 +670,22 @@ class Context:
                                                          gap_ext, C.byref(nn), _ptr(pos, u32p), _ptr(sc, f32p),
                                                          _ptr(own, f32p), cap))
         return pos[:nn.value].copy(), sc[:nn.value].copy(), own
+
+    def debug_family_profile_words(self, fam_ids):
+        """The same build as the chain the DP kernel reads: dict(n, rec [n, 4] (the row records' words), succ_min [n],
+        pred [n - 1] (the entries), sizes [8] (the size words)), all as they are on the device."""
+        fam_ids = _c(fam_ids, np.uint32)
+        cap = 65536
+        nn = C.c_uint32()
+        rec = np.zeros((cap, 4), np.uint32)
+        smin = np.zeros(cap, np.uint32)
+        pred = np.zeros(cap, np.uint32)
+        sz = np.zeros(8, np.uint32)
+        self._check(self.L.sina_hip_debug_family_profile_words(self.h, _ptr(fam_ids, u32p), len(fam_ids), C.byref(nn),
+                                                               _ptr(rec, u32p), _ptr(smin, u32p), _ptr(pred, u32p),
+                                                               _ptr(sz, u32p), cap))
+        n = nn.value
+        return dict(n=n, rec=rec[:n].copy(), succ_min=smin[:n].copy(), pred=pred[:max(n, 1) - 1].copy(), sizes=sz)
 
     def debug_mesh(self, gb, qmask, params=None, want_value=True, prune=False):
         """DP planes of ONE query.  prune=False (default): every row of every strip is swept, the planes are

@@ -352,13 +352,16 @@ struct ProfileLds {
     uint32_t tile_nodes, bitmap_off, member_off;
     size_t total;
 };
-bool profile_lds(uint32_t width, uint32_t max_family, uint32_t ncap, ProfileLds *l) {
+// forced != 0: at most that many nodes per tile (SINA_HIP_TEST=profile_tile=N), never more than the LDS allows
+bool profile_lds(uint32_t width, uint32_t max_family, uint32_t ncap, uint32_t forced, ProfileLds *l) {
     const size_t nwords = (width + 31) / 32;
     const size_t bm = (6 * nwords + 15) & ~(size_t)15, members = sizeof(PMember) * (size_t)max_family;
     const size_t budget = 160 * 1024 - kLdsSlack;
     if (bm + members + 12 * 64 + 16 > budget) return false;
     const size_t room = (budget - bm - members - 16) / 12;
-    l->tile_nodes = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ncap, kTileMax), room));
+    size_t tile = std::min<size_t>(std::min<size_t>(ncap, kTileMax), room);
+    if (forced) tile = std::min<size_t>(tile, forced);
+    l->tile_nodes = (uint32_t)std::max<size_t>(1, tile);
     l->bitmap_off = (uint32_t)((12 * (size_t)l->tile_nodes + 15) & ~(size_t)15);
     l->member_off = (uint32_t)(l->bitmap_off + bm);
     l->total = l->member_off + members;
@@ -407,9 +410,11 @@ int build_family_profiles(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64
     if (allow_full_lds(reinterpret_cast<const void *>(family_profile_kernel))) return 1;
     uint32_t ncap = c->prof_ncap ? c->prof_ncap : 4096u;
     uint32_t max_n = 1;
+    // (SINA_HIP_TEST=profile_tile=N: tiles of N nodes, so that a family of a few hundred nodes is swept in several)
+    const uint32_t forced_tile = (uint32_t)strtoul(test_knob("profile_tile").c_str(), nullptr, 10);
     for (int attempt = 0;; attempt++) {
         ProfileLds lds;
-        if (!profile_lds(c->st->width, max_f, ncap, &lds)) SH_FAIL_LIMIT("align_profiles: family too wide for the device profile build");
+        if (!profile_lds(c->st->width, max_f, ncap, forced_tile, &lds)) SH_FAIL_LIMIT("align_profiles: family too wide for the device profile build");
         const uint32_t pred_stride = ncap + 8;  // (slack behind every list, like the DAG build's)
         if (c->rec.reserve(sizeof(uint4) * (uint64_t)n * ncap) || c->node_pos.reserve(4 * (uint64_t)n * ncap) ||
             c->succ_minpos.reserve(4 * (uint64_t)n * ncap) || c->pred.reserve(4 * (uint64_t)n * pred_stride) ||
@@ -520,6 +525,32 @@ int sina_hip_debug_family_profile(sina_hip_ctx *c, const uint32_t *fam_ids, uint
     SH_CHECK(hipMemcpy(pos, c->node_pos.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
     SH_CHECK(hipMemcpy(score16, c->prof16.p, 64 * (size_t)N, hipMemcpyDeviceToHost));
     self_scores(&p, self16);
+    return 0;
+}
+
+int sina_hip_debug_family_profile_words(sina_hip_ctx *c, const uint32_t *fam_ids, uint32_t F, uint32_t *n_nodes,
+                                        uint32_t *rec_words, uint32_t *succ_min, uint32_t *pred_entries,
+                                        uint32_t *size_words, uint32_t cap_nodes) {
+    if (!c || !fam_ids || !n_nodes || !rec_words || !succ_min || !pred_entries || !size_words)
+        SH_FAIL("debug_family_profile_words: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->st->have_refs) SH_FAIL("debug_family_profile_words: upload references first");
+    if (F == 0 || F > (uint32_t)kFamilyMax) SH_FAIL("debug_family_profile_words: family size must be in 1..128");
+    if (c->st->width > 524288u) SH_FAIL("debug_family_profile_words: alignment wider than 524288 columns");
+    SH_CHECK(hipSetDevice(c->device));
+    sina_hip_align_params p;
+    sina_hip_align_params_default(&p);  // (the chain does not depend on the scheme)
+    const uint64_t foff[2] = {0, F};
+    BuiltGraphs bg;
+    if (build_family_profiles(c, fam_ids, foff, 0, 1, &p, 0, PrunePlan(), &bg)) return 1;
+    const uint32_t N = bg.sizes[kBuiltN];
+    *n_nodes = N;
+    if (N > cap_nodes) SH_FAIL("debug_family_profile_words: output buffers too small");
+    static_assert(sizeof(uint4) == 16, "four words per row record");
+    SH_CHECK(hipMemcpy(rec_words, c->rec.p, sizeof(uint4) * (size_t)N, hipMemcpyDeviceToHost));
+    SH_CHECK(hipMemcpy(succ_min, c->succ_minpos.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    if (N > 1) SH_CHECK(hipMemcpy(pred_entries, c->pred.p, 4 * (size_t)(N - 1), hipMemcpyDeviceToHost));
+    memcpy(size_words, bg.sizes.data(), 4 * kBuiltWords);
     return 0;
 }
 

@@ -267,8 +267,8 @@ def fuzz_knobs_and_scoring(rng, pick, refs, max_qlen):
 
 def set_knobs(monkeypatch, **kw):
     """Test hooks of the library, all in ONE environment variable (csrc/common.h test_knob):
-    SINA_HIP_TEST="geom=T,B;generic=1;dense_div=N;lds_kb=N;rho=X".  A value of None removes the key; the other keys
-    of the variable stay as they are."""
+    SINA_HIP_TEST="geom=T,B;generic=1;dense_div=N;lds_kb=N;rho=X;profile_tile=N".  A value of None removes the key;
+    the other keys of the variable stay as they are."""
     import os
     cur = dict(x.split("=", 1) for x in os.environ.get("SINA_HIP_TEST", "").split(";") if "=" in x)
     for k, v in kw.items():
