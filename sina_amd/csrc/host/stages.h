@@ -475,7 +475,7 @@ public:
         float match_score, mismatch_score, gap_penalty, gap_ext_penalty;
         bool debug_graph, write_used_rels, use_subst_matrix;
         bool wide_fallback;   // families beyond the fast DP path's limits go through sina_hip_align_graphs_any (default off)
-        bool device_profile;  // fs_no_graph: build the family profile on the GPU too (needs device_graph; default off: see stages.cpp)
+        bool device_profile;  // fs_no_graph: build the family profile on the GPU too (needs device_graph; default off: see aligner.cpp)
         bool device_graph;  // build the family DAG on the GPU (default) or on the host
         bool weight_sets;   // device-built DAGs: the weighted trays of a batch in ONE call whatever their filters
                             // (sina_hip_align_families_wsets; default on) instead of one call per filter
@@ -720,7 +720,7 @@ private:
 
 // ---------------------------------------------------------------- helpers
 // parallel for over [0, n) on a process-wide pool (stands in for TBB's workers)
-// first occurrence of `needle` in `hay`, like std::string::find (the aligner's exact-relative test; stages.cpp)
+// first occurrence of `needle` in `hay`, like std::string::find (the aligner's exact-relative test; aligner.cpp)
 size_t find_bases(const std::string &hay, const std::string &needle, int force_scalar = 0);
 void parallel_for(size_t n, const std::function<void(size_t)> &fn);
 void set_host_threads(unsigned n);

@@ -1,5 +1,5 @@
 // Launch ranges of the k-mer search's big select (kmer.hip: more than kKmerSelMax candidates per query), as plain
-// host code: no HIP, no context, no environment -- kmer.hip cuts its launches with it, host/stages.cpp its calls, and
+// host code: no HIP, no context, no environment -- kmer.hip cuts its launches with it, host/store.cpp its calls, and
 // tests/kmer_plan_check.cpp runs it without a device.
 #pragma once
 

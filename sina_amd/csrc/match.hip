@@ -1,7 +1,7 @@
 // Famfinder's identity filter on the GPU: match_count_kernel + sina_hip_match_count.
 //
 // What it computes: for every (query, candidate reference) pair the `match` counter of the lock-step walk behind
-// --fs-msc-max (host/stages.cpp, identity_cover_query): the number of columns where both sequences have a base and
+// --fs-msc-max (host/famfinder.cpp, identity_cover_query): the number of columns where both sequences have a base and
 // (maskA & maskB & 0xF) != 0 -- base_comp_optimistic, no lower-case filter.  The walk's score is
 // match / (match + mismatch + only_a + only_a_overhang), and that denominator is the query's base count whenever both
 // sides have a base, so this one integer per pair is all the host needs.

@@ -2,7 +2,7 @@
 //
 // What it computes: pseq::pseq + scoring_scheme_profile's match term for every query's family (reference
 // src/pseq.cpp, src/pseq.h:65-113, src/align.cpp:428-433) -- exactly what build_family_profile() / profile_comp()
-// (host/stages.cpp) tabulate on the host:
+// (host/family_graph.cpp) tabulate on the host:
 //   * one node for alignment column 0, occupied or not, then one per occupied column, ascending; every node's one
 //     predecessor is the node before it;
 //   * per node the column's base_profile: twelve points per member that has a base there, split evenly over the
@@ -368,7 +368,7 @@ bool profile_lds(uint32_t width, uint32_t max_family, uint32_t ncap, uint32_t fo
     return true;
 }
 
-void self_scores(const sina_hip_align_params *p, float *out16) {  // profile_self_scores (host/stages.cpp)
+void self_scores(const sina_hip_align_params *p, float *out16) {  // profile_self_scores (host/family_graph.cpp)
     out16[0] = 0.f;
     for (unsigned m = 1; m < 16; m++) {
         const Shares b = shares_of_mask(m);

@@ -2,7 +2,7 @@
 // sina_hip_upload_name_order, sina_hip_rank_stats; sina_hip_kmer_topk_rank (kmer.hip) launches the same kernels on the
 // select's id rows.
 //
-// What it computes: what search_filter does with a query's candidates after comparing them (host/stages.cpp): the
+// What it computes: what search_filter does with a query's candidates after comparing them (host/search_filter.cpp): the
 // score (float)match / denom of every candidate, denom an integer chosen by the cover rule (cseq_comparator::score),
 // and the max_result best by std::greater<result_item> -- score descending, equal scores by name descending.  With
 // unique names and no NaN that is a strict total order, so the best N are one sequence whatever sorts them.  A score

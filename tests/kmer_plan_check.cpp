@@ -17,7 +17,7 @@ static int fails = 0;
         }                                                             \
     } while (0)
 
-// walks the ranges as kmer.hip and host/stages.cpp do; returns their number, checks that they tile [0, nq)
+// walks the ranges as kmer.hip and host/store.cpp do; returns their number, checks that they tile [0, nq)
 static uint64_t walk(uint32_t nq, uint32_t M, uint64_t budget, uint32_t *first, uint32_t *last) {
     const uint32_t per = big_select_range(nq, M, budget);
     EXPECT(per >= 1 && per <= (nq ? nq : 1u));

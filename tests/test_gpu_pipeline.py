@@ -177,7 +177,7 @@ def test_pipeline_copy_shortcut_and_realign(oracle, world):
 def test_pipeline_exact_relatives_among_mutated_queries(oracle, world):
     """One batch in which every third query is an exact copy of its reference, every third an exact window of it and
     the rest are mutated (bench.py --exact-rate): copies and DP alignments side by side, short windows that several
-    family members hold (the aligner's containment search, host/stages.cpp find_bases) -- all against the oracle."""
+    family members hold (the aligner's containment search, host/aligner.cpp find_bases) -- all against the oracle."""
     refs, cs, idx, st = world
     full = synth.make_queries(refs, 60, seed=91, sub=[0.0, 0.03, 0.03], dele=[0.0, 0.005, 0.005], ins=[0.0, 0.003, 0.003])
     wins = synth.make_queries(refs, 60, seed=92, sub=[0.03, 0.0, 0.03], dele=[0.005, 0.0, 0.005], ins=[0.003, 0.0, 0.003],

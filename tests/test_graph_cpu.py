@@ -1,6 +1,6 @@
 """The family DAG build's named cases and its plain restatement, on the CPU: every case of tests/graph_cases.py sits
 on the edge it names; tests/graph_ref.py build equals the oracle's mseq and the host twin (build_family_graph,
-stages.cpp) field for field on every case and on the fuzz worlds' families; its dp_words equal dp_plan.h's prep_range
+family_graph.cpp) field for field on every case and on the fuzz worlds' families; its dp_words equal dp_plan.h's prep_range
 (tests/dp_plan_check.cpp --words, under the address and undefined-behaviour sanitizers).  No GPU."""
 import os
 import re
@@ -104,7 +104,7 @@ def test_plain_build_equals_oracle_mseq_on_the_fuzz_worlds(oracle, seed):
 
 
 def test_plain_build_equals_the_host_twin():
-    """build_family_graph (host/stages.cpp), what the aligner's host route hands to sina_hip_align_graphs."""
+    """build_family_graph (host/family_graph.cpp), what the aligner's host route hands to sina_hip_align_graphs."""
     for width, cases in gc.by_width():
         refs, fams = gc.refset(cases)
         st = pipeline.Store(":mem:graphcases%d" % width, refs)

@@ -131,7 +131,7 @@ def test_host_family_graph_equals_oracle(oracle):
 
 
 def test_host_family_profile_equals_oracle(oracle):
-    """--fs-no-graph on the host (build_family_profile, stages.cpp): the columns and the per-node match terms the
+    """--fs-no-graph on the host (build_family_profile, family_graph.cpp): the columns and the per-node match terms the
     aligner hands to the device against the oracle's pseq + base_profile::comp, bit for bit."""
     refs = synth.make_refs(80, length=300, width=3000, seed=43, amb_rate=0.03, lower_rate=0.03, long_del_prob=0.3)
     cs = util.cseqs_from_refs(refs)

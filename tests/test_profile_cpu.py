@@ -2,7 +2,7 @@
 the ABI surface, the refusal of a null context, and that the host's option routing is what it was; the profile
 kernel's named cases (tests/profile_cases.py) each on the edge it names, and its plain restatement
 (tests/profile_ref.py) pinned to the oracle's pseq + base_profile::comp, to the host twin (build_family_profile,
-stages.cpp) and -- the chain's words -- to dp_plan.h's prep_range (tests/dp_plan_check.cpp --words)."""
+family_graph.cpp) and -- the chain's words -- to dp_plan.h's prep_range (tests/dp_plan_check.cpp --words)."""
 import ctypes as C
 import os
 import re
@@ -177,7 +177,7 @@ def test_plain_build_equals_oracle_pseq_on_the_fuzz_families(oracle, seed):
 
 
 def test_plain_build_equals_the_host_twin():
-    """build_family_profile (host/stages.cpp), what the aligner's host route hands to sina_hip_align_graphs."""
+    """build_family_profile (host/family_graph.cpp), what the aligner's host route hands to sina_hip_align_graphs."""
     groups = pc.by_width() + pc.by_width(fresh=True) + [(None, [pc.fuzz_case(s)]) for s in range(4)]
     for k, (width, cases) in enumerate(groups):
         refs, fams = pc.refset(cases)

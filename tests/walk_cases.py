@@ -42,7 +42,7 @@ def _cseq(name, masks):
 
 
 def profile_tables(fam, opts):
-    """(graph, node_score16 [n, 16], self_score16 [16]) of a family as a profile, the way host/stages.cpp builds
+    """(graph, node_score16 [n, 16], self_score16 [16]) of a family as a profile, the way host/family_graph.cpp builds
     them for the pipeline: base_profile::comp of the column with each of the 15 iupac masks (mask 0: +inf, no
     query base has it); the scheme gets the negated scores (src/align.cpp:406-414)."""
     g = po.pseq_build(fam)

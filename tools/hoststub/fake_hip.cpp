@@ -1,6 +1,6 @@
 // HOST-PROFILING STUB -- not part of the product, never shipped in sina_amd/, never loaded by tests or bench.py.
 //
-// A stand-in for libsina_hip.so that answers the C-ABI calls of the host stages (host/stages.cpp) with
+// A stand-in for libsina_hip.so that answers the C-ABI calls of the host stages (host/store.cpp, famfinder.cpp, aligner.cpp, search_filter.cpp) with
 // plausible, deterministic, WRONG results in no time, so that the CPU cost of the host side of the boundary
 // (trays, famfinder's cascade, the aligner's glue, the sink) can be measured per query in a container
 // without a GPU (tools/hoststub/host_perf.py).  It computes nothing: k-mer "results" are hash-picked
@@ -108,6 +108,14 @@ int sina_hip_kmer_topk_rank(sina_hip_ctx *, const uint32_t *, const uint64_t *, 
 int sina_hip_rank_stats(sina_hip_ctx *, double *ms, uint64_t *pairs, uint64_t *bases, uint64_t *launches) {
     *ms = 0;
     *pairs = *bases = *launches = 0;
+    return 0;
+}
+// (a helix map is taken and forgotten; the stub counts no pairs)
+int sina_hip_upload_pairs(sina_hip_ctx *, const uint32_t *, uint32_t) { return 0; }
+int sina_hip_pair_counts(sina_hip_ctx *, const uint32_t *, const uint64_t *, uint32_t, uint32_t *) { g_err = "stub"; return 1; }
+int sina_hip_pair_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, uint64_t *entries, uint64_t *launches) {
+    *ms = 0;
+    *seqs = *entries = *launches = 0;
     return 0;
 }
 // (the switch is taken and nothing is counted: an align call of the stub leaves no rows)
