@@ -35,6 +35,25 @@ int make_streams(sina_hip_ctx *c) {
     return 0;
 }
 
+// The dynamic-LDS ceiling of a kernel is raised ONCE per kernel and device to all of a CU's 160 KB (a
+// per-launch size would race between contexts launching from different host threads; the attribute belongs
+// to the current device's function object, so a process with contexts on several devices sets it on each).
+int allow_full_lds(const void *kernel) {
+    static std::mutex mu;
+    static std::vector<std::pair<int, const void *>> done;
+    int dev = 0;
+    SH_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    for (const auto &k : done)
+        if (k.first == dev && k.second == kernel) return 0;
+    hipFuncAttributes fa;
+    SH_CHECK(hipFuncGetAttributes(&fa, kernel));  // (the ceiling is what the kernel's static LDS leaves of the 160 KB)
+    const int room = 160 * 1024 - (int)fa.sharedSizeBytes;
+    SH_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, room));
+    done.emplace_back(dev, kernel);
+    return 0;
+}
+
 // What sina_hip_debug_mesh asks of its one query: the planes, unpacked cell by cell (value: optional), and whether the
 // row skip stays on.
 struct MeshDebug {

@@ -384,34 +384,31 @@ struct BtArgs {
     const float *self16;  // --fs-no-graph: comp(base, base) per iupac mask (sum_weight's term), else nullptr
 };
 
-// Picks the (threads, cells per thread) geometry for the longest query of a batch.
+// The (threads, cells per thread) geometry of a DP launch: dp_geom_for (dp_plan.h) picks it for the longest query of a
+// batch; pick_geom (dp_launch.hip) is that with the SINA_HIP_TEST=geom=T,B hook read.
 struct DpGeom {
     int T, B;
     int Lp() const { return T * B; }
 };
 bool pick_geom(uint32_t maxL, DpGeom *g);
 // DP waves per SIMD of geometry B (one wave = one query): what launches are sized by (dp_wave_slots, ctx.h) and what
-// each wave's LDS is left for (dp_default_lds_budget).  (B = 4: the simple kernel needs 87 VGPRs, five waves per
+// each wave's LDS is left for (dp_default_lds_budget, dp_plan.h).  (B = 4: the simple kernel needs 87 VGPRs, five waves per
 // SIMD -- 5120-query launches of V4 amplicons run 11 % faster per query than 4096-query ones; the general B = 4
 // kernels stay at four.)  The kernels' __launch_bounds__ are minimum occupancies, not this number.
 #ifndef SINA_DP_SIMPLE_WAVES8
 #define SINA_DP_SIMPLE_WAVES8 3  // waves per SIMD the B = 8 kernel is compiled for
 #endif
 constexpr int dp_waves_per_simd(int B) { return B <= 4 ? 5 : (B <= 8 ? SINA_DP_SIMPLE_WAVES8 : 2); }
-size_t dp_slot_bytes(const DpGeom &g);
-size_t dp_fixed_lds_bytes(const DpGeom &g);
-int dp_max_ring(const DpGeom &g);  // deepest LDS ring the slot allocators support
-size_t dp_default_lds_budget(const DpGeom &g);  // LDS per workgroup that keeps the register-limited occupancy
 // (kind_out, if not null: the kernel it launched, SINA_DP_KERNEL_* -- dp_kernel_kind, dp_plan.h)
 int launch_mesh_dp(const DpGeom &g, bool weighted, bool forbid, const DpArgs &a, uint32_t nq,
                    size_t lds_bytes, hipStream_t s, uint32_t *kind_out = nullptr);
+// the walk (traceback.hip): one lane per query or one wave per query -- bt_by_lanes, dp_plan.h
 int launch_backtrack(const BtArgs &a, hipStream_t s);
-bool backtrack_by_lanes(const BtArgs &a);  // one lane per query (large launches of 16S-long queries), else one wave per query
 int launch_assemble(const BtArgs &a, hipStream_t s);  // (after launch_backtrack, same stream)
 // (after launch_assemble, same stream; pairs.hip) the helix base-pair counters of the launch's queries from the words
 // assemble_kernel left: counts [a.nq][6]; ent: the store's n_ent (column, partner) entries
 int launch_pair_count_assembled(const BtArgs &a, const void *ent, uint32_t n_ent, uint32_t *counts, hipStream_t s);
-// raises a kernel's dynamic-LDS ceiling to a CU's 160 KB, once per kernel and process (mesh_dp.hip)
+// raises a kernel's dynamic-LDS ceiling to a CU's 160 KB, once per kernel and device (api.hip)
 int allow_full_lds(const void *kernel);
 
 // geometry + LDS ring depth chosen for a batch

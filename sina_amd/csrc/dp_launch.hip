@@ -11,17 +11,18 @@
 
 namespace sina_hip {
 
+// dp_geom_for (dp_plan.h) with the test hook read: SINA_HIP_TEST="geom=T,B" (used if it covers the batch's longest query)
+bool pick_geom(uint32_t maxL, DpGeom *g) {
+    int t = 0, b = 0;
+    if (const std::string ov = test_knob("geom"); ov.empty() || sscanf(ov.c_str(), "%d,%d", &t, &b) != 2) t = b = 0;
+    return dp_geom_for(maxL, t, b, g);
+}
+
 int plan_dp(sina_hip_ctx *c, uint32_t maxL, DpPlan *pl) {
-    if (!pick_geom(maxL, &pl->geom)) SH_FAIL_LIMIT("align: query longer than SINA_HIP_MAX_QUERY_LEN bases");
-    const size_t slot = dp_slot_bytes(pl->geom), fixed = dp_fixed_lds_bytes(pl->geom);
-    size_t budget = c->lds_budget ? c->lds_budget : dp_default_lds_budget(pl->geom);
-    if (budget < fixed + slot) budget = fixed + slot;
-    if (budget > 160 * 1024) budget = 160 * 1024;
-    int W = (int)((budget - fixed) / slot);
-    if (W < 1) SH_FAIL("align: LDS cannot hold one DP row");
-    W = std::min(W, dp_max_ring(pl->geom));
-    pl->W = W;
-    pl->lds = fixed + (size_t)W * slot;
+    DpGeom g;
+    if (!pick_geom(maxL, &g)) SH_FAIL_LIMIT("align: query longer than SINA_HIP_MAX_QUERY_LEN bases");
+    dp_ring_plan(g, c->lds_budget, pl);
+    if (pl->W < 1) SH_FAIL("align: LDS cannot hold one DP row");
     return 0;
 }
 

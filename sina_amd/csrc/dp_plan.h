@@ -1,5 +1,5 @@
 // What a DP launch is planned from, as plain host code: no HIP runtime call, no context, no environment -- every
-// function here runs (and is tested: tests/dp_plan_check.cpp) without a device.  dp_launch.hip and api.hip call them.
+// function here runs (and is tested: tests/dp_plan_check.cpp) without a device.  dp_launch.hip, api.hip and the launchers (mesh_dp.hip, traceback.hip) call them.
 #pragma once
 
 #include <cassert>
@@ -73,6 +73,84 @@ inline bool scout_allowed(bool has_chain, bool weighted, bool forbid, bool prune
                           float gpe, int T, bool scout_knob_off, bool generic_only) {
     return has_chain && !weighted && !forbid && prune_on && !rho_fixed && below_init && gp >= gpe && T > 64 && !scout_knob_off &&
            !generic_only;
+}
+
+// ---- geometry and LDS ring of a launch, lanes or waves for its walk
+// A geometry is (columns per lane B, strips S): one wave sweeps S strips of 64*B columns; T = 64 * S
+// is kept as the geometry's "virtual thread count" (T * B columns).  Fat lanes amortise the per-row
+// fixed work of a wave (row record, chain exchange, publish) over more cells, thin lanes need fewer
+// registers and allow more waves per SIMD.  Measured on MI355X, 16S queries, DP kernel alone on a
+// launch that fills every wave slot (tools/perf_dp_geoms.sh): B = 12 (2 waves/SIMD) 403 Gcell/s,
+// B = 8 (3 waves/SIMD) 461, B = 4 (4 waves/SIMD) 226.  The geometry for a launch is the one with
+// the smallest padded width / throughput.
+constexpr int kLaneCells[] = {4, 8, 12};
+constexpr double kLaneRate[] = {226.0, 461.0, 403.0};  // Gcell/s of the B = 4, 8, 12 kernels (above)
+constexpr int kMaxStrips = 40;  // 40 x 256 columns (B = 4) cover SINA_HIP_MAX_QUERY_LEN
+
+// The geometry for a batch whose longest query has maxL bases; false: none covers it.  forced_T, forced_B: the
+// SINA_HIP_TEST="geom=T,B" hook (0, 0: none) -- taken if it is a geometry the kernels have and covers maxL, else ignored.
+inline bool dp_geom_for(uint32_t maxL, int forced_T, int forced_B, DpGeom *g) {
+    if (forced_T % 64 == 0 && forced_T >= 64 && forced_T <= 64 * kMaxStrips && (forced_B == 4 || forced_B == 8 || forced_B == 12) &&
+        (uint32_t)(forced_T * forced_B) >= maxL) {
+        g->T = forced_T;
+        g->B = forced_B;
+        return true;
+    }
+    // one strip covers the query: the thinnest lanes that do (a wider lane would only idle -- V4
+    // amplicons, 250 bases: B = 4 487 Gcell/s, B = 8 with half the lanes unused 260)
+    for (int i = 0; i < 3; i++)
+        if (maxL <= 64u * (uint32_t)kLaneCells[i]) {
+            g->T = 64;
+            g->B = kLaneCells[i];
+            return true;
+        }
+    // several strips: B = 8 or 12 by padded width / throughput
+    double best = 0;
+    bool found = false;
+    for (int i = 1; i < 3; i++) {
+        const int b = kLaneCells[i];
+        const uint32_t strips = (maxL + 64u * b - 1) / (64u * b);
+        if (strips > (uint32_t)kMaxStrips) continue;
+        const double cost = (double)(strips * 64u * b) / kLaneRate[i];
+        if (!found || cost < best) {
+            best = cost;
+            g->T = (int)strips * 64;
+            g->B = b;
+            found = true;
+        }
+    }
+    return found;
+}
+
+// one LDS row slot: value | gapm_val of the strip's columns + the value left of the strip
+inline size_t dp_slot_bytes(const DpGeom &g) { return (size_t)64 * g.B * 8 + 16; }
+constexpr int kDpMaxRing = 8;  // the slot allocators keep 8 slot states; deeper rings gain nothing
+// LDS per workgroup (= per wave) that still lets the kernel's register budget decide the occupancy
+inline size_t dp_default_lds_budget(const DpGeom &g) { return (size_t)160 * 1024 / (4 * dp_waves_per_simd(g.B)) - 64; }
+// The LDS ring of a launch of geometry g: as many row slots as the budget holds (budget_override, bytes per workgroup:
+// the context's lds_budget; 0: the default), one at least, no more than a CU's 160 KB and no deeper than kDpMaxRing.
+inline void dp_ring_plan(const DpGeom &g, size_t budget_override, DpPlan *pl) {
+    const size_t slot = dp_slot_bytes(g);
+    size_t budget = budget_override ? budget_override : dp_default_lds_budget(g);
+    if (budget < slot) budget = slot;
+    if (budget > 160 * 1024) budget = 160 * 1024;
+    pl->geom = g;
+    pl->W = std::min((int)(budget / slot), kDpMaxRing);
+    pl->lds = (size_t)pl->W * slot;
+}
+
+// Launches of kBtLanesMin queries and more, none longer than kBtLanesMaxLen, walk one lane per query
+// (backtrack_lanes_kernel, traceback.hip).  The lanes' walk takes a microsecond per step whatever the launch (3.2 ms for 16S), the
+// waves' walk 0.33 us of the device's instruction issue per query: at 9216 queries the two are the same 3 ms, and
+// the lanes' are latency that the launches queued behind on the other FIFO stream cover (k-mer search 5.8 ms, DAG
+// build 4.5) where the waves' are instructions taken from them.  A smaller launch is done sooner by waves -- with
+// half the queries duplicates (4608 per launch, neighbours of 2-3 ms) lanes cost 6 %: 380 k against 406 k sequences/s,
+// on the FIFO stream or off it -- and a launch of 23S-long queries (6000 steps, 14 ms) is waited for by a pipeline
+// that holds two batches of them.  forced: SINA_HIP_TEST=bt_lanes=0/1 forces one (-1: none).
+constexpr uint32_t kBtLanesMin = 8192, kBtLanesMaxLen = 2048;
+inline bool bt_by_lanes(uint32_t nq, uint32_t asm_cap, int forced) {
+    if (forced >= 0) return forced != 0;
+    return nq >= kBtLanesMin && asm_cap <= kBtLanesMaxLen;
 }
 
 // ---- launch ranges

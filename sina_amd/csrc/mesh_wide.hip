@@ -266,7 +266,7 @@ __global__ void __launch_bounds__(1024) mesh_wide_kernel(WideArgs a) {
 }
 
 // The cell walk of backtrack() (mesh.h:594-721) over the explicit (value_midx, value_sidx) planes, one lane per
-// query: what walk_query (mesh_dp.hip) emits with assemble = 0 -- tail overhang, the one-step deletion skip,
+// query: what walk_query (traceback.hip) emits with assemble = 0 -- tail overhang, the one-step deletion skip,
 // sum_weight in the reference's order, head overhang, self16 for profiles.  The wide path never assembles.
 __global__ void __launch_bounds__(64) mesh_wide_walk_kernel(WideArgs a) {
     const uint32_t q = blockIdx.x * 64u + threadIdx.x;

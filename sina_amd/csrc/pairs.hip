@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(kPT) pair_count_kernel(PairArgs a) {
     pair_count_wave(W, len, a.ent, a.n_ent, lane, a.out + (size_t)seq * 6);
 }
 
-// The same count where the words already lie: behind assemble_kernel (mesh_dp.hip) on its stream, over the words it
+// The same count where the words already lie: behind assemble_kernel (traceback.hip) on its stream, over the words it
 // left in BtArgs::out_pos -- no packing, no staging, no upload.  One wave per query of the DP launch range; a query
 // the device did not finish (assembled == 0) or that failed (status != 0) gets six zeros, so every row is defined.
 // There is no check of the columns here, as pair_first_descending is one for words a caller hands in: assembled == 1

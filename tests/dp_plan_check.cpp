@@ -36,8 +36,6 @@ using Rng = std::mt19937_64;
 static uint32_t below(Rng &r, uint32_t n) { return (uint32_t)(r() % n); }  // 0 .. n-1
 static uint32_t between(Rng &r, uint32_t lo, uint32_t hi) { return lo + below(r, hi - lo + 1); }
 
-constexpr int kMaxRing = 8;  // what dp_max_ring() answers (mesh_dp.hip): the deepest LDS ring a launch is planned with
-
 // ------------------------------------------------------------------------------------------------ prep_range
 struct Dag {
     std::vector<uint32_t> pos, pred_off{0}, pred;  // pred_off: N + 1 entries
@@ -257,7 +255,7 @@ NOINLINE static void test_prep_range() {
             b.add(random_dag(r, n), between(r, 1, 400));
         }
         const uint32_t q0 = below(r, nq), q1 = between(r, q0 + 1, nq);
-        check_prep(b, q0, q1, (int)(256 * between(r, 1, 4)), (int)between(r, 1, kMaxRing), below(r, 4) ? 128.f * 1.0001f : 0.f);
+        check_prep(b, q0, q1, (int)(256 * between(r, 1, 4)), (int)between(r, 1, kDpMaxRing), below(r, 4) ? 128.f * 1.0001f : 0.f);
     }
 }
 
@@ -265,7 +263,7 @@ NOINLINE static void test_prep_directed() {
     Rng r(20255);
     g_case = "prep_range, directed";
     std::string msg;
-    for (int W : {1, 4, kMaxRing}) {
+    for (int W : {1, 4, kDpMaxRing}) {
         Dag one;
         one.node(7, {});
         check_one(one, 1, W);
@@ -525,6 +523,116 @@ NOINLINE static void test_classify() {
     CHECK(classify_any(b.batch(), b.qoff.data(), false, &wide) == 1 && g_err_limit == 0, "a malformed DAG is a plain error");
 }
 
+// ------------------------------------------------------------------------------------------------ dp_geom_for
+// pick_geom as it stood in mesh_dp.hip before the geometry moved into dp_plan.h (less its test hook), kept to sweep against
+static bool geom_before(uint32_t maxL, DpGeom *g) {
+    static const int cells[] = {4, 8, 12};
+    static const double rate[] = {226.0, 461.0, 403.0};
+    for (int i = 0; i < 3; i++)
+        if (maxL <= 64u * (uint32_t)cells[i]) {
+            g->T = 64;
+            g->B = cells[i];
+            return true;
+        }
+    double best = 0;
+    bool found = false;
+    for (int i = 1; i < 3; i++) {
+        const int b = cells[i];
+        const uint32_t strips = (maxL + 64u * b - 1) / (64u * b);
+        if (strips > 40u) continue;
+        const double cost = (double)(strips * 64u * b) / rate[i];
+        if (!found || cost < best) {
+            best = cost;
+            g->T = (int)strips * 64;
+            g->B = b;
+            found = true;
+        }
+    }
+    return found;
+}
+NOINLINE static void test_geometry() {
+    g_case = "dp_geom_for";
+    struct Case {
+        uint32_t maxL;
+        int T, B;  // T = 0: no geometry
+    };
+    const Case cases[] = {{1, 64, 4},       {256, 64, 4},     {257, 64, 8},       {512, 64, 8},       {513, 64, 12},
+                          {768, 64, 12},    {769, 128, 8},    {1024, 128, 8},     {1025, 192, 8},     {10240, 1280, 8},
+                          {20480, 2560, 8}, {20481, 1728, 12}, {30720, 2560, 12}, {30721, 0, 0}};
+    for (const Case &c : cases) {
+        DpGeom g{-1, -1};
+        const bool ok = dp_geom_for(c.maxL, 0, 0, &g);
+        CHECK(ok == (c.T != 0), "maxL %u: %s", c.maxL, ok ? "a geometry where none covers it" : "no geometry");
+        if (ok) CHECK(g.T == c.T && g.B == c.B, "maxL %u: (%d, %d), expected (%d, %d)", c.maxL, g.T, g.B, c.T, c.B);
+    }
+    // every length: what pick_geom answered; and with the rates as measured, B = 12 wins no multi-strip launch that
+    // B = 8 has the strips for (up to 40 x 512 = 20480 columns) -- whoever re-measures kLaneRate sees that move here
+    for (uint32_t maxL = 1; maxL <= 31000; maxL++) {
+        DpGeom g{-1, -1}, w{-1, -1};
+        const bool ok = dp_geom_for(maxL, 0, 0, &g), want = geom_before(maxL, &w);
+        CHECK(ok == want && (!ok || (g.T == w.T && g.B == w.B)), "maxL %u: (%d, %d), pick_geom gave (%d, %d)", maxL, g.T, g.B, w.T, w.B);
+        CHECK(ok == (maxL <= 30720), "maxL %u: covered %d", maxL, (int)ok);
+        if (ok) CHECK((uint32_t)g.Lp() >= maxL && g.T % 64 == 0 && g.T <= 64 * kMaxStrips, "maxL %u: (%d, %d) does not cover it", maxL, g.T, g.B);
+        if (maxL > 768 && maxL <= 20480) CHECK(g.B == 8, "maxL %u: B = %d where B = 8 has the strips", maxL, g.B);
+        if (maxL > 20480 && ok) CHECK(g.B == 12, "maxL %u: B = %d beyond B = 8's 40 strips", maxL, g.B);
+    }
+    // a forced geometry: taken if the kernels have it and it covers maxL ...
+    auto forced = [](uint32_t maxL, int T, int B) {
+        DpGeom g{-1, -1};
+        CHECK(dp_geom_for(maxL, T, B, &g), "maxL %u forced (%d, %d): no geometry", maxL, T, B);
+        return g;
+    };
+    auto is = [](const DpGeom &g, int T, int B) { return g.T == T && g.B == B; };
+    CHECK(is(forced(900, 128, 8), 128, 8), "forced (128, 8)");
+    CHECK(is(forced(900, 256, 4), 256, 4) && is(forced(900, 192, 12), 192, 12) && is(forced(1, 64 * 40, 12), 2560, 12), "forced, accepted");
+    // ... else ignored: the unforced answer for 900 bases is (128, 8)
+    CHECK(is(forced(900, 0, 0), 128, 8), "unforced");
+    CHECK(is(forced(900, 64, 12), 128, 8), "forced (64, 12) covers 768 of 900 bases");
+    CHECK(is(forced(900, 96, 12), 128, 8), "forced T = 96");
+    CHECK(is(forced(900, 64 * 41, 4), 128, 8), "forced T = 64 * 41");
+    CHECK(is(forced(900, 256, 6), 128, 8), "forced B = 6");
+    CHECK(is(forced(900, 0, 8), 128, 8) && is(forced(900, -128, 8), 128, 8), "forced T <= 0");
+    DpGeom none{-1, -1};
+    CHECK(!dp_geom_for(30721, 64 * 40, 12, &none), "a forced geometry that does not cover the query made one");
+}
+
+// ------------------------------------------------------------------------------------------------ dp_ring_plan
+NOINLINE static void test_ring_plan() {
+    g_case = "dp_ring_plan";
+    const size_t want_lds[] = {6192, 12336, 18480};
+    for (int i = 0; i < 3; i++) {
+        const DpGeom g{128, 4 * (i + 1)};
+        const size_t slot = dp_slot_bytes(g);
+        CHECK(slot == (size_t)64 * g.B * 8 + 16, "slot bytes");
+        auto plan = [&](size_t budget) {
+            DpPlan pl{};
+            dp_ring_plan(g, budget, &pl);
+            CHECK(pl.geom.T == g.T && pl.geom.B == g.B && pl.lds == (size_t)pl.W * slot, "B %d budget %zu: geometry / lds", g.B, budget);
+            return pl.W;
+        };
+        DpPlan def{};
+        dp_ring_plan(g, 0, &def);
+        CHECK(def.W == 3 && def.lds == want_lds[i], "B %d: default ring %d, %zu bytes", g.B, def.W, def.lds);
+        CHECK(plan(dp_default_lds_budget(g)) == 3, "B %d: the default budget, given", g.B);
+        CHECK(plan(1) == 1 && plan(slot - 1) == 1, "B %d: a budget below one slot", g.B);
+        // (160 KB hold 26 slots and more: the clamp comes first, the ring's depth second)
+        CHECK(160 * 1024 / slot > (size_t)kDpMaxRing && plan(1u << 20) == kDpMaxRing && kDpMaxRing == 8, "B %d: 1 MB", g.B);
+        for (int k = 2; k <= kDpMaxRing; k++)
+            CHECK(plan(k * slot) == k && plan(k * slot - 1) == k - 1, "B %d: budgets around %d slots", g.B, k);
+        CHECK(plan((kDpMaxRing + 1) * slot) == kDpMaxRing, "B %d: nine slots' budget", g.B);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ bt_by_lanes
+NOINLINE static void test_lanes_rule() {
+    g_case = "bt_by_lanes";
+    CHECK(!bt_by_lanes(8191, 2048, -1) && bt_by_lanes(8192, 2048, -1) && !bt_by_lanes(8192, 2049, -1), "thresholds");
+    CHECK(bt_by_lanes(1u << 20, 64, -1) && !bt_by_lanes(1, 64, -1) && !bt_by_lanes(1u << 20, 4096, -1), "far from the thresholds");
+    for (uint32_t nq : {1u, 8191u, 8192u})
+        for (uint32_t cap : {2048u, 2049u})
+            CHECK(!bt_by_lanes(nq, cap, 0) && bt_by_lanes(nq, cap, 1), "forced, %u queries of %u bases", nq, cap);
+}
+
 // ------------------------------------------------------------------------------------------------ --words
 // `dp_plan_check --words FILE RING`: prep_range's words of one DAG read from FILE, for tests/test_graph_cpu.py to compare
 // with tests/graph_ref.py dp_words.  FILE is text: N E, then N columns, N masks, N weights (float bits), N + 1 pred_off,
@@ -535,7 +643,7 @@ NOINLINE static int print_words(const char *path, int W) {
     FILE *f = fopen(path, "r");
     CHECK(f != nullptr, "cannot read %s", path);
     unsigned n = 0, e = 0;
-    CHECK(fscanf(f, "%u %u", &n, &e) == 2 && W >= 1 && W <= kMaxRing, "header / ring");
+    CHECK(fscanf(f, "%u %u", &n, &e) == 2 && W >= 1 && W <= kDpMaxRing, "header / ring");
     Dag d;
     d.pos.resize(n), d.mask.resize(n), d.weight.resize(n), d.pred_off.resize(n + 1), d.pred.resize(e);
     auto read = [&](uint32_t *out) {
@@ -578,6 +686,9 @@ int main(int argc, char **argv) {
     test_family_qdescs();
     test_sweep_and_rho();
     test_classify();
+    test_geometry();
+    test_ring_plan();
+    test_lanes_rule();
     printf("dp_plan_check: ok\n");
     return 0;
 }

@@ -1,5 +1,5 @@
 """The planning code of the DP driver (sina_amd/csrc/dp_plan.h: launch ranges, slot allocation, spill rows, the
-row-skip bound, family sharing, the rho update) against plain models, on the CPU: tests/dp_plan_check.cpp, a
+row-skip bound, family sharing, the rho update, the launch geometry, the LDS ring, lanes or waves for the walk) against plain models, on the CPU: tests/dp_plan_check.cpp, a
 stand-alone program, built with the address and undefined-behaviour sanitizers and run once."""
 import os
 import shutil
