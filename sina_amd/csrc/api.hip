@@ -184,7 +184,7 @@ static int align_graphs_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, con
         const uint64_t ebase = g->edge_off[q0], ne = g->edge_off[q1] - ebase;
         const uint64_t qbase = qoff[q0], nqm = qoff[q1] - qbase;
         if (c->qd.reserve(sizeof(QDesc) * bq) || c->rec.reserve(sizeof(uint4) * nn) || c->node_pos.reserve(4 * nn) ||
-            c->pred.reserve(4 * std::max<uint64_t>(ne, 1)) || c->succ_minpos.reserve(4 * nn) ||
+            c->pred.reserve(4 * std::max<uint64_t>(ne, 1)) || c->pred4.reserve(sizeof(uint2) * nn) || c->succ_minpos.reserve(4 * nn) ||
             c->qmask.reserve(nqm) || (pp.on && c->rgain.reserve(8 * nn)))
             return 1;
         hipStream_t s = c->stream;
@@ -192,6 +192,7 @@ static int align_graphs_impl(sina_hip_ctx *c, const sina_hip_graph_batch *g, con
         SH_CHECK(hipMemcpyAsync(c->rec.p, hp.rec.data(), sizeof(uint4) * nn, hipMemcpyHostToDevice, s));
         SH_CHECK(hipMemcpyAsync(c->node_pos.p, g->node_pos + nbase, 4 * nn, hipMemcpyHostToDevice, s));
         if (ne) SH_CHECK(hipMemcpyAsync(c->pred.p, hp.pred.data(), 4 * ne, hipMemcpyHostToDevice, s));
+        SH_CHECK(hipMemcpyAsync(c->pred4.p, hp.pred4.data(), sizeof(uint2) * nn, hipMemcpyHostToDevice, s));
         if (g->succ_minpos)
             SH_CHECK(hipMemcpyAsync(c->succ_minpos.p, g->succ_minpos + nbase, 4 * nn, hipMemcpyHostToDevice, s));
         SH_CHECK(hipMemcpyAsync(c->qmask.p, qmask + qbase, nqm, hipMemcpyHostToDevice, s));

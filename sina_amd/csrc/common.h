@@ -202,6 +202,13 @@ static_assert(sizeof(QDesc) == 64, "uploaded as an array");
 // rows away (kRecFence), goes to a spill row in HBM instead.
 // Predecessor entries, ascending ids (= the reference's evaluation order, which decides ties):
 //   id | (LDS slot or spill row index) << 16 | spilled << 31
+// pred4, beside the records and indexed like them: the ids of a row's first four predecessors, 4 x u16 in 8 bytes
+// (x = id 0 | id 1 << 16, y = id 2 | id 3 << 16; zero where the row has no such predecessor).  Every builder that
+// writes predecessor entries writes it; the trace-back walk (traceback.hip) reads it together with the row's record,
+// so that the row a cell points at costs no round trip of its own.
+__host__ __device__ inline uint2 pred4_pack(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3) {
+    return uint2{(p0 & 0xffffu) | (p1 << 16), (p2 & 0xffffu) | (p3 << 16)};
+}
 constexpr uint32_t kRecSink = 1u << 16;
 constexpr uint32_t kRecFence = 1u << 17;
 // flags bits 2..7 (z bits 18..23): how far back the row's furthest predecessor is, in rows (1..62; 63: further, or
@@ -365,6 +372,7 @@ struct BtArgs {
     const QDesc *qd;
     const uint4 *rec;
     const uint32_t *pred;
+    const uint2 *pred4;  // per row: its first four predecessor ids (pred4_pack), indexed like rec
     const uint32_t *node_pos;
     const void *tb;  // u16 cells if lazy_sidx, else u32
     const DpResult *res;

@@ -189,6 +189,7 @@ struct sina_hip_ctx {
     sina_hip::DevBuf qd, order, rec, node_pos, pred, succ_minpos, qmask, spill, edge, res, weights, out, out_pos, dbg;
     sina_hip::DevBuf prof16, self16;  // --fs-no-graph: match-term tables of a profile batch (sina_hip_graph_batch)
     sina_hip::DevBuf rgain;           // per DAG node: bound on the gain still to come (the DP kernel's row skip, common.h)
+    sina_hip::DevBuf pred4;           // per DAG node: its first four predecessor ids (common.h, pred4_pack), beside rec
     sina_hip::DevBuf wset;            // per query of a launch: which of the call's weight vectors is its own (the _wsets entries)
     // the wide path (mesh_wide.hip): a launch's inputs, and its mesh -- every cell's fields in HBM; grow-only, apart from
     // the trace-back pool above, allocated by the first query that needs it
@@ -225,7 +226,7 @@ struct sina_hip_ctx {
 
     size_t lds_budget = 0;  // LDS per DP workgroup; 0 = what keeps the register-limited occupancy (dp_default_lds_budget)
 
-    static constexpr int kNumScratch = 50;
+    static constexpr int kNumScratch = 51;
     static_assert(kNumScratch <= 64, "sina_hip_store::cap_hint is too short");
     void scratch(sina_hip::DevBuf **all) {
         sina_hip::DevBuf *list[kNumScratch] = {&qd, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &res,
@@ -234,7 +235,7 @@ struct sina_hip_ctx {
                                                &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &order,
                                                &s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &edge, &prof16, &self16, &rgain,
                                                &scout, &scout_u, &wset, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag,
-                                               &r_cnt, &inplace[sina_hip::kInplacePairs].rows, &inplace[sina_hip::kInplaceIdentity].rows};
+                                               &r_cnt, &inplace[sina_hip::kInplacePairs].rows, &inplace[sina_hip::kInplaceIdentity].rows, &pred4};
         for (int i = 0; i < kNumScratch; i++) all[i] = list[i];
     }
     void publish_hints() {  // after a call: remember how big my buffers had to be
@@ -262,7 +263,7 @@ struct sina_hip_ctx {
     int prewarm(int kind) {
         sina_hip::DevBuf *search[] = {&k_qoff, &k_scores, &k_out_ids, &k_out_scores, &k_out_n, &k_tmp0, &k_tmp1, &k_tmp2, &qmask,
                                       &s_qab, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};  // (s_qab, r_*: sina_hip_kmer_topk_rank)
-        sina_hip::DevBuf *align[] = {&qd, &order, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &edge, &res, &weights, &out,
+        sina_hip::DevBuf *align[] = {&qd, &order, &rec, &node_pos, &pred, &pred4, &succ_minpos, &qmask, &spill, &edge, &res, &weights, &out,
                                      &out_pos, &g_fam_ids, &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &rgain, &scout, &scout_u,
                                      &prof16, &self16, &wset, &inplace[sina_hip::kInplacePairs].rows, &inplace[sina_hip::kInplaceIdentity].rows};
         sina_hip::DevBuf *compare[] = {&s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};

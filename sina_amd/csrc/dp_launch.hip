@@ -127,6 +127,7 @@ int fill_args(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const sina
     b->qd = a->qd;
     b->rec = a->rec;
     b->pred = a->pred;
+    b->pred4 = c->pred4.as<uint2>();
     b->node_pos = a->node_pos;
     b->res = a->res;
     b->weights = a->weights;

@@ -140,13 +140,16 @@ inline void dp_ring_plan(const DpGeom &g, size_t budget_override, DpPlan *pl) {
 }
 
 // Launches of kBtLanesMin queries and more, none longer than kBtLanesMaxLen, walk one lane per query
-// (backtrack_lanes_kernel, traceback.hip).  The lanes' walk takes a microsecond per step whatever the launch (3.2 ms for 16S), the
-// waves' walk 0.33 us of the device's instruction issue per query: at 9216 queries the two are the same 3 ms, and
-// the lanes' are latency that the launches queued behind on the other FIFO stream cover (k-mer search 5.8 ms, DAG
-// build 4.5) where the waves' are instructions taken from them.  A smaller launch is done sooner by waves -- with
-// half the queries duplicates (4608 per launch, neighbours of 2-3 ms) lanes cost 6 %: 380 k against 406 k sequences/s,
-// on the FIFO stream or off it -- and a launch of 23S-long queries (6000 steps, 14 ms) is waited for by a pipeline
-// that holds two batches of them.  forced: SINA_HIP_TEST=bt_lanes=0/1 forces one (-1: none).
+// (backtrack_lanes_kernel, traceback.hip).  The lanes' walk takes 1.4 us per step whatever the launch (2.2 ms for 16S; 2 us
+// and 3.1 ms before a step fetched its cell, record and predecessors together, round 11), the waves' walk 0.27 us of
+// the device's instruction issue per query (2.5 ms at 9216 queries, 1.1 at 3072): at 9216 queries the lanes' are
+// latency that the launches queued behind on the other FIFO stream cover where the waves' are instructions taken
+// from them.  Re-measured in round 11 with the shorter lane walk (profiles/r11_walk_onetrip_ab.txt), the rule stands:
+// the headline with waves forced is below every run with lanes; with half the queries duplicates (4608 per launch)
+// lanes and waves are within each other's run-to-run band, where lanes cost 6-8 % before; and a launch of
+// 23S-long queries (6000 steps; lanes 12 ms in the pipeline, 16 before) is waited for by a pipeline that holds two
+// batches of them -- 95 k sequences/s with lanes against 101 k with waves.  forced: SINA_HIP_TEST=bt_lanes=0/1 forces
+// one (-1: none).
 constexpr uint32_t kBtLanesMin = 8192, kBtLanesMaxLen = 2048;
 inline bool bt_by_lanes(uint32_t nq, uint32_t asm_cap, int forced) {
     if (forced >= 0) return forced != 0;
@@ -317,6 +320,7 @@ struct HostPrep {
     std::vector<uint2> rgain;     // the DP kernel's row-skip bound per node + its last successor (common.h), filled when kappa64 > 0
     bool rgain_ok = true;         // ... and valid: every DAG of the range is laid out by columns
     std::vector<uint32_t> pred;  // id | (LDS slot or spill row) << 16 | spilled << 31 (what mesh_dp_kernel reads)
+    std::vector<uint2> pred4;    // per node, beside rec: its first four predecessor ids (common.h, pred4_pack; what the walk reads)
     std::vector<uint32_t> last;  // scratch: last successor per row
 };
 
@@ -328,6 +332,7 @@ inline int prep_range(const sina_hip_graph_batch *g, const uint64_t *qoff, uint3
     const uint64_t nn = g->node_off[q1] - nbase;
     hp->qd.resize(q1 - q0);
     hp->rec.resize(nn);
+    hp->pred4.resize(nn);
     hp->rgain.assign(kappa64 > 0.f ? nn : 0, uint2{0u, 0u});
     hp->rgain_ok = true;
     hp->pred.resize(g->edge_off[q1] - ebase + 8);
@@ -409,8 +414,10 @@ inline int prep_range(const sina_hip_graph_batch *g, const uint64_t *qoff, uint3
         for (uint32_t m = 0; m < N; m++) {
             uint32_t first_far = 0;
             uint32_t dist = po[m + 1] > po[m] ? 0u : kRecDistFar;
+            uint32_t p4[4] = {0u, 0u, 0u, 0u};
             for (uint32_t e = po[m]; e < po[m + 1]; e++) {
                 const uint32_t p = g->pred[eo + e];
+                if (e - po[m] < 4u) p4[e - po[m]] = p;
                 const uint32_t pw = rec[p].w == kRowNone ? 0u : rec[p].w;  // (kRowNone: in registers for this row)
                 const bool sp = (pw & kRowSpilled) != 0;
                 if (sp && first_far == 0) first_far = e - po[m] + 1;
@@ -418,6 +425,7 @@ inline int prep_range(const sina_hip_graph_batch *g, const uint64_t *qoff, uint3
                 hp->pred[d.edge_off + e] = p | ((pw & 0x7FFFu) << 16) | (sp ? kPredSpilled : 0u);
             }
             rec[m].z |= (first_far << 24) | (std::min(dist, kRecDistFar) << kRecDistShift);
+            hp->pred4[d.node_off + m] = pred4_pack(p4[0], p4[1], p4[2], p4[3]);
         }
         if (nsp > kMaxSpillRows) {
             if (spill_q) *spill_q = q;

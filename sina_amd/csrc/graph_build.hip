@@ -90,7 +90,8 @@ struct GraphArgs {
     uint32_t *succ_min;        // [nq][ncap]
     uint32_t *far_mark;        // [nq][ncap] last successor row of every node (0: none)
     uint32_t *pred;            // per query area of total-family-bases entries
-    uint32_t *sizes;           // [nq][kBuiltWords]: N, raw edge entries, n_spill, status, first sink row, gmin, chain length (common.h, kBuiltN ...)
+    uint2 *pred4;              // [nq][ncap] ids of every node's first four predecessors (step 8; common.h, pred4_pack)
+    uint32_t *sizes;          // [nq][kBuiltWords]: N, raw edge entries, n_spill, status, first sink row, gmin, chain length (common.h, kBuiltN ...)
     uint16_t *chain_rows;      // [nq][ncap]: the node of every base of member 0, in base order (the DP wave's scout pass walks this chain)
     uint32_t width, ncap;
     uint32_t tile_bytes;       // LDS bytes of the tile tables (reused by the slot allocation) = bitmap_off
@@ -721,12 +722,15 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
     }
     __syncthreads();
     GP(10)
-    // 8. predecessor entries for the DP kernel: id | (LDS slot or spill row) << 16 | spilled << 31
+    // 8. predecessor entries for the DP kernel: id | (LDS slot or spill row) << 16 | spilled << 31; the first four
+    // ids once more, by row, for the trace-back walk (pred4: N <= ncap here)
+    uint2 *pred4 = a.pred4 + (size_t)q * a.ncap;
     for (uint32_t i = tid; i < N; i += kGT) {
         const uint4 r = rec[i];
         const uint32_t np = r.z & 0xFFu;
         uint32_t first_far = 0;
         uint32_t dist = np ? 0u : kRecDistFar;  // (ids ascend: the first predecessor is the furthest)
+        uint32_t p4[4] = {0u, 0u, 0u, 0u};
         for (uint32_t x = 0; x < np; x++) {
             const uint32_t pa = pred[r.x + x];
             uint32_t pw = in_lds ? codeL[pa] : rec[pa].w;
@@ -735,8 +739,13 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
             if (sp && first_far == 0) first_far = x + 1;
             dist = max(dist, i - pa);
             pred[r.x + x] = pa | ((pw & 0x7FFFu) << 16) | (sp ? kPredSpilled : 0u);
+            if (x == 0) p4[0] = pa;
+            else if (x == 1) p4[1] = pa;
+            else if (x == 2) p4[2] = pa;
+            else if (x == 3) p4[3] = pa;
         }
         rec[i].z = r.z | (first_far << 24) | (min(dist, kRecDistFar) << kRecDistShift);
+        pred4[i] = pred4_pack(p4[0], p4[1], p4[2], p4[3]);
     }
     GP(11)
     // 9. the DP kernel's row-skip bound (common.h "the bound", mesh_dp.hip PRUNE): R(m) = what a path can still gain
@@ -846,7 +855,7 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
             c->g_tmp1.reserve(8 * (uint64_t)bq) ||
             c->rec.reserve(sizeof(uint4) * (uint64_t)bq * ncap) || c->node_pos.reserve(4 * (uint64_t)bq * ncap) ||
             c->succ_minpos.reserve(4 * (uint64_t)bq * ncap) || c->g_tmp3.reserve(4 * (uint64_t)bq * ncap) ||
-            c->pred.reserve(4 * pred_total) || c->g_sizes.reserve(4 * kBuiltWords * (uint64_t)bq) ||
+            c->pred.reserve(4 * pred_total) || c->pred4.reserve(sizeof(uint2) * (uint64_t)bq * ncap) || c->g_sizes.reserve(4 * kBuiltWords * (uint64_t)bq) ||
             c->scout.reserve(2 * (uint64_t)bq * ncap) ||
             (kappa64 > 0.f && c->rgain.reserve(8 * (uint64_t)bq * ncap)))
             return 1;
@@ -866,6 +875,7 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
         ga.succ_min = c->succ_minpos.as<uint32_t>();
         ga.far_mark = c->g_tmp3.as<uint32_t>();
         ga.pred = c->pred.as<uint32_t>();
+        ga.pred4 = c->pred4.as<uint2>();
         ga.sizes = c->g_sizes.as<uint32_t>();
         ga.chain_rows = c->scout.as<uint16_t>();
         ga.width = c->st->width;
@@ -900,7 +910,7 @@ int build_family_graphs(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64_t
         {
             uint64_t bytes = 0;  // algorithmic: the families' bases in, the DAGs out
             for (uint32_t q = 0; q < bq; q++)
-                bytes += 4 * elems[q] + (uint64_t)bg->sizes[kBuiltWords * q + kBuiltN] * (16 + 4 + (kappa64 > 0.f ? 8 : 0)) +
+                bytes += 4 * elems[q] + (uint64_t)bg->sizes[kBuiltWords * q + kBuiltN] * (16 + 4 + 8 + (kappa64 > 0.f ? 8 : 0)) +
                          4 * (uint64_t)bg->sizes[kBuiltWords * q + kBuiltEdges];
             std::lock_guard<std::mutex> slk(c->st->stats_mu);
             c->st->stats.graph_ms += gms;

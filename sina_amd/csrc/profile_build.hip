@@ -78,7 +78,8 @@ struct ProfileArgs {
     uint32_t *node_pos;       // [n][ncap]
     uint32_t *succ_min;       // [n][ncap]
     uint32_t *pred;           // [n][pred_stride]
-    float *prof16;            // [n][ncap][16]
+    uint2 *pred4;             // [n][ncap] the first four predecessor ids of every node (common.h, pred4_pack): the one before it
+    float *prof16;           // [n][ncap][16]
     uint32_t *sizes;          // [n][kBuiltWords]: N, edges, 0, status (0 or kBuiltNodeCap: more than ncap or 65535 nodes), first sink row, 0
     uint32_t width, ncap, pred_stride;
     uint32_t tile_nodes;      // nodes per LDS tile
@@ -190,6 +191,7 @@ __global__ void __launch_bounds__(kPT) family_profile_kernel(ProfileArgs a) {
         uint32_t *node_pos = a.node_pos + (size_t)q * a.ncap;
         uint32_t *smin = a.succ_min + (size_t)q * a.ncap;
         uint32_t *pred = a.pred + (size_t)q * a.pred_stride;
+        uint2 *pred4 = a.pred4 + (size_t)q * a.ncap;
         for (uint32_t w = tid; w < nwords; w += kPT) {
             uint32_t bits = bitmap[w], n = wrank[w];
             while (bits) {
@@ -207,6 +209,7 @@ __global__ void __launch_bounds__(kPT) family_profile_kernel(ProfileArgs a) {
             r.z = (n > 0 ? 1u : 0u) | (n + 1 == N ? kRecSink : 0u) | ((n > 0 ? 1u : kRecDistFar) << kRecDistShift);
             r.w = kRowNone;             // (only the next row reads it: handed over in registers)
             rec[n] = r;
+            pred4[n] = pred4_pack(n > 0 ? n - 1u : 0u, 0u, 0u, 0u);
             if (n + 1 < N) pred[n] = n;  // entry n: node n + 1's predecessor
         }
         if (tid == 0) {
@@ -418,6 +421,7 @@ int build_family_profiles(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64
         const uint32_t pred_stride = ncap + 8;  // (slack behind every list, like the DAG build's)
         if (c->rec.reserve(sizeof(uint4) * (uint64_t)n * ncap) || c->node_pos.reserve(4 * (uint64_t)n * ncap) ||
             c->succ_minpos.reserve(4 * (uint64_t)n * ncap) || c->pred.reserve(4 * (uint64_t)n * pred_stride) ||
+            c->pred4.reserve(sizeof(uint2) * (uint64_t)n * ncap) ||
             c->prof16.reserve(64 * (uint64_t)n * ncap))
             return 1;
         ProfileArgs pa;
@@ -429,6 +433,7 @@ int build_family_profiles(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64
         pa.node_pos = c->node_pos.as<uint32_t>();
         pa.succ_min = c->succ_minpos.as<uint32_t>();
         pa.pred = c->pred.as<uint32_t>();
+        pa.pred4 = c->pred4.as<uint2>();
         pa.prof16 = c->prof16.as<float>();
         pa.sizes = c->g_sizes.as<uint32_t>();
         pa.width = c->st->width;
@@ -471,7 +476,7 @@ int build_family_profiles(sina_hip_ctx *c, const uint32_t *fam_ids, const uint64
             std::lock_guard<std::mutex> slk(c->st->stats_mu);
             c->st->stats.graph_ms += gms;
             if (!need_n) {
-                c->st->stats.graph_bytes += 4 * bases + nodes * (16 + 4 + 4 + 4 + 64);
+                c->st->stats.graph_bytes += 4 * bases + nodes * (16 + 4 + 4 + 4 + 8 + 64);
                 c->st->stats.graph_launches++;
             }
         }

@@ -5,7 +5,8 @@
 // kTbOpLast), and, where they are plain, the cseq container steps and the NAST fix-up (assemble_kernel).
 // How it maps to the hardware: the walk is one logical thread per query, a chain of dependent look-ups -- one WAVE per
 // query with a window of the plane in LDS (backtrack_kernel), or one LANE per query with plain global loads
-// (backtrack_lanes_kernel) for large launches of short queries; which: bt_by_lanes (dp_plan.h).  assemble_kernel is one
+// (backtrack_lanes_kernel) for large launches of short queries; which: bt_by_lanes (dp_plan.h).  Either way a step
+// fetches its cell, the row's record and the row's first four predecessor ids (pred4) together.  assemble_kernel is one
 // wave per query.  Built with the fill kernels' extra flags (Makefile): its code stays what it was inside mesh_dp.hip.
 #include <cstdlib>
 #include <type_traits>
@@ -18,11 +19,26 @@ namespace sina_hip {
 namespace {
 
 // The cell walk of backtrack() (mesh.h:594-721) reads three things of the trace-back plane: cells, row records
-// and predecessor entries.  Two memory policies fetch them; walk_query() below is the walk itself.  A policy
-// offers cell(row, col), rec(row) (the row record, .w replaced by the node's column), pred(row, pb, e)
-// (predecessor entry e of the row, whose first is pb = rec.x) and `writes`: whether this thread stores the
-// query's output.  LAZY: 16-bit cells (type code + predecessor ordinal) instead of 32-bit ones.
+// and predecessor ids.  Two memory policies fetch them; walk_query() below is the walk itself.  A policy
+// offers at(row, col) -- everything the walk needs of a cell, see BtAt --, cell(row, col) alone (the insertion
+// scan), pred_far(pb, e) (predecessor entry e >= 4 of a row whose first is pb = rec.x) and `writes`: whether
+// this thread stores the query's output.  LAZY: 16-bit cells (type code + predecessor ordinal) instead of 32-bit ones.
 //
+// What a step knows once it knows (row, col): the cell, the row's record (.w replaced by the node's column) and
+// the ids of its first four predecessors (pred4, common.h).  None of the three depends on another, so a policy
+// issues their loads together: one round trip per step where looking the predecessor entry up through the
+// record's .x, then the cell, then the next record took three.
+struct BtAt {
+    uint32_t c;
+    uint4 r;
+    uint2 p4;
+    __device__ uint32_t npred() const { return r.z & 0xffu; }
+    __device__ uint32_t pred_near(uint32_t e) const {  // e < 4
+        const uint32_t w = (e & 2u) ? p4.y : p4.x;
+        return (e & 1u) ? w >> 16 : w & 0xffffu;
+    }
+};
+
 // BtDirect: plain global loads, one lane per query (backtrack_lanes_kernel).
 template <bool LAZY>
 struct BtDirect {
@@ -30,25 +46,37 @@ struct BtDirect {
     static constexpr bool writes = true;
     const cell_t *tb;
     const uint4 *recs;
+    const uint2 *pred4;
     const uint32_t *node_pos, *preds;
     uint32_t Lp;
     __device__ BtDirect(const BtArgs &a, const QDesc &d)
-        : tb(reinterpret_cast<const cell_t *>(a.tb) + d.tb_off), recs(a.rec + d.node_off), node_pos(a.node_pos + d.node_off),
-          preds(a.pred + d.edge_off), Lp(a.Lp) {}
+        : tb(reinterpret_cast<const cell_t *>(a.tb) + d.tb_off), recs(a.rec + d.node_off), pred4(a.pred4 + d.node_off),
+          node_pos(a.node_pos + d.node_off), preds(a.pred + d.edge_off), Lp(a.Lp) {}
     __device__ uint32_t cell(uint32_t row, uint32_t col) const { return (uint32_t)tb[(size_t)row * Lp + col]; }
-    __device__ uint4 rec(uint32_t row) const {  // (a caller that reads no .w loads no column)
+    __device__ uint4 rec(uint32_t row) const {
         uint4 rx = recs[row];
         rx.w = node_pos[row];
         return rx;
     }
-    __device__ uint32_t pred(uint32_t, uint32_t pb, uint32_t e) const { return preds[pb + e] & 0xffffu; }
+    __device__ BtAt at(uint32_t row, uint32_t col) const {  // four loads, none waiting for another
+        BtAt x;
+        x.c = cell(row, col);
+        x.r = recs[row];
+        x.r.w = node_pos[row];
+        x.p4 = pred4[row];
+        // All of it in registers HERE: left alone the compiler moves each word's load down to its first use, behind
+        // the branches of the walk -- a round trip each again.
+        asm volatile("" : "+v"(x.c), "+v"(x.r.x), "+v"(x.r.y), "+v"(x.r.z), "+v"(x.r.w), "+v"(x.p4.x), "+v"(x.p4.y));
+        return x;
+    }
+    __device__ uint32_t pred_far(uint32_t pb, uint32_t e) const { return preds[pb + e] & 0xffffu; }
 };
 
 // BtWindow: one wave per query (backtrack_kernel).  There the walk is one logical thread (every lane computes the
 // same thing) -- a chain of dependent look-ups, two per step when they go to HBM.  It only ever moves to smaller
 // rows and smaller columns, so the wave keeps a WINDOW of the trace-back plane in LDS: the 64 rows x 32 columns
 // whose upper right corner is the cell that missed, one row per lane, together with those rows' records, columns
-// and first four predecessors.  A step inside the window costs LDS latency; a refill (two round trips, every ~30
+// and first four predecessors.  A step inside the window costs LDS latency; a refill (one round trip, every ~30
 // steps) is paid by 64 lanes at once.  Lane 0 writes.
 constexpr int kBtRows = 64, kBtCols = 32;
 template <bool LAZY>
@@ -58,7 +86,7 @@ struct BtWindow {
     struct Lds {
         cell_t cell[kBtRows][kBtCols];
         uint4 rec[kBtRows];   // row records, .w replaced by the node's column
-        uint4 pred[kBtRows];  // first four predecessor entries of the row
+        uint2 pred[kBtRows];  // ids of the row's first four predecessors (pred4)
     };
     BtDirect<LAZY> g;  // (refills and the look-ups outside the window)
     Lds &w;
@@ -79,15 +107,8 @@ struct BtWindow {
             uint4 *dst = reinterpret_cast<uint4 *>(&w.cell[lane][0]);
 #pragma unroll
             for (uint32_t i = 0; i < kBtCols / kAlign; i++) dst[i] = src[i];
-            const uint4 rx = g.rec(x);
-            w.rec[lane] = rx;
-            const uint32_t np = rx.z & 0xffu;
-            uint4 pe = {0u, 0u, 0u, 0u};
-            if (np > 0) pe.x = g.preds[rx.x];
-            if (np > 1) pe.y = g.preds[rx.x + 1];
-            if (np > 2) pe.z = g.preds[rx.x + 2];
-            if (np > 3) pe.w = g.preds[rx.x + 3];
-            w.pred[lane] = pe;
+            w.rec[lane] = g.rec(x);
+            w.pred[lane] = g.pred4[x];
         }
         __syncthreads();
     }
@@ -96,17 +117,14 @@ struct BtWindow {
         if (!(in_rows(row) && col - wc0 < (uint32_t)kBtCols)) refill(row, col);
         return (uint32_t)w.cell[row - wr0][col - wc0];
     }
-    __device__ uint4 rec(uint32_t row) const {
-        if (in_rows(row)) return w.rec[row - wr0];
-        return g.rec(row);
+    __device__ BtAt at(uint32_t row, uint32_t col) {
+        BtAt x;
+        x.c = cell(row, col);  // (first: a refill brings the row's record and predecessors along)
+        x.r = w.rec[row - wr0];
+        x.p4 = w.pred[row - wr0];
+        return x;
     }
-    __device__ uint32_t pred(uint32_t row, uint32_t pb, uint32_t e) const {
-        if (e < 4 && in_rows(row)) {
-            const uint4 pe = w.pred[row - wr0];
-            return (e == 0 ? pe.x : (e == 1 ? pe.y : (e == 2 ? pe.z : pe.w))) & 0xffffu;
-        }
-        return g.pred(row, pb, e);
-    }
+    __device__ uint32_t pred_far(uint32_t pb, uint32_t e) const { return g.pred_far(pb, e); }
 };
 
 // The walk of query q, from its DP result to its emitted columns (out_pos) and its sina_hip_align_out.
@@ -140,8 +158,8 @@ __device__ __forceinline__ void walk_query(const BtArgs &a, uint32_t q, const QD
     // right hand overhang (:594-615)
     const int tail = (int)(send - s);
     o.cutoff_tail = tail;
-    uint32_t c = mem.cell(m, s);  // (first: a window is filled around the end cell)
-    uint4 rm = mem.rec(m);
+    BtAt cur = mem.at(m, s);  // the cell the walk stands on, its row's record and predecessors
+    uint4 rm = cur.r;
     if (tail && a.overhang != SINA_OVERHANG_REMOVE) {
         int pos = (a.overhang == SINA_OVERHANG_ATTACH) ? (int)(width - 1 - rm.w - (uint32_t)tail) : 0;
         for (int i = 0; i < tail; i++) {
@@ -173,26 +191,28 @@ __device__ __forceinline__ void walk_query(const BtArgs &a, uint32_t q, const QD
     // value_midx of a cell whose deletion extends the gap of predecessor x: gapm_idx[x][col]
     // (common.h, Ext / OpLast) -- follow last predecessors to the row that opened the gap
     constexpr uint32_t ext_bit = LAZY ? kTb16Ext : kTbExt;
+    // predecessor e of the row of x: one of the four that came with it, or its entry in the list
+    auto pred_of = [&](const BtAt &x, uint32_t e) -> uint32_t { return e < 4u ? x.pred_near(e) : mem.pred_far(x.r.x, e); };
+    // (one round trip per hop: the hop's cell, record and last predecessor arrive together)
     auto gapm_idx = [&](uint32_t x, uint32_t col) -> uint32_t {
         for (uint32_t guard = 0; guard < 65536u; ++guard) {
-            const uint32_t cx = mem.cell(x, col);  // (first: a refill brings the row's record along)
-            const uint4 rx = mem.rec(x);
-            const uint32_t np = rx.z & 0xffu;
+            const BtAt ax = mem.at(x, col);
+            const uint32_t np = ax.npred();
             if (np == 0) return 0u;  // an edge row keeps its initial gapm_idx
-            const uint32_t lastp = mem.pred(x, rx.x, np - 1);
-            if (LAZY ? !(cx & kTb16XLast) : (cx & kTbOpLast) != 0) return lastp;
+            const uint32_t lastp = pred_of(ax, np - 1);
+            if (LAZY ? !(ax.c & kTb16XLast) : (ax.c & kTbOpLast) != 0) return lastp;
             x = lastp;
         }
         return 0u;
     };
-    // the row a cell of row `row` points at, before Ext is resolved: stored (32-bit cells), or the
+    // the row the cell x of row `row` points at, before Ext is resolved: stored (32-bit cells), or the
     // row itself / 0 / the predecessor with the stored ordinal (16-bit cells)
-    auto midx_raw = [&](uint32_t cc, uint32_t row, uint32_t pb) -> uint32_t {
-        if (!LAZY) return cc >> 16;
-        const uint32_t t = cc & kTbTypeMask;
+    auto midx_raw = [&](const BtAt &x, uint32_t row) -> uint32_t {
+        if (!LAZY) return x.c >> 16;
+        const uint32_t t = x.c & kTbTypeMask;
         if (t == kTbIns) return row;
         if (t == kTbNone) return 0u;
-        return mem.pred(row, pb, cc >> kTb16OrdShift);
+        return pred_of(x, x.c >> kTb16OrdShift);
     };
     // value_sidx of cell cc = (row, col): stored, or (type-code cells, common.h) what the type implies
     auto sidx_of = [&](uint32_t cc, uint32_t row, uint32_t col) -> uint32_t {
@@ -211,16 +231,18 @@ __device__ __forceinline__ void walk_query(const BtArgs &a, uint32_t q, const QD
     // :642-685 (a source node has no predecessors)
     uint32_t npred_m = rm.z & 0xffu;
     while (s != 0 && npred_m != 0) {
-        const uint32_t snew = sidx_of(c, m, s);
-        const uint32_t vm = midx_raw(c, m, rm.x);
-        m = (c & ext_bit) ? gapm_idx(vm, s) : vm;
-        c = mem.cell(m, snew);
-        if (snew != 0 && is_deletion_at(c, snew)) {  // the one-step deletion skip (:653-655)
-            const uint32_t vm2 = midx_raw(c, m, mem.rec(m).x);
-            m = (c & ext_bit) ? gapm_idx(vm2, snew) : vm2;
-            c = mem.cell(m, snew);
+        const uint32_t snew = sidx_of(cur.c, m, s);
+        const uint32_t vm = midx_raw(cur, m);
+        m = (cur.c & ext_bit) ? gapm_idx(vm, s) : vm;
+        // (the record comes with the cell, before the test below decides whether the walk stays on this row: a
+        // skipped row's record is dropped unread but for its predecessors)
+        cur = mem.at(m, snew);
+        if (snew != 0 && is_deletion_at(cur.c, snew)) {  // the one-step deletion skip (:653-655)
+            const uint32_t vm2 = midx_raw(cur, m);
+            m = (cur.c & ext_bit) ? gapm_idx(vm2, snew) : vm2;
+            cur = mem.at(m, snew);
         }
-        rm = mem.rec(m);
+        rm = cur.r;
         npred_m = rm.z & 0xffu;
         pos = width - 1 - rm.w;
         while (s != snew) {
@@ -263,9 +285,9 @@ __global__ void __launch_bounds__(64) backtrack_kernel(BtArgs a) {
 // wave's issue slots on one logical thread -- 60 instructions per step, 3000 steps, 9216 waves: 3 ms of a device
 // whose other kernels (the next batch's DAG build, k-mer search and DP, running beside it) are bound by instruction
 // issue as well.  Here a wave walks 64 queries: 64 times fewer instructions, every look-up a global load of its own
-// (cells 2 bytes, a 64-byte sector each: a quarter of the window refills' traffic), and the walk's latency -- a few
-// dependent round trips per step, the rare branches of any lane paid by the whole wave -- is hidden behind the
-// kernels it runs beside instead of competing with them.
+// (cells 2 bytes, a 64-byte sector each: a quarter of the window refills' traffic), and the walk's latency -- one
+// round trip per step, the cell's (BtDirect::at), the rare branches of any lane paid by the whole wave -- is hidden
+// behind the kernels it runs beside instead of competing with them.
 template <bool LAZY>
 __global__ void __launch_bounds__(64) backtrack_lanes_kernel(BtArgs a) {
     const uint32_t q = blockIdx.x * 64u + threadIdx.x;
