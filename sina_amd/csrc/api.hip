@@ -1,5 +1,6 @@
 // C-ABI entry points of include/sina_hip.h: context, reference store, alignment.
-// (k-mer entry points live in kmer.hip, the device DAG build in graph_build.hip, the DP driver in dp_launch.hip.)
+// (The k-mer search's entry points live in kmer_launch.hip, the index's in kmer_index.hip, the device DAG build in
+// graph_build.hip, the DP driver in dp_launch.hip.)
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -458,6 +459,66 @@ int sina_hip_upload_refs(sina_hip_ctx *c, const uint32_t *ab, const uint64_t *of
     c->st->total_bases = total;
     c->st->have_refs = true;
     c->st->have_name_order = false;  // (sina_hip_upload_name_order: the order belonged to the references before)
+    return 0;
+}
+
+int sina_hip_store_view_get(sina_hip_ctx *c, sina_hip_store_view *v) {
+    if (!c || !v) SH_FAIL("store_view_get: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->st->have_refs) SH_FAIL("store_view_get: no references uploaded");
+    memset(v, 0, sizeof(*v));
+    v->ref_ab = c->st->ref_ab.p;
+    v->ref_ab_bytes = 4 * c->st->total_bases;
+    v->ref_off = c->st->ref_off.p;
+    v->ref_off_bytes = 8 * ((uint64_t)c->st->n_refs + 1);
+    v->n_refs = c->st->n_refs;
+    v->width = c->st->width;
+    v->total_bases = c->st->total_bases;
+    if (c->st->have_index) {
+        v->idx_offsets = c->st->idx_off.p;
+        v->idx_offsets_bytes = 4 * ((1ull << (2 * c->st->k)) + 1);
+        v->idx_ids = c->st->idx_ids.p;
+        v->idx_ids_bytes = 4 * c->st->n_postings;
+        v->k = c->st->k;
+        v->nofast = c->st->nofast;
+        v->n_postings = c->st->n_postings;
+    }
+    return 0;
+}
+
+int sina_hip_store_alloc_like(sina_hip_ctx *c, sina_hip_store_view *v) {
+    if (!c || !v) SH_FAIL("store_alloc_like: null argument");
+    if (v->k < 1 || v->k > 12) SH_FAIL("store_alloc_like: k must be in 1..12");
+    if (!c->owns_store) SH_FAIL("store_alloc_like: a forked context cannot change the reference store");
+    std::lock_guard<std::mutex> lk(c->mu);
+    SH_CHECK(hipSetDevice(c->device));
+    const uint64_t nk = 1ull << (2 * v->k);
+    if (c->st->ref_ab.reserve(4 * std::max<uint64_t>(v->total_bases, 1)) ||
+        c->st->ref_off.reserve(8 * ((uint64_t)v->n_refs + 1)) || c->st->idx_off.reserve(4 * (nk + 1)) ||
+        c->st->idx_ids.reserve(4 * std::max<uint64_t>(v->n_postings, 1)))
+        return 1;
+    c->st->n_refs = v->n_refs;
+    c->st->width = v->width;
+    c->st->total_bases = v->total_bases;
+    c->st->k = v->k;
+    c->st->nofast = v->nofast;
+    c->st->n_postings = v->n_postings;
+    c->st->have_refs = c->st->have_index = true;
+    c->st->have_name_order = false;
+    c->st->dense_ready = false;  // (the index arrives by broadcast after this call: built by the first search)
+    {   // re-read from the device, once, after the broadcast filled it (ensure_ref_off_host)
+        std::lock_guard<std::mutex> alk(c->st->aux_mu);
+        c->st->ref_off_host_ready.store(false, std::memory_order_release);
+        c->st->ref_off_host.clear();
+    }
+    v->ref_ab = c->st->ref_ab.p;
+    v->ref_ab_bytes = 4 * v->total_bases;
+    v->ref_off = c->st->ref_off.p;
+    v->ref_off_bytes = 8 * ((uint64_t)v->n_refs + 1);
+    v->idx_offsets = c->st->idx_off.p;
+    v->idx_offsets_bytes = 4 * (nk + 1);
+    v->idx_ids = c->st->idx_ids.p;
+    v->idx_ids_bytes = 4 * v->n_postings;
     return 0;
 }
 

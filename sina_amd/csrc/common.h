@@ -15,6 +15,8 @@
 #include <ctime>
 
 #include "sina_hip.h"
+#include "kmer_plan.h"
+static_assert(sina_hip::kKmerMaxQueryLen == SINA_HIP_MAX_QUERY_LEN, "kmer_plan.h states the fast count kernel's limit by itself");
 
 namespace sina_hip {
 
@@ -470,5 +472,27 @@ int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const 
 // What a launch may skip rows with: the scoring of `p` (non-negative gap costs, the simple scheme), the
 // largest and smallest node weight it will see, its longest query.  SINA_HIP_DP_PRUNE=0: never.
 PrunePlan prune_plan(const sina_hip_align_params *p, float wmax, float wmin, uint32_t maxL, bool profile_batch);
+
+// ---- the k-mer search: kernels and launchers in kmer.hip, the store's index and dense bitmaps in kmer_index.hip, the
+// driver of a search call in kmer_launch.hip, every decision in kmer_plan.h
+// One launch range: nq queries whose masks and offsets are on the device.  The launchers read the store's index and
+// write the context's k_* buffers, which the driver has reserved for the range.
+struct KmerLaunch {
+    const uint8_t *qmask = nullptr;
+    const uint64_t *qoff = nullptr;  // nq + 1 offsets into qmask
+    uint32_t nq = 0;
+    uint32_t max = 0;                // top-M wanted of every query, at most the references there are
+    uint32_t max_qlen = 0;           // longest query the fast count kernel may meet (its LDS follows it)
+    KmerPath path = kKmerRows;       // the range's, from the plan ...
+    bool big = false;                // ... and whether its select is the big select
+    size_t big_tmp_bytes = 0;        // temporary storage of the big select's sort (reserve_kmer_big_select)
+};
+int launch_kmer_count(sina_hip_ctx *c, const KmerLaunch &l, hipStream_t s);
+int reserve_kmer_big_select(sina_hip_ctx *c, KmerLaunch *l);  // (before the range's launches: it may allocate)
+int launch_kmer_select(sina_hip_ctx *c, const KmerLaunch &l, hipStream_t s);  // (after launch_kmer_count, same stream)
+// fails unless the store has references and an index
+int index_ready(sina_hip_ctx *c);
+// the dense posting lists' bitmaps, built by the first search after the index changed
+int ensure_dense(sina_hip_ctx *c);
 
 }  // namespace sina_hip

@@ -23,7 +23,7 @@ struct sina_hip_store {
     uint32_t n_refs = 0, width = 0, k = 0, nofast = 0;
     uint64_t n_postings = 0, total_bases = 0;
     bool have_refs = false, have_index = false;
-    // Dense posting lists as bitmaps over the references (kmer.hip, ensure_dense): built lazily from
+    // Dense posting lists as bitmaps over the references (kmer_index.hip, ensure_dense): built lazily from
     // the CSR index by the first search after the index changed
     sina_hip::DevBuf dense_id, dense_bits;  // u32 [4^k]: bitmap number or ~0; u32 [n_dense][dense_words]
     uint32_t n_dense = 0, dense_words = 0;
@@ -196,7 +196,7 @@ struct sina_hip_ctx {
     sina_hip::DevBuf wide_in, wide_planes;
     uint64_t path_queries[sina_hip::kNumSlowPaths] = {};  // queries each slow path has taken on this context (read_path_queries)
     sina_hip::KernelUse use[sina_hip::kNumKernelUse];      // the counted kernels' own time and volume on this context (read_use)
-    // the big select (kmer.hip): a launch range's keys with their double buffer, and the segmented sort's temporary
+    // the big select (kmer.hip, reserve_kmer_big_select): a launch range's keys with their double buffer, and the segmented sort's temporary
     // storage -- grow-only, allocated by the first search that wants more than 4096 candidates
     sina_hip::DevBuf k_big_keys, k_big_tmp;
     sina_hip::DevBuf scout, scout_u;  // the scout pass (mesh_dp.hip): the DAG build's chain rows (u16 [DAGs][ncap]), and its result -- a bound U per query

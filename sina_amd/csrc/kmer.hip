@@ -23,40 +23,34 @@
 //           <= 4096 survivors.  More than 4096 wanted: the same cut search and ordered compaction leave the survivors
 //           as 64-bit keys in a per-query segment in HBM, one segmented radix sort orders every segment of the
 //           launch range, a small kernel unpacks the keys (kmer_select_big_kernel).
-#include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
+//
+// This unit: the count and select kernels, their argument structs and one launcher per stage (launch_kmer_count,
+// launch_kmer_select: common.h).  The index and the dense bitmaps are kmer_index.hip's, the driver of a search call
+// is kmer_launch.hip, and every decision either takes -- geometry, paths, launch ranges -- is kmer_plan.h's.
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
-#include <algorithm>
-#include <cstring>
 #include <type_traits>
 
 #include "common.h"
 #include "ctx.h"
 #include "kmer_plan.h"
-#include "match_plan.h"
-#include "compare_dev.h"
-#include "rank_plan.h"
 
 namespace sina_hip {
 namespace {
 
 constexpr int kCountThreads = 1024;
-constexpr int kTileRefs = 32768;            // refs per LDS histogram tile (64 KiB)
 constexpr int kWide = 2;                    // 1 KiB loads a wave of the count kernel keeps in flight
 constexpr int kMaxQueryLen = (int)SINA_HIP_MAX_QUERY_LEN;  // k-mer list capacity in LDS: 64 KiB tile + 9 B per base <= 160 KiB
-static_assert((size_t)kTileRefs * 2 + ((size_t)kMaxQueryLen + 63) / 64 * 64 * 9 + 64 <= 160 * 1024, "LDS of the count kernel");
+static_assert(kmer_count_lds(kmer_kmax(kMaxQueryLen, kKmerRows), kKmerRows) <= 160 * 1024, "LDS of the count kernel");
 // the long count kernel: a query of up to SINA_HIP_MAX_LONG_QUERY_LEN bases in chunks of
 // kLongChunk windows, each chunk with the k-mer list capacity of the fast kernel -- and its k - 1 <= 11 bases before
 // the chunk's first window end in qb[] (the 64 bytes more)
 constexpr int kMaxLongQueryLen = (int)SINA_HIP_MAX_LONG_QUERY_LEN;
 constexpr int kLongChunk = (int)SINA_HIP_KMER_LONG_CHUNK;
-constexpr int kLongQbExtra = 64;
 static_assert(kLongChunk <= kMaxQueryLen && kMaxLongQueryLen <= 32767, "a chunk fits the fast kernel's lists; int16 scores");
-static_assert((size_t)kTileRefs * 2 + (size_t)kMaxQueryLen * 9 + 64 + kLongQbExtra <= 160 * 1024, "LDS of the long count kernel");
+static_assert(kmer_count_lds(kmer_kmax(0, kKmerLong), kKmerLong) <= 160 * 1024, "LDS of the long count kernel");
 constexpr int kSelThreads = 256;
 constexpr int kSelMax = (int)kKmerSelMax;      // candidates sortable in LDS
 
@@ -78,52 +72,6 @@ __device__ __forceinline__ bool kmer_at(const uint8_t *m, uint32_t len, uint32_t
     return true;
 }
 
-// ---------------------------------------------------------------- index build
-
-// one (kmer << 32 | ref) key per valid window of every reference; invalid
-// windows emit ~0 (sorted to the end, dropped).
-__global__ void ref_kmer_keys(const uint32_t *ref_ab, const uint64_t *ref_off, uint32_t n_refs, unsigned k,
-                              bool fast, uint64_t *keys) {
-    const uint32_t r = blockIdx.x;
-    const uint64_t b = ref_off[r], e = ref_off[r + 1];
-    const uint32_t len = (uint32_t)(e - b);
-    for (uint32_t i = threadIdx.x; i < len; i += blockDim.x) {
-        uint64_t key = ~0ull;
-        if (i + 1 >= k && i + 2 <= len) {
-            uint32_t v = 0;
-            bool ok = true;
-            for (unsigned x = 0; x < k; x++) {
-                const uint32_t m = (ref_ab[b + i + 1 - k + x] >> 24) & 0xfu;
-                if (__popc(m) != 1) {
-                    ok = false;
-                    break;
-                }
-                v = (v << 2) | (uint32_t)(__ffs(m) - 1);
-            }
-            if (ok && fast && (v >> (2 * (k - 1))) != 0) ok = false;
-            if (ok) key = ((uint64_t)v << 32) | r;
-        }
-        keys[b + i] = key;
-    }
-}
-
-// after sorting: flag first occurrence of each (kmer, ref) key
-__global__ void mark_unique(const uint64_t *keys, uint64_t n, uint32_t *flag) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t kx = keys[i];
-    flag[i] = (kx != ~0ull && (i == 0 || keys[i - 1] != kx)) ? 1u : 0u;
-}
-
-__global__ void scatter_unique(const uint64_t *keys, const uint32_t *flag, const uint32_t *pos, uint64_t n,
-                               uint32_t *ids, uint32_t *counts) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !flag[i]) return;
-    const uint64_t kx = keys[i];
-    ids[pos[i]] = (uint32_t)kx;
-    atomicAdd(&counts[(uint32_t)(kx >> 32)], 1u);
-}
-
 // ---------------------------------------------------------------- count
 
 struct CountArgs {
@@ -137,7 +85,7 @@ struct CountArgs {
     uint32_t n_refs, stride, kmax;
     unsigned k;
     int fast;
-    // dense posting lists as bitmaps (see ensure_dense): bitmap number per k-mer or kNoDense, words per bitmap
+    // dense posting lists as bitmaps (kmer_index.hip, ensure_dense): bitmap number per k-mer or kNoDense, words per bitmap
     const uint32_t *dense_id;
     const uint32_t *dense_bits;
     uint32_t dense_words;
@@ -148,31 +96,8 @@ struct CountArgs {
     uint32_t cand_cap, topm;
 };
 
-constexpr uint32_t kNoDense = 0xFFFFFFFFu;
 constexpr uint32_t kMaxDenseQ = 1023;  // dense k-mers of one query counted bit-sliced in 10 planes
 static_assert(kTileRefs / 32 == kCountThreads, "one bitmap word of the tile per thread");
-
-// ---- dense lists: which k-mers, and their bitmaps
-__global__ void mark_dense(const uint32_t *idx_off, uint32_t n_kmers, uint32_t thresh, uint32_t *dense_id,
-                           uint32_t *counter) {
-    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= n_kmers) return;
-    const uint32_t len = idx_off[v + 1] - idx_off[v];
-    dense_id[v] = (len > thresh) ? atomicAdd(counter, 1u) : kNoDense;
-}
-__global__ void fill_dense(const uint32_t *idx_off, const uint32_t *idx_ids, const uint32_t *dense_id,
-                           uint32_t n_kmers, uint32_t *bits, uint32_t words) {
-    // one wave per k-mer (most leave at once)
-    const uint32_t v = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-    if (v >= n_kmers) return;
-    const uint32_t d = dense_id[v];
-    if (d == kNoDense) return;
-    uint32_t *b = bits + (size_t)d * words;
-    for (uint32_t x = idx_off[v] + lane; x < idx_off[v + 1]; x += 64) {
-        const uint32_t r = idx_ids[x];
-        atomicOr(&b[r >> 5], 1u << (r & 31));
-    }
-}
 
 // One workgroup (16 waves) per query.  Every query k-mer keeps a cursor into its (ascending)
 // posting list; the reference range is processed in tiles of kTileRefs whose int16 counters
@@ -812,610 +737,79 @@ __global__ void __launch_bounds__(kSelThreads) kmer_select_cand_kernel(SelectCan
     if (threadIdx.x == 0) a.out_n[q] = n < M ? n : M;
 }
 
+// The big select's sort: the range's nq segments of M keys each, descending over the 48 bits a key can have.
+// tmp == nullptr: only the size of rocPRIM's temporary storage.
+hipError_t big_sort(void *tmp, size_t &tmp_bytes, rocprim::double_buffer<unsigned long long> &kb, uint32_t nq, uint32_t M,
+                    hipStream_t s) {
+    using seg_iter = rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, BigSegOffset, uint32_t>;
+    const seg_iter seg_begin(rocprim::counting_iterator<uint32_t>(0), BigSegOffset{M});
+    return rocprim::segmented_radix_sort_keys_desc<BigSortConfig>(tmp, tmp_bytes, kb, (unsigned)((size_t)nq * M), nq, seg_begin,
+                                                                  seg_begin + 1, 0u, 48u, s);
+}
+
 }  // namespace
 
-static int index_ready(sina_hip_ctx *c) {
-    if (!c->st->have_refs) SH_FAIL("k-mer search: no references uploaded");
-    if (!c->st->have_index) SH_FAIL("k-mer search: no index (call sina_hip_build_index / upload_index)");
+// ---------------------------------------------------------------- launchers (common.h)
+// The range's buffers -- the context's k_* scratch -- are reserved by the driver (kmer_launch.hip, reserve_range).
+
+int launch_kmer_count(sina_hip_ctx *c, const KmerLaunch &l, hipStream_t s) {
+    const sina_hip_store *st = c->st;
+    const bool cand = l.path == kKmerCand;
+    const CountArgs a{l.qmask, l.qoff, st->idx_off.as<uint32_t>(), st->idx_ids.as<uint32_t>(), c->k_scores.as<int16_t>(), c->k_tmp0.as<uint32_t>(),
+                      c->k_tmp2.as<unsigned long long>(), st->n_refs, (uint32_t)kmer_row_stride(st->n_refs), kmer_kmax(l.max_qlen, l.path), st->k,
+                      st->nofast ? 0 : 1, st->n_dense ? st->dense_id.as<uint32_t>() : nullptr, st->dense_bits.as<uint32_t>(), st->dense_words,
+                      // (the candidate lists; kmer_select_cand_kernel turns cand_n into out_n in place)
+                      cand ? c->k_tmp1.as<unsigned long long>() : nullptr, cand ? c->k_out_n.as<uint32_t>() : nullptr, kCandCap, l.max};
+    void (*kernel)(CountArgs) = l.path == kKmerLong ? kmer_count_long_kernel : (cand ? kmer_count_kernel<true> : kmer_count_kernel<false>);
+    if (allow_full_lds(reinterpret_cast<const void *>(kernel))) return 1;
+    hipLaunchKernelGGL(kernel, dim3(l.nq), dim3(kCountThreads), kmer_count_lds(a.kmax, l.path), s, a);
+    SH_CHECK(hipGetLastError());
     return 0;
 }
 
-// Posting lists longer than 1/64 of the references (k-mers of conserved regions: a few hundred per
-// query hold 97 % of its postings) as bitmaps over the references, zero-padded to whole tiles, for
-// the count kernel's atomic-free path.  (By bytes a bitmap breaks even with a list at 1/32; the bitmaps of all
-// queries in flight are the same few thousand and come out of L2 / MALL, the lists out of HBM: 1/64 .. 1/128
-// measured 4 % faster at 100 000 references, 9 % at 500 000 -- tools/perf_kmer_dense.py.)  Built from the CSR index by the first search after the
-// index changed (also when the index arrived by broadcast), under the store's mutex.
-static int ensure_dense(sina_hip_ctx *c) {
-    sina_hip_store *st = c->st;
-    std::lock_guard<std::mutex> lk(st->aux_mu);
-    if (st->dense_ready) return 0;
-    hipStream_t s = c->stream;
-    const uint32_t nk = 1u << (2 * st->k);
-    uint32_t div_ = 64;
-    if (const std::string e_ = test_knob("dense_div"); !e_.empty()) div_ = (uint32_t)std::max(1, atoi(e_.c_str()));
-    const uint32_t thresh = std::max<uint32_t>(256u, st->n_refs / div_);
-    const uint32_t ntiles = (st->n_refs + kTileRefs - 1) / kTileRefs;
-    st->dense_words = ntiles * (uint32_t)(kTileRefs / 32);
-    sina_hip::DevBuf counter;
-    if (st->dense_id.reserve_exact(4 * (size_t)nk) || counter.reserve_exact(4)) return 1;
-    SH_CHECK(hipMemsetAsync(counter.p, 0, 4, s));
-    hipLaunchKernelGGL(mark_dense, dim3((nk + 255) / 256), dim3(256), 0, s, st->idx_off.as<uint32_t>(), nk, thresh,
-                       st->dense_id.as<uint32_t>(), counter.as<uint32_t>());
-    SH_CHECK(hipGetLastError());
-    SH_CHECK(hipStreamSynchronize(s));
-    uint32_t nd = 0;
-    SH_CHECK(hipMemcpy(&nd, counter.p, 4, hipMemcpyDeviceToHost));
-    counter.release();
-    st->n_dense = nd;
-    if (nd) {
-        const size_t bytes = 4 * (size_t)nd * st->dense_words;
-        if (st->dense_bits.reserve_exact(bytes)) return 1;
-        SH_CHECK(hipMemsetAsync(st->dense_bits.p, 0, bytes, s));
-        hipLaunchKernelGGL(fill_dense, dim3((unsigned)(((uint64_t)nk * 64 + 255) / 256)), dim3(256), 0, s,
-                           st->idx_off.as<uint32_t>(), st->idx_ids.as<uint32_t>(), st->dense_id.as<uint32_t>(), nk,
-                           st->dense_bits.as<uint32_t>(), st->dense_words);
-        SH_CHECK(hipGetLastError());
-    }
-    SH_CHECK(hipStreamSynchronize(s));  // (other contexts' streams read it next)
-    st->dense_ready = true;
-    return 0;
+// big select (l.big; the caller has clipped max to n_refs, so M = max): keys, their double buffer and rocPRIM's
+// temporary storage are context buffers that only grow -- sized here, before anything of the range is launched
+int reserve_kmer_big_select(sina_hip_ctx *c, KmerLaunch *l) {
+    l->big_tmp_bytes = 0;
+    if (!l->big) return 0;
+    const size_t n_keys = (size_t)l->nq * l->max;
+    if (n_keys > 0x7FFFFFFFull) SH_FAIL("kmer_topk: a launch range of the big select holds more than 2^31 candidates");
+    if (c->k_big_keys.reserve(2 * 8 * n_keys)) return 1;
+    rocprim::double_buffer<unsigned long long> kb(c->k_big_keys.as<unsigned long long>(), c->k_big_keys.as<unsigned long long>() + n_keys);
+    SH_CHECK(big_sort(nullptr, l->big_tmp_bytes, kb, l->nq, l->max, c->stream));
+    return c->k_big_tmp.reserve(l->big_tmp_bytes + 16);
 }
 
-// counts + selects for nq queries whose masks are already on the device
-// (the candidate-list path, kmer_count_kernel<true>: at least two tiles of references -- tile 0 must hold `max`
-// of them --, a top-M small enough for the list; SINA_HIP_TEST=kmer_rows=1 keeps the score rows)
-constexpr uint32_t kCandCap = 4096, kCandMaxM = 128;
-static bool kmer_cand_path(const sina_hip_ctx *c, uint32_t max) {
-    return max <= kCandMaxM && c->st->n_refs >= 2u * (uint32_t)kTileRefs && atoi(test_knob("kmer_rows").c_str()) == 0;
-}
-// long_path: the queries of this range are longer than kMaxQueryLen -- the long count kernel and its select kernel,
-// score rows only
-// big select (max > kSelMax; the caller has clipped max to n_refs, so M = max): kmer_select_big_kernel leaves every
-// query's M survivors as keys in its segment, one segmented radix sort -- descending over the 48 bits a key can have
-// -- orders all segments of the range, kmer_unpack_keys writes ids, scores and out_n.  Keys, their double buffer and
-// rocPRIM's temporary storage are context buffers that only grow: sized here, before anything is launched.
-static int kmer_topk_device(sina_hip_ctx *c, const uint8_t *d_qmask, const uint64_t *d_qoff, uint32_t nq,
-                            uint32_t max, uint32_t max_qlen, bool want_scores_only, bool cand_path, bool long_path = false) {
-    hipStream_t s = c->stream;
-    const uint32_t stride = (c->st->n_refs + 7u) & ~7u;  // rows 16-byte aligned (vector loads in the select kernel)
-    const bool big = !want_scores_only && !cand_path && max > (uint32_t)kSelMax;
-    using seg_iter = rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, BigSegOffset, uint32_t>;
-    const seg_iter seg_begin(rocprim::counting_iterator<uint32_t>(0), BigSegOffset{max});
-    const size_t n_keys = (size_t)nq * max;
-    size_t sort_tmp = 0;
-    if (big) {
-        if (n_keys > 0x7FFFFFFFull) SH_FAIL("kmer_topk: a launch range of the big select holds more than 2^31 candidates");
-        if (c->k_big_keys.reserve(2 * 8 * n_keys)) return 1;
-        rocprim::double_buffer<unsigned long long> kb(c->k_big_keys.as<unsigned long long>(), c->k_big_keys.as<unsigned long long>() + n_keys);
-        SH_CHECK(rocprim::segmented_radix_sort_keys_desc<BigSortConfig>(nullptr, sort_tmp, kb, (unsigned)n_keys, nq, seg_begin,
-                                                                        seg_begin + 1, 0u, 48u, s));
-        if (c->k_big_tmp.reserve(sort_tmp + 16)) return 1;
+// Candidate lists: kmer_select_cand_kernel.  Score rows: kmer_select_kernel, or kmer_select_big_kernel leaving every
+// query's M survivors as keys in its segment, one segmented radix sort over all segments of the range, and
+// kmer_unpack_keys writing ids, scores and out_n.
+int launch_kmer_select(sina_hip_ctx *c, const KmerLaunch &l, hipStream_t s) {
+    if (l.path == kKmerCand) {
+        const SelectCandArgs a{c->k_tmp1.as<unsigned long long>(), c->k_out_n.as<uint32_t>(), kCandCap, c->k_out_ids.as<uint32_t>(),
+                               c->k_out_scores.as<float>(), c->k_out_n.as<uint32_t>(), l.max};
+        hipLaunchKernelGGL(kmer_select_cand_kernel, dim3(l.nq), dim3(kSelThreads), 0, s, a);
+        SH_CHECK(hipGetLastError());
+        return 0;
     }
-    if ((!cand_path && c->k_scores.reserve((size_t)nq * stride * 2 + 64)) || c->k_tmp2.reserve(8) || c->k_tmp0.reserve(4 * (size_t)nq) ||
-        (cand_path && (c->k_tmp1.reserve(8 * (size_t)nq * kCandCap) || c->k_out_n.reserve((size_t)nq * 4))))
-        return 1;
-    SH_CHECK(hipMemsetAsync(c->k_tmp2.p, 0, 8, s));
-    CountArgs ca;
-    ca.qmask = d_qmask;
-    ca.qoff = d_qoff;
-    ca.idx_off = c->st->idx_off.as<uint32_t>();
-    ca.idx_ids = c->st->idx_ids.as<uint32_t>();
-    ca.scores = c->k_scores.as<int16_t>();
-    ca.nkq = c->k_tmp0.as<uint32_t>();
-    ca.postings = c->k_tmp2.as<unsigned long long>();
-    ca.n_refs = c->st->n_refs;
-    ca.stride = stride;
-    ca.kmax = long_path ? (uint32_t)kMaxQueryLen : (max_qlen + 63u) & ~63u;
-    ca.k = c->st->k;
-    ca.fast = c->st->nofast ? 0 : 1;
-    if (ensure_dense(c)) return 1;
-    ca.dense_id = c->st->n_dense ? c->st->dense_id.as<uint32_t>() : nullptr;
-    ca.dense_bits = c->st->dense_bits.as<uint32_t>();
-    ca.dense_words = c->st->dense_words;
-    ca.cand = cand_path ? c->k_tmp1.as<unsigned long long>() : nullptr;
-    ca.cand_n = cand_path ? c->k_out_n.as<uint32_t>() : nullptr;  // (kmer_select_cand_kernel turns it into out_n in place)
-    ca.cand_cap = kCandCap;
-    ca.topm = max;
-    const size_t clds = (size_t)kTileRefs * 2 + (size_t)ca.kmax * 9 + 64 + (long_path ? kLongQbExtra : 0);
-    if (allow_full_lds(reinterpret_cast<const void *>(kmer_count_kernel<false>)) ||
-        allow_full_lds(reinterpret_cast<const void *>(kmer_count_kernel<true>)) ||
-        (long_path && allow_full_lds(reinterpret_cast<const void *>(kmer_count_long_kernel))))
-        return 1;
-    heavy_launch hl(c, s, kHeavyKmer);  // (count + select: device-filling kernels, ctx.h)
-    const hipStream_t hs = hl.stream();
-    SH_CHECK(hipEventRecord(c->ev[3], hs));
-    if (long_path) hipLaunchKernelGGL(kmer_count_long_kernel, dim3(nq), dim3(kCountThreads), clds, hs, ca);
-    else if (cand_path) hipLaunchKernelGGL(kmer_count_kernel<true>, dim3(nq), dim3(kCountThreads), clds, hs, ca);
-    else hipLaunchKernelGGL(kmer_count_kernel<false>, dim3(nq), dim3(kCountThreads), clds, hs, ca);
+    const SelectArgs a{c->k_scores.as<int16_t>(), c->k_tmp0.as<uint32_t>(), c->k_out_ids.as<uint32_t>(), c->k_out_scores.as<float>(),
+                       c->k_out_n.as<uint32_t>(), c->st->n_refs, (uint32_t)kmer_row_stride(c->st->n_refs), l.max,
+                       l.big ? c->k_big_keys.as<unsigned long long>() : nullptr};
+    // (the rows of the long count kernel hold scores of up to 32757: the search for the cut starts above them)
+    const bool lng = l.path == kKmerLong;
+    void (*kernel)(SelectArgs) = l.big ? (lng ? kmer_select_big_kernel<kMaxLongQueryLen> : kmer_select_big_kernel<kMaxQueryLen>)
+                                       : (lng ? kmer_select_kernel<kMaxLongQueryLen> : kmer_select_kernel<kMaxQueryLen>);
+    hipLaunchKernelGGL(kernel, dim3(l.nq), dim3(kSelThreads), 0, s, a);
     SH_CHECK(hipGetLastError());
-    SH_CHECK(hipEventRecord(c->ev[4], hs));
-    if (cand_path) {
-        if (c->k_out_ids.reserve((size_t)nq * max * 4) || c->k_out_scores.reserve((size_t)nq * max * 4)) return 1;
-        SelectCandArgs sc;
-        sc.cand = ca.cand;
-        sc.cand_n = ca.cand_n;
-        sc.cand_cap = kCandCap;
-        sc.out_ids = c->k_out_ids.as<uint32_t>();
-        sc.out_scores = c->k_out_scores.as<float>();
-        sc.out_n = c->k_out_n.as<uint32_t>();
-        sc.max = max;
-        hipLaunchKernelGGL(kmer_select_cand_kernel, dim3(nq), dim3(kSelThreads), 0, hs, sc);
+    if (l.big) {
+        const size_t n_keys = (size_t)l.nq * l.max;
+        size_t tmp_bytes = l.big_tmp_bytes;
+        rocprim::double_buffer<unsigned long long> kb(a.keys, a.keys + n_keys);
+        SH_CHECK(big_sort(c->k_big_tmp.p, tmp_bytes, kb, l.nq, l.max, s));
+        hipLaunchKernelGGL(kmer_unpack_keys, dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, s, kb.current(), l.nq, l.max,
+                           a.out_ids, a.out_scores, a.out_n);
         SH_CHECK(hipGetLastError());
-    } else if (!want_scores_only) {
-        if (c->k_out_ids.reserve((size_t)nq * max * 4) || c->k_out_scores.reserve((size_t)nq * max * 4) ||
-            c->k_out_n.reserve((size_t)nq * 4))
-            return 1;
-        SelectArgs sa;
-        sa.scores = ca.scores;
-        sa.nkq = ca.nkq;
-        sa.stride = stride;
-        sa.out_ids = c->k_out_ids.as<uint32_t>();
-        sa.out_scores = c->k_out_scores.as<float>();
-        sa.out_n = c->k_out_n.as<uint32_t>();
-        sa.n_refs = c->st->n_refs;
-        sa.max = max;
-        sa.keys = big ? c->k_big_keys.as<unsigned long long>() : nullptr;
-        // (the rows of the long count kernel hold scores of up to 32757: the search for the cut starts above them)
-        if (big && long_path) hipLaunchKernelGGL(kmer_select_big_kernel<kMaxLongQueryLen>, dim3(nq), dim3(kSelThreads), 0, hs, sa);
-        else if (big) hipLaunchKernelGGL(kmer_select_big_kernel<kMaxQueryLen>, dim3(nq), dim3(kSelThreads), 0, hs, sa);
-        else if (long_path) hipLaunchKernelGGL(kmer_select_kernel<kMaxLongQueryLen>, dim3(nq), dim3(kSelThreads), 0, hs, sa);
-        else hipLaunchKernelGGL(kmer_select_kernel<kMaxQueryLen>, dim3(nq), dim3(kSelThreads), 0, hs, sa);
-        SH_CHECK(hipGetLastError());
-        if (big) {
-            rocprim::double_buffer<unsigned long long> kb(sa.keys, sa.keys + n_keys);
-            SH_CHECK(rocprim::segmented_radix_sort_keys_desc<BigSortConfig>(c->k_big_tmp.p, sort_tmp, kb, (unsigned)n_keys, nq, seg_begin,
-                                                                            seg_begin + 1, 0u, 48u, hs));
-            hipLaunchKernelGGL(kmer_unpack_keys, dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, hs, kb.current(), nq, max,
-                               sa.out_ids, sa.out_scores, sa.out_n);
-            SH_CHECK(hipGetLastError());
-        }
     }
-    SH_CHECK(hipEventRecord(c->ev[5], hs));
-    return hl.done();
+    return 0;
 }
 
 }  // namespace sina_hip
-
-using namespace sina_hip;
-
-extern "C" {
-
-int sina_hip_upload_index(sina_hip_ctx *c, unsigned k, int nofast, const uint32_t *offsets, const uint32_t *ids,
-                          uint64_t n_postings) {
-    if (!c || !offsets || (!ids && n_postings)) SH_FAIL("upload_index: null argument");
-    if (k < 1 || k > 12) SH_FAIL("upload_index: k must be in 1..12");
-    if (!c->owns_store) SH_FAIL("upload_index: a forked context cannot change the reference store");
-    std::lock_guard<std::mutex> lk(c->mu);
-    SH_CHECK(hipSetDevice(c->device));
-    const uint64_t nk = 1ull << (2 * k);
-    if (c->st->idx_off.reserve(4 * (nk + 1)) || c->st->idx_ids.reserve(4 * std::max<uint64_t>(n_postings, 1))) return 1;
-    SH_CHECK(hipMemcpyAsync(c->st->idx_off.p, offsets, 4 * (nk + 1), hipMemcpyHostToDevice, c->stream));
-    if (n_postings)
-        SH_CHECK(hipMemcpyAsync(c->st->idx_ids.p, ids, 4 * n_postings, hipMemcpyHostToDevice, c->stream));
-    SH_CHECK(hipStreamSynchronize(c->stream));
-    c->st->k = k;
-    c->st->nofast = nofast ? 1 : 0;
-    c->st->n_postings = n_postings;
-    c->st->have_index = true;
-    c->st->dense_ready = false;
-    return 0;
-}
-
-int sina_hip_download_index(sina_hip_ctx *c, uint32_t *offsets, uint32_t *ids) {
-    if (!c || !offsets) SH_FAIL("download_index: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->st->have_index) SH_FAIL("download_index: no index");
-    if (!ids && c->st->n_postings) SH_FAIL("download_index: null ids");
-    SH_CHECK(hipSetDevice(c->device));
-    const uint64_t nk = 1ull << (2 * c->st->k);
-    SH_CHECK(hipMemcpy(offsets, c->st->idx_off.p, 4 * (nk + 1), hipMemcpyDeviceToHost));
-    if (c->st->n_postings) SH_CHECK(hipMemcpy(ids, c->st->idx_ids.p, 4 * c->st->n_postings, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int sina_hip_build_index(sina_hip_ctx *c, unsigned k, int nofast) {
-    if (!c) SH_FAIL("build_index: null ctx");
-    if (k < 1 || k > 12) SH_FAIL("build_index: k must be in 1..12");
-    if (!c->owns_store) SH_FAIL("build_index: a forked context cannot change the reference store");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->st->have_refs) SH_FAIL("build_index: upload references first");
-    SH_CHECK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const uint64_t n = c->st->total_bases;
-    const uint64_t nk = 1ull << (2 * k);
-    if (n >= (1ull << 32)) SH_FAIL("build_index: more than 2^32 reference bases");
-    DevBuf keys_in, keys_out, flag, pos, tmp;
-    int rc = 1;
-    do {
-        if (keys_in.reserve(8 * std::max<uint64_t>(n, 1)) || keys_out.reserve(8 * std::max<uint64_t>(n, 1)) ||
-            flag.reserve(4 * std::max<uint64_t>(n, 1)) || pos.reserve(4 * std::max<uint64_t>(n, 1)))
-            break;
-        if (c->st->n_refs)
-            hipLaunchKernelGGL(ref_kmer_keys, dim3(c->st->n_refs), dim3(256), 0, s, c->st->ref_ab.as<uint32_t>(),
-                               c->st->ref_off.as<uint64_t>(), c->st->n_refs, k, nofast == 0, keys_in.as<uint64_t>());
-        size_t tb = 0;
-        const int end_bit = 32 + 2 * (int)k;
-        // (rocPRIM directly; only the bits a key can have: k-mer << 32 | reference id)
-        if (rocprim::radix_sort_keys(nullptr, tb, keys_in.as<uint64_t>(), keys_out.as<uint64_t>(), (size_t)n, 0u,
-                                     (unsigned)end_bit, s) != hipSuccess)
-            break;
-        if (tmp.reserve(tb + 16)) break;
-        if (n && rocprim::radix_sort_keys(tmp.p, tb, keys_in.as<uint64_t>(), keys_out.as<uint64_t>(), (size_t)n, 0u,
-                                          (unsigned)end_bit, s) != hipSuccess)
-            break;
-        const unsigned blocks = (unsigned)((n + 255) / 256);
-        if (n) hipLaunchKernelGGL(mark_unique, dim3(blocks), dim3(256), 0, s, keys_out.as<uint64_t>(), n,
-                                  flag.as<uint32_t>());
-        size_t tb2 = 0;
-        if (rocprim::exclusive_scan(nullptr, tb2, flag.as<uint32_t>(), pos.as<uint32_t>(), 0u, (size_t)n,
-                                    rocprim::plus<uint32_t>(), s) != hipSuccess)
-            break;
-        if (tmp.reserve(tb2 + 16)) break;
-        if (n && rocprim::exclusive_scan(tmp.p, tb2, flag.as<uint32_t>(), pos.as<uint32_t>(), 0u, (size_t)n,
-                                         rocprim::plus<uint32_t>(), s) != hipSuccess)
-            break;
-        uint32_t last_flag = 0, last_pos = 0;
-        if (n) {
-            if (hipMemcpyAsync(&last_flag, flag.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(&last_pos, pos.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                break;
-        }
-        const uint64_t np = (uint64_t)last_flag + last_pos;
-        DevBuf counts;
-        if (counts.reserve(4 * (nk + 1)) || c->st->idx_off.reserve(4 * (nk + 1)) ||
-            c->st->idx_ids.reserve(4 * std::max<uint64_t>(np, 1))) {
-            counts.release();
-            break;
-        }
-        bool ok = hipMemsetAsync(counts.p, 0, 4 * (nk + 1), s) == hipSuccess;
-        if (ok && n)
-            hipLaunchKernelGGL(scatter_unique, dim3(blocks), dim3(256), 0, s, keys_out.as<uint64_t>(),
-                               flag.as<uint32_t>(), pos.as<uint32_t>(), n, c->st->idx_ids.as<uint32_t>(),
-                               counts.as<uint32_t>());
-        size_t tb3 = 0;
-        ok = ok && rocprim::exclusive_scan(nullptr, tb3, counts.as<uint32_t>(), c->st->idx_off.as<uint32_t>(), 0u,
-                                           (size_t)(nk + 1), rocprim::plus<uint32_t>(), s) == hipSuccess;
-        ok = ok && tmp.reserve(tb3 + 16) == 0;
-        ok = ok && rocprim::exclusive_scan(tmp.p, tb3, counts.as<uint32_t>(), c->st->idx_off.as<uint32_t>(), 0u,
-                                           (size_t)(nk + 1), rocprim::plus<uint32_t>(), s) == hipSuccess;
-        ok = ok && hipStreamSynchronize(s) == hipSuccess;
-        counts.release();
-        if (!ok) break;
-        c->st->k = k;
-        c->st->nofast = nofast ? 1 : 0;
-        c->st->n_postings = np;
-        c->st->have_index = true;
-        c->st->dense_ready = false;
-        rc = 0;
-    } while (0);
-    keys_in.release();
-    keys_out.release();
-    flag.release();
-    pos.release();
-    tmp.release();
-    if (rc) {
-        hipError_t e = hipGetLastError();
-        set_error(std::string("build_index failed: ") + hipGetErrorString(e));
-    }
-    return rc;
-}
-
-// sina_hip_kmer_topk / _any behind their checks (c->mu held, 1 <= max <= n_refs): queries 0 .. n_fast - 1 on the fast
-// count kernel (none of them longer than kMaxQueryLen), queries n_fast .. nq - 1 -- every one of them longer -- on the
-// long kernel, in launch ranges of their own
-// q_ab / out_match (sina_hip_kmer_topk_match; else null): the queries' packed aligned bases, one per mask byte, and
-// where every range's match counts go (match.hip), [nq * max] like out_ids
-// rk (sina_hip_kmer_topk_rank; else null): the rules under which every range's candidates are ranked where the select
-// left them (rank.hip); out_ids / out_scores are then [nq * rk->N] rows of the rank kernel, out_n its counts, and no id
-// or k-mer score of the select is copied out
-struct RankReq {
-    int iupac, filter_lc, cover;
-    uint32_t N;
-    uint32_t *out_flag;  // [nq]
-};
-static int kmer_topk_run(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t n_fast,
-                         uint32_t max, uint32_t *out_ids, float *out_scores, uint32_t *out_n, const uint32_t *q_ab = nullptr,
-                         uint16_t *out_match = nullptr, const RankReq *rk = nullptr) {
-    uint32_t max_qlen = 1;
-    for (uint32_t q = 0; q < n_fast; q++) max_qlen = std::max<uint32_t>(max_qlen, (uint32_t)(qoff[q + 1] - qoff[q]));
-    hipStream_t s = c->stream;
-    const uint64_t nqm = qoff[nq] - qoff[0];
-    // sub-batches bound the [nq][n_refs] int16 score matrix to ~2 GiB
-    uint32_t per = (uint32_t)std::max<uint64_t>(1, ((uint64_t)2 << 30) / (2ull * std::max<uint32_t>(c->st->n_refs, 1)));
-    // ... and, for the big select, keys + outputs to kBigSelBudget (kmer_plan.h; SINA_HIP_TEST=big_sel_bytes=N: a test's budget)
-    const bool big = max > (uint32_t)kSelMax;
-    if (big) {
-        uint64_t budget = kBigSelBudget;
-        if (const std::string e_ = test_knob("big_sel_bytes"); !e_.empty()) budget = std::min<uint64_t>(kBigSelBudget, strtoull(e_.c_str(), nullptr, 10));
-        per = std::min(per, big_select_range(nq, max, budget));
-    }
-    if (c->qmask.reserve(std::max<uint64_t>(nqm, 1)) || c->k_qoff.reserve(8 * ((uint64_t)nq + 1))) return 1;
-    std::vector<uint64_t> rel(nq + 1);
-    for (uint32_t q = 0; q <= nq; q++) rel[q] = qoff[q] - qoff[0];
-    if (upload(c, 7, c->qmask.p, qmask + qoff[0], nqm, s) || upload(c, 8, c->k_qoff.p, rel.data(), 8 * ((uint64_t)nq + 1), s))
-        return 1;
-    if ((out_match || rk) && (c->s_qab.reserve(4 * std::max<uint64_t>(nqm, 1)) || upload(c, 1, c->s_qab.p, q_ab + qoff[0], 4 * nqm, s))) return 1;
-    // one launch range: kernels, results back through pinned staging, statistics; *overflow = a candidate list of the
-    // range did not hold its query's candidates (nothing was copied out then: the caller repeats the range with rows)
-    auto run_range = [&](uint32_t q0, uint32_t bq, bool cand_path, bool *overflow, bool long_path = false) -> int {
-        if (kmer_topk_device(c, c->qmask.as<uint8_t>(), c->k_qoff.as<uint64_t>() + q0, bq, max, max_qlen, false, cand_path, long_path)) return 1;
-        // (the kernels have finished: kmer_topk_device waits for the heavy stream)
-        if ((!rk && (download(c, 9, c->k_out_ids.p, (size_t)bq * max * 4, s) || download(c, 10, c->k_out_scores.p, (size_t)bq * max * 4, s))) ||
-            download(c, 11, c->k_out_n.p, (size_t)bq * 4, s) || download(c, 0, c->k_tmp2.p, 8, s))
-            return 1;
-        SH_CHECK(wait_stream(c, s));
-        *overflow = false;
-        if (cand_path) {
-            const uint32_t *n = static_cast<const uint32_t *>(c->h_stage[11].p);
-            for (uint32_t q = 0; q < bq && !*overflow; q++) *overflow = n[q] == 0xFFFFFFFFu;
-        }
-        unsigned long long visited = 0;
-        memcpy(&visited, c->h_stage[0].p, 8);
-        float ms = 0, ms2 = 0;
-        SH_CHECK(hipEventElapsedTime(&ms, c->ev[3], c->ev[4]));
-        SH_CHECK(hipEventElapsedTime(&ms2, c->ev[4], c->ev[5]));
-        {
-            std::lock_guard<std::mutex> slk(c->st->stats_mu);
-            c->st->stats.kmer_count_ms += ms;
-            c->st->stats.kmer_select_ms += ms2;
-            c->st->stats.kmer_launches++;
-            if (!*overflow) {
-                c->st->stats.postings += visited;
-                c->st->stats.kmer_queries += bq;
-            }
-        }
-        if (*overflow) return 0;
-        if (long_path) c->path_queries[kPathLong] += bq;
-        if (big) c->path_queries[kPathBigSelect] += bq;
-        if (rk) {  // the range's select is final: its candidates ranked, ids and lengths read where they lie
-            uint32_t max_la = 0;
-            for (uint32_t q = q0; q < q0 + bq; q++) max_la = std::max<uint32_t>(max_la, (uint32_t)(qoff[q + 1] - qoff[q]));
-            return rank_launch(c, c->s_qab.as<uint32_t>(), c->k_qoff.as<uint64_t>() + q0, bq, c->k_out_ids.as<uint32_t>(), nullptr,
-                               c->k_out_n.as<uint32_t>(), max, max, max_la, rk->iupac, rk->filter_lc, rk->cover, rk->N,
-                               out_ids + (size_t)q0 * rk->N, out_scores + (size_t)q0 * rk->N, out_n + q0, rk->out_flag + q0);
-        }
-        memcpy(out_ids + (size_t)q0 * max, c->h_stage[9].p, (size_t)bq * max * 4);
-        memcpy(out_scores + (size_t)q0 * max, c->h_stage[10].p, (size_t)bq * max * 4);
-        memcpy(out_n + q0, c->h_stage[11].p, (size_t)bq * 4);
-        if (out_match) {  // the range's select is final: its candidates' match counts, ids and lengths read where they lie
-            const size_t row_bytes = (size_t)bq * max * 2;
-            if (c->m_out.reserve(row_bytes)) return 1;
-            SH_CHECK(hipMemsetAsync(c->m_out.p, 0, row_bytes, s));
-            if (match_launch(c, c->s_qab.as<uint32_t>(), c->k_qoff.as<uint64_t>() + q0, bq, c->k_out_ids.as<uint32_t>(),
-                             c->k_out_n.as<uint32_t>(), max, c->m_out.as<uint16_t>(), static_cast<const uint32_t *>(c->h_stage[9].p),
-                             static_cast<const uint32_t *>(c->h_stage[11].p)) ||
-                download(c, 5, c->m_out.p, row_bytes, s))
-                return 1;
-            SH_CHECK(wait_stream(c, s));
-            memcpy(out_match + (size_t)q0 * max, c->h_stage[5].p, row_bytes);
-        }
-        return 0;
-    };
-    const bool cand_path = kmer_cand_path(c, max);
-    const uint32_t per_cand = 16384;  // (candidate lists: 32 KB per query)
-    for (uint32_t q0 = 0; q0 < n_fast; q0 += cand_path ? per_cand : per) {
-        const uint32_t bq = std::min(cand_path ? per_cand : per, n_fast - q0);
-        bool overflow = false;
-        if (run_range(q0, bq, cand_path, &overflow)) return 1;
-        if (overflow)  // a giant group of equal scores somewhere in the range: the score rows and the full select
-            for (uint32_t r0 = q0; r0 < q0 + bq; r0 += per) {
-                bool dummy = false;
-                if (run_range(r0, std::min(per, q0 + bq - r0), false, &dummy)) return 1;
-            }
-    }
-    for (uint32_t q0 = n_fast; q0 < nq; q0 += per) {
-        bool dummy = false;
-        if (run_range(q0, std::min(per, nq - q0), false, &dummy, true)) return 1;
-    }
-    return 0;
-}
-
-// any: queries of up to kMaxLongQueryLen bases (sina_hip_kmer_topk_any), the longer ones behind the others for
-// kmer_topk_run and back into the caller's order
-static int kmer_topk_checked(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max,
-                             uint32_t *out_ids, float *out_scores, uint32_t *out_n, bool any, const uint32_t *q_ab = nullptr,
-                             uint16_t *out_match = nullptr, const RankReq *rk = nullptr) {
-    if (!c || !qmask || !qoff || !out_ids || !out_scores || !out_n) SH_FAIL("kmer_topk: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    sina_hip_hint_guard hints(c);
-    if (index_ready(c)) return 1;
-    if (out_match && match_table_bytes(c->st->width) > kMatchMaxLds)
-        SH_FAIL_LIMIT("kmer_topk_match: alignment too wide for the device match count");
-    if (rk) {
-        if (rank_check_rules("kmer_topk_rank", c, rk->iupac, rk->cover, rk->N)) return 1;
-        uint32_t max_la = 0;
-        for (uint32_t q = 0; q < nq; q++) max_la = std::max<uint32_t>(max_la, (uint32_t)(qoff[q + 1] - qoff[q]));
-        if (compare_table_bytes(c->st->width, max_la) > kCompareMaxLds)
-            SH_FAIL_LIMIT("kmer_topk_rank: alignment too wide for the device comparison");
-        if (std::min(max, c->st->n_refs) > (uint32_t)kSelMax)
-            SH_FAIL_LIMIT("kmer_topk_rank: more than 4096 candidates per query");
-    }
-    if (nq == 0) return 0;
-    SH_CHECK(hipSetDevice(c->device));
-    if (max > c->st->n_refs) max = c->st->n_refs;
-    if (max == 0) {
-        memset(out_n, 0, sizeof(uint32_t) * nq);
-        if (rk) memset(rk->out_flag, 0, sizeof(uint32_t) * nq);
-        return 0;
-    }
-    uint32_t n_long = 0;
-    for (uint32_t q = 0; q < nq; q++) {
-        const uint64_t len = qoff[q + 1] - qoff[q];
-        if (!any && len > (uint64_t)kMaxQueryLen) SH_FAIL("kmer_topk: query longer than SINA_HIP_MAX_QUERY_LEN bases");
-        if (len > (uint64_t)kMaxLongQueryLen) SH_FAIL_LIMIT("kmer_topk_any: query longer than SINA_HIP_MAX_LONG_QUERY_LEN bases");
-        n_long += len > (uint64_t)kMaxQueryLen;
-    }
-    if (n_long == 0) return kmer_topk_run(c, qmask, qoff, nq, nq, max, out_ids, out_scores, out_n, q_ab, out_match, rk);
-    const uint32_t n_fast = nq - n_long;
-    const uint32_t row = rk ? rk->N : max;  // entries of an output row
-    std::vector<uint32_t> order(nq);  // order[slot] = the caller's query
-    for (uint32_t q = 0, f = 0, l = n_fast; q < nq; q++) order[qoff[q + 1] - qoff[q] > (uint64_t)kMaxQueryLen ? l++ : f++] = q;
-    std::vector<uint64_t> off(nq + 1, 0);
-    for (uint32_t x = 0; x < nq; x++) off[x + 1] = off[x] + (qoff[order[x] + 1] - qoff[order[x]]);
-    std::vector<uint8_t> mask(off[nq]);
-    for (uint32_t x = 0; x < nq; x++) memcpy(mask.data() + off[x], qmask + qoff[order[x]], off[x + 1] - off[x]);
-    std::vector<uint32_t> ids((size_t)nq * row), n(nq), fl(rk ? nq : 0);
-    std::vector<float> sc((size_t)nq * row);
-    std::vector<uint32_t> ab(q_ab ? off[nq] : 0);  // (the packed bases and the match rows move with their queries)
-    std::vector<uint16_t> mt(out_match ? (size_t)nq * max : 0);
-    if (q_ab)
-        for (uint32_t x = 0; x < nq; x++) memcpy(ab.data() + off[x], q_ab + qoff[order[x]], 4 * (off[x + 1] - off[x]));
-    RankReq rk2;
-    if (rk) {
-        rk2 = *rk;
-        rk2.out_flag = fl.data();
-    }
-    if (kmer_topk_run(c, mask.data(), off.data(), nq, n_fast, max, ids.data(), sc.data(), n.data(), q_ab ? ab.data() : nullptr,
-                      out_match ? mt.data() : nullptr, rk ? &rk2 : nullptr))
-        return 1;
-    for (uint32_t x = 0; x < nq; x++) {
-        if (out_match) memcpy(out_match + (size_t)order[x] * max, mt.data() + (size_t)x * max, (size_t)max * 2);
-        memcpy(out_ids + (size_t)order[x] * row, ids.data() + (size_t)x * row, (size_t)row * 4);
-        memcpy(out_scores + (size_t)order[x] * row, sc.data() + (size_t)x * row, (size_t)row * 4);
-        out_n[order[x]] = n[x];
-        if (rk) rk->out_flag[order[x]] = fl[x];
-    }
-    return 0;
-}
-
-static int kmer_scores_checked(sina_hip_ctx *c, const uint8_t *qmask, uint32_t qlen, int16_t *scores, bool any) {
-    if (!c || !qmask || !scores) SH_FAIL("kmer_scores: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (index_ready(c)) return 1;
-    if (!any && qlen > (uint32_t)kMaxQueryLen) SH_FAIL("kmer_scores: query longer than SINA_HIP_MAX_QUERY_LEN bases");
-    if (qlen > (uint32_t)kMaxLongQueryLen) SH_FAIL_LIMIT("kmer_scores_any: query longer than SINA_HIP_MAX_LONG_QUERY_LEN bases");
-    const bool long_path = qlen > (uint32_t)kMaxQueryLen;
-    SH_CHECK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const uint64_t rel[2] = {0, qlen};
-    if (c->qmask.reserve(std::max<uint32_t>(qlen, 1)) || c->k_qoff.reserve(16)) return 1;
-    SH_CHECK(hipMemcpyAsync(c->qmask.p, qmask, qlen, hipMemcpyHostToDevice, s));
-    SH_CHECK(hipMemcpyAsync(c->k_qoff.p, rel, 16, hipMemcpyHostToDevice, s));
-    if (kmer_topk_device(c, c->qmask.as<uint8_t>(), c->k_qoff.as<uint64_t>(), 1, 1, std::max<uint32_t>(qlen, 1), true, false, long_path)) return 1;
-    if (long_path) c->path_queries[kPathLong]++;
-    SH_CHECK(hipMemcpyAsync(scores, c->k_scores.p, (size_t)c->st->n_refs * 2, hipMemcpyDeviceToHost, s));
-    SH_CHECK(hipStreamSynchronize(s));
-    return 0;
-}
-
-int sina_hip_kmer_topk(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max,
-                       uint32_t *out_ids, float *out_scores, uint32_t *out_n) {
-    return kmer_topk_checked(c, qmask, qoff, nq, max, out_ids, out_scores, out_n, false);
-}
-int sina_hip_kmer_topk_any(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max,
-                           uint32_t *out_ids, float *out_scores, uint32_t *out_n) {
-    return kmer_topk_checked(c, qmask, qoff, nq, max, out_ids, out_scores, out_n, true);
-}
-int sina_hip_kmer_topk_match(sina_hip_ctx *c, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t max,
-                             uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint16_t *out_match) {
-    if (!c || !q_ab || !q_off || !out_ids || !out_scores || !out_n || !out_match) SH_FAIL("kmer_topk_match: null argument");
-    if (match_check_queries("kmer_topk_match", q_ab, q_off, nq)) return 1;
-    // the mask bytes the count kernel reads, one per packed word; offsets from the first query's first base
-    const uint64_t b = q_off[0], e = q_off[nq];
-    std::vector<uint8_t> mask(e - b + 1);
-    for (uint64_t i = b; i < e; i++) mask[i - b] = (uint8_t)(q_ab[i] >> 24);
-    std::vector<uint64_t> rel(nq + 1);
-    for (uint32_t q = 0; q <= nq; q++) rel[q] = q_off[q] - b;
-    return kmer_topk_checked(c, mask.data(), rel.data(), nq, max, out_ids, out_scores, out_n, true, q_ab + b, out_match);
-}
-int sina_hip_kmer_topk_rank(sina_hip_ctx *c, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t kmer_candidates,
-                            int iupac_rule, int filter_lowercase, int cover_rule, uint32_t max_result, uint32_t *out_ids,
-                            float *out_scores, uint32_t *out_n, uint32_t *out_flag) {
-    if (!c || !q_ab || !q_off || !out_ids || !out_scores || !out_n || !out_flag) SH_FAIL("kmer_topk_rank: null argument");
-    if (match_check_queries("kmer_topk_rank", q_ab, q_off, nq)) return 1;
-    const uint64_t b = q_off[0], e = q_off[nq];
-    std::vector<uint8_t> mask(e - b + 1);
-    for (uint64_t i = b; i < e; i++) mask[i - b] = (uint8_t)(q_ab[i] >> 24);
-    std::vector<uint64_t> rel(nq + 1);
-    for (uint32_t q = 0; q <= nq; q++) rel[q] = q_off[q] - b;
-    // (results through vectors of the call's own: the outputs stay untouched if a range fails)
-    std::vector<uint32_t> ids((size_t)nq * std::max(max_result, 1u)), n(nq), fl(nq);
-    std::vector<float> sc(ids.size());
-    const RankReq rk{iupac_rule, filter_lowercase ? 1 : 0, cover_rule, max_result, fl.data()};
-    if (kmer_topk_checked(c, mask.data(), rel.data(), nq, kmer_candidates, ids.data(), sc.data(), n.data(), true, q_ab + b, nullptr, &rk))
-        return 1;
-    memcpy(out_ids, ids.data(), 4 * (size_t)nq * max_result);
-    memcpy(out_scores, sc.data(), 4 * (size_t)nq * max_result);
-    memcpy(out_n, n.data(), 4 * (size_t)nq);
-    memcpy(out_flag, fl.data(), 4 * (size_t)nq);
-    return 0;
-}
-int sina_hip_kmer_scores(sina_hip_ctx *c, const uint8_t *qmask, uint32_t qlen, int16_t *scores) {
-    return kmer_scores_checked(c, qmask, qlen, scores, false);
-}
-int sina_hip_kmer_scores_any(sina_hip_ctx *c, const uint8_t *qmask, uint32_t qlen, int16_t *scores) {
-    return kmer_scores_checked(c, qmask, qlen, scores, true);
-}
-int sina_hip_long_queries(sina_hip_ctx *c, uint64_t *n) {
-    if (!c || !n) SH_FAIL("long_queries: null argument");
-    return read_path_queries(c, kPathLong, n);
-}
-
-int sina_hip_big_select_queries(sina_hip_ctx *c, uint64_t *n) {
-    if (!c || !n) SH_FAIL("big_select_queries: null argument");
-    return read_path_queries(c, kPathBigSelect, n);
-}
-
-int sina_hip_store_view_get(sina_hip_ctx *c, sina_hip_store_view *v) {
-    if (!c || !v) SH_FAIL("store_view_get: null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->st->have_refs) SH_FAIL("store_view_get: no references uploaded");
-    memset(v, 0, sizeof(*v));
-    v->ref_ab = c->st->ref_ab.p;
-    v->ref_ab_bytes = 4 * c->st->total_bases;
-    v->ref_off = c->st->ref_off.p;
-    v->ref_off_bytes = 8 * ((uint64_t)c->st->n_refs + 1);
-    v->n_refs = c->st->n_refs;
-    v->width = c->st->width;
-    v->total_bases = c->st->total_bases;
-    if (c->st->have_index) {
-        v->idx_offsets = c->st->idx_off.p;
-        v->idx_offsets_bytes = 4 * ((1ull << (2 * c->st->k)) + 1);
-        v->idx_ids = c->st->idx_ids.p;
-        v->idx_ids_bytes = 4 * c->st->n_postings;
-        v->k = c->st->k;
-        v->nofast = c->st->nofast;
-        v->n_postings = c->st->n_postings;
-    }
-    return 0;
-}
-
-int sina_hip_store_alloc_like(sina_hip_ctx *c, sina_hip_store_view *v) {
-    if (!c || !v) SH_FAIL("store_alloc_like: null argument");
-    if (v->k < 1 || v->k > 12) SH_FAIL("store_alloc_like: k must be in 1..12");
-    if (!c->owns_store) SH_FAIL("store_alloc_like: a forked context cannot change the reference store");
-    std::lock_guard<std::mutex> lk(c->mu);
-    SH_CHECK(hipSetDevice(c->device));
-    const uint64_t nk = 1ull << (2 * v->k);
-    if (c->st->ref_ab.reserve(4 * std::max<uint64_t>(v->total_bases, 1)) ||
-        c->st->ref_off.reserve(8 * ((uint64_t)v->n_refs + 1)) || c->st->idx_off.reserve(4 * (nk + 1)) ||
-        c->st->idx_ids.reserve(4 * std::max<uint64_t>(v->n_postings, 1)))
-        return 1;
-    c->st->n_refs = v->n_refs;
-    c->st->width = v->width;
-    c->st->total_bases = v->total_bases;
-    c->st->k = v->k;
-    c->st->nofast = v->nofast;
-    c->st->n_postings = v->n_postings;
-    c->st->have_refs = c->st->have_index = true;
-    c->st->have_name_order = false;
-    c->st->dense_ready = false;  // (the index arrives by broadcast after this call: built by the first search)
-    {   // re-read from the device, once, after the broadcast filled it (ensure_ref_off_host)
-        std::lock_guard<std::mutex> alk(c->st->aux_mu);
-        c->st->ref_off_host_ready.store(false, std::memory_order_release);
-        c->st->ref_off_host.clear();
-    }
-    v->ref_ab = c->st->ref_ab.p;
-    v->ref_ab_bytes = 4 * v->total_bases;
-    v->ref_off = c->st->ref_off.p;
-    v->ref_off_bytes = 8 * ((uint64_t)v->n_refs + 1);
-    v->idx_offsets = c->st->idx_off.p;
-    v->idx_offsets_bytes = 4 * (nk + 1);
-    v->idx_ids = c->st->idx_ids.p;
-    v->idx_ids_bytes = 4 * v->n_postings;
-    return 0;
-}
-
-}  // extern "C"

@@ -1,5 +1,5 @@
 // Search-stage ranking on the GPU: rank_kernel, rank_merge_kernel + sina_hip_compare_rank,
-// sina_hip_upload_name_order, sina_hip_rank_stats; sina_hip_kmer_topk_rank (kmer.hip) launches the same kernels on the
+// sina_hip_upload_name_order, sina_hip_rank_stats; sina_hip_kmer_topk_rank (kmer_launch.hip) launches the same kernels on the
 // select's id rows.
 //
 // What it computes: what search_filter does with a query's candidates after comparing them (host/search_filter.cpp): the

@@ -145,7 +145,7 @@ def check_csr(case):
 # (reachability only: no expected result comes from these)
 
 def dense_threshold(n_refs, dense_div):
-    """ensure_dense: a list LONGER than this is also kept as a bitmap."""
+    """kmer_dense_threshold (csrc/kmer_plan.h): a list LONGER than this is also kept as a bitmap."""
     return max(256, n_refs // (64 if dense_div is None else max(1, int(dense_div))))
 
 

@@ -1,9 +1,13 @@
-// csrc/kmer_plan.h -- the launch ranges of the k-mer search's big select -- against plain arithmetic, as a stand-alone
-// program: tests/test_kmer_big_cpu.py builds it with the address and undefined-behaviour sanitizers and runs it once.
+// csrc/kmer_plan.h -- what a k-mer search call is planned from: the launch ranges of the big select, the paths and
+// ranges of a call, the count kernels' geometry, the dense rule, the fast-first order -- against plain arithmetic, as a
+// stand-alone program: tests/test_kmer_big_cpu.py builds it with the address and undefined-behaviour sanitizers and
+// runs it once.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
+#include "../include/sina_hip.h"  // (beside this file's directory: the limits the plan must agree with)
 #include "kmer_plan.h"
 
 using namespace sina_hip;
@@ -17,7 +21,7 @@ static int fails = 0;
         }                                                             \
     } while (0)
 
-// walks the ranges as kmer.hip and host/store.cpp do; returns their number, checks that they tile [0, nq)
+// walks the big select's ranges as host/store.cpp does; returns their number, checks that they tile [0, nq)
 static uint64_t walk(uint32_t nq, uint32_t M, uint64_t budget, uint32_t *first, uint32_t *last) {
     const uint32_t per = big_select_range(nq, M, budget);
     EXPECT(per >= 1 && per <= (nq ? nq : 1u));
@@ -35,7 +39,168 @@ static uint64_t walk(uint32_t nq, uint32_t M, uint64_t budget, uint32_t *first, 
     return n;
 }
 
+// ---- the rest of the plan, against arithmetic written out here (none of it calls the plan to learn what to expect)
+static uint64_t own_stride(uint32_t n_refs) { return ((uint64_t)n_refs + 7) / 8 * 8; }
+static const uint64_t kTwoGiB = 1ull << 31;
+static uint64_t own_rows_per(uint32_t n_refs) {
+    const uint64_t per = kTwoGiB / (2 * own_stride(n_refs ? n_refs : 1));
+    return per ? per : 1;
+}
+// queries per range of the score-row paths
+static uint64_t own_per(uint32_t nq, uint32_t max, uint32_t n_refs, uint64_t budget) {
+    uint64_t per = own_rows_per(n_refs);
+    if (max > 4096) {
+        uint64_t fit = budget / (24ull * max);
+        if (fit > nq) fit = nq;
+        if (fit < 1) fit = 1;
+        if (fit < per) per = fit;
+    }
+    return per;
+}
+static bool own_cand(uint32_t max, uint32_t n_refs, bool force_rows) { return max <= 128 && n_refs >= 65536 && !force_rows; }
+
+// a score-row range is within 2 GiB of rows, and within the budget if its select is the big one -- or holds one query
+static void check_rows_range(const KmerRange &r, uint32_t max, uint32_t n_refs, uint64_t budget) {
+    EXPECT(r.bq == 1 || (uint64_t)r.bq * own_stride(n_refs) * 2 <= kTwoGiB);
+    EXPECT(r.big == (max > 4096));
+    if (r.big) EXPECT(r.bq == 1 || (uint64_t)r.bq * max * 24 <= budget);
+}
+static size_t check_ranges(uint32_t nq, uint32_t n_fast, uint32_t max, uint32_t n_refs, uint64_t budget, bool force_rows) {
+    const std::vector<KmerRange> rs = kmer_ranges(nq, n_fast, max, n_refs, budget, force_rows);
+    const bool cand = own_cand(max, n_refs, force_rows);
+    uint64_t at = 0;
+    for (const KmerRange &r : rs) {
+        EXPECT(r.q0 == at && r.bq >= 1);  // in order, no gap, no overlap
+        at += r.bq;
+        EXPECT(at <= n_fast || r.q0 >= n_fast);  // none straddles n_fast
+        if (r.q0 >= n_fast) {
+            EXPECT(r.path == kKmerLong);
+            check_rows_range(r, max, n_refs, budget);
+        } else if (cand) {
+            EXPECT(r.path == kKmerCand && !r.big && r.bq <= 16384);
+            // its repeat tiles exactly the range, on score rows with the LDS select
+            uint64_t rat = r.q0;
+            for (const KmerRange &h : kmer_overflow_ranges(r, n_refs)) {
+                EXPECT(h.q0 == rat && h.bq >= 1 && h.path == kKmerRows && !h.big);
+                EXPECT(h.bq == 1 || (uint64_t)h.bq * own_stride(n_refs) * 2 <= kTwoGiB);
+                rat += h.bq;
+            }
+            EXPECT(rat == (uint64_t)r.q0 + r.bq);
+        } else {
+            EXPECT(r.path == kKmerRows);
+            check_rows_range(r, max, n_refs, budget);
+        }
+        EXPECT(!(r.path == kKmerCand && r.big));  // the candidate path and the big select never coincide
+    }
+    EXPECT(at == nq);
+    return rs.size();
+}
+// one case of (max, n_refs, budget, force_rows) at nq in {0, 1, per, per + 1}, the batch all fast, all long and split
+static void check_case(uint32_t max, uint32_t n_refs, uint64_t budget, bool force_rows) {
+    const uint64_t per = own_cand(max, n_refs, force_rows) ? 16384 : own_per(0xFFFFFFFFu, max, n_refs, budget);
+    const uint64_t nqs[4] = {0, 1, per, per + 1};
+    for (uint64_t nq64 : nqs) {
+        const uint32_t nq = (uint32_t)nq64;
+        const uint32_t fasts[4] = {nq, 0, nq / 2, nq ? nq - 1 : 0};
+        for (uint32_t n_fast : fasts) check_ranges(nq, n_fast, max, n_refs, budget, force_rows);
+    }
+}
+static void check_plan() {
+    static_assert(kKmerMaxQueryLen == SINA_HIP_MAX_QUERY_LEN, "the plan's own statement of the fast kernel's limit");
+    // ---- gate edges
+    EXPECT(kmer_cand_gate(128, 65536, false) && !kmer_cand_gate(129, 65536, false));
+    EXPECT(!kmer_cand_gate(128, 65535, false) && kmer_cand_gate(1, 0xFFFFFFFFu, false));
+    EXPECT(!kmer_cand_gate(128, 65536, true) && !kmer_cand_gate(1, 500000, true));
+    EXPECT(!kmer_big_select(4096) && kmer_big_select(4097) && !kmer_big_select(1) && kmer_big_select(0xFFFFFFFFu));
+    static_assert(kCandCap == 4096 && kCandMaxM == 128 && kCandRangeQueries == 16384, "the candidate lists");
+    static_assert(kScoreMatrixBytes == (1ull << 31) && kTileRefs == 32768 && kNoDense == 0xFFFFFFFFu, "constants");
+    // ---- ranges: every gate edge, with budgets that cut and budgets that do not
+    const uint32_t maxes[] = {1, 128, 129, 4096, 4097, 5000, 100000};
+    const uint32_t refs[] = {1, 7, 8, 9, 65535, 65536, 65537, 500000, 0x7FFFFFFFu, 0xFFFFFFFFu};
+    const uint64_t budgets[] = {0, 1000, 24ull * 5000 * 4, kBigSelBudget};
+    for (uint32_t max : maxes)
+        for (uint32_t n_refs : refs)
+            for (uint64_t budget : budgets)
+                for (int force = 0; force < 2; force++)
+                    if (max <= n_refs) check_case(max, n_refs, budget, force != 0);  // (the driver clips max to n_refs)
+    // the paths at the edges, as ranges
+    EXPECT(kmer_ranges(10, 10, 128, 65536, kBigSelBudget, false)[0].path == kKmerCand);
+    EXPECT(kmer_ranges(10, 10, 129, 65536, kBigSelBudget, false)[0].path == kKmerRows);
+    EXPECT(kmer_ranges(10, 10, 128, 65535, kBigSelBudget, false)[0].path == kKmerRows);
+    EXPECT(kmer_ranges(10, 10, 128, 65536, kBigSelBudget, true)[0].path == kKmerRows);
+    EXPECT(!kmer_ranges(10, 10, 4096, 65536, kBigSelBudget, false)[0].big && kmer_ranges(10, 10, 4097, 65536, kBigSelBudget, false)[0].big);
+    EXPECT(kmer_ranges(10, 4, 4097, 65536, kBigSelBudget, false).back().big && kmer_ranges(10, 4, 4097, 65536, kBigSelBudget, false).back().path == kKmerLong);
+    // a batch with both classes on the candidate path: fast ranges of 16384, long ranges of 2^30 / 65536
+    {
+        const std::vector<KmerRange> rs = kmer_ranges(16384 + 5 + 16384 + 1, 16384 + 5, 10, 65536, kBigSelBudget, false);
+        EXPECT(rs.size() == 4 && rs[0].bq == 16384 && rs[1].bq == 5 && rs[1].path == kKmerCand);
+        EXPECT(rs[2].q0 == 16389 && rs[2].bq == 16384 && rs[2].path == kKmerLong && rs[3].bq == 1);
+    }
+    // ---- known values: 500 000 references, 9216 queries on score rows -- 2^30 / 500 000 = 2147 queries per range, five ranges
+    EXPECT(check_ranges(9216, 9216, 10, 500000, kBigSelBudget, true) == 5);
+    EXPECT(kmer_ranges(9216, 9216, 10, 500000, kBigSelBudget, true)[0].bq == 2147 && kmer_ranges(9216, 9216, 10, 500000, kBigSelBudget, true)[4].bq == 9216 - 4 * 2147);
+    EXPECT(check_ranges(9216, 9216, 10, 500000, kBigSelBudget, false) == 1);  // (candidate lists: one)
+    // the smallest and the largest store.  One reference: a row is 8 entries, 2^27 rows are 2 GiB -- any real batch is
+    // one range.  2^32 - 1 references: a row alone is 8 GiB, one query per range, and no 32-bit product on the way
+    EXPECT(check_ranges(1000, 1000, 1, 1, kBigSelBudget, false) == 1);
+    EXPECT(check_ranges((1u << 27) + 1, (1u << 27) + 1, 1, 1, kBigSelBudget, false) == 2);
+    EXPECT(check_ranges(3, 3, 200, 0xFFFFFFFFu, kBigSelBudget, false) == 3);
+    EXPECT(check_ranges(3, 2, 10, 0xFFFFFFFFu, kBigSelBudget, true) == 3);
+    {
+        const std::vector<KmerRange> rs = kmer_ranges(3, 3, 10, 0xFFFFFFFFu, kBigSelBudget, false);  // candidate lists: one range ...
+        EXPECT(rs.size() == 1 && rs[0].path == kKmerCand && kmer_overflow_ranges(rs[0], 0xFFFFFFFFu).size() == 3);  // ... repeated query by query
+    }
+    // ---- geometry
+    for (uint32_t n_refs : {0u, 1u, 7u, 8u, 9u, 65537u, 500000u, 0xFFFFFFF8u, 0xFFFFFFF9u, 0xFFFFFFFFu}) {
+        const uint64_t s = kmer_row_stride(n_refs);
+        EXPECT(s % 8 == 0 && s >= n_refs && s < (uint64_t)n_refs + 8);
+    }
+    EXPECT(kmer_row_stride(0xFFFFFFFFu) == (1ull << 32) && kmer_row_stride(500000) == 500000 && kmer_row_stride(65537) == 65544);
+    EXPECT(kmer_kmax(1, kKmerRows) == 64 && kmer_kmax(64, kKmerCand) == 64 && kmer_kmax(65, kKmerRows) == 128);
+    EXPECT(kmer_kmax(SINA_HIP_MAX_QUERY_LEN - 1, kKmerCand) == SINA_HIP_MAX_QUERY_LEN && kmer_kmax(SINA_HIP_MAX_QUERY_LEN, kKmerRows) == SINA_HIP_MAX_QUERY_LEN);
+    EXPECT(kmer_kmax(1, kKmerLong) == SINA_HIP_MAX_QUERY_LEN && kmer_kmax(32767, kKmerLong) == SINA_HIP_MAX_QUERY_LEN);
+    const size_t kmax = SINA_HIP_MAX_QUERY_LEN;
+    EXPECT(kmer_count_lds(SINA_HIP_MAX_QUERY_LEN, kKmerRows) == 32768 * 2 + kmax * 9 + 64 && kmer_count_lds(SINA_HIP_MAX_QUERY_LEN, kKmerRows) <= 160 * 1024);
+    EXPECT(kmer_count_lds(SINA_HIP_MAX_QUERY_LEN, kKmerCand) == kmer_count_lds(SINA_HIP_MAX_QUERY_LEN, kKmerRows));
+    EXPECT(kmer_count_lds(SINA_HIP_MAX_QUERY_LEN, kKmerLong) == 32768 * 2 + kmax * 9 + 64 + 64 && kmer_count_lds(SINA_HIP_MAX_QUERY_LEN, kKmerLong) <= 160 * 1024);
+    EXPECT(kmer_count_lds(64, kKmerRows) == 65536 + 576 + 64);
+    // ---- dense lists
+    EXPECT(kmer_dense_threshold(0, 64) == 256 && kmer_dense_threshold(255 * 64, 64) == 256 && kmer_dense_threshold(256 * 64 + 64, 64) == 257);
+    EXPECT(kmer_dense_threshold(256 * 64 + 63, 64) == 256 && kmer_dense_threshold(100000, 64) == 1562 && kmer_dense_threshold(500000, 64) == 7812);
+    EXPECT(kmer_dense_threshold(1000, 1) == 1000 && kmer_dense_threshold(100, 1) == 256 && kmer_dense_threshold(0xFFFFFFFFu, 1) == 0xFFFFFFFFu);
+    EXPECT(kmer_dense_words(1) == 1024 && kmer_dense_words(32768) == 1024 && kmer_dense_words(32769) == 2048 && kmer_dense_words(0) == 0);
+    EXPECT(kmer_dense_words(0xFFFFFFFFu) == 131072u * 1024u);
+    // ---- the fast-first order
+    const uint32_t S = 100, L = SINA_HIP_MAX_QUERY_LEN + 1;  // a short and a long query
+    const std::vector<std::vector<uint32_t>> batches = {{S, S, SINA_HIP_MAX_QUERY_LEN, 0, S}, {L, L + 5, 32767}, {S, L, S, L, S, L, S}, {L, S, L, S}, {}};
+    for (const std::vector<uint32_t> &lens : batches) {
+        const uint32_t nq = (uint32_t)lens.size();
+        std::vector<uint64_t> qoff(nq + 1, 17);  // (offsets need not start at 0)
+        for (uint32_t q = 0; q < nq; q++) qoff[q + 1] = qoff[q] + lens[q];
+        uint32_t n_fast = 12345, want_fast = 0;
+        const std::vector<uint32_t> order = kmer_fast_first(qoff.data(), nq, &n_fast);
+        for (uint32_t q = 0; q < nq; q++) want_fast += lens[q] <= SINA_HIP_MAX_QUERY_LEN;
+        EXPECT(order.size() == nq && n_fast == want_fast);
+        for (uint32_t x = 0; x < nq; x++) {
+            EXPECT(order[x] < nq && (lens[order[x]] <= SINA_HIP_MAX_QUERY_LEN) == (x < n_fast));  // the classes, in their places
+            if (x && x != n_fast) EXPECT(order[x - 1] < order[x]);                                   // stable within each
+        }
+        // gather by the order, scatter back: the caller's rows
+        std::vector<uint32_t> gathered(nq), back(nq, 0xdeadu);
+        for (uint32_t x = 0; x < nq; x++) gathered[x] = 1000 + order[x];
+        for (uint32_t x = 0; x < nq; x++) back[order[x]] = gathered[x];
+        for (uint32_t q = 0; q < nq; q++) EXPECT(back[q] == 1000 + q);
+    }
+    {
+        const uint64_t qoff[5] = {0, L, L + S, 2 * L + S, 2 * L + 2 * S};  // long, short, long, short
+        uint32_t n_fast = 0;
+        const std::vector<uint32_t> order = kmer_fast_first(qoff, 4, &n_fast);
+        EXPECT(n_fast == 2 && order[0] == 1 && order[1] == 3 && order[2] == 0 && order[3] == 2);
+    }
+}
+
 int main() {
+    check_plan();
     static_assert(kBigSelBudget <= (1ull << 30), "the budget is at most 1 GiB");
     static_assert(kKmerSelMax == 4096, "the LDS select kernels' limit");
     uint32_t first, last;

@@ -1,6 +1,6 @@
 """CPU side of the big select (more than 4096 candidates per query): tests/kmer_ref.py pinned to the oracle at such
 sizes, every case of tests/kmer_big_cases.py built (which runs its builder's assertions) and asked again for the edge it
-names, the launch-range arithmetic of sina_amd/csrc/kmer_plan.h in a stand-alone program under the address and
+names, the search call's plan -- sina_amd/csrc/kmer_plan.h -- in a stand-alone program under the address and
 undefined-behaviour sanitizers, the additions to the C ABI, and the precondition of tests/test_gpu_escalation.py.  No
 GPU."""
 import os
@@ -123,8 +123,8 @@ def test_abi_additions():
     assert callable(pipeline.Store.big_select_queries)
     stub = open(os.path.join(ROOT, "tools", "hoststub", "fake_hip.cpp")).read()
     assert re.search(r"\bint %s\(" % sym, stub)
-    kmer = open(os.path.join(ROOT, "sina_amd", "csrc", "kmer.hip")).read()
-    assert "not supported by the LDS select kernel" not in kmer
+    for unit in ("kmer.hip", "kmer_launch.hip"):                       # (the kernels' unit, the search call's driver)
+        assert "not supported by the LDS select kernel" not in open(os.path.join(ROOT, "sina_amd", "csrc", unit)).read()
     plan = open(os.path.join(ROOT, "sina_amd", "csrc", "kmer_plan.h")).read()
     assert "kBigSelBudget = 1ull << 30" in plan and kb.BIG_BUDGET == 1 << 30
     assert "kBigSelBytesPerCand = %d" % kb.BIG_BYTES_PER_CAND in plan

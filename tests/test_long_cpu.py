@@ -151,7 +151,7 @@ def test_tiles_case_holds_more_dense_kmers_than_a_chunk_takes(oracle, wname):
     m_off, _ = lc.oracle_csr("main")
     some = np.unique(lc.windows(lc.lengths().qmasks[0], m_k, not m_nofast))[1:200]
     assert (lc.posting_lengths(m_refs, m_k, not m_nofast, some) == np.diff(m_off.astype(np.int64))[some]).all()
-    dense = ln > max(256, refs.n // 64)                         # (ensure_dense, csrc/kmer.hip)
+    dense = ln > max(256, refs.n // 64)                         # (kmer_dense_threshold, csrc/kmer_plan.h)
     assert int(dense.sum()) > 1023
     assert int((ln > 0).sum()) > int(dense.sum())               # cursor lists beside them
 
