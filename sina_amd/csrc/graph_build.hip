@@ -32,7 +32,9 @@
 //   5. one thread per node writes record and predecessor list; atomicMin / atomicMax collect the
 //      successor minimum column (for --insertion=forbid) and the last successor;
 //   6. sinks and fence flags; LDS-slot / spill-row assignment for the DP kernel by liveness
-//      (sequential over the rows: 16 lanes, a segment each); predecessor entries; the row skip's bound.
+//      (sequential over the rows: 16 lanes, a segment each) -- the other waves find the row skip's column maxima
+//      meanwhile; predecessor entries, the finished record and the row skip's bound in one pass over the rows.  What
+//      these steps change of a row is one LDS word until then (a DAG too large for that: in global memory).
 // HBM traffic: the family's bases twice (bitmap, entries) and the DAG once.
 // All arithmetic is integer except the node weight, which is looked up in a table the
 // HOST computed with the reference's own mixed double/float expression.
@@ -199,6 +201,71 @@ __device__ uint32_t block_exscan_f(uint32_t n, Get get, Out *out, uint32_t *tmp)
     }
     __syncthreads();
     return total;
+}
+
+// inclusive scan of v[0..n) in place; returns the total.
+__device__ uint32_t block_incscan(uint32_t *v, uint32_t n, uint32_t *tmp) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t chunk = (n + kGT - 1) / kGT;
+    const uint32_t b = min(n, tid * chunk), e = min(n, b + chunk);
+    uint32_t s = 0;
+    for (uint32_t i = b; i < e; i++) s += v[i];
+    uint32_t x = s;
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) tmp[wave] = x;
+    __syncthreads();
+    uint32_t base = 0, total = 0;
+    for (int w = 0; w < kGT / 64; w++) {
+        if (w < wave) base += tmp[w];
+        total += tmp[w];
+    }
+    uint32_t run = base + x - s;
+    for (uint32_t i = b; i < e; i++) {  // (a thread's own stretch: nobody else reads or writes it before the barrier)
+        run += v[i];
+        v[i] = run;
+    }
+    __syncthreads();
+    return total;
+}
+
+// A row's code in LDS, steps 6-8 of the DAGs whose rows fit the tile tables' space.  In front of step 7: the row's last
+// successor | kCdSink | kCdFence; behind it: where the finished DP row is kept -- an LDS slot, or kCdSpilled | spill row
+// (fewer than 65 536), or kCdNone (handed to the next row in registers) -- with the two flags still in place.
+constexpr uint32_t kCdSpilled = 1u << 16, kCdNone = 1u << 17, kCdSink = 1u << 30, kCdFence = 1u << 31;
+__device__ __forceinline__ uint32_t row_of_code(uint32_t c) {  // rec.w of a code
+    return (c & kCdNone) ? kRowNone : (c & kCdSpilled) ? (kRowSpilled | (c & 0xFFFFu)) : (c & 0xFFFFu);
+}
+
+// Step 7 for one segment, the rows [b, e): get(m) is row m's code in front of the step, put(m, that, code) takes the code
+// behind it (without the flags); K slots are searched, W of them exist.  Returns the segment's spill rows.
+template <int K, typename Get, typename Put>
+__device__ __forceinline__ uint32_t slot_walk(uint32_t b, uint32_t e, int W, Get get, Put put) {
+    uint32_t fa[K];  // last successor of the row in slot x (0: empty)
+#pragma unroll
+    for (int x = 0; x < K; x++) fa[x] = (x < W) ? 0u : 0xFFFFFFFFu;
+    uint32_t nsp = 0;
+    for (uint32_t m = b; m < e; m++) {
+        const uint32_t cd = get(m);
+        const uint32_t l = cd & 0xFFFFu;
+        uint32_t c = kCdNone;
+        if (!(cd & kCdSink) && l != m + 1) {  // (a row only the next row reads is handed over in registers)
+            // (a row with a successor beyond kFarLds, or in a later segment, is always a spill row)
+            const bool may_slot = !(cd & kCdFence) && l < e;
+            uint32_t slot = K;
+#pragma unroll
+            for (int x = K - 1; x >= 0; x--) slot = (may_slot && fa[x] <= m) ? (uint32_t)x : slot;
+#pragma unroll
+            for (int x = 0; x < K; x++) fa[x] = (slot == (uint32_t)x) ? l : fa[x];
+            c = slot < (uint32_t)K ? slot : (kCdSpilled | nsp++);
+        }
+        put(m, cd, c);
+    }
+    return nsp;
 }
 
 // Step 2 of a tile as a function of its own: the kernel runs with 78 scalar registers at eight waves per SIMD and
@@ -625,26 +692,51 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
         return;
     }
     GP(8)
-    // 6. sinks, successor minimum, fence flag -- and, in the same pass over the rows, the slot allocator's
-    // row codes (step 7) when they fit the tile tables' space
+    // 6. sinks, successor minimum, fence flag.  Where the rows' words fit the tile tables' space (in_lds: a 16S DAG
+    // does) steps 6-8 keep what they change of a row in ONE LDS word, the row's code (kCd...), and step 8 stores the
+    // finished record: rec is written whole by the tile loop and whole by step 8, not a word at a time by every step
+    // in between.  Where they do not fit, the steps work on rec / last in global memory.
     const uint32_t seg_len = dp_slot_segment(N);
     const uint32_t n_seg = (N + seg_len - 1) / seg_len;
     uint32_t *codeL = reinterpret_cast<uint32_t *>(smem);  // (the tile tables' space: everything in front of the bitmap)
     const bool in_lds = (size_t)N * 4 <= a.tile_bytes;
-    if (tid == 0) s_tmp[kGT / 64 + 1] = 0xFFFFFFFFu;  // first sink row
+    // ... and where a second word per row fits behind the codes, step 9's column maxima are found there BESIDE step 7's
+    // walk (which is one wave's work), not behind it
+    const bool beside = a.reach != nullptr && (size_t)N * 8 <= a.tile_bytes;
+    uint32_t *cwL = codeL + N;
+    constexpr int kSFirstSink = kGT / 64 + 1, kSGmin = kGT / 64 + 2, kSSpill = kGT / 64 + 3;  // (s_tmp)
+    if (tid == 0) {
+        s_tmp[kSFirstSink] = 0xFFFFFFFFu;  // first sink row
+        s_tmp[kSGmin] = 0xFFFFFFFFu;       // smallest column maximum (step 9)
+    }
     __syncthreads();
     for (uint32_t i = tid; i < N; i += kGT) {
-        uint32_t z = rec[i].z;
         const uint32_t l = last[i];
+        uint32_t cd = l;
         if (l == 0) {  // (a successor's id is greater than its predecessor's: never 0)
-            z |= kRecSink;
-            atomicMin(&s_tmp[kGT / 64 + 1], i);
+            cd |= kCdSink;
+            atomicMin(&s_tmp[kSFirstSink], i);
             if (a.want_smin) smin[i] = 1000000u;  // "no successor" sentinel of mesh.h:480
         }
-        if (l > i && l - i > (uint32_t)kFarLds) z |= kRecFence;
-        rec[i].z = z;
-        if (in_lds) codeL[i] = l | ((z & kRecSink) ? (1u << 30) : 0u) | ((z & kRecFence) ? (1u << 31) : 0u);
+        if (l > i && l - i > (uint32_t)kFarLds) cd |= kCdFence;
+        if (in_lds) codeL[i] = cd;
+        else if (cd & (kCdSink | kCdFence)) rec[i].z |= ((cd & kCdSink) ? kRecSink : 0u) | ((cd & kCdFence) ? kRecFence : 0u);
     }
+    // step 9's column maxima: the nodes of a column have consecutive ids, the thread of a column's FIRST node finds the
+    // column's maximum and leaves it at that node, 0 at the column's others
+    auto column_maxima = [&](uint32_t *cw, uint32_t first, uint32_t step) {
+        for (uint32_t i = first; i < N; i += step) {
+            const uint32_t pos = node_pos[i];
+            if (i > 0 && node_pos[i - 1] == pos) continue;
+            uint32_t mx = 0;
+            for (uint32_t j = i; j < N && node_pos[j] == pos; j++) {
+                mx = max(mx, prune_gain_units(__uint_as_float(rec[j].y), a.kappa64));
+                cw[j] = 0;
+            }
+            cw[i] = mx;
+            atomicMin(&s_tmp[kSGmin], mx);
+        }
+    };
     __syncthreads();
     GP(9)
     // 7. where every finished DP row is kept for its successors: LDS slots by liveness (first slot
@@ -655,136 +747,162 @@ __global__ void __launch_bounds__(kGT) __attribute__((amdgpu_waves_per_eu(SINA_G
     // order (per-segment counts, prefix sum).  tests/util.py row_store_model states the same rule.
     // (the lanes walk their segments row by row: from LDS when the rows fit the tile tables' space --
     // a dependent global load per row was most of this step's time)
-    if (tid < n_seg) {
-        // (the walk is one dependent chain per lane in a CU that runs 31 other waves: every instruction waits its turn,
-        // so the slot search is compiled for 4 slots -- the DP kernels keep 3 -- and for 8)
-        auto walk = [&](auto kslots) {
-            constexpr int K = decltype(kslots)::value;
-            uint32_t fa[K];  // last successor of the row in slot x (0: empty)
-#pragma unroll
-            for (int x = 0; x < K; x++) fa[x] = (x < a.W) ? 0u : 0xFFFFFFFFu;
-            uint32_t nsp = 0;
+    if (wave == 0) {
+        uint32_t nsp = 0;
+        if (tid < n_seg) {
             const uint32_t b = tid * seg_len, e = min(N, b + seg_len);
-            for (uint32_t m = b; m < e; m++) {
-                uint32_t l, sink, fence;
-                if (in_lds) {
-                    const uint32_t cd = codeL[m];
-                    l = cd & 0xFFFFu;
-                    sink = cd & (1u << 30);
-                    fence = cd & (1u << 31);
-                } else {
-                    const uint32_t z = rec[m].z;
-                    l = last[m];
-                    sink = z & kRecSink;
-                    fence = z & kRecFence;
-                }
-                uint32_t wv = kRowNone;
-                if (!sink && l != m + 1) {  // (a row only the next row reads is handed over in registers)
-                    // (a row with a successor beyond kFarLds, or in a later segment, is always a spill row)
-                    const bool may_slot = !fence && l < e;
-                    uint32_t slot = K;
+            // (the walk is one dependent chain per lane in a CU that runs 31 other waves: every instruction waits its turn,
+            // so the slot search is compiled for 4 slots -- the DP kernels keep 3 -- and for 8)
+            auto walk = [&](auto kslots) {
+                constexpr int K = decltype(kslots)::value;
+                if (in_lds)
+                    return slot_walk<K>(b, e, a.W, [&](uint32_t m) { return codeL[m]; },
+                                        [&](uint32_t m, uint32_t cd, uint32_t c) { codeL[m] = (cd & (kCdSink | kCdFence)) | c; });
+                return slot_walk<K>(b, e, a.W,
+                                    [&](uint32_t m) {
+                                        const uint32_t z = rec[m].z;
+                                        return last[m] | ((z & kRecSink) ? kCdSink : 0u) | ((z & kRecFence) ? kCdFence : 0u);
+                                    },
+                                    [&](uint32_t m, uint32_t, uint32_t c) { rec[m].w = row_of_code(c); });
+            };
+            nsp = (a.W <= 4) ? walk(std::integral_constant<int, 4>()) : walk(std::integral_constant<int, 8>());
+        }
+        // the segments' first spill rows: a prefix sum over the (at most 16) lanes that walked; s_ids is free by now
+        uint32_t x = nsp;
 #pragma unroll
-                    for (int x = K - 1; x >= 0; x--) slot = (may_slot && fa[x] <= m) ? (uint32_t)x : slot;
-#pragma unroll
-                    for (int x = 0; x < K; x++) fa[x] = (slot == (uint32_t)x) ? l : fa[x];
-                    wv = slot < (uint32_t)K ? slot : (kRowSpilled | nsp++);
-                }
-                if (in_lds) codeL[m] = wv;
-                else rec[m].w = wv;
-            }
-            mb[tid].id = nsp;  // (s_ids is free by now: spill rows of my segment)
-        };
-        if (a.W <= 4) walk(std::integral_constant<int, 4>());
-        else walk(std::integral_constant<int, 8>());
+        for (int off = 1; off < 16; off <<= 1) {
+            const uint32_t y = __shfl_up(x, off);
+            if (lane >= (uint32_t)off) x += y;
+        }
+        if (tid < n_seg) mb[tid].id = x - nsp;
+        if (tid == 15) s_tmp[kSSpill] = x;
+    } else if (beside) {
+        column_maxima(cwL, tid - 64u, (uint32_t)kGT - 64u);
     }
     __syncthreads();
-    {   // spill rows get their final numbers: segment base + number within the segment
-        uint32_t tot = 0;
-        for (uint32_t g = 0; g < n_seg; g++) tot += mb[g].id;
-        for (uint32_t i = tid; i < N; i += kGT) {
-            uint32_t w = in_lds ? codeL[i] : rec[i].w;
-            if (w != kRowNone && (w & kRowSpilled)) {
-                uint32_t base = 0;
-                for (uint32_t g = 0; g < i / seg_len; g++) base += mb[g].id;
-                w += base;
-            }
-            rec[i].w = w;
-            if (in_lds) codeL[i] = w;  // (read again by step 8)
-        }
-        if (tid == 0) {
-            sz[kBuiltN] = N;
-            sz[kBuiltEdges] = E;
-            sz[kBuiltSpill] = tot;
-            sz[kBuiltStatus] = (tot > kMaxSpillRows) ? kBuiltSpillCap : 0u;
-            sz[kBuiltFirstSink] = s_tmp[kGT / 64 + 1];
-            sz[kBuiltChainLen] = mb[0].len;
-        }
+    const uint32_t tot = s_tmp[kSSpill];
+    if (tid == 0) {
+        sz[kBuiltN] = N;
+        sz[kBuiltEdges] = E;
+        sz[kBuiltSpill] = tot;
+        sz[kBuiltStatus] = (tot > kMaxSpillRows) ? kBuiltSpillCap : 0u;
+        sz[kBuiltFirstSink] = s_tmp[kSFirstSink];
+        sz[kBuiltChainLen] = mb[0].len;
+        if (beside) sz[kBuiltGmin] = s_tmp[kSGmin];
     }
-    __syncthreads();
-    GP(10)
-    // 8. predecessor entries for the DP kernel: id | (LDS slot or spill row) << 16 | spilled << 31; the first four
-    // ids once more, by row, for the trace-back walk (pred4: N <= ncap here)
     uint2 *pred4 = a.pred4 + (size_t)q * a.ncap;
-    for (uint32_t i = tid; i < N; i += kGT) {
-        const uint4 r = rec[i];
-        const uint32_t np = r.z & 0xFFu;
-        uint32_t first_far = 0;
-        uint32_t dist = np ? 0u : kRecDistFar;  // (ids ascend: the first predecessor is the furthest)
-        uint32_t p4[4] = {0u, 0u, 0u, 0u};
-        for (uint32_t x = 0; x < np; x++) {
-            const uint32_t pa = pred[r.x + x];
-            uint32_t pw = in_lds ? codeL[pa] : rec[pa].w;
-            if (pw == kRowNone) pw = 0;  // (kept in registers for this row: the entry's slot is not read)
-            const bool sp = (pw & kRowSpilled) != 0;
-            if (sp && first_far == 0) first_far = x + 1;
-            dist = max(dist, i - pa);
-            pred[r.x + x] = pa | ((pw & 0x7FFFu) << 16) | (sp ? kPredSpilled : 0u);
-            if (x == 0) p4[0] = pa;
-            else if (x == 1) p4[1] = pa;
-            else if (x == 2) p4[2] = pa;
-            else if (x == 3) p4[3] = pa;
-        }
-        rec[i].z = r.z | (first_far << 24) | (min(dist, kRecDistFar) << kRecDistShift);
-        pred4[i] = pred4_pack(p4[0], p4[1], p4[2], p4[3]);
-    }
-    GP(11)
-    // 9. the DP kernel's row-skip bound (common.h "the bound", mesh_dp.hip PRUNE): R(m) = what a path can still gain
-    // right of node m's column = the sum, over the occupied columns right of it, of the column's best node's gain
-    // (an edge always leads to a column further right, a path takes at most one node per column).  Integer units:
-    // the sums are exact and do not depend on the order of the scan.  The nodes of a column have consecutive ids:
-    // the thread of a column's FIRST node finds the column's maximum; an exclusive scan of "maximum at the first
-    // node, 0 elsewhere" gives every column the total of the columns left of it.
-    if (a.reach != nullptr) {
-        uint2 *rg = a.reach + (size_t)q * a.ncap;
-        // (scratch: nobody reads succ_min in a launch that skips rows -- want_smin is --insertion=forbid; the debug
-        // entry wants both and gets the last successors overwritten instead)
-        // (in LDS where the rows' words fit the tile tables' space: step 8 was the last reader of the slot codes there)
-        uint32_t *cw = in_lds ? codeL : (a.want_smin ? last : smin);
-        if (tid == 0) s_tmp[kGT / 64 + 2] = 0xFFFFFFFFu;  // smallest column maximum
-        __syncthreads();
+    uint2 *rg = a.reach + (size_t)q * a.ncap;  // (used where a.reach is not null)
+    if (in_lds) {
+        // spill rows get their final numbers: segment base + number within the segment
         for (uint32_t i = tid; i < N; i += kGT) {
-            const uint32_t pos = node_pos[i];
-            if (i > 0 && node_pos[i - 1] == pos) continue;
-            uint32_t mx = 0;
-            for (uint32_t j = i; j < N && node_pos[j] == pos; j++) {
-                mx = max(mx, prune_gain_units(__uint_as_float(rec[j].y), a.kappa64));
-                cw[j] = 0;
+            const uint32_t c = codeL[i];
+            if (c & kCdSpilled) codeL[i] = c + mb[i / seg_len].id;  // (fewer than 65 536 rows: no carry out of the number)
+        }
+        // (the scan's first barrier is also the one behind the numbering)
+        uint32_t total = 0;
+        if (beside) total = block_incscan(cwL, N, s_tmp);
+        else __syncthreads();
+        GP(10)
+        // 8. predecessor entries for the DP kernel: id | (LDS slot or spill row) << 16 | spilled << 31; the first four
+        // ids once more, by row, for the trace-back walk (pred4: N <= ncap here); the row's finished record; and, where
+        // the column maxima are in (beside), step 9's bound of the row
+        for (uint32_t i = tid; i < N; i += kGT) {
+            const uint4 r = rec[i];
+            const uint32_t cd = codeL[i];
+            const uint32_t np = r.z & 0xFFu;
+            uint32_t first_far = 0;
+            uint32_t dist = np ? 0u : kRecDistFar;  // (ids ascend: the first predecessor is the furthest)
+            uint32_t p4[4] = {0u, 0u, 0u, 0u};
+            for (uint32_t x = 0; x < np; x++) {
+                const uint32_t pa = pred[r.x + x];
+                const uint32_t pc = codeL[pa];
+                const bool sp = (pc & kCdSpilled) != 0;  // (kCdNone, kept in registers for this row: the number is 0, the entry's slot is not read)
+                if (sp && first_far == 0) first_far = x + 1;
+                dist = max(dist, i - pa);
+                pred[r.x + x] = pa | ((pc & 0x7FFFu) << 16) | (sp ? kPredSpilled : 0u);
+                if (x == 0) p4[0] = pa;
+                else if (x == 1) p4[1] = pa;
+                else if (x == 2) p4[2] = pa;
+                else if (x == 3) p4[3] = pa;
             }
-            cw[i] = mx;
-            atomicMin(&s_tmp[kGT / 64 + 2], mx);
+            uint4 o;
+            o.x = r.x;
+            o.y = r.y;
+            o.z = r.z | ((cd & kCdSink) ? kRecSink : 0u) | ((cd & kCdFence) ? kRecFence : 0u) | (first_far << 24) |
+                  (min(dist, kRecDistFar) << kRecDistShift);
+            o.w = row_of_code(cd);
+            rec[i] = o;
+            pred4[i] = pred4_pack(p4[0], p4[1], p4[2], p4[3]);
+            if (beside) rg[i] = uint2{total - cwL[i], last[i] | ((NC - 1u - rank(node_pos[i])) << 16)};
+        }
+        GP(11)
+        // 9. the DP kernel's row-skip bound (common.h "the bound", mesh_dp.hip PRUNE): R(m) = what a path can still gain
+        // right of node m's column = the sum, over the occupied columns right of it, of the column's best node's gain
+        // (an edge always leads to a column further right, a path takes at most one node per column).  Integer units:
+        // the sums are exact and do not depend on the order of the scan.  An INCLUSIVE scan of "maximum at the column's
+        // first node, 0 at its others" gives every node of a column the total up to and including its column.
+        // (here for the DAGs whose codes fit the tile tables' space but not the maxima beside them: step 8 was the last
+        // reader of the codes)
+        if (a.reach != nullptr && !beside) {
+            __syncthreads();
+            column_maxima(codeL, tid, (uint32_t)kGT);
+            __syncthreads();
+            if (tid == 0) sz[kBuiltGmin] = s_tmp[kSGmin];
+            total = block_incscan(codeL, N, s_tmp);
+            for (uint32_t i = tid; i < N; i += kGT)
+                rg[i] = uint2{total - codeL[i], last[i] | ((NC - 1u - rank(node_pos[i])) << 16)};
+        }
+        GP(12)
+    } else {
+        for (uint32_t i = tid; i < N; i += kGT) {
+            const uint32_t w = rec[i].w;
+            if (w != kRowNone && (w & kRowSpilled)) rec[i].w = w + mb[i / seg_len].id;
         }
         __syncthreads();
-        if (tid == 0) sz[kBuiltGmin] = s_tmp[kGT / 64 + 2];
-        const uint32_t total = block_exscan(cw, cw, N, s_tmp);
+        GP(10)
+        // 8. as above, a predecessor's row from its record
         for (uint32_t i = tid; i < N; i += kGT) {
-            const uint32_t pos = node_pos[i];
-            if (i > 0 && node_pos[i - 1] == pos) continue;
-            const uint32_t right = (i + 1 < N) ? total - cw[i + 1] : 0u;  // (cw[i + 1] = columns up to and including mine)
-            const uint32_t cols_right = NC - 1u - rank(pos);                 // (the dense column index of step 2)
-            for (uint32_t j = i; j < N && node_pos[j] == pos; j++) rg[j] = uint2{right, ((a.want_smin && !in_lds) ? 0u : last[j]) | (cols_right << 16)};
+            const uint4 r = rec[i];
+            const uint32_t np = r.z & 0xFFu;
+            uint32_t first_far = 0;
+            uint32_t dist = np ? 0u : kRecDistFar;
+            uint32_t p4[4] = {0u, 0u, 0u, 0u};
+            for (uint32_t x = 0; x < np; x++) {
+                const uint32_t pa = pred[r.x + x];
+                uint32_t pw = rec[pa].w;
+                if (pw == kRowNone) pw = 0;  // (kept in registers for this row: the entry's slot is not read)
+                const bool sp = (pw & kRowSpilled) != 0;
+                if (sp && first_far == 0) first_far = x + 1;
+                dist = max(dist, i - pa);
+                pred[r.x + x] = pa | ((pw & 0x7FFFu) << 16) | (sp ? kPredSpilled : 0u);
+                if (x == 0) p4[0] = pa;
+                else if (x == 1) p4[1] = pa;
+                else if (x == 2) p4[2] = pa;
+                else if (x == 3) p4[3] = pa;
+            }
+            rec[i].z = r.z | (first_far << 24) | (min(dist, kRecDistFar) << kRecDistShift);
+            pred4[i] = pred4_pack(p4[0], p4[1], p4[2], p4[3]);
         }
+        GP(11)
+        // 9. as above, with an exclusive scan and the thread of a column's first node storing the column's bounds
+        if (a.reach != nullptr) {
+            // (scratch: nobody reads succ_min in a launch that skips rows -- want_smin is --insertion=forbid; the debug
+            // entry wants both and gets the last successors overwritten instead)
+            uint32_t *cw = a.want_smin ? last : smin;
+            column_maxima(cw, tid, (uint32_t)kGT);
+            __syncthreads();
+            if (tid == 0) sz[kBuiltGmin] = s_tmp[kSGmin];
+            const uint32_t total = block_exscan(cw, cw, N, s_tmp);
+            for (uint32_t i = tid; i < N; i += kGT) {
+                const uint32_t pos = node_pos[i];
+                if (i > 0 && node_pos[i - 1] == pos) continue;
+                const uint32_t right = (i + 1 < N) ? total - cw[i + 1] : 0u;  // (cw[i + 1] = columns up to and including mine)
+                const uint32_t cols_right = NC - 1u - rank(pos);                 // (the dense column index of step 2)
+                for (uint32_t j = i; j < N && node_pos[j] == pos; j++) rg[j] = uint2{right, (a.want_smin ? 0u : last[j]) | (cols_right << 16)};
+            }
+        }
+        GP(12)
     }
-    GP(12)
     GP_FLUSH
 }
 
