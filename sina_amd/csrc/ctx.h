@@ -25,7 +25,7 @@ struct sina_hip_store {
     bool have_refs = false, have_index = false;
     // Dense posting lists as bitmaps over the references (kmer_index.hip, ensure_dense): built lazily from
     // the CSR index by the first search after the index changed
-    sina_hip::DevBuf dense_id, dense_bits;  // u32 [4^k]: bitmap number or ~0; u32 [n_dense][dense_words]
+    sina_hip::DevBuf dense_id, dense_bits;  // u32 [4^k]: bitmap number or ~0; u32 [n_dense + 1][dense_words], the last row zero
     uint32_t n_dense = 0, dense_words = 0;
     std::atomic<bool> dense_ready{false};
     // The references' name order for the rank kernel (rank.hip, sina_hip_upload_name_order): u32 [n_refs] position of

@@ -89,6 +89,7 @@ struct CountArgs {
     const uint32_t *dense_id;
     const uint32_t *dense_bits;
     uint32_t dense_words;
+    uint32_t dense_zero;  // number of the all-zero bitmap behind the lists' (no k-mer's: pads a query's list to eights)
     // CAND (kmer_count_kernel<true>): instead of the score row, the references that can still be among the top
     // `topm` -- keys (score + 32768) << 32 | id, at most cand_cap per query; cand_n[q] = how many there were
     unsigned long long *cand;
@@ -757,7 +758,7 @@ int launch_kmer_count(sina_hip_ctx *c, const KmerLaunch &l, hipStream_t s) {
     const bool cand = l.path == kKmerCand;
     const CountArgs a{l.qmask, l.qoff, st->idx_off.as<uint32_t>(), st->idx_ids.as<uint32_t>(), c->k_scores.as<int16_t>(), c->k_tmp0.as<uint32_t>(),
                       c->k_tmp2.as<unsigned long long>(), st->n_refs, (uint32_t)kmer_row_stride(st->n_refs), kmer_kmax(l.max_qlen, l.path), st->k,
-                      st->nofast ? 0 : 1, st->n_dense ? st->dense_id.as<uint32_t>() : nullptr, st->dense_bits.as<uint32_t>(), st->dense_words,
+                      st->nofast ? 0 : 1, st->n_dense ? st->dense_id.as<uint32_t>() : nullptr, st->dense_bits.as<uint32_t>(), st->dense_words, st->n_dense,
                       // (the candidate lists; kmer_select_cand_kernel turns cand_n into out_n in place)
                       cand ? c->k_tmp1.as<unsigned long long>() : nullptr, cand ? c->k_out_n.as<uint32_t>() : nullptr, kCandCap, l.max};
     void (*kernel)(CountArgs) = l.path == kKmerLong ? kmer_count_long_kernel : (cand ? kmer_count_kernel<true> : kmer_count_kernel<false>);

@@ -80,31 +80,51 @@
             // hundred bitmaps need four of the seven; the ripple and the unpacking below are compiled for each count)
             auto dense_path = [&](auto nhi_c) {
                 constexpr int NHI = decltype(nhi_c)::value;
-                const uint32_t *bw = a.dense_bits + (size_t)(tile_lo >> 5) + tid;
+                // A bitmap's number and its row's address are the same for every thread: both stay on the scalar unit.
+                // A wave fetches up to 64 numbers with one LDS read, a number per lane, padded to a multiple of eight
+                // with the all-zero row (a.dense_zero: no branch per word); a word's load is the row's base in SGPRs
+                // plus my_word, the loop-invariant byte offset of this thread's word in any row (32 bits: a row is at
+                // most 2^29 bytes) -- one VGPR per word in flight, no vector multiply, no LDS wait in the body.
+                const uint32_t my_word = 4u * ((tile_lo >> 5) + tid);
+                const uint32_t row_bytes = 4u * a.dense_words;
                 uint32_t ones = 0, twos = 0, fours = 0, hi[NHI > 0 ? NHI : 1] = {0};  // hi[p]: weight 8 << p
                 auto csa = [](uint32_t &h, uint32_t &l, uint32_t x, uint32_t y, uint32_t z) {
                     const uint32_t u = x ^ y;
                     h = (x & y) | (u & z);
                     l = u ^ z;
                 };
-                for (uint32_t i = 0; i < nd; i += 8) {
-                    uint32_t w[8];
+                for (uint32_t i0 = 0; i0 < nd; i0 += 64) {
+                    const uint32_t n = min(nd - i0, 64u);
+                    const uint32_t num = (uint32_t)lane < n ? *(dtop - (i0 + lane)) : a.dense_zero;
+                    for (uint32_t j = 0; j < n; j += 8) {
+                        uint32_t w[8];
+                        uint32_t word = my_word;
+                        asm("" : "+v"(word));  // (its 64-bit extension made here, where the loads' address selection sees it)
 #pragma unroll
-                    for (int u = 0; u < 8; u++) w[u] = (i + u < nd) ? bw[(size_t)*(dtop - (i + u)) * a.dense_words] : 0u;
-                    uint32_t twosA, twosB, foursA, foursB, eights;
-                    csa(twosA, ones, ones, w[0], w[1]);
-                    csa(twosB, ones, ones, w[2], w[3]);
-                    csa(foursA, twos, twos, twosA, twosB);
-                    csa(twosA, ones, ones, w[4], w[5]);
-                    csa(twosB, ones, ones, w[6], w[7]);
-                    csa(foursB, twos, twos, twosA, twosB);
-                    csa(eights, fours, fours, foursA, foursB);
-                    uint32_t carry = eights;
+                        for (int u = 0; u < 8; u++) {
+                            const uint32_t id = (uint32_t)__builtin_amdgcn_readlane((int)num, (int)(j + u));
+                            // (the base pinned to SGPRs, in the global address space: the load takes it as its scalar base;
+                            // folded into the thread's 64-bit address it costs a vector add and two VGPRs per word)
+                            using global_bytes = const __attribute__((address_space(1))) char *;
+                            global_bytes row_bits = (global_bytes)a.dense_bits + (uint64_t)id * row_bytes;
+                            asm("" : "+s"(row_bits));
+                            w[u] = *(const __attribute__((address_space(1))) uint32_t *)(row_bits + word);
+                        }
+                        uint32_t twosA, twosB, foursA, foursB, eights;
+                        csa(twosA, ones, ones, w[0], w[1]);
+                        csa(twosB, ones, ones, w[2], w[3]);
+                        csa(foursA, twos, twos, twosA, twosB);
+                        csa(twosA, ones, ones, w[4], w[5]);
+                        csa(twosB, ones, ones, w[6], w[7]);
+                        csa(foursB, twos, twos, twosA, twosB);
+                        csa(eights, fours, fours, foursA, foursB);
+                        uint32_t carry = eights;
 #pragma unroll
-                    for (int p = 0; p < NHI; p++) {
-                        const uint32_t t2 = hi[p] & carry;
-                        hi[p] ^= carry;
-                        carry = t2;
+                        for (int p = 0; p < NHI; p++) {
+                            const uint32_t t2 = hi[p] & carry;
+                            hi[p] ^= carry;
+                            carry = t2;
+                        }
                     }
                 }
                 // add my 32 counts to the tile's counters: words 16 t .. 16 t + 15 are mine alone now
@@ -145,9 +165,12 @@
                     }
                 }
             };
+            // (in the last tile a wave whose 2048 references all lie behind the store's end has zero words only:
+            // nothing to count, nothing to add -- wave-uniform, and the barrier below is taken all the same)
+            const bool live = tile_lo + 2048u * (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)) < a.n_refs;
             // (counts up to nd: 32 - clz(nd) bits, three of them in ones / twos / fours)
             const int bits = 32 - __builtin_clz(nd);
-            switch (bits > 3 ? bits - 3 : 0) {
+            if (live) switch (bits > 3 ? bits - 3 : 0) {
             case 0: dense_path(std::integral_constant<int, 0>()); break;
             case 1: dense_path(std::integral_constant<int, 1>()); break;
             case 2: dense_path(std::integral_constant<int, 2>()); break;

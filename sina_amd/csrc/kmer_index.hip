@@ -174,7 +174,9 @@ int ensure_dense(sina_hip_ctx *c) {
     counter.release();
     st->n_dense = nd;
     if (nd) {
-        const size_t bytes = 4 * (size_t)nd * st->dense_words;
+        // (one row more than lists: row nd stays all zero -- no k-mer's, dense_id never names it, n_dense does not count
+        // it; the count kernels pad a query's bitmap numbers to a multiple of eight with it)
+        const size_t bytes = 4 * ((size_t)nd + 1) * st->dense_words;
         if (st->dense_bits.reserve_exact(bytes)) return 1;
         SH_CHECK(hipMemsetAsync(st->dense_bits.p, 0, bytes, s));
         hipLaunchKernelGGL(fill_dense, dim3((unsigned)(((uint64_t)nk * 64 + 255) / 256)), dim3(256), 0, s,
