@@ -362,9 +362,43 @@ typedef struct sina_hip_align_params {
     const float *weights;   /* posvar weights => scoring_scheme_weighted, or NULL (the _wsets entries: n_sets vectors) */
     uint32_t n_weights;
     int32_t assemble;       /* 1: also do the cseq container steps of backtrack() on the device where they
-                             * are plain (see sina_hip_align_out::assembled); 0 (default): columns only */
+                             * are plain (see sina_hip_align_out::assembled); 0 (default): columns only;
+                             * 2 (SINA_ASSEMBLE_SHIFT): 1 plus the insertions that shift their neighbours */
 } sina_hip_align_params;
 void sina_hip_align_params_default(sina_hip_align_params *p);
+
+/* assemble == SINA_ASSEMBLE_SHIFT: what assemble == 1 does, and an insertion that does not fit the free columns in
+ * front of the next base is placed by the reference's widening loop (cseq_base::fix_duplicate_positions,
+ * src/cseq.cpp:503-570): the range grows towards the nearer free column, left on a tie, and takes the bases it passes
+ * along -- a later run of duplicates the right scan walks through included.  Every base so placed is lower-cased under
+ * SINA_LOWERCASE_UNALIGNED; nast_total / nast_longest count the widened runs, nast_last_run the last run before its
+ * widening.  It holds for every entry of the fast path (sina_hip_align_graphs, _graphs_wsets, _graphs_any for the
+ * queries it routes there, _families, _families_wsets, _profiles); the wide path assembles nothing, as before.
+ * Still left to the host (assembled = 0, out_pos as the walk wrote it): more than SINA_HIP_SHIFT_LOG shifted runs in
+ * one query, no free column on either side (the reference throws), a column at or beyond the width -- appended, or
+ * taken for free by a widening that reaches the last base in column width - 1 --, more than 4096 bases.
+ *
+ * sina_hip_staged_shift_log: [nq][1 + 3 * SINA_HIP_SHIFT_LOG] words of the context's last align call, laid out like
+ * that call's `out`: word 0 of row q is the number of shifted runs of query q, then {N, B, E} per run in sequence
+ * order -- the reference's "shifting bases to fit in N bases at pos B to E;", written before the run is widened.
+ * Host memory owned by the context, valid until its next align call; NULL unless that call ran with assemble == 2.
+ * A query with assembled == 0 has no events.
+ *
+ * sina_hip_assemble_stats: since init / fork, over the fast path's launches that ran with assemble != 0: their
+ * queries, those the device assembled, and of these the queries with at least one shifted run and their shifted runs.
+ *
+ * sina_hip_debug_assemble (test hook): the assembly alone, on columns the caller made.  out[q] comes in with n_out,
+ * end_s, cutoff_head, cutoff_tail, aligned_bases and status, out_pos (laid out by qoff like qmask) with the columns as
+ * handed to cseq::append; both go out as after an align call with these params (p->assemble 1 or 2), and the shift log
+ * is staged.  n_out may not exceed the query's length, and end_s + the kept tail overhang must name a base of the
+ * query at least n_out - 1 from its start: the call fails otherwise, nothing is read out of bounds.
+ * sina_hip_debug_assemble_ms: the kernel's own time in the context's last sina_hip_debug_assemble call (events
+ * around its launch; 0 before the first) -- what tools/perf_shift.py compares the two instantiations with. */
+#define SINA_ASSEMBLE_SHIFT 2
+#define SINA_HIP_SHIFT_LOG 32u
+const uint32_t *sina_hip_staged_shift_log(sina_hip_ctx *ctx);
+int sina_hip_assemble_stats(sina_hip_ctx *ctx, uint64_t *queries, uint64_t *assembled, uint64_t *shifted_queries,
+                            uint64_t *shifted_runs);
 /* The aligned columns of the context's last sina_hip_align_graphs / sina_hip_align_families call, laid out like
  * that call's out_pos with qoff[0] taken as 0 (query q's entries start at qoff[q] - qoff[0]).  Host memory owned
  * by the context; valid until the next align call on this context (or its destruction). */
@@ -432,7 +466,8 @@ typedef struct sina_hip_align_out {
      * after the append rule, setWidth, reverse and the NAST fix-up (src/mesh.h:603-726,
      * src/cseq.cpp:456-594) -- and the fix-up's log facts below; 0 if out_pos holds the appended
      * columns as without the switch (an insertion that does not fit its gap and makes neighbours
-     * move, a column beyond the alignment, more than 4096 bases: the host finishes those). */
+     * move, a column beyond the alignment, more than 4096 bases: the host finishes those; with
+     * assemble == SINA_ASSEMBLE_SHIFT the first of these is the device's too, see there). */
     uint32_t assembled;
     uint32_t nast_total, nast_longest, nast_last_run; /* "total inserted bases", "longest insertion",
                                                         * "total inserted bases before shifting"     */
@@ -532,6 +567,11 @@ int sina_hip_debug_mesh(sina_hip_ctx *ctx, const sina_hip_graph_batch *g, const 
 int sina_hip_debug_mesh_wide(sina_hip_ctx *ctx, const sina_hip_graph_batch *g, const uint8_t *qmask,
                              uint32_t qlen, const sina_hip_align_params *p, uint32_t *tb_vm,
                              uint32_t *tb_vs, float *value);
+
+/* Test hook: assemble_kernel alone on caller-made emitted columns -- see SINA_ASSEMBLE_SHIFT above. */
+int sina_hip_debug_assemble(sina_hip_ctx *ctx, const sina_hip_align_params *p, uint32_t width, const uint8_t *qmask,
+                            const uint64_t *qoff, uint32_t nq, sina_hip_align_out *out, uint32_t *out_pos);
+int sina_hip_debug_assemble_ms(sina_hip_ctx *ctx, double *kernel_ms);
 
 /* Test hooks for the certified row skip: what the DP kernel reported for query q of the context's LAST launch
  * (attempts 0: that launch swept everything), and the first n entries of the per-node bound R(m) the last launch /

@@ -38,7 +38,12 @@ ABI_SYMBOLS = [
     "sina_hip_upload_pairs", "sina_hip_pair_counts", "sina_hip_pair_stats",
     "sina_hip_align_count_pairs", "sina_hip_staged_pair_counts", "sina_hip_pair_inplace_stats",
     "sina_hip_align_count_identity", "sina_hip_staged_identity", "sina_hip_identity_inplace_stats",
+    "sina_hip_staged_shift_log", "sina_hip_assemble_stats", "sina_hip_debug_assemble", "sina_hip_debug_assemble_ms",
 ]
+
+# include/sina_hip.h: SINA_ASSEMBLE_SHIFT, SINA_HIP_SHIFT_LOG
+ASSEMBLE_SHIFT = 2
+SHIFT_LOG = 32
 
 # include/sina_hip.h: SINA_CMP_COVER_*, in CMP_COVER_TYPE's order
 COVER_RULES = ("abs", "query", "target", "overlap", "all", "average", "min", "max", "nogap")
@@ -171,6 +176,11 @@ def load():
     L.sina_hip_staged_identity.restype = C.POINTER(C.c_uint32)
     L.sina_hip_staged_identity.argtypes = [vp]
     L.sina_hip_identity_inplace_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
+    L.sina_hip_staged_shift_log.restype = C.POINTER(C.c_uint32)
+    L.sina_hip_staged_shift_log.argtypes = [vp]
+    L.sina_hip_assemble_stats.argtypes = [vp, u64p, u64p, u64p, u64p]
+    L.sina_hip_debug_assemble.argtypes = [vp, C.POINTER(AlignParams), C.c_uint32, u8p, u64p, C.c_uint32, C.POINTER(AlignOut), u32p]
+    L.sina_hip_debug_assemble_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.sina_hip_last_error_is_limit.restype = C.c_int
     L.sina_hip_debug_mesh_wide.argtypes = [vp, C.POINTER(GraphBatch), u8p, C.c_uint32, C.POINTER(AlignParams),
                                            u32p, u32p, f32p]
@@ -564,6 +574,40 @@ class Context:
         """The in-place pair-count kernel on this context so far: dict(kernel_ms, sequences, launches); sequences
         counts assembled queries only."""
         return self._counters(self.L.sina_hip_pair_inplace_stats, KERNEL_MS + u64_fields("sequences", "launches"))
+
+    def staged_shift_log(self):
+        """The shifted runs of this context's last align call (assemble=2): a list with one entry per query, laid out
+        like the call's `out` -- the query's events [(N, B, E), ...] in sequence order, the numbers of the reference's
+        "shifting bases to fit in N bases at pos B to E;".  None unless that call ran with assemble=2."""
+        p = self.L.sina_hip_staged_shift_log(self.h)
+        if not p:
+            return None
+        nq = getattr(self, "_align_nq", 0)
+        rows = np.ctypeslib.as_array(p, shape=(max(nq, 1), 1 + 3 * SHIFT_LOG))[:nq]
+        return [[tuple(int(x) for x in r[1 + 3 * e:4 + 3 * e]) for e in range(int(r[0]))] for r in rows]
+
+    def assemble_stats(self):
+        """The device assembly on this context so far: dict(queries, assembled, shifted_queries, shifted_runs) over the
+        fast path's launches that ran with assemble != 0."""
+        return self._counters(self.L.sina_hip_assemble_stats, u64_fields("queries", "assembled", "shifted_queries", "shifted_runs"))
+
+    def debug_assemble(self, params, width, qmask, qoff, out, out_pos):
+        """The assembly alone on caller-made columns: out (ALIGN_OUT_DTYPE, with n_out, end_s, cutoff_head, cutoff_tail,
+        aligned_bases, status) and out_pos (the columns as handed to cseq::append, laid out by qoff) come back as
+        after an align call with `params` (assemble 1 or 2), as copies; the shift log is staged."""
+        qmask = _c(qmask, np.uint8)
+        qoff = _c(qoff, np.uint64)
+        out = np.array(out, ALIGN_OUT_DTYPE, copy=True)
+        pos = np.array(out_pos, np.uint32, copy=True)
+        assert len(out) == len(qoff) - 1 and len(pos) >= int(qoff[-1]) and len(qmask) >= int(qoff[-1])
+        self._align_nq = len(qoff) - 1
+        self._check(self.L.sina_hip_debug_assemble(self.h, C.byref(params), width, _ptr(qmask, u8p), _ptr(qoff, u64p), len(out),
+                                                   out.ctypes.data_as(C.POINTER(AlignOut)), _ptr(pos, u32p)))
+        return out, pos
+
+    def debug_assemble_ms(self):
+        """The assembly kernel's own time in this context's last debug_assemble call, in milliseconds."""
+        return self._counters(self.L.sina_hip_debug_assemble_ms, KERNEL_MS)["kernel_ms"]
 
     def count_identity(self, on=True):
         """The switch of the in-place family identity (--calc-idty): with it on, align_families, align_families_wsets

@@ -586,6 +586,98 @@ int sina_hip_debug_mesh(sina_hip_ctx *c, const sina_hip_graph_batch *g, const ui
     return align_graphs_impl(c, g, qmask, qoff, p, &o, pos.data(), &dbg);
 }
 
+const uint32_t *sina_hip_staged_shift_log(sina_hip_ctx *c) {
+    if (!c) {
+        set_error("staged_shift_log: null ctx");
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    return c->shift.staged();
+}
+
+int sina_hip_assemble_stats(sina_hip_ctx *c, uint64_t *queries, uint64_t *assembled, uint64_t *shifted_queries, uint64_t *shifted_runs) {
+    if (!c || !queries || !assembled || !shifted_queries || !shifted_runs) SH_FAIL("assemble_stats: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *queries = c->asm_use.queries;
+    *assembled = c->asm_use.assembled;
+    *shifted_queries = c->asm_use.shifted_queries;
+    *shifted_runs = c->asm_use.shifted_runs;
+    return 0;
+}
+
+// The assembly alone: the caller's columns and walk results go up as a launch's would lie on the device behind the
+// walk, assemble_kernel runs over them, both come down again.  Everything the kernel indexes with is checked here.
+int sina_hip_debug_assemble(sina_hip_ctx *c, const sina_hip_align_params *p, uint32_t width, const uint8_t *qmask, const uint64_t *qoff,
+                            uint32_t nq, sina_hip_align_out *out, uint32_t *out_pos) {
+    if (!c || !p || !qmask || !qoff || !out || !out_pos) SH_FAIL("debug_assemble: null argument");
+    if (p->assemble != 1 && p->assemble != SINA_ASSEMBLE_SHIFT) SH_FAIL("debug_assemble: p->assemble must be 1 or 2");
+    if (width == 0 || width > 0x1000000u) SH_FAIL("debug_assemble: width must be in 1..2^24");
+    align_call call(c);
+    sina_hip_hint_guard hints(c);
+    if (nq == 0) return 0;
+    const bool keep_over = p->overhang != SINA_OVERHANG_REMOVE;
+    std::vector<QDesc> qd(nq);
+    uint32_t max_l = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        if (qoff[q + 1] <= qoff[q] || qoff[q + 1] - qoff[q] > 65535) SH_FAIL("debug_assemble: query length must be in 1..65535");
+        const uint64_t L = qoff[q + 1] - qoff[q];
+        const sina_hip_align_out &o = out[q];
+        if (o.status == 0) {
+            if (o.cutoff_tail < 0 || o.cutoff_head < 0 || o.aligned_bases < 0) SH_FAIL("debug_assemble: negative count");
+            const uint64_t first_q = (uint64_t)o.end_s + (keep_over ? (uint64_t)o.cutoff_tail : 0u);  // query index of append 0
+            if (o.n_out > L || first_q >= L || (o.n_out != 0 && first_q + 1 < o.n_out))
+                SH_FAIL("debug_assemble: query " + std::to_string(q) + ": n_out, end_s and cutoff_tail do not fit its length");
+        }
+        memset(&qd[q], 0, sizeof(QDesc));
+        qd[q].q_off = qoff[q] - qoff[0];
+        qd[q].L = (uint32_t)L;
+        max_l = std::max<uint32_t>(max_l, (uint32_t)L);
+    }
+    const uint64_t nqm = qoff[nq] - qoff[0];
+    SH_CHECK(hipSetDevice(c->device));
+    if (call.begin(0, p, nq)) return 1;  // (no counts; the shift log of assemble = 2)
+    if (c->qd.reserve(sizeof(QDesc) * nq) || c->qmask.reserve(nqm) || c->out.reserve(sizeof(sina_hip_align_out) * nq) ||
+        c->out_pos.reserve(4 * nqm) || c->h_out.reserve(sizeof(sina_hip_align_out) * nq) || c->h_out_pos.reserve(4 * nqm) ||
+        c->shift.reserve(nq))
+        return 1;
+    hipStream_t s = c->stream;
+    for (uint32_t q = 0; q < nq; q++) out[q].assembled = out[q].nast_total = out[q].nast_longest = out[q].nast_last_run = 0;
+    if (upload(c, 5, c->qd.p, qd.data(), sizeof(QDesc) * nq, s) || upload(c, 6, c->qmask.p, qmask + qoff[0], nqm, s) ||
+        upload(c, 7, c->out.p, out, sizeof(sina_hip_align_out) * nq, s) || upload(c, 8, c->out_pos.p, out_pos + qoff[0], 4 * nqm, s))
+        return 1;
+    BtArgs b{};
+    b.qd = c->qd.as<QDesc>();
+    b.out = c->out.as<sina_hip_align_out>();
+    b.out_pos = c->out_pos.as<uint32_t>();
+    b.nq = nq;
+    b.width = width;
+    b.overhang = p->overhang;
+    b.qmask = c->qmask.as<uint8_t>();
+    b.lowercase = p->lowercase;
+    b.asm_cap = max_l;
+    b.shift_log = p->assemble == SINA_ASSEMBLE_SHIFT ? c->shift.rows.as<uint32_t>() : nullptr;
+    SH_CHECK(hipEventRecord(c->ev[0], s));  // (no launch of the DP path is under way: the context's mutex is held)
+    if (launch_assemble(b, s)) return 1;
+    SH_CHECK(hipEventRecord(c->ev[1], s));
+    SH_CHECK(hipMemcpyAsync(c->h_out.p, c->out.p, sizeof(sina_hip_align_out) * nq, hipMemcpyDeviceToHost, s));
+    SH_CHECK(hipMemcpyAsync(c->h_out_pos.p, c->out_pos.p, 4 * nqm, hipMemcpyDeviceToHost, s));
+    if (c->shift.copy(0, nq, s)) return 1;
+    SH_CHECK(wait_stream(c, s));
+    memcpy(out, c->h_out.p, sizeof(sina_hip_align_out) * nq);
+    memcpy(out_pos + qoff[0], c->h_out_pos.p, 4 * nqm);
+    float ms = 0;
+    SH_CHECK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    c->debug_assemble_ms = ms;
+    return 0;
+}
+
+int sina_hip_debug_assemble_ms(sina_hip_ctx *c, double *kernel_ms) {
+    if (!c || !kernel_ms) SH_FAIL("debug_assemble_ms: null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *kernel_ms = c->debug_assemble_ms;
+    return 0;
+}
+
 int sina_hip_debug_dp_info(sina_hip_ctx *c, uint32_t q, sina_hip_dp_info *out) {
     if (!c || !out) SH_FAIL("debug_dp_info: null argument");
     std::lock_guard<std::mutex> lk(c->mu);

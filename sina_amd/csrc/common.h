@@ -392,6 +392,8 @@ struct BtArgs {
     int lowercase;
     uint32_t asm_cap;  // bases of the launch's longest query (the kernel's LDS follows it)
     const float *self16;  // --fs-no-graph: comp(base, base) per iupac mask (sum_weight's term), else nullptr
+    // assemble = 2 (SINA_ASSEMBLE_SHIFT): the launch's shift log, [nq][1 + 3 * SINA_HIP_SHIFT_LOG] words; nullptr: assemble_kernel<false>
+    uint32_t *shift_log;
 };
 
 // The (threads, cells per thread) geometry of a DP launch: dp_geom_for (dp_plan.h) picks it for the longest query of a

@@ -170,6 +170,38 @@ struct InplaceCount {
     const uint32_t *staged() const { return active ? h_rows.as<uint32_t>() : nullptr; }
 };
 enum inplace_count { kInplacePairs, kInplaceIdentity, kNumInplace };
+
+// The shift log of an align call that runs with assemble = 2 (traceback.hip, assemble_kernel<true>;
+// sina_hip_staged_shift_log): a launch range's rows on the device and the whole call's rows in pinned memory, laid out
+// like the call's `out` -- InplaceCount's layout and lifetime, but no kernel, event or switch of its own: the assembly
+// writes the rows, the call's params say whether.
+struct ShiftLog {
+    static constexpr size_t row_bytes = 4 * (1 + 3 * (size_t)SINA_HIP_SHIFT_LOG);
+    bool active = false;  // the call in progress -- afterwards: the last one -- ran with assemble = 2 (align_call)
+    DevBuf rows;
+    HostBuf h_rows;
+    int begin(bool on, uint32_t nq) {
+        active = false;
+        if (!on) return 0;
+        if (h_rows.reserve(row_bytes * nq)) return 1;
+        memset(h_rows.p, 0, row_bytes * nq);  // (the queries that never see a launch range of the fast path: no events)
+        active = true;
+        return 0;
+    }
+    int reserve(uint32_t bq) { return active ? rows.reserve(row_bytes * bq) : 0; }
+    int copy(uint32_t q_base, uint32_t bq, hipStream_t s) {
+        if (!active) return 0;
+        SH_CHECK(hipMemcpyAsync(h_rows.as<unsigned char>() + row_bytes * q_base, rows.p, row_bytes * bq, hipMemcpyDeviceToHost, s));
+        return 0;
+    }
+    const uint32_t *staged() const { return active ? h_rows.as<uint32_t>() : nullptr; }
+    const uint32_t *row(uint32_t q) const { return h_rows.as<uint32_t>() + (row_bytes / 4) * q; }
+};
+// What the device assembly has done on a context (sina_hip_assemble_stats): queries of the fast path's launches that
+// ran with assemble != 0, those it finished, and of these the queries with a shifted run and their shifted runs.
+struct AssembleUse {
+    uint64_t queries = 0, assembled = 0, shifted_queries = 0, shifted_runs = 0;
+};
 }  // namespace sina_hip
 
 struct sina_hip_ctx {
@@ -217,6 +249,9 @@ struct sina_hip_ctx {
     // the counts that ride on an align call: [n][6] pair counters in 24 bytes, [n][2] identity words in 8
     sina_hip::InplaceCount inplace[sina_hip::kNumInplace] = {{24, sina_hip::kUsePairsInplace, 12},
                                                              {sina_hip::identity_row_bytes(1), sina_hip::kUseIdentityInplace, 13}};
+    sina_hip::ShiftLog shift;            // assemble = 2: the shifted runs' log rows
+    sina_hip::AssembleUse asm_use;       // (by the context's caller, who holds its mutex)
+    double debug_assemble_ms = 0;        // the kernel's time in the last sina_hip_debug_assemble call
     sina_hip::HostBuf h_out, h_out_pos;  // pinned staging for the DP results
     // h_out_pos holds the aligned columns of a whole align call (laid out like the caller's out_pos): a launch
     // range writes at DpLaunch::out_pos_base, callers that pass no out_pos read them here (sina_hip_staged_out_pos)
@@ -292,6 +327,8 @@ struct sina_hip_ctx {
         h_out.release();
         h_out_pos.release();
         for (auto &ic : inplace) ic.h_rows.release();
+        shift.rows.release();
+        shift.h_rows.release();
         h_res.release();
         for (auto &h : h_stage) h.release();
         if (owns_store && st) {
@@ -730,8 +767,9 @@ int rank_check_rules(const char *who, sina_hip_ctx *c, int iupac_rule, int cover
 namespace sina_hip {
 // ---- the one way into an align call.  Every entry that can run the DP path (sina_hip_align_graphs, _graphs_wsets,
 // _graphs_any, align_family_batches, sina_hip_debug_mesh, _debug_mesh_wide) holds one for the call: it takes the
-// context's mutex and deactivates both in-place counts, so a call that ends early, or an entry that counts nothing (the
-// debug entries), has counted nothing and the staged getters give NULL.  begin() then activates what the entry may
+// context's mutex and deactivates both in-place counts and the shift log, so a call that ends early, or an entry that
+// counts nothing (the debug entries), has counted nothing and the staged getters give NULL.  begin() also opens the
+// shift log of a call with assemble = 2 (ShiftLog).  begin() then activates what the entry may
 // count and this call does count, for its nq queries: the pairs if their switch is on, the call assembles and the store
 // has a helix map; the identity by identity_plan.h's rule -- only the entries that bring families to the device may.
 enum { kMayCountPairs = 1, kMayCountIdentity = 2 };
@@ -740,16 +778,18 @@ struct align_call {
     std::lock_guard<std::mutex> lk;
     explicit align_call(sina_hip_ctx *c_) : c(c_), lk(c_->mu) {
         for (auto &ic : c->inplace) ic.active = false;
+        c->shift.active = false;
     }
     int begin(int may, const sina_hip_align_params *p, uint32_t nq) {
         const bool assemble = p && p->assemble;
         const bool counts[kNumInplace] = {
             (may & kMayCountPairs) && c->inplace[kInplacePairs].on && assemble && nq != 0 && c->st->n_pair_ent != 0,
             identity_call_counts(c->inplace[kInplaceIdentity].on, assemble, (may & kMayCountIdentity) != 0, nq)};
-        if (counts[kInplacePairs] || counts[kInplaceIdentity]) SH_CHECK(hipSetDevice(c->device));  // (pinned memory)
+        const bool shifts = p && p->assemble == SINA_ASSEMBLE_SHIFT && nq != 0;
+        if (counts[kInplacePairs] || counts[kInplaceIdentity] || shifts) SH_CHECK(hipSetDevice(c->device));  // (pinned memory)
         for (int i = 0; i < kNumInplace; i++)
             if (c->inplace[i].begin(counts[i], nq)) return 1;
-        return 0;
+        return c->shift.begin(shifts, nq);
     }
 };
 

@@ -75,6 +75,7 @@ int reserve_launch_buffers(sina_hip_ctx *c, const DpPlan &pl, const DpLaunch &l,
         return 1;
     for (InplaceCount &ic : c->inplace)
         if (ic.reserve(l.bq)) return 1;
+    if (c->shift.reserve(l.bq)) return 1;
     if (l.want_dbg_value && c->dbg.reserve(4 * sums.tb_cells)) return 1;
     return 0;
 }
@@ -145,6 +146,10 @@ int fill_args(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const sina
     b->lowercase = p->lowercase;
     b->self16 = l.profile_batch ? c->self16.as<float>() : nullptr;
     b->asm_cap = sums.max_l;
+    // (assemble = 2 outside an entry that opened the shift log -- the plane debug entries -- would have nowhere to
+    // write its events: refused, not run as assemble = 1)
+    if (p->assemble == SINA_ASSEMBLE_SHIFT && !c->shift.active) SH_FAIL("align: this entry takes no assemble = 2 (no shift log is staged)");
+    b->shift_log = p->assemble == SINA_ASSEMBLE_SHIFT ? c->shift.rows.as<uint32_t>() : nullptr;
     return 0;
 }
 
@@ -279,6 +284,7 @@ int fetch_results(sina_hip_ctx *c, const DpLaunch &l) {
     SH_CHECK(hipMemcpyAsync(staged_pos, c->out_pos.p, 4 * l.nqm, hipMemcpyDeviceToHost, s));
     for (InplaceCount &ic : c->inplace)
         if (ic.copy(l.q_base, l.bq, s)) return 1;
+    if (c->shift.copy(l.q_base, l.bq, s)) return 1;
     SH_CHECK(wait_stream(c, s));
     memcpy(l.out, c->h_out.p, sizeof(sina_hip_align_out) * l.bq);
     if (l.out_pos) memcpy(l.out_pos, staged_pos, 4 * l.nqm);
@@ -286,7 +292,7 @@ int fetch_results(sina_hip_ctx *c, const DpLaunch &l) {
 }
 
 // folds the launch into the store's statistics and its two guesses of optimum / bound
-int account_launch(sina_hip_ctx *c, const DpPlan &pl, const DpLaunch &l, uint64_t cells, uint64_t dp_no) {
+int account_launch(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_params *p, const DpLaunch &l, uint64_t cells, uint64_t dp_no) {
     float ms = 0;
     SH_CHECK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     // ... of which this launch shared the device with the DP launch before it (chained launches, ctx.h)
@@ -327,6 +333,16 @@ int account_launch(sina_hip_ctx *c, const DpPlan &pl, const DpLaunch &l, uint64_
                 c->use[kUseIdentityInplace].a++;
                 c->use[kUseIdentityInplace].b += l.fam_off ? l.fam_off[q + 1] - l.fam_off[q] : 0;
             }
+    if (p->assemble) {  // (sina_hip_assemble_stats)
+        c->asm_use.queries += l.bq;
+        for (uint32_t q = 0; q < l.bq; q++) {
+            if (!assembled(q)) continue;
+            c->asm_use.assembled++;
+            const uint32_t runs = c->shift.active ? c->shift.row(l.q_base + q)[0] : 0u;
+            c->asm_use.shifted_queries += runs != 0 ? 1u : 0u;
+            c->asm_use.shifted_runs += runs;
+        }
+    }
     st.dp_cells += cells;
     st.dp_launches++;
     st.dp_rows += sw.rows_nominal;
@@ -364,7 +380,7 @@ int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const 
         SH_CHECK(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(plane.ptr), (unsigned short)kTbNone, sums.tb_cells, c->stream));
     uint64_t dp_no = ~0ull;
     if (launch_dp_and_walk(c, pl, p, l, a, b, &dp_no) || fetch_results(c, l)) return 1;
-    return account_launch(c, pl, l, sums.cells, dp_no);
+    return account_launch(c, pl, p, l, sums.cells, dp_no);
 }
 
 int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {

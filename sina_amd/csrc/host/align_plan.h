@@ -18,7 +18,13 @@ namespace sina __attribute__((visibility("hidden"))) {
 struct align_switches {
     bool fs_no_graph = false, device_graph = true, device_profile = false, wide_fallback = false, weight_sets = true;
     bool device_bps = false, device_idty = false, calc_idty = false;
+    bool device_shift = false;  // the align call runs with assemble = SINA_ASSEMBLE_SHIFT: see align_assemble_mode
 };
+
+// What sina_hip_align_params::assemble is for a group's call: the device finishes the insertions that shift their
+// neighbours too where the option asks for it.  Every route takes the value (the wide path assembles nothing either way);
+// plan_counting's `assembles` input is this != 0, so device-bps and device-idty score shifted trays from the same call.
+inline int align_assemble_mode(const align_switches &s) { return s.device_shift ? SINA_ASSEMBLE_SHIFT : 1; }
 
 // what the plan reads of one DP job
 struct align_job_facts {

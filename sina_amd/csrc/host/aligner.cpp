@@ -48,6 +48,9 @@ static aligner::options al_defaults() {  // src/align.cpp:231-274
     // calc-idty from the align call itself (sina_hip_align_count_identity) instead of a second trip with the finished
     // alignments (set_family_identity): on request, until it has been decided on measurements
     o.device_idty = false;
+    // the device also finishes alignments whose insertions shift their neighbours (assemble = 2): on request, until it
+    // has been decided on measurements
+    o.device_shift = false;
     return o;
 }
 static aligner::options &al_opts() {
@@ -91,6 +94,7 @@ void aligner::set_option(const std::string &name, const std::string &value) {
     else if (name == "weight-sets") o.weight_sets = to_bool(value);
     else if (name == "device-bps") o.device_bps = to_bool(value);
     else if (name == "device-idty") o.device_idty = to_bool(value);
+    else if (name == "device-shift") o.device_shift = to_bool(value);
     else if (name == "db") o.database = value;
     else throw std::logic_error("aligner: unknown option " + name);
 }
@@ -303,7 +307,7 @@ static bool prepare_tray(tray &t, const aligner::options &o, reference_store *pr
 
 // Takes the options and a group's positional weights (none: simple scheme; they outlive the result; a group of several
 // filters: their vectors of n_weights floats one after the other); gives the device call's parameters.
-static sina_hip_align_params make_align_params(const aligner::options &o, const float *weights, size_t n_weights) {
+static sina_hip_align_params make_align_params(const aligner::options &o, const align_switches &sw, const float *weights, size_t n_weights) {
     sina_hip_align_params p;
     sina_hip_align_params_default(&p);
     p.match_score = o.match_score;
@@ -316,7 +320,7 @@ static sina_hip_align_params make_align_params(const aligner::options &o, const 
     p.insertion = (int)o.insertion;
     p.weights = n_weights == 0 ? nullptr : weights;
     p.n_weights = (uint32_t)n_weights;
-    p.assemble = 1;  // (the device finishes what it can: sina_hip_align_out::assembled)
+    p.assemble = align_assemble_mode(sw);  // (the device finishes what it can: sina_hip_align_out::assembled)
     return p;
 }
 
@@ -553,8 +557,10 @@ static uint64_t assemble_on_host(tray &t, cseq &c, const sina_hip_align_out &r, 
 // (backtrack()'s container steps, src/mesh.h:603-736, + do_align's attributes, src/align.cpp:507-509).  Throws on a failed query.
 // pair_row (device-bps; else null): the six helix base-pair counters the align call counted for the slot -- the tray's
 // score if the device assembled the alignment (only then the counters are of the finished words); gives whether it was taken.
+// shift_row (device-shift; else null): the slot's row of the call's shift log -- its events become the log's
+// "shifting bases to fit in ...;" texts, in order, in front of the totals, where the host's fix-up writes them.
 static bool finish_tray(dp_job &jb, const sina_hip_align_out &r, const uint32_t *pos, uint32_t width, const aligner::options &o,
-                        bool defer_score_line, const uint32_t *pair_row = nullptr) {
+                        bool defer_score_line, const uint32_t *pair_row = nullptr, const uint32_t *shift_row = nullptr) {
     tray &t = *jb.t;
     if (r.status != 0) throw std::runtime_error("device alignment failed for " + t.input_sequence->getName());
     uint64_t tk = host_tsc();
@@ -580,8 +586,9 @@ static bool finish_tray(dp_job &jb, const sina_hip_align_out &r, const uint32_t 
     c.copy_meta_with(*t.input_sequence, extra, 5);
     tk = host_tick("finish: working copy + attributes", tk);
     if (r.assembled) {
-        // the device did the container steps (append rule, setWidth, reverse) and a NAST fix-up
-        // in which every insertion fitted its gap: the finished bases, and the fix-up's log line
+        // the device did the container steps (append rule, setWidth, reverse) and the NAST fix-up -- one in which
+        // every insertion fitted its gap, or (device-shift) its shifted runs too: the finished bases, and the
+        // fix-up's log texts
         c.clearSequence();
         base_vector &fin = c.mutableAlignedBases();  // (a recycled sequence: no allocation)
         // (one pass, past the cache: base lists are not zeroed by resize() -- cseq.h, base_block_allocator -- and
@@ -591,6 +598,10 @@ static bool finish_tray(dp_job &jb, const sina_hip_align_out &r, const uint32_t 
         c.setWidth(width);
         tk = host_tick("finish: assemble", tk);
         if (o.insertion == INSERTION_REMOVE) t.log << "insertion=remove not implemented, using shift; ";
+        if (shift_row != nullptr)
+            for (uint32_t e = 0; e < shift_row[0]; e++)
+                t.log << "shifting bases to fit in " << shift_row[1 + 3 * e] << " bases at pos " << shift_row[2 + 3 * e] << " to "
+                      << shift_row[3 + 3 * e] << ";";
         if (r.nast_total > 0)
             t.log << "total inserted bases=" << r.nast_total << ";"
                   << "longest insertion=" << r.nast_longest << ";"
@@ -655,6 +666,7 @@ static align_switches plan_switches(const aligner::options &o) {
     s.device_bps = o.device_bps;
     s.device_idty = o.device_idty;
     s.calc_idty = o.calc_idty;
+    s.device_shift = o.device_shift;
     return s;
 }
 
@@ -736,15 +748,20 @@ static void align_long_slots(sina_hip_ctx *ctx, const group_call &g, const sina_
             refused = e.what();
         }
         const uint32_t *const pos = sina_hip_staged_out_pos(ctx);
+        // (a slot the call routed to the fast path may come back assembled, shifted runs included: its row is the call's first)
+        const uint32_t *const shift_row = refused.empty() && p.assemble == SINA_ASSEMBLE_SHIFT ? sina_hip_staged_shift_log(ctx) : nullptr;
+        uint64_t fin[2] = {0, 0};  // trays the host finished, trays the device had assembled
         for (size_t x = 0; x < members.size(); x++) {
             if (slots.slot_of[x] != u) continue;
             if (!refused.empty()) {
                 members[x]->t->log << "unable to align: " << refused << ";";
                 continue;
             }
-            finish_tray(*members[x], out[u], pos, width, g.o, g.defer_score_line);
+            finish_tray(*members[x], out[u], pos, width, g.o, g.defer_score_line, nullptr, shift_row);
+            fin[out[u].assembled ? 1 : 0]++;
             aligned.push_back(members[x]);
         }
+        g.store.count_finished(fin[1], fin[0]);
     }
     if (g.o.calc_idty && !aligned.empty()) set_family_identity(aligned, g.store);
 }
@@ -752,19 +769,24 @@ static void align_long_slots(sina_hip_ctx *ctx, const group_call &g, const sina_
 // Finishes the group's trays from out[slot] and the aligned columns where the device copied them, in the context's
 // pinned staging buffer (sina_hip_staged_out_pos -- the context stays leased until the group's last tray is finished).
 static void finish_group(sina_hip_ctx *ctx, const group_call &g, const std::vector<dp_job *> &members, const device_slots &slots,
-                         const sina_hip_align_out *out, uint32_t width, bool counted_pairs) {
+                         const sina_hip_align_out *out, uint32_t width, bool counted_pairs, bool shifted) {
     const uint32_t *const staged_pos = sina_hip_staged_out_pos(ctx);
+    // (null unless the call ran with assemble = 2; a slot's row: its shifted runs)
+    const uint32_t *const staged_shift = shifted ? sina_hip_staged_shift_log(ctx) : nullptr;
+    constexpr size_t shift_row_words = 1 + 3 * (size_t)SINA_HIP_SHIFT_LOG;
     // (null unless this call counted; the trays of a slot share its row)
     const uint32_t *const staged_pairs = counted_pairs ? sina_hip_staged_pair_counts(ctx) : nullptr;
     scoped_phase ph("al.finish(NAST,log)");
-    std::atomic<uint64_t> scored{0};
+    std::atomic<uint64_t> scored{0}, by_device{0};
     parallel_for(members.size(), [&](size_t x) {
         const uint32_t u = slots.slot_of[x];
         if (finish_tray(*members[x], out[u], staged_pos + slots.dqoff[u], width, g.o, g.defer_score_line,
-                        staged_pairs ? staged_pairs + 6 * (size_t)u : nullptr))
+                        staged_pairs ? staged_pairs + 6 * (size_t)u : nullptr, staged_shift ? staged_shift + shift_row_words * u : nullptr))
             scored.fetch_add(1, std::memory_order_relaxed);
+        if (out[u].assembled) by_device.fetch_add(1, std::memory_order_relaxed);
     });
     if (staged_pairs) g.store.count_pairs_inplace(scored.load());
+    g.store.count_finished(by_device.load(), members.size() - by_device.load());
 }
 
 // --calc-idty for a finished group: from the rows the align call staged where it counted (device-idty), and by
@@ -799,7 +821,7 @@ static void align_group_members(const group_call &g, const align_group_key &key,
     device_slots slots = distinct_slots(members);
     std::vector<float> several;
     const float *weights = gather_weights(g.o, key, slots, several);
-    const sina_hip_align_params p = make_align_params(g.o, weights, key.weight_width);
+    const sina_hip_align_params p = make_align_params(g.o, g.sw, weights, key.weight_width);
     std::vector<sina_hip_align_out> out(slots.dnq);
     auto dev = g.store.worker_device(reference_store::dev_align);
     const align_counting counting = set_counting(dev.get(), g, key.route, p);
@@ -807,7 +829,7 @@ static void align_group_members(const group_call &g, const align_group_key &key,
     // out[u] = slot u's result, its aligned columns at sina_hip_staged_out_pos + dqoff[u] while the context stays leased
     const uint32_t width = key.route == route_device ? align_family_ids(dev.get(), g.store, g.o, p, slots, out.data())
                                                      : align_host_graphs(dev.get(), g.o, p, slots, out.data());
-    finish_group(dev.get(), g, members, slots, out.data(), width, counting.count_pairs);
+    finish_group(dev.get(), g, members, slots, out.data(), width, counting.count_pairs, p.assemble == SINA_ASSEMBLE_SHIFT);
     if (g.o.calc_idty) set_group_identity(dev.get(), g, members, slots, out.data(), counting.count_idty);
 }
 }  // namespace

@@ -393,6 +393,16 @@ int sina_host_store_identity_inplace_stats(const char *key, uint64_t *trays, dou
         reference_store::get(key)->identity_inplace_stats(trays, kernel_ms, sequences, pairs, launches);
     });
 }
+// the aligner's finish step on this store: trays the device had assembled / the host finished, and the device
+// assembly's volume (sina_hip_assemble_stats) on its contexts -- between runs
+int sina_host_store_assemble_stats(const char *key, uint64_t *trays_device, uint64_t *trays_host, uint64_t *queries, uint64_t *assembled,
+                                   uint64_t *shifted_queries, uint64_t *shifted_runs) {
+    return guarded([&] {
+        if (!trays_device || !trays_host || !queries || !assembled || !shifted_queries || !shifted_runs)
+            throw std::logic_error("store_assemble_stats: null argument");
+        reference_store::get(key)->assemble_stats(trays_device, trays_host, queries, assembled, shifted_queries, shifted_runs);
+    });
+}
 // The host walk (cseq_base::calcPairScore), no device involved, of an aligned string.  counts6 (optional): num, AG,
 // AU, CG, GG, GU.
 int sina_host_pair_score(const char *aligned_text, const uint32_t *pairs, uint32_t n, float *score, uint32_t *counts6) {

@@ -349,6 +349,15 @@ public:
     // the aligner's device-idty, likewise: trays that took their identity from the row their align call brought back,
     // and the in-place kernel's time and volume on the store's contexts -- sina_hip_identity_inplace_stats
     void count_identity_inplace(uint64_t trays) { n_idty_inplace.fetch_add(trays, std::memory_order_relaxed); }
+    // the aligner's finish step: trays whose alignment the device had assembled / the host finished with the container's
+    // own code since the store was opened, and the device assembly's volume on the store's contexts --
+    // sina_hip_assemble_stats
+    void count_finished(uint64_t by_device, uint64_t by_host) {
+        n_fin_device.fetch_add(by_device, std::memory_order_relaxed);
+        n_fin_host.fetch_add(by_host, std::memory_order_relaxed);
+    }
+    void assemble_stats(uint64_t *trays_device, uint64_t *trays_host, uint64_t *queries, uint64_t *assembled, uint64_t *shifted_queries,
+                        uint64_t *shifted_runs);
     void identity_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches);
 
 private:
@@ -382,6 +391,7 @@ private:
     std::atomic<int> name_order_state{0};  // 0: not looked at, 1: uploaded, 2: names repeat
     std::atomic<uint64_t> n_ranked{0}, n_rank_host{0};
     std::atomic<uint64_t> n_bp_inplace{0}, n_idty_inplace{0};
+    std::atomic<uint64_t> n_fin_device{0}, n_fin_host{0};
     pair_map helix;
     std::mutex helix_mu;
 };
@@ -483,6 +493,8 @@ public:
                             // their trays leave the aligner scored (sina_hip_align_count_pairs; default off)
         bool device_idty;   // calc-idty: the align call of a device-built group scores the queries it assembles against their
                             // families and their trays take that identity (sina_hip_align_count_identity; default off)
+        bool device_shift;  // the device also finishes alignments whose insertions shift their neighbours (assemble = 2,
+                            // sina_hip.h SINA_ASSEMBLE_SHIFT; default off); the host keeps the cap cases
         std::string database;  // reference store the DAGs are built from (same as famfinder "db")
     };
     static options *opts;

@@ -353,6 +353,20 @@ void reference_store::identity_inplace_stats(uint64_t *trays, double *kernel_ms,
     sum_kernel_use("sina_hip_identity_inplace_stats", sina_hip_identity_inplace_stats, kernel_ms, sequences, pairs, launches);
     *trays = n_idty_inplace.load(std::memory_order_relaxed);
 }
+void reference_store::assemble_stats(uint64_t *trays_device, uint64_t *trays_host, uint64_t *queries, uint64_t *assembled,
+                                     uint64_t *shifted_queries, uint64_t *shifted_runs) {
+    *queries = *assembled = *shifted_queries = *shifted_runs = 0;
+    for_each_context([&](sina_hip_ctx *c) {
+        uint64_t q = 0, a = 0, sq = 0, sr = 0;
+        hip_check(sina_hip_assemble_stats(c, &q, &a, &sq, &sr), "sina_hip_assemble_stats");
+        *queries += q;
+        *assembled += a;
+        *shifted_queries += sq;
+        *shifted_runs += sr;
+    });
+    *trays_device = n_fin_device.load(std::memory_order_relaxed);
+    *trays_host = n_fin_host.load(std::memory_order_relaxed);
+}
 bool reference_store::match_counts_too_wide() {
     if (sina_hip::match_table_bytes(width) <= sina_hip::kMatchMaxLds) return false;
     if (!too_wide_said.exchange(true))

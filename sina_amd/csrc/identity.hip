@@ -62,7 +62,8 @@ __global__ void __launch_bounds__(kCT) family_identity_kernel(IdentityArgs a) {
     uint32_t *row = a.rows + (size_t)q * 2;
     const uint32_t la = o->n_out;
     // (the same for every thread of the workgroup; la > max_l cannot happen for an assembled query -- assemble_kernel
-    // leaves a longer one alone -- and would overrun the mask bytes)
+    // leaves a longer one alone -- and would overrun the mask bytes.  An assembled query's columns ascend strictly and
+    // lie below the width, shifted insertions included: assemble_kernel<true> places them into free columns only)
     if (o->status != 0 || o->assembled == 0 || la > a.max_l) {
         if (tid < 2) row[tid] = 0;
         return;

@@ -50,8 +50,10 @@ __global__ void __launch_bounds__(kPT) pair_count_kernel(PairArgs a) {
 // left in BtArgs::out_pos -- no packing, no staging, no upload.  One wave per query of the DP launch range; a query
 // the device did not finish (assembled == 0) or that failed (status != 0) gets six zeros, so every row is defined.
 // There is no check of the columns here, as pair_first_descending is one for words a caller hands in: assembled == 1
-// says that every insertion fitted its gap and every column is below the width (assemble_kernel), so the n_out words
-// are the query's bases in strictly ascending columns -- what mask_at's search needs.
+// says that every insertion has been placed -- in its gap, or with assemble = 2 in the range its widening reached -- and
+// every column is below the width (assemble_kernel, both instantiations: a widening that would place a base at the
+// width leaves the query to the host), so the n_out words are the query's bases in strictly ascending columns -- what
+// mask_at's search needs.
 struct PairAsmArgs {
     const QDesc *qd;
     const sina_hip_align_out *out;

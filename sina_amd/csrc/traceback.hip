@@ -305,14 +305,142 @@ __global__ void __launch_bounds__(64) backtrack_lanes_kernel(BtArgs a) {
 //   * setWidth(width) + reverse() (:283-289): written back to front, column c -> width - 1 - c;
 //   * fix_duplicate_positions (src/cseq.cpp:456-594): bases sharing a column are an
 //     insertion; where the free columns up to the next base suffice they are placed right-aligned
-//     there (and lower-cased with --lowercase=unaligned) -- the only case handled here.  An insertion
+//     there (and lower-cased with --lowercase=unaligned).
+// SHIFT = false (sina_hip_align_params::assemble == 1) handles that case only.  An insertion
 //     that does not fit and makes its neighbours move, a column at or beyond the alignment's width,
 //     or more than kAsmMax bases leave out_pos as backtrack_kernel wrote it (assembled = 0): the host
 //     finishes those with the container's own code.
+// SHIFT = true (assemble == 2, SINA_ASSEMBLE_SHIFT) also places the insertions that do not fit: the
+//     reference's widening loop (src/cseq.cpp:503-570; assemble_shift below).  Left to the host there:
+//     more than kShiftLog shifted runs, no free column on either side (the reference throws), a
+//     column at or beyond the width -- in the input or reached by a widening --, more than kAsmMax bases.
 // out_pos is rewritten in place: columns in, packed aligned bases (column | mask << 24) out.
 // LDS: 4 bytes per base of the launch's longest query + 1 KB (16S: 7 KB -- what a resident DP kernel
-// leaves free on a CU, so the wave runs beside it like backtrack_kernel does).
+// leaves free on a CU, so the wave runs beside it like backtrack_kernel does).  The same for both: SHIFT
+// needs no bitmap of the duplicates and keeps its event row (97 words, 388 bytes) in that bitmap's 512.
 constexpr int kAsmMax = 4096;
+constexpr uint32_t kShiftLog = SINA_HIP_SHIFT_LOG, kShiftRow = 1 + 3 * kShiftLog;  // events, words of a query's log row
+
+__device__ __forceinline__ uint32_t first_lane_of(unsigned long long m) { return (uint32_t)__ffsll((long long)m) - 1u; }
+
+// The fix-up with widening, over col[0 .. n): the bases' columns in SEQUENCE order, after the append rule and the
+// mirror.  The runs are taken left to right as the reference takes them (so_cseq_fix_duplicate_positions,
+// oracle/sina_oracle.c, is the same loop with indices): a widening reads the columns earlier runs have left on its
+// left and the raw ones, later insertions included, on its right.  Every variable is the wave's (the same in all
+// lanes); the lanes share the searches -- 64 positions per ballot -- and the placing.  moved: one bit per base the
+// fix-up placed; ev: the event row (word 0 is written by the caller); facts: total, longest, last run.
+// Returns the number of events, or 0xFFFFFFFF: the host finishes the query.
+__device__ __forceinline__ uint32_t assemble_shift(uint32_t *col, unsigned long long *moved, uint32_t *ev, uint32_t n,
+                                                   uint32_t width, uint32_t lane, uint32_t *facts) {
+    auto uni = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+    // the base from which everything up to `from` sits column to column: the largest l <= from with l == 0 or a
+    // free column between l - 1 and l
+    auto gap_left_of = [&](uint32_t from) -> uint32_t {
+        for (uint32_t l = from;; l -= 64) {  // (position 0 stops: l never passes it)
+            const int p = (int)l - (int)lane;
+            const bool stop = p >= 0 && (p == 0 || col[p - 1] + 1 < col[p]);
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(stop);
+            if (m != 0ull) return l - first_lane_of(m);
+        }
+    };
+    // ... and to the right: the smallest r >= from with r == n - 1 or a free column between r and r + 1
+    auto gap_right_of = [&](uint32_t from) -> uint32_t {
+        for (uint32_t r = from;; r += 64) {  // (position n - 1 stops)
+            const uint32_t p = r + lane;
+            const bool stop = p < n && (p + 1 == n || col[p] + 1 < col[p + 1]);
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(stop);
+            if (m != 0ull) return r + first_lane_of(m);
+        }
+    };
+    uint32_t total = 0, longest = 0, last_run = 0, nev = 0;
+    for (uint32_t anchor = 0;;) {
+        // the next insertion: the first j >= anchor that shares its column with j + 1
+        uint32_t j = n;
+        for (uint32_t b = anchor; b + 1 < n; b += 64) {
+            const uint32_t p = b + lane;
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(p + 1 < n && col[p] == col[p + 1]);
+            if (m != 0ull) {
+                j = b + first_lane_of(m);
+                break;
+            }
+        }
+        if (j >= n) break;
+        const uint32_t c0 = uni(col[j]);
+        uint32_t k = n;  // the first base behind the run, or the sequence's end
+        for (uint32_t b = j + 2; b < n; b += 64) {
+            const uint32_t p = b + lane;
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(p < n && col[p] != c0);
+            if (m != 0ull) {
+                k = b + first_lane_of(m);
+                break;
+            }
+        }
+        // bases first .. last go into the free columns [range_begin, range_end)
+        uint32_t first = j + 1, last = k - 1, num = k - j - 1;
+        uint32_t range_begin = c0 + 1, range_end = k == n ? width : uni(col[k]);
+        last_run = num;
+        if (range_end - range_begin < num) {
+            if (nev == kShiftLog) return 0xFFFFFFFFu;
+            if (lane == 0) {
+                ev[1 + 3 * nev] = num;
+                ev[2 + 3 * nev] = range_begin;
+                ev[3 + 3 * nev] = range_end;
+            }
+            nev++;
+            while (range_end - range_begin < num) {  // (each turn gains one free column or gives up)
+                int next_left_gap, next_right_gap;
+                uint32_t left = first, right = last;
+                if (left == 0) {
+                    next_left_gap = range_begin > 0 ? (int)(range_begin - 1) : -1;
+                } else if (uni(col[left - 1]) + 1 < range_begin) {
+                    next_left_gap = (int)(range_begin - 1);
+                } else {
+                    left = gap_left_of(left - 1);
+                    next_left_gap = (int)(uni(col[left]) - 1u);
+                }
+                if (right + 1 == n) {
+                    next_right_gap = range_end < width ? (int)range_end : -1;
+                } else if (uni(col[right + 1]) > range_end) {
+                    next_right_gap = (int)range_end;
+                } else {
+                    right = gap_right_of(right + 1);
+                    next_right_gap = (int)(uni(col[right]) + 1);
+                }
+                if (next_right_gap == -1 ||
+                    (next_left_gap != -1 && range_begin - (uint32_t)next_left_gap <= (uint32_t)next_right_gap - (range_end - 1))) {
+                    if (next_left_gap == -1) return 0xFFFFFFFFu;  // (no space to left and right: the reference throws)
+                    num += first - left;
+                    range_begin = (uint32_t)next_left_gap;
+                    first = left;
+                } else {
+                    num += right - last;
+                    range_end = (uint32_t)next_right_gap + 1;
+                    last = right;
+                }
+            }
+            // (a right scan that ends on a last base in column width - 1 takes `width` for a free column, as the
+            // reference does: a column the alignment does not have)
+            if (range_begin + num > width) return 0xFFFFFFFFu;
+        } else {
+            range_begin = range_end - num;  // enough room: right-aligned in the free range
+        }
+        for (uint32_t t = lane; t < num; t += 64) col[first + t] = range_begin + t;
+        for (uint32_t w = (first >> 6) + lane; w <= (last >> 6); w += 64) {
+            const uint32_t lo = w == (first >> 6) ? (first & 63u) : 0u, hi = w == (last >> 6) ? (last & 63u) : 63u;
+            moved[w] |= (~0ull << lo) & (~0ull >> (63u - hi));
+        }
+        __syncthreads();  // (one wave: the next run's searches read what this one placed)
+        total += num;
+        longest = max(longest, num);
+        anchor = last + 1;
+    }
+    facts[0] = total;
+    facts[1] = longest;
+    facts[2] = last_run;
+    return nev;
+}
+
+template <bool SHIFT>
 __global__ void __launch_bounds__(64) assemble_kernel(BtArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char asm_lds[];
     unsigned long long *dupm = reinterpret_cast<unsigned long long *>(asm_lds);  // [kAsmMax / 64]
@@ -324,12 +452,67 @@ __global__ void __launch_bounds__(64) assemble_kernel(BtArgs a) {
     const QDesc d = a.qd[q];
     const sina_hip_align_out o = a.out[q];
     const uint32_t n = o.n_out, width = a.width;
+    if constexpr (SHIFT) {  // (every query's log row is defined: no events unless the fix-up below says otherwise)
+        for (uint32_t t = lane; t < kShiftRow; t += 64) a.shift_log[(size_t)q * kShiftRow + t] = 0u;
+    }
     if (o.status != 0 || n == 0 || n > a.asm_cap) return;
     uint32_t *pos = a.out_pos + d.q_off;
     const uint8_t *qm = a.qmask + d.q_off;
     const bool keep_over = a.overhang != SINA_OVERHANG_REMOVE;
     const uint32_t tail = keep_over ? (uint32_t)o.cutoff_tail : 0u;
     const uint32_t n_aligned = (uint32_t)o.aligned_bases;
+    if constexpr (SHIFT) {
+        // ---- append rule as below, stored mirrored and in sequence order: col[n-1-i] = width - 1 - (column of emission i)
+        uint32_t *col = colm, *ev = reinterpret_cast<uint32_t *>(dupm);
+        uint32_t carry = 0;
+        bool beyond = false;
+        for (uint32_t base = 0; base < n; base += 64) {
+            const uint32_t i = base + lane;
+            uint32_t v = i < n ? pos[i] : 0u;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t y = __shfl_up(v, off);
+                if ((int)lane >= off) v = max(v, y);
+            }
+            v = max(v, carry);
+            if (lane == 0) movedm[base >> 6] = 0ull;
+            if (i < n) {
+                col[n - 1 - i] = width - 1 - v;
+                beyond = beyond || v >= width;
+            }
+            carry = __shfl(v, 63);
+        }
+        if (__builtin_amdgcn_ballot_w64(beyond) != 0ull) return;
+        __syncthreads();
+        // ---- the fix-up, widening included
+        uint32_t nast[3];  // total, longest, last run
+        const uint32_t nev = assemble_shift(col, movedm, ev, n, width, lane, nast);
+        if (nev == 0xFFFFFFFFu) return;
+        __syncthreads();
+        // ---- bases: sequence position j is emission n-1-j
+        const uint32_t keep_case = a.lowercase == SINA_LOWERCASE_ORIGINAL ? 0xFFu : 0xEFu;
+        const uint32_t lower = a.lowercase == SINA_LOWERCASE_UNALIGNED ? 0x10u : 0u;
+        const uint32_t first_q = (uint32_t)o.end_s + tail;  // query index of emission 0
+        for (uint32_t base = 0; base < n; base += 64) {
+            const uint32_t j = base + lane;
+            if (j >= n) break;
+            const uint32_t i = n - 1 - j;
+            const bool overhang_base = i < tail || i >= tail + n_aligned;
+            const bool moved = (movedm[j >> 6] >> (j & 63)) & 1ull;
+            const uint32_t bits = ((uint32_t)qm[first_q - i] & keep_case) | ((overhang_base || moved) ? lower : 0u);
+            pos[j] = (col[j] & 0xFFFFFFu) | (bits << 24);
+        }
+        uint32_t *row = a.shift_log + (size_t)q * kShiftRow;
+        for (uint32_t t = lane; t < 1 + 3 * nev; t += 64) row[t] = t == 0 ? nev : ev[t];
+        if (lane == 0) {
+            sina_hip_align_out *out = a.out + q;
+            out->assembled = 1;
+            out->nast_total = nast[0];
+            out->nast_longest = nast[1];
+            out->nast_last_run = nast[2];
+        }
+        return;
+    }
     // ---- append rule: prefix maximum of the emitted columns; equal neighbours are insertions
     uint32_t carry = 0;
     bool beyond = false;
@@ -425,7 +608,10 @@ int launch_assemble(const BtArgs &a0, hipStream_t s) {
     BtArgs a = a0;
     a.asm_cap = std::min<uint32_t>((a.asm_cap + 63u) & ~63u, (uint32_t)kAsmMax);  // (longer queries: the host finishes them)
     const size_t lds = 2 * (size_t)(kAsmMax / 64) * 8 + 4 * (size_t)a.asm_cap;
-    hipLaunchKernelGGL(assemble_kernel, dim3(a.nq), dim3(64), lds, s, a);
+    static_assert(kShiftRow * 4 <= (kAsmMax / 64) * 8, "the event row lives in the duplicates' bitmap");
+    // (shift_log: the launch's [nq][kShiftRow] log rows -- assemble = 2 --, or nullptr)
+    if (a.shift_log != nullptr) hipLaunchKernelGGL(assemble_kernel<true>, dim3(a.nq), dim3(64), lds, s, a);
+    else hipLaunchKernelGGL(assemble_kernel<false>, dim3(a.nq), dim3(64), lds, s, a);
     SH_CHECK(hipGetLastError());
     return 0;
 }

@@ -99,6 +99,7 @@ def load_host():
     H.sina_host_store_pair_stats.argtypes = [C.c_char_p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_store_pair_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p]
     H.sina_host_store_identity_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_store_assemble_stats.argtypes = [C.c_char_p] + [capi.u64p] * 6
     H.sina_host_pair_score.argtypes =[C.c_char_p, capi.u32p, C.c_uint32, capi.f32p, capi.u32p]
     H.sina_host_pair_scores_packed.argtypes = [capi.u32p, capi.u64p, C.c_uint32, capi.u32p, C.c_uint32, capi.f32p, capi.u32p,
                                                C.POINTER(C.c_double)]
@@ -294,6 +295,14 @@ class Store:
                            capi.u64_fields("sequences", "pairs", "launches"))
         d["kernel_ms"] = d.pop("kernel_ms")  # (the dict ends with it)
         return d
+
+    def assemble_stats(self):
+        """The aligner's finish step on this store so far: dict(trays_device, trays_host, queries, assembled,
+        shifted_queries, shifted_runs) -- trays whose alignment the device had assembled and trays the host finished
+        with the container's own code, and the device assembly's volume on the store's contexts (with the aligner's
+        device-shift the shifted ones among them) -- between runs, like pair_inplace_stats()."""
+        return self._counters(self.H.sina_host_store_assemble_stats,
+                              capi.u64_fields("trays_device", "trays_host", "queries", "assembled", "shifted_queries", "shifted_runs"))
 
     def close(self):
         self.H.sina_host_store_close(self.key.encode())

@@ -134,6 +134,18 @@ int sina_hip_identity_inplace_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, 
     *seqs = *pairs = *launches = 0;
     return 0;
 }
+// (the stub assembles nothing: no shift log, nothing counted)
+const uint32_t *sina_hip_staged_shift_log(sina_hip_ctx *) { return nullptr; }
+int sina_hip_assemble_stats(sina_hip_ctx *, uint64_t *queries, uint64_t *assembled, uint64_t *shifted_queries, uint64_t *shifted_runs) {
+    *queries = *assembled = *shifted_queries = *shifted_runs = 0;
+    return 0;
+}
+int sina_hip_debug_assemble(sina_hip_ctx *, const sina_hip_align_params *, uint32_t, const uint8_t *, const uint64_t *, uint32_t,
+                            sina_hip_align_out *, uint32_t *) { g_err = "stub"; return 1; }
+int sina_hip_debug_assemble_ms(sina_hip_ctx *, double *ms) {
+    *ms = 0;
+    return 0;
+}
 void sina_hip_align_params_default(sina_hip_align_params *p) {
     memset(p, 0, sizeof(*p));
     p->match_score = 2;
