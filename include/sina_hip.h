@@ -339,6 +339,40 @@ const uint32_t *sina_hip_staged_identity(sina_hip_ctx *ctx);
 int sina_hip_identity_inplace_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *sequences, uint64_t *pairs,
                                     uint64_t *launches);
 
+/* The search stage's ranking (search_filter: k-mer candidates, cseq_comparator::score, the max_result best) where the
+ * device assembles the alignment.  Replaces, for the queries an align call assembles, the second trip of
+ * sina_hip_kmer_topk_rank -- finished words packed and uploaded again, one k-mer search and one ranking per launch
+ * range of that call --: the call's queries are searched once, before its first DP launch range, the id rows stay on
+ * the device, and a kernel queued right behind the assembly ranks each query's candidates against the words the
+ * assembly has just left.  One row per query comes back with the results.
+ *
+ * sina_hip_align_rank: the switch, per context, off after init and after fork, and the rules the ranking runs with --
+ * the index it expects (k, nofast), kmer_candidates (the search's max; more than 4096 after clamping to the
+ * references is refused, as sina_hip_kmer_topk_rank refuses it) and sina_hip_compare_rank's iupac_rule,
+ * filter_lowercase, cover_rule and max_result (1..64).  on = 0 ignores the rest.  With it on, a call of
+ * sina_hip_align_graphs, _graphs_wsets, _graphs_any, _families, _families_wsets or _profiles on this context ranks if
+ * it runs with p->assemble, the store has references, a name order (sina_hip_upload_name_order) and an index of
+ * that k / nofast, every query has at most SINA_HIP_MAX_QUERY_LEN bases and the comparison's tables fit the LDS;
+ * otherwise the call runs exactly as without the switch.  A missing precondition never fails the align call.
+ *
+ * sina_hip_staged_rank: [nq][130] of the context's last align call, laid out like that call's `out`.  Host memory
+ * owned by the context, valid until its next align call.  NULL if that call did not rank.  Row q: word 0 the number
+ * of rows n, word 1 the flags (bit 0: a candidate had a denominator of 0, the host's NaN -- rank that query on the
+ * host; bit 1: ranked), words 2..65 the ids, words 66..129 the scores' bit patterns, best first, zero from n on --
+ * equal to what sina_hip_kmer_topk_rank gives for the same words.  A query is ranked if out[q].status == 0,
+ * out[q].assembled == 1 and out[q].n_out equals its length: the candidates are searched with the input's k-mers,
+ * the reference searches with the aligned sequence's, and the two differ once a base was dropped.  Every other row
+ * is all zero (bit 1 clear tells "not ranked" from "ranked, no rows").
+ *
+ * sina_hip_rank_inplace_stats: this kernel's own time (events around its launches) and volume on this context since
+ * init / fork: queries ranked, their (query, candidate) pairs, launch ranges.  sina_hip_rank_stats counts the
+ * re-upload route only. */
+int sina_hip_align_rank(sina_hip_ctx *ctx, int on, unsigned k, int nofast, uint32_t kmer_candidates, int iupac_rule,
+                        int filter_lowercase, int cover_rule, uint32_t max_result);
+const uint32_t *sina_hip_staged_rank(sina_hip_ctx *ctx);
+int sina_hip_rank_inplace_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *sequences, uint64_t *pairs,
+                                uint64_t *launches);
+
 /* ------------------------------------------------------------- alignment
  * Replaces, for a batch of queries: mseq::mseq + sort + reduce_edges
  * (src/mseq.cpp:47-118, src/graph.h:451-488) when given family ids, compute()

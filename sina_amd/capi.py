@@ -38,12 +38,16 @@ ABI_SYMBOLS = [
     "sina_hip_upload_pairs", "sina_hip_pair_counts", "sina_hip_pair_stats",
     "sina_hip_align_count_pairs", "sina_hip_staged_pair_counts", "sina_hip_pair_inplace_stats",
     "sina_hip_align_count_identity", "sina_hip_staged_identity", "sina_hip_identity_inplace_stats",
+    "sina_hip_align_rank", "sina_hip_staged_rank", "sina_hip_rank_inplace_stats",
     "sina_hip_staged_shift_log", "sina_hip_assemble_stats", "sina_hip_debug_assemble", "sina_hip_debug_assemble_ms",
 ]
 
 # include/sina_hip.h: SINA_ASSEMBLE_SHIFT, SINA_HIP_SHIFT_LOG
 ASSEMBLE_SHIFT = 2
 SHIFT_LOG = 32
+
+# include/sina_hip.h, sina_hip_staged_rank: words of a query's row
+RANK_ROW_WORDS = 130
 
 # include/sina_hip.h: SINA_CMP_COVER_*, in CMP_COVER_TYPE's order
 COVER_RULES = ("abs", "query", "target", "overlap", "all", "average", "min", "max", "nogap")
@@ -176,6 +180,10 @@ def load():
     L.sina_hip_staged_identity.restype = C.POINTER(C.c_uint32)
     L.sina_hip_staged_identity.argtypes = [vp]
     L.sina_hip_identity_inplace_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
+    L.sina_hip_align_rank.argtypes = [vp, C.c_int, C.c_uint, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32]
+    L.sina_hip_staged_rank.restype = C.POINTER(C.c_uint32)
+    L.sina_hip_staged_rank.argtypes = [vp]
+    L.sina_hip_rank_inplace_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
     L.sina_hip_staged_shift_log.restype = C.POINTER(C.c_uint32)
     L.sina_hip_staged_shift_log.argtypes = [vp]
     L.sina_hip_assemble_stats.argtypes = [vp, u64p, u64p, u64p, u64p]
@@ -630,6 +638,32 @@ class Context:
         """The in-place family-identity kernel on this context so far: dict(kernel_ms, sequences, pairs, launches);
         sequences counts assembled queries only, pairs their (query, member) pairs."""
         return self._counters(self.L.sina_hip_identity_inplace_stats, KERNEL_MS + u64_fields("sequences", "pairs", "launches"))
+
+    def rank_assembled(self, on=True, k=10, nofast=False, kmer_candidates=1000, iupac=0, filter_lc=False, cover="query",
+                       max_result=10):
+        """The switch of the in-place ranking (the search stage where the device assembles): with it on, every fast-path
+        align call with assemble != 0 on a store with a name order and an index of that k / nofast also searches its
+        queries' k-mer candidates (kmer_candidates, at most 4096 after clamping to the references) and ranks them
+        against every query it assembles without dropping a base (staged_rank).  The rules are compare_rank's.  Off
+        after init and fork; a missing precondition leaves the align call as it is without the switch."""
+        self._check(self.L.sina_hip_align_rank(self.h, 1 if on else 0, int(k), 1 if nofast else 0, int(kmer_candidates),
+                                               int(iupac), int(filter_lc), self._cover(cover), int(max_result)))
+
+    def staged_rank(self):
+        """uint32 [nq, 130] of this context's last align call (a copy), rows laid out like its `out`: the number of rows
+        n, the flags (bit 0: a candidate had a denominator of 0; bit 1: ranked), 64 ids, 64 score bit patterns, zero
+        from n on -- kmer_topk_rank's rows for the same words.  A row the device did not rank is all zero.  None if
+        that call did not rank (switch off, assemble=0, no index of the switch's k, no name order, no query)."""
+        p = self.L.sina_hip_staged_rank(self.h)
+        if not p:
+            return None
+        nq = getattr(self, "_align_nq", 0)
+        return np.ctypeslib.as_array(p, shape=(max(nq, 1), RANK_ROW_WORDS))[:nq].copy()
+
+    def rank_inplace_stats(self):
+        """The in-place ranking kernel on this context so far: dict(kernel_ms, sequences, pairs, launches); sequences
+        counts ranked queries, pairs their candidates, launches the DP launch ranges that ranked."""
+        return self._counters(self.L.sina_hip_rank_inplace_stats, KERNEL_MS + u64_fields("sequences", "pairs", "launches"))
 
     def align_families(self, fam_ids, fam_off, qmask, qoff, params=None):
         params = params or self.params()

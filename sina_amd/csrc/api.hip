@@ -529,6 +529,7 @@ int sina_hip_align_graphs(sina_hip_ctx *c, const sina_hip_graph_batch *g, const 
     align_call call(c);
     sina_hip_hint_guard hints(c);
     if (call.begin(kMayCountPairs, p, g ? g->nq : 0)) return 1;  // (no family comes to the device: no identity)
+    if (call.begin_rank(p, qmask, qoff, g ? g->nq : 0)) return 1;
     return align_graphs_impl(c, g, qmask, qoff, p, out, out_pos);
 }
 
@@ -540,6 +541,7 @@ int sina_hip_align_graphs_wsets(sina_hip_ctx *c, const sina_hip_graph_batch *g, 
     align_call call(c);
     sina_hip_hint_guard hints(c);
     if (call.begin(kMayCountPairs, p, g ? g->nq : 0)) return 1;  // (no family comes to the device: no identity)
+    if (call.begin_rank(p, qmask, qoff, g ? g->nq : 0)) return 1;
     return align_graphs_impl(c, g, qmask, qoff, p, out, out_pos, nullptr, 0, 0, nullptr, nullptr, weight_set, n_sets);
 }
 
@@ -550,6 +552,7 @@ int sina_hip_align_graphs_any(sina_hip_ctx *c, const sina_hip_graph_batch *g, co
     align_call call(c);
     sina_hip_hint_guard hints(c);
     if (call.begin(kMayCountPairs, p, g ? g->nq : 0)) return 1;  // (no family comes to the device: no identity)
+    if (call.begin_rank(p, qmask, qoff, g ? g->nq : 0)) return 1;
     return align_graphs_any_impl(c, g, qmask, qoff, p, out, out_pos);
 }
 

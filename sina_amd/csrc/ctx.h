@@ -36,7 +36,7 @@ struct sina_hip_store {
     // column, ascending in the column; n_pair_ent == 0: no map.  Kept when the references change (it describes columns)
     sina_hip::DevBuf pair_ent;
     uint32_t n_pair_ent = 0;
-    std::atomic<size_t> inplace_rows_hint[2] = {};  // bytes of pinned rows the largest counted align call took (InplaceCount::h_rows)
+    std::atomic<size_t> inplace_rows_hint[3] = {};  // bytes of pinned rows the largest counted align call took (InplaceCount::h_rows)
     std::mutex aux_mu;
     std::mutex stats_mu;
     // The device-filling kernels of all contexts (k-mer count/select, DAG build, DP) go through ONE
@@ -117,6 +117,7 @@ namespace sina_hip {
 //   kUsePairs              sequences  entries_visited    sina_hip_pair_stats
 //   kUsePairsInplace       sequences  --                 sina_hip_pair_inplace_stats
 //   kUseIdentityInplace    sequences  pairs              sina_hip_identity_inplace_stats
+//   kUseRankInplace        sequences  pairs              sina_hip_rank_inplace_stats
 struct KernelUse {
     double ms = 0;
     uint64_t a = 0, b = 0, launches = 0;
@@ -127,14 +128,15 @@ struct KernelUse {
         launches += launches_;
     }
 };
-enum kernel_use { kUseMatch, kUseRank, kUsePairs, kUsePairsInplace, kUseIdentityInplace, kNumKernelUse };
+enum kernel_use { kUseMatch, kUseRank, kUsePairs, kUsePairsInplace, kUseIdentityInplace, kUseRankInplace, kNumKernelUse };
 // queries a path off the fast one has taken on a context (sina_hip_ctx::path_queries; sina_hip_wide_queries,
 // sina_hip_long_queries, sina_hip_big_select_queries): the wide DP kernel, the long k-mer count kernel, the big select
 enum slow_path { kPathWide, kPathLong, kPathBigSelect, kNumSlowPaths };
 
 // A count that rides on an align call, over the words the device assembly left: the helix base pairs (pairs.hip,
 // pair_count_assembled_kernel; sina_hip_align_count_pairs, sina_hip_staged_pair_counts) and the family identity
-// (identity.hip, family_identity_kernel; sina_hip_align_count_identity, sina_hip_staged_identity).
+// (identity.hip, family_identity_kernel; sina_hip_align_count_identity, sina_hip_staged_identity); and, a row instead
+// of a count, the search stage's ranking (rank.hip, rank_assembled_kernel; sina_hip_align_rank, sina_hip_staged_rank).
 struct InplaceCount {
     const size_t row_bytes;  // of a query's row: six counters, or the best score's bits and the members that scored
     const int kernel;        // its record in sina_hip_ctx::use
@@ -169,7 +171,19 @@ struct InplaceCount {
     }
     const uint32_t *staged() const { return active ? h_rows.as<uint32_t>() : nullptr; }
 };
-enum inplace_count { kInplacePairs, kInplaceIdentity, kNumInplace };
+enum inplace_count { kInplacePairs, kInplaceIdentity, kInplaceRank, kNumInplace };
+
+// What the ranking that rides on an align call (inplace[kInplaceRank]) runs with: the rules sina_hip_align_rank set,
+// and the call's candidates -- the id rows its k-mer search left on the device before the first DP launch range
+// (kmer_launch.hip, kmer_rows_resident), kept for the whole call, with a host copy of their lengths.
+struct RankRider {
+    static constexpr size_t row_bytes = 4 * (2 + 2 * 64);  // n, flags, 64 ids, 64 score bit patterns (rank_plan.h, kRankRowWords)
+    uint32_t k = 0, nofast = 0, cands = 0, N = 0;
+    int iupac = 0, filter_lc = 0, cover = 0;
+    uint32_t stride = 0;   // this call's candidates per query: min(cands, n_refs)
+    DevBuf ids, n;         // [nq][stride], [nq]
+    std::vector<uint32_t> h_n;
+};
 
 // The shift log of an align call that runs with assemble = 2 (traceback.hip, assemble_kernel<true>;
 // sina_hip_staged_shift_log): a launch range's rows on the device and the whole call's rows in pinned memory, laid out
@@ -211,8 +225,8 @@ struct sina_hip_ctx {
     hipStream_t stream_dp = nullptr;  // DP hand-over, result copies
     std::mutex mu;
     // [10], [11]: hand-over to / from the store's heavy stream; [12]: end of the in-place pair count; [13]: end of the
-    // in-place family identity
-    hipEvent_t ev[14];
+    // in-place family identity; [14]: end of the in-place ranking
+    hipEvent_t ev[15];
 
     sina_hip_store *st = nullptr;
     bool owns_store = false;
@@ -248,7 +262,9 @@ struct sina_hip_ctx {
     // (the pair-count kernel, pairs.hip, borrows s_qab, s_qoff and s_out)
     // the counts that ride on an align call: [n][6] pair counters in 24 bytes, [n][2] identity words in 8
     sina_hip::InplaceCount inplace[sina_hip::kNumInplace] = {{24, sina_hip::kUsePairsInplace, 12},
-                                                             {sina_hip::identity_row_bytes(1), sina_hip::kUseIdentityInplace, 13}};
+                                                             {sina_hip::identity_row_bytes(1), sina_hip::kUseIdentityInplace, 13},
+                                                             {sina_hip::RankRider::row_bytes, sina_hip::kUseRankInplace, 14}};
+    sina_hip::RankRider rider;           // the in-place ranking's rules and the call's candidate rows
     sina_hip::ShiftLog shift;            // assemble = 2: the shifted runs' log rows
     sina_hip::AssembleUse asm_use;       // (by the context's caller, who holds its mutex)
     double debug_assemble_ms = 0;        // the kernel's time in the last sina_hip_debug_assemble call
@@ -261,7 +277,7 @@ struct sina_hip_ctx {
 
     size_t lds_budget = 0;  // LDS per DP workgroup; 0 = what keeps the register-limited occupancy (dp_default_lds_budget)
 
-    static constexpr int kNumScratch = 51;
+    static constexpr int kNumScratch = 54;
     static_assert(kNumScratch <= 64, "sina_hip_store::cap_hint is too short");
     void scratch(sina_hip::DevBuf **all) {
         sina_hip::DevBuf *list[kNumScratch] = {&qd, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &res,
@@ -270,7 +286,8 @@ struct sina_hip_ctx {
                                                &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &order,
                                                &s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &edge, &prof16, &self16, &rgain,
                                                &scout, &scout_u, &wset, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag,
-                                               &r_cnt, &inplace[sina_hip::kInplacePairs].rows, &inplace[sina_hip::kInplaceIdentity].rows, &pred4};
+                                               &r_cnt, &inplace[sina_hip::kInplacePairs].rows, &inplace[sina_hip::kInplaceIdentity].rows, &pred4,
+                                               &inplace[sina_hip::kInplaceRank].rows, &rider.ids, &rider.n};
         for (int i = 0; i < kNumScratch; i++) all[i] = list[i];
     }
     void publish_hints() {  // after a call: remember how big my buffers had to be
@@ -300,7 +317,8 @@ struct sina_hip_ctx {
                                       &s_qab, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};  // (s_qab, r_*: sina_hip_kmer_topk_rank)
         sina_hip::DevBuf *align[] = {&qd, &order, &rec, &node_pos, &pred, &pred4, &succ_minpos, &qmask, &spill, &edge, &res, &weights, &out,
                                      &out_pos, &g_fam_ids, &g_fam_off, &g_tmp0, &g_tmp1, &g_tmp2, &g_tmp3, &g_sizes, &g_wtab, &rgain, &scout, &scout_u,
-                                     &prof16, &self16, &wset, &inplace[sina_hip::kInplacePairs].rows, &inplace[sina_hip::kInplaceIdentity].rows};
+                                     &prof16, &self16, &wset, &inplace[sina_hip::kInplacePairs].rows, &inplace[sina_hip::kInplaceIdentity].rows,
+                                     &inplace[sina_hip::kInplaceRank].rows, &rider.ids, &rider.n};
         sina_hip::DevBuf *compare[] = {&s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag, &r_cnt};
         sina_hip::DevBuf **list = kind == 0 ? search : (kind == 1 ? align : compare);
         const size_t n = kind == 0 ? sizeof search / sizeof *search : (kind == 1 ? sizeof align / sizeof *align : sizeof compare / sizeof *compare);
@@ -762,6 +780,17 @@ int rank_launch(sina_hip_ctx *c, const uint32_t *d_qab, const uint64_t *d_qoff, 
                 int filter_lc, int cover, uint32_t N, uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint32_t *out_flag);
 // fails on an unknown rule, max_result outside 1..64, a store without references or without a name order
 int rank_check_rules(const char *who, sina_hip_ctx *c, int iupac_rule, int cover_rule, uint32_t max_result);
+// ---- the same ranking over the words the assembly left (rank_assembled_kernel), behind launch_assemble on its stream:
+// the launch range's rows [b.nq][kRankRowWords] from the call's candidate rows q_base .. (ctx.h, RankRider);
+// max_l: the range's longest query; reserve_rank_assembled before the range's launches: it may allocate
+int reserve_rank_assembled(sina_hip_ctx *c, uint32_t bq);
+int launch_rank_assembled(sina_hip_ctx *c, const BtArgs &b, uint32_t q_base, uint32_t max_l, uint32_t *rows, hipStream_t s);
+// ---- the candidates of an align call that ranks (kmer_launch.hip): the call's nq queries (none longer than
+// SINA_HIP_MAX_QUERY_LEN) searched as sina_hip_kmer_topk would, every range's final select rows copied device to device
+// into d_ids [nq][max] / d_n [nq], the lengths also into h_n.  The caller holds the context's mutex; returns when the
+// rows are there.  Uploads into c->qmask and c->k_qoff: before the call's first DP launch range
+int kmer_rows_resident(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max, uint32_t *d_ids,
+                       uint32_t *d_n, uint32_t *h_n);
 }  // namespace sina_hip
 
 namespace sina_hip {
@@ -784,13 +813,17 @@ struct align_call {
         const bool assemble = p && p->assemble;
         const bool counts[kNumInplace] = {
             (may & kMayCountPairs) && c->inplace[kInplacePairs].on && assemble && nq != 0 && c->st->n_pair_ent != 0,
-            identity_call_counts(c->inplace[kInplaceIdentity].on, assemble, (may & kMayCountIdentity) != 0, nq)};
+            identity_call_counts(c->inplace[kInplaceIdentity].on, assemble, (may & kMayCountIdentity) != 0, nq),
+            false};  // (the ranking: begin_rank, which needs the queries)
         const bool shifts = p && p->assemble == SINA_ASSEMBLE_SHIFT && nq != 0;
         if (counts[kInplacePairs] || counts[kInplaceIdentity] || shifts) SH_CHECK(hipSetDevice(c->device));  // (pinned memory)
         for (int i = 0; i < kNumInplace; i++)
             if (c->inplace[i].begin(counts[i], nq)) return 1;
         return c->shift.begin(shifts, nq);
     }
+    // The ranking rides (dp_launch.hip, rank_rider_begin) if its switch is on, the call assembles and the store has
+    // what it needs; then the call's candidates are searched here, before its first DP launch range.  After begin().
+    int begin_rank(const sina_hip_align_params *p, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq);
 };
 
 // ---- the counters' readers, under the context's mutex: what the public getters are shims over (they check their

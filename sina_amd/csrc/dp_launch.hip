@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "ctx.h"
+#include "compare_dev.h"
 
 namespace sina_hip {
 
@@ -75,7 +76,7 @@ int reserve_launch_buffers(sina_hip_ctx *c, const DpPlan &pl, const DpLaunch &l,
         return 1;
     for (InplaceCount &ic : c->inplace)
         if (ic.reserve(l.bq)) return 1;
-    if (c->shift.reserve(l.bq)) return 1;
+    if (c->shift.reserve(l.bq) || reserve_rank_assembled(c, l.bq)) return 1;
     if (l.want_dbg_value && c->dbg.reserve(4 * sums.tb_cells)) return 1;
     return 0;
 }
@@ -204,7 +205,7 @@ int choose_bound(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const s
 }
 
 // The in-place counts of a call that counts them (ctx.h, align_call): right behind the assembly, on its stream, over
-// the words it left -- the pair count, then the family identity.  Like launch_assemble they take no part in the FIFO's
+// the words it left -- the pair count, then the family identity, then the search stage's ranking.  Like launch_assemble they take no part in the FIFO's
 // dry signal -- the DP kernel gives that --, and each records its own event behind its kernel: from the event before
 // it (ev[2], the walk's and the assembly's end, or the event of the count that ran before) to that one is its own time
 // (account_launch).
@@ -216,7 +217,7 @@ int choose_bound(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const s
 // call off these buffers meanwhile.  The uploads between the build and the chunk's last range (qd, qmask, wset,
 // order, scout values) go to other buffers.
 static int launch_inplace_counts(sina_hip_ctx *c, const BtArgs &b, const DpLaunch &l, hipStream_t s) {
-    InplaceCount &pc = c->inplace[kInplacePairs], &id = c->inplace[kInplaceIdentity];
+    InplaceCount &pc = c->inplace[kInplacePairs], &id = c->inplace[kInplaceIdentity], &rk = c->inplace[kInplaceRank];
     if (pc.active) {
         if (launch_pair_count_assembled(b, c->st->pair_ent.p, c->st->n_pair_ent, pc.rows.as<uint32_t>(), s)) return 1;
         SH_CHECK(hipEventRecord(c->ev[pc.ev], s));
@@ -224,6 +225,10 @@ static int launch_inplace_counts(sina_hip_ctx *c, const BtArgs &b, const DpLaunc
     if (id.active) {
         if (launch_family_identity(c, b, l.fam_ncap, b.asm_cap, id.rows.as<uint32_t>(), s)) return 1;
         SH_CHECK(hipEventRecord(c->ev[id.ev], s));
+    }
+    if (rk.active) {  // (reads the call's candidate rows: searched, and copied on c->stream, before this launch was queued)
+        if (launch_rank_assembled(c, b, l.q_base, b.asm_cap, rk.rows.as<uint32_t>(), s)) return 1;
+        SH_CHECK(hipEventRecord(c->ev[rk.ev], s));
     }
     return 0;
 }
@@ -333,6 +338,14 @@ int account_launch(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_param
                 c->use[kUseIdentityInplace].a++;
                 c->use[kUseIdentityInplace].b += l.fam_off ? l.fam_off[q + 1] - l.fam_off[q] : 0;
             }
+    if (c->inplace[kInplaceRank].active)  // (the rows are down: fetch_results; a ranked query's candidates were all scored)
+        for (uint32_t q = 0; q < l.bq; q++) {
+            const uint32_t *row = c->inplace[kInplaceRank].h_rows.as<uint32_t>() + (RankRider::row_bytes / 4) * (l.q_base + q);
+            if (!(row[1] & 2u)) continue;
+            const uint32_t n = c->rider.h_n[l.q_base + q];
+            c->use[kUseRankInplace].a++;
+            c->use[kUseRankInplace].b += n == 0xFFFFFFFFu ? 0u : std::min(n, c->rider.stride);
+        }
     if (p->assemble) {  // (sina_hip_assemble_stats)
         c->asm_use.queries += l.bq;
         for (uint32_t q = 0; q < l.bq; q++) {
@@ -357,6 +370,31 @@ int account_launch(sina_hip_ctx *c, const DpPlan &pl, const sina_hip_align_param
 }
 
 }  // namespace
+
+// Whether this call ranks, and if it does its candidates.  What the store or the call lacks never fails the call: it
+// then runs as without the switch and stages nothing.  (A call with a query beyond the fast k-mer count kernel's
+// length -- sina_hip_align_graphs_any alone takes one -- does not rank either: its queries go the caller's own way.)
+int align_call::begin_rank(const sina_hip_align_params *p, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq) {
+    InplaceCount &rk = c->inplace[kInplaceRank];
+    const sina_hip_store *st = c->st;
+    RankRider &rr = c->rider;
+    if (!rk.on || !p || !p->assemble || !qmask || !qoff || nq == 0) return 0;
+    if (!st->have_refs || st->n_refs == 0 || !st->have_name_order || !st->have_index || st->k != rr.k || st->nofast != rr.nofast) return 0;
+    const uint32_t stride = std::min(rr.cands, st->n_refs);
+    if (stride == 0 || kmer_big_select(stride)) return 0;
+    uint32_t max_l = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        if (qoff[q + 1] <= qoff[q] || qoff[q + 1] - qoff[q] > (uint64_t)SINA_HIP_MAX_QUERY_LEN) return 0;
+        max_l = std::max<uint32_t>(max_l, (uint32_t)(qoff[q + 1] - qoff[q]));
+    }
+    if (compare_table_bytes(st->width, max_l) > kCompareMaxLds) return 0;
+    SH_CHECK(hipSetDevice(c->device));
+    rr.stride = stride;
+    rr.h_n.assign(nq, 0);
+    if (rr.ids.reserve(4 * (size_t)nq * stride) || rr.n.reserve(4 * (size_t)nq)) return 1;
+    if (kmer_rows_resident(c, qmask, qoff, nq, stride, rr.ids.as<uint32_t>(), rr.n.as<uint32_t>(), rr.h_n.data())) return 1;
+    return rk.begin(true, nq);
+}
 
 int run_dp_device(sina_hip_ctx *c, const DpPlan &pl, const PrunePlan &pp, const sina_hip_align_params *p, const DpLaunch &l) {
     const bool forbid = p->insertion == SINA_INSERTION_FORBID;
@@ -414,7 +452,7 @@ int align_family_batches(sina_hip_ctx *c, const FamilyCall &f) {
     const int Lp = pl.geom.Lp();
     if (upload_weights(c, p, n_sets)) return 1;
     if (c->h_out_pos.reserve(4 * std::max<uint64_t>(qoff[nq] - qoff[0], 1))) return 1;
-    if (call.begin(kMayCountPairs | kMayCountIdentity, p, nq)) return 1;
+    if (call.begin(kMayCountPairs | kMayCountIdentity, p, nq) || call.begin_rank(p, f.qmask, qoff, nq)) return 1;
     // (SINA_HIP_TEST=dp_range_q=N: at most N queries per DP launch range, so that a small call takes several;
     // fam_chunk_q=N: at most N queries per build chunk, so that it spans several builds)
     const uint32_t range_q = (uint32_t)strtoul(test_knob("dp_range_q").c_str(), nullptr, 10);

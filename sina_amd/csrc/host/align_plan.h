@@ -1,5 +1,5 @@
 // What the aligner sends to the device in which call: the route of a DP job, the groups of a batch and their order,
-// the weight sets of a several-filter group, and whether a group's call counts in place.  Header-only; no HIP, no
+// the weight sets of a several-filter group, and whether a group's call counts or ranks in place.  Header-only; no HIP, no
 // stages.h, no cseq.h, no globals, no environment: a stand-alone program can include it (tests/align_plan_check.cpp).
 // aligner.cpp fills the switches and the jobs' facts and runs one device call per group, in the order given here.
 #pragma once
@@ -19,6 +19,7 @@ struct align_switches {
     bool fs_no_graph = false, device_graph = true, device_profile = false, wide_fallback = false, weight_sets = true;
     bool device_bps = false, device_idty = false, calc_idty = false;
     bool device_shift = false;  // the align call runs with assemble = SINA_ASSEMBLE_SHIFT: see align_assemble_mode
+    bool device_search = false;  // the align call ranks the search stage's candidates where it assembles: see plan_search_inplace
 };
 
 // What sina_hip_align_params::assemble is for a group's call: the device finishes the insertions that shift their
@@ -146,6 +147,30 @@ inline align_counting plan_counting(const align_switches &s, align_route route, 
     c.count_pairs = s.device_bps && batch_driver && route != route_long && has_pair_map && assembles;
     c.count_idty = s.calc_idty && s.device_idty && route == route_device && assembles;
     return c;
+}
+
+// Whether a group's align call also ranks the search stage's k-mer candidates against the words it assembles
+// (device-search; sina_hip_align_rank).  What the aligner reads of the search stage and of the store, in one place:
+struct search_stage_facts {
+    bool correction_none = false;  // search-correction none (Jukes-Cantor: rounding can merge ratios into ties)
+    bool ignore_super = false;     // search-ignore-super
+    bool search_all = false;       // search-all (every reference is a candidate: sina_hip_compare_rank serves it)
+    int max_result = 0;            // search-max-result
+    uint64_t candidates = 0;       // min(search-kmer-candidates, references of the store)
+    bool name_order = false;       // the store's name order is on the device (no two references share a name)
+    bool same_store = false;       // search-db names the aligner's store
+    bool index_matches = false;    // that store's index is the one search-kmer-len / search-no-fast ask for
+};
+constexpr int kSearchInplaceMaxResult = 64;            // rows of a query's staged row (rank_plan.h, kRankMaxResult)
+constexpr uint64_t kSearchInplaceMaxCandidates = 4096;  // what the k-mer search's LDS select sorts (kmer_plan.h, kKmerSelMax)
+// The stage's options are those its own device ranking accepts (search_filter.cpp, device_rank), the candidates and
+// the comparison must be over the aligner's store, and the call must assemble: the rows are of finished words.  Never
+// for the one-slot calls of the long route (the wide path assembles nothing).  A group that does not rank leaves
+// its trays to the search stage's own path, as does every tray of a ranking group whose row says "not ranked".
+inline bool plan_search_inplace(const align_switches &s, align_route route, bool assembles, const search_stage_facts &f) {
+    return s.device_search && route != route_long && assembles && f.correction_none && !f.ignore_super && !f.search_all &&
+           f.max_result >= 1 && f.max_result <= kSearchInplaceMaxResult && f.candidates <= kSearchInplaceMaxCandidates &&
+           f.name_order && f.same_store && f.index_matches;
 }
 
 }  // namespace sina

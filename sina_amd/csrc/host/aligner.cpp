@@ -3,6 +3,8 @@
 // (include/sina_hip.h).  No CPU fallback: if the HIP library reports an error, the stage throws.
 #include "stages_internal.h"
 #include "align_plan.h"
+#include "../kmer_plan.h"
+#include "../rank_plan.h"
 #include <immintrin.h>
 
 #include <algorithm>
@@ -51,6 +53,9 @@ static aligner::options al_defaults() {  // src/align.cpp:231-274
     // the device also finishes alignments whose insertions shift their neighbours (assemble = 2): on request, until it
     // has been decided on measurements
     o.device_shift = false;
+    // the search stage's rows from the align call itself (sina_hip_align_rank) instead of a second trip with the
+    // finished sequences (default off)
+    o.device_search = false;
     return o;
 }
 static aligner::options &al_opts() {
@@ -95,6 +100,7 @@ void aligner::set_option(const std::string &name, const std::string &value) {
     else if (name == "device-bps") o.device_bps = to_bool(value);
     else if (name == "device-idty") o.device_idty = to_bool(value);
     else if (name == "device-shift") o.device_shift = to_bool(value);
+    else if (name == "device-search") o.device_search = to_bool(value);
     else if (name == "db") o.database = value;
     else throw std::logic_error("aligner: unknown option " + name);
 }
@@ -667,6 +673,7 @@ static align_switches plan_switches(const aligner::options &o) {
     s.device_idty = o.device_idty;
     s.calc_idty = o.calc_idty;
     s.device_shift = o.device_shift;
+    s.device_search = o.device_search;
     return s;
 }
 
@@ -729,6 +736,39 @@ static align_counting set_counting(sina_hip_ctx *ctx, const group_call &g, align
     return c;
 }
 
+static_assert(kSearchInplaceMaxResult == (int)sina_hip::kRankMaxResult && kSearchInplaceMaxCandidates == sina_hip::kKmerSelMax,
+              "align_plan.h disagrees with rank_plan.h / kmer_plan.h");
+// Sets the ranking switch of the leased context as the plan has it for this group (either way, as set_counting); gives
+// whether the group's call ranks.  The store's name order is looked at -- and, the first time, uploaded -- only when
+// everything else holds.
+static bool set_search_inplace(sina_hip_ctx *ctx, const group_call &g, align_route route, const sina_hip_align_params &p) {
+    bool ranks = false;
+    search_stage_request rq{};
+    if (g.sw.device_search) {
+        rq = search_filter_request();
+        search_stage_facts f;
+        f.correction_none = rq.correction_none;
+        f.ignore_super = rq.ignore_super;
+        f.search_all = rq.search_all;
+        f.max_result = rq.max_result;
+        f.candidates = std::min<uint64_t>((uint64_t)std::max(rq.kmer_candidates, 0), g.store.size());
+        f.same_store = !rq.database.empty() && rq.database == g.store.getFileName();
+        f.index_matches = f.same_store && rq.kmer_len >= 1 && g.store.index_is((unsigned)rq.kmer_len, rq.no_fast);
+        f.name_order = true;  // (asked last: the store's first answer computes and uploads the order)
+        if (f.candidates >= 1 && plan_search_inplace(g.sw, route, p.assemble != 0, f)) {
+            f.name_order = g.store.name_order_ready();
+            ranks = plan_search_inplace(g.sw, route, p.assemble != 0, f);
+        }
+    }
+    if (ranks)
+        hip_check(sina_hip_align_rank(ctx, 1, (unsigned)rq.kmer_len, rq.no_fast ? 1 : 0, (uint32_t)rq.kmer_candidates, rq.iupac_rule,
+                                      rq.filter_lowercase ? 1 : 0, rq.cover_rule, (uint32_t)rq.max_result),
+                  "sina_hip_align_rank");
+    else
+        hip_check(sina_hip_align_rank(ctx, 0, 0, 0, 0, 0, 0, 0, 0), "sina_hip_align_rank");
+    return ranks;
+}
+
 // The long route.  One call per slot: a wide mesh of this size fills a launch of the wide kernel nearly alone anyway,
 // and a query whose mesh exceeds SINA_HIP_WIDE_CELLS -- the one thing a call refuses a well-formed query for -- then
 // fails alone, softly, with the call's message in its log.  The trays of a slot are finished before the next call
@@ -769,13 +809,17 @@ static void align_long_slots(sina_hip_ctx *ctx, const group_call &g, const sina_
 // Finishes the group's trays from out[slot] and the aligned columns where the device copied them, in the context's
 // pinned staging buffer (sina_hip_staged_out_pos -- the context stays leased until the group's last tray is finished).
 static void finish_group(sina_hip_ctx *ctx, const group_call &g, const std::vector<dp_job *> &members, const device_slots &slots,
-                         const sina_hip_align_out *out, uint32_t width, bool counted_pairs, bool shifted) {
+                         const sina_hip_align_out *out, uint32_t width, bool counted_pairs, bool shifted, bool ranked) {
     const uint32_t *const staged_pos = sina_hip_staged_out_pos(ctx);
     // (null unless the call ran with assemble = 2; a slot's row: its shifted runs)
     const uint32_t *const staged_shift = shifted ? sina_hip_staged_shift_log(ctx) : nullptr;
     constexpr size_t shift_row_words = 1 + 3 * (size_t)SINA_HIP_SHIFT_LOG;
     // (null unless this call counted; the trays of a slot share its row)
     const uint32_t *const staged_pairs = counted_pairs ? sina_hip_staged_pair_counts(ctx) : nullptr;
+    // (null unless this call ranked -- a call the device found a precondition missing for has not; a slot's row, cut to
+    // its length, goes to the slot's trays: the search stage reads it, search_filter.cpp)
+    const uint32_t *const staged_rank = ranked ? sina_hip_staged_rank(ctx) : nullptr;
+    constexpr size_t rank_row_words = 2 + 2 * (size_t)kSearchInplaceMaxResult;
     scoped_phase ph("al.finish(NAST,log)");
     std::atomic<uint64_t> scored{0}, by_device{0};
     parallel_for(members.size(), [&](size_t x) {
@@ -784,6 +828,14 @@ static void finish_group(sina_hip_ctx *ctx, const group_call &g, const std::vect
                         staged_pairs ? staged_pairs + 6 * (size_t)u : nullptr, staged_shift ? staged_shift + shift_row_words * u : nullptr))
             scored.fetch_add(1, std::memory_order_relaxed);
         if (out[u].assembled) by_device.fetch_add(1, std::memory_order_relaxed);
+        const uint32_t *const row = staged_rank ? staged_rank + rank_row_words * u : nullptr;
+        if (row != nullptr && (row[1] & 2u) && row[0] <= (uint32_t)kSearchInplaceMaxResult) {
+            auto cut = std::make_shared<std::vector<uint32_t>>(2 + 2 * (size_t)row[0]);
+            (*cut)[0] = row[0], (*cut)[1] = row[1];
+            std::copy(row + 2, row + 2 + row[0], cut->begin() + 2);
+            std::copy(row + 2 + kSearchInplaceMaxResult, row + 2 + kSearchInplaceMaxResult + row[0], cut->begin() + 2 + row[0]);
+            members[x]->t->search_row = std::move(cut);
+        }
     });
     if (staged_pairs) g.store.count_pairs_inplace(scored.load());
     g.store.count_finished(by_device.load(), members.size() - by_device.load());
@@ -825,11 +877,12 @@ static void align_group_members(const group_call &g, const align_group_key &key,
     std::vector<sina_hip_align_out> out(slots.dnq);
     auto dev = g.store.worker_device(reference_store::dev_align);
     const align_counting counting = set_counting(dev.get(), g, key.route, p);
+    const bool ranks = set_search_inplace(dev.get(), g, key.route, p);
     if (key.route == route_long) return align_long_slots(dev.get(), g, p, members, slots, out.data());
     // out[u] = slot u's result, its aligned columns at sina_hip_staged_out_pos + dqoff[u] while the context stays leased
     const uint32_t width = key.route == route_device ? align_family_ids(dev.get(), g.store, g.o, p, slots, out.data())
                                                      : align_host_graphs(dev.get(), g.o, p, slots, out.data());
-    finish_group(dev.get(), g, members, slots, out.data(), width, counting.count_pairs, p.assemble == SINA_ASSEMBLE_SHIFT);
+    finish_group(dev.get(), g, members, slots, out.data(), width, counting.count_pairs, p.assemble == SINA_ASSEMBLE_SHIFT, ranks);
     if (g.o.calc_idty) set_group_identity(dev.get(), g, members, slots, out.data(), counting.count_idty);
 }
 }  // namespace

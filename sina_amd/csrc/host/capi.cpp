@@ -393,6 +393,15 @@ int sina_host_store_identity_inplace_stats(const char *key, uint64_t *trays, dou
         reference_store::get(key)->identity_inplace_stats(trays, kernel_ms, sequences, pairs, launches);
     });
 }
+// the aligner's device-search on this store: trays whose search rows came from the row their align call brought back,
+// and the in-place ranking's time and volume (sina_hip_rank_inplace_stats) on its contexts -- between runs
+int sina_host_store_search_inplace_stats(const char *key, uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs,
+                                         uint64_t *launches) {
+    return guarded([&] {
+        if (!trays || !kernel_ms || !sequences || !pairs || !launches) throw std::logic_error("store_search_inplace_stats: null argument");
+        reference_store::get(key)->search_inplace_stats(trays, kernel_ms, sequences, pairs, launches);
+    });
+}
 // the aligner's finish step on this store: trays the device had assembled / the host finished, and the device
 // assembly's volume (sina_hip_assemble_stats) on its contexts -- between runs
 int sina_host_store_assemble_stats(const char *key, uint64_t *trays_device, uint64_t *trays_host, uint64_t *queries, uint64_t *assembled,

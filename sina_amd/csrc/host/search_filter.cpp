@@ -130,6 +130,11 @@ static search_filter::options &sf_opts() {
 }
 void search_filter::reset_options() { sf_opts() = sf_defaults(); }
 std::string search_filter_database() { return sf_opts().pt_database; }
+search_stage_request search_filter_request() {
+    const search_filter::options &o = sf_opts();
+    return {o.pt_database, o.search_all, o.fs_no_fast, o.ignore_super, o.comparator.dist_rule == CMP_DIST_NONE, o.comparator.filter_lc_rule,
+            o.fs_kmer_len, o.kmer_candidates, o.max_result, (int)o.comparator.iupac_rule, (int)o.comparator.cover_rule};
+}
 
 void search_filter::set_option(const std::string &name, const std::string &value) {
     options &o = sf_opts();
@@ -508,6 +513,34 @@ bool device_rank(const search_call &s, const std::vector<size_t> &idx) {
     return true;
 }
 
+// device-search: a tray whose row says "ranked" and "every candidate had a score" takes its rows from the row, cut at
+// --search-min-sim; it is never packed, uploaded or searched again.  Takes the searched trays; gives the others, in
+// order -- copy-shortcut trays, trays the host finished, the long route's, flagged ones, trays that lost a base, and
+// every tray when the aligner did not rank (align_plan.h, plan_search_inplace).  Nothing of this reaches a tray's log.
+std::vector<size_t> rows_in_place(const search_call &s, const std::vector<size_t> &idx) {
+    std::vector<size_t> rest;
+    uint64_t taken = 0;
+    for (size_t i : idx) {
+        const tray &t = s.batch[i];
+        const std::vector<uint32_t> *row = t.search_row.get();
+        if (row == nullptr || row->size() < 2 || ((*row)[1] & 3u) != 2u || row->size() < 2 + 2 * (size_t)(*row)[0]) {
+            rest.push_back(i);
+            continue;
+        }
+        const uint32_t n = (*row)[0];
+        auto &vc = *t.search_result;
+        for (uint32_t r = 0; r < n; r++) {
+            float score;
+            memcpy(&score, row->data() + 2 + n + r, 4);
+            if (!(score > s.o.min_sim)) break;
+            vc.emplace_back(score, &s.st.getCseq((*row)[2 + r]));
+        }
+        taken++;
+    }
+    s.st.count_search_inplace(taken);
+    return rest;
+}
+
 // boost::split(..., is_any_of(";")) of a taxonomy path, without the empty (or " ") group after the last ';'
 void split_tax_path(const std::string &tax_path, std::vector<std::string> &group_names) {
     std::string cur;
@@ -560,13 +593,15 @@ void annotate_tray(const search_filter::options &o, reference_store &st, tray &t
 // src/search_filter.cpp:244-412 for a batch of trays: the k-mer search and the comparisons of the
 // whole batch are one GPU call each (sina_hip_kmer_topk, sina_hip_compare) -- or, with device-rank, one call for
 // both that brings down the max_result best only (sina_hip_kmer_topk_rank; search-all: sina_hip_compare_rank).
+// -- or, for a tray the aligner's device-search has ranked, no call at all: its rows came back with its alignment.
 void search_filter::operator()(std::vector<tray> &batch) {
     const search_call s{sf_opts(), *data->arb, data->index, batch};
     const std::vector<size_t> idx = searched_trays(batch);
     if (idx.empty()) return;
-    if (!device_rank(s, idx)) {
-        if (s.o.device_rank) s.st.count_ranked(0, idx.size());
-        host_rank(s, idx);
+    const std::vector<size_t> rest = rows_in_place(s, idx);
+    if (!rest.empty() && !device_rank(s, rest)) {
+        if (s.o.device_rank) s.st.count_ranked(0, rest.size());
+        host_rank(s, rest);
     }
     scoped_phase ph("sf.rank+lca");
     parallel_for(idx.size(), [&](size_t x) { annotate_tray(s.o, s.st, batch[idx[x]]); });

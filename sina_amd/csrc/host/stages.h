@@ -205,6 +205,10 @@ public:
     // if it has none (tray_pair_score).
     float bp_score{0.f};
     bool bp_score_set{false};
+    // The search stage's rows of aligned_sequence where the aligner's align call ranked them (device-search): the
+    // slot's staged row cut to its length -- n, flags (bit 0: a candidate without a score, bit 1: ranked), n ids, n
+    // score bit patterns --, shared by the trays of a slot.  Null: the search stage takes its own path.
+    std::shared_ptr<const std::vector<uint32_t>> search_row;
     std::string log_text() const;   // log, with a pending score line rendered in its place
     void clear_log() {
         log.str(std::string());
@@ -359,6 +363,15 @@ public:
     void assemble_stats(uint64_t *trays_device, uint64_t *trays_host, uint64_t *queries, uint64_t *assembled, uint64_t *shifted_queries,
                         uint64_t *shifted_runs);
     void identity_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches);
+    // the aligner's device-search, likewise: trays whose search rows came from the row their align call brought back,
+    // and the in-place ranking's time and volume on the store's contexts -- sina_hip_rank_inplace_stats
+    void count_search_inplace(uint64_t trays) { n_search_inplace.fetch_add(trays, std::memory_order_relaxed); }
+    void search_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches);
+    // whether the index in HBM is the one of this k / nofast (ensure_index, adopt_index)
+    bool index_is(unsigned k, bool nofast) {
+        std::lock_guard<std::mutex> lk(gpu_mu);
+        return idx_k == (int)k && idx_nofast == nofast;
+    }
 
 private:
     reference_store() = default;
@@ -390,7 +403,7 @@ private:
     std::atomic<bool> too_wide_said{false};
     std::atomic<int> name_order_state{0};  // 0: not looked at, 1: uploaded, 2: names repeat
     std::atomic<uint64_t> n_ranked{0}, n_rank_host{0};
-    std::atomic<uint64_t> n_bp_inplace{0}, n_idty_inplace{0};
+    std::atomic<uint64_t> n_bp_inplace{0}, n_idty_inplace{0}, n_search_inplace{0};
     std::atomic<uint64_t> n_fin_device{0}, n_fin_host{0};
     pair_map helix;
     std::mutex helix_mu;
@@ -495,6 +508,8 @@ public:
                             // families and their trays take that identity (sina_hip_align_count_identity; default off)
         bool device_shift;  // the device also finishes alignments whose insertions shift their neighbours (assemble = 2,
                             // sina_hip.h SINA_ASSEMBLE_SHIFT; default off); the host keeps the cap cases
+        bool device_search; // the align call ranks the search stage's k-mer candidates against the words it assembles and
+                            // the trays carry the rows to that stage (sina_hip_align_rank; default off)
         std::string database;  // reference store the DAGs are built from (same as famfinder "db")
     };
     static options *opts;
@@ -570,6 +585,13 @@ public:
     static const char *fn_nearest;  // "nearest_slv" (query_arb.cpp:126)
 };
 std::string search_filter_database();  // the store the search stage was configured for
+// ... and what the aligner's device-search reads of the stage's options (align_plan.h, plan_search_inplace)
+struct search_stage_request {
+    std::string database;
+    bool search_all, no_fast, ignore_super, correction_none, filter_lowercase;
+    int kmer_len, kmer_candidates, max_result, iupac_rule, cover_rule;
+};
+search_stage_request search_filter_request();
 
 // ---------------------------------------------------------------- FASTA I/O + accuracy metrics
 enum FASTA_META_TYPE { FASTA_META_NONE = 0, FASTA_META_HEADER = 1, FASTA_META_COMMENT = 2, FASTA_META_CSV = 3 };

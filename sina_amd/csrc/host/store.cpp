@@ -51,7 +51,7 @@ tray::tray(const tray &o)
     : seqno(o.seqno), input_sequence(o.input_sequence), aligned_sequence(o.aligned_sequence),
       alignment_reference(o.alignment_reference), search_result(o.search_result), astats(o.astats),
       family_scores_kmer_k(o.family_scores_kmer_k), query_kmer_count(o.query_kmer_count), bp_score(o.bp_score),
-      bp_score_set(o.bp_score_set) {
+      bp_score_set(o.bp_score_set), search_row(o.search_row) {
     log.str(o.log.str());
     log.seekp(0, std::ios_base::end);
     pending_score = o.pending_score;
@@ -103,6 +103,7 @@ tray &tray::operator=(const tray &o) {
     query_kmer_count = o.query_kmer_count;
     bp_score = o.bp_score;
     bp_score_set = o.bp_score_set;
+    search_row = o.search_row;
     return *this;
 }
 alignment_stats *alignment_stats::shared_default() {
@@ -120,6 +121,7 @@ void tray::destroy() {  // (src/tray.cpp:77-86; the objects go back to their cac
     astats = nullptr;
     bp_score = 0.f;
     bp_score_set = false;
+    search_row.reset();
 }
 
 // ================================================================ reference_store
@@ -352,6 +354,10 @@ void reference_store::pair_inplace_stats(uint64_t *trays, double *kernel_ms, uin
 void reference_store::identity_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches) {
     sum_kernel_use("sina_hip_identity_inplace_stats", sina_hip_identity_inplace_stats, kernel_ms, sequences, pairs, launches);
     *trays = n_idty_inplace.load(std::memory_order_relaxed);
+}
+void reference_store::search_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches) {
+    sum_kernel_use("sina_hip_rank_inplace_stats", sina_hip_rank_inplace_stats, kernel_ms, sequences, pairs, launches);
+    *trays = n_search_inplace.load(std::memory_order_relaxed);
 }
 void reference_store::assemble_stats(uint64_t *trays_device, uint64_t *trays_host, uint64_t *queries, uint64_t *assembled,
                                      uint64_t *shifted_queries, uint64_t *shifted_runs) {

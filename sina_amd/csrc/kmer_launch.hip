@@ -21,11 +21,17 @@ struct RankReq {
     uint32_t N;
     uint32_t *out_flag;  // [nq]
 };
+// kmer_rows_resident: every range's final select rows stay on the device, in the caller's call-sized buffers
+struct KeepReq {
+    uint32_t *d_ids, *d_n;  // [nq][max], [nq] device memory
+    uint32_t *h_n;          // [nq] the lengths again, on the host
+};
 // One search call.  out_ids / out_scores: [nq * row()], out_n: [nq].
 // q_ab / out_match (sina_hip_kmer_topk_match; else null): the queries' packed aligned bases, one per mask byte, and
 // where every range's match counts go (match.hip), [nq * max] like out_ids
 // rk (sina_hip_kmer_topk_rank; else null): out_ids / out_scores are rows of the rank kernel, out_n its counts, and no
 // id or k-mer score of the select is copied out
+// keep (kmer_rows_resident; else null): nothing comes to the host but the lengths; out_ids / out_scores / out_n are null
 struct KmerRequest {
     const uint8_t *qmask;
     const uint64_t *qoff;
@@ -36,6 +42,7 @@ struct KmerRequest {
     const uint32_t *q_ab = nullptr;
     uint16_t *out_match = nullptr;
     const RankReq *rk = nullptr;
+    const KeepReq *keep = nullptr;
     uint32_t row() const { return rk ? rk->N : max; }  // entries of an output row
     uint32_t qlen(uint32_t q) const { return (uint32_t)(qoff[q + 1] - qoff[q]); }
 };
@@ -71,7 +78,7 @@ int run_range(sina_hip_ctx *c, const KmerRequest &r, const KmerRange &g, uint32_
     KmerLaunch l{c->qmask.as<uint8_t>(), c->k_qoff.as<uint64_t>() + q0, bq, max, max_qlen, g.path, g.big};
     if (run_kernels(c, l, true)) return 1;
     // (the kernels have finished: run_kernels waits for the heavy stream)
-    if ((!r.rk && (download(c, 9, c->k_out_ids.p, (size_t)bq * max * 4, s) || download(c, 10, c->k_out_scores.p, (size_t)bq * max * 4, s))) ||
+    if ((!r.rk && !r.keep && (download(c, 9, c->k_out_ids.p, (size_t)bq * max * 4, s) || download(c, 10, c->k_out_scores.p, (size_t)bq * max * 4, s))) ||
         download(c, 11, c->k_out_n.p, (size_t)bq * 4, s) || download(c, 0, c->k_tmp2.p, 8, s))
         return 1;
     SH_CHECK(wait_stream(c, s));
@@ -98,6 +105,12 @@ int run_range(sina_hip_ctx *c, const KmerRequest &r, const KmerRange &g, uint32_
     if (*overflow) return 0;
     if (g.path == kKmerLong) c->path_queries[kPathLong] += bq;
     if (g.big) c->path_queries[kPathBigSelect] += bq;
+    if (r.keep) {  // the range's select is final: its rows to their place in the call's, before the next range's select writes over them
+        SH_CHECK(hipMemcpyAsync(r.keep->d_ids + (size_t)q0 * max, c->k_out_ids.p, (size_t)bq * max * 4, hipMemcpyDeviceToDevice, s));
+        SH_CHECK(hipMemcpyAsync(r.keep->d_n + q0, c->k_out_n.p, (size_t)bq * 4, hipMemcpyDeviceToDevice, s));
+        memcpy(r.keep->h_n + q0, c->h_stage[11].p, (size_t)bq * 4);
+        return 0;
+    }
     if (r.rk) {  // the range's select is final: its candidates ranked, ids and lengths read where they lie
         uint32_t max_la = 0;
         for (uint32_t q = q0; q < q0 + bq; q++) max_la = std::max(max_la, r.qlen(q));
@@ -276,6 +289,17 @@ struct PackedMasks {
 };
 
 }  // namespace
+
+int kmer_rows_resident(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max, uint32_t *d_ids,
+                       uint32_t *d_n, uint32_t *h_n) {
+    if (index_ready(c)) return 1;
+    if (nq == 0 || max == 0 || max > c->st->n_refs) SH_FAIL("kmer_rows_resident: nothing to search, or more rows than references");
+    const KeepReq keep{d_ids, d_n, h_n};
+    KmerRequest r{qmask, qoff, nq, max, nullptr, nullptr, nullptr};
+    r.keep = &keep;
+    return kmer_topk_run(c, r, nq);
+}
+
 }  // namespace sina_hip
 
 using namespace sina_hip;

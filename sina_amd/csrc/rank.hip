@@ -1,6 +1,8 @@
 // Search-stage ranking on the GPU: rank_kernel, rank_merge_kernel + sina_hip_compare_rank,
 // sina_hip_upload_name_order, sina_hip_rank_stats; sina_hip_kmer_topk_rank (kmer_launch.hip) launches the same kernels on the
-// select's id rows.
+// select's id rows.  And the same ranking riding on an align call: rank_assembled_kernel,
+// rank_merge_assembled_kernel + sina_hip_align_rank, sina_hip_staged_rank, sina_hip_rank_inplace_stats, launched by
+// dp_launch.hip (launch_inplace_counts) over the words the device assembly left.
 //
 // What it computes: what search_filter does with a query's candidates after comparing them (host/search_filter.cpp): the
 // score (float)match / denom of every candidate, denom an integer chosen by the cover rule (cseq_comparator::score),
@@ -82,6 +84,69 @@ __device__ __forceinline__ void write_row(const RankArgs &a, uint32_t q, uint32_
     }
 }
 
+// What a wave has after its share of a chunk: its N best stored keys (topn_insert), whether a candidate had
+// denom == 0, and the volume it scored.  Every lane holds the same flags and counts.
+struct WaveBest {
+    uint64_t mine = 0;
+    bool flagged = false;
+    unsigned long long bases = 0;
+    uint32_t pairs = 0;
+};
+// The per-candidate loop of both rank kernels: candidates i0 + wave, i0 + wave + 4 .. below i1 of the query whose
+// tables are t, the id rows or lists at a.ids + c_base (no ids: every reference).
+__device__ __forceinline__ void rank_candidates(const RankArgs &a, const QueryTables &t, uint64_t c_base, uint32_t i0, uint32_t i1,
+                                                uint32_t lc_bit, int lane, int wave, WaveBest &wb) {
+    for (uint32_t i = i0 + wave; i < i1; i += kCT / 64) {
+        const uint32_t id = a.ids ? a.ids[c_base + i] : i;
+        const bool valid = id < a.n_refs;
+        const uint32_t *Bp = valid ? a.ref_ab + a.ref_off[id] : nullptr;
+        const uint32_t lb = valid ? (uint32_t)(a.ref_off[id + 1] - a.ref_off[id]) : 0u;
+        const sina_hip_match_counts m = classify_candidate(t, Bp, lb, valid, lc_bit, a.iupac, lane);
+        if (!valid) continue;
+        wb.pairs++;
+        wb.bases += lb;
+        const int32_t denom = cover_denominator(m, a.cover);  // (cseq_comparator::score: compare_dev.h)
+        if (denom == 0) {  // the host's 0 / 0
+            wb.flagged = true;
+            continue;
+        }
+        const float score = __fdiv_rn((float)m.match, (float)denom);
+        const uint64_t key = ((uint64_t)__float_as_uint(score) << 32) | a.name_rank[id];
+        topn_insert(wb.mine, key + 1, lane, a.N);
+    }
+}
+// The four waves' lists into one (s_keys: [kCT], all threads call): the place of this thread's key among them -- the
+// number of keys that beat it, equal keys: the earlier slot first --, or N for a lane that holds no place of its list.
+__device__ __forceinline__ uint32_t merged_place(uint64_t *s_keys, uint64_t mine, uint32_t tid, int lane, uint32_t N) {
+    s_keys[tid] = mine;
+    __syncthreads();
+    if (lane >= (int)N) return N;
+    uint32_t place = 0;
+    for (int w = 0; w < kCT / 64; w++)
+        for (uint32_t j = 0; j < N; j++) {
+            const uint32_t slot = (uint32_t)w * 64 + j;
+            const uint64_t o = s_keys[slot];
+            place += (o > mine || (o == mine && slot < tid)) ? 1u : 0u;
+        }
+    return place;
+}
+// One wave folds the chunks' key rows of query q (rank_merge_kernel and its assembled twin): lane i ends with place i
+__device__ __forceinline__ uint64_t merged_chunks(const RankArgs &a, uint32_t q, int lane) {
+    const uint64_t *rows = a.keys + (size_t)q * a.chunks * a.N;
+    const uint32_t total = a.chunks * a.N;
+    uint64_t mine = 0;
+    for (uint32_t base = 0; base < total; base += 64) {
+        const uint64_t v = base + lane < total ? rows[base + lane] : 0;
+        unsigned long long left = __ballot(v != 0);
+        while (left) {
+            const int j = __ffsll(left) - 1;
+            left &= left - 1;
+            topn_insert(mine, shfl64(v, j), lane, a.N);
+        }
+    }
+    return mine;
+}
+
 __global__ void __launch_bounds__(kCT) rank_kernel(RankArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint32_t s_tmp[8];
@@ -121,28 +186,12 @@ __global__ void __launch_bounds__(kCT) rank_kernel(RankArgs a) {
     const QueryTables t = build_query_tables(smem, s_tmp, s_scal, A, la, a.width, lc_bit);
     if (tid == 0) s_n = 0;
 
-    uint64_t mine = 0;
-    bool flagged = false;
-    unsigned long long bases = 0;
-    uint32_t pairs = 0;
-    for (uint32_t i = i0 + wave; i < i1; i += kCT / 64) {
-        const uint32_t id = a.ids ? a.ids[c_base + i] : i;
-        const bool valid = id < a.n_refs;
-        const uint32_t *Bp = valid ? a.ref_ab + a.ref_off[id] : nullptr;
-        const uint32_t lb = valid ? (uint32_t)(a.ref_off[id + 1] - a.ref_off[id]) : 0u;
-        const sina_hip_match_counts m = classify_candidate(t, Bp, lb, valid, lc_bit, a.iupac, lane);
-        if (!valid) continue;
-        pairs++;
-        bases += lb;
-        const int32_t denom = cover_denominator(m, a.cover);  // (cseq_comparator::score: compare_dev.h)
-        if (denom == 0) {  // the host's 0 / 0
-            flagged = true;
-            continue;
-        }
-        const float score = __fdiv_rn((float)m.match, (float)denom);
-        const uint64_t key = ((uint64_t)__float_as_uint(score) << 32) | a.name_rank[id];
-        topn_insert(mine, key + 1, lane, a.N);
-    }
+    WaveBest wb;
+    rank_candidates(a, t, c_base, i0, i1, lc_bit, lane, wave, wb);
+    const uint64_t mine = wb.mine;
+    const bool flagged = wb.flagged;
+    const unsigned long long bases = wb.bases;
+    const uint32_t pairs = wb.pairs;
     if (lane == 0) {
         if (flagged) atomicOr(&a.out_flag[q], 1u);
         if (pairs) {
@@ -152,16 +201,8 @@ __global__ void __launch_bounds__(kCT) rank_kernel(RankArgs a) {
     }
 
     // the four lists into one: a key's place is the number of keys that beat it (equal keys: the earlier slot first)
-    s_keys[tid] = mine;
-    __syncthreads();
-    if (lane < (int)a.N) {
-        uint32_t place = 0;
-        for (int w = 0; w < kCT / 64; w++)
-            for (uint32_t j = 0; j < a.N; j++) {
-                const uint32_t slot = (uint32_t)w * 64 + j;
-                const uint64_t o = s_keys[slot];
-                place += (o > mine || (o == mine && slot < tid)) ? 1u : 0u;
-            }
+    {
+        const uint32_t place = merged_place(s_keys, mine, tid, lane, a.N);
         if (place < a.N) {
             if (a.chunks == 1) {
                 write_row(a, q, place, mine);
@@ -181,24 +222,164 @@ __global__ void __launch_bounds__(kCT) rank_kernel(RankArgs a) {
 __global__ void __launch_bounds__(64) rank_merge_kernel(RankArgs a) {
     const uint32_t q = blockIdx.x;
     const int lane = threadIdx.x;
-    const uint64_t *rows = a.keys + (size_t)q * a.chunks * a.N;
-    const uint32_t total = a.chunks * a.N;
-    uint64_t mine = 0;
-    for (uint32_t base = 0; base < total; base += 64) {
-        const uint64_t v = base + lane < total ? rows[base + lane] : 0;
-        unsigned long long left = __ballot(v != 0);
-        while (left) {
-            const int j = __ffsll(left) - 1;
-            left &= left - 1;
-            topn_insert(mine, shfl64(v, j), lane, a.N);
-        }
-    }
+    const uint64_t mine = merged_chunks(a, q, lane);
     if (lane < (int)a.N) write_row(a, q, lane, mine);
     const uint32_t filled = __popcll(__ballot(lane < (int)a.N && mine != 0));
     if (lane == 0) a.out_n[q] = filled;
 }
 
+// ---- the same ranking where the device assembles: the query is what assemble_kernel has just left in
+// the launch range's out_pos, its candidates the id rows the call's k-mer search left on the device.  r.ids / r.row_n
+// point at the range's first row; r.q_ab, r.q_off, r.out_* and r.cnt are not used.
+struct RankAssembledArgs {
+    RankArgs r;
+    const QDesc *qd;
+    const sina_hip_align_out *out;
+    const uint32_t *out_pos;
+    uint32_t *rows;  // [n][kRankRowWords], zero before the launch: n, flags, 64 ids, 64 score bit patterns
+    uint32_t max_l;  // longest query of the range: the tables' mask bytes
+};
+constexpr uint32_t kRowRanked = 2u, kRowNan = 1u;  // flag bits of a row's word 1
+
+// Which queries of a range are ranked (the same for every thread of a workgroup): finished by the assembly -- a longer
+// one than max_l never is, and would overrun the mask bytes -- and with every base of the input kept: the candidates
+// come from the input's k-mers, the host searches with the aligned sequence's.
+__device__ __forceinline__ bool ranked_here(const RankAssembledArgs &a, uint32_t q) {
+    const sina_hip_align_out *o = a.out + q;
+    return o->status == 0 && o->assembled != 0 && o->n_out <= a.max_l && o->n_out == a.qd[q].L;
+}
+__device__ __forceinline__ void write_assembled(uint32_t *row, const RankArgs &r, uint32_t place, uint64_t stored) {
+    if (!stored) return;  // (the row was zero)
+    const uint64_t key = stored - 1;
+    row[2 + place] = r.name_inv[(uint32_t)key];
+    row[2 + kRankMaxResult + place] = (uint32_t)(key >> 32);
+}
+
+__global__ void __launch_bounds__(kCT) rank_assembled_kernel(RankAssembledArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ uint32_t s_tmp[8];
+    __shared__ uint32_t s_scal[3];
+    __shared__ uint32_t s_n;
+    __shared__ uint64_t s_keys[kCT];
+    const RankArgs &r = a.r;
+    const uint32_t q = blockIdx.x / r.chunks, ch = blockIdx.x % r.chunks, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    if (!ranked_here(a, q)) return;  // (its row stays zero: not ranked)
+    uint32_t *row = a.rows + (size_t)q * kRankRowWords;
+    const uint64_t c_base = (uint64_t)q * r.stride;
+    uint32_t n = r.row_n[q];
+    if (n == 0xFFFFFFFFu) n = 0;
+    if (n > r.stride) n = r.stride;
+    const uint32_t i0 = ch * r.chunk;
+    if (i0 >= n) {  // (the whole workgroup: nothing of this query falls into the chunk)
+        if (r.chunks == 1) {
+            if (tid == 0) atomicOr(&row[1], kRowRanked);  // ranked, no rows
+        } else if (tid < r.N) {
+            r.keys[((size_t)q * r.chunks + ch) * r.N + tid] = 0;
+        }
+        return;
+    }
+    const uint32_t i1 = r.chunk < n - i0 ? i0 + r.chunk : n;
+
+    const uint32_t lc_bit = r.filter_lc ? 0x10u : 0u;
+    const QueryTables t = build_query_tables(smem, s_tmp, s_scal, a.out_pos + a.qd[q].q_off, a.out[q].n_out, r.width, lc_bit);
+    if (tid == 0) s_n = 0;
+
+    WaveBest wb;
+    rank_candidates(r, t, c_base, i0, i1, lc_bit, lane, wave, wb);
+    if (lane == 0 && wb.flagged) atomicOr(&row[1], kRowNan);
+
+    const uint32_t place = merged_place(s_keys, wb.mine, tid, lane, r.N);
+    if (place < r.N) {
+        if (r.chunks == 1) {
+            write_assembled(row, r, place, wb.mine);
+            if (wb.mine) atomicAdd(&s_n, 1u);
+        } else {
+            r.keys[((size_t)q * r.chunks + ch) * r.N + place] = wb.mine;
+        }
+    }
+    if (r.chunks == 1) {
+        __syncthreads();
+        if (tid == 0) {
+            row[0] = s_n;
+            atomicOr(&row[1], kRowRanked);
+        }
+    }
+}
+
+// one wave per query: the chunks' key rows into the final row
+__global__ void __launch_bounds__(64) rank_merge_assembled_kernel(RankAssembledArgs a) {
+    const uint32_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (!ranked_here(a, q)) return;
+    uint32_t *row = a.rows + (size_t)q * kRankRowWords;
+    const uint64_t mine = merged_chunks(a.r, q, lane);
+    if (lane < (int)a.r.N) write_assembled(row, a.r, lane, mine);
+    const uint32_t filled = __popcll(__ballot(lane < (int)a.r.N && mine != 0));
+    if (lane == 0) {
+        row[0] = filled;
+        atomicOr(&row[1], kRowRanked);
+    }
+}
+
+// the grid of a launch range of bq queries with up to `stride` candidates each (SINA_HIP_TEST=rank_chunk=N applies)
+RankPlan rank_assembled_plan(const sina_hip_ctx *c, uint32_t bq, uint32_t stride) {
+    const std::string chunk_knob = test_knob("rank_chunk");
+    const uint32_t forced = chunk_knob.empty() ? 0u : std::max(1u, (uint32_t)strtoul(chunk_knob.c_str(), nullptr, 10));
+    return rank_plan(bq, stride, (uint32_t)c->n_cu, kRankChunkFloor, forced);
+}
+
 }  // namespace
+
+static_assert(RankRider::row_bytes == 4 * (size_t)kRankRowWords, "ctx.h and rank_plan.h disagree on the row");
+
+// (before the range's launches: it may allocate) the key scratch of a range with few queries
+int reserve_rank_assembled(sina_hip_ctx *c, uint32_t bq) {
+    if (!c->inplace[kInplaceRank].active || bq == 0) return 0;
+    const RankPlan pl = rank_assembled_plan(c, bq, c->rider.stride);
+    return c->r_keys.reserve(std::max<uint64_t>(rank_scratch_bytes(bq, pl, c->rider.N), 8));
+}
+
+int launch_rank_assembled(sina_hip_ctx *c, const BtArgs &b, uint32_t q_base, uint32_t max_l, uint32_t *rows, hipStream_t s) {
+    if (b.nq == 0) return 0;
+    const RankRider &rr = c->rider;
+    const size_t lds = compare_table_bytes(b.width, max_l);
+    if (lds > kCompareMaxLds) SH_FAIL_LIMIT("align_rank: alignment too wide for the device comparison");  // (align_call::begin_rank asked)
+    const RankPlan pl = rank_assembled_plan(c, b.nq, rr.stride);
+    if (pl.chunk == 0) SH_FAIL("align_rank: too many queries for one launch");
+    if (c->r_keys.cap < rank_scratch_bytes(b.nq, pl, rr.N)) SH_FAIL("align_rank: key scratch not reserved");
+    RankAssembledArgs a{};
+    a.r.ref_ab = c->st->ref_ab.as<uint32_t>();
+    a.r.ref_off = c->st->ref_off.as<uint64_t>();
+    a.r.ids = rr.ids.as<uint32_t>() + (size_t)q_base * rr.stride;
+    a.r.row_n = rr.n.as<uint32_t>() + q_base;
+    a.r.name_rank = c->st->name_rank.as<uint32_t>();
+    a.r.name_inv = c->st->name_inv.as<uint32_t>();
+    a.r.keys = c->r_keys.as<uint64_t>();
+    a.r.width = b.width;
+    a.r.n_refs = c->st->n_refs;
+    a.r.stride = rr.stride;
+    a.r.chunk = pl.chunk;
+    a.r.chunks = pl.chunks;
+    a.r.N = rr.N;
+    a.r.iupac = rr.iupac;
+    a.r.filter_lc = rr.filter_lc;
+    a.r.cover = rr.cover;
+    a.qd = b.qd;
+    a.out = b.out;
+    a.out_pos = b.out_pos;
+    a.rows = rows;
+    a.max_l = max_l;
+    if (allow_full_lds(reinterpret_cast<const void *>(rank_assembled_kernel))) return 1;
+    SH_CHECK(hipMemsetAsync(rows, 0, RankRider::row_bytes * b.nq, s));
+    hipLaunchKernelGGL(rank_assembled_kernel, dim3((unsigned)((uint64_t)b.nq * pl.chunks)), dim3(kCT), lds, s, a);
+    SH_CHECK(hipGetLastError());
+    if (pl.chunks > 1) {
+        hipLaunchKernelGGL(rank_merge_assembled_kernel, dim3(b.nq), dim3(64), 0, s, a);
+        SH_CHECK(hipGetLastError());
+    }
+    return 0;
+}
 
 // nq queries (packed aligned bases d_qab at d_qoff[q], device memory) against their candidates -- d_ids + d_coff
 // (lists), d_ids + d_rown with `stride` (rows), or neither (every reference) --, at most M per query: the N best of each
@@ -379,4 +560,47 @@ extern "C" int sina_hip_compare_rank(sina_hip_ctx *c, const uint32_t *q_ab, cons
 extern "C" int sina_hip_rank_stats(sina_hip_ctx *c, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches) {
     if (!c || !kernel_ms || !pairs || !cand_bases || !launches) SH_FAIL("rank_stats: null argument");
     return read_use(c, kUseRank, kernel_ms, pairs, cand_bases, launches);
+}
+
+// ---- the ranking that rides on an align call (rank_assembled_kernel): its switch, rows and counters
+extern "C" int sina_hip_align_rank(sina_hip_ctx *c, int on, unsigned k, int nofast, uint32_t kmer_candidates, int iupac_rule,
+                                    int filter_lowercase, int cover_rule, uint32_t max_result) {
+    if (!c) SH_FAIL("align_rank: null ctx");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!on) {
+        c->inplace[kInplaceRank].on = false;
+        return 0;
+    }
+    // (the rules alone: what the store lacks never fails a call -- the align calls then run as without the switch)
+    if (iupac_rule < 0 || iupac_rule > 2) SH_FAIL("align_rank: unknown iupac rule");
+    if (cover_rule < 0 || cover_rule > SINA_CMP_COVER_NOGAP) SH_FAIL("align_rank: unknown cover rule");
+    if (max_result < 1 || max_result > kRankMaxResult) SH_FAIL("align_rank: max_result outside 1..64");
+    if (k < 1 || k > 12) SH_FAIL("align_rank: k must be in 1..12");
+    if (kmer_candidates == 0) SH_FAIL("align_rank: kmer_candidates must be at least 1");
+    if (kmer_big_select(c->st->have_refs ? std::min(kmer_candidates, std::max(c->st->n_refs, 1u)) : kmer_candidates))
+        SH_FAIL_LIMIT("align_rank: more than 4096 candidates per query");
+    RankRider &rr = c->rider;
+    rr.k = k;
+    rr.nofast = nofast ? 1u : 0u;
+    rr.cands = kmer_candidates;
+    rr.iupac = iupac_rule;
+    rr.filter_lc = filter_lowercase ? 1 : 0;
+    rr.cover = cover_rule;
+    rr.N = max_result;
+    c->inplace[kInplaceRank].on = true;
+    return 0;
+}
+
+extern "C" const uint32_t *sina_hip_staged_rank(sina_hip_ctx *c) {
+    if (!c) {
+        set_error("staged_rank: null ctx");
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    return c->inplace[kInplaceRank].staged();
+}
+
+extern "C" int sina_hip_rank_inplace_stats(sina_hip_ctx *c, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches) {
+    if (!c || !kernel_ms || !sequences || !pairs || !launches) SH_FAIL("rank_inplace_stats: null argument");
+    return read_use(c, kUseRankInplace, kernel_ms, sequences, pairs, launches);
 }

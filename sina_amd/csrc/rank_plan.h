@@ -16,6 +16,9 @@ constexpr uint32_t kRankChunkFloor = 128;
 constexpr uint32_t kRankWgPerCu = 4;
 constexpr uint32_t kRankMaxResult = 64;                // rows per query: one per lane of a wave
 constexpr uint64_t kRankGridMax = 0x7FFFFFFFull;       // workgroups of a one-dimensional grid
+// words of a query's row where the ranking rides on an align call (rank_assembled_kernel): the number of rows, the
+// flags, then kRankMaxResult ids and as many score bit patterns -- fixed width, whatever max_result is
+constexpr uint32_t kRankRowWords = 2 + 2 * kRankMaxResult;
 
 struct RankPlan {
     uint32_t chunk;   // candidates per workgroup (the last chunk of a query may be short); 0: the launch cannot be cut

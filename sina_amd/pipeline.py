@@ -99,6 +99,7 @@ def load_host():
     H.sina_host_store_pair_stats.argtypes = [C.c_char_p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_store_pair_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p]
     H.sina_host_store_identity_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_store_search_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_store_assemble_stats.argtypes = [C.c_char_p] + [capi.u64p] * 6
     H.sina_host_pair_score.argtypes =[C.c_char_p, capi.u32p, C.c_uint32, capi.f32p, capi.u32p]
     H.sina_host_pair_scores_packed.argtypes = [capi.u32p, capi.u64p, C.c_uint32, capi.u32p, C.c_uint32, capi.f32p, capi.u32p,
@@ -292,6 +293,16 @@ class Store:
         took their identity from the row their align call brought back, and the in-place kernel's assembled queries,
         (query, member) pairs, launches and time on the store's contexts -- between runs, like pair_inplace_stats()."""
         d = self._counters(self.H.sina_host_store_identity_inplace_stats, capi.u64_fields("trays") + capi.KERNEL_MS +
+                           capi.u64_fields("sequences", "pairs", "launches"))
+        d["kernel_ms"] = d.pop("kernel_ms")  # (the dict ends with it)
+        return d
+
+    def search_inplace_stats(self):
+        """The aligner's device-search on this store so far: dict(trays, sequences, pairs, launches, kernel_ms) -- trays
+        whose search rows came from the row their align call brought back, and the in-place ranking's ranked queries,
+        (query, candidate) pairs, launch ranges and time on the store's contexts -- between runs, like
+        identity_inplace_stats()."""
+        d = self._counters(self.H.sina_host_store_search_inplace_stats, capi.u64_fields("trays") + capi.KERNEL_MS +
                            capi.u64_fields("sequences", "pairs", "launches"))
         d["kernel_ms"] = d.pop("kernel_ms")  # (the dict ends with it)
         return d

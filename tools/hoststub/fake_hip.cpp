@@ -134,6 +134,14 @@ int sina_hip_identity_inplace_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, 
     *seqs = *pairs = *launches = 0;
     return 0;
 }
+// (likewise: the switch is taken, an align call of the stub ranks nothing)
+int sina_hip_align_rank(sina_hip_ctx *, int, unsigned, int, uint32_t, int, int, int, uint32_t) { return 0; }
+const uint32_t *sina_hip_staged_rank(sina_hip_ctx *) { return nullptr; }
+int sina_hip_rank_inplace_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, uint64_t *pairs, uint64_t *launches) {
+    *ms = 0;
+    *seqs = *pairs = *launches = 0;
+    return 0;
+}
 // (the stub assembles nothing: no shift log, nothing counted)
 const uint32_t *sina_hip_staged_shift_log(sina_hip_ctx *) { return nullptr; }
 int sina_hip_assemble_stats(sina_hip_ctx *, uint64_t *queries, uint64_t *assembled, uint64_t *shifted_queries, uint64_t *shifted_runs) {

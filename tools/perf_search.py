@@ -1,13 +1,18 @@
-"""The search stage in a pipeline, with and without `device-rank`, and the comparison kernel alone.
+"""The search stage in a pipeline, without and with `device-rank` and with the aligner's `device-search`
+(3.5d), and the comparison kernel alone.
 
     python tools/perf_search.py stage [--queries 9216] [--refs 100000] [--search-all] [--rounds 3] [--out FILE]
 
 runs famfinder -> aligner -> search_filter (lca-fields set) over the bench's world in ONE process: a warm-up pass with
-each setting, then `--rounds` rounds that alternate device-rank off and on.  Per run one JSON line: the stage's wall
-seconds (Pipeline.search_seconds()), its host phases (SINA_HOST_PROFILE), the kernels' milliseconds by events with their
-algorithmic bytes (4 B per candidate base) over that time, and the bytes the stage's device calls copy each way
-(computed from the entries' contracts: ids, scores and counters per candidate off; rows per query on).  All search
-results of the two settings are compared; a last line says whether they are identical.  --out appends the raw lines.
+each setting, then `--rounds` rounds that alternate the three settings: device-rank off, device-rank on, and device-rank
+on with the aligner's device-search and device-shift (the rows come back with the alignments; the stage's own path
+takes the trays the device did not rank).  Per run one JSON line: the pipeline's sequences per second and busy host
+cores, the stage's wall seconds (Pipeline.search_seconds()), its host phases (SINA_HOST_PROFILE), the kernels'
+milliseconds by events with their algorithmic bytes (4 B per candidate base) over that time, and the bytes the stage's
+device calls copy each way (computed from the entries' contracts: ids, scores and counters per candidate off; rows per
+query on; in place nothing up and a 520-byte row per query down, plus the rest's share of the device-rank route).  All
+search results of the three settings are compared; a last line says whether they are identical.  --out appends the raw
+lines.
 
     python tools/perf_search.py [nq] [n_refs]
 
@@ -119,14 +124,16 @@ def stage(argv):
                 out.append((r["search_ids"].tobytes(), r["search_scores"].tobytes(), pl.attr(q, "nearest_slv"), pl.attr(q, "lca_tax_slv")))
         return out
 
-    def run(on, tag):
+    def run(on, tag, in_place=False):
         pl._set("search", "device-rank", bool(on))
+        pl._set("aligner", "device-search", bool(in_place))
+        pl._set("aligner", "device-shift", bool(in_place))
         pl.profile(reset=True)
-        s0, r0 = store.stats(), store.rank_stats()
-        t = time.time()
+        s0, r0, i0 = store.stats(), store.rank_stats(), store.search_inplace_stats()
+        t, cpu = time.time(), time.process_time()
         pl.run(qs.mask, qs.off, batch=a.batch, inflight=a.inflight)
-        wall = time.time() - t
-        s1, r1 = store.stats(), store.rank_stats()
+        wall, cpu = time.time() - t, time.process_time() - cpu
+        s1, r1, i1 = store.stats(), store.rank_stats(), store.search_inplace_stats()
         prof = {}
         for ln in pl.profile(reset=True).splitlines():
             m = re.match(r"^(.*?)\s+([0-9.]+) s\s+[0-9]+ calls$", ln)
@@ -135,14 +142,23 @@ def stage(argv):
         res = results()
         searched = sum(r is not None for r in res)
         pairs_off = searched * (refs.n if a.search_all else kmer_cand)
-        rec = dict(tag=tag, device_rank=bool(on), queries=qs.n, searched=searched, refs=refs.n, search_all=bool(a.search_all),
-                   wall_s=wall, search_seconds=pl.search_seconds(), phases=prof)
+        rec = dict(tag=tag, device_rank=bool(on), device_search=bool(in_place), queries=qs.n, searched=searched, refs=refs.n,
+                   search_all=bool(a.search_all), wall_s=wall, sequences_per_s=qs.n / wall, busy_host_cores=cpu / wall,
+                   search_seconds=pl.search_seconds(), phases=prof)
+        trays = i1["trays"] - i0["trays"]
+        if in_place:
+            # nothing goes up again for a tray ranked in place; its slot's 520-byte row came down with the alignment
+            rec.update(in_place_trays=trays, rank_inplace_kernel_ms=i1["kernel_ms"] - i0["kernel_ms"],
+                       rank_inplace_launches=i1["launches"] - i0["launches"], rank_inplace_sequences=i1["sequences"] - i0["sequences"],
+                       rank_inplace_pairs=i1["pairs"] - i0["pairs"], in_place_bytes_up=0,
+                       in_place_bytes_down=520 * (i1["sequences"] - i0["sequences"]))
         if on:
             ms, bases = r1["kernel_ms"] - r0["kernel_ms"], r1["cand_bases"] - r0["cand_bases"]
             rec.update(ranked=r1["ranked"] - r0["ranked"], fallen_back=r1["fallen_back"] - r0["fallen_back"],
                        rank_kernel_ms=ms, rank_launches=r1["launches"] - r0["launches"], pairs=r1["pairs"] - r0["pairs"],
                        # up: the queries' packed bases; down: max_result ids and scores, a count and a flag per query
-                       bytes_up=4 * int(qs.off[-1]), bytes_down=searched * (8 * n_best + 8))
+                       # (in place: only the trays the stage's own path still takes -- their share of the bases)
+                       bytes_up=4 * int(qs.off[-1]) * (searched - trays) // max(searched, 1), bytes_down=(searched - trays) * (8 * n_best + 8))
         else:
             ms, bases = s1["compare_ms"] - s0["compare_ms"], s1["compare_bases"] - s0["compare_bases"]
             rec.update(compare_kernel_ms=ms, compare_launches=s1["compare_launches"] - s0["compare_launches"], pairs=pairs_off,
@@ -155,9 +171,11 @@ def stage(argv):
 
     base = run(False, "warm-up")
     same = run(True, "warm-up") == base
+    same = (run(True, "warm-up", in_place=True) == base) and same
     for rnd in range(a.rounds):
         same = (run(False, "round %d" % rnd) == base) and same
         same = (run(True, "round %d" % rnd) == base) and same
+        same = (run(True, "round %d" % rnd, in_place=True) == base) and same
     emit(dict(tag="results", identical_between_settings=bool(same), queries_with_results=sum(r is not None for r in base)))
     if a.out:
         with open(a.out, "a") as f:
