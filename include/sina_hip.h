@@ -209,6 +209,48 @@ int sina_hip_kmer_topk_match(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint
                              uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint16_t *out_match);
 int sina_hip_match_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches);
 
+/* ------------------------------------------------------------- famfinder's filter cascade (device-cascade)
+ * The cascade of src/famfinder.cpp:497-612 over ranked candidates, restated on the device: candidates
+ * are taken in their list's order; one is removed when its reference has fewer than fs_min_len bases, when its id is
+ * in the query's self list (--fs-leave-query-out), or -- only where fs_msc_max < 1 --
+ * (float)match / (float)(bases of the query) > fs_msc_max (0 for a query without bases); otherwise by the stateful
+ * test over have / have_full / have_cover_left / have_cover_right, the score test being `score < fs_msc` (sic).
+ *
+ * A query's row is 2 + 2 K 32-bit words, K = max(fs_min, fs_max) + fs_req_full + 2 * fs_cover_gene:
+ *   word 0 the number kept; word 1 flags (bit 0: the cascade has enough; bit 1: the list was empty); K ids; K score
+ *   bit patterns; entries beyond the number kept are zero.
+ * sina_hip_family_row_words gives 2 + 2 K; a rule whose K exceeds 1024 is refused as a limit, by every entry here.
+ *
+ * sina_hip_family_cascade: the cascade over the caller's lists against the uploaded references.
+ *   cand_ids, cand_scores, cand_match : query q's candidates at cand_off[q] .. cand_off[q + 1] - 1 (sub-ranges of larger
+ *                                       offset arrays included); cand_match may be NULL when fs_msc_max >= 1 and is
+ *                                       not read then
+ *   q_bases   : [nq] bases of every query
+ *   self_ids, self_off : the queries' self lists, like the candidates; both NULL: no leave-out
+ *   out_rows  : [nq][2 + 2 K]
+ * sina_hip_kmer_topk_family: sina_hip_kmer_topk_match's search with the cascade behind it, over the select's rows where
+ * they lie in device memory; nothing but the rows comes to the host.  With fs_msc_max >= 1 no match count is launched
+ * and the queries' columns are not checked.
+ * Refused with a message, before anything runs and with out_rows untouched: a null argument, a reference id or a self
+ * id out of range, and for fs_msc_max < 1 a query whose columns do not ascend strictly; as a limit: a rule over the
+ * cap, and for fs_msc_max < 1 an alignment too wide for the match count's table.
+ *
+ * sina_hip_family_stats: the cascade kernel's own time and volume on this context since init / fork: queries,
+ * candidates their lists held, candidates the kernel's steps covered before it stopped, launches. */
+typedef struct sina_hip_family_rule {
+    uint32_t fs_min, fs_max, fs_req_full, fs_full_len, fs_min_len, fs_cover_gene;
+    float fs_msc, fs_msc_max;
+} sina_hip_family_rule;
+int sina_hip_family_row_words(const sina_hip_family_rule *r, uint32_t *words);
+int sina_hip_family_cascade(sina_hip_ctx *ctx, const uint32_t *cand_ids, const float *cand_scores, const uint16_t *cand_match,
+                            const uint64_t *cand_off, const uint32_t *q_bases, uint32_t nq, const sina_hip_family_rule *r,
+                            const uint32_t *self_ids, const uint64_t *self_off, uint32_t *out_rows);
+int sina_hip_kmer_topk_family(sina_hip_ctx *ctx, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t max,
+                              const sina_hip_family_rule *r, const uint32_t *self_ids, const uint64_t *self_off,
+                              uint32_t *out_rows);
+int sina_hip_family_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *queries, uint64_t *candidates_listed,
+                          uint64_t *candidates_scanned, uint64_t *launches);
+
 /* ------------------------------------------------------------- search stage: score and rank on the device
  * What search_filter::operator() does with the counters above (src/search_filter.cpp:271-331): the score
  * (float)match / denom of every candidate, denom the integer the cover rule picks (cseq_comparator::score,

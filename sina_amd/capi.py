@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "sina_hip_kmer_topk_any", "sina_hip_kmer_scores_any", "sina_hip_long_queries", "sina_hip_big_select_queries",
     "sina_hip_align_graphs_wsets", "sina_hip_align_families_wsets",
     "sina_hip_match_count", "sina_hip_kmer_topk_match", "sina_hip_match_stats",
+    "sina_hip_family_row_words", "sina_hip_family_cascade", "sina_hip_kmer_topk_family", "sina_hip_family_stats",
     "sina_hip_upload_name_order", "sina_hip_compare_rank", "sina_hip_kmer_topk_rank", "sina_hip_rank_stats",
     "sina_hip_upload_pairs", "sina_hip_pair_counts", "sina_hip_pair_stats",
     "sina_hip_align_count_pairs", "sina_hip_staged_pair_counts", "sina_hip_pair_inplace_stats",
@@ -48,6 +49,29 @@ SHIFT_LOG = 32
 
 # include/sina_hip.h, sina_hip_staged_rank: words of a query's row
 RANK_ROW_WORDS = 130
+
+# csrc/family_plan.h: the most entries a rule's family may have on the device
+FAMILY_MAX_K = 1024
+
+
+class FamilyRule(C.Structure):
+    """sina_hip_family_rule: famfinder's options the cascade reads; the defaults are famfinder's."""
+    _fields_ = [("fs_min", C.c_uint32), ("fs_max", C.c_uint32), ("fs_req_full", C.c_uint32), ("fs_full_len", C.c_uint32),
+                ("fs_min_len", C.c_uint32), ("fs_cover_gene", C.c_uint32), ("fs_msc", C.c_float), ("fs_msc_max", C.c_float)]
+
+    def __init__(self, fs_min=40, fs_max=40, fs_req_full=1, fs_full_len=1400, fs_min_len=150, fs_cover_gene=0, fs_msc=0.7,
+                 fs_msc_max=2.0):
+        super().__init__(fs_min, fs_max, fs_req_full, fs_full_len, fs_min_len, fs_cover_gene, fs_msc, fs_msc_max)
+
+    @property
+    def K(self):
+        return max(self.fs_min, self.fs_max) + self.fs_req_full + 2 * self.fs_cover_gene
+
+    @property
+    def row_words(self):
+        """2 + 2 K (the mirror of sina_hip_family_row_words, which also refuses K > FAMILY_MAX_K)."""
+        return 2 + 2 * self.K
+
 
 # include/sina_hip.h: SINA_CMP_COVER_*, in CMP_COVER_TYPE's order
 COVER_RULES = ("abs", "query", "target", "overlap", "all", "average", "min", "max", "nogap")
@@ -163,6 +187,11 @@ def load():
     L.sina_hip_match_count.argtypes = [vp, u32p, u64p, C.c_uint32, u32p, u64p, u16p]
     L.sina_hip_kmer_topk_match.argtypes = [vp, u32p, u64p, C.c_uint32, C.c_uint32, u32p, f32p, u32p, u16p]
     L.sina_hip_match_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
+    rulep = C.POINTER(FamilyRule)
+    L.sina_hip_family_row_words.argtypes = [rulep, u32p]
+    L.sina_hip_family_cascade.argtypes = [vp, u32p, f32p, u16p, u64p, u32p, C.c_uint32, rulep, u32p, u64p, u32p]
+    L.sina_hip_kmer_topk_family.argtypes = [vp, u32p, u64p, C.c_uint32, C.c_uint32, rulep, u32p, u64p, u32p]
+    L.sina_hip_family_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p, u64p]
     L.sina_hip_upload_name_order.argtypes = [vp, u32p, C.c_uint32]
     L.sina_hip_compare_rank.argtypes = [vp, u32p, u64p, C.c_uint32, u32p, u64p, C.c_int, C.c_int, C.c_int, C.c_uint32, u32p, f32p,
                                         u32p, u32p]
@@ -493,6 +522,53 @@ class Context:
     def match_stats(self):
         """The match-count kernel on this context so far: dict(kernel_ms, pairs, cand_bases, launches)."""
         return self._counters(self.L.sina_hip_match_stats, KERNEL_MS + u64_fields("pairs", "cand_bases", "launches"))
+
+    def family_row_words(self, rule):
+        """Words of a query's row under `rule` (FamilyRule): 2 + 2 K; a rule over the cap raises (a limit)."""
+        w = C.c_uint32(0)
+        self._check(self.L.sina_hip_family_row_words(C.byref(rule), C.byref(w)))
+        return int(w.value)
+
+    @staticmethod
+    def _self_lists(self_ids, self_off):
+        if self_ids is None:
+            return None, None, None, None
+        ids = _c(np.concatenate([np.asarray(self_ids, np.uint32), np.zeros(1, np.uint32)]), np.uint32)   # (never empty)
+        off = _c(self_off, np.uint64)
+        return ids, off, _ptr(ids, u32p), _ptr(off, u64p)
+
+    def family_cascade(self, cand_ids, cand_scores, cand_match, cand_off, q_bases, rule, self_ids=None, self_off=None):
+        """Famfinder's filter cascade over the caller's ranked lists: uint32 [nq, 2 + 2 K] rows (kept, flags, K ids,
+        K score bit patterns).  cand_match: None where rule.fs_msc_max >= 1."""
+        cand_off = _c(cand_off, np.uint64)
+        nq = len(cand_off) - 1
+        ids = _c(np.concatenate([np.asarray(cand_ids, np.uint32), np.zeros(1, np.uint32)]), np.uint32)
+        sc = _c(np.concatenate([np.asarray(cand_scores, np.float32), np.zeros(1, np.float32)]), np.float32)
+        mt = None if cand_match is None else _c(np.concatenate([np.asarray(cand_match, np.uint16), np.zeros(1, np.uint16)]), np.uint16)
+        qb = _c(np.concatenate([np.asarray(q_bases, np.uint32), np.zeros(1, np.uint32)]), np.uint32)
+        keep = self._self_lists(self_ids, self_off)
+        rows = np.zeros((nq, rule.row_words), np.uint32)
+        self._check(self.L.sina_hip_family_cascade(self.h, _ptr(ids, u32p), _ptr(sc, f32p), None if mt is None else _ptr(mt, u16p),
+                                                   _ptr(cand_off, u64p), _ptr(qb, u32p), nq, C.byref(rule), keep[2], keep[3],
+                                                   _ptr(rows, u32p) if rows.size else None))
+        return rows
+
+    def kmer_topk_family(self, q_ab, q_off, mx, rule, self_ids=None, self_off=None):
+        """kmer_topk_match's search with the cascade behind it, on the device: uint32 [nq, 2 + 2 K] rows."""
+        q_ab = _c(np.concatenate([np.asarray(q_ab, np.uint32), np.zeros(1, np.uint32)]), np.uint32)
+        q_off = _c(q_off, np.uint64)
+        nq = len(q_off) - 1
+        keep = self._self_lists(self_ids, self_off)
+        rows = np.zeros((nq, rule.row_words), np.uint32)
+        self._check(self.L.sina_hip_kmer_topk_family(self.h, _ptr(q_ab, u32p), _ptr(q_off, u64p), nq, mx, C.byref(rule),
+                                                     keep[2], keep[3], _ptr(rows, u32p) if rows.size else None))
+        return rows
+
+    def family_stats(self):
+        """The cascade kernel on this context so far: dict(kernel_ms, queries, candidates_listed, candidates_scanned,
+        launches)."""
+        return self._counters(self.L.sina_hip_family_stats,
+                              KERNEL_MS + u64_fields("queries", "candidates_listed", "candidates_scanned", "launches"))
 
     def upload_name_order(self, rank):
         """rank[id] = position of reference id's name in ascending byte-wise order (a permutation of 0..n_refs-1)."""

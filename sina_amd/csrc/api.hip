@@ -459,6 +459,7 @@ int sina_hip_upload_refs(sina_hip_ctx *c, const uint32_t *ab, const uint64_t *of
     c->st->total_bases = total;
     c->st->have_refs = true;
     c->st->have_name_order = false;  // (sina_hip_upload_name_order: the order belonged to the references before)
+    c->st->fam_meta_ready.store(false, std::memory_order_release);  // (family.hip: rebuilt by the next cascade)
     return 0;
 }
 
@@ -505,6 +506,7 @@ int sina_hip_store_alloc_like(sina_hip_ctx *c, sina_hip_store_view *v) {
     c->st->n_postings = v->n_postings;
     c->st->have_refs = c->st->have_index = true;
     c->st->have_name_order = false;
+    c->st->fam_meta_ready.store(false, std::memory_order_release);
     c->st->dense_ready = false;  // (the index arrives by broadcast after this call: built by the first search)
     {   // re-read from the device, once, after the broadcast filled it (ensure_ref_off_host)
         std::lock_guard<std::mutex> alk(c->st->aux_mu);

@@ -32,6 +32,10 @@ struct sina_hip_store {
     // every reference's name in ascending order, and its inverse; forgotten when the references change
     sina_hip::DevBuf name_rank, name_inv;
     bool have_name_order = false;
+    // The references' size, first and last column for the family cascade (family.hip): u32 [n_refs][3], built by the
+    // first cascade after the references changed, under aux_mu
+    sina_hip::DevBuf fam_meta;
+    std::atomic<bool> fam_meta_ready{false};
     // The helix map for the base-pair count (pairs.hip, sina_hip_upload_pairs): (column, partner) of every paired
     // column, ascending in the column; n_pair_ent == 0: no map.  Kept when the references change (it describes columns)
     sina_hip::DevBuf pair_ent;
@@ -118,17 +122,19 @@ namespace sina_hip {
 //   kUsePairsInplace       sequences  --                 sina_hip_pair_inplace_stats
 //   kUseIdentityInplace    sequences  pairs              sina_hip_identity_inplace_stats
 //   kUseRankInplace        sequences  pairs              sina_hip_rank_inplace_stats
+//   kUseFamily             listed     scanned            sina_hip_family_stats (c: queries)
 struct KernelUse {
     double ms = 0;
-    uint64_t a = 0, b = 0, launches = 0;
-    void add(double ms_, uint64_t a_, uint64_t b_, uint64_t launches_) {  // (by the context's caller, who holds its mutex)
+    uint64_t a = 0, b = 0, launches = 0, c = 0;
+    void add(double ms_, uint64_t a_, uint64_t b_, uint64_t launches_, uint64_t c_ = 0) {  // (by the context's caller, who holds its mutex)
         ms += ms_;
         a += a_;
         b += b_;
         launches += launches_;
+        c += c_;
     }
 };
-enum kernel_use { kUseMatch, kUseRank, kUsePairs, kUsePairsInplace, kUseIdentityInplace, kUseRankInplace, kNumKernelUse };
+enum kernel_use { kUseMatch, kUseRank, kUsePairs, kUsePairsInplace, kUseIdentityInplace, kUseRankInplace, kUseFamily, kNumKernelUse };
 // queries a path off the fast one has taken on a context (sina_hip_ctx::path_queries; sina_hip_wide_queries,
 // sina_hip_long_queries, sina_hip_big_select_queries): the wide DP kernel, the long k-mer count kernel, the big select
 enum slow_path { kPathWide, kPathLong, kPathBigSelect, kNumSlowPaths };
@@ -259,6 +265,9 @@ struct sina_hip_ctx {
     // the rank kernel (rank.hip): the chunks' key rows, the final rows on their way to the host, the flags and the
     // volume counters the kernel keeps
     sina_hip::DevBuf r_keys, r_ids, r_scores, r_n, r_flag, r_cnt;
+    // the family cascade (family.hip): a launch's rows, its counter of scanned candidates, the call's self lists and,
+    // for caller-given lists, their scores (the ids borrow s_cand, the counts m_out, the lengths m_n, the offsets s_qoff)
+    sina_hip::DevBuf f_rows, f_cnt, f_self_ids, f_self_off, f_scores;
     // (the pair-count kernel, pairs.hip, borrows s_qab, s_qoff and s_out)
     // the counts that ride on an align call: [n][6] pair counters in 24 bytes, [n][2] identity words in 8
     sina_hip::InplaceCount inplace[sina_hip::kNumInplace] = {{24, sina_hip::kUsePairsInplace, 12},
@@ -277,7 +286,7 @@ struct sina_hip_ctx {
 
     size_t lds_budget = 0;  // LDS per DP workgroup; 0 = what keeps the register-limited occupancy (dp_default_lds_budget)
 
-    static constexpr int kNumScratch = 54;
+    static constexpr int kNumScratch = 59;
     static_assert(kNumScratch <= 64, "sina_hip_store::cap_hint is too short");
     void scratch(sina_hip::DevBuf **all) {
         sina_hip::DevBuf *list[kNumScratch] = {&qd, &rec, &node_pos, &pred, &succ_minpos, &qmask, &spill, &res,
@@ -287,7 +296,8 @@ struct sina_hip_ctx {
                                                &s_qab, &s_qoff, &s_cand, &s_coff, &s_out, &edge, &prof16, &self16, &rgain,
                                                &scout, &scout_u, &wset, &m_out, &m_n, &r_keys, &r_ids, &r_scores, &r_n, &r_flag,
                                                &r_cnt, &inplace[sina_hip::kInplacePairs].rows, &inplace[sina_hip::kInplaceIdentity].rows, &pred4,
-                                               &inplace[sina_hip::kInplaceRank].rows, &rider.ids, &rider.n};
+                                               &inplace[sina_hip::kInplaceRank].rows, &rider.ids, &rider.n, &f_rows, &f_cnt, &f_self_ids,
+                                               &f_self_off, &f_scores};
         for (int i = 0; i < kNumScratch; i++) all[i] = list[i];
     }
     void publish_hints() {  // after a call: remember how big my buffers had to be
@@ -367,6 +377,7 @@ struct sina_hip_ctx {
             st->name_rank.release();
             st->name_inv.release();
             st->pair_ent.release();
+            st->fam_meta.release();
             for (auto &pl : st->tb_pool.plane) pl.release();
             delete st;
         }
@@ -768,6 +779,23 @@ int match_launch(sina_hip_ctx *c, const uint32_t *d_qab, const uint64_t *d_qoff,
                  const uint32_t *d_n, uint32_t stride, uint16_t *d_out, const uint32_t *h_ids, const uint32_t *h_n);
 // fails unless every query has at most 65535 bases in strictly ascending columns
 int match_check_queries(const char *who, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq);
+}  // namespace sina_hip
+
+namespace sina_hip {
+// ---- the family cascade (family.hip).  family_rule_plan: the rule's rows and grid, or a limit error for a rule over
+// the cap.  family_launch: nq queries' candidates d_ids / d_scores / d_match[q * stride + i], i < d_n[q] (0xFFFFFFFF = 0;
+// d_match is read only where the rule's fs_msc_max < 1), their base counts as differences of d_qoff, their self lists
+// (device memory, or null) -- rows into out_rows [nq][plan.row_words] on the host; queued behind what the context's
+// stream holds, returns when the rows are there.  h_n: the lengths on the host (volume counter).
+struct FamilyPlan;
+int family_rule_plan(const char *who, const sina_hip_family_rule *r, uint32_t nq, FamilyPlan *plan);
+int family_launch(sina_hip_ctx *c, const uint32_t *d_ids, const float *d_scores, const uint16_t *d_match, const uint32_t *d_n,
+                  uint32_t stride, const uint64_t *d_qoff, uint32_t nq, const sina_hip_family_rule *r, const FamilyPlan &plan,
+                  const uint32_t *d_self_ids, const uint64_t *d_self_off, const uint32_t *h_n, uint32_t *out_rows);
+// fails on a self list that descends or names a reference the store does not have (null lists: nothing to check)
+int family_check_self(const char *who, sina_hip_ctx *c, const uint32_t *self_ids, const uint64_t *self_off, uint32_t nq);
+// the row of a query without candidates
+void family_empty_row(const sina_hip_family_rule *r, uint32_t row_words, uint32_t *row);
 }  // namespace sina_hip
 
 namespace sina_hip {

@@ -354,6 +354,13 @@ int sina_host_store_match_stats(const char *key, double *kernel_ms, uint64_t *pa
         reference_store::get(key)->match_stats(kernel_ms, pairs, cand_bases, launches);
     });
 }
+// famfinder's device-cascade on this store: the cascade kernel's time and volume (sina_hip_family_stats) on its contexts
+int sina_host_store_family_stats(const char *key, double *kernel_ms, uint64_t *queries, uint64_t *candidates_listed,
+                                 uint64_t *candidates_scanned, uint64_t *launches) {
+    return guarded([&] {
+        reference_store::get(key)->family_stats(kernel_ms, queries, candidates_listed, candidates_scanned, launches);
+    });
+}
 // search_filter's device-rank on this store: queries ranked on the device, queries sent back to the host path, and the
 // rank kernel's time and volume (sina_hip_rank_stats) on its contexts -- between runs, like the counters above
 int sina_host_store_rank_stats(const char *key, uint64_t *ranked, uint64_t *fallen_back, double *kernel_ms, uint64_t *pairs,

@@ -1,6 +1,7 @@
 // Host side of the boundary: famfinder (its options, --turn, the auto-filter vote, the filter cascade over the
 // k-mer search's candidates).  Behaviour follows the reference (citations inline).
 #include "stages_internal.h"
+#include "../family_plan.h"
 #include <charconv>
 
 #include <algorithm>
@@ -27,6 +28,7 @@ struct ff_options {
     std::string database;
     bool long_queries;  // search queries of up to SINA_HIP_MAX_LONG_QUERY_LEN bases (default off: SINA_HIP_MAX_QUERY_LEN)
     bool device_msc;    // fs-msc-max < 1: the candidates' identities from the device's match counts (default off: the host walk)
+    bool device_cascade;  // the filter cascade on the device, behind the search (default off: match_pass below)
 };
 ff_options ff_defaults() {  // src/famfinder.cpp:144-203
     ff_options o;
@@ -47,6 +49,7 @@ ff_options ff_defaults() {  // src/famfinder.cpp:144-203
     o.fs_cover_gene = 0;
     o.long_queries = false;
     o.device_msc = false;
+    o.device_cascade = false;
     o.posvar_autofilter_thres = 0.8f;  // src/famfinder.cpp:205-208
     return o;
 }
@@ -120,6 +123,7 @@ void famfinder::set_option(const std::string &name, const std::string &value) {
     else if (name == "auto-filter-threshold") o.posvar_autofilter_thres = std::stof(value);
     else if (name == "long-queries") o.long_queries = to_bool(value);
     else if (name == "device-msc") o.device_msc = to_bool(value);
+    else if (name == "device-cascade") o.device_cascade = to_bool(value);
     else throw std::logic_error("famfinder: unknown option " + name);
 }
 
@@ -400,12 +404,22 @@ void famfinder::impl::run(std::vector<tray *> &batch) {
         for (size_t i = 0; i < todo.size(); i++) found[i].swap(*todo[i]->alignment_reference);  // (their heap blocks, recycled)
         std::vector<uint32_t> nk;
         // device-msc: every candidate's match count comes with the ids (an empty row: that query keeps the walk)
-        const bool device_msc = o.device_msc && o.fs_msc_max < 1;
+        // device-cascade: the cascade runs behind the search and a query's family comes back -- unless the
+        // rule allows a family beyond the device's row, or the identity limit meets a store too wide for the match count;
+        // then, and for a query the device cannot take, match_pass below
+        kmer_search::family_request family{
+            sina_hip_family_rule{o.fs_min, o.fs_max, o.fs_req_full, o.fs_full_len, o.fs_min_len, o.fs_cover_gene, o.fs_msc, o.fs_msc_max},
+            o.fs_leave_query_out, {}};
+        const bool device_cascade = o.device_cascade && o.engine == ENGINE_SINA_KMER &&
+                                    sina_hip::family_plan(o.fs_min, o.fs_max, o.fs_req_full, o.fs_cover_gene, 0).ok &&
+                                    !(o.fs_msc_max < 1 && arb->match_counts_too_wide());
+        const bool device_msc = o.device_msc && o.fs_msc_max < 1 && !device_cascade;
         std::vector<std::vector<uint16_t>> match_rows;
         {
             scoped_phase ph_find("ff.find_batch");
             index->find_batch(qs, found, (unsigned)std::min<size_t>(max_results, isize),
-                              o.engine == ENGINE_SINA_KMER ? &nk : nullptr, device_msc ? &match_rows : nullptr);
+                              o.engine == ENGINE_SINA_KMER ? &nk : nullptr, device_msc ? &match_rows : nullptr,
+                              device_cascade ? &family : nullptr);
         }
         for (size_t i = 0; i < nk.size(); i++) todo[i]->query_kmer_count = (int)nk[i];
         std::vector<char> done(todo.size(), 0);
@@ -413,6 +427,11 @@ void famfinder::impl::run(std::vector<tray *> &batch) {
         parallel_for(todo.size(), [&](size_t i) {
             search::result_vector &res = *todo[i]->alignment_reference;
             res.swap(found[i]);
+            if (device_cascade && (family.state[i] & kmer_search::family_request::on_device)) {  // (res is the family)
+                const uint8_t state = family.state[i];
+                done[i] = ((state & (kmer_search::family_request::enough | kmer_search::family_request::empty_list)) || max_results >= isize) ? 1 : 0;
+                return;
+            }
             if (res.empty()) {
                 done[i] = 1;
                 return;

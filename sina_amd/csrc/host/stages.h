@@ -26,6 +26,7 @@
 #include <sstream>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "cseq.h"
@@ -323,6 +324,11 @@ public:
     void big_select_queries(uint64_t *n);
     // ... and the match-count kernel's time and volume (famfinder's device-msc) -- sina_hip_match_stats
     void match_stats(double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches);
+    // ... and the family cascade's (famfinder's device-cascade) -- sina_hip_family_stats
+    void family_stats(double *kernel_ms, uint64_t *queries, uint64_t *candidates_listed, uint64_t *candidates_scanned, uint64_t *launches);
+    // the references that carry `name` (famfinder's fs-leave-query-out on the device: a query's self list); references may
+    // share a name.  The map is built once, by the first call
+    const std::vector<uint32_t> &ids_of_name(const std::string &name);
     // the alignment is wider than the match-count kernel's table takes: said once (stderr), then true every time
     bool match_counts_too_wide();
     // search_filter's device-rank: the references' name order is on the device (computed and uploaded by the first
@@ -401,6 +407,8 @@ private:
     std::atomic<bool> labels_ready{false};
     std::mutex gpu_mu;
     std::atomic<bool> too_wide_said{false};
+    std::unordered_map<std::string, std::vector<uint32_t>> name_ids;
+    std::once_flag name_ids_once;
     std::atomic<int> name_order_state{0};  // 0: not looked at, 1: uploaded, 2: names repeat
     std::atomic<uint64_t> n_ranked{0}, n_rank_host{0};
     std::atomic<uint64_t> n_bp_inplace{0}, n_idty_inplace{0}, n_search_inplace{0};
@@ -433,9 +441,19 @@ public:
     // (match_rows, optional: famfinder's device-msc -- per query the device's match count of every result, by rank;
     // the row of a query whose columns do not ascend strictly, and every row of a store too wide for the kernel, stays
     // empty: those identities are the host walk's)
+    // (family, optional: famfinder's device-cascade -- the filter cascade runs on the device behind the search, and
+    // results[i] is query i's FAMILY, found by id; family->state[i] says what became of query i.  A query that cannot
+    // take the device path -- columns that do not ascend strictly while the rule has an identity limit -- is searched
+    // in a call of its own and gets its candidates, as without the request)
+    struct family_request {
+        sina_hip_family_rule rule;
+        bool leave_out;                // the self list of a query: the references that carry its name
+        enum { enough = 1, empty_list = 2, on_device = 4 };
+        std::vector<uint8_t> state;    // out, [queries]
+    };
     void find_batch(const std::vector<const cseq *> &queries, std::vector<result_vector> &results,
                     unsigned int max, std::vector<uint32_t> *kmer_counts = nullptr,
-                    std::vector<std::vector<uint16_t>> *match_rows = nullptr);
+                    std::vector<std::vector<uint16_t>> *match_rows = nullptr, family_request *family = nullptr);
     unsigned int size() const override;
     ~kmer_search() override;
 
@@ -465,7 +483,8 @@ public:
     // option names as on the SINA command line: "db", "turn", "fs-kmer-len", "fs-req", "fs-min",
     // "fs-max", "fs-msc", "fs-req-full", "fs-full-len", "fs-req-gaps", "fs-min-len",
     // "fs-kmer-no-fast", "fs-msc-max", "fs-leave-query-out", "fs-cover-gene", "filter", "auto-filter-field",
-    // "auto-filter-threshold", "long-queries", "device-msc" (fs-msc-max < 1: identities from the device's match counts)
+    // "auto-filter-threshold", "long-queries", "device-msc" (fs-msc-max < 1: identities from the device's match counts),
+    // "device-cascade" (the filter cascade on the device: a round brings down one family row per query)
     static void set_option(const std::string &name, const std::string &value);
     static void reset_options();
     static void validate_options();

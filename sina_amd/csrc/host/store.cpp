@@ -298,6 +298,30 @@ void reference_store::big_select_queries(uint64_t *n) {
 void reference_store::match_stats(double *kernel_ms, uint64_t *pairs, uint64_t *cand_bases, uint64_t *launches) {
     sum_kernel_use("sina_hip_match_stats", sina_hip_match_stats, kernel_ms, pairs, cand_bases, launches);
 }
+void reference_store::family_stats(double *kernel_ms, uint64_t *queries, uint64_t *candidates_listed, uint64_t *candidates_scanned,
+                                   uint64_t *launches) {
+    *kernel_ms = 0;
+    *queries = *candidates_listed = *candidates_scanned = *launches = 0;
+    for_each_context([&](sina_hip_ctx *c) {
+        double ms = 0;
+        uint64_t q = 0, listed = 0, scanned = 0, l = 0;
+        hip_check(sina_hip_family_stats(c, &ms, &q, &listed, &scanned, &l), "sina_hip_family_stats");
+        *kernel_ms += ms;
+        *queries += q;
+        *candidates_listed += listed;
+        *candidates_scanned += scanned;
+        *launches += l;
+    });
+}
+const std::vector<uint32_t> &reference_store::ids_of_name(const std::string &name) {
+    static const std::vector<uint32_t> none;
+    std::call_once(name_ids_once, [this] {
+        name_ids.reserve(seqs.size() * 2);
+        for (size_t i = 0; i < seqs.size(); i++) name_ids[seqs[i].getName()].push_back((uint32_t)i);
+    });
+    const auto it = name_ids.find(name);
+    return it == name_ids.end() ? none : it->second;
+}
 bool reference_store::name_order_ready() {
     int state = name_order_state.load(std::memory_order_acquire);
     if (state == 0) {
@@ -702,11 +726,71 @@ static void search_slices(reference_store &st, sina_hip_ctx *ctx, const distinct
     }
 }
 
+// famfinder's device-cascade: searches the distinct (words, self list) pairs of a batch with the cascade behind the
+// search (sina_hip_kmer_topk_family) and fills every query's results with its family, found by id.  More than 4096
+// candidates per query: in slices of one launch range of the device's big select, like search_slices.
+static void search_families(reference_store &st, sina_hip_ctx *ctx, const std::vector<const cseq *> &queries, const uint32_t *qab,
+                            const uint64_t *qoff, unsigned int max, std::vector<search::result_vector> &results,
+                            kmer_search::family_request &fr) {
+    using request = kmer_search::family_request;
+    const size_t nq = queries.size();
+    // a query's self list: the references of its name.  Two trays with the same bases under different names share a row
+    // only where their lists are equal
+    static const std::vector<uint32_t> no_self;
+    std::vector<const std::vector<uint32_t> *> selfs(nq, &no_self);
+    if (fr.leave_out)
+        for (size_t i = 0; i < nq; i++) selfs[i] = &st.ids_of_name(queries[i]->name_ref());
+    const distinct_items d = distinct_spans(
+        dedup_enabled(), parallel_for, qab, qoff, nq,
+        [&](size_t i) { return hash_bytes(selfs[i]->data(), 4 * selfs[i]->size(), selfs[i]->size()); },
+        [&](size_t a, size_t b) { return selfs[a] == selfs[b] || *selfs[a] == *selfs[b]; });
+    thread_local batch_scratch<uint32_t> uab_buf;
+    const uint32_t *const dev_ab = gather_distinct(d, parallel_for, qab, qoff, uab_buf);
+    const size_t nu = d.n;
+    std::vector<uint32_t> self_ids;
+    std::vector<uint64_t> self_off(nu + 1, 0);
+    for (size_t u = 0; u < nu; u++) {
+        const std::vector<uint32_t> &s = *selfs[d.first.empty() ? u : d.first[u]];
+        self_ids.insert(self_ids.end(), s.begin(), s.end());
+        self_off[u + 1] = self_ids.size();
+    }
+    self_ids.push_back(0);  // (never empty: data() is the list's address)
+    uint32_t words = 0;
+    hip_check(sina_hip_family_row_words(&fr.rule, &words), "family_row_words");
+    const uint32_t K = (words - 2) / 2;
+    const size_t slice = max > sina_hip::kKmerSelMax ? sina_hip::big_select_range((uint32_t)nu, max, sina_hip::kBigSelBudget) : nu;
+    thread_local batch_scratch<uint32_t> rows_buf;
+    uint32_t *const rows = rows_buf.get(slice * words);
+    for (size_t u0 = 0; u0 < nu; u0 += slice) {
+        const size_t u1 = std::min(nu, u0 + slice);
+        {
+            scoped_phase ph("ff.kmer_topk_family(C-ABI)");
+            hip_check(sina_hip_kmer_topk_family(ctx, dev_ab, d.off.data() + u0, (uint32_t)(u1 - u0), max, &fr.rule,
+                                                fr.leave_out ? self_ids.data() : nullptr, fr.leave_out ? self_off.data() + u0 : nullptr, rows),
+                      "kmer_topk_family");
+        }
+        parallel_for(nq, [&](size_t i) {
+            const size_t u = d.slot_of[i];
+            if (u < u0 || u >= u1) return;
+            const uint32_t *row = rows + (u - u0) * words;
+            results[i].reserve(row[0]);
+            for (uint32_t x = 0; x < row[0]; x++) {
+                float score;
+                memcpy(&score, &row[2 + K + x], 4);
+                results[i].emplace_back(score, &st.getCseq(row[2 + x]));
+            }
+            fr.state[i] = (uint8_t)(request::on_device | (row[1] & 1u ? request::enough : 0) | (row[1] & 2u ? request::empty_list : 0));
+        });
+    }
+}
+
 // Clears the outputs, packs the queries, finds the distinct ones, searches those and scatters what they found.
 void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vector<result_vector> &results,
-                             unsigned int max, std::vector<uint32_t> *kmer_counts, std::vector<std::vector<uint16_t>> *match_rows) {
+                             unsigned int max, std::vector<uint32_t> *kmer_counts, std::vector<std::vector<uint16_t>> *match_rows,
+                             family_request *family) {
     reference_store &st = *pimpl->store;
     const size_t nq = queries.size();
+    if (family) family->state.assign(nq, 0);
     // (the callers' vectors are kept -- famfinder hands in recycled ones -- and only emptied)
     results.resize(nq);
     for (auto &r : results) r.clear();
@@ -719,7 +803,32 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
     // The device's match counts (famfinder's device-msc): kept from a store too wide for the kernel's table -- said
     // once, then every query keeps the host walk -- and from a query whose columns do not ascend strictly.
     if (match_rows && st.match_counts_too_wide()) match_rows = nullptr;
-    if (match_rows) {
+    if (family && family->rule.fs_msc_max < 1) {
+        // the cascade's identity limit asks for strictly ascending columns too: the queries without them keep the
+        // path without the request, in a call of their own
+        std::vector<size_t> at[2];
+        for (size_t i = 0; i < nq; i++) at[columns_ascend(*queries[i]) ? 0 : 1].push_back(i);
+        if (!at[1].empty()) {
+            if (kmer_counts) kmer_counts->assign(nq, 0);
+            for (int pass = 0; pass < 2; pass++) {
+                if (at[pass].empty()) continue;
+                std::vector<const cseq *> sub;
+                for (size_t i : at[pass]) sub.push_back(queries[i]);
+                std::vector<result_vector> sub_results(sub.size());
+                for (size_t x = 0; x < sub.size(); x++) sub_results[x].swap(results[at[pass][x]]);
+                std::vector<uint32_t> sub_counts;
+                family_request sub_family{family->rule, family->leave_out, {}};
+                find_batch(sub, sub_results, max, kmer_counts ? &sub_counts : nullptr, nullptr, pass == 0 ? &sub_family : nullptr);
+                for (size_t x = 0; x < sub.size(); x++) {
+                    results[at[pass][x]].swap(sub_results[x]);
+                    if (kmer_counts) (*kmer_counts)[at[pass][x]] = sub_counts[x];
+                    if (pass == 0) family->state[at[pass][x]] = sub_family.state[x];
+                }
+            }
+            return;
+        }
+    }
+    if (match_rows && !family) {
         std::vector<char> is_plain(nq, 0);
         bool any_plain = false;
         for (size_t i = 0; i < nq; i++) any_plain |= (is_plain[i] = !columns_ascend(*queries[i]));
@@ -736,9 +845,11 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
     });
     // with match counts the device takes the queries as packed aligned bases
     thread_local batch_scratch<uint32_t> qab_buf;
-    uint32_t *const qab = match_rows ? qab_buf.get(qoff.back() + 1) : nullptr;
-    if (match_rows) pack_words(nq, seq_of, qoff.data(), qab);
+    if (family) match_rows = nullptr;  // (the counts stay on the device)
+    uint32_t *const qab = match_rows || family ? qab_buf.get(qoff.back() + 1) : nullptr;
+    if (qab) pack_words(nq, seq_of, qoff.data(), qab);
     auto dev = st.worker_device(reference_store::dev_search);
+    if (family) return search_families(st, dev.get(), queries, qab, qoff.data(), max, results, *family);
     // repeated queries (same bases, same case: the packed mask bytes) are searched once
     // (with match counts: same PACKED WORDS -- equal bases in other columns are another query there)
     const distinct_items d = qab ? distinct_spans(dedup_enabled(), parallel_for, qab, qoff.data(), nq)

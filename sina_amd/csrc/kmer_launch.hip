@@ -3,10 +3,12 @@
 // rank kernels -- and the C ABI's search entry points.  The kernels and their launchers are kmer.hip's, the index and
 // the dense bitmaps kmer_index.hip's.
 #include <cstring>
+#include <memory>
 
 #include "common.h"
 #include "ctx.h"
 #include "match_plan.h"
+#include "family_plan.h"
 #include "compare_dev.h"
 
 namespace sina_hip {
@@ -26,12 +28,23 @@ struct KeepReq {
     uint32_t *d_ids, *d_n;  // [nq][max], [nq] device memory
     uint32_t *h_n;          // [nq] the lengths again, on the host
 };
+// sina_hip_kmer_topk_family: every range's candidates go through the family cascade where the select (and, for an
+// identity limit, the match count) left them (family.hip), and nothing but the cascade's rows comes to the host
+struct FamilyReq {
+    const sina_hip_family_rule *rule;
+    FamilyPlan plan;
+    const uint32_t *self_ids;  // the queries' self lists at self_off[q] .. self_off[q + 1] (host, absolute); null: none
+    const uint64_t *self_off;
+    uint32_t *out_rows;        // [nq][plan.row_words]
+    bool msc() const { return rule->fs_msc_max < 1; }
+};
 // One search call.  out_ids / out_scores: [nq * row()], out_n: [nq].
 // q_ab / out_match (sina_hip_kmer_topk_match; else null): the queries' packed aligned bases, one per mask byte, and
 // where every range's match counts go (match.hip), [nq * max] like out_ids
 // rk (sina_hip_kmer_topk_rank; else null): out_ids / out_scores are rows of the rank kernel, out_n its counts, and no
 // id or k-mer score of the select is copied out
 // keep (kmer_rows_resident; else null): nothing comes to the host but the lengths; out_ids / out_scores / out_n are null
+// fam (sina_hip_kmer_topk_family; else null): the cascade's rows come to the host; out_ids / out_scores / out_n are null
 struct KmerRequest {
     const uint8_t *qmask;
     const uint64_t *qoff;
@@ -43,6 +56,7 @@ struct KmerRequest {
     uint16_t *out_match = nullptr;
     const RankReq *rk = nullptr;
     const KeepReq *keep = nullptr;
+    const FamilyReq *fam = nullptr;
     uint32_t row() const { return rk ? rk->N : max; }  // entries of an output row
     uint32_t qlen(uint32_t q) const { return (uint32_t)(qoff[q + 1] - qoff[q]); }
 };
@@ -78,7 +92,7 @@ int run_range(sina_hip_ctx *c, const KmerRequest &r, const KmerRange &g, uint32_
     KmerLaunch l{c->qmask.as<uint8_t>(), c->k_qoff.as<uint64_t>() + q0, bq, max, max_qlen, g.path, g.big};
     if (run_kernels(c, l, true)) return 1;
     // (the kernels have finished: run_kernels waits for the heavy stream)
-    if ((!r.rk && !r.keep && (download(c, 9, c->k_out_ids.p, (size_t)bq * max * 4, s) || download(c, 10, c->k_out_scores.p, (size_t)bq * max * 4, s))) ||
+    if ((!r.rk && !r.keep && !r.fam && (download(c, 9, c->k_out_ids.p, (size_t)bq * max * 4, s) || download(c, 10, c->k_out_scores.p, (size_t)bq * max * 4, s))) ||
         download(c, 11, c->k_out_n.p, (size_t)bq * 4, s) || download(c, 0, c->k_tmp2.p, 8, s))
         return 1;
     SH_CHECK(wait_stream(c, s));
@@ -110,6 +124,23 @@ int run_range(sina_hip_ctx *c, const KmerRequest &r, const KmerRange &g, uint32_
         SH_CHECK(hipMemcpyAsync(r.keep->d_n + q0, c->k_out_n.p, (size_t)bq * 4, hipMemcpyDeviceToDevice, s));
         memcpy(r.keep->h_n + q0, c->h_stage[11].p, (size_t)bq * 4);
         return 0;
+    }
+    if (r.fam) {  // the range's select is final: the match counts if the rule has an identity limit, then the cascade
+        const uint32_t *h_n = static_cast<const uint32_t *>(c->h_stage[11].p);
+        if (r.fam->msc()) {
+            const size_t row_bytes = (size_t)bq * max * 2;
+            if (c->m_out.reserve(row_bytes)) return 1;
+            SH_CHECK(hipMemsetAsync(c->m_out.p, 0, row_bytes, s));
+            if (match_launch(c, c->s_qab.as<uint32_t>(), l.qoff, bq, c->k_out_ids.as<uint32_t>(), c->k_out_n.as<uint32_t>(), max,
+                             c->m_out.as<uint16_t>(), nullptr, h_n))
+                return 1;
+        }
+        return family_launch(c, c->k_out_ids.as<uint32_t>(), c->k_out_scores.as<float>(), c->m_out.as<uint16_t>(), c->k_out_n.as<uint32_t>(),
+                             max, l.qoff, bq, r.fam->rule, family_plan(r.fam->rule->fs_min, r.fam->rule->fs_max, r.fam->rule->fs_req_full,
+                                                                       r.fam->rule->fs_cover_gene, bq),
+                             r.fam->self_ids ? c->f_self_ids.as<uint32_t>() : nullptr,
+                             r.fam->self_ids ? c->f_self_off.as<uint64_t>() + q0 : nullptr, h_n,
+                             r.fam->out_rows + (size_t)q0 * r.fam->plan.row_words);
     }
     if (r.rk) {  // the range's select is final: its candidates ranked, ids and lengths read where they lie
         uint32_t max_la = 0;
@@ -151,7 +182,15 @@ int kmer_topk_run(sina_hip_ctx *c, const KmerRequest &r, uint32_t n_fast) {
     for (uint32_t q = 0; q <= nq; q++) rel[q] = qoff[q] - qoff[0];
     if (upload(c, 7, c->qmask.p, r.qmask + qoff[0], nqm, s) || upload(c, 8, c->k_qoff.p, rel.data(), 8 * ((uint64_t)nq + 1), s))
         return 1;
-    if ((r.out_match || r.rk) && (c->s_qab.reserve(4 * std::max<uint64_t>(nqm, 1)) || upload(c, 1, c->s_qab.p, r.q_ab + qoff[0], 4 * nqm, s))) return 1;
+    if ((r.out_match || r.rk || (r.fam && r.fam->msc())) && (c->s_qab.reserve(4 * std::max<uint64_t>(nqm, 1)) || upload(c, 1, c->s_qab.p, r.q_ab + qoff[0], 4 * nqm, s))) return 1;
+    if (r.fam && r.fam->self_ids) {  // the call's self lists, offsets from the first query's
+        const uint64_t *so = r.fam->self_off;
+        std::vector<uint64_t> srel(nq + 1);
+        for (uint32_t q = 0; q <= nq; q++) srel[q] = so[q] - so[0];
+        if (c->f_self_ids.reserve(4 * std::max<uint64_t>(srel[nq], 1)) || c->f_self_off.reserve(8 * ((uint64_t)nq + 1)) ||
+            upload(c, 2, c->f_self_ids.p, r.fam->self_ids + so[0], 4 * srel[nq], s) || upload(c, 3, c->f_self_off.p, srel.data(), 8 * ((uint64_t)nq + 1), s))
+            return 1;
+    }
     // (SINA_HIP_TEST=big_sel_bytes=N: a test's budget of the big select; kmer_rows=1: no candidate lists)
     uint64_t budget = kBigSelBudget;
     if (const std::string e_ = test_knob("big_sel_bytes"); !e_.empty()) budget = std::min<uint64_t>(kBigSelBudget, strtoull(e_.c_str(), nullptr, 10));
@@ -173,7 +212,10 @@ struct Reordered {
     std::vector<uint32_t> ab, ids, n, fl;
     std::vector<float> sc;
     std::vector<uint16_t> mt;
+    std::vector<uint32_t> self_ids, rows;  // the family request's self lists, in the new order, and its rows
+    std::vector<uint64_t> self_off;
     RankReq rk;
+    FamilyReq fam;
     KmerRequest req;  // the request over these buffers
 };
 // ... which gather_queries fills with the request's queries (the packed bases move with their queries) ...
@@ -187,6 +229,25 @@ void gather_queries(const KmerRequest &r, const std::vector<uint32_t> &order, Re
         memcpy(g->mask.data() + g->off[x], r.qmask + r.qoff[order[x]], g->off[x + 1] - g->off[x]);
         if (r.q_ab) memcpy(g->ab.data() + g->off[x], r.q_ab + r.qoff[order[x]], 4 * (g->off[x + 1] - g->off[x]));
     }
+    if (r.fam) {
+        g->fam = *r.fam;
+        g->rows.resize((size_t)nq * r.fam->plan.row_words);
+        g->fam.out_rows = g->rows.data();
+        if (r.fam->self_ids) {
+            g->self_off.assign(nq + 1, 0);
+            for (uint32_t x = 0; x < nq; x++) {
+                const uint64_t b = r.fam->self_off[order[x]], e = r.fam->self_off[order[x] + 1];
+                g->self_ids.insert(g->self_ids.end(), r.fam->self_ids + b, r.fam->self_ids + e);
+                g->self_off[x + 1] = g->self_ids.size();
+            }
+            g->self_ids.push_back(0);  // (never empty: data() is the list's address)
+            g->fam.self_ids = g->self_ids.data();
+            g->fam.self_off = g->self_off.data();
+        }
+        g->req = KmerRequest{g->mask.data(), g->off.data(), nq, r.max, nullptr, nullptr, nullptr, r.q_ab ? g->ab.data() : nullptr};
+        g->req.fam = &g->fam;
+        return;
+    }
     g->ids.resize((size_t)nq * r.row());
     g->sc.resize((size_t)nq * r.row());
     g->n.resize(nq);
@@ -199,6 +260,11 @@ void gather_queries(const KmerRequest &r, const std::vector<uint32_t> &order, Re
 // ... and scatter_results empties into the caller's rows, in the caller's order
 void scatter_results(const Reordered &g, const std::vector<uint32_t> &order, const KmerRequest &r) {
     const uint32_t row = r.row(), max = r.max;
+    if (r.fam) {
+        const size_t w = r.fam->plan.row_words;
+        for (uint32_t x = 0; x < r.nq; x++) memcpy(r.fam->out_rows + order[x] * w, g.rows.data() + x * w, 4 * w);
+        return;
+    }
     for (uint32_t x = 0; x < r.nq; x++) {
         if (r.out_match) memcpy(r.out_match + (size_t)order[x] * max, g.mt.data() + (size_t)x * max, (size_t)max * 2);
         memcpy(r.out_ids + (size_t)order[x] * row, g.ids.data() + (size_t)x * row, (size_t)row * 4);
@@ -211,7 +277,7 @@ void scatter_results(const Reordered &g, const std::vector<uint32_t> &order, con
 // any: queries of up to kMaxLongQueryLen bases (sina_hip_kmer_topk_any), the longer ones behind the others for
 // kmer_topk_run and back into the caller's order
 int kmer_topk_checked(sina_hip_ctx *c, const KmerRequest &in, bool any) {
-    if (!c || !in.qmask || !in.qoff || !in.out_ids || !in.out_scores || !in.out_n) SH_FAIL("kmer_topk: null argument");
+    if (!c || !in.qmask || !in.qoff || (!in.fam && (!in.out_ids || !in.out_scores || !in.out_n))) SH_FAIL("kmer_topk: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
     sina_hip_hint_guard hints(c);
     if (index_ready(c)) return 1;
@@ -219,6 +285,11 @@ int kmer_topk_checked(sina_hip_ctx *c, const KmerRequest &in, bool any) {
     const uint32_t nq = r.nq;
     if (r.out_match && match_table_bytes(c->st->width) > kMatchMaxLds)
         SH_FAIL_LIMIT("kmer_topk_match: alignment too wide for the device match count");
+    if (r.fam) {
+        if (r.fam->msc() && match_table_bytes(c->st->width) > kMatchMaxLds)
+            SH_FAIL_LIMIT("kmer_topk_family: alignment too wide for the device match count");
+        if (family_check_self("kmer_topk_family", c, r.fam->self_ids, r.fam->self_off, nq)) return 1;
+    }
     if (r.rk) {
         if (rank_check_rules("kmer_topk_rank", c, r.rk->iupac, r.rk->cover, r.rk->N)) return 1;
         uint32_t max_la = 0;
@@ -231,6 +302,10 @@ int kmer_topk_checked(sina_hip_ctx *c, const KmerRequest &in, bool any) {
     if (nq == 0) return 0;
     SH_CHECK(hipSetDevice(c->device));
     if (r.max > c->st->n_refs) r.max = c->st->n_refs;
+    if (r.max == 0 && r.fam) {
+        for (uint32_t q = 0; q < nq; q++) family_empty_row(r.fam->rule, r.fam->plan.row_words, r.fam->out_rows + (size_t)q * r.fam->plan.row_words);
+        return 0;
+    }
     if (r.max == 0) {
         memset(r.out_n, 0, sizeof(uint32_t) * nq);
         if (r.rk) memset(r.rk->out_flag, 0, sizeof(uint32_t) * nq);
@@ -337,6 +412,34 @@ int sina_hip_kmer_topk_rank(sina_hip_ctx *c, const uint32_t *q_ab, const uint64_
     memcpy(out_scores, sc.data(), 4 * (size_t)nq * max_result);
     memcpy(out_n, n.data(), 4 * (size_t)nq);
     memcpy(out_flag, fl.data(), 4 * (size_t)nq);
+    return 0;
+}
+int sina_hip_kmer_topk_family(sina_hip_ctx *c, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t max,
+                              const sina_hip_family_rule *rule, const uint32_t *self_ids, const uint64_t *self_off, uint32_t *out_rows) {
+    if (!c || !q_ab || !q_off || !rule || !out_rows || (!self_ids) != (!self_off)) SH_FAIL("kmer_topk_family: null argument");
+    FamilyReq fam{rule, FamilyPlan(), self_ids, self_off, nullptr};
+    if (family_rule_plan("kmer_topk_family", rule, nq, &fam.plan)) return 1;
+    if (fam.msc() && match_check_queries("kmer_topk_family", q_ab, q_off, nq)) return 1;
+    for (uint32_t q = 0; q < nq; q++)
+        if (q_off[q + 1] < q_off[q]) SH_FAIL("kmer_topk_family: query offsets descend");
+    // the mask bytes the count kernel reads, bits 24..31 of every word (PackedMasks' bytes; an uninitialised block and
+    // restrict pointers: on the default path, 41 candidates per query, this loop is most of what the entry adds)
+    const uint64_t n_bases = q_off[nq] - q_off[0];
+    const std::unique_ptr<uint8_t[]> mask(new uint8_t[n_bases + 1]);
+    {
+        const uint32_t *__restrict src = q_ab + q_off[0];
+        uint8_t *__restrict dst = mask.get();
+        for (uint64_t i = 0; i < n_bases; i++) dst[i] = (uint8_t)(src[i] >> 24);
+    }
+    std::vector<uint64_t> rel(nq + 1);
+    for (uint32_t q = 0; q <= nq; q++) rel[q] = q_off[q] - q_off[0];
+    // (rows through a vector of the call's own: out_rows stays untouched if a range fails)
+    std::vector<uint32_t> rows((size_t)nq * fam.plan.row_words);
+    fam.out_rows = rows.data();
+    KmerRequest r{mask.get(), rel.data(), nq, max, nullptr, nullptr, nullptr, q_ab + q_off[0]};
+    r.fam = &fam;
+    if (kmer_topk_checked(c, r, true)) return 1;
+    memcpy(out_rows, rows.data(), 4 * rows.size());
     return 0;
 }
 int sina_hip_kmer_scores(sina_hip_ctx *c, const uint8_t *qmask, uint32_t qlen, int16_t *scores) {

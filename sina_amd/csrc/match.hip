@@ -92,7 +92,8 @@ __global__ void __launch_bounds__(kMT) match_count_kernel(MatchArgs a) {
 
 // nq queries (packed aligned bases d_qab at d_qoff[q], device memory) against the candidates d_ids[q * stride + i],
 // i < d_n[q]: counts into d_out[q * stride + i].  Queued behind what the context's stream holds; returns when the
-// kernel has ended.  h_ids / h_n: the same lists on the host, for the volume counters only.
+// kernel has ended.  h_ids / h_n: the same lists on the host, for the volume counters only (h_ids null: the ids stayed
+// on the device, the candidates' bases are not counted).
 int match_launch(sina_hip_ctx *c, const uint32_t *d_qab, const uint64_t *d_qoff, uint32_t nq, const uint32_t *d_ids,
                  const uint32_t *d_n, uint32_t stride, uint16_t *d_out, const uint32_t *h_ids, const uint32_t *h_n) {
     if (nq == 0 || stride == 0) return 0;
@@ -134,11 +135,11 @@ int match_launch(sina_hip_ctx *c, const uint32_t *d_qab, const uint64_t *d_qoff,
     float ms = 0;
     SH_CHECK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
     uint64_t pairs = 0, bases = 0;
-    const bool have_off = ensure_ref_off_host(c) == 0;
+    const bool have_off = h_ids && ensure_ref_off_host(c) == 0;
     for (uint32_t q = 0; q < nq; q++) {
         const uint32_t n = h_n[q] == 0xFFFFFFFFu ? 0u : std::min(h_n[q], stride);
         pairs += n;
-        if (have_off)
+        if (have_off && h_ids)
             for (uint32_t i = 0; i < n; i++) {
                 const uint32_t id = h_ids[(size_t)q * stride + i];
                 if (id < c->st->n_refs) bases += c->st->ref_off_host[id + 1] - c->st->ref_off_host[id];

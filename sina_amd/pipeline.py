@@ -39,6 +39,7 @@ def load_host():
     H.sina_host_pipeline_run_aligned.argtypes = [vp, capi.u32p, capi.u64p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32,
                                                  C.c_uint32]
     H.sina_host_store_match_stats.argtypes = [C.c_char_p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_store_family_stats.argtypes = [C.c_char_p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_store_rank_stats.argtypes = [C.c_char_p, capi.u64p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_pipeline_run_single_trays.argtypes = [vp, capi.u8p, capi.u64p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                       C.c_uint32, C.c_int32, capi.u8p, C.c_char_p, C.c_uint32]
@@ -259,6 +260,12 @@ class Store:
         """The match-count kernel (famfinder's device-msc) on this store's contexts so far: dict(kernel_ms, pairs,
         cand_bases, launches) -- between runs, like big_select_queries()."""
         return self._counters(self.H.sina_host_store_match_stats, capi.KERNEL_MS + capi.u64_fields("pairs", "cand_bases", "launches"))
+
+    def family_stats(self):
+        """The family cascade (famfinder's device-cascade) on this store's contexts so far: dict(kernel_ms, queries,
+        candidates_listed, candidates_scanned, launches) -- between runs, like big_select_queries()."""
+        return self._counters(self.H.sina_host_store_family_stats, capi.KERNEL_MS +
+                              capi.u64_fields("queries", "candidates_listed", "candidates_scanned", "launches"))
 
     def rank_stats(self):
         """The search stage's device-rank on this store so far: dict(ranked, fallen_back, kernel_ms, pairs, cand_bases,

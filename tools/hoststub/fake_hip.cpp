@@ -100,6 +100,40 @@ int sina_hip_match_stats(sina_hip_ctx *, double *ms, uint64_t *pairs, uint64_t *
     *pairs = *bases = *launches = 0;
     return 0;
 }
+int sina_hip_family_row_words(const sina_hip_family_rule *r, uint32_t *words) {
+    *words = 2 + 2 * ((r->fs_min > r->fs_max ? r->fs_min : r->fs_max) + r->fs_req_full + 2 * r->fs_cover_gene);
+    return 0;
+}
+int sina_hip_family_cascade(sina_hip_ctx *, const uint32_t *, const float *, const uint16_t *, const uint64_t *, const uint32_t *, uint32_t,
+                            const sina_hip_family_rule *, const uint32_t *, const uint64_t *, uint32_t *) { g_err = "stub"; return 1; }
+// (the "family" is the first fs_max of the hash-picked candidates, and that is always enough)
+int sina_hip_kmer_topk_family(sina_hip_ctx *c, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t max,
+                              const sina_hip_family_rule *r, const uint32_t *, const uint64_t *, uint32_t *out_rows) {
+    if (max > c->root->n_refs) max = c->root->n_refs;
+    std::vector<uint32_t> ids((size_t)nq * max + 1), n(nq + 1);
+    std::vector<float> sc(ids.size());
+    std::vector<uint16_t> mt(ids.size());
+    if (sina_hip_kmer_topk_match(c, q_ab, q_off, nq, max, ids.data(), sc.data(), n.data(), mt.data())) return 1;
+    uint32_t words = 0;
+    sina_hip_family_row_words(r, &words);
+    const uint32_t K = (words - 2) / 2;
+    memset(out_rows, 0, 4 * (size_t)nq * words);
+    for (uint32_t q = 0; q < nq; q++) {
+        uint32_t *row = out_rows + (size_t)q * words;
+        row[0] = std::min(std::min(n[q], r->fs_max), K);
+        row[1] = 1u | (n[q] == 0 ? 2u : 0u);
+        for (uint32_t x = 0; x < row[0]; x++) {
+            row[2 + x] = ids[(size_t)q * max + x];
+            memcpy(&row[2 + K + x], &sc[(size_t)q * max + x], 4);
+        }
+    }
+    return 0;
+}
+int sina_hip_family_stats(sina_hip_ctx *, double *ms, uint64_t *queries, uint64_t *listed, uint64_t *scanned, uint64_t *launches) {
+    *ms = 0;
+    *queries = *listed = *scanned = *launches = 0;
+    return 0;
+}
 int sina_hip_upload_name_order(sina_hip_ctx *, const uint32_t *, uint32_t) { return 0; }
 int sina_hip_compare_rank(sina_hip_ctx *, const uint32_t *, const uint64_t *, uint32_t, const uint32_t *, const uint64_t *, int, int,
                           int, uint32_t, uint32_t *, float *, uint32_t *, uint32_t *) { g_err = "stub"; return 1; }
