@@ -6,6 +6,7 @@ import pytest
 
 from sina_amd import capi, pipeline, synth
 from tests import util, walk_cases as wc, walk_ref, wide_cases as wd
+from tests.util import check_trays
 
 pytestmark = pytest.mark.gpu
 
@@ -178,37 +179,6 @@ def test_malformed_graph_is_still_rejected(ctx):
 
 
 # ---------------------------------------------------------------- the aligner stage with wide-fallback on
-
-def _oracle_run(oracle, cs, idx, qs, qi, ff=None):
-    q = util.query_cseq(qs, qi, upper=False)
-    ids, sc, fflog = idx.famfinder(q, oracle.ff_opts(**(ff or {})))
-    if len(ids) == 0:
-        return dict(status=2, log=fflog, ids=ids, sc=sc)
-    r = oracle.align([cs[i] for i in ids], q, oracle.align_opts())
-    r["log"] = fflog + r["log"]
-    r["ids"], r["sc"] = ids, sc
-    return r
-
-
-def check_trays(oracle, qs, pl, cs, idx, ff):
-    """Every tray against the oracle's so_align: family, columns and case bits, attributes, log text (the check of
-    tests/test_gpu_pipeline.py).  Returns the number of trays that went through the DP."""
-    n_dp = 0
-    for qi in range(qs.n):
-        want = _oracle_run(oracle, cs, idx, qs, qi, ff)
-        got = pl.result(qi)
-        if want["status"] == 2:
-            assert got["status"] == 2 and got["log"] == want["log"]
-            continue
-        assert got["family"] == "".join("ref%d.0:%.2f " % (i, s) for i, s in zip(want["ids"], want["sc"]))
-        assert got["status"] == want["status"], (qi, got["log"], want["log"])
-        assert (got["packed"] == want["packed"]).all()          # columns AND case bits
-        assert (got["head"], got["tail"], got["qual"]) == (want["head"], want["tail"], want["qual"])
-        if want["status"] == 0:
-            assert got["log"] == want["log"]                      # NAST + scoring text
-            n_dp += 1
-    return n_dp
-
 
 def _packed(cols, masks):
     return (np.asarray(cols, np.uint32) | (np.asarray(masks, np.uint32) << 24)).astype(np.uint32)

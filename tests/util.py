@@ -280,3 +280,38 @@ def set_knobs(monkeypatch, **kw):
         monkeypatch.setenv("SINA_HIP_TEST", ";".join("%s=%s" % kv for kv in cur.items()))
     else:
         monkeypatch.delenv("SINA_HIP_TEST", raising=False)
+
+
+# ---------------------------------------------------------------- a pipeline's trays against the oracle
+# (test_gpu_wide.py and test_gpu_all_options.py share these)
+
+def oracle_run(oracle, cs, idx, qs, qi, ff=None, align_opts=None):
+    q = query_cseq(qs, qi, upper=False)
+    ids, sc, fflog = idx.famfinder(q, oracle.ff_opts(**(ff or {})))
+    if len(ids) == 0:
+        return dict(status=2, log=fflog, ids=ids, sc=sc)
+    r = oracle.align([cs[i] for i in ids], q, oracle.align_opts(**(align_opts or {})))
+    r["log"] = fflog + r["log"]
+    r["ids"], r["sc"] = ids, sc
+    return r
+
+
+def check_trays(oracle, qs, pl, cs, idx, ff, align_opts=None):
+    """Every tray against the oracle's so_align: family, columns and case bits, attributes, log text (the check of
+    tests/test_gpu_pipeline.py).  align_opts: the oracle's aligner options where the pipeline's are not the defaults.
+    Returns the number of trays that went through the DP."""
+    n_dp = 0
+    for qi in range(qs.n):
+        want = oracle_run(oracle, cs, idx, qs, qi, ff, align_opts)
+        got = pl.result(qi)
+        if want["status"] == 2:
+            assert got["status"] == 2 and got["log"] == want["log"]
+            continue
+        assert got["family"] == "".join("ref%d.0:%.2f " % (i, s) for i, s in zip(want["ids"], want["sc"]))
+        assert got["status"] == want["status"], (qi, got["log"], want["log"])
+        assert (got["packed"] == want["packed"]).all()          # columns AND case bits
+        assert (got["head"], got["tail"], got["qual"]) == (want["head"], want["tail"], want["qual"])
+        if want["status"] == 0:
+            assert got["log"] == want["log"]                      # NAST + scoring text
+            n_dp += 1
+    return n_dp
