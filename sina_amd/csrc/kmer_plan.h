@@ -1,12 +1,14 @@
 // What a k-mer search call is planned from, as plain host code: no HIP, no context, no environment (knob values come
 // in as arguments) -- the geometry of the count kernels, which path a launch range takes, how a call is cut into
-// ranges, which posting lists are dense, the order that puts long queries last.  kmer.hip sizes its launches with it,
-// kmer_launch.hip walks its ranges, kmer_index.hip takes the dense rule, host/store.cpp cuts its calls with
+// ranges, which posting lists are dense, the order that puts long queries last and the copies that bring a call's
+// inputs into it and its rows back.  kmer.hip sizes its launches with it,
+// kmer_launch.hip walks its ranges and moves its queries, kmer_index.hip takes the dense rule, host/store.cpp cuts its calls with
 // big_select_range, and tests/kmer_plan_check.cpp runs all of it without a device.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 namespace sina_hip {
@@ -122,6 +124,44 @@ inline std::vector<uint32_t> kmer_fast_first(const uint64_t *qoff, uint32_t nq, 
     for (uint32_t q = 0, f = 0, l = nf; q < nq; q++) order[qoff[q + 1] - qoff[q] > (uint64_t)kKmerMaxQueryLen ? l++ : f++] = q;
     *n_fast = nf;
     return order;
+}
+
+// ---- ... and what moves with the queries, as data.  A ragged input: query q's elements of `elem` bytes are
+// off[q] .. off[q + 1] of `base` (the mask bytes and the packed bases of a call share the queries' offsets, its self
+// lists have their own).  An output column: `bytes` per query from `base` on (ids and scores: 4 per entry of a row, the
+// count and the flag: 4, match counts: 2 per candidate, family rows: 4 per word).
+struct KmerRagged {
+    const void *base;
+    const uint64_t *off;
+    size_t elem;
+};
+struct KmerColumn {
+    void *base;
+    size_t bytes;
+    template <class T>
+    T *row(size_t q) const { return reinterpret_cast<T *>(static_cast<uint8_t *>(base) + q * bytes); }
+};
+// the offsets of nq queries' elements once query order[x] stands in slot x, from 0 ...
+inline std::vector<uint64_t> kmer_gather_offsets(const uint64_t *off, const uint32_t *order, uint32_t nq) {
+    std::vector<uint64_t> out((size_t)nq + 1, 0);
+    for (uint32_t x = 0; x < nq; x++) out[x + 1] = out[x] + (off[order[x] + 1] - off[order[x]]);
+    return out;
+}
+// ... and the elements at those offsets, in storage of the call's own (one element more than there are: data() is an
+// address whatever the queries hold)
+inline std::vector<uint8_t> kmer_gather(const KmerRagged &in, const uint32_t *order, uint32_t nq, const uint64_t *new_off) {
+    std::vector<uint8_t> out((new_off[nq] + 1) * in.elem);
+    for (uint32_t x = 0; x < nq; x++)
+        if (const uint64_t n = new_off[x + 1] - new_off[x])
+            memcpy(out.data() + new_off[x] * in.elem, static_cast<const uint8_t *>(in.base) + in.off[order[x]] * in.elem, n * in.elem);
+    return out;
+}
+// row x of `from` to row order[x] of `to`, a column of the same width (order null: row x to row x)
+inline void kmer_scatter(const KmerColumn &from, const KmerColumn &to, const uint32_t *order, uint32_t nq) {
+    if (from.bytes == 0 || nq == 0) return;
+    if (!order) memcpy(to.base, from.base, (size_t)nq * from.bytes);
+    else
+        for (uint32_t x = 0; x < nq; x++) memcpy(to.row<uint8_t>(order[x]), from.row<uint8_t>(x), from.bytes);
 }
 
 }  // namespace sina_hip

@@ -1,7 +1,7 @@
 // csrc/kmer_plan.h -- what a k-mer search call is planned from: the launch ranges of the big select, the paths and
-// ranges of a call, the count kernels' geometry, the dense rule, the fast-first order -- against plain arithmetic, as a
-// stand-alone program: tests/test_kmer_big_cpu.py builds it with the address and undefined-behaviour sanitizers and
-// runs it once.
+// ranges of a call, the count kernels' geometry, the dense rule, the fast-first order, the gather and scatter that move
+// a call's queries and rows by it -- against plain arithmetic and plain per-query loops, as a stand-alone program:
+// tests/test_kmer_big_cpu.py builds it with the address and undefined-behaviour sanitizers and runs it once.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -199,8 +199,91 @@ static void check_plan() {
     }
 }
 
+// ---- the copies that bring a call's inputs into the fast-first order and its rows back, against plain per-query loops
+static std::vector<uint64_t> offsets_of(const std::vector<uint32_t> &lens, uint64_t first) {
+    std::vector<uint64_t> off(lens.size() + 1, first);
+    for (size_t q = 0; q < lens.size(); q++) off[q + 1] = off[q] + lens[q];
+    return off;
+}
+// a ragged input of `elem`-byte elements at `off`, every byte its own function of its place; gathered, byte by byte
+static void check_gather(const std::vector<uint64_t> &off, size_t elem, const std::vector<uint32_t> &order) {
+    const uint32_t nq = (uint32_t)order.size();
+    std::vector<uint8_t> src((off[nq] + 3) * elem);  // (elements before the first offset and behind the last one)
+    for (size_t i = 0; i < src.size(); i++) src[i] = (uint8_t)(i * 131 + i / 251 + elem);
+    const std::vector<uint64_t> new_off = kmer_gather_offsets(off.data(), order.data(), nq);
+    EXPECT(new_off.size() == (size_t)nq + 1 && new_off[0] == 0);
+    const std::vector<uint8_t> got = kmer_gather(KmerRagged{src.data(), off.data(), elem}, order.data(), nq, new_off.data());
+    EXPECT(got.size() == (new_off[nq] + 1) * elem && got.data() != nullptr);
+    uint64_t at = 0, bad = 0;
+    for (uint32_t x = 0; x < nq; x++) {
+        EXPECT(new_off[x] == at);
+        for (uint64_t i = off[order[x]]; i < off[order[x] + 1]; i++, at++)
+            for (size_t b = 0; b < elem; b++) bad += got[at * elem + b] != src[i * elem + b];
+    }
+    EXPECT(new_off[nq] == at && at == off[nq] - off[0] && bad == 0);
+}
+// a column of `bytes` per query scattered into the caller's rows, a guard row behind them
+static void check_scatter(size_t bytes, const std::vector<uint32_t> &order, bool identity) {
+    const uint32_t nq = (uint32_t)order.size();
+    std::vector<uint8_t> from((size_t)nq * bytes + 1), to(((size_t)nq + 1) * bytes + 1, 0xEE);
+    for (size_t i = 0; i < from.size(); i++) from[i] = (uint8_t)(i * 37 + i / 253 + 1);
+    kmer_scatter(KmerColumn{from.data(), bytes}, KmerColumn{to.data(), bytes}, identity ? nullptr : order.data(), nq);
+    uint64_t bad = 0;
+    for (uint32_t x = 0; x < nq; x++)
+        for (size_t b = 0; b < bytes; b++) bad += to[(size_t)(identity ? x : order[x]) * bytes + b] != from[(size_t)x * bytes + b];
+    for (size_t i = (size_t)nq * bytes; i < to.size(); i++) bad += to[i] != 0xEE;  // the guard row
+    EXPECT(bad == 0);
+}
+static void check_moves() {
+    const uint32_t S = 100, L = SINA_HIP_MAX_QUERY_LEN + 1;
+    struct Batch {
+        std::vector<uint32_t> lens, self_lens;
+        uint64_t first, self_first;
+    };
+    const std::vector<Batch> batches = {
+        {{S, 7, SINA_HIP_MAX_QUERY_LEN, S}, {2, 0, 0, 5}, 0, 0},                        // no long query
+        {{L, L + 5, 32767}, {1, 1, 1}, 0, 3},                                           // only long queries
+        {{S, L, 50, L + 9, 30}, {0, 3, 0, 0, 4}, 0, 0},                                 // long and short interleaved
+        {{S, L, 50, L + 9, 30}, {0, 0, 0, 0, 0}, 17, 5},                                // a sub-range of larger arrays; no self list at all
+        {{S, 0, L, 0, 1}, {3, 0, 2, 1, 0}, 4099, 11},                                   // queries of length 0                                
+        {{0}, {0}, 9, 9},                                                               // one empty query
+        {{}, {}, 5, 5},                                                                 // no query
+    };
+    for (const Batch &b : batches) {
+        const uint32_t nq = (uint32_t)b.lens.size();
+        const std::vector<uint64_t> qoff = offsets_of(b.lens, b.first), self_off = offsets_of(b.self_lens, b.self_first);
+        uint32_t n_fast = 0;
+        const std::vector<uint32_t> order = kmer_fast_first(qoff.data(), nq, &n_fast);
+        check_gather(qoff, 1, order);      // mask bytes ...
+        check_gather(qoff, 4, order);      // ... and packed bases, on the queries' offsets
+        check_gather(self_off, 4, order);  // the self lists on their own
+        // ids and scores of rows of 1, 10, 41 and 4097 entries, n and flag, match counts of 1 and 41 candidates, family
+        // rows of 2 + 2 * 41 words; a column without bytes (max == 0)
+        for (size_t bytes : {(size_t)1 * 4, (size_t)10 * 4, (size_t)41 * 4, (size_t)4097 * 4, (size_t)4, (size_t)1 * 2, (size_t)41 * 2, (size_t)84 * 4, (size_t)0})
+            for (int identity = 0; identity < 2; identity++) check_scatter(bytes, order, identity != 0);
+    }
+    {
+        // known values: long, short, long, short with 2, 1, 0, 3 self ids
+        const uint64_t qoff[5] = {10, 10 + L, 10 + L + S, 10 + 2 * L + S, 10 + 2 * L + 2 * S}, self_off[5] = {4, 6, 7, 7, 10};
+        const uint32_t self_ids[10] = {90, 91, 92, 93, 40, 41, 50, 60, 61, 62};
+        uint32_t n_fast = 0;
+        const std::vector<uint32_t> order = kmer_fast_first(qoff, 4, &n_fast);
+        const std::vector<uint64_t> q_new = kmer_gather_offsets(qoff, order.data(), 4), s_new = kmer_gather_offsets(self_off, order.data(), 4);
+        EXPECT(q_new[1] == S && q_new[2] == 2 * S && q_new[3] == 2 * S + L && q_new[4] == 2 * S + 2 * L);
+        EXPECT(s_new[1] == 1 && s_new[2] == 4 && s_new[3] == 6 && s_new[4] == 6);
+        const std::vector<uint8_t> got = kmer_gather(KmerRagged{self_ids, self_off, 4}, order.data(), 4, s_new.data());
+        const uint32_t want[6] = {50, 60, 61, 62, 40, 41};
+        EXPECT(got.size() == 7 * 4 && memcmp(got.data(), want, sizeof(want)) == 0);
+        uint32_t rows[4] = {1000, 1001, 1002, 1003}, back[5] = {7, 7, 7, 7, 7};
+        kmer_scatter(KmerColumn{rows, 4}, KmerColumn{back, 4}, order.data(), 4);
+        EXPECT(back[0] == 1002 && back[1] == 1000 && back[2] == 1003 && back[3] == 1001 && back[4] == 7);
+        EXPECT((KmerColumn{back, 8}.row<uint32_t>(2) == back + 4));
+    }
+}
+
 int main() {
     check_plan();
+    check_moves();
     static_assert(kBigSelBudget <= (1ull << 30), "the budget is at most 1 GiB");
     static_assert(kKmerSelMax == 4096, "the LDS select kernels' limit");
     uint32_t first, last;

@@ -2,7 +2,8 @@
 best of every query, the counts and the flags, on the directed cases of tests/rank_cases.py (list lengths, ties decided
 by the name, zero scores, scores above one, candidates without a score, duplicated ids, forced chunks, every reference
 without an id list) and on tests/compare_cases.py's worlds under every rule; sina_hip_kmer_topk_rank against
-sina_hip_kmer_topk_any followed by sina_hip_compare_rank; then every refusal.  tests/test_rank_cpu.py pins rank_ref to
+sina_hip_kmer_topk_any followed by sina_hip_compare_rank (also with long queries among short ones, which the driver
+puts last, and after a candidate-list overflow); then every refusal.  tests/test_rank_cpu.py pins rank_ref to
 the host stage and to the reference, and checks that every case reaches its edge."""
 import contextlib
 import os
@@ -12,8 +13,12 @@ import pytest
 
 from sina_amd import capi, synth
 from tests import compare_cases as cc
+from tests import kmer_big_cases as kb
+from tests import kmer_cases as kc
 from tests import rank_cases as rc
 from tests import rank_ref
+from tests import util
+from tests.test_gpu_msc import WORLD_WIDTH, _packed_queries, _world_refs
 
 pytestmark = pytest.mark.gpu
 
@@ -161,6 +166,73 @@ def test_kmer_topk_rank_equals_topk_then_compare_rank(gpu_ctx):
             assert a.tobytes() == b.tobytes()
         chunks = rc.plan(len(qs), min(kmer_candidates, refs.n), 256, forced=chunk or 0)[1]
         assert after["pairs"] - before["pairs"] == int(n.sum()) and after["launches"] - before["launches"] == (2 if chunks > 1 else 1)
+
+
+def _fused_equals_two_step(ctx, qmasks, kmer_candidates):
+    """kmer_topk_rank on the k-mer cases' mask bytes as aligned queries (base i in column i) against kmer_topk_any
+    followed by compare_rank on its lists, byte for byte; gives the lengths of the lists and by how much the fused call
+    moved the k-mer launches and the rank kernel's counters."""
+    qs = _packed_queries(qmasks, 1)
+    q_ab, q_off = cc.flat(qs), cc.offsets(qs)
+    ids, _, n = ctx.kmer_topk_any(np.concatenate(qmasks), q_off, kmer_candidates)
+    cand = [ids[q, :n[q]] for q in range(len(qs))]
+    two_step = ctx.compare_rank(q_ab, q_off, cc.flat(cand), cc.offsets(cand), 0, False, "query", 10)
+    l0, before = ctx.stats()["kmer_launches"], ctx.rank_stats()
+    fused = ctx.kmer_topk_rank(q_ab, q_off, kmer_candidates, 0, False, "query", 10)
+    l1, after = ctx.stats()["kmer_launches"], ctx.rank_stats()
+    for a, b in zip(fused, two_step):
+        assert a.tobytes() == b.tobytes(), kmer_candidates
+    return n, l1 - l0, {k: after[k] - before[k] for k in ("pairs", "launches")}
+
+
+def _kmer_world(ctx, c, width, monkeypatch):
+    """The case's hand-built index over the three-base references of tests/test_gpu_msc.py, in an alignment of `width`
+    columns, names in id order."""
+    ab, off, _, _ = _world_refs(c.n_refs)
+    ctx.upload_refs(ab, off, width)
+    util.set_knobs(monkeypatch, dense_div=None, kmer_rows=None, big_sel_bytes=None)
+    ctx.upload_index(c.k, c.nofast, c.off, c.ids)
+    ctx.upload_name_order(np.arange(c.n_refs, dtype=np.uint32))
+
+
+def test_kmer_topk_rank_long_query_among_short_ones(monkeypatch):
+    """Queries above 10 240 bases between short ones: the long count kernel's range runs behind the others and is
+    ranked in a launch of its own; ids, scores, counts and flags come back in the caller's order."""
+    c = kb.long_query()
+    qmasks = [c.qmasks[0], c.qmasks[2], kc.poly("A", 50), c.qmasks[1], kc.poly("C", 30)]
+    assert [len(m) > kc.FAST_MAX for m in qmasks] == [False, True, False, True, False]
+    width = max(len(m) for m in qmasks)                 # every query column inside the alignment
+    assert width > WORLD_WIDTH and 6 * (width // 32) + width < 150 * 1024
+    ctx = capi.Context(0)
+    try:
+        _kmer_world(ctx, c, width, monkeypatch)
+        long0 = ctx.long_queries()
+        n, _, moved = _fused_equals_two_step(ctx, qmasks, 41)
+        assert (n == 41).all()
+        assert ctx.long_queries() - long0 == 2 * 2      # (two search calls, two long queries)
+        assert moved["launches"] == 2                    # the fast range and the long one
+    finally:
+        ctx.close()
+
+
+def test_kmer_topk_rank_after_a_candidate_list_overflow(monkeypatch):
+    """cap_4097: the candidate list of the first pass overflows and the range is repeated with the score rows; the
+    overflowed pass ranks nothing, the rows ranked are those of the final select.  cap_4096: the list just fits."""
+    c = kc.cap(4097)
+    ctx = capi.Context(0)
+    try:
+        _kmer_world(ctx, c, max(WORLD_WIDTH, max(len(m) for m in c.qmasks)), monkeypatch)
+        for kmer_candidates in (41, 128):
+            n, kmer_launches, moved = _fused_equals_two_step(ctx, c.qmasks, kmer_candidates)
+            assert kmer_launches == 2                    # the overflowed pass and its repeat
+            assert moved == {"launches": 1, "pairs": int(n.sum())}
+        c1 = kc.cap(4096)
+        assert c1.n_refs == c.n_refs and [len(m) for m in c1.qmasks] == [len(m) for m in c.qmasks]
+        ctx.upload_index(c1.k, c1.nofast, c1.off, c1.ids)
+        n, kmer_launches, moved = _fused_equals_two_step(ctx, c1.qmasks, 41)
+        assert kmer_launches == 1 and moved == {"launches": 1, "pairs": int(n.sum())}
+    finally:
+        ctx.close()
 
 
 def test_kmer_topk_rank_refuses_more_than_the_lds_select_sorts():
