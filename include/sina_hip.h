@@ -415,6 +415,40 @@ const uint32_t *sina_hip_staged_rank(sina_hip_ctx *ctx);
 int sina_hip_rank_inplace_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *sequences, uint64_t *pairs,
                                 uint64_t *launches);
 
+/* ------------------------------------------------------------- --show-dist: sps, closest relative, cpm (device-dist)
+ * The counting behind Log::printer::show_dist (src/log.cpp:279-325) for sequences that arrive aligned: three
+ * comparisons per query under cseq_comparator(iupac, CMP_DIST_NONE, CMP_COVER_QUERY, false), the query side first --
+ *   self   : the input alignment `orig` against the finished alignment `aligned`, SINA_CMP_IUPAC_EXACT;
+ *   before : `orig` against the closest relative, SINA_CMP_IUPAC_OPTIMISTIC;
+ *   after  : `aligned` against the same relative, SINA_CMP_IUPAC_OPTIMISTIC
+ * -- the closest relative being the member of the query's list that std::sort by result_item::operator< puts last
+ * (src/search.h:56-68): the largest score (float)match / (float)(match + mismatch + only_a + only_a_overhang) of
+ * `orig` against it, equal scores by the reference's NAME (sina_hip_upload_name_order).  The float scores and cpm stay
+ * with the caller (cseq_comparator::score of the counters): only integers come back.
+ *
+ * sina_hip_show_dist: nq queries.
+ *   orig_ab/orig_off : concatenated packed words of the input alignments, offsets [nq+1] (as sina_hip_compare's q_ab /
+ *                      q_off; sub-ranges of larger offset arrays included)
+ *   al_ab/al_off     : the same for the finished alignments
+ *   ref_ids/ref_off  : concatenated reference ids of the queries' relatives -- a family or a search result, in any
+ *                      order --, offsets [nq+1]; ref_ids may be NULL if every list is empty
+ *   rows             : [nq][20] 32-bit words: 0..5 self, 6..11 before, 12..17 after (each in sina_hip_match_counts'
+ *                      order), 18 the closest relative's id or 0xFFFFFFFF, 19 flags -- bit 0: a member of the list had
+ *                      a denominator of 0 (the host's NaN; it is left out: the caller walks that query itself), bit 1:
+ *                      the row was computed.  Without a closest relative (an empty list, or every member left out)
+ *                      before and after are zero.
+ * A duplicated id in a list is allowed.  Refused with a message, before anything runs and with rows untouched: a null
+ * argument, a reference id out of range, no name order uploaded, offsets that descend, an orig or aligned of more than
+ * 65535 bases or whose columns do not ascend strictly.  An alignment too wide for the kernel's LDS tables is refused as
+ * a limit (sina_hip_last_error_is_limit() == 1).  nq == 0 succeeds and touches nothing.  One launch per range of
+ * queries (csrc/showdist_plan.h).
+ *
+ * sina_hip_show_dist_stats: the kernel's own time (events around its launches) and volume on this context since init /
+ * fork: queries scored, (orig, member) pairs compared, launches. */
+int sina_hip_show_dist(sina_hip_ctx *ctx, const uint32_t *orig_ab, const uint64_t *orig_off, const uint32_t *al_ab,
+                       const uint64_t *al_off, uint32_t nq, const uint32_t *ref_ids, const uint64_t *ref_off, uint32_t *rows);
+int sina_hip_show_dist_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches);
+
 /* ------------------------------------------------------------- alignment
  * Replaces, for a batch of queries: mseq::mseq + sort + reduce_edges
  * (src/mseq.cpp:47-118, src/graph.h:451-488) when given family ids, compute()

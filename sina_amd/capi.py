@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "sina_hip_align_count_pairs", "sina_hip_staged_pair_counts", "sina_hip_pair_inplace_stats",
     "sina_hip_align_count_identity", "sina_hip_staged_identity", "sina_hip_identity_inplace_stats",
     "sina_hip_align_rank", "sina_hip_staged_rank", "sina_hip_rank_inplace_stats",
+    "sina_hip_show_dist", "sina_hip_show_dist_stats",
     "sina_hip_staged_shift_log", "sina_hip_assemble_stats", "sina_hip_debug_assemble", "sina_hip_debug_assemble_ms",
 ]
 
@@ -209,6 +210,8 @@ def load():
     L.sina_hip_staged_identity.restype = C.POINTER(C.c_uint32)
     L.sina_hip_staged_identity.argtypes = [vp]
     L.sina_hip_identity_inplace_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
+    L.sina_hip_show_dist.argtypes = [vp, u32p, u64p, u32p, u64p, C.c_uint32, u32p, u64p, u32p]
+    L.sina_hip_show_dist_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
     L.sina_hip_align_rank.argtypes = [vp, C.c_int, C.c_uint, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32]
     L.sina_hip_staged_rank.restype = C.POINTER(C.c_uint32)
     L.sina_hip_staged_rank.argtypes = [vp]
@@ -638,6 +641,24 @@ class Context:
     def pair_stats(self):
         """The pair-count kernel on this context so far: dict(kernel_ms, sequences, entries_visited, launches)."""
         return self._counters(self.L.sina_hip_pair_stats, KERNEL_MS + u64_fields("sequences", "entries_visited", "launches"))
+
+    def show_dist(self, orig_ab, orig_off, al_ab, al_off, ref_ids, ref_off, out=None):
+        """The counters behind --show-dist: uint32 [nq, 20] -- words 0..5 the input alignment against the finished one
+        (exact IUPAC), 6..11 the input alignment and 12..17 the finished one against the closest relative of the list
+        (optimistic), each in sina_hip_match_counts' order; word 18 that relative's reference id (0xFFFFFFFF: none);
+        word 19 flags (bit 0: a member had no score, bit 1: computed).  The store needs a name order
+        (upload_name_order).  out: the array to write into."""
+        orig_ab, al_ab, ref_ids = _c(orig_ab, np.uint32), _c(al_ab, np.uint32), _c(ref_ids, np.uint32)
+        orig_off, al_off, ref_off = _c(orig_off, np.uint64), _c(al_off, np.uint64), _c(ref_off, np.uint64)
+        nq = len(orig_off) - 1
+        rows = out if out is not None else np.zeros((nq, 20), np.uint32)
+        self._check(self.L.sina_hip_show_dist(self.h, _ptr(orig_ab, u32p), _ptr(orig_off, u64p), _ptr(al_ab, u32p), _ptr(al_off, u64p),
+                                              nq, _ptr(ref_ids, u32p), _ptr(ref_off, u64p), _ptr(rows, u32p)))
+        return rows
+
+    def show_dist_stats(self):
+        """The show-dist kernel on this context so far: dict(kernel_ms, sequences, pairs, launches)."""
+        return self._counters(self.L.sina_hip_show_dist_stats, KERNEL_MS + u64_fields("sequences", "pairs", "launches"))
 
     def count_pairs(self, on=True):
         """The switch of the in-place pair count: with it on, an align call with assemble=1 on a store with a helix map

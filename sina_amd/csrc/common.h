@@ -34,6 +34,7 @@ void set_limit_error(const std::string &msg);
 //                                        wide=1 (every query of sina_hip_align_graphs_any takes the wide kernel)  wide_cells=N (its budget, cells per launch)
 //                                        match_floor=N  match_loads=1 (the match-count kernel's chunk floor / one load in flight: tools/perf_msc.py)
 //                                        pair_words=N (words per launch range of the pair-count kernel, pairs.hip)
+//                                        showdist_range=N (queries per launch range of the show-dist kernel, showdist.hip)
 //                                        profile_tile=N (at most N nodes per LDS tile of the family profile kernel, profile_build.hip)
 //                                        dp_range_q=N (at most N queries per DP launch range: a small call takes several)
 //                                        fam_chunk_q=N (at most N queries per DAG / profile build chunk of the family entries)

@@ -56,6 +56,9 @@ static aligner::options al_defaults() {  // src/align.cpp:231-274
     // the search stage's rows from the align call itself (sina_hip_align_rank) instead of a second trip with the
     // finished sequences (default off)
     o.device_search = false;
+    // --show-dist's comparisons in one device call per batch (sina_hip_show_dist, show_dist_batch) instead of the
+    // sink's walks: on request, until it has been decided on measurements
+    o.device_dist = false;
     return o;
 }
 static aligner::options &al_opts() {
@@ -101,6 +104,7 @@ void aligner::set_option(const std::string &name, const std::string &value) {
     else if (name == "device-idty") o.device_idty = to_bool(value);
     else if (name == "device-shift") o.device_shift = to_bool(value);
     else if (name == "device-search") o.device_search = to_bool(value);
+    else if (name == "device-dist") o.device_dist = to_bool(value);
     else if (name == "db") o.database = value;
     else throw std::logic_error("aligner: unknown option " + name);
 }

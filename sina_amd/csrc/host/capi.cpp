@@ -79,6 +79,10 @@ struct result {
     const void *family_owner = nullptr;
     void (*family_render)(const void *, const uint64_t *, size_t, std::string &) = nullptr;
     float idty = -1.f;              // align_ident_slv (--calc-idty), -1 if not computed
+    // --show-dist (host option show-dist): sps, idty, cpm and the closest relative's id where the report has one
+    float dist[3] = {0.f, 0.f, 0.f};
+    uint32_t dist_closest = 0xFFFFFFFFu;
+    bool have_dist = false;
     float bps = 0.f;                // the helix base-pair score (align_bp_score_slv = (int)(100 * bps)); 0 without a helix map
     bool searched = false;          // search stage ran and produced a result vector
     std::vector<uint32_t> sr_ids;   // search results, best first
@@ -163,6 +167,24 @@ void extract_tray(pipeline *p, tray &t, result &r, uint32_t query_bases, const r
     if (t.aligned_sequence) {
         cseq &c = *t.aligned_sequence;
         r.bps = tray_pair_score(t, helix);
+        if (show_dist_wanted()) {  // (the metric alone: the report's text is the FASTA drivers')
+            log_printer::report rep;
+            show_dist_of_tray(t, rep);
+            if (rep.has_closest) {
+                r.dist[0] = rep.sps;
+                r.dist[1] = rep.idty;
+                r.dist[2] = rep.cpm;
+                r.dist_closest = rep.closest_id;
+                if (rep.closest_seq != nullptr)
+                    for (const std::string &key : {aligner::opts->database, search_filter_database()})
+                        if (const std::shared_ptr<reference_store> st = key.empty() ? nullptr : reference_store::find(key))
+                            if (st->owns(rep.closest_seq)) {
+                                r.dist_closest = st->id_of(rep.closest_seq);
+                                break;
+                            }
+                r.have_dist = true;
+            }
+        }
         r.width = c.getWidth();
         r.status = (r.log.find("copied alignment from") != std::string::npos) ? 1 : 0;
         // one walk over the attributes, the stages' own keys told by their interned addresses
@@ -409,6 +431,50 @@ int sina_host_store_search_inplace_stats(const char *key, uint64_t *trays, doubl
         reference_store::get(key)->search_inplace_stats(trays, kernel_ms, sequences, pairs, launches);
     });
 }
+// the aligner's device-dist on this store: trays whose --show-dist counters came from the device, and the show-dist
+// kernel's time and volume (sina_hip_show_dist_stats) on its contexts -- between runs
+int sina_host_store_show_dist_stats(const char *key, uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs,
+                                    uint64_t *launches) {
+    return guarded([&] {
+        if (!trays || !kernel_ms || !sequences || !pairs || !launches) throw std::logic_error("store_show_dist_stats: null argument");
+        reference_store::get(key)->show_dist_stats(trays, kernel_ms, sequences, pairs, launches);
+    });
+}
+// show_dist_report alone (no device), for tests: nq (orig, aligned) pairs as packed words of the store's width, their
+// relatives as reference ids of the store; rows: null -- the host walk -- or [nq][20] counters to take instead
+// (sina_hip_show_dist's rows).  out [nq][3]: sps, idty, cpm; flags [nq]: bit 0 has_sps, bit 1 has_closest; closest [nq];
+// text (optional): the reports' lines, truncated at cap.
+int sina_host_show_dist_reports(const char *key, const uint32_t *orig_ab, const uint64_t *orig_off, const uint32_t *al_ab,
+                                const uint64_t *al_off, uint32_t nq, const uint32_t *ref_ids, const uint64_t *ref_off,
+                                const uint32_t *rows, float *out, uint32_t *flags, uint32_t *closest, char *text, uint32_t cap) {
+    return guarded([&] {
+        if (!orig_ab || !orig_off || !al_ab || !al_off || !ref_off || !out || !flags || !closest)
+            throw std::logic_error("show_dist_reports: null argument");
+        const std::shared_ptr<reference_store> st = reference_store::get(key);
+        std::string all;
+        for (uint32_t q = 0; q < nq; q++) {
+            cseq orig("orig"), aligned("aligned");
+            orig.setAlignedBases(reinterpret_cast<const aligned_base *>(orig_ab + orig_off[q]), (size_t)(orig_off[q + 1] - orig_off[q]));
+            aligned.setAlignedBases(reinterpret_cast<const aligned_base *>(al_ab + al_off[q]), (size_t)(al_off[q + 1] - al_off[q]));
+            orig.setWidth(st->getAlignmentWidth());
+            aligned.setWidth(st->getAlignmentWidth());
+            search::result_vector ref;
+            for (uint64_t i = ref_off[q]; i < ref_off[q + 1]; i++) {
+                if (ref_ids[i] >= st->size()) throw std::logic_error("show_dist_reports: reference id out of range");
+                ref.emplace_back(0.f, &st->getCseq(ref_ids[i]));
+            }
+            log_printer::report rep;
+            show_dist_report(orig, aligned, ref, rows ? rows + 20 * (size_t)q : nullptr, rep);
+            out[3 * (size_t)q] = rep.sps;
+            out[3 * (size_t)q + 1] = rep.idty;
+            out[3 * (size_t)q + 2] = rep.cpm;
+            flags[q] = (rep.has_sps ? 1u : 0u) | (rep.has_closest ? 2u : 0u);
+            closest[q] = rep.closest_seq ? st->id_of(rep.closest_seq) : rep.closest_id;
+            all += rep.text;
+        }
+        if (text && cap) snprintf(text, cap, "%s", all.c_str());
+    });
+}
 // the aligner's finish step on this store: trays the device had assembled / the host finished, and the device
 // assembly's volume (sina_hip_assemble_stats) on its contexts -- between runs
 int sina_host_store_assemble_stats(const char *key, uint64_t *trays_device, uint64_t *trays_host, uint64_t *queries, uint64_t *assembled,
@@ -544,6 +610,8 @@ static int run_fasta(const char *in_path, const char *out_path, const char *log_
                      uint32_t batch, double *summary7, bool staged) {
     return guarded([&] {
         fasta_run r(in_path, out_path, log_path, do_search, show_dist);
+        const show_dist_scope dist_scope(show_dist != 0);  // (what show_dist_batch asks; the host option is the pipeline's)
+        show_dist_prepare();
         if (batch == 0) batch = 1024;
         std::vector<log_printer::report> reports;
         auto sink_serial = [&](std::vector<tray> &trays) {
@@ -557,7 +625,10 @@ static int run_fasta(const char *in_path, const char *out_path, const char *log_
         };
         auto sink_staged = [&](std::vector<tray> &trays) {
             reports.resize(trays.size());
-            parallel_for(trays.size(), [&](size_t i) { r.lp->render(trays[i], reports[i]); });
+            {
+                host_phase hp("sink.report");  // (the log reports, --show-dist's walks among them: tools/perf_showdist.py)
+                parallel_for(trays.size(), [&](size_t i) { r.lp->render(trays[i], reports[i]); });
+            }
             r.wr->precompose(trays);  // (after render: the reports' attributes are part of the records' meta data)
             for (size_t i = 0; i < trays.size(); i++) {
                 tray &t = trays[i];
@@ -580,6 +651,7 @@ static int run_fasta(const char *in_path, const char *out_path, const char *log_
                 r.al(trays);
                 if (r.sf) (*r.sf)(trays);
                 pair_score_batch(trays);
+                show_dist_batch(trays);  // (nothing unless the run shows dist and the aligner's device-dist is on)
             });
         if (staged) {
             tune_allocator();
@@ -709,6 +781,7 @@ int sina_host_reset_options(void) {
     aligner::reset_options();
     search_filter::reset_options();
     rw_fasta::reset_options();
+    set_show_dist(false);
     return 0;
 }
 
@@ -727,6 +800,7 @@ int sina_host_set_option(const char *stage, const char *name, const char *value)
         else if (!strcmp(stage, "fasta")) rw_fasta::set_option(name, value);
         else if (!strcmp(stage, "host") && !strcmp(name, "threads")) set_host_threads((unsigned)atoi(value));
         else if (!strcmp(stage, "host") && !strcmp(name, "dedup")) set_batch_dedup(atoi(value) != 0);
+        else if (!strcmp(stage, "host") && !strcmp(name, "show-dist")) set_show_dist(atoi(value) != 0);
         else throw std::logic_error(std::string("unknown stage ") + stage);
     });
 }
@@ -787,6 +861,7 @@ template <class Fill>
 static int run_queries(pipeline *p, uint32_t nq, const uint64_t *qoff, uint32_t batch, uint32_t inflight, Fill &&fill) {
     return guarded([&] {
         host_profile_mark("MARK:run-entered");
+        show_dist_prepare();
         if (batch == 0) batch = nq ? nq : 1;
         if (p->chunk_q != batch) p->chunks.clear();  // (chunks follow the batch size)
         p->chunk_q = batch;
@@ -827,6 +902,7 @@ static int run_queries(pipeline *p, uint32_t nq, const uint64_t *qoff, uint32_t 
             timed(al_ns, [&] { p->al(it.trays); });
             if (p->sf) timed(sf_ns, [&] { (*p->sf)(it.trays); });
             pair_score_batch(it.trays);  // (nothing without a helix map)
+            show_dist_batch(it.trays);   // (nothing without the host option show-dist and the aligner's device-dist)
         };
         auto extract = [&](item &it) {  // sink
             {
@@ -1041,6 +1117,18 @@ const char *sina_host_result_attr(void *pp, uint32_t q, const char *name) {
     const result &r = result_at(pp, q);
     const std::string *v = r.attrs.find(name);
     return v ? v->c_str() : "";
+}
+// --show-dist of query q (host option show-dist, sina_host_pipeline_run_aligned): out = sps, idty, cpm, closest = the
+// closest relative's reference id; have = 0 where the report has no closest relative (no alignment, no relatives, widths
+// that differ) or the run had no alignment to compare with
+int sina_host_result_dist(void *pp, uint32_t q, float out[3], uint32_t *closest, int *have) {
+    pipeline *p = (pipeline *)pp;
+    if (q >= p->n_results || !out || !closest || !have) return 1;
+    const result &r = result_at(pp, q);
+    memcpy(out, r.dist, sizeof r.dist);
+    *closest = r.dist_closest;
+    *have = r.have_dist ? 1 : 0;
+    return 0;
 }
 double sina_host_search_seconds(void *pp) { return ((pipeline *)pp)->sf_s; }
 float sina_host_result_idty(void *pp, uint32_t q) { return result_at(pp, q).idty; }

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "stages.h"
+#include "../showdist_plan.h"
 
 namespace sina {
 
@@ -656,7 +657,9 @@ log_printer::~log_printer() = default;
 //   orig_closest_idty  identity of the input alignment with its closest relative,
 //   closest_idty       identity of the new alignment with that same relative,
 // and cpm, the loss against the closest relative: orig_closest_idty - closest_idty.
-static void show_dist_report(cseq &orig, cseq &aligned, search::result_vector &ref, log_printer::report &out) {
+// row: the tray's counters where the device has compared (tray::dist_row, sina_hip_show_dist's layout) -- the floats are
+// then cseq_comparator::score of them, the same function of the same integers the walk ends in -- or null: walk.
+void show_dist_report(cseq &orig, cseq &aligned, search::result_vector &ref, const uint32_t *row, log_printer::report &out) {
     auto report = [&](const char *what, float v) {
         char line[96];
         snprintf(line, sizeof line, "%s: %.6f\n", what, (double)v);
@@ -670,7 +673,12 @@ static void show_dist_report(cseq &orig, cseq &aligned, search::result_vector &r
                     std::to_string(orig.getWidth()) + " and " + std::to_string(aligned.getWidth()) + "\n";
         return;
     }
-    const float sps = identity(orig, aligned, CMP_IUPAC_EXACT);
+    auto from_row = [&](uint32_t at) {
+        sina_hip_match_counts m;
+        memcpy(&m, row + at, sizeof m);
+        return cseq_comparator(CMP_IUPAC_OPTIMISTIC, CMP_DIST_NONE, CMP_COVER_QUERY, false).score(m);
+    };
+    const float sps = row ? from_row(sina_hip::kShowDistSelf) : identity(orig, aligned, CMP_IUPAC_EXACT);
     report("orig_idty", sps);
     out.has_sps = true;
     out.sps = sps;
@@ -681,11 +689,20 @@ static void show_dist_report(cseq &orig, cseq &aligned, search::result_vector &r
     // the closest relative of the input alignment: the last of the relatives sorted by identity
     // (std::sort on a copy, as the reference does: which of several equally close ones that is, is
     // the sort's business)
-    search::result_vector by_identity(ref);
-    for (search::result_item &r : by_identity) r.score = identity(orig, *r.sequence, CMP_IUPAC_OPTIMISTIC);
-    std::sort(by_identity.begin(), by_identity.end());
-    const search::result_item &closest = by_identity.back();
-    const float before = closest.score, after = identity(aligned, *closest.sequence, CMP_IUPAC_OPTIMISTIC);
+    float before, after;
+    if (row) {  // (a set row of a tray with relatives has a closest one: show_dist_batch sets no other)
+        before = from_row(sina_hip::kShowDistBefore);
+        after = from_row(sina_hip::kShowDistAfter);
+        out.closest_id = row[sina_hip::kShowDistClosest];
+    } else {
+        search::result_vector by_identity(ref);
+        for (search::result_item &r : by_identity) r.score = identity(orig, *r.sequence, CMP_IUPAC_OPTIMISTIC);
+        std::sort(by_identity.begin(), by_identity.end());
+        const search::result_item &closest = by_identity.back();
+        before = closest.score;
+        after = identity(aligned, *closest.sequence, CMP_IUPAC_OPTIMISTIC);
+        out.closest_seq = closest.sequence;
+    }
     report("orig_closest_idty", before);
     report("closest_idty", after);
     report("cpm", before - after);
@@ -730,12 +747,14 @@ void log_printer::render(tray &t, report &out) const {
         log += attr_to_string(ap.second);
         log += "\n";
     }
-    if (data->show_dist) {
-        search::result_vector ref;
-        if (t.search_result != nullptr) ref = *t.search_result;
-        else if (t.alignment_reference != nullptr) ref = *t.alignment_reference;
-        show_dist_report(*t.input_sequence, aligned, ref, out);
-    }
+    if (data->show_dist) show_dist_of_tray(t, out);
+}
+
+void show_dist_of_tray(tray &t, log_printer::report &out) {
+    search::result_vector ref;
+    if (t.search_result != nullptr) ref = *t.search_result;
+    else if (t.alignment_reference != nullptr) ref = *t.alignment_reference;
+    show_dist_report(*t.input_sequence, *t.aligned_sequence, ref, t.dist_row_set ? t.dist_row.data() : nullptr, out);
 }
 
 // ... and what does: the count and the running totals, in tray order (the sums are doubles: their order shows)

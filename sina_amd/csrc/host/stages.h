@@ -18,6 +18,7 @@
 
 #include <condition_variable>
 #include <deque>
+#include <array>
 #include <atomic>
 #include <functional>
 #include <future>
@@ -210,6 +211,11 @@ public:
     // slot's staged row cut to its length -- n, flags (bit 0: a candidate without a score, bit 1: ranked), n ids, n
     // score bit patterns --, shared by the trays of a slot.  Null: the search stage takes its own path.
     std::shared_ptr<const std::vector<uint32_t>> search_row;
+    // The --show-dist counters of the tray where a batch driver's step (show_dist_batch, device-dist) has computed
+    // them: sina_hip_show_dist's row -- self, before, after, the closest relative's id, the flags.  Not set: the sink
+    // walks (show_dist_report).
+    std::array<uint32_t, 20> dist_row{};
+    bool dist_row_set{false};
     std::string log_text() const;   // log, with a pending score line rendered in its place
     void clear_log() {
         log.str(std::string());
@@ -373,6 +379,10 @@ public:
     // and the in-place ranking's time and volume on the store's contexts -- sina_hip_rank_inplace_stats
     void count_search_inplace(uint64_t trays) { n_search_inplace.fetch_add(trays, std::memory_order_relaxed); }
     void search_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches);
+    // the aligner's device-dist (show_dist_batch): trays whose --show-dist counters came from the device since the store
+    // was opened, and the show-dist kernel's time and volume on the store's contexts -- sina_hip_show_dist_stats
+    void count_show_dist(uint64_t trays) { n_show_dist.fetch_add(trays, std::memory_order_relaxed); }
+    void show_dist_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches);
     // whether the index in HBM is the one of this k / nofast (ensure_index, adopt_index)
     bool index_is(unsigned k, bool nofast) {
         std::lock_guard<std::mutex> lk(gpu_mu);
@@ -411,7 +421,7 @@ private:
     std::once_flag name_ids_once;
     std::atomic<int> name_order_state{0};  // 0: not looked at, 1: uploaded, 2: names repeat
     std::atomic<uint64_t> n_ranked{0}, n_rank_host{0};
-    std::atomic<uint64_t> n_bp_inplace{0}, n_idty_inplace{0}, n_search_inplace{0};
+    std::atomic<uint64_t> n_bp_inplace{0}, n_idty_inplace{0}, n_search_inplace{0}, n_show_dist{0};
     std::atomic<uint64_t> n_fin_device{0}, n_fin_host{0};
     pair_map helix;
     std::mutex helix_mu;
@@ -523,6 +533,7 @@ public:
                             // (sina_hip_align_families_wsets; default on) instead of one call per filter
         bool device_bps;    // a store with a helix map: the align call counts the base pairs of the queries it assembles and
                             // their trays leave the aligner scored (sina_hip_align_count_pairs; default off)
+        bool device_dist;   // --show-dist: a batch driver's step (show_dist_batch) counts on the device what the sink would walk (default off)
         bool device_idty;   // calc-idty: the align call of a device-built group scores the queries it assembles against their
                             // families and their trays take that identity (sina_hip_align_count_identity; default off)
         bool device_shift;  // the device also finishes alignments whose insertions shift their neighbours (assemble = 2,
@@ -672,6 +683,10 @@ public:
         std::string text;
         bool aligned = false, has_sps = false, has_closest = false;
         float sps = 0, idty = 0, cpm = 0, bps = 0;
+        // the closest relative (has_closest): the sequence where the host walked, the reference id where the tray
+        // brought its counters (tray::dist_row)
+        const cseq *closest_seq = nullptr;
+        uint32_t closest_id = 0xFFFFFFFFu;
     };
     explicit log_printer(bool show_dist);
     log_printer(const log_printer &);
@@ -693,6 +708,29 @@ reference_store::pair_map aligner_pair_map();
 void pair_score_batch(std::vector<tray> &batch);
 // a tray's score for its sink: the field if set, else the host walk over `map`, else (no map, or not aligned) 0
 float tray_pair_score(const tray &t, const reference_store::pair_map &map);
+
+// ---------------------------------------------------------------- --show-dist (sps, closest relative, cpm)
+// Whether the run in progress shows dist: the FASTA drivers' argument for the length of their run (show_dist_scope),
+// the host option "show-dist" for a pipeline (Pipeline(show_dist=True)).
+bool show_dist_wanted();
+void set_show_dist(bool on);
+struct show_dist_scope {
+    bool before;
+    explicit show_dist_scope(bool on) : before(show_dist_wanted()) { set_show_dist(on); }
+    ~show_dist_scope() { set_show_dist(before); }
+};
+// The step of a batch driver behind pair_score_batch: with show-dist wanted and the aligner's device-dist on, the
+// trays of the batch get their dist_row from ONE sina_hip_show_dist call over a dev_compare context of the store that
+// owns their relatives (search_result where the tray has one, else alignment_reference: what the report picks).  A tray
+// the device cannot take keeps the host walk (see host/show_dist.cpp); nothing of this reaches a tray's log.
+void show_dist_batch(std::vector<tray> &batch);
+// ... and what a driver does before its threads start: the stores' name order computed and uploaded now (the first
+// batch would do it in the middle of the run: an allocation and a copy beside resident kernels)
+void show_dist_prepare();
+// The report's show-dist part for one tray (src/log.cpp:279-325): from the tray's dist_row if set, else by walking.
+void show_dist_of_tray(tray &t, log_printer::report &out);
+// ... and for sequences given directly: ref the relatives; row: a set row (sina_hip_show_dist's) or null to walk
+void show_dist_report(cseq &orig, cseq &aligned, search::result_vector &ref, const uint32_t *row, log_printer::report &out);
 
 // text of a family attribute kept as a list (annotated_cseq::lazy_text; famfinder sets it, sinks may keep the list)
 void render_family_list(const void *store, const uint64_t *items, size_t n, std::string &out);

@@ -51,7 +51,7 @@ tray::tray(const tray &o)
     : seqno(o.seqno), input_sequence(o.input_sequence), aligned_sequence(o.aligned_sequence),
       alignment_reference(o.alignment_reference), search_result(o.search_result), astats(o.astats),
       family_scores_kmer_k(o.family_scores_kmer_k), query_kmer_count(o.query_kmer_count), bp_score(o.bp_score),
-      bp_score_set(o.bp_score_set), search_row(o.search_row) {
+      bp_score_set(o.bp_score_set), search_row(o.search_row), dist_row(o.dist_row), dist_row_set(o.dist_row_set) {
     log.str(o.log.str());
     log.seekp(0, std::ios_base::end);
     pending_score = o.pending_score;
@@ -104,6 +104,8 @@ tray &tray::operator=(const tray &o) {
     bp_score = o.bp_score;
     bp_score_set = o.bp_score_set;
     search_row = o.search_row;
+    dist_row = o.dist_row;
+    dist_row_set = o.dist_row_set;
     return *this;
 }
 alignment_stats *alignment_stats::shared_default() {
@@ -122,6 +124,7 @@ void tray::destroy() {  // (src/tray.cpp:77-86; the objects go back to their cac
     bp_score = 0.f;
     bp_score_set = false;
     search_row.reset();
+    dist_row_set = false;
 }
 
 // ================================================================ reference_store
@@ -382,6 +385,10 @@ void reference_store::identity_inplace_stats(uint64_t *trays, double *kernel_ms,
 void reference_store::search_inplace_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches) {
     sum_kernel_use("sina_hip_rank_inplace_stats", sina_hip_rank_inplace_stats, kernel_ms, sequences, pairs, launches);
     *trays = n_search_inplace.load(std::memory_order_relaxed);
+}
+void reference_store::show_dist_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches) {
+    sum_kernel_use("sina_hip_show_dist_stats", sina_hip_show_dist_stats, kernel_ms, sequences, pairs, launches);
+    *trays = n_show_dist.load(std::memory_order_relaxed);
 }
 void reference_store::assemble_stats(uint64_t *trays_device, uint64_t *trays_host, uint64_t *queries, uint64_t *assembled,
                                      uint64_t *shifted_queries, uint64_t *shifted_runs) {

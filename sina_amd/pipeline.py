@@ -101,6 +101,10 @@ def load_host():
     H.sina_host_store_pair_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p]
     H.sina_host_store_identity_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_store_search_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_store_show_dist_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_show_dist_reports.argtypes = [C.c_char_p, capi.u32p, capi.u64p, capi.u32p, capi.u64p, C.c_uint32, capi.u32p, capi.u64p,
+                                              capi.u32p, capi.f32p, capi.u32p, capi.u32p, C.c_char_p, C.c_uint32]
+    H.sina_host_result_dist.argtypes = [vp, C.c_uint32, capi.f32p, capi.u32p, C.POINTER(C.c_int)]
     H.sina_host_store_assemble_stats.argtypes = [C.c_char_p] + [capi.u64p] * 6
     H.sina_host_pair_score.argtypes =[C.c_char_p, capi.u32p, C.c_uint32, capi.f32p, capi.u32p]
     H.sina_host_pair_scores_packed.argtypes = [capi.u32p, capi.u64p, C.c_uint32, capi.u32p, C.c_uint32, capi.f32p, capi.u32p,
@@ -314,6 +318,15 @@ class Store:
         d["kernel_ms"] = d.pop("kernel_ms")  # (the dict ends with it)
         return d
 
+    def show_dist_stats(self):
+        """The aligner's device-dist on this store so far: dict(trays, sequences, pairs, launches, kernel_ms) -- trays
+        whose --show-dist counters came from the device, and the show-dist kernel's queries, (query, relative) pairs,
+        launches and time on the store's contexts -- between runs, like identity_inplace_stats()."""
+        d = self._counters(self.H.sina_host_store_show_dist_stats, capi.u64_fields("trays") + capi.KERNEL_MS +
+                           capi.u64_fields("sequences", "pairs", "launches"))
+        d["kernel_ms"] = d.pop("kernel_ms")  # (the dict ends with it)
+        return d
+
     def assemble_stats(self):
         """The aligner's finish step on this store so far: dict(trays_device, trays_host, queries, assembled,
         shifted_queries, shifted_runs) -- trays whose alignment the device had assembled and trays the host finished
@@ -330,11 +343,16 @@ class Pipeline:
     """famfinder + aligner (+ search_filter when `search` is given, as `sina --search`) over one Store.
     Options use SINA's command-line names."""
 
-    def __init__(self, store, famfinder=None, aligner=None, host_threads=None, search=None, dedup=True):
+    def __init__(self, store, famfinder=None, aligner=None, host_threads=None, search=None, dedup=True, show_dist=False):
         self.H = load_host()
         self.store = store
         self.H.sina_host_reset_options()
         self._set("host", "dedup", bool(dedup))  # repeated queries of a batch go to the device once
+        # --show-dist for run_aligned: result(q)["dist"] (the aligner's device-dist counts it on the device)
+        self.show_dist = bool(show_dist)
+        self._aligned_run = False
+        if self.show_dist:
+            self._set("host", "show-dist", True)
         self._set("famfinder", "db", store.key)
         self._set("aligner", "db", store.key)
         for k, v in (famfinder or {}).items():
@@ -363,6 +381,7 @@ class Pipeline:
         qmask = np.ascontiguousarray(qmask, np.uint8)
         qoff = np.ascontiguousarray(qoff, np.uint64)
         self.nq = len(qoff) - 1
+        self._aligned_run = False
         _chk(self.H.sina_host_pipeline_run(self.h, qmask.ctypes.data_as(capi.u8p), qoff.ctypes.data_as(capi.u64p),
                                            self.nq, batch, inflight))
         return self.timings()
@@ -371,11 +390,12 @@ class Pipeline:
         """run() for ALIGNED queries under their own names: q_ab / q_off the packed aligned bases (column | mask << 24)
         of every query, names[q] its name.  This is what reaches famfinder's identity filter (fs-msc-max) and
         fs-leave-query-out -- a leave-out run takes its queries from the references themselves.  Results through
-        result(q)."""
+        result(q); with show_dist=True the alignment given here is what result(q)["dist"] compares the new one with."""
         q_ab = np.ascontiguousarray(q_ab, np.uint32)
         q_off = np.ascontiguousarray(q_off, np.uint64)
         self.nq = len(q_off) - 1
         assert len(names) == self.nq
+        self._aligned_run = True
         arr = (C.c_char_p * max(self.nq, 1))(*[n.encode() for n in names])
         _chk(self.H.sina_host_pipeline_run_aligned(self.h, q_ab.ctypes.data_as(capi.u32p), q_off.ctypes.data_as(capi.u64p),
                                                    arr, self.nq, batch, inflight))
@@ -390,6 +410,7 @@ class Pipeline:
         qmask = np.ascontiguousarray(qmask, np.uint8)
         qoff = np.ascontiguousarray(qoff, np.uint64)
         self.nq = len(qoff) - 1
+        self._aligned_run = False
         failed = np.zeros(max(self.nq, 1), np.uint8)
         err = C.create_string_buffer(512)
         _chk(self.H.sina_host_pipeline_run_single_trays(self.h, qmask.ctypes.data_as(capi.u8p),
@@ -421,6 +442,14 @@ class Pipeline:
         _chk(self.H.sina_host_result_bps(self.h, q, C.byref(bps), C.byref(bp_attr)))
         d["bps"] = np.float32(bps.value)  # the helix base-pair score; 0 without a helix map (Store.set_pairs)
         d["bp_score"] = bp_attr.value     # align_bp_score_slv
+        # --show-dist: sps, idty, cpm and the closest relative's id; None where the report has no closest relative,
+        # without show_dist=True, and after run(), which has no alignment to compare with
+        d["dist"] = None
+        if self.show_dist and self._aligned_run:
+            f3, closest, have = np.zeros(3, np.float32), C.c_uint32(), C.c_int()
+            _chk(self.H.sina_host_result_dist(self.h, q, f3.ctypes.data_as(capi.f32p), C.byref(closest), C.byref(have)))
+            if have.value:
+                d["dist"] = dict(sps=f3[0], idty=f3[1], cpm=f3[2], closest=closest.value)
         if self.has_search:
             ids = np.zeros(4096, np.uint32)
             sc = np.zeros(4096, np.float32)

@@ -163,6 +163,13 @@ int sina_hip_pair_inplace_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, uint
 // (likewise: the switch is taken, an align call of the stub scores no family)
 int sina_hip_align_count_identity(sina_hip_ctx *, int) { return 0; }
 const uint32_t *sina_hip_staged_identity(sina_hip_ctx *) { return nullptr; }
+int sina_hip_show_dist(sina_hip_ctx *, const uint32_t *, const uint64_t *, const uint32_t *, const uint64_t *, uint32_t, const uint32_t *,
+                       const uint64_t *, uint32_t *) { g_err = "stub"; return 1; }
+int sina_hip_show_dist_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, uint64_t *pairs, uint64_t *launches) {
+    *ms = 0;
+    *seqs = *pairs = *launches = 0;
+    return 0;
+}
 int sina_hip_identity_inplace_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, uint64_t *pairs, uint64_t *launches) {
     *ms = 0;
     *seqs = *pairs = *launches = 0;
