@@ -449,6 +449,33 @@ int sina_hip_show_dist(sina_hip_ctx *ctx, const uint32_t *orig_ab, const uint64_
                        const uint64_t *al_off, uint32_t nq, const uint32_t *ref_ids, const uint64_t *ref_off, uint32_t *rows);
 int sina_hip_show_dist_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches);
 
+/* ------------------------------------------------------------- the aligner's exact-relative test (device-copy)
+ * boost::icontains / ifind_first of the query's unaligned bases in a family member's (src/align.cpp:329-388), for
+ * every (query, reference) pair of a batch.  Upper-cased characters of two bases are equal exactly when the four base
+ * bits of their masks are (T and U share a code, bit 4 is the case), so the device compares `mask & 0xF` for EQUALITY:
+ * a query N does not match a reference A.
+ *
+ * sina_hip_find_bases: nq queries.
+ *   qmask/q_off       : concatenated mask bytes of the queries, one per base (as sina_hip_kmer_topk takes them),
+ *                       offsets [nq+1]; sub-ranges of larger offset arrays included
+ *   cand_ids/cand_off : concatenated reference ids of the queries' candidates, offsets [nq+1] (as
+ *                       sina_hip_match_count's)
+ *   out_at            : out_at[cand_off[q] + i] belongs to candidate i of query q: std::string::find's answer -- the
+ *                       lowest start, in bases of the reference, at which the reference holds the query's n bases, or
+ *                       0xFFFFFFFF without one or with more query bases than reference bases.  "The reference IS the
+ *                       query" is at == 0 with equal lengths.
+ * The call blocks until out_at is written.  Refused with a message, before anything runs and with out_at untouched:
+ * a null argument, no references uploaded, a reference id out of range, offsets that descend, a query of 0 or of more
+ * than 65535 bases.  cand_off[nq] == cand_off[0] succeeds and launches nothing.  One launch per range of pairs
+ * (csrc/contain_plan.h).
+ *
+ * sina_hip_find_bases_stats: the kernel's own time (events around its launches) and volume on this context since init /
+ * fork: pairs answered, bases of their references, launches. */
+int sina_hip_find_bases(sina_hip_ctx *ctx, const uint8_t *qmask, const uint64_t *q_off, uint32_t nq,
+                        const uint32_t *cand_ids, const uint64_t *cand_off, uint32_t *out_at);
+int sina_hip_find_bases_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *pairs, uint64_t *ref_bases,
+                              uint64_t *launches);
+
 /* ------------------------------------------------------------- alignment
  * Replaces, for a batch of queries: mseq::mseq + sort + reduce_edges
  * (src/mseq.cpp:47-118, src/graph.h:451-488) when given family ids, compute()

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "sina_hip_align_count_identity", "sina_hip_staged_identity", "sina_hip_identity_inplace_stats",
     "sina_hip_align_rank", "sina_hip_staged_rank", "sina_hip_rank_inplace_stats",
     "sina_hip_show_dist", "sina_hip_show_dist_stats",
+    "sina_hip_find_bases", "sina_hip_find_bases_stats",
     "sina_hip_staged_shift_log", "sina_hip_assemble_stats", "sina_hip_debug_assemble", "sina_hip_debug_assemble_ms",
 ]
 
@@ -212,6 +213,8 @@ def load():
     L.sina_hip_identity_inplace_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
     L.sina_hip_show_dist.argtypes = [vp, u32p, u64p, u32p, u64p, C.c_uint32, u32p, u64p, u32p]
     L.sina_hip_show_dist_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
+    L.sina_hip_find_bases.argtypes = [vp, u8p, u64p, C.c_uint32, u32p, u64p, u32p]
+    L.sina_hip_find_bases_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
     L.sina_hip_align_rank.argtypes = [vp, C.c_int, C.c_uint, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32]
     L.sina_hip_staged_rank.restype = C.POINTER(C.c_uint32)
     L.sina_hip_staged_rank.argtypes = [vp]
@@ -659,6 +662,23 @@ class Context:
     def show_dist_stats(self):
         """The show-dist kernel on this context so far: dict(kernel_ms, sequences, pairs, launches)."""
         return self._counters(self.L.sina_hip_show_dist_stats, KERNEL_MS + u64_fields("sequences", "pairs", "launches"))
+
+    def find_bases(self, qmask, q_off, cand_ids, cand_off, out=None):
+        """Where each candidate reference holds its query's bases (std::string::find over `mask & 0xF`): uint32, one word
+        per candidate at out[cand_off[q] + i] -- the lowest start or 0xFFFFFFFF.  qmask / q_off: the queries' mask bytes
+        and offsets [nq + 1]; cand_ids / cand_off: the candidates' reference ids and offsets [nq + 1] (sub-ranges of
+        larger arrays included).  out: the array to write into, at least cand_off[-1] words."""
+        qmask, cand_ids = _c(qmask, np.uint8), _c(cand_ids, np.uint32)
+        q_off, cand_off = _c(q_off, np.uint64), _c(cand_off, np.uint64)
+        nq = len(q_off) - 1
+        at = out if out is not None else np.zeros(int(cand_off[-1]) if len(cand_off) else 0, np.uint32)
+        self._check(self.L.sina_hip_find_bases(self.h, _ptr(qmask, u8p), _ptr(q_off, u64p), nq, _ptr(cand_ids, u32p), _ptr(cand_off, u64p),
+                                               _ptr(at, u32p)))
+        return at
+
+    def find_bases_stats(self):
+        """The containment kernel on this context so far: dict(kernel_ms, pairs, ref_bases, launches)."""
+        return self._counters(self.L.sina_hip_find_bases_stats, KERNEL_MS + u64_fields("pairs", "ref_bases", "launches"))
 
     def count_pairs(self, on=True):
         """The switch of the in-place pair count: with it on, an align call with assemble=1 on a store with a helix map

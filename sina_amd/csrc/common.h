@@ -35,6 +35,7 @@ void set_limit_error(const std::string &msg);
 //                                        match_floor=N  match_loads=1 (the match-count kernel's chunk floor / one load in flight: tools/perf_msc.py)
 //                                        pair_words=N (words per launch range of the pair-count kernel, pairs.hip)
 //                                        showdist_range=N (queries per launch range of the show-dist kernel, showdist.hip)
+//                                        contain_pairs=N (pairs per launch range of the containment kernel, contain.hip)  contain_fail=1 (sina_hip_find_bases refuses every call: the aligner's fallback)
 //                                        profile_tile=N (at most N nodes per LDS tile of the family profile kernel, profile_build.hip)
 //                                        dp_range_q=N (at most N queries per DP launch range: a small call takes several)
 //                                        fam_chunk_q=N (at most N queries per DAG / profile build chunk of the family entries)

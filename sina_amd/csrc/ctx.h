@@ -124,6 +124,7 @@ namespace sina_hip {
 //   kUseRankInplace        sequences  pairs              sina_hip_rank_inplace_stats
 //   kUseFamily             listed     scanned            sina_hip_family_stats (c: queries)
 //   kUseShowDist           sequences  pairs              sina_hip_show_dist_stats
+//   kUseContain            pairs      ref_bases          sina_hip_find_bases_stats
 struct KernelUse {
     double ms = 0;
     uint64_t a = 0, b = 0, launches = 0, c = 0;
@@ -135,7 +136,7 @@ struct KernelUse {
         c += c_;
     }
 };
-enum kernel_use { kUseMatch, kUseRank, kUsePairs, kUsePairsInplace, kUseIdentityInplace, kUseRankInplace, kUseFamily, kUseShowDist, kNumKernelUse };
+enum kernel_use { kUseMatch, kUseRank, kUsePairs, kUsePairsInplace, kUseIdentityInplace, kUseRankInplace, kUseFamily, kUseShowDist, kUseContain, kNumKernelUse };
 // queries a path off the fast one has taken on a context (sina_hip_ctx::path_queries; sina_hip_wide_queries,
 // sina_hip_long_queries, sina_hip_big_select_queries): the wide DP kernel, the long k-mer count kernel, the big select
 enum slow_path { kPathWide, kPathLong, kPathBigSelect, kNumSlowPaths };
@@ -270,7 +271,8 @@ struct sina_hip_ctx {
     // for caller-given lists, their scores (the ids borrow s_cand, the counts m_out, the lengths m_n, the offsets s_qoff)
     sina_hip::DevBuf f_rows, f_cnt, f_self_ids, f_self_off, f_scores;
     // (the pair-count kernel, pairs.hip, borrows s_qab, s_qoff and s_out; the show-dist kernel, showdist.hip, borrows
-    // s_qab and s_qoff for both alignments, s_cand and s_coff for the lists and s_out for the rows)
+    // s_qab and s_qoff for both alignments, s_cand and s_coff for the lists and s_out for the rows; the containment
+    // kernel, contain.hip, borrows s_qab, s_qoff and m_n for the packed queries, s_cand and s_coff for the pairs and s_out)
     // the counts that ride on an align call: [n][6] pair counters in 24 bytes, [n][2] identity words in 8
     sina_hip::InplaceCount inplace[sina_hip::kNumInplace] = {{24, sina_hip::kUsePairsInplace, 12},
                                                              {sina_hip::identity_row_bytes(1), sina_hip::kUseIdentityInplace, 13},

@@ -5,6 +5,7 @@
 #include "align_plan.h"
 #include "../kmer_plan.h"
 #include "../rank_plan.h"
+#include "../contain_plan.h"
 #include <immintrin.h>
 
 #include <algorithm>
@@ -59,6 +60,9 @@ static aligner::options al_defaults() {  // src/align.cpp:231-274
     // --show-dist's comparisons in one device call per batch (sina_hip_show_dist, show_dist_batch) instead of the
     // sink's walks: on request, until it has been decided on measurements
     o.device_dist = false;
+    // the exact-relative test of a batch's suspects in one device call (sina_hip_find_bases, find_on_device) instead of
+    // the host's substring searches: on request, until it has been decided on measurements
+    o.device_copy = false;
     return o;
 }
 static aligner::options &al_opts() {
@@ -105,6 +109,7 @@ void aligner::set_option(const std::string &name, const std::string &value) {
     else if (name == "device-shift") o.device_shift = to_bool(value);
     else if (name == "device-search") o.device_search = to_bool(value);
     else if (name == "device-dist") o.device_dist = to_bool(value);
+    else if (name == "device-copy") o.device_copy = to_bool(value);
     else if (name == "db") o.database = value;
     else throw std::logic_error("aligner: unknown option " + name);
 }
@@ -218,13 +223,38 @@ static unsigned query_kmer_count(const cseq &c, int stamp) {
     return n;
 }
 
-// Takes a tray as famfinder left it (prep_store: the reference store, if there is one, for its cached upper-case bases);
-// gives true if it needs the DP, false if it is done: nothing to align, too long, or its alignment copied from a relative.
-static bool prepare_tray(tray &t, const aligner::options &o, reference_store *prep_store) {
-    if (t.input_sequence == nullptr || t.alignment_reference == nullptr || t.astats == nullptr) return false;  // :310-318
-    // (device limit: soft failure of this tray.  With wide-fallback a query beyond the fast DP path's length is aligned
-    // by the wide kernel -- up to the length the k-mer search can have found its family for)
-    const unsigned max_len = o.wide_fallback ? SINA_HIP_MAX_LONG_QUERY_LEN : SINA_HIP_MAX_QUERY_LEN;
+// Whether prepare_tray looks at the tray's family at all, and the longest query it does that for (device limit: soft
+// failure of the tray.  With wide-fallback a query beyond the fast DP path's length is aligned by the wide kernel -- up to
+// the length the k-mer search can have found its family for)
+static bool tray_is_complete(const tray &t) { return t.input_sequence != nullptr && t.alignment_reference != nullptr && t.astats != nullptr; }
+static unsigned max_query_len(const aligner::options &o) { return o.wide_fallback ? SINA_HIP_MAX_LONG_QUERY_LEN : SINA_HIP_MAX_QUERY_LEN; }
+// A family member can only contain the query's bases if it has every one of the query's
+// k-mers, i.e. if its k-mer score (what famfinder ranked it by) is the query's k-mer count --
+// which spares the string search for all but exact relatives.  Gives that count; -1: the scores are no k-mer counts.
+static float all_kmers_of(const tray &t) {
+    return t.family_scores_kmer_k == 0 ? -1.f
+                                       : (float)(t.query_kmer_count >= 0 ? (unsigned)t.query_kmer_count
+                                                                         : query_kmer_count(*t.input_sequence, t.family_scores_kmer_k));
+}
+
+// device-copy: where the suspects of one tray -- the family members that pass the k-mer-count test -- hold the query's
+// bases, as sina_hip_find_bases answered for the batch (find_on_device): the start, or kContainNone.  A member without
+// an entry is searched on the host.
+struct copy_answers {
+    std::vector<std::pair<const cseq *, uint32_t>> at;
+    const uint32_t *find(const cseq *r) const {
+        for (const auto &e : at)
+            if (e.first == r) return &e.second;
+        return nullptr;
+    }
+};
+
+// Takes a tray as famfinder left it (prep_store: the reference store, if there is one, for its cached upper-case bases;
+// dev: the device's answers for the tray's suspects, or null); gives true if it needs the DP, false if it is done:
+// nothing to align, too long, or its alignment copied from a relative.
+static bool prepare_tray(tray &t, const aligner::options &o, reference_store *prep_store, const copy_answers *dev) {
+    if (!tray_is_complete(t)) return false;  // :310-318
+    const unsigned max_len = max_query_len(o);
     if (t.input_sequence->size() > max_len) {
         t.log << "unable to align: sequence of " << t.input_sequence->size() << " bases (device limit "
               << max_len << ");";
@@ -252,14 +282,12 @@ static bool prepare_tray(tray &t, const aligner::options &o, reference_store *pr
         tmp = upper_copy(r->getBases());
         return tmp;
     };
-    // A family member can only contain the query's bases if it has every one of the query's
-    // k-mers, i.e. if its k-mer score (what famfinder ranked it by) is the query's k-mer count --
-    // which spares the string search for all but exact relatives.
-    const float all_kmers = t.family_scores_kmer_k == 0 ? -1.f
-                            : (float)(t.query_kmer_count >= 0 ? (unsigned)t.query_kmer_count
-                                                              : query_kmer_count(*t.input_sequence, t.family_scores_kmer_k));
+    const float all_kmers = all_kmers_of(t);
+    // (the device's answer for a member, where the batch's pre-pass has one)
+    auto device_at = [&](const cseq *r) -> const uint32_t * { return dev != nullptr ? dev->find(r) : nullptr; };
     auto lacks_query = [&](search::result_item &item) {
         if (item.score < all_kmers) return true;
+        if (const uint32_t *at = device_at(item.sequence)) return *at == sina_hip::kContainNone;
         std::string tmp;
         return find_bases(ref_ubases(item.sequence, tmp), ubases_of_query()) == std::string::npos;
     };
@@ -280,6 +308,7 @@ static bool prepare_tray(tray &t, const aligner::options &o, reference_store *pr
             }
         } else {  // :349-388 steal the alignment
             auto is_query_itself = [&](search::result_item &item) {
+                if (const uint32_t *at = device_at(item.sequence)) return *at == 0 && item.sequence->size() == n_bases;
                 std::string tmp;
                 return ref_ubases(item.sequence, tmp) == ubases_of_query();
             };
@@ -294,7 +323,8 @@ static bool prepare_tray(tray &t, const aligner::options &o, reference_store *pr
             } else {
                 const auto &refal = holders->sequence->getAlignedBases();
                 std::string tmp;
-                const size_t at = find_bases(ref_ubases(holders->sequence, tmp), ubases_of_query());
+                const uint32_t *const dev_at = device_at(holders->sequence);
+                const size_t at = dev_at ? (size_t)*dev_at : find_bases(ref_ubases(holders->sequence, tmp), ubases_of_query());
                 c.setAlignedBases(refal.data() + at, n_bases);
                 t.log << "copied alignment from (longer) template sequence "
                       << holders->sequence->get_attr<std::string>(fn::acc) << ":"
@@ -681,6 +711,66 @@ static align_switches plan_switches(const aligner::options &o) {
     return s;
 }
 
+// device-copy: the exact-relative test of a whole batch in ONE sina_hip_find_bases call on a leased
+// worker context, before the trays are prepared.  Takes the batch as famfinder left it; gives, per tray, the answers for
+// its suspects: the members of its family the store owns whose score is not below the query's k-mer count (what
+// prepare_tray's lacks_query tests before it searches; scores that are no k-mer counts: every member).  Kept with the
+// host walk, silently: members the store does not own; trays beyond the call's length limit; the whole batch if the
+// call fails or is refused (the table stays empty).  A batch without suspects launches nothing.  walks: whether some
+// suspect the store owns is left to the host walk (which reads the store's upper-case cache).
+static std::vector<copy_answers> find_on_device(std::vector<tray> &batch, const aligner::options &o, reference_store &store, bool *walks) {
+    scoped_phase ph("al.prepare(device-copy)");
+    std::vector<copy_answers> table(batch.size());
+    const unsigned max_len = max_query_len(o);
+    std::vector<size_t> dev;  // the trays with suspects
+    uint64_t too_long = 0;
+    *walks = false;
+    for (size_t i = 0; i < batch.size(); i++) {
+        const tray &t = batch[i];
+        if (!tray_is_complete(t) || t.input_sequence->size() > max_len || t.input_sequence->size() == 0) continue;
+        const bool fits = t.input_sequence->size() <= sina_hip::kContainMaxBases;
+        const float all_kmers = all_kmers_of(t);
+        for (const search::result_item &item : *t.alignment_reference) {
+            if (item.score < all_kmers || !store.owns(item.sequence)) continue;
+            if (fits) table[i].at.emplace_back(item.sequence, sina_hip::kContainNone);
+            else *walks = true;
+        }
+        if (!table[i].at.empty()) dev.push_back(i);
+        else if (!fits && *walks) too_long++;
+    }
+    if (dev.empty()) {
+        store.count_copy(0, too_long);
+        return table;
+    }
+    const size_t n = dev.size();
+    auto seq_of = [&](size_t x) -> const cseq & { return *batch[dev[x]].input_sequence; };
+    const std::vector<uint64_t> qoff = offsets_of(n, seq_of);
+    std::vector<uint64_t> coff(n + 1, 0);
+    for (size_t x = 0; x < n; x++) coff[x + 1] = coff[x] + table[dev[x]].at.size();
+    std::vector<uint8_t> qmask(qoff.back() + 1);
+    pack_masks(n, seq_of, qoff.data(), qmask.data());
+    std::vector<uint32_t> ids(coff.back()), at(coff.back(), sina_hip::kContainNone);
+    for (size_t x = 0; x < n; x++)
+        for (size_t y = 0; y < table[dev[x]].at.size(); y++) ids[coff[x] + y] = store.id_of(table[dev[x]].at[y].first);
+    bool answered = false;
+    try {
+        scoped_phase call("al.find_bases(C-ABI)");
+        reference_store::lease dv = store.worker_device(reference_store::dev_compare);
+        answered = sina_hip_find_bases(dv.get(), qmask.data(), qoff.data(), (uint32_t)n, ids.data(), coff.data(), at.data()) == 0;
+    } catch (const std::exception &) {  // (no context to be had: the walk)
+    }
+    if (!answered) {
+        for (size_t i : dev) table[i].at.clear();
+        *walks = true;
+        store.count_copy(0, n + too_long);
+        return table;
+    }
+    for (size_t x = 0; x < n; x++)
+        for (size_t y = 0; y < table[dev[x]].at.size(); y++) table[dev[x]].at[y].second = at[coff[x] + y];
+    store.count_copy(n, too_long);
+    return table;
+}
+
 // Takes the batch (and the store's name; gives the store, if it can be had: a batch without DP jobs does without);
 // prepares every tray.  Gives one job per tray: a tray that needs the DP has its job's `t` set.
 static std::vector<dp_job> prepare_jobs(std::vector<tray> &batch, const aligner::options &o, const std::string &db,
@@ -692,10 +782,13 @@ static std::vector<dp_job> prepare_jobs(std::vector<tray> &batch, const aligner:
             store = reference_store::get(db);
         } catch (const std::exception &) {  // (a batch without DP jobs does without the store)
         }
-        if (store && !batch.empty() && store->size() > 0) store->upper_bases(0);  // (fills the cache outside the loop)
     }
+    // (device-copy: the suspects' answers from one call; the store's upper-case cache only if a tray has to walk)
+    bool walks = true;
+    const std::vector<copy_answers> dev = o.device_copy && store ? find_on_device(batch, o, *store, &walks) : std::vector<copy_answers>();
+    if (store && !batch.empty() && store->size() > 0 && walks) store->upper_bases(0);  // (fills the cache outside the loop)
     parallel_for(batch.size(), [&](size_t i) {
-        if (!prepare_tray(batch[i], o, store.get())) return;
+        if (!prepare_tray(batch[i], o, store.get(), dev.empty() || dev[i].at.empty() ? nullptr : &dev[i])) return;
         jobs[i].t = &batch[i];
         jobs[i].fam = batch[i].alignment_reference;
     });

@@ -283,7 +283,8 @@ void reserve_workers(SearchStore &&search_store, unsigned n_find, unsigned n_ali
         const std::shared_ptr<reference_store> sstore = search_store();
         store->reserve_workers(reference_store::dev_search, n_find + (sstore == store ? n_align : 0));
         store->reserve_workers(reference_store::dev_align, n_align);
-        if (store->pairs() && sstore != store) store->reserve_workers(reference_store::dev_compare, n_align);  // (the pair step)
+        // (the pair step; the aligner's device-copy pre-pass)
+        if ((store->pairs() || aligner::opts->device_copy) && sstore != store) store->reserve_workers(reference_store::dev_compare, n_align);
         if (sstore) {
             if (sstore != store) sstore->reserve_workers(reference_store::dev_search, n_align);
             sstore->reserve_workers(reference_store::dev_compare, n_align);
@@ -438,6 +439,16 @@ int sina_host_store_show_dist_stats(const char *key, uint64_t *trays, double *ke
     return guarded([&] {
         if (!trays || !kernel_ms || !sequences || !pairs || !launches) throw std::logic_error("store_show_dist_stats: null argument");
         reference_store::get(key)->show_dist_stats(trays, kernel_ms, sequences, pairs, launches);
+    });
+}
+// the aligner's device-copy on this store: (query, suspect) pairs the containment kernel answered, its time and launches
+// (sina_hip_find_bases_stats) on the store's contexts, trays answered by the device and trays with suspects that kept
+// the host walk -- between runs
+int sina_host_store_copy_stats(const char *key, uint64_t *pairs, double *kernel_ms, uint64_t *launches, uint64_t *trays,
+                               uint64_t *fallback_trays) {
+    return guarded([&] {
+        if (!pairs || !kernel_ms || !launches || !trays || !fallback_trays) throw std::logic_error("store_copy_stats: null argument");
+        reference_store::get(key)->copy_stats(pairs, kernel_ms, launches, trays, fallback_trays);
     });
 }
 // show_dist_report alone (no device), for tests: nq (orig, aligned) pairs as packed words of the store's width, their
@@ -1375,6 +1386,28 @@ int sina_host_cseq_op(const char *aligned, int op, uint32_t arg, int what, char 
     } catch (const std::exception &e) {
         return fail(e);
     }
+}
+
+// The aligner's exact-relative walk on one pair, for CPU-only tests of its device twin (sina_hip_find_bases): the two
+// sequences as packed words, rendered by the container (getBases) and upper-cased as prepare_tray does; hay_text /
+// needle_text (optional, cap bytes each): the strings; at: find_bases' answer, 0xFFFFFFFF for npos.
+int sina_host_find_bases_packed(const uint32_t *hay, uint32_t n_hay, const uint32_t *needle, uint32_t n_needle, uint32_t *at,
+                                char *hay_text, char *needle_text, uint32_t cap) {
+    return guarded([&] {
+        if ((!hay && n_hay) || (!needle && n_needle) || !at) throw std::logic_error("find_bases_packed: null argument");
+        auto rendered = [](const uint32_t *ab, uint32_t n) {
+            cseq c("");
+            c.setAlignedBases(reinterpret_cast<const aligned_base *>(ab), n);
+            std::string s = c.getBases();
+            for (auto &ch : s) ch = (char)toupper((unsigned char)ch);
+            return s;
+        };
+        const std::string h = rendered(hay, n_hay), nd = rendered(needle, n_needle);
+        const size_t pos = find_bases(h, nd);
+        *at = pos == std::string::npos ? 0xFFFFFFFFu : (uint32_t)pos;
+        if (hay_text && cap) snprintf(hay_text, cap, "%s", h.c_str());
+        if (needle_text && cap) snprintf(needle_text, cap, "%s", nd.c_str());
+    });
 }
 
 // NAST fix-up exposed for CPU-only property tests against the oracle

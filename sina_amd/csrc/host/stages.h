@@ -383,6 +383,15 @@ public:
     // was opened, and the show-dist kernel's time and volume on the store's contexts -- sina_hip_show_dist_stats
     void count_show_dist(uint64_t trays) { n_show_dist.fetch_add(trays, std::memory_order_relaxed); }
     void show_dist_stats(uint64_t *trays, double *kernel_ms, uint64_t *sequences, uint64_t *pairs, uint64_t *launches);
+    // the aligner's device-copy (find_on_device): trays whose exact-relative test was answered by the device, trays with
+    // suspects that kept the host walk (beyond the call's length limit, or their batch's call failed or was refused)
+    // since the store was opened, and the containment kernel's time and volume on the store's contexts --
+    // sina_hip_find_bases_stats
+    void count_copy(uint64_t trays, uint64_t fallback_trays) {
+        n_copy_trays.fetch_add(trays, std::memory_order_relaxed);
+        n_copy_fallback.fetch_add(fallback_trays, std::memory_order_relaxed);
+    }
+    void copy_stats(uint64_t *pairs, double *kernel_ms, uint64_t *launches, uint64_t *trays, uint64_t *fallback_trays);
     // whether the index in HBM is the one of this k / nofast (ensure_index, adopt_index)
     bool index_is(unsigned k, bool nofast) {
         std::lock_guard<std::mutex> lk(gpu_mu);
@@ -422,6 +431,7 @@ private:
     std::atomic<int> name_order_state{0};  // 0: not looked at, 1: uploaded, 2: names repeat
     std::atomic<uint64_t> n_ranked{0}, n_rank_host{0};
     std::atomic<uint64_t> n_bp_inplace{0}, n_idty_inplace{0}, n_search_inplace{0}, n_show_dist{0};
+    std::atomic<uint64_t> n_copy_trays{0}, n_copy_fallback{0};
     std::atomic<uint64_t> n_fin_device{0}, n_fin_host{0};
     pair_map helix;
     std::mutex helix_mu;
@@ -533,6 +543,8 @@ public:
                             // (sina_hip_align_families_wsets; default on) instead of one call per filter
         bool device_bps;    // a store with a helix map: the align call counts the base pairs of the queries it assembles and
                             // their trays leave the aligner scored (sina_hip_align_count_pairs; default off)
+        bool device_copy;   // the exact-relative test (which family members hold the query's bases) of a batch in one device call
+                            // before the trays are prepared (sina_hip_find_bases; default off); what it cannot take keeps the host walk
         bool device_dist;   // --show-dist: a batch driver's step (show_dist_batch) counts on the device what the sink would walk (default off)
         bool device_idty;   // calc-idty: the align call of a device-built group scores the queries it assembles against their
                             // families and their trays take that identity (sina_hip_align_count_identity; default off)
@@ -558,7 +570,7 @@ public:
     void align_batch(std::vector<tray> &batch, bool batch_driver);
 
     // "realign", "overhang", "lowercase", "insertion", "fs-weight", "match-score",
-    // "mismatch-score", "pen-gap", "pen-gapext", "write-used-rels", "calc-idty", "db", "weight-sets"
+    // "mismatch-score", "pen-gap", "pen-gapext", "write-used-rels", "calc-idty", "db", "weight-sets", "device-copy"
     static void set_option(const std::string &name, const std::string &value);
     static void reset_options();
     static void validate_options();

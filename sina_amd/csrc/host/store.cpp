@@ -390,6 +390,12 @@ void reference_store::show_dist_stats(uint64_t *trays, double *kernel_ms, uint64
     sum_kernel_use("sina_hip_show_dist_stats", sina_hip_show_dist_stats, kernel_ms, sequences, pairs, launches);
     *trays = n_show_dist.load(std::memory_order_relaxed);
 }
+void reference_store::copy_stats(uint64_t *pairs, double *kernel_ms, uint64_t *launches, uint64_t *trays, uint64_t *fallback_trays) {
+    uint64_t ref_bases = 0;
+    sum_kernel_use("sina_hip_find_bases_stats", sina_hip_find_bases_stats, kernel_ms, pairs, &ref_bases, launches);
+    *trays = n_copy_trays.load(std::memory_order_relaxed);
+    *fallback_trays = n_copy_fallback.load(std::memory_order_relaxed);
+}
 void reference_store::assemble_stats(uint64_t *trays_device, uint64_t *trays_host, uint64_t *queries, uint64_t *assembled,
                                      uint64_t *shifted_queries, uint64_t *shifted_runs) {
     *queries = *assembled = *shifted_queries = *shifted_runs = 0;

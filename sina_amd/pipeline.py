@@ -102,6 +102,8 @@ def load_host():
     H.sina_host_store_identity_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_store_search_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_store_show_dist_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_store_copy_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_find_bases_packed.argtypes = [capi.u32p, C.c_uint32, capi.u32p, C.c_uint32, capi.u32p, C.c_char_p, C.c_char_p, C.c_uint32]
     H.sina_host_show_dist_reports.argtypes = [C.c_char_p, capi.u32p, capi.u64p, capi.u32p, capi.u64p, C.c_uint32, capi.u32p, capi.u64p,
                                               capi.u32p, capi.f32p, capi.u32p, capi.u32p, C.c_char_p, C.c_uint32]
     H.sina_host_result_dist.argtypes = [vp, C.c_uint32, capi.f32p, capi.u32p, C.POINTER(C.c_int)]
@@ -324,6 +326,16 @@ class Store:
         launches and time on the store's contexts -- between runs, like identity_inplace_stats()."""
         d = self._counters(self.H.sina_host_store_show_dist_stats, capi.u64_fields("trays") + capi.KERNEL_MS +
                            capi.u64_fields("sequences", "pairs", "launches"))
+        d["kernel_ms"] = d.pop("kernel_ms")  # (the dict ends with it)
+        return d
+
+    def copy_stats(self):
+        """The aligner's device-copy on this store so far: dict(pairs, launches, trays, fallback_trays, kernel_ms) --
+        (query, suspect) pairs the containment kernel answered and its launches and time on the store's contexts, trays
+        whose exact-relative test the device answered and trays with suspects that kept the host walk -- between runs,
+        like show_dist_stats()."""
+        d = self._counters(self.H.sina_host_store_copy_stats, capi.u64_fields("pairs") + capi.KERNEL_MS +
+                           capi.u64_fields("launches", "trays", "fallback_trays"))
         d["kernel_ms"] = d.pop("kernel_ms")  # (the dict ends with it)
         return d
 

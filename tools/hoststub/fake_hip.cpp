@@ -170,6 +170,16 @@ int sina_hip_show_dist_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, uint64_
     *seqs = *pairs = *launches = 0;
     return 0;
 }
+// (the aligner's device-copy then keeps its host walk)
+int sina_hip_find_bases(sina_hip_ctx *, const uint8_t *, const uint64_t *, uint32_t, const uint32_t *, const uint64_t *, uint32_t *) {
+    g_err = "stub";
+    return 1;
+}
+int sina_hip_find_bases_stats(sina_hip_ctx *, double *ms, uint64_t *pairs, uint64_t *bases, uint64_t *launches) {
+    *ms = 0;
+    *pairs = *bases = *launches = 0;
+    return 0;
+}
 int sina_hip_identity_inplace_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, uint64_t *pairs, uint64_t *launches) {
     *ms = 0;
     *seqs = *pairs = *launches = 0;
