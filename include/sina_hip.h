@@ -67,7 +67,8 @@ int sina_hip_sync(sina_hip_ctx *ctx);
  */
 
 /* Copies n_refs packed aligned references (concatenated `ab`, offsets `off`
- * [n_refs+1]) of common alignment width `width` into HBM. */
+ * [n_refs+1]) of common alignment width `width` into HBM.  An index the store held is forgotten with the
+ * references it was made from (its ids name those): build or upload one again before the next search. */
 int sina_hip_upload_refs(sina_hip_ctx *ctx, const uint32_t *ab, const uint64_t *off,
                          uint32_t n_refs, uint32_t width);
 
@@ -260,7 +261,9 @@ int sina_hip_family_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *querie
  *
  * sina_hip_upload_name_order: rank[id] = position of reference id's name in ascending byte-wise order, n = the number
  * of uploaded references.  Anything but a permutation of 0..n_refs-1 is refused before anything runs; a forked context
- * cannot call it; sina_hip_upload_refs (and sina_hip_store_alloc_like) forget it.  The identity permutation gives
+ * cannot call it; sina_hip_upload_refs (and sina_hip_store_alloc_like) forget it -- sina_hip_upload_refs also forgets
+ * the k-mer index and its bitmaps: until the next sina_hip_build_index / sina_hip_upload_index a search fails with "no
+ * index", sina_hip_download_index too, and sina_hip_store_view_get shows none.  The identity permutation gives
  * "score descending, id descending", sina_hip_kmer_topk's own tie rule.
  *
  * sina_hip_compare_rank: arguments as sina_hip_compare's (sub-ranges of larger offset arrays included), plus

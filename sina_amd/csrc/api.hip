@@ -460,6 +460,12 @@ int sina_hip_upload_refs(sina_hip_ctx *c, const uint32_t *ab, const uint64_t *of
     c->st->have_refs = true;
     c->st->have_name_order = false;  // (sina_hip_upload_name_order: the order belonged to the references before)
     c->st->fam_meta_ready.store(false, std::memory_order_release);  // (family.hip: rebuilt by the next cascade)
+    // and the index: its lists name the references before (an id at or above n_refs would take the count kernels
+    // outside their counters) -- build or upload one again
+    c->st->have_index = false;
+    c->st->dense_ready = false;
+    c->st->n_postings = 0;
+    c->st->n_dense = 0;
     return 0;
 }
 

@@ -12,7 +12,7 @@ import pytest
 
 from sina_amd import capi
 from tests import kmer_cases as kc
-from tests import kmer_ref, util
+from tests import index_ref, kmer_ref, util
 
 pytestmark = pytest.mark.gpu
 
@@ -78,20 +78,6 @@ def test_kmer_cand_cases(monkeypatch, name):
     _run(kc.case(name), monkeypatch)
 
 
-def _csr_of(codes, k):
-    """The index of references given as base codes [n][length], by its definition: r is in list v iff v is the value of
-    a window of r that does not end on r's last base; ids ascending."""
-    n, length = codes.shape
-    n_win = length - k
-    v = np.zeros((n, n_win), np.int64)
-    for x in range(k):
-        v = (v << 2) | codes[:, x:x + n_win]
-    keys = np.unique(((v << 32) | np.arange(n, dtype=np.int64)[:, None]).ravel())
-    off = np.zeros((1 << (2 * k)) + 1, np.uint32)
-    off[1:] = np.cumsum(np.bincount(keys >> 32, minlength=1 << (2 * k)))
-    return off, (keys & 0xFFFFFFFF).astype(np.uint32)
-
-
 def test_one_call_through_every_path_of_the_range_walk(monkeypatch):
     """One sina_hip_kmer_topk_any call that the driver takes through all it has: 65 537 references of 60 bases (two tiles
     and one reference: the candidate path), k = 6, the index built on the device; six short queries -- five copies of
@@ -106,7 +92,7 @@ def test_one_call_through_every_path_of_the_range_walk(monkeypatch):
     codes = rng.integers(0, 4, size=(n_refs, length), dtype=np.int64)
     masks = (1 << codes).astype(np.uint8)
     ab = (np.arange(length, dtype=np.uint32)[None, :] | (masks.astype(np.uint32) << 24)).ravel()
-    off, ids = _csr_of(codes, k)
+    off, ids = index_ref.build(list(masks), k, True)
     short = [masks[r].copy() for r in (5, 32767, 32768, 65535, 65536)]
     qmasks = short[:2] + [masks[100:271].ravel().copy()] + short[2:4] + [np.full(k + 3, kc.N_MASK, np.uint8)] + short[4:]
     assert [len(m) for m in qmasks] == [60, 60, 10260, 60, 60, 9, 60] and kc.FAST_MAX < 10260 <= kc.LONG_MAX
