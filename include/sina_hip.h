@@ -158,6 +158,34 @@ int sina_hip_long_queries(sina_hip_ctx *ctx, uint64_t *n);
  * M <= 4096 leaves it alone. */
 int sina_hip_big_select_queries(sina_hip_ctx *ctx, uint64_t *n);
 
+/* ------------------------------------------------------------- famfinder's --turn (device-turn)
+ * Replaces famfinder::turn_check (src/famfinder.cpp:344-378: one top-1 search per tried orientation of the query, made
+ * with cseq::reverse / cseq::complement, src/famfinder.cpp:312-341) AND the search of the chosen orientation that
+ * follows it (src/famfinder.cpp:439-455), for a batch.  Orientation o = (bit 0: reversed) | (bit 1: complemented);
+ * complement is base_iupac::complement on the mask byte (bits 1 <-> 8 and 2 <-> 4, the case bit kept), reverse the
+ * byte order.  The queries go up once, as they are; the device makes the variants, searches them, and chooses: over
+ * o = 0, 1, 2, 3 the first strictly largest top-1 score above 0, else 0.
+ *
+ * sina_hip_kmer_topk_turn: nq queries of 0..SINA_HIP_MAX_LONG_QUERY_LEN bases (routing per query as sina_hip_kmer_topk_any's).
+ *   qmask/qoff : as sina_hip_kmer_topk takes them
+ *   max        : results wanted per query, 1 or more (clamped to n_refs)
+ *   all        : 0 tries o = 0 and 3 ("revcomp"), else all four, in the order 0, 3, 1, 2
+ *   out_turn   : [nq] the chosen orientation
+ *   out_top1   : [nq][4] the top-1 score by orientation (0 for an orientation not tried or without a result): what four
+ *                sina_hip_kmer_topk_any calls with max = 1 give as scores
+ *   out_ids, out_scores, out_n : as sina_hip_kmer_topk's, bit for bit what sina_hip_kmer_topk_any gives for the CHOSEN
+ *                orientation's mask bytes with the same max
+ * Refused with a message before anything runs: a null argument, max == 0; a query beyond SINA_HIP_MAX_LONG_QUERY_LEN
+ * bases fails the call as a limit.  nq == 0 succeeds and touches nothing.
+ *
+ * sina_hip_turn_stats: the two kernels' own time (events around their launches) and volume on this context since init /
+ * fork: queries oriented, those of them whose chosen orientation is not 0, launches (one of the orient kernel per
+ * call, one of the pick kernel per launch range). */
+int sina_hip_kmer_topk_turn(sina_hip_ctx *ctx, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq,
+                            uint32_t max, int all, uint8_t *out_turn, float *out_top1 /* [nq][4] */,
+                            uint32_t *out_ids, float *out_scores, uint32_t *out_n);
+int sina_hip_turn_stats(sina_hip_ctx *ctx, double *kernel_ms, uint64_t *queries, uint64_t *turned, uint64_t *launches);
+
 /* ------------------------------------------------------------- search stage
  * Replaces the per-candidate cseq_comparator::operator() calls of search_filter::operator()
  * (src/search_filter.cpp:311-313 and :274-276; traverse + match_counter,

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "sina_hip_align_rank", "sina_hip_staged_rank", "sina_hip_rank_inplace_stats",
     "sina_hip_show_dist", "sina_hip_show_dist_stats",
     "sina_hip_find_bases", "sina_hip_find_bases_stats",
+    "sina_hip_kmer_topk_turn", "sina_hip_turn_stats",
     "sina_hip_staged_shift_log", "sina_hip_assemble_stats", "sina_hip_debug_assemble", "sina_hip_debug_assemble_ms",
 ]
 
@@ -215,6 +216,8 @@ def load():
     L.sina_hip_show_dist_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
     L.sina_hip_find_bases.argtypes = [vp, u8p, u64p, C.c_uint32, u32p, u64p, u32p]
     L.sina_hip_find_bases_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
+    L.sina_hip_kmer_topk_turn.argtypes = [vp, u8p, u64p, C.c_uint32, C.c_uint32, C.c_int, u8p, f32p, u32p, f32p, u32p]
+    L.sina_hip_turn_stats.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p, u64p]
     L.sina_hip_align_rank.argtypes = [vp, C.c_int, C.c_uint, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32]
     L.sina_hip_staged_rank.restype = C.POINTER(C.c_uint32)
     L.sina_hip_staged_rank.argtypes = [vp]
@@ -374,6 +377,29 @@ class Context:
 
     def kmer_scores_any(self, qmask):
         return self.kmer_scores(qmask, long_ok=True)
+
+    def kmer_topk_turn(self, qmask, qoff, mx, all):
+        """kmer_topk_any for the orientation of every query that scores best (famfinder's --turn): the device makes the
+        tried orientations -- o = 0 and 3, with `all` 0, 3, 1, 2; o = (bit 0: reversed) | (bit 1: complemented) --
+        searches them and chooses the first strictly largest top-1 score above 0 over o = 0 .. 3, else 0.  Returns
+        (turn uint8 [nq], top1 float32 [nq, 4] by orientation, ids, scores, n): the last three as kmer_topk_any's for the
+        chosen orientation's mask bytes."""
+        qmask = _c(qmask, np.uint8)
+        qoff = _c(qoff, np.uint64)
+        nq = len(qoff) - 1
+        mx_eff = max(1, min(mx, self.n_refs))
+        turn = np.zeros(nq, np.uint8)
+        top1 = np.zeros((nq, 4), np.float32)
+        ids = np.zeros((nq, mx_eff), np.uint32)
+        sc = np.zeros((nq, mx_eff), np.float32)
+        n = np.zeros(nq, np.uint32)
+        self._check(self.L.sina_hip_kmer_topk_turn(self.h, _ptr(qmask, u8p), _ptr(qoff, u64p), nq, mx, 1 if all else 0, _ptr(turn, u8p),
+                                                   _ptr(top1, f32p), _ptr(ids, u32p), _ptr(sc, f32p), _ptr(n, u32p)))
+        return turn, top1, ids, sc, n
+
+    def turn_stats(self):
+        """The orient and pick kernels on this context so far: dict(kernel_ms, queries, turned, launches)."""
+        return self._counters(self.L.sina_hip_turn_stats, KERNEL_MS + u64_fields("queries", "turned", "launches"))
 
     def long_queries(self):
         """Queries the long k-mer count kernel has counted on this context so far."""

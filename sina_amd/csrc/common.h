@@ -36,6 +36,7 @@ void set_limit_error(const std::string &msg);
 //                                        pair_words=N (words per launch range of the pair-count kernel, pairs.hip)
 //                                        showdist_range=N (queries per launch range of the show-dist kernel, showdist.hip)
 //                                        contain_pairs=N (pairs per launch range of the containment kernel, contain.hip)  contain_fail=1 (sina_hip_find_bases refuses every call: the aligner's fallback)
+//                                        turn_range=N (at most N queries per launch range of a search call that orients its queries, kmer_launch.hip)  turn_fail=1 (sina_hip_kmer_topk_turn refuses every call: famfinder's fallback)
 //                                        profile_tile=N (at most N nodes per LDS tile of the family profile kernel, profile_build.hip)
 //                                        dp_range_q=N (at most N queries per DP launch range: a small call takes several)
 //                                        fam_chunk_q=N (at most N queries per DAG / profile build chunk of the family entries)

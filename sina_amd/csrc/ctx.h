@@ -125,6 +125,7 @@ namespace sina_hip {
 //   kUseFamily             listed     scanned            sina_hip_family_stats (c: queries)
 //   kUseShowDist           sequences  pairs              sina_hip_show_dist_stats
 //   kUseContain            pairs      ref_bases          sina_hip_find_bases_stats
+//   kUseTurn               queries    turned             sina_hip_turn_stats
 struct KernelUse {
     double ms = 0;
     uint64_t a = 0, b = 0, launches = 0, c = 0;
@@ -136,7 +137,7 @@ struct KernelUse {
         c += c_;
     }
 };
-enum kernel_use { kUseMatch, kUseRank, kUsePairs, kUsePairsInplace, kUseIdentityInplace, kUseRankInplace, kUseFamily, kUseShowDist, kUseContain, kNumKernelUse };
+enum kernel_use { kUseMatch, kUseRank, kUsePairs, kUsePairsInplace, kUseIdentityInplace, kUseRankInplace, kUseFamily, kUseShowDist, kUseContain, kUseTurn, kNumKernelUse };
 // queries a path off the fast one has taken on a context (sina_hip_ctx::path_queries; sina_hip_wide_queries,
 // sina_hip_long_queries, sina_hip_big_select_queries): the wide DP kernel, the long k-mer count kernel, the big select
 enum slow_path { kPathWide, kPathLong, kPathBigSelect, kNumSlowPaths };
@@ -253,6 +254,10 @@ struct sina_hip_ctx {
     // the big select (kmer.hip, reserve_kmer_big_select): a launch range's keys with their double buffer, and the segmented sort's temporary
     // storage -- grow-only, allocated by the first search that wants more than 4096 candidates
     sina_hip::DevBuf k_big_keys, k_big_tmp;
+    // a search call that orients its queries (turn.hip, kmer_launch.hip): the call's mask bytes as they came and their
+    // offsets (the variants go where a search's queries go: qmask, k_qoff), and a launch range's picked rows -- ids, scores,
+    // lengths, and [5] words of orientation and top-1 scores per query; grow-only, allocated by the first such call
+    sina_hip::DevBuf t_src, t_qoff, t_ids, t_scores, t_n, t_meta;
     sina_hip::DevBuf scout, scout_u;  // the scout pass (mesh_dp.hip): the DAG build's chain rows (u16 [DAGs][ncap]), and its result -- a bound U per query
     sina_hip::HostBuf h_res;          // pinned copy of a launch's DpResults (row-skip statistics, the next launch's guess)
     void *last_tb = nullptr;  // the plane of the last launch (debug read-back: sina_hip_debug_mesh)
@@ -356,6 +361,7 @@ struct sina_hip_ctx {
         wide_planes.release();
         k_big_keys.release();
         k_big_tmp.release();
+        for (sina_hip::DevBuf *b : {&t_src, &t_qoff, &t_ids, &t_scores, &t_n, &t_meta}) b->release();
         h_out.release();
         h_out_pos.release();
         for (auto &ic : inplace) ic.h_rows.release();
@@ -823,6 +829,14 @@ int launch_rank_assembled(sina_hip_ctx *c, const BtArgs &b, uint32_t q_base, uin
 // rows are there.  Uploads into c->qmask and c->k_qoff: before the call's first DP launch range
 int kmer_rows_resident(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max, uint32_t *d_ids,
                        uint32_t *d_n, uint32_t *h_n);
+// ---- the orientation kernels (turn.hip), queued on s without a wait.  turn_orient_launch: the n tried variants of nq
+// queries (n_bases mask bytes at d_src, readable as aligned dwords; offsets d_roff from 0) to d_dst, query q's from
+// n d_roff[q] on.  turn_pick_launch: of bq queries' n select rows each (d_ids / d_scores [bq n][max], d_n [bq n]) the
+// four top-1 scores, the pick and the winner's row, into c->t_ids, t_scores, t_n and t_meta.
+int turn_orient_launch(sina_hip_ctx *c, const uint32_t *d_src, uint64_t n_bases, const uint64_t *d_roff, uint32_t nq, uint32_t n, uint8_t *d_dst,
+                       hipStream_t s);
+int turn_pick_launch(sina_hip_ctx *c, const uint32_t *d_ids, const float *d_scores, const uint32_t *d_n, uint32_t bq, uint32_t n, uint32_t max,
+                     hipStream_t s);
 }  // namespace sina_hip
 
 namespace sina_hip {

@@ -451,6 +451,18 @@ int sina_host_store_copy_stats(const char *key, uint64_t *pairs, double *kernel_
         reference_store::get(key)->copy_stats(pairs, kernel_ms, launches, trays, fallback_trays);
     });
 }
+// famfinder's device-turn on this store: queries the orient and pick kernels took and those of them they turned, the
+// kernels' time and launches (sina_hip_turn_stats) on the store's contexts; trays whose first round's rows came with
+// the orientation, trays of which only the orientation was taken, and trays of batches that fell back to the host's
+// searches -- between runs
+int sina_host_store_turn_stats(const char *key, uint64_t *queries, uint64_t *turned, double *kernel_ms, uint64_t *launches,
+                               uint64_t *rows_trays, uint64_t *orient_trays, uint64_t *fallback_trays) {
+    return guarded([&] {
+        if (!queries || !turned || !kernel_ms || !launches || !rows_trays || !orient_trays || !fallback_trays)
+            throw std::logic_error("store_turn_stats: null argument");
+        reference_store::get(key)->turn_stats(queries, turned, kernel_ms, launches, rows_trays, orient_trays, fallback_trays);
+    });
+}
 // show_dist_report alone (no device), for tests: nq (orig, aligned) pairs as packed words of the store's width, their
 // relatives as reference ids of the store; rows: null -- the host walk -- or [nq][20] counters to take instead
 // (sina_hip_show_dist's rows).  out [nq][3]: sps, idty, cpm; flags [nq]: bit 0 has_sps, bit 1 has_closest; closest [nq];

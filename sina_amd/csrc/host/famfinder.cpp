@@ -29,6 +29,7 @@ struct ff_options {
     bool long_queries;  // search queries of up to SINA_HIP_MAX_LONG_QUERY_LEN bases (default off: SINA_HIP_MAX_QUERY_LEN)
     bool device_msc;    // fs-msc-max < 1: the candidates' identities from the device's match counts (default off: the host walk)
     bool device_cascade;  // the filter cascade on the device, behind the search (default off: match_pass below)
+    bool device_turn;     // --turn: the device makes, searches and chooses the orientations (default off: best_orientations below)
 };
 ff_options ff_defaults() {  // src/famfinder.cpp:144-203
     ff_options o;
@@ -50,6 +51,7 @@ ff_options ff_defaults() {  // src/famfinder.cpp:144-203
     o.long_queries = false;
     o.device_msc = false;
     o.device_cascade = false;
+    o.device_turn = false;
     o.posvar_autofilter_thres = 0.8f;  // src/famfinder.cpp:205-208
     return o;
 }
@@ -124,6 +126,7 @@ void famfinder::set_option(const std::string &name, const std::string &value) {
     else if (name == "long-queries") o.long_queries = to_bool(value);
     else if (name == "device-msc") o.device_msc = to_bool(value);
     else if (name == "device-cascade") o.device_cascade = to_bool(value);
+    else if (name == "device-turn") o.device_turn = to_bool(value);
     else throw std::logic_error("famfinder: unknown option " + name);
 }
 
@@ -147,6 +150,7 @@ public:
     int turn_check(const cseq &query, bool all);
     std::vector<int> best_orientations(const std::vector<const cseq *> &queries, bool all);
     void orient_batch(std::vector<tray *> &batch);
+    bool orient_on_device(std::vector<tray *> &batch, unsigned max, std::vector<search::result_vector> *found, std::vector<uint32_t> *nk);
     void select_astats(tray &t);
     void run(std::vector<tray *> &batch);
 };
@@ -219,6 +223,32 @@ void famfinder::impl::orient_batch(std::vector<tray *> &batch) {
         c.set_attr(fn::turn, orientation_names[o[i]]);
         if (o[i]) c = oriented(c, o[i]);
     }
+}
+
+// device-turn: the batch's inputs go to the device as they are, once; it makes the orientations,
+// searches them and chooses as turn_check does (sina_hip_kmer_topk_turn).  The inputs are then turned in place and
+// fn::turn is set, as orient_batch does.  found (or null): the `max` best of every input AS TURNED -- a first round's
+// rows -- with their k-mer counts in nk.  false: the call failed or was refused, nothing was done.
+bool famfinder::impl::orient_on_device(std::vector<tray *> &batch, unsigned max, std::vector<search::result_vector> *found,
+                                       std::vector<uint32_t> *nk) {
+    std::vector<const cseq *> qs;
+    for (tray *t : batch) qs.push_back(t->input_sequence);
+    kmer_search::turn_request turn{ff_opts.turn_which == TURN_ALL, {}, false};
+    std::vector<search::result_vector> top1;
+    {
+        scoped_phase ph_find("ff.find_batch");
+        index->find_batch(qs, found ? *found : top1, max, found ? nk : nullptr, nullptr, nullptr, &turn);
+    }
+    if (!turn.done) {
+        if (found) found->clear();
+        return false;
+    }
+    for (size_t i = 0; i < batch.size(); i++) {
+        cseq &c = *batch[i]->input_sequence;
+        c.set_attr(fn::turn, orientation_names[turn.o[i]]);
+        if (turn.o[i]) c = oriented(c, turn.o[i]);
+    }
+    return true;
 }
 
 int autofilter_vote(const std::vector<std::string> &filter_names, const std::vector<std::string> &field_texts,
@@ -387,7 +417,35 @@ void famfinder::impl::run(std::vector<tray *> &batch) {
             searchable.push_back(t);
         }
     }
-    orient_batch(searchable);
+    // device-cascade: the cascade runs behind the search and a query's family comes back -- unless the
+    // rule allows a family beyond the device's row, or the identity limit meets a store too wide for the match count
+    // device-msc: every candidate's match count comes with the ids
+    const bool device_cascade = o.device_cascade && o.engine == ENGINE_SINA_KMER &&
+                                sina_hip::family_plan(o.fs_min, o.fs_max, o.fs_req_full, o.fs_cover_gene, 0).ok &&
+                                !(o.fs_msc_max < 1 && arb->match_counts_too_wide());
+    const bool device_msc = o.device_msc && o.fs_msc_max < 1 && !device_cascade;
+    size_t max_results = (size_t)o.fs_max + 1;
+    const unsigned isize = index->size();
+    // device-turn: where the first round is the plain search its rows come with the orientation; where it rides with
+    // match counts or the cascade only the orientation is taken (max = 1) and the round runs as ever on the turned input
+    std::vector<search::result_vector> turn_found;
+    std::vector<uint32_t> turn_nk;
+    bool first_round_found = false;
+    {
+        scoped_phase ph_orient("ff.orient");
+        if (o.device_turn && o.turn_which != TURN_NONE && o.engine == ENGINE_SINA_KMER && !searchable.empty()) {
+            const bool rows = !device_msc && !device_cascade;
+            if (orient_on_device(searchable, rows ? (unsigned)std::min<size_t>(max_results, isize) : 1u, rows ? &turn_found : nullptr, &turn_nk)) {
+                first_round_found = rows;
+                arb->count_turn(rows ? searchable.size() : 0, rows ? 0 : searchable.size(), 0);
+            } else {
+                arb->count_turn(0, 0, searchable.size());
+                orient_batch(searchable);
+            }
+        } else {
+            orient_batch(searchable);
+        }
+    }
     for (tray *t : searchable) {
         t->alignment_reference = object_cache<search::result_vector>::take();
         // (what the scores below are: raw k-mer counts of this engine -- the aligner's containment pre-filter asks)
@@ -395,27 +453,23 @@ void famfinder::impl::run(std::vector<tray *> &batch) {
         t->query_kmer_count = -1;
         todo.push_back(t);
     }
-    size_t max_results = (size_t)o.fs_max + 1;
-    const unsigned isize = index->size();
     while (!todo.empty()) {
         std::vector<const cseq *> qs;
         for (tray *t : todo) qs.push_back(t->input_sequence);
         std::vector<search::result_vector> found(todo.size());
         for (size_t i = 0; i < todo.size(); i++) found[i].swap(*todo[i]->alignment_reference);  // (their heap blocks, recycled)
         std::vector<uint32_t> nk;
-        // device-msc: every candidate's match count comes with the ids (an empty row: that query keeps the walk)
-        // device-cascade: the cascade runs behind the search and a query's family comes back -- unless the
-        // rule allows a family beyond the device's row, or the identity limit meets a store too wide for the match count;
-        // then, and for a query the device cannot take, match_pass below
+        // device-msc: an empty row: that query keeps the walk; device-cascade: for a query the device cannot take,
+        // match_pass below
         kmer_search::family_request family{
             sina_hip_family_rule{o.fs_min, o.fs_max, o.fs_req_full, o.fs_full_len, o.fs_min_len, o.fs_cover_gene, o.fs_msc, o.fs_msc_max},
             o.fs_leave_query_out, {}};
-        const bool device_cascade = o.device_cascade && o.engine == ENGINE_SINA_KMER &&
-                                    sina_hip::family_plan(o.fs_min, o.fs_max, o.fs_req_full, o.fs_cover_gene, 0).ok &&
-                                    !(o.fs_msc_max < 1 && arb->match_counts_too_wide());
-        const bool device_msc = o.device_msc && o.fs_msc_max < 1 && !device_cascade;
         std::vector<std::vector<uint16_t>> match_rows;
-        {
+        if (first_round_found) {  // (device-turn searched the turned inputs with this round's max already)
+            first_round_found = false;
+            found.swap(turn_found);
+            nk.swap(turn_nk);
+        } else {
             scoped_phase ph_find("ff.find_batch");
             index->find_batch(qs, found, (unsigned)std::min<size_t>(max_results, isize),
                               o.engine == ENGINE_SINA_KMER ? &nk : nullptr, device_msc ? &match_rows : nullptr,

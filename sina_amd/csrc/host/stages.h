@@ -392,6 +392,17 @@ public:
         n_copy_fallback.fetch_add(fallback_trays, std::memory_order_relaxed);
     }
     void copy_stats(uint64_t *pairs, double *kernel_ms, uint64_t *launches, uint64_t *trays, uint64_t *fallback_trays);
+    // famfinder's device-turn (orient_on_device): trays whose first round's rows came with their orientation, trays of
+    // which only the orientation was taken (device-msc or device-cascade then run the round), trays of batches whose call
+    // failed or was refused and kept the host's best_orientations, since the store was opened; and the orient and pick
+    // kernels' time and volume on the store's contexts -- sina_hip_turn_stats
+    void count_turn(uint64_t rows_trays, uint64_t orient_trays, uint64_t fallback_trays) {
+        n_turn_rows.fetch_add(rows_trays, std::memory_order_relaxed);
+        n_turn_orient.fetch_add(orient_trays, std::memory_order_relaxed);
+        n_turn_fallback.fetch_add(fallback_trays, std::memory_order_relaxed);
+    }
+    void turn_stats(uint64_t *queries, uint64_t *turned, double *kernel_ms, uint64_t *launches, uint64_t *rows_trays, uint64_t *orient_trays,
+                    uint64_t *fallback_trays);
     // whether the index in HBM is the one of this k / nofast (ensure_index, adopt_index)
     bool index_is(unsigned k, bool nofast) {
         std::lock_guard<std::mutex> lk(gpu_mu);
@@ -432,6 +443,7 @@ private:
     std::atomic<uint64_t> n_ranked{0}, n_rank_host{0};
     std::atomic<uint64_t> n_bp_inplace{0}, n_idty_inplace{0}, n_search_inplace{0}, n_show_dist{0};
     std::atomic<uint64_t> n_copy_trays{0}, n_copy_fallback{0};
+    std::atomic<uint64_t> n_turn_rows{0}, n_turn_orient{0}, n_turn_fallback{0};
     std::atomic<uint64_t> n_fin_device{0}, n_fin_host{0};
     pair_map helix;
     std::mutex helix_mu;
@@ -471,9 +483,19 @@ public:
         enum { enough = 1, empty_list = 2, on_device = 4 };
         std::vector<uint8_t> state;    // out, [queries]
     };
+    // (turn, optional: famfinder's device-turn -- the device tries the orientations of every query, two or four, and
+    // chooses as famfinder::turn_check does (sina_hip_kmer_topk_turn); turn->o[i] is query i's orientation, results[i]
+    // and kmer_counts[i] are those of the query IN that orientation.  Without match_rows and family.  A call the device
+    // fails or refuses leaves done false and the results empty: nothing was searched)
+    struct turn_request {
+        bool all;                      // four orientations instead of two
+        std::vector<uint8_t> o;        // out, [queries]
+        bool done = false;             // out
+    };
     void find_batch(const std::vector<const cseq *> &queries, std::vector<result_vector> &results,
                     unsigned int max, std::vector<uint32_t> *kmer_counts = nullptr,
-                    std::vector<std::vector<uint16_t>> *match_rows = nullptr, family_request *family = nullptr);
+                    std::vector<std::vector<uint16_t>> *match_rows = nullptr, family_request *family = nullptr,
+                    turn_request *turn = nullptr);
     unsigned int size() const override;
     ~kmer_search() override;
 

@@ -8,6 +8,7 @@
 #include "id_order.h"
 #include "../kmer_plan.h"
 #include "../match_plan.h"
+#include "../turn_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -396,6 +397,13 @@ void reference_store::copy_stats(uint64_t *pairs, double *kernel_ms, uint64_t *l
     *trays = n_copy_trays.load(std::memory_order_relaxed);
     *fallback_trays = n_copy_fallback.load(std::memory_order_relaxed);
 }
+void reference_store::turn_stats(uint64_t *queries, uint64_t *turned, double *kernel_ms, uint64_t *launches, uint64_t *rows_trays,
+                                 uint64_t *orient_trays, uint64_t *fallback_trays) {
+    sum_kernel_use("sina_hip_turn_stats", sina_hip_turn_stats, kernel_ms, queries, turned, launches);
+    *rows_trays = n_turn_rows.load(std::memory_order_relaxed);
+    *orient_trays = n_turn_orient.load(std::memory_order_relaxed);
+    *fallback_trays = n_turn_fallback.load(std::memory_order_relaxed);
+}
 void reference_store::assemble_stats(uint64_t *trays_device, uint64_t *trays_host, uint64_t *queries, uint64_t *assembled,
                                      uint64_t *shifted_queries, uint64_t *shifted_runs) {
     *queries = *assembled = *shifted_queries = *shifted_runs = 0;
@@ -706,8 +714,11 @@ static void find_by_columns(kmer_search &ks, const std::vector<const cseq *> &qu
 // scratch block -- the distinct queries are taken in slices of as many as one launch range of the device's big
 // select holds (kmer_plan.h: the same function, the same budget, so a slice is one launch), and `results` is filled
 // slice by slice.
-static void search_slices(reference_store &st, sina_hip_ctx *ctx, const distinct_items &d, const uint8_t *dev_mask, const uint32_t *dev_ab,
-                          unsigned int max, std::vector<search::result_vector> &results, std::vector<std::vector<uint16_t>> *match_rows) {
+// turn (famfinder's device-turn; null: none): the device orients every distinct query first and the rows are those of
+// its chosen orientation, slot_turn[u] (sina_hip_kmer_topk_turn).  Returns false, without a throw, if such a call fails.
+static bool search_slices(reference_store &st, sina_hip_ctx *ctx, const distinct_items &d, const uint8_t *dev_mask, const uint32_t *dev_ab,
+                          unsigned int max, std::vector<search::result_vector> &results, std::vector<std::vector<uint16_t>> *match_rows,
+                          const kmer_search::turn_request *turn = nullptr, uint8_t *slot_turn = nullptr) {
     const size_t nu = d.n;
     const size_t slice = max > sina_hip::kKmerSelMax ? sina_hip::big_select_range((uint32_t)nu, max, sina_hip::kBigSelBudget) : nu;
     thread_local batch_scratch<uint32_t> ids_buf;
@@ -723,7 +734,12 @@ static void search_slices(reference_store &st, sina_hip_ctx *ctx, const distinct
             scoped_phase ph("ff.kmer_topk(C-ABI)");
             // (the _any entry: the class has no length limit of its own, as the reference's -- a query beyond the fast count
             // kernel's goes to the long one, per query; offsets are absolute, so a slice starts at d.off + u0)
-            if (match_rows)
+            if (turn) {
+                std::vector<float> top1(4 * (u1 - u0));
+                if (sina_hip_kmer_topk_turn(ctx, dev_mask, d.off.data() + u0, (uint32_t)(u1 - u0), max, turn->all ? 1 : 0, slot_turn + u0, top1.data(),
+                                            ids, sc, cnt.data()) != 0)
+                    return false;
+            } else if (match_rows)
                 hip_check(sina_hip_kmer_topk_match(ctx, dev_ab, d.off.data() + u0, (uint32_t)(u1 - u0), max, ids, sc, cnt.data(), mt), "kmer_topk_match");
             else
                 hip_check(sina_hip_kmer_topk_any(ctx, dev_mask, d.off.data() + u0, (uint32_t)(u1 - u0), max, ids, sc, cnt.data()), "kmer_topk");
@@ -737,6 +753,7 @@ static void search_slices(reference_store &st, sina_hip_ctx *ctx, const distinct
             if (match_rows) (*match_rows)[i].assign(mt + at, mt + at + cnt[u - u0]);
         });
     }
+    return true;
 }
 
 // famfinder's device-cascade: searches the distinct (words, self list) pairs of a batch with the cascade behind the
@@ -800,10 +817,15 @@ static void search_families(reference_store &st, sina_hip_ctx *ctx, const std::v
 // Clears the outputs, packs the queries, finds the distinct ones, searches those and scatters what they found.
 void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vector<result_vector> &results,
                              unsigned int max, std::vector<uint32_t> *kmer_counts, std::vector<std::vector<uint16_t>> *match_rows,
-                             family_request *family) {
+                             family_request *family, turn_request *turn) {
     reference_store &st = *pimpl->store;
     const size_t nq = queries.size();
     if (family) family->state.assign(nq, 0);
+    if (turn) {
+        if (match_rows || family) throw std::logic_error("find_batch: a turn request goes with neither match counts nor the cascade");
+        turn->o.assign(nq, 0);
+        turn->done = false;
+    }
     // (the callers' vectors are kept -- famfinder hands in recycled ones -- and only emptied)
     results.resize(nq);
     for (auto &r : results) r.clear();
@@ -871,7 +893,27 @@ void kmer_search::find_batch(const std::vector<const cseq *> &queries, std::vect
     thread_local batch_scratch<uint32_t> uab_buf;
     const uint8_t *const dev_mask = gather_distinct(d, parallel_for, qmask, qoff.data(), umask_buf);
     const uint32_t *const dev_ab = qab ? gather_distinct(d, parallel_for, qab, qoff.data(), uab_buf) : nullptr;
-    search_slices(st, dev.get(), d, dev_mask, dev_ab, max, results, match_rows);
+    if (!turn) {
+        search_slices(st, dev.get(), d, dev_mask, dev_ab, max, results, match_rows);
+        return;
+    }
+    std::vector<uint8_t> slot_turn(d.n, 0);
+    if (!search_slices(st, dev.get(), d, dev_mask, nullptr, max, results, nullptr, turn, slot_turn.data())) {
+        for (auto &r : results) r.clear();  // (a later slice's call failed: nothing of the batch counts)
+        return;
+    }
+    // the orientations, and the k-mer counts of the queries as turned (with the fast index they differ by orientation)
+    parallel_for(nq, [&](size_t i) {
+        const uint32_t o = slot_turn[d.slot_of[i]];
+        turn->o[i] = (uint8_t)o;
+        if (!o || !kmer_counts) return;
+        const uint8_t *m = qmask + qoff[i];
+        const size_t nb = (size_t)(qoff[i + 1] - qoff[i]);
+        std::vector<uint8_t> v(nb);
+        for (size_t x = 0; x < nb; x++) v[x] = sina_hip::turn_variant_byte(m, nb, o, x);
+        (*kmer_counts)[i] = count_query_kmers(v.data(), nb, pimpl->k, pimpl->nofast);
+    });
+    turn->done = true;
 }
 
 }  // namespace sina

@@ -5,6 +5,10 @@
 // one it is.  The copies that bring a call's queries into the order it runs in and its rows back are kmer_plan.h's, over
 // the inputs and columns the sink lists.  The kernels and their launchers are kmer.hip's, match.hip's, rank.hip's and
 // family.hip's, the index and the dense bitmaps kmer_index.hip's.
+// A call with a turn request (sina_hip_kmer_topk_turn) searches the n tried orientations of every query
+// as n virtual queries: the queries go up once, turn.hip's orient kernel writes the variants where a search's queries
+// lie, the ranges -- whole queries, turn_plan.h -- run through the same launchers, and where a range's select is final
+// turn.hip's pick kernel leaves the winners' rows, which is what the sink sees: a range of real queries.
 #include <cstring>
 #include <memory>
 
@@ -12,6 +16,7 @@
 #include "ctx.h"
 #include "match_plan.h"
 #include "family_plan.h"
+#include "turn_plan.h"
 #include "compare_dev.h"
 
 namespace sina_hip {
@@ -28,6 +33,7 @@ struct KmerRequest {
     uint32_t nq, max;
     const uint32_t *q_ab;
     KmerSink *sink;
+    uint32_t turn_n = 0;  // a turn request: the orientations tried per query (turn_plan.h: 2 or 4); 0: none
     uint32_t qlen(uint32_t q) const { return (uint32_t)(qoff[q + 1] - qoff[q]); }
 };
 
@@ -103,6 +109,28 @@ struct MatchSink : PlainSink {
             return 1;
         SH_CHECK(wait_stream(c, c->stream));
         memcpy(match.row<uint16_t>(q0), c->h_stage[5].p, row_bytes);
+        return 0;
+    }
+};
+// sina_hip_kmer_topk_turn: the chosen orientation's rows, and what the pick kernel left of the choice in pinned staging
+// (h_stage[6]: [5] words per query, the orientation and the four top-1 scores' bits): turn [nq] bytes, top1 [nq][4]
+struct TurnSink : PlainSink {
+    KmerColumn turn, top1;
+    TurnSink(uint8_t *out_turn, float *out_top1, uint32_t *out_ids, float *out_scores, uint32_t *out_n)
+        : PlainSink(out_ids, out_scores, out_n), turn{out_turn, 1}, top1{out_top1, 16} {}
+    std::vector<KmerColumn *> columns() override { return {&ids, &scores, &n, &turn, &top1}; }
+    void empty(uint32_t nq) override {
+        PlainSink::empty(nq);
+        memset(turn.base, 0, nq);
+        memset(top1.base, 0, (size_t)16 * nq);
+    }
+    int range(sina_hip_ctx *c, const KmerRequest &r, const KmerLaunch &l, uint32_t q0, uint32_t bq, const uint32_t *h_n) override {
+        if (PlainSink::range(c, r, l, q0, bq, h_n)) return 1;
+        const uint32_t *meta = static_cast<const uint32_t *>(c->h_stage[6].p);
+        for (uint32_t q = 0; q < bq; q++) {
+            *turn.row<uint8_t>(q0 + q) = (uint8_t)meta[(size_t)5 * q];
+            memcpy(top1.row<float>(q0 + q), meta + (size_t)5 * q + 1, 16);
+        }
         return 0;
     }
 };
@@ -218,16 +246,56 @@ int run_kernels(sina_hip_ctx *c, KmerLaunch &l, bool want_select) {
     return hl.done();
 }
 
+// The winners' rows in place of the select's, for as long as this lives: a sink reads a range's rows in c->k_out_ids,
+// k_out_scores and k_out_n, and of a call that orients its queries those are the pick kernel's
+struct PickedRows {
+    sina_hip_ctx *c;
+    explicit PickedRows(sina_hip_ctx *c_) : c(c_) { swap(); }
+    ~PickedRows() { swap(); }
+    PickedRows(const PickedRows &) = delete;
+    PickedRows &operator=(const PickedRows &) = delete;
+    void swap() {
+        std::swap(c->k_out_ids, c->t_ids);
+        std::swap(c->k_out_scores, c->t_scores);
+        std::swap(c->k_out_n, c->t_n);
+    }
+};
+
+// A range of a call that orients its queries, its select final (g, lv: the range and its launch, of virtual queries):
+// the pick, the stagings that precede the sink's step -- of the picked rows -- the kernel's record, and the sink's step
+// on a range of real queries
+int turn_range(sina_hip_ctx *c, const KmerRequest &r, const KmerLaunch &lv, const KmerRange &g) {
+    hipStream_t s = c->stream;
+    const uint32_t n = r.turn_n, q0 = g.q0 / n, bq = g.bq / n, max = r.max;
+    SH_CHECK(hipEventRecord(c->ev[6], s));
+    if (turn_pick_launch(c, c->k_out_ids.as<uint32_t>(), c->k_out_scores.as<float>(), c->k_out_n.as<uint32_t>(), bq, n, max, s)) return 1;
+    SH_CHECK(hipEventRecord(c->ev[7], s));
+    const PickedRows picked(c);
+    if ((r.sink->downloads_rows() && (download(c, 9, c->k_out_ids.p, (size_t)bq * max * 4, s) || download(c, 10, c->k_out_scores.p, (size_t)bq * max * 4, s))) ||
+        download(c, 11, c->k_out_n.p, (size_t)bq * 4, s) || download(c, 6, c->t_meta.p, (size_t)bq * 20, s))
+        return 1;
+    SH_CHECK(wait_stream(c, s));
+    float ms = 0;
+    SH_CHECK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
+    const uint32_t *meta = static_cast<const uint32_t *>(c->h_stage[6].p);
+    uint64_t turned = 0;
+    for (uint32_t q = 0; q < bq; q++) turned += meta[(size_t)5 * q] != 0;
+    c->use[kUseTurn].add(ms, bq, turned, 1);
+    const KmerLaunch l{c->t_src.as<uint8_t>(), c->t_qoff.as<uint64_t>() + q0, bq, max, lv.max_qlen, g.path, g.big};
+    return r.sink->range(c, r, l, q0, bq, static_cast<const uint32_t *>(c->h_stage[11].p));
+}
+
 // One launch range: kernels, the lengths (and what the sink wants of the rows) back through pinned staging,
 // statistics, the sink's step; *overflow = a candidate list of the range did not hold its query's candidates (the sink
 // saw nothing of it then: the caller repeats the range with rows)
 int run_range(sina_hip_ctx *c, const KmerRequest &r, const KmerRange &g, uint32_t max_qlen, bool *overflow) {
     hipStream_t s = c->stream;
     const uint32_t q0 = g.q0, bq = g.bq, max = r.max;
+    const uint32_t per_query = r.turn_n ? r.turn_n : 1u;  // (a turn request: the range is of virtual queries, its rows are staged behind the pick)
     KmerLaunch l{c->qmask.as<uint8_t>(), c->k_qoff.as<uint64_t>() + q0, bq, max, max_qlen, g.path, g.big};
     if (run_kernels(c, l, true)) return 1;
     // (the kernels have finished: run_kernels waits for the heavy stream)
-    if ((r.sink->downloads_rows() && (download(c, 9, c->k_out_ids.p, (size_t)bq * max * 4, s) || download(c, 10, c->k_out_scores.p, (size_t)bq * max * 4, s))) ||
+    if ((r.sink->downloads_rows() && !r.turn_n && (download(c, 9, c->k_out_ids.p, (size_t)bq * max * 4, s) || download(c, 10, c->k_out_scores.p, (size_t)bq * max * 4, s))) ||
         download(c, 11, c->k_out_n.p, (size_t)bq * 4, s) || download(c, 0, c->k_tmp2.p, 8, s))
         return 1;
     SH_CHECK(wait_stream(c, s));
@@ -251,15 +319,60 @@ int run_range(sina_hip_ctx *c, const KmerRequest &r, const KmerRange &g, uint32_
         }
     }
     if (*overflow) return 0;
-    if (g.path == kKmerLong) c->path_queries[kPathLong] += bq;
-    if (g.big) c->path_queries[kPathBigSelect] += bq;
+    if (g.path == kKmerLong) c->path_queries[kPathLong] += bq / per_query;
+    if (g.big) c->path_queries[kPathBigSelect] += bq / per_query;
+    if (r.turn_n) return turn_range(c, r, l, g);
     return r.sink->range(c, r, l, q0, bq, h_n);  // the range's select is final
+}
+
+// A call that orients its queries, behind its checks as kmer_topk_run's: the queries up once, as they are; their
+// variants made where a search's queries lie; the ranges of virtual queries, whole queries each (turn_plan.h)
+int kmer_turn_run(sina_hip_ctx *c, const KmerRequest &r, uint32_t n_fast) {
+    const uint32_t nq = r.nq, n = r.turn_n, n_refs = c->st->n_refs;
+    const uint64_t *qoff = r.qoff;
+    uint32_t max_qlen = 1;
+    for (uint32_t q = 0; q < n_fast; q++) max_qlen = std::max(max_qlen, r.qlen(q));
+    hipStream_t s = c->stream;
+    const uint64_t nqm = qoff[nq] - qoff[0];
+    std::vector<uint64_t> rel(nq + 1);
+    for (uint32_t q = 0; q <= nq; q++) rel[q] = qoff[q] - qoff[0];
+    const std::vector<uint64_t> voff = turn_offsets(qoff, nq, n);
+    if (c->t_src.reserve(turn_source_bytes(nqm)) || c->t_qoff.reserve(8 * rel.size()) || c->qmask.reserve(turn_variant_bytes(nqm, n)) ||
+        c->k_qoff.reserve(8 * voff.size()))
+        return 1;
+    if (upload(c, 7, c->t_src.p, r.qmask + qoff[0], nqm, s) || upload(c, 4, c->t_qoff.p, rel.data(), 8 * rel.size(), s) ||
+        upload(c, 8, c->k_qoff.p, voff.data(), 8 * voff.size(), s))
+        return 1;
+    if (r.sink->upload(c, nq, s)) return 1;
+    // (a thin kernel beside whatever is resident: on the context's own stream)
+    SH_CHECK(hipEventRecord(c->ev[6], s));
+    if (turn_orient_launch(c, c->t_src.as<uint32_t>(), nqm, c->t_qoff.as<uint64_t>(), nq, n, c->qmask.as<uint8_t>(), s)) return 1;
+    SH_CHECK(hipEventRecord(c->ev[7], s));
+    SH_CHECK(wait_stream(c, s));
+    float ms = 0;
+    SH_CHECK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
+    c->use[kUseTurn].add(ms, 0, 0, 1);
+    // (SINA_HIP_TEST=turn_range=N: at most N queries per launch range, so that a small call takes several; the others
+    // as kmer_topk_run reads them)
+    uint64_t budget = kBigSelBudget;
+    if (const std::string e_ = test_knob("big_sel_bytes"); !e_.empty()) budget = std::min<uint64_t>(kBigSelBudget, strtoull(e_.c_str(), nullptr, 10));
+    const bool force_rows = atoi(test_knob("kmer_rows").c_str()) != 0;
+    const uint32_t range_queries = (uint32_t)std::min<uint64_t>(strtoull(test_knob("turn_range").c_str(), nullptr, 10), kTurnMaxQueries);
+    for (const KmerRange &g : turn_ranges(nq, n_fast, n, r.max, n_refs, budget, force_rows, range_queries)) {
+        bool overflow = false;
+        if (run_range(c, r, g, max_qlen, &overflow)) return 1;
+        if (!overflow) continue;  // (kmer_topk_run: the score rows and the full select, a query's variants kept together)
+        for (const KmerRange &h : turn_overflow_ranges(g, n, n_refs))
+            if (run_range(c, r, h, max_qlen, &overflow)) return 1;
+    }
+    return 0;
 }
 
 // A call behind its checks (c->mu held, 1 <= max <= n_refs): the queries' masks and offsets, the packed bases and
 // whatever else the sink needs to the device, then range by range as kmer_plan.h cuts them -- queries 0 .. n_fast - 1
 // are at most kMaxQueryLen bases long, queries n_fast .. nq - 1 longer
 int kmer_topk_run(sina_hip_ctx *c, const KmerRequest &r, uint32_t n_fast) {
+    if (r.turn_n) return kmer_turn_run(c, r, n_fast);
     const uint32_t nq = r.nq, n_refs = c->st->n_refs;
     const uint64_t *qoff = r.qoff;
     uint32_t max_qlen = 1;
@@ -366,6 +479,8 @@ int kmer_topk_checked(sina_hip_ctx *c, const KmerRequest &in, bool any) {
     KmerRequest r = in;
     const uint32_t nq = r.nq;
     if (r.sink->check(c, r)) return 1;
+    if (r.turn_n && r.sink->needs_bases()) SH_FAIL("kmer_topk: a call that orients its queries takes no sink that reads their packed bases");
+    if (r.turn_n && nq > kTurnMaxQueries) SH_FAIL_LIMIT("kmer_topk_turn: more than 2^30 - 1 queries");
     if (nq == 0) return 0;
     SH_CHECK(hipSetDevice(c->device));
     if (r.max > c->st->n_refs) r.max = c->st->n_refs;
@@ -454,6 +569,16 @@ int sina_hip_kmer_topk_any(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t
     if (!out_ids || !out_scores || !out_n) SH_FAIL("kmer_topk: null argument");
     PlainSink plain(out_ids, out_scores, out_n);
     return kmer_topk_checked(c, KmerRequest{qmask, qoff, nq, max, nullptr, &plain}, true);
+}
+int sina_hip_kmer_topk_turn(sina_hip_ctx *c, const uint8_t *qmask, const uint64_t *qoff, uint32_t nq, uint32_t max, int all,
+                            uint8_t *out_turn, float *out_top1, uint32_t *out_ids, float *out_scores, uint32_t *out_n) {
+    if (!out_turn || !out_top1 || !out_ids || !out_scores || !out_n) SH_FAIL("kmer_topk_turn: null argument");
+    if (max == 0) SH_FAIL("kmer_topk_turn: max must be 1 or more");
+    if (test_knob("turn_fail") == "1") SH_FAIL("kmer_topk_turn: refused by the test knob turn_fail");
+    TurnSink turn(out_turn, out_top1, out_ids, out_scores, out_n);
+    KmerRequest r{qmask, qoff, nq, max, nullptr, &turn};
+    r.turn_n = turn_variants(all != 0);
+    return kmer_topk_checked(c, r, true);
 }
 int sina_hip_kmer_topk_match(sina_hip_ctx *c, const uint32_t *q_ab, const uint64_t *q_off, uint32_t nq, uint32_t max,
                              uint32_t *out_ids, float *out_scores, uint32_t *out_n, uint16_t *out_match) {

@@ -103,6 +103,7 @@ def load_host():
     H.sina_host_store_search_inplace_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_store_show_dist_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_store_copy_stats.argtypes = [C.c_char_p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p]
+    H.sina_host_store_turn_stats.argtypes = [C.c_char_p, capi.u64p, capi.u64p, C.POINTER(C.c_double), capi.u64p, capi.u64p, capi.u64p, capi.u64p]
     H.sina_host_find_bases_packed.argtypes = [capi.u32p, C.c_uint32, capi.u32p, C.c_uint32, capi.u32p, C.c_char_p, C.c_char_p, C.c_uint32]
     H.sina_host_show_dist_reports.argtypes = [C.c_char_p, capi.u32p, capi.u64p, capi.u32p, capi.u64p, C.c_uint32, capi.u32p, capi.u64p,
                                               capi.u32p, capi.f32p, capi.u32p, capi.u32p, C.c_char_p, C.c_uint32]
@@ -336,6 +337,17 @@ class Store:
         like show_dist_stats()."""
         d = self._counters(self.H.sina_host_store_copy_stats, capi.u64_fields("pairs") + capi.KERNEL_MS +
                            capi.u64_fields("launches", "trays", "fallback_trays"))
+        d["kernel_ms"] = d.pop("kernel_ms")  # (the dict ends with it)
+        return d
+
+    def turn_stats(self):
+        """famfinder's device-turn on this store so far: dict(queries, turned, launches, rows_trays, orient_trays,
+        fallback_trays, kernel_ms) -- queries the orient and pick kernels took, those they turned, the kernels' launches
+        and time on the store's contexts; trays whose first round's rows came with the orientation, trays of which only
+        the orientation was taken (device-msc, device-cascade), trays of batches that fell back to the host's searches
+        -- between runs, like copy_stats()."""
+        d = self._counters(self.H.sina_host_store_turn_stats, capi.u64_fields("queries", "turned") + capi.KERNEL_MS +
+                           capi.u64_fields("launches", "rows_trays", "orient_trays", "fallback_trays"))
         d["kernel_ms"] = d.pop("kernel_ms")  # (the dict ends with it)
         return d
 

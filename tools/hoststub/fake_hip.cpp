@@ -180,6 +180,17 @@ int sina_hip_find_bases_stats(sina_hip_ctx *, double *ms, uint64_t *pairs, uint6
     *pairs = *bases = *launches = 0;
     return 0;
 }
+// (famfinder's device-turn then keeps its host route)
+int sina_hip_kmer_topk_turn(sina_hip_ctx *, const uint8_t *, const uint64_t *, uint32_t, uint32_t, int, uint8_t *, float *, uint32_t *,
+                            float *, uint32_t *) {
+    g_err = "stub";
+    return 1;
+}
+int sina_hip_turn_stats(sina_hip_ctx *, double *ms, uint64_t *queries, uint64_t *turned, uint64_t *launches) {
+    *ms = 0;
+    *queries = *turned = *launches = 0;
+    return 0;
+}
 int sina_hip_identity_inplace_stats(sina_hip_ctx *, double *ms, uint64_t *seqs, uint64_t *pairs, uint64_t *launches) {
     *ms = 0;
     *seqs = *pairs = *launches = 0;
